@@ -11,7 +11,10 @@ by re-executing itself under torch.distributed.run.  Every rank runs the same st
 scaling, no data-path collective in the forward path; `--mode train` adds the bucketed RCCL gradient exchange); the
 timed region is bracketed by barrier + synchronize and the MAX over ranks is reported.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the last timed step
+returned (.npy, float32) for output-for-output comparisons of two builds.  Everything below is measured only with `--full`.
+
+Extra objects on the JSON line (`--full`):
   roofline     -- the kernel family that takes the most time in the step (picked from an all-families profile of the last
                   warm-up step, so it always names what the profile ranks first): algorithmic FLOPs (or bytes) of its
                   launches / their summed duration, both taken from HIP events the library records around EVERY launch of
@@ -21,6 +24,7 @@ Extra objects on the JSON line:
                   family armed): launches/step, us/launch, TFLOP/s, GB/s, which roof bounds it and the fraction reached.
   cpu_baseline -- the CPU oracle (oracle/, kind "port") timed on this box's host cores: B = 48 forward at 32 / 64 / 128 threads
                   (best point = value); `train.cpu_baseline` = the oracle's optimisation step (autograd + clip + Adam) there.
+  one_batch_at_a_time, x3, train, pgrm_mfma_util -- see main().
 """
 import argparse
 import json
@@ -68,10 +72,15 @@ def parse():
                     help="train mode: run the frozen PSN inside the step instead of prefetching the next batch's PSN image during it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="fwd mode: skip the `train` object (configs[2] step timed after the forward region)")
-    ap.add_argument("--no-x3", action="store_true", help="default line: skip the `x3` object (the same forward / training legs in mode 2, f32 via bf16x3)")
+    ap.add_argument("--no-x3", action="store_true", help="--full: skip the `x3` object (the same forward / training legs in mode 2, f32 via bf16x3)")
     ap.add_argument("--train-steps", type=int, default=10, help="timed steps of the `train` object")
     ap.add_argument("--no-kernel-profile", action="store_true", help="skip the per-kernel event timing (roofline = null)")
     ap.add_argument("--cpu-sample", type=int, default=None, help="images in the CPU-baseline sample (default: the per-GPU batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel roofline / kernels, one batch at a time, the x3 and train "
+                         "objects, the CPU baseline, PGRM MFMA-util (the --no-* options above switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, rank 0)")
     return ap.parse_args()
 
 
@@ -281,10 +290,11 @@ UNFORKED_FAMILIES = ("k_conv_igemm<128,128>", "k_conv_splitk_reduce", "k_bigru",
 UNFORKED_FAMILIES_TRAIN = ("k_bigru", "k_mha32")
 
 
-def timed_leg(step, steps, warmup, profiling, torch, dist, _abi, post=3, arm_timed=True, unforked=UNFORKED_FAMILIES):
+def timed_leg(step, steps, warmup, profiling, torch, dist, _abi, post=3, arm_timed=True, unforked=UNFORKED_FAMILIES, on_last=None):
     """W untimed warm-up steps, then EXACTLY `steps` steps bracketed by barrier + synchronize on both sides; MAX over ranks.
     Returns (seconds, rows of the dominant family event-timed inside the timed steps, per-family rows of `post` extra steps).
-    Family ranking (last warm-up steps) and the per-family table (`post` steps after the region): branches on one stream."""
+    Family ranking (last warm-up steps) and the per-family table (`post` steps after the region): branches on one stream.
+    on_last(r): called with what the last timed step returned, after the region and before any further step."""
     dominant = None
     n_pick = min(2, warmup)                        # all families armed on the last warm-up steps: who is the dominant kernel?
     rank_in_warmup = profiling and arm_timed        # legs that do not arm the timed region rank the families in the post steps
@@ -293,7 +303,7 @@ def timed_leg(step, steps, warmup, profiling, torch, dist, _abi, post=3, arm_tim
             torch.cuda.synchronize()
             set_branch_streams(False)
             _abi.profile_begin(None)
-        step()
+        last = step()                               # (held like in the timed loop: the allocator settles on the same pools)
         if rank_in_warmup and i == warmup - 1:
             torch.cuda.synchronize()
             rows = _abi.profile_end()
@@ -301,7 +311,7 @@ def timed_leg(step, steps, warmup, profiling, torch, dist, _abi, post=3, arm_tim
             if rows:
                 dominant = max(rows, key=lambda r: r["total_ms"])["kernel"]
     if rank_in_warmup:
-        step()                                      # one more warm-up in the product configuration (side streams, allocator pools)
+        last = step()                               # one more warm-up in the product configuration (side streams, allocator pools)
     arm_timed = arm_timed and dominant in unforked      # else: measured in the joined-stream steps after the region
     torch.cuda.synchronize()
     if dist.is_initialized():
@@ -311,13 +321,15 @@ def timed_leg(step, steps, warmup, profiling, torch, dist, _abi, post=3, arm_tim
         _abi.profile_begin([dominant])     # only this family is bracketed by events inside the timed region
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if dist.is_initialized():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     live = _abi.profile_end() if (profiling and dominant and arm_timed) else []
+    if on_last is not None:
+        on_last(last)
     if dist.is_initialized():
         tt = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -401,6 +413,7 @@ def build_train_step(args, workload, world, force_dist, dist, torch, drop):
 
         def step():   # noqa: F811  (same batch every step, like the eager path of this bench)
             return run(inp["images_lr"], inp["images_hr"], inp.get("label_vecs"), inp["text_priors"])
+    step.params = [p for m in models + distill for p in m.parameters()]      # what the step updates (--dump-outputs)
     freeze_heap()
     return step, trainer, inp["images_lr"].shape[0]
 
@@ -413,6 +426,28 @@ def freeze_heap():
     import gc
     gc.collect()
     gc.freeze()
+
+
+DUMP_MAX = 1 << 22      # elements per --dump-outputs array: 16 MB of float32, a dump holds at most two
+
+
+def dump_array(t):
+    """host float32 copy of a device tensor for --dump-outputs; above DUMP_MAX elements a fixed, seeded sample of its flattened
+    elements (the same indices in every run of the same arguments)"""
+    import numpy as np
+    import torch
+    t = t.detach()
+    if t.numel() > DUMP_MAX:
+        idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), DUMP_MAX))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def write_outputs(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def train_object(args, workload, world, rank, force_dist, dist, torch, _abi):
@@ -537,12 +572,23 @@ def main():
                 return pipe.submit(inp["images_lr"], inp.get("label_vecs"), **kw)
             return sr.refine(models, psn, inp["images_lr"], inp.get("label_vecs"), **kw)
 
-    profiling = rank == 0 and not args.graph and not args.no_kernel_profile
+    profiling = args.full and rank == 0 and not args.graph and not args.no_kernel_profile
     pipelined = args.mode == "fwd" and max(1, args.pipeline) > 1
+    outputs = {}
+
+    def keep_outputs(r):        # host copies of what the last timed step returned: the SR images, or the loss and the updated weights
+        if args.mode == "train":
+            outputs["loss"] = dump_array(r.reshape(1))
+            outputs["params_sample"] = dump_array(torch.cat([p.detach().reshape(-1) for p in step.params]))
+        else:
+            outputs["sr_images"] = dump_array(r)
     elapsed, live, kernels = timed_leg(step, args.steps, args.warmup, profiling, torch, dist, _abi,
-                                       unforked=() if pipelined else (UNFORKED_FAMILIES if args.mode == "fwd" else UNFORKED_FAMILIES_TRAIN))
+                                       unforked=() if pipelined else (UNFORKED_FAMILIES if args.mode == "fwd" else UNFORKED_FAMILIES_TRAIN),
+                                       on_last=keep_outputs if (args.dump_outputs and rank == 0) else None)
+    if outputs:
+        write_outputs(args.dump_outputs, outputs)
     latency_ms = None
-    if pipelined:       # the same step one batch at a time (what `ms_per_step` meant before round 4's pipeline): reported next to the throughput
+    if pipelined and args.full:       # the same step one batch at a time (what `ms_per_step` meant before round 4's pipeline): reported next to the throughput
         PIPE_ON[0] = False
         n_lat = max(4, args.steps // 2)
         for _ in range(2):
@@ -555,7 +601,7 @@ def main():
         latency_ms = (time.perf_counter() - t0) / n_lat * 1e3
         PIPE_ON[0] = True
     # the same forward in mode 2 (f32 via bf16x3), same process, same models and inputs: the `x3` object of the default line
-    want_x3 = (args.mode == "fwd" and args.workload == "cfg1" and args.prior == "synthetic" and not args.graph and args.dtype == "f32" and not args.no_x3)
+    want_x3 = (args.full and args.mode == "fwd" and args.workload == "cfg1" and args.prior == "synthetic" and not args.graph and args.dtype == "f32" and not args.no_x3)
     x3 = None
     if want_x3:
         _abi.check(_abi.lib.dpmn_set_compute_dtype(2))
@@ -604,6 +650,7 @@ def main():
                                ("dp%d (coalesced gradient groups, RCCL %s overlapped with backward)" % (
                                    world, "reduce-scatter + sharded clip/Adam + all-gather" if trainer.zero1 else "all-reduce"))},
         }
+    if rank == 0 and args.full:
         roof = roofline_of(live, args.steps, B, (args.mode if args.mode == "fwd" else "train") + ("_x3" if args.dtype == "x3" else "") if args.dtype in ("f32", "x3") else args.mode)
         if latency_ms is not None:
             line["one_batch_at_a_time"] = {"ms_per_step": round(latency_ms, 3), "images_per_s": round(world * B / latency_ms * 1e3, 2),
@@ -615,7 +662,7 @@ def main():
     # the configs[2] training step, timed after the forward region in the same process (every rank takes part: the step holds
     # the RCCL gradient exchange when N > 1); headline `value` stays the forward
     train = None
-    if args.mode == "fwd" and args.workload == "cfg1" and args.prior == "synthetic" and not args.no_train and not args.graph and args.dtype == "f32":
+    if args.full and args.mode == "fwd" and args.workload == "cfg1" and args.prior == "synthetic" and not args.no_train and not args.graph and args.dtype == "f32":
         del step
         train = train_object(args, workload, world, rank, force_dist, dist, torch, _abi)
         if want_x3:
@@ -625,12 +672,13 @@ def main():
             if rank == 0 and x3 is not None:
                 t3["kernels"] = x3_rows(t3.get("kernels", []))
                 x3["train"] = t3
-    if rank == 0:
+    if rank == 0 and args.full:
         line["train"] = train
         line["x3"] = x3
         line["cpu_baseline"] = None if (args.no_cpu_baseline or world > 1 or args.mode != "fwd") else cpu_baseline(args.workload, args.cpu_sample or B, train=train is not None) if args.prior == "synthetic" else None   # N=1 only
         if train is not None and line["cpu_baseline"] and "train_step" in line["cpu_baseline"]:
             train["cpu_baseline"] = line["cpu_baseline"].pop("train_step")
+    if rank == 0:
         print(json.dumps(line))
     if dist.is_initialized():
         dist.barrier()

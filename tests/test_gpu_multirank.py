@@ -41,7 +41,7 @@ def _bench(extra, timeout=600):
 
 
 def test_bench_forward_two_ranks_one_line():
-    d = _bench(["--no-train"])
+    d = _bench(["--full", "--no-train"])
     assert d["n_gpus"] == 2 and d["config"]["ranks"] == 2 and d["config"]["per_gpu_batch"] == 4 and d["config"]["global_batch"] == 8
     assert d["config"]["backend"].startswith("gloo") and d["scaling"] == "weak" and d["steps"] == 2 and d["warmup"] == 1
     assert abs(d["value"] - 2 * 4 * 2 / (d["ms_per_step"] * 2 * 1e-3)) < 0.02 * d["value"]      # whole-job images/s over both ranks
@@ -51,7 +51,7 @@ def test_bench_forward_two_ranks_one_line():
 def test_bench_default_line_two_ranks_carries_train_and_x3_objects():
     """The driver's N > 1 command has no flags beyond --gpus / --steps / --warmup: every rank runs the forward leg, the two training legs
     (gradient exchange over the process group) and the same legs in mode 2; rank 0 prints one line with the `train` and `x3` objects."""
-    d = _bench(["--train-steps", "2"], timeout=900)
+    d = _bench(["--full", "--train-steps", "2"], timeout=900)
     assert d["n_gpus"] == 2 and d["dtype"] == "f32" and d["value"] > 0
     assert d["train"]["ms_per_step"] > 0 and d["train"]["without_dropout"]["ms_per_step"] > 0
     assert len(d["train"]["per_step_ms"]) == 2

@@ -10,7 +10,7 @@ rm -rf $OUT; mkdir -p $OUT
 # the whole GPU suite first (both compute modes): its error record travels as <tag>_parity_errors.json
 (cd $R && timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -3 > $OUT/gpu_suite.txt)
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-kernel-profile --no-train"
+B="python $R/bench.py --full --no-cpu-baseline --no-kernel-profile --no-train"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/fwd -- $B --steps 10 --warmup 3 > $OUT/fwd.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/train -- $B --mode train --steps 5 --warmup 2 > $OUT/train.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $B --steps 3 --warmup 2 > $OUT/pmc_fetch.log 2>&1
@@ -37,21 +37,21 @@ if [ "${1:-}" != "quick" ]; then
   timeout 600 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_mfma_train_x3 -- $TX > $OUT/pmc_mfma_train_x3.log 2>&1
 fi
 cd $R
-timeout 900 python bench.py 2>$OUT/bench_default.err | tail -1 > $OUT/bench_default.json
-timeout 600 python bench.py --mode train 2>/dev/null | tail -1 > $OUT/bench_train.json
-timeout 600 python bench.py --dtype x3 --no-cpu-baseline --no-train 2>/dev/null | tail -1 > $OUT/bench_x3.json
-timeout 600 python bench.py --dtype x3 --mode train --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_train_x3.json
+timeout 900 python bench.py --full 2>$OUT/bench_default.err | tail -1 > $OUT/bench_default.json
+timeout 600 python bench.py --full --mode train 2>/dev/null | tail -1 > $OUT/bench_train.json
+timeout 600 python bench.py --full --dtype x3 --no-cpu-baseline --no-train 2>/dev/null | tail -1 > $OUT/bench_x3.json
+timeout 600 python bench.py --full --dtype x3 --mode train --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_train_x3.json
 if [ "${1:-}" != "quick" ]; then
-  timeout 600 python bench.py --mode train --drop 0 2>/dev/null | tail -1 > $OUT/bench_train_nodrop.json
-  timeout 900 python bench.py --workload cfg4 --mode train --steps 5 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_cfg4_train.json
-  timeout 600 python bench.py --workload cfg3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_cfg3.json
-  timeout 900 python bench.py --workload cfg4 --steps 5 --warmup 6 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_cfg4.json
+  timeout 600 python bench.py --full --mode train --drop 0 2>/dev/null | tail -1 > $OUT/bench_train_nodrop.json
+  timeout 900 python bench.py --full --workload cfg4 --mode train --steps 5 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_cfg4_train.json
+  timeout 600 python bench.py --full --workload cfg3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_cfg3.json
+  timeout 900 python bench.py --full --workload cfg4 --steps 5 --warmup 6 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_cfg4.json
 fi
 if [ "${1:-}" != "quick" ]; then
   # the RCCL code path priced at world size 1 (ZeRO-1 reduce-scatter / all-gather, segmented CMM exchange), fp32 and mode 2
   for dt in f32 x3; do
     DPMN_FORCE_DIST=1 NCCL_DEBUG=VERSION timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-      bench.py --mode train --dtype $dt --no-cpu-baseline >> $OUT/rccl_world1.log 2>&1
+      bench.py --full --mode train --dtype $dt --no-cpu-baseline >> $OUT/rccl_world1.log 2>&1
   done
 fi
 if [ "${1:-}" != "quick" ]; then
@@ -61,9 +61,9 @@ if [ "${1:-}" != "quick" ]; then
   cp gpurun_out/pmc_sq_f32.txt gpurun_out/pmc_sq_x3.txt $OUT/ 2>/dev/null
   # torch's own device ops per training step
   timeout 600 python tools/prof_torch_ops.py 2>&1 | grep -v "amdgpu.ids\|Warning\|_warn_once" > $OUT/torch_ops_per_step.txt
-  timeout 900 python bench.py --workload cfg4 --steps 5 --warmup 6 --no-cpu-baseline --dtype x3 2>/dev/null | tail -1 > $OUT/bench_cfg4_x3.json
-  timeout 900 python bench.py --workload cfg4 --mode train --steps 5 --warmup 3 --no-cpu-baseline --dtype x3 2>/dev/null | tail -1 > $OUT/bench_cfg4_train_x3.json
-  timeout 600 python bench.py --workload cfg3 --no-cpu-baseline --dtype x3 2>/dev/null | tail -1 > $OUT/bench_cfg3_x3.json
+  timeout 900 python bench.py --full --workload cfg4 --steps 5 --warmup 6 --no-cpu-baseline --dtype x3 2>/dev/null | tail -1 > $OUT/bench_cfg4_x3.json
+  timeout 900 python bench.py --full --workload cfg4 --mode train --steps 5 --warmup 3 --no-cpu-baseline --dtype x3 2>/dev/null | tail -1 > $OUT/bench_cfg4_train_x3.json
+  timeout 600 python bench.py --full --workload cfg3 --no-cpu-baseline --dtype x3 2>/dev/null | tail -1 > $OUT/bench_cfg3_x3.json
 fi
 # keep the merge-back small: the per-dispatch traces are reduced on the box, only summaries travel
 python tools/collect_profiles.py --reduce $OUT > $OUT/reduce.log 2>&1

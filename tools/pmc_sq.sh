@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT; tag=$1; shift
 OUT=$R/gpurun_out/pmc_sq_$tag; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for v in "$@"; do export "$v"; done
-B="python $R/bench.py --no-cpu-baseline --no-kernel-profile --no-train --steps 2 --warmup 2 --pipeline 1 ${BENCH_ARGS:-}"
+B="python $R/bench.py --full --no-cpu-baseline --no-kernel-profile --no-train --steps 2 --warmup 2 --pipeline 1 ${BENCH_ARGS:-}"
 timeout 900 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT --output-format csv -d $OUT/p1 -- $B > $OUT/p1.log 2>&1
 timeout 900 rocprofv3 --kernel-trace --pmc SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_RD SQ_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE --output-format csv -d $OUT/p2 -- $B > $OUT/p2.log 2>&1
 cd $R
