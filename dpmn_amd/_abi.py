@@ -246,6 +246,11 @@ SIGNATURES = {
     "dpmn_vl_tokens_f32": (_i, [fp, fp, fp, _i, _i, _i, _i, fp]),
     "dpmn_vl_pp_pool_f32": (_i, [fp, _i, fp, fp, fp, fp, _i, _i, _i, _i, _i, fp]),
     "dpmn_vl_decode_i32": (_i, [fp, fp, fp, _i, _i, _i, _i, fp]),
+    "dpmn_crnn_prep_f32": (_i, [fp, _l, fp, _i, _i, _i, _i, _i, fp]),
+    "dpmn_maxpool2d_f32": (_i, [fp, fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, fp]),
+    "dpmn_bilstm_f32": (_i, [fp, fp, fp, fp, _i, _i, _i, fp]),
+    "dpmn_ctc_greedy_i32": (_i, [fp, _i, _i, fp, fp, _i, _i, fp]),
+    "dpmn_crnn_label_vecs_f32": (_i, [fp, _i, _i, fp, _i, _i, fp]),
     "dpmn_text_prior_compose_f32": (_i, [fp, fp, fp, fp, fp, _i, _i, _i, _i, _i, _i, _i, fp]),
     "dpmn_ln_qkv_window_attn_supported": (_i, [_i, _i, _i, _IP, _i, _i]),
     "dpmn_ln_qkv_window_attn_f32": (_i, [fp, fp, fp, fp, fp, fp, _f, fp, fp, fp, fp, _PP, _IP, _IP, _i, _i, fp, fp, _i, _i, _i, _i, _i, fp]),

@@ -2,7 +2,8 @@
 
 Keeps the attribute names, the per-PGRM hyper-parameter string parsing (base.py:64-82, with a safe
 parser instead of eval()), ``generator_init`` (base.py:127-198) and the checkpoint format
-(base.py:328-373).  Out of scope here: LMDB datasets, recognisers, pygame renderer.
+(base.py:328-373), and the CRNN recogniser of the word accuracy (``CRNN_init`` / ``parse_crnn_data``, base.py:411-425) on the
+native NativeCRNN.  Out of scope here: the ASTER / MORAN recognisers, pygame renderer.
 """
 import os
 
@@ -134,6 +135,28 @@ class TextBase(object):
             print('loading pre-trained model from %s ' % path)
             model.load_state_dict(torch.load(path, map_location=self.device)['state_dict_G'])
         return {'model': model, 'crit': image_crit}
+
+    def CRNN_init(self, path=None):
+        """base.py:411-417: CRNN(32, 1, 37, 256) from config.TRAIN.VAL.crnn_pretrained (or `path`), here the native NativeCRNN,
+        frozen and in eval mode.  A missing or empty path raises: an untrained recogniser never produces an accuracy."""
+        from ..model.crnn import NativeCRNN
+        val = getattr(self.config.TRAIN, "VAL", None)
+        model_path = (getattr(val, "crnn_pretrained", None) if val is not None else None) if path is None else path
+        if not model_path or not os.path.isfile(model_path):
+            raise FileNotFoundError("dpmn_amd: the CRNN recogniser needs its weights: config TRAIN.VAL.crnn_pretrained (or the path "
+                                    "argument) names no file (%r)" % (model_path,))
+        model = NativeCRNN(32, 1, 37, 256).to(self.device)
+        print('loading pretrained crnn model from %s' % model_path)
+        model.load_state_dict(torch.load(model_path, map_location=self.device))
+        for p in model.parameters():
+            p.requires_grad = False
+        return model.eval()
+
+    def parse_crnn_data(self, imgs_input):
+        """base.py:419-425: bicubic resize to 32x100 and ITU-601 luma -> (B, 1, 32, 100), a view of the NHWC buffer NativeCRNN's
+        first conv reads (dpmn_crnn_prep_f32; channels 0..2 of the input are read)."""
+        from .. import ops
+        return ops.crnn_prep(imgs_input.float(), 32, 100)[..., 0:1].permute(0, 3, 1, 2)
 
     def save_checkpoint(self, netG_list, epoch, iters, best_acc_dict, best_model_info, is_best, converge_list,
                         recognizer=None, metric="sum", trainer=None):

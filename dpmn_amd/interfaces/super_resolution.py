@@ -222,11 +222,13 @@ class TextSR(base.TextBase):
     @torch.no_grad()
     def eval(self, model_list, val_loader, index=0, rec=None, aster_info=None, rec_list=None, model_psn=None, crnn_psn=None,
              text_prior_fn=None):
-        """super_resolution.py:340-513.  PSNR/SSIM always; recognition accuracy (lines 453-493) only when `rec` is a
-        callable images (B,3,H,W) -> list[str] and the loader yields label strings as a 4th item -- the reference's
-        ASTER / MORAN / CRNN recognisers are out of scope, so by default 'accuracy' is
-        None ("not computed"), never a fake 0.0."""
+        """super_resolution.py:340-513.  PSNR/SSIM always; recognition accuracy (lines 453-493) only when `rec` reads the SR images
+        and the loader yields label strings as a 4th item: `rec` is the native CRNN (TextBase.CRNN_init, --rec crnn: its `read`) or
+        any callable images (B,3,H,W) -> list[str].  The reference's ASTER / MORAN recognisers are out of scope (SURVEY.md section 2
+        rows 16-17), so by default 'accuracy' is None ("not computed"), never a fake 0.0."""
         from ..utils.util import str_filt
+        from ..model.crnn import NativeCRNN
+        reader = rec.read if isinstance(rec, NativeCRNN) else (rec if callable(rec) else None)
         for m in model_list:
             m.eval()
         fn = text_prior_fn or self.default_text_prior()
@@ -252,8 +254,8 @@ class TextSR(base.TextBase):
             psnr.append(p)
             ssim.append(s)
             n += sr.shape[0]
-            if callable(rec) and labels is not None:
-                for pred, target in zip(rec(sr[:, :3]), labels):
+            if reader is not None and labels is not None:      # (the host sync of the read: batch i + 1 is already submitted)
+                for pred, target in zip(reader(sr[:, :3]), labels):
                     n_correct += int(pred == str_filt(target, 'lower'))
                 n_labelled += len(labels)
 
@@ -604,7 +606,7 @@ class TextSR(base.TextBase):
                 if val_sets and it % val_int == 0:
                     # super_resolution.py:293-330: every validation subset on its own -- a log.csv row and a best-so-far checkpoint
                     # per data_name -- and the best model overall by the SUM of the subsets' scores (score = recognition accuracy
-                    # when `rec` computes one, as in the reference; PSNR otherwise: the recognisers are out of scope)
+                    # when `rec` computes one, as in the reference; PSNR otherwise, e.g. without --rec crnn)
                     trainer.sync_params()
                     current, psnr_d, ssim_d = {}, {}, {}
                     for data_name, vl in val_sets:

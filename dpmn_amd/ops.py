@@ -651,3 +651,55 @@ def text_prior_compose(cls, length, atlas, advance, out_h, out_w):
     check(lib.dpmn_text_prior_compose_f32(cls.data_ptr(), length.data_ptr(), dptr(atlas), advance.data_ptr(), dptr(out), B, max_len,
                                           n_glyph, GH, GW, out_h, out_w, stream()))
     return out
+
+
+# ------------------------------------------------------------------------------ native CRNN recogniser (csrc/crnn.hip)
+def crnn_prep(img, out_h=32, out_w=100):
+    """parse_crnn_data (base.py:419-425) for a batch: (B, >=3, H, W) -> NHWC (B, out_h, out_w, 4), channel 0 = luma, 1..3 zero."""
+    B, Cc, H, W = img.shape
+    if Cc < 3:
+        raise _abi.DpmnError("crnn_prep: channels 0..2 (RGB) are read, got %d channels" % Cc)
+    v, ptr, stride = _nchw_view(img)
+    out = torch.empty(B, out_h, out_w, 4, device=img.device)
+    check(lib.dpmn_crnn_prep_f32(ptr, stride, dptr(out), B, H, W, out_h, out_w, stream()))
+    return out
+
+
+def maxpool2d(x, k, stride, pad=(0, 0)):
+    """nn.MaxPool2d(k, stride, pad) over NHWC (B, H, W, C); k, stride, pad are (y, x) pairs."""
+    B, H, W, Cc = x.shape
+    Ho, Wo = (H + 2 * pad[0] - k[0]) // stride[0] + 1, (W + 2 * pad[1] - k[1]) // stride[1] + 1
+    y = torch.empty(B, Ho, Wo, Cc, device=x.device)
+    check(lib.dpmn_maxpool2d_f32(dptr(x), dptr(y), B, H, W, Cc, k[0], k[1], stride[0], stride[1], pad[0], pad[1], stream()))
+    return y
+
+
+def bilstm(gx, w_hh, B, T):
+    """Recurrence of a bidirectional nn.LSTM with hidden 256: gx (B*T, 2048) input projection + both biases (row b*T + t,
+    columns [forward i f g o | backward i f g o]), w_hh (2, 1024, 256) -> (B*T, 512) = [h_fwd | h_bwd]."""
+    Hd = w_hh.shape[2]
+    if tuple(gx.shape) != (B * T, 8 * Hd) or tuple(w_hh.shape) != (2, 4 * Hd, Hd):
+        raise _abi.DpmnError("bilstm: gx (B*T, 8H) and w_hh (2, 4H, H) expected, got %s, %s" % (tuple(gx.shape), tuple(w_hh.shape)))
+    out = torch.empty(B * T, 2 * Hd, device=gx.device)
+    c = torch.empty(2, B, Hd, device=gx.device)
+    check(lib.dpmn_bilstm_f32(dptr(gx), dptr(w_hh), dptr(out), dptr(c), B, T, Hd, stream()))
+    return out
+
+
+def ctc_greedy(logits, B, T, n_class):
+    """logits rows b*T + t (B*T, ld) -> one int32 buffer (B*T + B): cls (B, T) collapsed classes then length (B); returned as
+    (buffer, cls view, length view) so that the host reads both with one copy."""
+    if logits.dim() != 2 or logits.shape[0] != B * T or logits.shape[1] < n_class:
+        raise _abi.DpmnError("ctc_greedy: logits rows (B*T, >= n_class) expected")
+    buf = torch.empty(B * T + B, dtype=torch.int32, device=logits.device)
+    check(lib.dpmn_ctc_greedy_i32(dptr(logits), logits.shape[1], n_class, buf.data_ptr(), buf.data_ptr() + 4 * B * T, B, T, stream()))
+    return buf, buf[:B * T].view(B, T), buf[B * T:]
+
+
+def crnn_label_vecs(logits, B, T, n_class):
+    """softmax over the classes of logits rows b*T + t (B*T, ld) -> (B, n_class, 1, T)."""
+    if logits.dim() != 2 or logits.shape[0] != B * T or logits.shape[1] < n_class:
+        raise _abi.DpmnError("crnn_label_vecs: logits rows (B*T, >= n_class) expected")
+    out = torch.empty(B, n_class, 1, T, device=logits.device)
+    check(lib.dpmn_crnn_label_vecs_f32(dptr(logits), logits.shape[1], n_class, dptr(out), B, T, stream()))
+    return out

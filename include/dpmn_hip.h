@@ -374,6 +374,25 @@ int dpmn_vl_pp_pool_f32(const float* scores, int ld_scores, const float* enc, co
 int dpmn_vl_decode_i32(const float* logits, int* cls, int* length, int B, int n_steps, int n_class, int max_len, dpmn_stream_t stream);
 int dpmn_text_prior_compose_f32(const int* cls, const int* length, const float* atlas, const int* advance, float* out, int B, int max_len,
                                 int n_glyph, int GH, int GW, int Ho, int Wo, dpmn_stream_t stream);
+
+/* ------------------------------------------------------------------ native CRNN recogniser (crnn.hip; model/crnn.py NativeCRNN)
+ * crnn_prep:       parse_crnn_data (interfaces/base.py:419-425): img (B, >=3, H, W) planes with batch stride img_stride (channels
+ *                  0..2 read) -> torch's bicubic resize to Ho x Wo (align_corners=False, A = -0.75, taps clamped to the border, no
+ *                  antialias) -> 0.299 R + 0.587 G + 0.114 B, stored NHWC with 4 channels (channel 0 = luma, 1..3 = 0).
+ * maxpool2d:       nn.MaxPool2d((kh,kw), (sh,sw), (ph,pw)) over NHWC (C % 4 == 0), padding taps are -inf; y (B, Ho, Wo, C) with
+ *                  Ho = (H + 2 ph - kh) / sh + 1, Wo likewise.
+ * bilstm:          the recurrence of nn.LSTM(nIn, H, bidirectional=True), H = 256: gx (B*T, 8H) = x W_ih^T + b_ih + b_hh with row
+ *                  b*T + t and columns [forward i f g o | backward i f g o]; w_hh (2, 4H, H); out (B*T, 2H) = [h_fwd | h_bwd];
+ *                  c_state (2, B, H) scratch.  One launch per time step (both directions, whole batch).
+ * ctc_greedy:      rows b*T + t of logits (leading dimension ld) -> arg-max class per step (first maximum), repeats collapsed,
+ *                  blank 0 dropped: cls (B, T) (zero beyond the length), length (B).
+ * crnn_label_vecs: softmax over n_class of rows b*T + t -> out (B, n_class, 1, T) (CRNN.label_vecs). */
+int dpmn_crnn_prep_f32(const float* img, long img_stride, float* out_nhwc4, int B, int H, int W, int Ho, int Wo, dpmn_stream_t stream);
+int dpmn_maxpool2d_f32(const float* x, float* y, int B, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
+                       dpmn_stream_t stream);
+int dpmn_bilstm_f32(const float* gx, const float* w_hh, float* out, float* c_state, int B, int T, int H, dpmn_stream_t stream);
+int dpmn_ctc_greedy_i32(const float* logits, int ld, int n_class, int* cls, int* length, int B, int T, dpmn_stream_t stream);
+int dpmn_crnn_label_vecs_f32(const float* logits, int ld, int n_class, float* out, int B, int T, dpmn_stream_t stream);
 int dpmn_layernorm_std_f32(const float* x, const float* a2, const float* b2, float eps, float* y, long M, int C,
                            dpmn_stream_t stream);
 /* GPU half of the TextZoom collate (dataset/dataset.py:1266-1319 resizeNormalize, 2007-2013 alignCollate_realWTLAMask.__call__):

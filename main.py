@@ -2,10 +2,10 @@
 """Command-line entry with the reference's flags (main.py:37-67) and config file (config/super_resolution.yaml, main.py:69).
 
 `python main.py --arch tatt --mask --gradient --stu_iter_b1 3 --stu_iter_b2 3 ...` builds the same TextSR mission on the
-HIP-backed modules.  The TextZoom LMDB reader and the recognisers are outside this repo's scope, so the
-loop is fed synthetic (images_hr, images_lr, label_vecs) batches of the real shapes -- `--synthetic_steps` of them --
-and the text priors come from `TextSR.synthetic_text_prior()`; everything between the loader and the optimizer step is
-the real path.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
+HIP-backed modules.  `--rec crnn` loads the native CRNN recogniser (config TRAIN.VAL.crnn_pretrained) for the word accuracy;
+ASTER and MORAN are not built.  Without a TextZoom LMDB directory the loop is fed synthetic (images_hr, images_lr, label_vecs)
+batches of the real shapes -- `--synthetic_steps` of them -- and the text priors come from `TextSR.synthetic_text_prior()`;
+everything between the loader and the optimizer step is the real path.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
 import argparse
 import csv
@@ -26,11 +26,28 @@ class AttrDict(dict):
     __setattr__ = dict.__setitem__
 
 
-def synthetic_loader(batch_size, steps, seed):
+def synthetic_loader(batch_size, steps, seed, labels=False):
+    """labels=True: a 4th item of seeded random words (the label strings a recogniser's accuracy is counted against; on noise
+    images they only exercise the accuracy path, they say nothing about the recogniser)."""
+    import numpy as np
     from dpmn_amd.utils import synth
     for i in range(steps):
         b = synth.synth_batch(batch_size, seed=seed + i)
-        yield b["images_hr"], b["images_lr"], b["label_vecs"]
+        if not labels:
+            yield b["images_hr"], b["images_lr"], b["label_vecs"]
+            continue
+        rng = np.random.RandomState(seed + i)
+        words = ["".join(rng.choice(list("abcdefghijklmnopqrstuvwxyz0123456789"), rng.randint(1, 9))) for _ in range(batch_size)]
+        yield b["images_hr"], b["images_lr"], b["label_vecs"], words
+
+
+def recogniser(mission, args):
+    """--rec crnn: the native CRNN of config TRAIN.VAL.crnn_pretrained (TextBase.CRNN_init) -> word accuracy in test / eval and
+    best-model selection by accuracy; --rec aster / moran are not built here: accuracy is not computed (None)."""
+    if args.rec == "crnn":
+        return mission.CRNN_init()
+    print("--rec %s: recogniser not built (only --rec crnn is); accuracy is not computed" % args.rec)
+    return None
 
 
 def main(config, args):
@@ -51,6 +68,7 @@ def main(config, args):
     mission.rank_seed = config.TRAIN.manualSeed + rank
     bs = args.batch_size or config.TRAIN.batch_size
     os.makedirs(config.TRAIN.ckpt_dir, exist_ok=True)
+    rec = recogniser(mission, args)
     if args.test:
         result_path = os.path.join(config.TRAIN.ckpt_dir, "test_result.csv")
         if rank == 0 and not os.path.exists(result_path):
@@ -60,12 +78,13 @@ def main(config, args):
             from dpmn_amd.dataset.textzoom import sr_batches
             loader = sr_batches(mission.get_test_data(args.test_data_dir)[1], mission.device, mission.mask)
         else:
-            loader = synthetic_loader(bs, args.synthetic_steps, 1000 + rank)
-        res = mission.test(loader)
+            loader = synthetic_loader(bs, args.synthetic_steps, 1000 + rank, labels=rec is not None)
+        res = mission.test(loader, rec=rec)
         if rank == 0:
             with open(result_path, "a") as out:
                 csv.writer(out).writerow([args.rec, "synthetic", res["accuracy"], res["psnr_avg"], res["ssim_avg"]])
-            print("psnr %.4f ssim %.4f over %d synthetic batches" % (res["psnr_avg"], res["ssim_avg"], args.synthetic_steps))
+            print("psnr %.4f ssim %.4f accuracy %s over %d synthetic batches" % (res["psnr_avg"], res["ssim_avg"], res["accuracy"],
+                                                                                args.synthetic_steps))
     else:
         log_path = os.path.join(config.TRAIN.ckpt_dir, "log.csv")
         if rank == 0 and not os.path.exists(log_path):
@@ -86,9 +105,9 @@ def main(config, args):
             val_loader = {name: (lambda v=vdl: sr_batches(v, mission.device, mission.mask))
                           for name, vdl in zip(subset_names(val_dirs), val_dls)} if val_dls else None
             mission.train(lambda epoch: sr_batches(dl, mission.device, mission.mask), epochs=config.TRAIN.epochs,
-                          sampler=getattr(mission, "train_sampler", None), val_loader=val_loader)
+                          sampler=getattr(mission, "train_sampler", None), val_loader=val_loader, rec=rec)
         else:
-            mission.train(synthetic_loader(bs, args.synthetic_steps, 2000 + rank), steps=args.synthetic_steps)
+            mission.train(synthetic_loader(bs, args.synthetic_steps, 2000 + rank), steps=args.synthetic_steps, rec=rec)
 
 
 def subset_names(val_dirs):

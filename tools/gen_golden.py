@@ -632,6 +632,39 @@ def gen_crnn():
     save("crnn", logits=logits, label_vecs=lv.contiguous(), manifest=manifest(sd), checksum=checksum(sd))
 
 
+def gen_crnn_ctc():
+    """Greedy CTC decoding of the CRNN recogniser: the reference's own strLabelConverter.decode(raw=False) (utils/utils_crnn.py:54-90)
+    with the converter of base.py:62 (digits + lowercase) on hand-made (B, 26) class sequences -- all blank, repeats with and without
+    a blank between them, a full 26-character run, every class once, leading / trailing blanks -- exactly as eval() calls it
+    (super_resolution.py:474-479: the (B*26) flattened arg-max classes with 26 per image)."""
+    import string
+    from utils import utils_crnn
+    conv = utils_crnn.strLabelConverter(string.digits + string.ascii_lowercase)
+    T = 26
+    rows = [[0] * T,                                                          # all blank
+            [5] * T,                                                          # one class repeated: one character
+            [5, 5, 0, 5, 5] + [0] * (T - 5),                                  # a blank between repeats keeps both
+            [11, 11, 12, 12, 12, 13] + [0] * (T - 6),                         # repeats collapse
+            [(i % 36) + 1 for i in range(T)],                                 # 26 distinct characters, no blank
+            [1 + ((2 * i) % 36) for i in range(T)],
+            [0, 0, 0, 20, 21, 22] + [0] * (T - 6),                            # leading and trailing blanks
+            [36, 0, 36, 36, 0, 0, 1, 1, 0, 1] + [0] * (T - 10),
+            [0] + list(range(1, 26)),                                         # every class once (with the next row)
+            list(range(26, 37)) + [0] * (T - 11),
+            [7, 8] * (T // 2),                                                # alternation, no repeat to collapse
+            [3, 0] * (T // 2)]
+    rng = np.random.RandomState(11)
+    for _ in range(8):                                                        # random sequences, blank-heavy
+        r = rng.randint(0, 37, T)
+        r[rng.rand(T) < 0.4] = 0
+        rows.append(r.tolist())
+    cls = torch.tensor(rows, dtype=torch.int64)
+    preds = cls.reshape(-1)
+    sizes = torch.IntTensor([T] * cls.shape[0])
+    texts = conv.decode(preds, sizes, raw=False)
+    save("crnn_ctc", classes=cls.to(torch.int32), texts=np.array(texts), alphabet=np.array(conv.alphabet[:-1]))
+
+
 def gen_collate():
     """Data path: the reference's own `resizeNormalize` and `alignCollate_realWTLAMask.__call__`
     (dataset/dataset.py:1266-1319, 1966-2076) and `str_filt` (utils/util.py) run on five synthetic RGB images of ragged sizes
@@ -704,6 +737,7 @@ if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["all"]
     GENS["crnn"] = gen_crnn
+    GENS["crnn_ctc"] = gen_crnn_ctc
     GENS["collate"] = gen_collate      # last: it installs extra import shims (lmdb, imgaug, torchvision.utils)
     for name, fn in GENS.items():
         if "all" in which or name in which:
