@@ -17,20 +17,14 @@
 
 namespace {
 
-template <int BM, int BN, int WM, int WN, bool UNI = false, int BKT = 32, bool SIMPLE = false, bool AFF = false, bool BF = false, bool M32 = false>
+template <int BM, int BN, int WM, int WN, bool UNI = false, bool SIMPLE = false, bool AFF = false, bool BF = false>
 __global__ __launch_bounds__(256) void k_conv_igemm(ConvArgs a) {
-  conv_igemm_body<BM, BN, WM, WN, UNI, BKT, SIMPLE, AFF, BF, M32>(a);
+  conv_igemm_body<BM, BN, WM, WN, UNI, SIMPLE, AFF, BF>(a);
 }
 // split-K with the reduction inside the launch (XRED above)
 template <int BM, int BN, int WM, int WN, bool AFF>
 __global__ __launch_bounds__(256, 2) void k_conv_igemm_xr(ConvArgs a) {      // two resident blocks per CU (<= 256 registers), as the fixed-split kernel
-  conv_igemm_body<BM, BN, WM, WN, true, 32, true, AFF, false, false, true>(a);
-}
-// the SIMPLE path with 16-deep chunks (36.9 KB of LDS) AND a register budget for three waves per SIMD (<= 168 registers): three
-// resident blocks per CU instead of two -- the 16-deep switch alone (DPMN_CONV_BK16) stayed at two because of its 200 registers
-template <int BM, int BN, int WM, int WN, bool AFF>
-__global__ __launch_bounds__(256, 3) void k_conv_igemm_o3(ConvArgs a) {
-  conv_igemm_body<BM, BN, WM, WN, true, 16, true, AFF, false, false>(a);
+  conv_igemm_body<BM, BN, WM, WN, true, true, AFF, false, true>(a);
 }
 
 // sum the split-K partials and run the epilogue.  Block = 64 channel-quads x 4 row lanes, 64 rows per block, so the
@@ -676,20 +670,11 @@ int launch_halo_c4(const ConvArgs& a, hipStream_t st) {
 }
 
 template <int KS, int BN, int TH, bool BF = false>
-int launch_halo_th(const ConvArgs& a, hipStream_t st, bool x3 = false) {
-  if constexpr (!BF && KS == 3 && BN == 64) {
+int launch_halo_th(const ConvArgs& a, hipStream_t st) {
+  if constexpr (!BF && KS == 3 && BN == 64)
     if (g_dpmn_bf16) return launch_halo_th<KS, BN, TH, true>(a, st);
-    if (x3) {
-      ProfScope prof(PT_CONV_HALO, st, conv_flops(a), conv_bytes(a));
-      if (dpmn_conv::x3_launch_halo(KS, BN, TH, a, dim3(a.B * (a.Hin / TH) * (a.Win / 16), cdiv(a.Cout, BN)), st) != 0)
-        return dpmn_set_error(DPMN_ERR_LAUNCH, "conv2d: bf16x3 halo launch failed");
-      DPMN_CHECK_LAUNCH();
-      return DPMN_OK;
-    }
-  }
   constexpr int NPX = (TH + KS - 1) * (16 + KS - 1);
-  constexpr int TPS = (KS == 3 && !BF && TH == 4) ? DPMN_HALO_TPS : 1;      // as in the kernel
-  const size_t smem = (size_t)(NPX + 2 * TPS * BN) * (BF ? (BK + 8) / 2 : LDK) * sizeof(float);
+  const size_t smem = (size_t)(NPX + 2 * BN) * (BF ? (BK + 8) / 2 : LDK) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_halo<KS, BN, TH, BF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
@@ -706,34 +691,21 @@ template <int KS, int BN>
 int launch_halo(const ConvArgs& a, hipStream_t st) {
   // 8x16-pixel tiles amortise the weight staging best, but a map with fewer than ~3 tiles per CU leaves the CUs unevenly
   // loaded (384 tiles on 256 CUs = 1 or 2 per CU): halve the tile there
-  static const int force = getenv("DPMN_HALO_TH") ? atoi(getenv("DPMN_HALO_TH")) : 0;
   const long blocks8 = (long)a.B * (a.Hin / 8) * (a.Win / 16) * cdiv(a.Cout, BN);
-  const bool small = force ? force == 4 : blocks8 < 768;
   // mode 2 ("f32 via bf16x3", conv_x3.hip): 8-row tiles only -- with one output row per wave the split of a tap's weight slice costs
   // more vector time than the tap has MFMA time (measured: the 4-row variant is SLOWER than the fp32 kernel) -- and only where
-  // those tiles fill the chip (DPMN_X3_HALO_MIN blocks); the other layers keep the fp32 kernel
+  // those tiles fill the chip (8 row tiles per image); the other layers keep the fp32 kernel
   // (the rule is per IMAGE -- 8-row tiles x 64-channel blocks of one image, 8 = the 384 blocks of the B = 48 forward -- so that a sample
   //  meets the same kernel family whatever batch it travels in: the bf16x3 and the fp32 kernel differ by fp32-class round-off, which
   //  a mask threshold downstream -- toMask, util.py:27-35 -- can turn into a flipped pixel)
-  static const int x3_min_img = getenv("DPMN_X3_HALO_MIN") ? atoi(getenv("DPMN_X3_HALO_MIN")) : 8;
-  const long x3_min = (long)x3_min_img * a.B;
-  static const int x3_th4 = getenv("DPMN_X3_HALO_TH4") ? atoi(getenv("DPMN_X3_HALO_TH4")) : 0;
-  if constexpr (KS == 3 && BN == 64) {
-    // 16 x 16-pixel tiles on eight waves (k_conv_halo_x3w): the small maps, where 8-row tiles do not fill the chip and the 4-row
-    // variant is slower than fp32 -- and, by default, every layer the 8-row x3 kernel would take (half the weight-split work per MFMA)
-    static const int x3_w16 = getenv("DPMN_X3_HALO16") ? atoi(getenv("DPMN_X3_HALO16")) : 0;      // 0 off (default: measured 55.8 vs 54.4 us forward, 79.6 vs 74.3 us training step per launch), 1 only below x3_min, 2 wherever it applies
-    static const int x3_w16_min = getenv("DPMN_X3_HALO16_MIN") ? atoi(getenv("DPMN_X3_HALO16_MIN")) : 96;
-    const long blocks16 = (long)a.B * (a.Hin / 16) * (a.Win / 16) * cdiv(a.Cout, BN);
-    if (x3_on(2) && x3_w16 && a.Hin % 16 == 0 && blocks16 >= x3_w16_min && (x3_w16 >= 2 || blocks8 < x3_min)) {
-      ProfScope prof(PT_CONV_HALO, st, conv_flops(a), conv_bytes(a));
-      if (dpmn_conv::x3_launch_halo(KS, BN, 16, a, dim3(a.B * (a.Hin / 16) * (a.Win / 16), cdiv(a.Cout, BN)), st) != 0)
-        return dpmn_set_error(DPMN_ERR_LAUNCH, "conv2d: bf16x3 halo launch failed");
-      DPMN_CHECK_LAUNCH();
-      return DPMN_OK;
-    }
+  if (x3_on(2) && KS == 3 && BN == 64 && blocks8 >= 8L * a.B) {
+    ProfScope prof(PT_CONV_HALO, st, conv_flops(a), conv_bytes(a));
+    if (dpmn_conv::x3_launch_halo(a, dim3(a.B * (a.Hin / 8) * (a.Win / 16), cdiv(a.Cout, BN)), st) != 0)
+      return dpmn_set_error(DPMN_ERR_LAUNCH, "conv2d: bf16x3 halo launch failed");
+    DPMN_CHECK_LAUNCH();
+    return DPMN_OK;
   }
-  if (x3_on(2) && KS == 3 && BN == 64 && blocks8 >= x3_min) return launch_halo_th<KS, BN, 8>(a, st, true);
-  if (KS == 3 && small) return launch_halo_th<KS, BN, 4>(a, st, x3_on(2) && x3_th4);
+  if (KS == 3 && blocks8 < 768) return launch_halo_th<KS, BN, 4>(a, st);
   return launch_halo_th<KS, BN, 8>(a, st);
 }
 
@@ -778,8 +750,7 @@ int launch_conv_sk(const ConvArgs& a, float* ws, size_t ws_bytes, unsigned* cnt,
   // consecutive tiles run on one XCD: let them share what costs more to re-read (as the wlocal rule of the fixed-split path)
   const double w_reread = (double)a.Cout * a.Kp * nph * (a.groups > 1 ? 2 : 1) * (sk.tiles_m > 8 ? 8 : sk.tiles_m);
   const double x_reread = (double)a.B * a.Hin * a.Win * a.cin * (sk.tiles_n > 8 ? 8 : sk.tiles_n);
-  static const int force_order = getenv("DPMN_SK_ORDER") ? atoi(getenv("DPMN_SK_ORDER")) : -1;
-  sk.order = force_order >= 0 ? force_order : (w_reread > x_reread ? 0 : 1);
+  sk.order = w_reread > x_reread ? 0 : 1;
   ProfScope prof(PT_CONV_IGEMM_SK, st, conv_flops(a), conv_bytes(a));
   if (n_aff) hipLaunchKernelGGL((k_conv_igemm_sk<BM, BN, WM, WN, true>), dim3(G), dim3(256), 0, st, a, sk);
   else hipLaunchKernelGGL((k_conv_igemm_sk<BM, BN, WM, WN, false>), dim3(G), dim3(256), 0, st, a, sk);
@@ -813,14 +784,12 @@ int launch_conv(ConvArgs a, float* ws, size_t ws_bytes, hipStream_t st, unsigned
   const int tiles = cdiv(M, BM) * cdiv(a.Cout, BN) * nph;
   const int nk = a.Kp / BK;
   int S = 1;
-  static const int force_s = getenv("DPMN_CONV_S") ? atoi(getenv("DPMN_CONV_S")) : 0;      // experiment knob: fixed split count
-  static const int target = getenv("DPMN_CONV_TARGET") ? atoi(getenv("DPMN_CONV_TARGET")) : 768;
   if (ws && tiles < 384 && nk >= 16) {
-    S = force_s > 0 ? force_s : cdiv(target, tiles);
+    S = cdiv(768, tiles);              // ~3 blocks per CU
     if (S > nk / 8) S = nk / 8;
     if (S > 64) S = 64;
-    static const size_t cap_mb = getenv("DPMN_SPLITK_CAP_MB") ? (size_t)atoi(getenv("DPMN_SPLITK_CAP_MB")) : 32;
-    const size_t cap = ws_bytes < (cap_mb << 20) ? ws_bytes : (cap_mb << 20);   // keep the partial-sum round trip small
+    const size_t cap_max = (size_t)32 << 20;      // keep the partial-sum round trip small
+    const size_t cap = ws_bytes < cap_max ? ws_bytes : cap_max;
     while (S > 1 && (size_t)S * nph * M * a.npad * sizeof(float) > cap) --S;
     const int cps = cdiv(nk, S);
     S = cdiv(nk, cps);   // no empty splits
@@ -830,26 +799,20 @@ int launch_conv(ConvArgs a, float* ws, size_t ws_bytes, hipStream_t st, unsigned
   dim3 grid(cdiv(M, BM), cdiv(a.Cout, BN), S * nph);
   {
     // weight-local XCD mapping when re-reading the weights per row tile costs more than re-reading the input per column tile
-    static const int wlocal_on = getenv("DPMN_CONV_WLOCAL") ? atoi(getenv("DPMN_CONV_WLOCAL")) : 1;
     const double w_reread = (double)a.Cout * a.Kp * nph * (a.groups > 1 ? 2 : 1) * (grid.x > 8 ? 8 : grid.x);
     const double x_reread = (double)a.B * a.Hin * a.Win * a.cin * (grid.y > 8 ? 8 : grid.y);
-    a.wlocal = wlocal_on && ((grid.y * grid.z) % 8 == 0) && grid.x > 1 && w_reread > x_reread;
+    a.wlocal = ((grid.y * grid.z) % 8 == 0) && grid.x > 1 && w_reread > x_reread;
   }
   // segment-uniform chunks (all channel counts multiples of 32) and 32-bit byte offsets: the buffer-load instantiation
-  static const int uni_on = getenv("DPMN_CONV_UNI") ? atoi(getenv("DPMN_CONV_UNI")) : 1;
-  bool uni = uni_on && a.cin % 32 == 0 && (size_t)a.Cout * a.Kp * 4 < (1ull << 31);
+  bool uni = a.cin % 32 == 0 && (size_t)a.Cout * a.Kp * 4 < (1ull << 31);
   for (int i = 0; i < 3; ++i)
     uni = uni && a.cseg[i] % 32 == 0 && (size_t)a.B * a.Hin * a.Win * a.cseg[i] * 4 < (1ull << 31);
   {
     // split-K launches additionally move S partial-sum slabs (written here, read by the reduce kernel): not algorithmic
     ProfScope prof(BN == 128 ? PT_CONV_IGEMM_128 : (BN == 64 ? PT_CONV_IGEMM_64 : PT_CONV_IGEMM_NARROW), st, conv_flops(a), conv_bytes(a));
-    static const int bk16 = getenv("DPMN_CONV_BK16") ? atoi(getenv("DPMN_CONV_BK16")) : 0;
-    static const int simple_on = getenv("DPMN_CONV_SIMPLE") ? atoi(getenv("DPMN_CONV_SIMPLE")) : 1;
-    static const int m32_on = getenv("DPMN_CONV_M32") ? atoi(getenv("DPMN_CONV_M32")) : 0;
     static const int xred_env = getenv("DPMN_CONV_XRED") ? atoi(getenv("DPMN_CONV_XRED")) : 0;      // split-K reduced in the launch through one XCD's L2
     const int xred_on = g_xred_enabled >= 0 ? g_xred_enabled : xred_env;
-    static const int o3_on = getenv("DPMN_CONV_O3") ? atoi(getenv("DPMN_CONV_O3")) : 0;          // 16-deep chunks + 3 waves per SIMD      // 32x32x2 MFMAs on the 128 x 128 tile
-    bool simple = simple_on && uni && a.KH * a.KW <= 31 && (a.pro_act == ACT_NONE || a.pro_act == ACT_RELU || a.pro_act == ACT_LEAKY02);
+    bool simple = uni && a.KH * a.KW <= 31 && (a.pro_act == ACT_NONE || a.pro_act == ACT_RELU || a.pro_act == ACT_LEAKY02);
     int n_seg = 0, n_aff = 0;
     for (int i = 0; i < 3; ++i) {    // + the shift of the buffer base must keep the byte range below 2^31
       if (a.cseg[i] > 0) { ++n_seg; n_aff += a.in_scale[i] != nullptr; }
@@ -857,28 +820,16 @@ int launch_conv(ConvArgs a, float* ws, size_t ws_bytes, hipStream_t st, unsigned
                ((size_t)a.B * a.Hin * a.Win + (size_t)(abs(a.pad_y) + a.KH * abs(a.dil_y) + 2) * a.Win) * a.cseg[i] * 4 < (1ull << 31);
     }
     simple = simple && (n_aff == 0 || n_aff == n_seg);       // mixed segments: the general UNI path
-  static const int x3_t64 = getenv("DPMN_X3_TILE64") ? atoi(getenv("DPMN_X3_TILE64")) : 0;      // the 64 x 64 tile in mode 2: measured 93 vs 88 us (forward), 65 vs 60 (training step) -- off
-  if (x3_on(1) && simple && ((BM == BN && (BM == 128 || (BM == 64 && x3_t64))) || (BM == 128 && BN == 64))) {
-    if (dpmn_conv::x3_launch_igemm(BM == BN ? BM : 12864, n_aff != 0, a, grid, st) != 0) return dpmn_set_error(DPMN_ERR_LAUNCH, "conv2d: bf16x3 launch failed");
+  // mode 2 ("f32 via bf16x3"): the 128 x 128 tile only -- the operand split of a 64 x 64 tile costs as many vector instructions as the
+  // tile has MFMA cycles (measured 93 vs 88 us forward); 128 x 64 tiles lost to the fp32 64 x 64 tile too (73.7 vs 60.1 us)
+  if (x3_on(1) && simple && BM == 128 && BN == 128) {
+    if (dpmn_conv::x3_launch_igemm(n_aff != 0, a, grid, st) != 0) return dpmn_set_error(DPMN_ERR_LAUNCH, "conv2d: bf16x3 launch failed");
   } else
   if (g_dpmn_bf16 && simple && BM == BN && (BM == 128 || BM == 64)) {
-    if (n_aff) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, 32, true, true, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, 32, true, false, true>), grid, dim3(256), 0, st, a);
+    if (n_aff) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, true, true, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, true, false, true>), grid, dim3(256), 0, st, a);
   } else
-  if (uni && BM == 128 && BN == 128 && bk16) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, 16>), grid, dim3(256), 0, st, a);
-  else if (simple && o3_on && BM == 128 && BN == 128) {
-    if constexpr (BM == 128 && BN == 128) {
-      if (n_aff) hipLaunchKernelGGL((k_conv_igemm_o3<BM, BN, WM, WN, true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((k_conv_igemm_o3<BM, BN, WM, WN, false>), grid, dim3(256), 0, st, a);
-    }
-  }
-  else if (simple && m32_on && BM / WM == 64 && BN / WN == 64) {
-    if constexpr (BM / WM == 64 && BN / WN == 64) {
-      if (n_aff) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, 32, true, true, false, true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, 32, true, false, false, true>), grid, dim3(256), 0, st, a);
-    }
-  }
-  else if (simple && S > 1 && BM == 128 && BN == 128 && xred_on && cnt && xred_fits(tiles, S, cnt_len, a) &&
+  if (simple && S > 1 && BM == 128 && BN == 128 && xred_on && cnt && xred_fits(tiles, S, cnt_len, a) &&
            (size_t)tiles * S * BM * BN * sizeof(float) <= ws_bytes) {
     // split-K reduced inside the launch through one XCD's L2 (XRED in conv_igemm_body): 1-D grid, XCD c owns a contiguous run of
     // tiles.  Tile order = the one that re-reads fewer bytes: every XCD fetches the weight column tiles and the input row tiles
@@ -916,8 +867,8 @@ int launch_conv(ConvArgs a, float* ws, size_t ws_bytes, hipStream_t st, unsigned
       return DPMN_OK;
     }
   }
-  else if (simple && n_aff) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, 32, true, true>), grid, dim3(256), 0, st, a);
-  else if (simple) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, 32, true>), grid, dim3(256), 0, st, a);
+  else if (simple && n_aff) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, true, true>), grid, dim3(256), 0, st, a);
+  else if (simple) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true, true>), grid, dim3(256), 0, st, a);
   else if (uni) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_conv_igemm<BM, BN, WM, WN>), grid, dim3(256), 0, st, a);
   }
@@ -1001,10 +952,9 @@ int dpmn_conv2d_nhwc_f32(const dpmn_conv_desc* d, dpmn_stream_t stream) {
                        (size_t)a.B * a.Hin * a.Win * (size_t)cin * 4 < (1ull << 31);   // 32-bit buffer-load offsets
   // too few 8x16-pixel tiles to fill 256 CUs (deep decoder levels with 3-segment inputs): split-K implicit GEMM instead
   const bool halo_starved = (M / 128) * cdiv(a.Cout, 64) < 256 && a.Cout >= 128 && ws != nullptr;
-  static const bool direct_on = !(getenv("DPMN_CONV_DIRECT") && atoi(getenv("DPMN_CONV_DIRECT")) == 0);
   // (measured: 8 -> 4 with statistics 95 -> 20 us, 4 -> 4 25 -> 12 us; 12 -> 12 over 49152 pixels 22 -> 37 us -- too few,
   //  too heavy threads -- so the rule is cin * Cout <= 64)
-  if (direct_on && cin <= 16 && a.Cout <= 16 && cin * a.Cout <= 64 && a.nphase == 1 && a.groups == 1 && !a.pixel_shuffle && M >= 4096) {
+  if (cin <= 16 && a.Cout <= 16 && cin * a.Cout <= 64 && a.nphase == 1 && a.groups == 1 && !a.pixel_shuffle && M >= 4096) {
     ProfScope prof(PT_CONV_IGEMM_NARROW, st, conv_flops(a), conv_bytes(a));
     const dim3 grid(cdiv(M, 256));
     if (a.Cout <= 4) hipLaunchKernelGGL(k_conv_direct<1>, grid, dim3(256), 0, st, a);
@@ -1014,14 +964,11 @@ int dpmn_conv2d_nhwc_f32(const dpmn_conv_desc* d, dpmn_stream_t stream) {
     DPMN_CHECK_LAUNCH();
     return DPMN_OK;
   }
-  static const bool c4_on = !(getenv("DPMN_CONV_C4") && atoi(getenv("DPMN_CONV_C4")) == 0);
-  if (halo_ok && a.Cout <= 4 && c4_on && !a.pixel_shuffle && !a.res && a.groups == 1)
+  if (halo_ok && a.Cout <= 4 && !a.pixel_shuffle && !a.res && a.groups == 1)
     return a.KH == 3 ? launch_halo_c4<3, 8>(a, st) : launch_halo_c4<9, 8>(a, st);   // (3x3: 4- and 16-row tiles measured no better)
   if (halo_ok && !halo_starved) {
     // (128 output channels per block -- one halo staging instead of two, 64 MFMAs per tap and barrier -- measured 212-220 us
-    //  against 143-148 us on the 64 -> 128 / 64 -> 256 convs: rejected, switch kept for the record)
-    static const int bn128 = getenv("DPMN_HALO_BN128") ? atoi(getenv("DPMN_HALO_BN128")) : 0;
-    if (a.KH == 3 && bn128 && a.Cout % 128 == 0) return launch_halo<3, 128>(a, st);
+    //  against 143-148 us on the 64 -> 128 / 64 -> 256 convs: rejected)
     if (a.KH == 3) return a.Cout <= 16 ? launch_halo<3, 16>(a, st) : launch_halo<3, 64>(a, st);
     return a.Cout <= 16 ? launch_halo<9, 16>(a, st) : launch_halo<9, 64>(a, st);
   }
@@ -1046,8 +993,6 @@ int dpmn_conv2d_nhwc_f32(const dpmn_conv_desc* d, dpmn_stream_t stream) {
   if (a.Cout <= 32) return launch_conv<128, 32, 4, 1>(a, ws, wsb, st);
   // 128x128 tiles halve the L2->LDS bytes per FLOP of the 64x64 tile (which is L2-bound); small-M convs regain
   // parallelism through split-K (deep CMM levels: K = 2304..13824)
-  static const int force_tile = getenv("DPMN_CONV_TILE") ? atoi(getenv("DPMN_CONV_TILE")) : 0;          // experiment knob
-  if (force_tile == 64) return launch_conv<64, 64, 2, 2>(a, ws, wsb, st);
   if (a.Cout >= 128 && M >= 128) {
     // stream-K (one persistent launch, no reduce kernel) where the fixed-split path would split K or leave CUs idle; 64-pixel
     // row tiles when 128-pixel ones would be partly empty (the 1x4 bottleneck maps: M = 192 per branch / phase)
@@ -1056,27 +1001,12 @@ int dpmn_conv2d_nhwc_f32(const dpmn_conv_desc* d, dpmn_stream_t stream) {
     // DPMN_CONV_SK: 0 never, 1 (default) the 64-row layers only, 2 every layer that qualifies (measured: the deep-K layers lose
     // to the fixed split + parallel reduce launch -- a tile shared by 5 ... 21 workgroups is collected by ONE of them)
     static const int sk_mode = getenv("DPMN_CONV_SK") ? atoi(getenv("DPMN_CONV_SK")) : 1;
-    static const int rows64_fixed = getenv("DPMN_ROWS64_FIXED") ? atoi(getenv("DPMN_ROWS64_FIXED")) : 0;
-    if (rows64 && rows64_fixed && (a.groups != 2 || mg % 64 == 0)) return launch_conv<64, 128, 1, 4>(a, ws, wsb, st);
     const int r = rows64 ? launch_conv_sk<64, 128, 1, 4>(a, ws, wsb, d->arrive_cnt, d->arrive_cnt_len, st)
                          : (sk_mode >= 2 ? launch_conv_sk<128, 128, 2, 2>(a, ws, wsb, d->arrive_cnt, d->arrive_cnt_len, st) : -1);
     if (r >= 0) return r;
     if (a.groups == 2 && mg % 128 != 0) return split_groups();
-    {
-      // 64-pixel row tiles WITHOUT a K split where the 128 x 128 tiling would split K only to fill the CUs (no partial-sum slabs, no
-      // reduce launch): DPMN_CONV_ALT64 = minimum number of 64 x 128 tiles (0 = off)
-      static const int alt64 = getenv("DPMN_CONV_ALT64") ? atoi(getenv("DPMN_CONV_ALT64")) : 0;
-      const int nph = a.nphase > 1 ? a.nphase : 1;
-      const int t128 = cdiv(M, 128) * cdiv(a.Cout, 128) * nph, t64 = cdiv(M, 64) * cdiv(a.Cout, 128) * nph;
-      if (alt64 > 0 && ws && t128 < 384 && a.Kp / 32 >= 16 && t64 >= alt64 && (a.groups != 2 || mg % 64 == 0))
-        return launch_conv<64, 128, 1, 4>(a, nullptr, 0, st);
-    }
     return launch_conv<128, 128, 2, 2>(a, ws, wsb, st, d->arrive_cnt, d->arrive_cnt_len);
   }
-  // mode 2 ("f32 via bf16x3"): 128-pixel row tiles -- the operand split of a 64 x 64 tile costs as many vector instructions as the
-  // tile has MFMA cycles (conv_x3.hip); the fp32 kernels keep the 64 x 64 tile (more blocks for the small maps)
-  static const int x3_rows128 = getenv("DPMN_X3_ROWS128") ? atoi(getenv("DPMN_X3_ROWS128")) : 0;      // measured: 73.7 vs 60.1 us (fp32 64 x 64) over the 18 launches of the training step -- off
-  if (x3_on(1) && x3_rows128 && M >= 128 * 256 && (a.groups != 2 || a.m_per_group % 128 == 0)) return launch_conv<128, 64, 2, 2>(a, ws, wsb, st);
   return launch_conv<64, 64, 2, 2>(a, ws, wsb, st);
 }
 

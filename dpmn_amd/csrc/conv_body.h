@@ -50,9 +50,9 @@ struct ConvArgs {
   int xr_cstride;             // words between two arrival words
   int xr_ablate;              // timing experiments only (DPMN_XRED_ABLATE): 1 no collect loads, 2 no wait for the partial stores, 4 no atomics / barriers
 };
-// conv_x3.hip ("f32 via bf16x3" instantiations, dpmn_set_compute_dtype(2)); both return 0 or -1 = no such variant (caller falls through)
-int x3_launch_igemm(int tile, bool aff, const ConvArgs& a, dim3 grid, hipStream_t st);      // tile: 128 (128 x 128), 12864 (128 x 64) or 64 (64 x 64), SIMPLE path
-int x3_launch_halo(int ks, int bn, int th, const ConvArgs& a, dim3 grid, hipStream_t st);  // 3 x 3, 64 output channels per block
+// conv_x3.hip ("f32 via bf16x3" instantiations, dpmn_set_compute_dtype(2)); both return 0, or -1 if the launch could not be made
+int x3_launch_igemm(bool aff, const ConvArgs& a, dim3 grid, hipStream_t st);      // 128 x 128 tile, SIMPLE path
+int x3_launch_halo(const ConvArgs& a, dim3 grid, hipStream_t st);                  // 3 x 3, 64 output channels, 8 x 16 pixels per block
 }  // namespace dpmn_conv
 
 namespace {
@@ -143,8 +143,6 @@ __device__ __forceinline__ void conv_store(const ConvArgs& a, int m, int n, floa
 // block.  The chunk is then decoded once, on scalars, and every tile load is a raw buffer load whose hardware range check
 // returns 0 for the lanes that fall outside the image (offset 0x80000000) or past Cout -- no predicated loads, i.e. no
 // branches whose joins make hipcc drain vmcnt(0) in front of the MFMA block.
-// BKT = k-chunk: 32, or 16 for the 128x128 tile (36.9 KB of LDS instead of 73.7: three resident blocks per CU instead of two, the
-// same trade the pointwise GEMM makes -- fewer MFMAs per barrier, but a third block to run while two wait)
 __device__ __forceinline__ float vmax_raw(float x, float y) {
   float r;
   asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
@@ -158,12 +156,6 @@ __device__ __forceinline__ float vmax_raw(float x, float y) {
 // part of the address in the buffer load's scalar offset, and the store to LDS needs no validity mask (act(0) = 0).
 // BF (with SIMPLE): the operands are rounded to bf16 on the way into LDS (80-byte rows: conflict-free ds_read_b128) and one
 // v_mfma_f32_16x16x32_bf16 per tile pair replaces the eight fp32 MFMAs of a 32-deep chunk; accumulation and epilogue stay fp32.
-// M32 (with SIMPLE, fp32, 64 x 64 wave tiles): v_mfma_f32_32x32x2_f32 instead of 16x16x4 -- the same FLOPs per cycle and the same
-// LDS words per FLOP (a ds_read_b128 still feeds 4 MFMAs: lane (l & 31, l >> 5) holds k = 4 (l >> 5) + s of an 8-deep step), but
-// half the MFMA instructions, each with a 64-cycle shadow: the per-chunk vector work (prologue activation, LDS staging) costs
-// less matrix time (profiles/r03e_ubench_mfma_valu.txt).  D layout: register v of lane l = out[co = 8 (v / 4) + 4 (l >> 5) +
-// v % 4][pixel = l & 31] -- again 4 consecutive output channels per lane and register quad.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 // XRED (with SIMPLE, 16x16x4 MFMAs): the split-K reduction inside the launch, through the L2 of ONE XCD.  Workgroups are dealt to
 // the 8 XCDs round-robin by linear id; the grid is 1-D and block L = 8 j + c is the j-th block of XCD c, which works on tile
 // c * xr_t8 + j / S, k split j % S: all S splits of a tile run on the same XCD, next to each other in time.  A block stores its
@@ -175,42 +167,31 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // (1, x, x^2) of its hardware XCC id x to the arrival word; the last block takes the fast path only if all S ids equal its own
 // (sum x = S m and sum x^2 = S m^2).  Otherwise it recomputes the S splits itself, in order, with the running sum parked in its
 // own slot -- the same additions in the same order, so even a misplaced tile is bitwise equal (counted in g_xred_fallbacks).
-// X3 (with SIMPLE, 32-deep chunks; dpmn_set_compute_dtype(2), common.h x3_split2t): both operands are split into three bf16 planes on
-// the way into LDS (80-byte rows per plane, the BF layout three times) and a tile pair costs six v_mfma_f32_16x16x32_bf16 per chunk
-// instead of eight v_mfma_f32_16x16x4_f32 -- 96 x 16 cycles against 128 x 32 per wave and chunk on the 128 x 128 tile.  The
-// accumulator layout is that of the fp32 path, so everything behind the k loop (split-K partials, epilogues, statistics) is shared.
-// 128 x 128: ONE LDS buffer (61 KB, two blocks per CU as the fp32 kernel): the split + store of chunk k + 1 sits between two
-// barriers while the other resident block multiplies; 64 x 64: both buffers (61 KB).
-template <int BM, int BN, int WM, int WN, bool UNI = false, int BKT = 32, bool SIMPLE = false, bool AFF = false, bool BF = false, bool M32 = false,
-          bool XRED = false, int X3 = 0>      // X3: 0 off, 1 = 80-byte LDS rows, 2 = 96-byte rows
+// X3 (with SIMPLE; dpmn_set_compute_dtype(2), common.h x3_split2t): both operands are split into three bf16 planes on the way into
+// LDS (96-byte rows per plane) and a tile pair costs six v_mfma_f32_16x16x32_bf16 per chunk instead of eight v_mfma_f32_16x16x4_f32
+// -- 96 x 16 cycles against 128 x 32 per wave and chunk on the 128 x 128 tile.  The accumulator layout is that of the fp32 path, so
+// everything behind the k loop (split-K partials, epilogues, statistics) is shared.  ONE LDS buffer (two blocks per CU as the fp32
+// kernel): the split + store of chunk k + 1 sits between two barriers while the other resident block multiplies.
+template <int BM, int BN, int WM, int WN, bool UNI = false, bool SIMPLE = false, bool AFF = false, bool BF = false, bool XRED = false,
+          bool X3 = false>
 __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
-  static_assert(!X3 || (SIMPLE && !BF && !M32 && !XRED && BKT == 32), "the bf16x3 variant exists for the SIMPLE path with 32-deep chunks");
-  static_assert(!XRED || (SIMPLE && !M32 && BKT == 32), "the in-L2 reduction exists for the SIMPLE path");
-  static_assert(!M32 || (SIMPLE && !BF && BKT == 32 && BM / WM == 64 && BN / WN == 64), "the 32x32x2 variant: fp32 SIMPLE path, 64 x 64 wave tiles");
-  static_assert(!BF || (SIMPLE && BKT == 32), "the bf16 variant exists for the SIMPLE path with 32-deep chunks");
+  static_assert(!X3 || (SIMPLE && !BF && !XRED), "the bf16x3 variant exists for the SIMPLE path");
+  static_assert(!XRED || SIMPLE, "the in-L2 reduction exists for the SIMPLE path");
+  static_assert(!BF || SIMPLE, "the bf16 variant exists for the SIMPLE path");
   static_assert(!SIMPLE || UNI, "SIMPLE is a refinement of the UNI path");
   static_assert(!AFF || SIMPLE, "AFF is a variant of the SIMPLE path");
-#ifndef DPMN_IGEMM_FENCE
-#define DPMN_IGEMM_FENCE 1
-#endif
-  constexpr bool SCHED_FENCE = DPMN_IGEMM_FENCE;
-#ifndef DPMN_IGEMM_ABLATE
-#define DPMN_IGEMM_ABLATE 0      // timing experiments only (tools/build_variants.sh): 1 no global loads, 2 no LDS stores, 4 no barrier, 8 no LDS reads
-#endif
-  constexpr int ABL = SIMPLE ? DPMN_IGEMM_ABLATE : 0;
   constexpr int MT = BM / WM / 16, NT = BN / WN / 16;
-  constexpr int TPR = BKT / 4, RPP = 256 / TPR;          // threads per tile row, tile rows per pass
+  constexpr int TPR = BK / 4, RPP = 256 / TPR;            // threads per tile row, tile rows per pass
   constexpr int APASS = BM / RPP, BPASS = (BN + RPP - 1) / RPP;
-  constexpr int BK = BKT, LDK = BKT + PAD;
   // bf16 row stride.  BF: 32 + 8 elements = 80 bytes.  X3: 32 + 16 = 96 bytes -- a ds_read_b128 is served in groups of 16 lanes
   // ({0-3, 12-15, 20-27}, ...: MI355X_MICROARCH.md, LDS): with 80-byte rows three of a group's sixteen 16-byte reads share a bank
   // quad with another lane (quad = 5 lr + kq mod 16) and every group takes two LDS cycles -- SQ_LDS_BANK_CONFLICT = 50 % of the
   // active LDS cycles (profiles/r06_pmc_sq.txt) -- while 96-byte rows (quad = 6 lr + kq mod 16) give sixteen different quads for
   // any row base.  The x3 kernels move 1.5 x the LDS bytes of the fp32 kernel in 0.375 x its MFMA time: the conflicts are not free there.
-  constexpr int LDKB = X3 == 2 ? BKT + 16 : BKT + 8;
+  constexpr int LDKB = X3 ? BK + 16 : BK + 8;
   constexpr bool B16 = BF || X3;                              // bf16 rows in LDS
   constexpr int NPL = X3 ? 3 : 1;                             // operand planes
-  constexpr int NBUF = (X3 && BM * BN > 64 * 64) ? 1 : 2;
+  constexpr int NBUF = X3 ? 1 : 2;
   constexpr int XPL = BM * LDKB, WPL = BN * LDKB;             // one bf16 plane (halves)
   typedef typename std::conditional<B16, unsigned short, float>::type lds_t;
   __shared__ __attribute__((aligned(16))) lds_t Xs[NBUF][NPL * BM * (B16 ? LDKB : LDK)];
@@ -435,13 +416,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
     // scalar, >= 0 (readfirstlane: keeps it in an SGPR -- a VGPR soffset makes hipcc emit a waterfall loop around every load)
     const int soff = __builtin_amdgcn_readfirstlane(((u_ky * a.dil_y * a.Win + u_kx * a.dil_x - minoff) * cs + u_c0 - s_segstart) * 4);
     const int sh = 31 - min(u_tap, 31);
-    if (ABL & 1) {
-#pragma unroll
-      for (int p = 0; p < APASS; ++p) xr[p] = make_float4(1.f, 1.f, 1.f, (float)(soff + sh));
-#pragma unroll
-      for (int p = 0; p < BPASS; ++p) wr[p] = make_float4(1.f, 1.f, 1.f, 1.f);
-      return;
-    }
 #pragma unroll
     for (int p = 0; p < APASS; ++p) {
       const unsigned oob = (nok[p] << sh) & 0x80000000u;
@@ -477,7 +451,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
         xr[p].z = vmax_raw(xr[p].z, sl * xr[p].z); xr[p].w = vmax_raw(xr[p].w, sl * xr[p].w);
       }
     }
-    if ((ABL & 2) && xr[0].w != 12345.f) return;
     if (AFF) {          // act(shift) is not 0: out-of-image taps are zeroed explicitly
 #pragma unroll
       for (int p = 0; p < APASS; ++p)
@@ -551,16 +524,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
   for (int i = 0; i < NT; ++i)
 #pragma unroll
     for (int j = 0; j < MT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  f32x16 acc32[2][2];
-  if constexpr (M32) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int v = 0; v < 16; ++v) acc32[i][j][v] = 0.f;
-  }
-  const int l31 = lane & 31, lh = lane >> 5;
 
   const int nk_all = a.Kp / BK;
   const int cps = (nk_all + a.ksplit - 1) / a.ksplit;          // chunks per split
@@ -585,18 +548,14 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
     }
   }
   __syncthreads();
-#ifndef DPMN_X3_DBG
-#define DPMN_X3_DBG 0      // debugging builds (tools/build_variants.sh): 1 = an extra barrier + LDS fence at the top of every chunk, 4 = no MFMAs behind the barrier
-#endif
   for (int kt = kt0; kt < nk; ++kt) {
     const int buf = NBUF == 2 ? (kt - kt0) & 1 : 0;
-    if (X3 && (DPMN_X3_DBG & 1)) { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __syncthreads(); }
     if (SIMPLE) gload_simple(min(kt + 1, nk - 1));
     else if (UNI) gload_uni(min(kt + 1, nk - 1) * BK);      // unconditional: the refill past the end re-reads the last chunk
     else if (kt + 1 < nk) gload((kt + 1) * BK);
     // hipcc otherwise sinks the buffer loads deep into the MFMA block (the last ones ~100 MFMAs down): they must be in
     // flight for the WHOLE block to cover HBM / L2 latency before sstore waits for them
-    if (UNI && SCHED_FENCE) __builtin_amdgcn_sched_barrier(0);
+    if (UNI) __builtin_amdgcn_sched_barrier(0);
     if constexpr (X3) {
       const lds_t* xa = &Xs[buf][(wm * (MT * 16) + lr) * LDKB + kq * 8];
       const lds_t* wa = &Ws[buf][(wn * (NT * 16) + lr) * LDKB + kq * 8];
@@ -633,23 +592,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
       for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int j = 0; j < MT; ++j) acc[i][j] = mfma16_bf16(wf[i], xf[j], acc[i][j]);
-    } else if constexpr (M32) {
-      const float* xa = reinterpret_cast<const float*>(&Xs[buf][0]) + (wm * 64 + l31) * LDK + lh * 4;
-      const float* wa = reinterpret_cast<const float*>(&Ws[buf][0]) + (wn * 64 + l31) * LDK + lh * 4;
-#pragma unroll
-      for (int kc = 0; kc < BK; kc += 8) {
-        f32x4 xf[2], wf[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) xf[j] = *reinterpret_cast<const f32x4*>(xa + j * 32 * LDK + kc);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) wf[i] = *reinterpret_cast<const f32x4*>(wa + i * 32 * LDK + kc);
-#pragma unroll
-        for (int s_ = 0; s_ < 4; ++s_)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc32[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[i][s_], xf[j][s_], acc32[i][j], 0, 0, 0);
-      }
     } else {
     const float* xa = reinterpret_cast<const float*>(&Xs[buf][0]) + (wm * (MT * 16) + lr) * LDK + kq * 4;
     const float* wa = reinterpret_cast<const float*>(&Ws[buf][0]) + (wn * (NT * 16) + lr) * LDK + kq * 4;
@@ -657,11 +599,9 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
     for (int kc = 0; kc < BK; kc += 16) {
       f32x4 xf[MT], wf[NT];
 #pragma unroll
-      for (int j = 0; j < MT; ++j)
-        if (ABL & 8) xf[j] = (f32x4){1.f, (float)kt, 1.f, 1.f}; else xf[j] = *reinterpret_cast<const f32x4*>(xa + j * 16 * LDK + kc);
+      for (int j = 0; j < MT; ++j) xf[j] = *reinterpret_cast<const f32x4*>(xa + j * 16 * LDK + kc);
 #pragma unroll
-      for (int i = 0; i < NT; ++i)
-        if (ABL & 8) wf[i] = (f32x4){1.f, (float)kt, 1.f, 1.f}; else wf[i] = *reinterpret_cast<const f32x4*>(wa + i * 16 * LDK + kc);
+      for (int i = 0; i < NT; ++i) wf[i] = *reinterpret_cast<const f32x4*>(wa + i * 16 * LDK + kc);
 #pragma unroll
       for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -670,12 +610,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
           for (int j = 0; j < MT; ++j) acc[i][j] = mfma16(wf[i][s], xf[j][s], acc[i][j]);
     }
     }
-    if (X3 && (DPMN_X3_DBG & 4)) __builtin_amdgcn_sched_barrier(0);
     if (NBUF == 1) __syncthreads();                           // single buffer: every wave has read chunk kt before it is overwritten
-    if (X3 && (DPMN_X3_DBG & 4)) __builtin_amdgcn_sched_barrier(0);
     if (SIMPLE) sstore_simple(NBUF == 2 ? buf ^ 1 : 0);
     else if (UNI || kt + 1 < nk) sstore(buf ^ 1);
-    if (!(ABL & 4)) __syncthreads();
+    __syncthreads();
   }
   if constexpr (!XRED) break;
   else {
@@ -797,51 +735,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
   }
   }
 
-  if constexpr (M32) {
-    // lane holds out[pixel m = .. + j * 32 + (l & 31)][co = .. + i * 32 + 8 g + 4 (l >> 5) + r], r = register 4 g + r of tile (i, j)
-    float ssum[8][4], ssq[8][4];
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { ssum[q][r] = 0.f; ssq[q][r] = 0.f; }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int m = m_blk + wm * 64 + j * 32 + l31;
-      if (m >= M) continue;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int n = n_blk + wn * 64 + i * 32 + g * 8 + lh * 4;
-          if (a.ksplit > 1) {
-            if (n < a.npad)
-              *reinterpret_cast<float4*>(ph.partial + ((size_t)zsplit * M + m) * a.npad + n) =
-                  make_float4(acc32[i][j][4 * g], acc32[i][j][4 * g + 1], acc32[i][j][4 * g + 2], acc32[i][j][4 * g + 3]);
-          } else if (n < a.Cout) {
-            float v[4] = {acc32[i][j][4 * g], acc32[i][j][4 * g + 1], acc32[i][j][4 * g + 2], acc32[i][j][4 * g + 3]};
-            conv_store(a, m, n, v, ssum[i * 4 + g], ssq[i * 4 + g], ph.ooy, ph.oox);
-          }
-        }
-    }
-    if (a.stats && a.ksplit <= 1) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int n = n_blk + wn * 64 + (q >> 2) * 32 + (q & 3) * 8 + lh * 4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float s_ = ssum[q][r], q_ = ssq[q][r];
-#pragma unroll
-          for (int o = 1; o < 32; o <<= 1) { s_ += xshfl_v(s_, o); q_ += xshfl_v(q_, o); }
-          if (l31 == 0 && n + r < a.Cout) {
-            double* st = reinterpret_cast<double*>(a.stats) + (size_t)(bx % STAT_SLOTS) * 2 * a.Cout;
-            atomicAdd(st + n + r, (double)(s_));
-            atomicAdd(st + a.Cout + n + r, (double)(q_));
-          }
-        }
-      }
-    }
-    return;
-  }
   // ---- epilogue: lane holds out[pixel m = .. + (l&15)][co = .. + (l>>4)*4 + r]
   if (!XRED && a.ksplit > 1) {
 #pragma unroll
@@ -904,34 +797,24 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a) {
 // BF: bf16 operands (halo tile and weight slices rounded on the way into LDS, 80-byte rows), one v_mfma_f32_16x16x32_bf16 per tap
 // and tile pair instead of eight fp32 MFMAs; fp32 accumulation and epilogue.
 // X3: "f32 via bf16x3" (common.h x3_split2t): halo tile and weight slices as three bf16 planes each, six bf16 MFMAs per tap and tile pair.
-// NW waves per block (4, or 8 for the 16-row tile of mode 2: the weight slice of a tap is split once per BLOCK, so twice the pixels per
-// block halve the split work per MFMA; LDS for one block per CU, its eight waves = the two blocks of four it replaces) and R96: 96-byte
-// LDS rows (conflict-free ds_read_b128 at any pixel base, conv_igemm_body) where one block per CU leaves the room.
-template <int KS, int BN, int TH, bool BF = false, bool X3 = false, int NW = 4, bool R96 = false>    // TH x 16 output pixels per block: TH / NW rows per wave
+template <int KS, int BN, int TH, bool BF = false, bool X3 = false>    // TH x 16 output pixels per block: TH / 4 rows per wave
 __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
   static_assert(!(BF && X3), "one operand format");
-  constexpr int NTH = NW * 64, RPS = NTH / 8;            // threads; pixel rows (8 float4 each) staged per pass
-  static_assert(!R96 || X3, "96-byte rows: the bf16x3 variant");
-  constexpr int LDH = R96 ? (BK + 16) / 2 : (BF || X3) ? (BK + 8) / 2 : LDK;   // LDS row stride in FLOAT units (bf16 rows: 40 halves = 20 floats = 80 bytes; 96-byte rows -- conflict-free
+  constexpr int NTH = 256, RPS = NTH / 8;                // threads; pixel rows (8 float4 each) staged per pass
+  constexpr int LDH = (BF || X3) ? (BK + 8) / 2 : LDK;   // LDS row stride in FLOAT units (bf16 rows: 40 halves = 20 floats = 80 bytes; 96-byte rows -- conflict-free
                                                          // ds_read_b128, conv_igemm_body -- cost the second resident block here: 77.6 vs 54.4 us per launch, measured)
   constexpr int NPL = X3 ? 3 : 1;                        // operand planes
   constexpr int TW = 16, HH = TH + KS - 1, HW_ = TW + KS - 1, NPX = HH * HW_;
-  constexpr int NT = BN / 16, T = KS * KS, MR = TH / NW;
-  constexpr bool PREFETCH = false;
-  static_assert(!(BF || X3) || !PREFETCH, "bf16 variants: direct staging only");   // halo staged directly into ONE LDS buffer: 3 blocks per CU hide the staging latency
-                                     // (measured: tatt 3x3 60.6 -> 55.3 us, en2b 118 -> 84 us vs the register-prefetch variant;
-                                     //  weights straight from L1/L2 to registers instead of LDS measured 76 / 146 us: rejected)
-  constexpr int HBUF = PREFETCH ? 2 : 1;
-  constexpr int HV = PREFETCH ? (NPX * 8 + NTH - 1) / NTH : 1;   // halo float4 per thread held in registers
+  constexpr int NT = BN / 16, T = KS * KS, MR = TH / 4;
+  // halo staged directly into ONE LDS buffer: 3 blocks per CU hide the staging latency (measured: tatt 3x3 60.6 -> 55.3 us, en2b
+  // 118 -> 84 us vs the register-prefetch variant; weights straight from L1/L2 to registers instead of LDS measured 76 / 146 us: rejected)
   constexpr int WV = (BN * 8 + NTH - 1) / NTH;               // weight float4 per thread and tap
-#ifndef DPMN_HALO_TPS
-#define DPMN_HALO_TPS 1                                   // 3: the three taps of a kernel row share one weight stage and ONE barrier
-#endif
-  constexpr int TPS = (KS == 3 && !BF && !X3 && TH == 4) ? DPMN_HALO_TPS : 1;      // taps per weight stage
-  static_assert(T % TPS == 0, "whole stages");
+  // taps per weight stage: 1 (three taps of a kernel row per stage and barrier measured slower).  The one-tap stage loops
+  // stay: without them hipcc assigns registers and branches differently in the 9 x 9 and 16-channel kernels
+  constexpr int TPS = 1;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* halo = smem;                                    // [HBUF][NPL][NPX][LDK]
-  float* Wt = smem + HBUF * NPL * NPX * LDH;             // [2][TPS][NPL][BN][LDK]
+  float* halo = smem;                                    // [NPL][NPX][LDK]
+  float* Wt = smem + NPL * NPX * LDH;                    // [2][TPS][NPL][BN][LDK]
   constexpr int HPL = NPX * LDH, WPLH = BN * LDH;        // plane strides (float units)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -943,7 +826,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
   const int c01 = a.cseg[0] + a.cseg[1];
   const int nchunks = a.cin / BK;
 
-  float4 hraw[HV], wraw[TPS * WV];
+  float4 wraw[TPS * WV];
   // one staged float4 (4 consecutive k of one row) -> LDS, fp32 or rounded to bf16
   auto put4 = [&](float* base, int row, int c4, const float4& v, int plane) {
     if constexpr (X3) {
@@ -987,7 +870,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
   // image: no predicated load, no branch, so the HVD loads are in flight together instead of one wait per element), then
   // transformed and stored.  256 % 8 == 0: every element of a thread has the same channel quad, hence one affine pair.
   constexpr int HVD = (NPX * 8 + NTH - 1) / NTH;
-  constexpr bool HALO_BUF = TH == 4 || NW == 8;      // (8-row tiles, 6-12 loads per thread: measured slower than the per-element loop)
+  constexpr bool HALO_BUF = TH == 4;      // (8-row tiles, 6-12 loads per thread: measured slower than the per-element loop)
   auto stage_halo_direct = [&](int chunk) {
     if constexpr (!HALO_BUF) {
       for (int i = tid; i < NPX * 8; i += NTH)
@@ -1026,20 +909,6 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
       }
       if (!((inb >> v) & 1u)) val = make_float4(0.f, 0.f, 0.f, 0.f);      // padding stays exactly 0 after the transform
       if (HVD * RPS == NPX || px < NPX) put4(halo, px, (tid & 7) * 4, val, HPL);
-    }
-  };
-  auto issue_halo = [&](int chunk) {
-#pragma unroll
-    for (int v = 0; v < HV; ++v) {
-      const int i = tid + v * NTH;
-      hraw[v] = (i < NPX * 8) ? halo_elem(chunk, i) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  auto commit_halo = [&](int buf) {
-#pragma unroll
-    for (int v = 0; v < HV; ++v) {
-      const int i = tid + v * NTH;
-      if (i < NPX * 8) put4(halo + (size_t)buf * NPX * LDH, i >> 3, (i & 7) * 4, hraw[v], HPL);
     }
   };
   // weight slice of one (chunk, tap): raw buffer loads -- per-thread byte offsets are loop invariants, the (chunk, tap) part
@@ -1090,24 +959,18 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
 #pragma unroll
     for (int j = 0; j < MR; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  if (PREFETCH) { issue_halo(0); commit_halo(0); }
   issue_w(0, 0);
   commit_w(0);
   __syncthreads();
   int wb = 0;
   for (int chunk = 0; chunk < nchunks; ++chunk) {
-    const int hb = PREFETCH ? (chunk & 1) : 0;
     const bool more = chunk + 1 < nchunks;
-    if (PREFETCH) {
-      if (more) issue_halo(chunk + 1);
-    } else {
-      stage_halo_direct(chunk);     // all reads of the previous chunk finished at the last barrier
-      __syncthreads();
-    }
+    stage_halo_direct(chunk);     // all reads of the previous chunk finished at the last barrier
+    __syncthreads();
     // 3x3: the nine taps fully unrolled -- (ky, kx), the halo offsets of the B-operand reads and the weight-buffer parity become
     // immediates instead of per-tap scalar / vector arithmetic (81 VALU + 81 SALU per 64-MFMA tap before; the vector ALU shares
     // its issue with the fp32 matrix pipe).  T = 9 is odd, so the buffer parity of tap t is (chunk + t) & 1.
-    const float* hp0 = halo + (size_t)hb * NPX * LDH + ((MR * wave) * HW_ + lr) * LDH + kq * 4;      // (bf16: 8 halves = 4 float units)
+    const float* hp0 = halo + ((MR * wave) * HW_ + lr) * LDH + kq * 4;      // (bf16: 8 halves = 4 float units)
     const float* wp0 = Wt + lr * LDH + kq * 4;
     constexpr int NS = T / TPS;
     constexpr int TAP_UNROLL = KS == 3 ? NS : 1;
@@ -1169,7 +1032,6 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
       }
       }
       if (!lastt || more) commit_w(wb ^ 1);
-      if (PREFETCH && lastt && more) commit_halo(hb ^ 1);
       __syncthreads();
       wb ^= 1;
     }
@@ -1218,10 +1080,6 @@ __global__ __launch_bounds__(256) void k_conv_halo(ConvArgs a) {
 template <int KS, int BN, int TH>
 __global__ __launch_bounds__(256, 2) void k_conv_halo_x3(ConvArgs a) {
   conv_halo_body<KS, BN, TH, false, true>(a);
-}
-template <int KS, int BN>
-__global__ __launch_bounds__(512, 1) void k_conv_halo_x3w(ConvArgs a) {      // 16 x 16 pixels, eight waves, 96-byte rows
-  conv_halo_body<KS, BN, 16, false, true, 8, true>(a);
 }
 
 static inline double conv_flops(const ConvArgs& a) {

@@ -837,10 +837,9 @@ static int launch_wgrad(const dpmn_conv_desc* d, const float* dy, float* dw, int
   if (excl_slots > 0 || plan_only) {
     // no atomic epilogue to amortise: split for parallelism (~768 blocks), bounded by the slot round trip (every split writes
     // and the unpack reads one Cout x Kp slot: <= 32 MB in flight, but never fewer than 2 splits of a large M)
-    static const int want_blocks = getenv("DPMN_WG_BLOCKS") ? atoi(getenv("DPMN_WG_BLOCKS")) : 768;
-    static const long cap_bytes = (long)(getenv("DPMN_WG_CAP_MB") ? atoi(getenv("DPMN_WG_CAP_MB")) : 32) << 20;
+    const long cap_bytes = 32L << 20;
     const long slot_bytes = (long)a.Cout * s_co * 4;
-    long sp = cdiv(want_blocks, tiles);
+    long sp = cdiv(768, tiles);
     const long by_cap = cap_bytes / slot_bytes < 2 ? 2 : cap_bytes / slot_bytes;
     if (sp > by_cap) sp = by_cap;
     if (sp > M / 64) sp = M / 64;
@@ -859,16 +858,16 @@ static int launch_wgrad(const dpmn_conv_desc* d, const float* dy, float* dw, int
   // 2 M Cout K FLOPs; bytes: the input and dY read once, one (Cout, Kp) partial tile set written per split (exclusive slots)
   ProfScope prof(PT_CONV_WGRAD, as_stream(stream), 2.0 * M * (double)a.Cout * a.K,
                  4.0 * ((double)a.B * a.Hin * a.Win * cin + (double)a.B * a.Hout * a.Wout * a.Cout + (double)(a.excl ? splits : 1) * a.Cout * a.K));
-  static const int p2_on = getenv("DPMN_WG_P2") ? atoi(getenv("DPMN_WG_P2")) : 1;
   auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-  bool p2 = p2_on && pow2(a.Hp) && pow2(a.Wp) && (a.pro_act == ACT_NONE || a.pro_act == ACT_RELU || a.pro_act == ACT_LEAKY02) &&
+  bool p2 = pow2(a.Hp) && pow2(a.Wp) && (a.pro_act == ACT_NONE || a.pro_act == ACT_RELU || a.pro_act == ACT_LEAKY02) &&
             (size_t)a.B * a.Hout * a.Wout * a.Cout * 4 < (1ull << 31);
   for (int s = 0; s < 3; ++s) p2 = p2 && (size_t)a.B * a.Hin * a.Win * (a.cseg[s] > 0 ? a.cseg[s] : 1) * 4 < (1ull << 31);
   if (p2) {
     for (a.lgW = 0; (1 << a.lgW) < a.Wp; ++a.lgW) {}
     for (a.lgHW = 0; (1 << a.lgHW) < a.Hp * a.Wp; ++a.lgHW) {}
-    if (x3_on(16) && bn != 16 && dpmn_conv::x3_wgrad_ok(a, bn, bk)) (void)dpmn_conv::x3_launch_wgrad(a, bn, bk, grid, as_stream(stream));
-    else if (bn == 16) hipLaunchKernelGGL((k_conv_wgrad<16, 256, true>), grid, dim3(256), 0, as_stream(stream), a);
+    if (x3_on(16) && bn != 16 && dpmn_conv::x3_wgrad_ok(a, bn, bk)) {
+      if (dpmn_conv::x3_launch_wgrad(a, bn, bk, grid, as_stream(stream)) != 0) return dpmn_set_error(DPMN_ERR_LAUNCH, "conv2d_wgrad: bf16x3 launch failed");
+    } else if (bn == 16) hipLaunchKernelGGL((k_conv_wgrad<16, 256, true>), grid, dim3(256), 0, as_stream(stream), a);
     else if (bn == 64 && bk == 128) hipLaunchKernelGGL((k_conv_wgrad<64, 128, true>), grid, dim3(256), 0, as_stream(stream), a);
     else if (bn == 64) hipLaunchKernelGGL((k_conv_wgrad<64, 256, true>), grid, dim3(256), 0, as_stream(stream), a);
     else hipLaunchKernelGGL((k_conv_wgrad<128, 128, true>), grid, dim3(256), 0, as_stream(stream), a);
@@ -997,7 +996,7 @@ int dpmn_affine_act_bwd_stats_f32(const float* dA, const float* r, const float* 
   DPMN_REQUIRE(dA && r && G && mean && rstd && sums && pixels > 0, "affine_act_bwd_stats: bad arguments");
   DPMN_REQUIRE(C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0, "affine_act_bwd_stats: C/4 must divide 256");
   DPMN_REQUIRE(act == ACT_NONE || act == ACT_RELU || act == ACT_LEAKY02 || act == ACT_LEAKY001, "affine_act_bwd_stats: piecewise-linear activations");
-  static const long aab_blocks = getenv("DPMN_AAB_BLOCKS") ? atol(getenv("DPMN_AAB_BLOCKS")) : 512;      // (2048: 28.1 us per launch on average, 512: 25.0 -- same-address fp64 atomics)
+  const long aab_blocks = 512;      // (2048: 28.1 us per launch on average, 512: 25.0 -- same-address fp64 atomics)
   int ppb = (int)((pixels + aab_blocks - 1) / aab_blocks);       // <= 2048 blocks: one fp64 atomic pair per channel and block
   const int pl = 256 / (C / 4);
   if (ppb < 8 * pl) ppb = 8 * pl;                // two 4-pixel rounds per thread at least

@@ -217,13 +217,13 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_x3(WgArgs a) {
 
 namespace dpmn_conv {
 bool x3_wgrad_ok(const WgArgs& a, int bn, int bk) {      // (the caller established the power-of-two fast path)
-  static const int t64 = getenv("DPMN_X3_WGRAD64") ? atoi(getenv("DPMN_X3_WGRAD64")) : 1;
-  return a.pix_per_block % 32 == 0 && ((bn == 128 && bk == 128) || (t64 && bn == 64 && (bk == 128 || bk == 256)));
+  return a.pix_per_block % 32 == 0 && ((bn == 128 && bk == 128) || (bn == 64 && (bk == 128 || bk == 256)));
 }
 int x3_launch_wgrad(const WgArgs& a, int bn, int bk, dim3 grid, hipStream_t st) {
-  if (bn == 128) hipLaunchKernelGGL((k_conv_wgrad_x3<128, 128>), grid, dim3(256), 0, st, a);
-  else if (bk == 256) hipLaunchKernelGGL((k_conv_wgrad_x3<64, 256>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((k_conv_wgrad_x3<64, 128>), grid, dim3(256), 0, st, a);
+  if (bn == 128 && bk == 128) hipLaunchKernelGGL((k_conv_wgrad_x3<128, 128>), grid, dim3(256), 0, st, a);
+  else if (bn == 64 && bk == 256) hipLaunchKernelGGL((k_conv_wgrad_x3<64, 256>), grid, dim3(256), 0, st, a);
+  else if (bn == 64 && bk == 128) hipLaunchKernelGGL((k_conv_wgrad_x3<64, 128>), grid, dim3(256), 0, st, a);
+  else return -1;
   return 0;
 }
 }  // namespace dpmn_conv

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Timing-experiment builds of one source file: tools/build_variants.sh conv "-DDPMN_IGEMM_ABLATE=1" v1  ->  tools/variants/libdpmn_v1.so
+# Timing-experiment builds of one source file: tools/build_variants.sh attn_fused "-DFA_TIMING=1" v1  ->  tools/variants/libdpmn_v1.so
 # (the other objects come from the normal build; select with DPMN_HIP_LIB=tools/variants/libdpmn_v1.so)
 set -e
 cd "$(dirname "$0")/../dpmn_amd/csrc"
