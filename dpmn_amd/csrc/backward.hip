@@ -6,7 +6,6 @@
 //   * k_act_bwd        dpre = dy * act'(pre)  (GELU / ReLU / LeakyReLU / mish)
 //   * k_image_loss_*   ImageLoss = MSE + L1 of gradient-magnitude maps (loss/image_loss.py:15-43), forward + backward
 // Data-gradients of linears / convs reuse the forward GEMM / implicit-GEMM kernels with transposed weights.
-#include <cstdlib>
 #include <vector>
 #include "common.h"
 
@@ -735,13 +734,17 @@ __global__ void k_image_loss_bwd(const float* __restrict__ o, long o_stride, con
 
 extern "C" {
 
+// true: the two (dw, db) destination pairs share a tensor (db may be null)
+static bool same_dest(const float* dw_a, const float* db_a, const float* dw_b, const float* db_b) {
+  return dw_a == dw_b || (db_b && (db_a == db_b || dw_a == db_b)) || (db_a && db_a == dw_b);
+}
+
 static void tn_plan(int M, int N, int K, int* splits_out, int* rows_out) {
   const int tiles = cdiv(N, 96) * cdiv(K, 96);
-  static const int want = getenv("DPMN_TN_BLOCKS") ? atoi(getenv("DPMN_TN_BLOCKS")) : 256;       // experiment knob
   // (one block per CU and product: since the products of a Swin block share launches (dpmn_gemm_tn_group_f32) the CUs hold blocks of
   //  several products anyway, and fewer splits are fewer partial slabs to write and re-read -- 512 blocks for the 4-tile shapes fc1 / fc2
   //  were 45.0 against 48.2 us per product launched alone, but 23.56 against 23.12 ms per training step grouped; 128: 23.22, 64: 24.14)
-  int splits = cdiv(want, tiles);
+  int splits = cdiv(256, tiles);
   int rows = cdiv(cdiv(M, splits), 32) * 32;      // (multiples of 32: the LDS kernel's chunk; of 4: an MFMA step of the register kernel)
   if (rows < 32) rows = 32;
   *splits_out = cdiv(M, rows);
@@ -761,9 +764,8 @@ static int gemm_tn_impl(const float* dy, const float* x, float* dw, float* db, i
   float* part = (ws && ws_bytes >= need && (splits > 1 || defer)) ? ws : nullptr;      // (deferred: also a single split goes through the reduce)
   // operands straight from global memory into the MFMA registers when a wave's 48 columns tile N and K (every Linear of the
   // PGRM block: 96 / 192 / 384) and the byte offsets fit the buffer instructions
-  static const int reg_on = getenv("DPMN_TN_REG") ? atoi(getenv("DPMN_TN_REG")) : 1;
   ProfScope prof(PT_GEMM_TN, as_stream(stream), 2.0 * M * (double)N * K, 4.0 * ((double)M * N + (double)M * K + (double)splits * ((double)N * K + N)));
-  const bool reg_ok = reg_on && part && N % 48 == 0 && K % 48 == 0 && (size_t)rows * (N > K ? N : K) * 4 < (1ull << 31);
+  const bool reg_ok = part && N % 48 == 0 && K % 48 == 0 && (size_t)rows * (N > K ? N : K) * 4 < (1ull << 31);
   if (reg_ok && x3_on(64))       // mode 2: the same partials on six bf16 MFMAs per tile (gemm_tn_x3.hip)
     dpmn_gemm::x3_launch_tn(dy, x, M, N, K, rows, db, part, grid, as_stream(stream));
   else if (reg_ok)
@@ -793,8 +795,6 @@ int dpmn_gemm_tn_f32(const float* dy, const float* x, float* dw, float* db, int 
 // operands-in-registers kernel and has its workspace in ONE launch (k_gemm_tn_reg_multi; up to 8 per launch)
 int dpmn_gemm_tn_group_f32(const dpmn_tn_item* items, int n, dpmn_stream_t stream) {
   DPMN_REQUIRE(items && n >= 0, "gemm_tn_group: bad arguments");
-  static const int reg_on = getenv("DPMN_TN_REG") ? atoi(getenv("DPMN_TN_REG")) : 1;
-  static const int group_on = getenv("DPMN_TN_GROUP") ? atoi(getenv("DPMN_TN_GROUP")) : 1;
   dpmn_gemm::TnGroup g{};
   int idx[8], splits_of[8];
   double flops = 0.0, bytes = 0.0;
@@ -824,9 +824,16 @@ int dpmn_gemm_tn_group_f32(const dpmn_tn_item* items, int n, dpmn_stream_t strea
     int splits, rows;
     tn_plan(t.M, t.N, t.K, &splits, &rows);
     const size_t need = (size_t)splits * ((size_t)t.N * t.K + t.N) * sizeof(float);
-    const bool reg_ok = group_on && reg_on && t.ws && t.ws_bytes >= need && splits > 1 && t.N % 48 == 0 && t.K % 48 == 0 &&
+    const bool reg_ok = t.ws && t.ws_bytes >= need && splits > 1 && t.N % 48 == 0 && t.K % 48 == 0 &&
                         (size_t)rows * (t.N > t.K ? t.N : t.K) * 4 < (1ull << 31);
     if (!reg_ok) {
+      // it runs at once: a pending product that adds into the same tensor goes out first, so the sums stay in array order
+      for (int j = 0; j < g.n; ++j)
+        if (same_dest(items[idx[j]].dw, items[idx[j]].db, t.dw, t.db)) {
+          const int rc = flush();
+          if (rc != DPMN_OK) return rc;
+          break;
+        }
       const int rc = gemm_tn_impl(t.dy, t.x, t.dw, t.db, t.M, t.N, t.K, t.ws, t.ws_bytes, nullptr, stream);
       if (rc != DPMN_OK) return rc;
       continue;
@@ -862,7 +869,6 @@ int dpmn_gemm_tn_partial_f32(const float* dy, const float* x, float* dw, float* 
 
 int dpmn_tn_reduce_multi_f32(const dpmn_tn_pending* pending, int n, dpmn_stream_t stream) {
   DPMN_REQUIRE(pending && n >= 0, "tn_reduce_multi: bad arguments");
-  static const bool tn_vec = !(getenv("DPMN_TN_REDUCE_VEC") && atoi(getenv("DPMN_TN_REDUCE_VEC")) == 0);
   int i0 = 0;
   while (i0 < n) {
     // one launch = up to 16 descriptors with pairwise DIFFERENT destinations (two sums into one tensor inside a launch would race:
@@ -873,11 +879,11 @@ int dpmn_tn_reduce_multi_f32(const dpmn_tn_pending* pending, int n, dpmn_stream_
       const dpmn_tn_pending& d = pending[i0 + cnt];
       bool clash = false;
       for (int j = 0; j < cnt && !clash; ++j)
-        clash = m.d[j].dw == d.dw || (d.db && (m.d[j].db == d.db || m.d[j].dw == d.db)) || (m.d[j].db && m.d[j].db == d.dw);
+        clash = same_dest(m.d[j].dw, m.d[j].db, d.dw, d.db);
       if (clash) break;
       m.d[cnt] = d;
       m.first_block[cnt] = nb;
-      const bool vec = tn_vec && d.NK % 4 == 0 && d.N % 4 == 0 && ((uintptr_t)d.part & 15) == 0 && ((uintptr_t)d.dw & 15) == 0 &&
+      const bool vec = d.NK % 4 == 0 && d.N % 4 == 0 && ((uintptr_t)d.part & 15) == 0 && ((uintptr_t)d.dw & 15) == 0 &&
                        (!d.db || ((uintptr_t)d.db & 15) == 0);
       if (vec) m.vec |= 1u << cnt;
       nb += cdiv(d.NK + (d.db ? d.N : 0), vec ? 256 : 64);
@@ -962,28 +968,20 @@ static int layernorm_bwd_impl(const float* x, const float* dy, const float* gamm
   DPMN_REQUIRE(!dr.out2 || ((C == 96 || C == 192) && dr.row_len > 0 && dr.p_elem >= 0.f && dr.p_elem < 1.f && dr.p_row >= 0.f && dr.p_row < 1.f),
                "layernorm_bwd: the masked second output needs C = 96 / 192 and drop rates in [0, 1)");
   DPMN_REQUIRE(!part || part_bytes >= (size_t)512 * 2 * C * sizeof(float), "layernorm_bwd_det: workspace of 512 * 2 C floats");
-  // every block ends with 2*C same-address atomics (dgamma, dbeta), which serialise: few, fat blocks (4 rows in flight per
-  // 32-thread group).  In-pipeline sweep at M = 49152: 256 blocks 46.6 us, 512: 36.9, 1024: 41.9, 2048: 59.9
-  static const long cap = getenv("DPMN_LNB_BLOCKS") ? atol(getenv("DPMN_LNB_BLOCKS")) : 512;
-  const unsigned blocks = (unsigned)(M / 8 < cap ? (M + 7) / 8 : cap);
-  unsigned nblk = blocks;
-  static const int v4 = getenv("DPMN_LNB_V4") ? atoi(getenv("DPMN_LNB_V4")) : 1;
+  unsigned nblk;
   ProfScope prof(PT_LN_BWD, as_stream(stream), 0.0, 4.0 * (accumulate_dx ? 4 : 3) * (double)M * C);
-  if ((C == 96 || C == 192) && (v4 || dr.out2)) {
+  if (C == 96 || C == 192) {
     // in-pipeline sweep of the vector kernel at M = 49152: 256 blocks 20.2 us, 384: 21.2, 512: 24.3, 768: 27.6, 1024: 33.3
     // (the scalar kernel it replaces: 36.8 us) -- one block per CU, the same-address dgamma / dbeta atomics set the slope
-    static const long cap4 = getenv("DPMN_LNB_BLOCKS") ? atol(getenv("DPMN_LNB_BLOCKS")) : 256;
-    const unsigned b4 = (unsigned)(M / 32 < cap4 ? (M + 31) / 32 : cap4);
-    if (C == 96) hipLaunchKernelGGL((k_ln_bwd_v4<96>), dim3(b4), dim3(256), 0, as_stream(stream), x, dy, gamma, eps, dx, accumulate_dx, dgamma, dbeta, M, part, dr);
-    else hipLaunchKernelGGL((k_ln_bwd_v4<192>), dim3(b4), dim3(256), 0, as_stream(stream), x, dy, gamma, eps, dx, accumulate_dx, dgamma, dbeta, M, part, dr);
-    nblk = b4;
-  } else if (C == 96)
-    hipLaunchKernelGGL((k_ln_bwd<96>), dim3(blocks), dim3(256), 0, as_stream(stream), x, dy, gamma, eps, dx, accumulate_dx, dgamma, dbeta, M, part);
-  else if (C == 192)
-    hipLaunchKernelGGL((k_ln_bwd<192>), dim3(blocks), dim3(256), 0, as_stream(stream), x, dy, gamma, eps, dx, accumulate_dx, dgamma, dbeta, M, part);
-  else if (C == 64)
-    hipLaunchKernelGGL((k_ln_bwd<64>), dim3(blocks), dim3(256), 0, as_stream(stream), x, dy, gamma, eps, dx, accumulate_dx, dgamma, dbeta, M, part);
-  else
+    nblk = (unsigned)(M / 32 < 256 ? (M + 31) / 32 : 256);
+    if (C == 96) hipLaunchKernelGGL((k_ln_bwd_v4<96>), dim3(nblk), dim3(256), 0, as_stream(stream), x, dy, gamma, eps, dx, accumulate_dx, dgamma, dbeta, M, part, dr);
+    else hipLaunchKernelGGL((k_ln_bwd_v4<192>), dim3(nblk), dim3(256), 0, as_stream(stream), x, dy, gamma, eps, dx, accumulate_dx, dgamma, dbeta, M, part, dr);
+  } else if (C == 64) {
+    // every block ends with 2*C same-address atomics (dgamma, dbeta), which serialise: few, fat blocks (4 rows in flight per
+    // 32-thread group).  In-pipeline sweep at M = 49152: 256 blocks 46.6 us, 512: 36.9, 1024: 41.9, 2048: 59.9
+    nblk = (unsigned)(M / 8 < 512 ? (M + 7) / 8 : 512);
+    hipLaunchKernelGGL((k_ln_bwd<64>), dim3(nblk), dim3(256), 0, as_stream(stream), x, dy, gamma, eps, dx, accumulate_dx, dgamma, dbeta, M, part);
+  } else
     return dpmn_set_error(DPMN_ERR_ARG, "layernorm_bwd: C must be 64, 96 or 192");
   DPMN_CHECK_LAUNCH();
   if (part) {      // the blocks' [dgamma | dbeta] rows, added in block order (no atomics: bitwise reproducible)

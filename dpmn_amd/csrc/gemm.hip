@@ -26,10 +26,8 @@ namespace {
 // the way from registers to the LDS tile.  Two barriers per tile, 3 blocks per CU (51 KB LDS at K=96)
 // so one block's VALU prologue/epilogue overlaps the other's MFMAs.
 // Block: 256 threads; waves 2(m: 16 tokens) x 2(n: 48 features): acc[3 n-tiles][1 m-tile].
+// (One X buffer and the second barrier: measured 5-8 % faster than two X buffers at 2 x 64 KB per CU.)
 constexpr int WS_BM = 32, WS_BN = 96;
-#ifndef WSTAT_NBUF
-#define WSTAT_NBUF 1   // single X buffer + second barrier: 51 KB LDS at K = 96 -> 3 blocks per CU (measured 5-8 % faster than 2 x 64 KB)
-#endif
 
 // EPI (with FULL): 0 = the generic epilogue above (every option a run-time branch); 1 = (bias), 2 = (bias) + GELU, 3 / 5 = (bias) + two / one residuals, 4 = (bias) + GELU column sums as
 // straight-line code: three unconditional float4 stores per lane.  With no branch between a tile's loads, its stores and
@@ -81,8 +79,8 @@ __global__ __launch_bounds__(TH) void k_gemm_wstat(const float* __restrict__ x, 
   constexpr int NRAW = (PRO == PRO_SKSEL) ? 4 : (PRO == PRO_ADD ? 2 : 1);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Ws = smem;                       // [BN][LDK]
-  float* Xs = Ws + BN * LDK;              // [2][BM][LDK]
-  float* red = Xs + WSTAT_NBUF * BM * LDK;   // [4][BN] colsum scratch
+  float* Xs = Ws + BN * LDK;              // [BM][LDK]
+  float* red = Xs + BM * LDK;             // [4][BN] colsum scratch
   float* lng = red + (TH / 64) * BN;      // [K] LayerNorm gamma, [K] beta   (red: one row of BN column sums per wave)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -142,8 +140,8 @@ __global__ __launch_bounds__(TH) void k_gemm_wstat(const float* __restrict__ x, 
       }
     }
   };
-  auto commit = [&](float4 (&raw)[NRAW][VPT], int tile, int buf) {
-    float* dst = Xs + (size_t)(WSTAT_NBUF == 1 ? 0 : buf) * BM * LDK + srow * LDK + scol;
+  auto commit = [&](float4 (&raw)[NRAW][VPT], int tile) {
+    float* dst = Xs + srow * LDK + scol;
     float vals[VPT * 4];
     if (PRO == PRO_SKSEL) {
       const int m = tile * BM + srow;
@@ -205,33 +203,21 @@ __global__ __launch_bounds__(TH) void k_gemm_wstat(const float* __restrict__ x, 
   }
   __syncthreads();                       // Ws / lng visible
   if (FULL) {
-    commit(rawA, tile, 0);
+    commit(rawA, tile);
     issue(rawA, min(tile + 2 * stride, tiles - 1));
   } else {
-    if (tile < tiles) commit(rawA, tile, 0);
+    if (tile < tiles) commit(rawA, tile);
     if (tile + 2 * stride < tiles) issue(rawA, tile + 2 * stride);
   }
-  int buf = 0;
-  // one pipeline step: MFMA on Xs[buf] (tile), commit tile+stride from RAWN into Xs[buf^1], refill RAWN with tile+3*stride
-// experiment hooks (tools/variants): -DWSTAT_NOMFMA runs one k-chunk only, -DWSTAT_NOEPI skips the epilogue
-#ifdef WSTAT_NOMFMA
-#define WSTAT_KLIM 16
-#else
-#define WSTAT_KLIM K
-#endif
-#ifdef WSTAT_NOEPI
-#define WSTAT_EPI_GUARD if (acc[0][0][0] == 12345.678f)
-#else
-#define WSTAT_EPI_GUARD
-#endif
+  // one pipeline step: MFMA on Xs (tile), commit tile+stride from RAWN into Xs, refill RAWN with tile+3*stride
 #define WSTAT_STEP(RAWN)                                                                                     \
   {                                                                                                          \
-    __syncthreads(); /* Xs[buf] committed by everyone; previous MFMA reads of Xs[buf^1] done */               \
+    __syncthreads(); /* Xs committed by everyone */                                                          \
     f32x4 acc[3][1];                                                                                         \
     _Pragma("unroll") for (int i = 0; i < 3; ++i) acc[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f};                    \
-    const float* xa = Xs + (size_t)(WSTAT_NBUF == 1 ? 0 : buf) * BM * LDK + (wm * 16 + lr) * LDK + kq * 4;     \
+    const float* xa = Xs + (wm * 16 + lr) * LDK + kq * 4;                                                    \
     const float* wa = Ws + (wn * 48 + lr) * LDK + kq * 4;                                                    \
-    _Pragma("unroll") for (int kc = 0; kc < WSTAT_KLIM; kc += 16) {                                          \
+    _Pragma("unroll") for (int kc = 0; kc < K; kc += 16) {                                                   \
       const f32x4 xf = *reinterpret_cast<const f32x4*>(xa + kc);                                             \
       f32x4 wf[3];                                                                                           \
       _Pragma("unroll") for (int i = 0; i < 3; ++i) wf[i] = *reinterpret_cast<const f32x4*>(wa + i * 16 * LDK + kc); \
@@ -240,18 +226,18 @@ __global__ __launch_bounds__(TH) void k_gemm_wstat(const float* __restrict__ x, 
     }                                                                                                        \
     /* commit BEFORE the epilogue's stores: vmcnt retires in order, waiting for loads issued after stores   \
        would also wait for those stores */                                                                   \
-    if (WSTAT_NBUF == 1) __syncthreads(); /* single X buffer: everyone is done reading it */                 \
+    __syncthreads(); /* everyone is done reading Xs */                                                       \
     if constexpr (FULL) { /* unconditional (tile index clamped): a branch here costs the counted vmcnt waits */ \
-      commit(RAWN, min(tile + stride, tiles - 1), buf ^ 1);                                                  \
+      commit(RAWN, min(tile + stride, tiles - 1));                                                           \
       issue(RAWN, min(tile + 3 * stride, tiles - 1));                                                        \
     } else {                                                                                                 \
-      if (tile + stride < tiles) commit(RAWN, tile + stride, buf ^ 1);                                       \
+      if (tile + stride < tiles) commit(RAWN, tile + stride);                                                \
       if (tile + 3 * stride < tiles) issue(RAWN, tile + 3 * stride);                                         \
     }                                                                                                        \
     if constexpr (EPI != 0) {                                                                                \
-      WSTAT_EPI_GUARD epilogue_fast<EPI>(acc, tile * BM + wm * 16, n_blk + wn * 48, ldy, y, bias4, e.res1, e.res2, red, BN, n_blk); \
+      epilogue_fast<EPI>(acc, tile * BM + wm * 16, n_blk + wn * 48, ldy, y, bias4, e.res1, e.res2, red, BN, n_blk); \
     } else {                                                                                                 \
-      WSTAT_EPI_GUARD epilogue<3, 1, FULL>(acc, tile * BM + wm * 16, n_blk + wn * 48, M, N, ldy, y, e, red, BN, n_blk); \
+      epilogue<3, 1, FULL>(acc, tile * BM + wm * 16, n_blk + wn * 48, M, N, ldy, y, e, red, BN, n_blk);      \
     }                                                                                                        \
     if ((EPI == 0 && e.colsum) || EPI == 4) {                                                                \
       __syncthreads();                                                                                       \
@@ -262,7 +248,6 @@ __global__ __launch_bounds__(TH) void k_gemm_wstat(const float* __restrict__ x, 
         if (n_blk + col < N) e.colsum[((size_t)tile * (BM / 32) + part) * N + n_blk + col] = s_;             \
       }                                                                                                      \
     }                                                                                                        \
-    buf ^= 1;                                                                                                \
     tile += stride;                                                                                          \
   }
   while (tile < tiles) {
@@ -942,8 +927,8 @@ __global__ __launch_bounds__(256, ((K <= 96 && !(PRO == PRO_SKSEL && K > 32)) ? 
 // LayerNorm 10 + fc1 45): the time of these K <= 96 products is the MFMA time PLUS the vector / LDS issue time of the waves of a
 // SIMD (DESIGN.md "What bounds these fp32 kernels"), ~2x the MFMA floor in both forms -- fusing removes launches, not that.
 // SAVE (training forward): the first column group also writes sel (M, CG) and n2 = LayerNorm2(x1) (M, C) for the backward.
-template <int C, int CG, bool SAVE, int OCC>      // OCC: resident blocks per CU (3: <= 168 registers, weight fragments single-buffered)
-__global__ __launch_bounds__(256, OCC) void k_sk_mlp_in(const float* __restrict__ cat, const float* __restrict__ sel, int rows_per_image,
+template <int C, int CG, bool SAVE>      // two resident blocks per CU, weight fragments double-buffered
+__global__ __launch_bounds__(256, 2) void k_sk_mlp_in(const float* __restrict__ cat, const float* __restrict__ sel, int rows_per_image,
                                                       const float* __restrict__ w_head, const float* __restrict__ b_head,
                                                       const float* __restrict__ feats, const float* __restrict__ shortcut, float* __restrict__ x1,
                                                       const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
@@ -1123,19 +1108,6 @@ __global__ __launch_bounds__(256, OCC) void k_sk_mlp_in(const float* __restrict_
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const float* wa = Ws + lr * LDW + 4 * kq;
-    if constexpr (OCC >= 3) {
-#pragma unroll
-      for (int c = 0; c < KC; ++c) {
-        f32x4 wf1[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) wf1[nt] = *reinterpret_cast<const f32x4*>(wa + 16 * nt * LDW + 16 * c);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) acc[nt] = mfma16(wf1[nt][s4], x1r[c][s4], acc[nt]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else {
     f32x4 wf[2][NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) wf[0][nt] = *reinterpret_cast<const f32x4*>(wa + 16 * nt * LDW);
@@ -1150,7 +1122,6 @@ __global__ __launch_bounds__(256, OCC) void k_sk_mlp_in(const float* __restrict_
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) acc[nt] = mfma16(wf[c & 1][nt][s4], x1r[c][s4], acc[nt]);
       __builtin_amdgcn_sched_barrier(0);
-    }
     }
     const float nm = -mean * rstd;
     const size_t yoff = m * N + n_blk + 4 * kq;
@@ -1180,23 +1151,21 @@ int launch_rowreg(const float* x, int ldx, const float* w, float* y, int ldy, in
   }
   const int tiles = M / (EPI == 4 ? 32 : 16), ny = N / 96;      // work items of a wave (pairs of 16-row tiles under RR_EPI 4)
   // resident waves: LDS-limited blocks per CU x 4; every wave gets the same number of tiles when that divides evenly
-  static const int rr_blocks = getenv("DPMN_RR_BLOCKS") ? atoi(getenv("DPMN_RR_BLOCKS")) : 0;
   const bool x3 = (PRO == PRO_NONE || PRO == PRO_LN) && (K == 96 || K == 192) && x3_on(128);
   // (mode 2: the weight planes are 1.5x the fp32 copy -- two blocks per CU at K = 96, one at K = 192 -- and a tile's MFMAs take 0.4x the
   //  time, so two tiles per wave are enough to overlap: 96 -> 384 at M = 49152 30.3 vs 33.2 us)
   const int per_cu = x3 ? (K <= 96 ? 2 : 1) : (smem <= 40 * 1024 ? 3 : (smem <= 80 * 1024 ? 2 : 1));
-  int gx = (rr_blocks > 0 ? rr_blocks : 256 * per_cu) / ny;
+  int gx = 256 * per_cu / ny;
   if (gx < 1) gx = 1;
   // at least 3 tiles per wave, so that the load / MFMA / store pipeline of a wave has something to overlap
-  static const int rr_tpw_env = getenv("DPMN_RR_TPW") ? atoi(getenv("DPMN_RR_TPW")) : 0;
-  const int rr_tpw = rr_tpw_env > 0 ? rr_tpw_env : (x3 ? 2 : 3);
+  const int rr_tpw = x3 ? 2 : 3;
   while (gx > 256 / ny && gx > 1 && (long)gx * 4 * rr_tpw > tiles) gx -= 256 / ny > 0 ? 256 / ny : 1;
   if (gx * 4 > tiles) gx = cdiv(tiles, 4);
   ProfScope prof(PRO == PRO_LN ? PT_GEMM_WSTAT_LN : PT_GEMM_WSTAT, st, 2.0 * M * (double)N * K,
                  4.0 * ((double)M * K * (PRO == PRO_SKSEL ? 3 : 1) + (double)M * N * (1 + (EPI == 3 ? 2 : (EPI == 5 ? 1 : 0))) + (double)N * K));
   if constexpr ((PRO == PRO_NONE || PRO == PRO_LN) && (K == 96 || K == 192)) {
     if (x3) {                  // mode 2: weights split once per block into bf16 planes, rows split in registers (gemm_rowreg_x3.hip)
-      (void)dpmn_gemm::x3_launch_rowreg(K, PRO, EPI, x, ldx, w, y, ldy, M, N, p, e, gx, st);
+      if (dpmn_gemm::x3_launch_rowreg(K, PRO, EPI, x, ldx, w, y, ldy, M, N, p, e, gx, st) != 0) return dpmn_set_error(DPMN_ERR_LAUNCH, "linear: bf16x3 rowreg launch failed");
       DPMN_CHECK_LAUNCH();
       return DPMN_OK;
     }
@@ -1210,8 +1179,7 @@ int launch_rowreg(const float* x, int ldx, const float* w, float* y, int ldy, in
 template <int K, int PRO>
 int try_rowreg(const float* x, int ldx, const float* w, float* y, int ldy, int M, int N, const ProArgs& p, const EpiArgs& e,
                hipStream_t st) {
-  static const int on = getenv("DPMN_ROWREG") ? atoi(getenv("DPMN_ROWREG")) : 1;
-  if (!on || M % 16 || N % 96 || e.atomic || ldy % 4 || ldx % 4 || M < 1024) return -1;
+  if (M % 16 || N % 96 || e.atomic || ldy % 4 || ldx % 4 || M < 1024) return -1;
   if constexpr (PRO == PRO_SKSEL && (K == 32 || K == 64)) {
     if (p.groups != 3 || p.rows_per_image % 16 || !(e.res1 && e.res2) || e.act != ACT_NONE || e.colsum) return -1;
     return launch_rowreg<K, PRO_SKSEL, 3>(x, ldx, w, y, ldy, M, N, p, e, st);
@@ -1236,15 +1204,13 @@ template <int K, int PRO, int TH, bool FULL = false, int EPI = 0>
 int launch_wholeK_th(const float* x, int ldx, const float* w, float* y, int ldy, int M, int N, const ProArgs& p,
                      const EpiArgs& e, hipStream_t st, int target_blocks) {
   constexpr int BM = TH / 8;
-  const size_t smem = (size_t)((WS_BN + WSTAT_NBUF * BM) * (K + PAD) + (TH / 64) * WS_BN + 2 * K) * sizeof(float);
+  const size_t smem = (size_t)((WS_BN + BM) * (K + PAD) + (TH / 64) * WS_BN + 2 * K) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_wstat<K, PRO, TH, FULL, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr_set = true;
   }
   const int tiles = cdiv(M, BM), ny = cdiv(N, WS_BN);
-  static const int force_blocks = getenv("DPMN_WSTAT_BLOCKS") ? atoi(getenv("DPMN_WSTAT_BLOCKS")) : 0;      // experiment knob
-  if (force_blocks > 0) target_blocks = force_blocks;
   int gx = target_blocks / ny;
   if (gx < 1) gx = 1;
   if (gx > tiles) gx = tiles;
@@ -1261,52 +1227,39 @@ int launch_wholeK(const float* x, int ldx, const float* w, float* y, int ldy, in
   // 512-thread blocks (64-token tiles, 8 waves sharing one W tile): 64 KB LDS at K = 96 -> 2 blocks = 16 waves per CU;
   // 256-thread blocks (32-token tiles): 51 KB -> 3 blocks = 12 waves per CU, and the only variant with the per-32-row
   // column-sum epilogue (SKConv GAP partials)
-  static const int big = getenv("DPMN_WSTAT_TH") ? atoi(getenv("DPMN_WSTAT_TH")) : 512;
   {
     const int rc = try_rowreg<K, PRO>(x, ldx, w, y, ldy, M, N, p, e, st);
     if (rc != -1) return rc;
   }
+  // K = 96 NONE / LN whole tiles belong to rowreg: every caller passes ldx = K, ldy = N (a multiple of 4) and no atomics, so
+  // try_rowreg has taken each such call that one of the straight-line epilogues below would serve
+  constexpr bool rowreg96 = K == 96 && (PRO == PRO_NONE || PRO == PRO_LN);
   if constexpr (K <= 128) {
-    if (big == 512 && !e.colsum && M >= 4096) {
+    if (!e.colsum && M >= 4096) {
       if (M % 64 == 0 && N % WS_BN == 0 && !e.atomic) {    // every tile interior: the predicate-free instantiations
-        const bool plain = !e.res1 && !e.res2 && ldy % 4 == 0;      // bias optional (data-gradient GEMMs have none)
-        if constexpr (K == 96 && (PRO == PRO_NONE || PRO == PRO_LN)) {
-          // one column block and a 64-row tile count that does not divide over 512 resident blocks (M = 49152: 768 tiles =
-          // 1.5 per block): 32-row tiles over 768 blocks (3 per CU) are balanced, 2 tiles each
-          const int tiles64 = M / 64;
-          if (N == WS_BN && plain && e.act == ACT_NONE && tiles64 % 512 != 0 && tiles64 < 2048 && (M / 32) % 768 == 0)
-            return launch_wholeK_th<K, PRO, 256, true, 1>(x, ldx, w, y, ldy, M, N, p, e, st, 768);
-        }
-        if (plain && e.act == ACT_NONE) return launch_wholeK_th<K, PRO, 512, true, 1>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
-        if (plain && e.act == ACT_GELU) return launch_wholeK_th<K, PRO, 512, true, 2>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
-        if constexpr (PRO == PRO_SKSEL || PRO == PRO_NONE) {
-          if (e.res1 && e.res2 && e.act == ACT_NONE && ldy % 4 == 0)
-            return launch_wholeK_th<K, PRO, 512, true, 3>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
-        }
-        if constexpr (PRO == PRO_NONE) {
-          if (e.res1 && !e.res2 && e.act == ACT_NONE && ldy % 4 == 0)
-            return launch_wholeK_th<K, PRO, 512, true, 5>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
+        if constexpr (!rowreg96) {
+          const bool plain = !e.res1 && !e.res2 && ldy % 4 == 0;      // bias optional (data-gradient GEMMs have none)
+          if (plain && e.act == ACT_NONE) return launch_wholeK_th<K, PRO, 512, true, 1>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
+          if (plain && e.act == ACT_GELU) return launch_wholeK_th<K, PRO, 512, true, 2>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
+          if constexpr (PRO == PRO_SKSEL || PRO == PRO_NONE) {
+            if (e.res1 && e.res2 && e.act == ACT_NONE && ldy % 4 == 0)
+              return launch_wholeK_th<K, PRO, 512, true, 3>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
+          }
+          if constexpr (PRO == PRO_NONE) {
+            if (e.res1 && !e.res2 && e.act == ACT_NONE && ldy % 4 == 0)
+              return launch_wholeK_th<K, PRO, 512, true, 5>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
+          }
         }
         return launch_wholeK_th<K, PRO, 512, true>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
       }
       return launch_wholeK_th<K, PRO, 512>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
     }
   }
-  if constexpr (K == 96 && PRO == PRO_LN) {        // experiment: 32-row tiles with the straight-line epilogues (DPMN_WSTAT_TH=256)
-    if (big == 256 && !e.colsum && M % 32 == 0 && N % WS_BN == 0 && !e.atomic && !e.res1 && !e.res2 && ldy % 4 == 0) {
-      if (e.act == ACT_NONE) return launch_wholeK_th<K, PRO, 256, true, 1>(x, ldx, w, y, ldy, M, N, p, e, st, 768);
-      if (e.act == ACT_GELU) return launch_wholeK_th<K, PRO, 256, true, 2>(x, ldx, w, y, ldy, M, N, p, e, st, 768);
-    }
+  if constexpr (PRO == PRO_NONE && K == 96) {      // SKConv projection + GAP partials, straight-line (pgrm.py:84-86); M >= 1024 took rowreg
+    if (e.colsum && M % 32 == 0 && N % WS_BN == 0 && !e.atomic && !e.res1 && !e.res2 && e.act == ACT_NONE && ldy % 4 == 0)
+      return launch_wholeK_th<K, PRO, 256, true, 4>(x, ldx, w, y, ldy, M, N, p, e, st, 768);
   }
-  if constexpr (PRO == PRO_NONE && K == 96) {      // SKConv projection + GAP partials, straight-line (pgrm.py:84-86)
-    if (e.colsum && M % 32 == 0 && N % WS_BN == 0 && !e.atomic && !e.res1 && !e.res2 && e.act == ACT_NONE && ldy % 4 == 0) {
-      static const int cs512 = getenv("DPMN_COLSUM_TH") ? atoi(getenv("DPMN_COLSUM_TH")) : 512;
-      if (cs512 == 512 && M % 64 == 0 && M >= 4096)     // 64-row tiles, two 32-row partials each: half the barriers
-        return launch_wholeK_th<K, PRO, 512, true, 4>(x, ldx, w, y, ldy, M, N, p, e, st, 512);
-      return launch_wholeK_th<K, PRO, 256, true, 4>(x, ldx, w, y, ldy, M, N, p, e, st, WSTAT_NBUF == 1 ? 768 : 512);
-    }
-  }
-  return launch_wholeK_th<K, PRO, 256>(x, ldx, w, y, ldy, M, N, p, e, st, WSTAT_NBUF == 1 ? 768 : 512);
+  return launch_wholeK_th<K, PRO, 256>(x, ldx, w, y, ldy, M, N, p, e, st, 768);
 }
 
 template <int PRO>
@@ -1338,7 +1291,7 @@ int dpmn_linear_f32(const float* x, const float* w, const float* bias, const flo
   DPMN_REQUIRE(K % 32 == 0, "linear: K must be a multiple of 32");
   dim3 grid(cdiv(M, 64), cdiv(N, 96));
   ProfScope prof(PT_GEMM_KLOOP, as_stream(stream), 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)M * N * (res1 ? 2 : 1) + (double)N * K));
-  if (x3_on(8)) (void)dpmn_gemm::x3_launch_kloop(x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L, grid, as_stream(stream));
+  if (x3_on(8)) dpmn_gemm::x3_launch_kloop(x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L, grid, as_stream(stream));
   else hipLaunchKernelGGL(k_gemm_kloop, grid, dim3(256), 0, as_stream(stream), x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
@@ -1356,7 +1309,7 @@ int dpmn_linear_drop_f32(const float* x, const float* w, const float* bias, cons
   e.p_elem = p_elem; e.p_row = p_row; e.seed_elem = seed_elem; e.seed_row = seed_row; e.row_len = row_len;
   dim3 grid(cdiv(M, 64), cdiv(N, 96));
   ProfScope prof(PT_GEMM_KLOOP, as_stream(stream), 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)M * N * 2 + (double)N * K));
-  if (x3_on(8)) (void)dpmn_gemm::x3_launch_kloop(x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L, grid, as_stream(stream));
+  if (x3_on(8)) dpmn_gemm::x3_launch_kloop(x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L, grid, as_stream(stream));
   else hipLaunchKernelGGL(k_gemm_kloop, grid, dim3(256), 0, as_stream(stream), x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
@@ -1428,29 +1381,25 @@ int dpmn_sk_mlp_in_drop_f32(const float* cat, const float* attn_vec, const float
   const size_t smem = (size_t)(96 * (Cc + PAD) + 3 * 96 + 96 * (CG + PAD)) * sizeof(float);      // 53376 B: proj_head is the larger tenant of its region
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_mlp_in<Cc, CG, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_mlp_in<Cc, CG, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_mlp_in<Cc, CG, false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_mlp_in<Cc, CG, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_mlp_in<Cc, CG, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_mlp_in<Cc, CG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr_set = true;
   }
-  static const int occ = getenv("DPMN_SKMLP_OCC") ? atoi(getenv("DPMN_SKMLP_OCC")) : 2;
   const int tiles = M / 16, ny = N / 96;
-  static const int blocks = getenv("DPMN_SKMLP_BLOCKS") ? atoi(getenv("DPMN_SKMLP_BLOCKS")) : 256 * (occ >= 3 ? 3 : 2);
-  int gx = blocks / ny;
+  int gx = 512 / ny;      // two resident blocks per CU
   if (gx < 1) gx = 1;
   if (gx * 4 > tiles) gx = cdiv(tiles, 4);
   hipStream_t st = as_stream(stream);
   // algorithmic work of the two products; compulsory bytes: cat, feats, shortcut in, x1 and y out, both weight matrices
   ProfScope prof(PT_GEMM_WSTAT_LN, st, 2.0 * M * ((double)N * Cc + (double)Cc * CG),
                  4.0 * ((double)M * Cc * 4 + (double)M * N + (double)N * Cc + (double)Cc * CG));
-#define SKMLP_LAUNCH(SAVE_, OCC_) hipLaunchKernelGGL((k_sk_mlp_in<Cc, CG, SAVE_, OCC_>), dim3(gx, ny), dim3(256), smem, st, cat, attn_vec, rows_per_image, \
-                                                    w_head, b_head, feats, shortcut, x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N, v_out, n2_out, p_row, seed_row)
+#define SKMLP_LAUNCH(SAVE_) hipLaunchKernelGGL((k_sk_mlp_in<Cc, CG, SAVE_>), dim3(gx, ny), dim3(256), smem, st, cat, attn_vec, rows_per_image, \
+                                              w_head, b_head, feats, shortcut, x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N, v_out, n2_out, p_row, seed_row)
   if (x3_on(128))
-    (void)dpmn_gemm::x3_launch_sk_mlp_in(cat, attn_vec, rows_per_image, w_head, b_head, feats, shortcut, x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N,
-                                         v_out, n2_out, p_row, seed_row, gx, st);
-  else if (v_out) { if (occ >= 3) SKMLP_LAUNCH(true, 3); else SKMLP_LAUNCH(true, 2); }
-  else { if (occ >= 3) SKMLP_LAUNCH(false, 3); else SKMLP_LAUNCH(false, 2); }
+    dpmn_gemm::x3_launch_sk_mlp_in(cat, attn_vec, rows_per_image, w_head, b_head, feats, shortcut, x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N,
+                                   v_out, n2_out, p_row, seed_row, gx, st);
+  else if (v_out) SKMLP_LAUNCH(true);
+  else SKMLP_LAUNCH(false);
 #undef SKMLP_LAUNCH
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
@@ -1465,8 +1414,7 @@ int dpmn_pointwise_wgrad_f32(const float* dz, const float* g, float* dw, int B, 
   DPMN_REQUIRE(dz && g && dw && L % 32 == 0 && Ch % 4 == 0, "pointwise_wgrad: bad arguments");
   EpiArgs e{nullptr, nullptr, nullptr, nullptr, ACT_NONE, 0.f, 1};   // split over (b, s), atomic accumulation
   dim3 grid(cdiv(Ch, 64), cdiv(Ch, 96), 32);
-  if (x3_on(8)) (void)dpmn_gemm::x3_launch_kloop(dz, L, g, L, dw, Ch, Ch, Ch, B * L, e, L,
-                     (long)Ch * L, (long)Ch * L, grid, as_stream(stream));
+  if (x3_on(8)) dpmn_gemm::x3_launch_kloop(dz, L, g, L, dw, Ch, Ch, Ch, B * L, e, L, (long)Ch * L, (long)Ch * L, grid, as_stream(stream));
   else hipLaunchKernelGGL(k_gemm_kloop, grid, dim3(256), 0, as_stream(stream), dz, L, g, L, dw, Ch, Ch, Ch, B * L, e, L,
                      (long)Ch * L, (long)Ch * L);
   DPMN_CHECK_LAUNCH();
@@ -1477,8 +1425,7 @@ int dpmn_pointwise_wgrad_f32(const float* dz, const float* g, float* dw, int B, 
 // Ch a multiple of 128, L of 32: 128 x 128 tiles with ~504 workgroups (k_gemm_kloop128: 56 splits for Ch = 384); otherwise the
 // 64 x 96 k-loop with 32 splits.  Workspace: dpmn_pointwise_wgrad_det_bytes(Ch, L).
 static int pw_wgrad_splits(int Ch, int L) {
-  static const int nt_on = getenv("DPMN_PW_WGRAD_128") ? atoi(getenv("DPMN_PW_WGRAD_128")) : 1;
-  if (!nt_on || Ch % 128 != 0 || L % 32 != 0) return 0;
+  if (Ch % 128 != 0 || L % 32 != 0) return 0;
   const int tiles = (Ch / 128) * (Ch / 128);
   int s = 504 / tiles;                 // just under the 512 resident workgroups (2 per CU)
   s &= ~7;                             // a multiple of 8: the XCD-local order
@@ -1499,7 +1446,7 @@ int dpmn_pointwise_wgrad_det_f32(const float* dz, const float* g, float* dw, int
   if (s128) {
     const int nchunks = B * (L / 32);
     ProfScope prof(PT_GEMM_KLOOP, as_stream(stream), 2.0 * Ch * (double)Ch * B * L, 4.0 * (2.0 * B * Ch * (double)L + (double)Ch * Ch));
-    if (x3_on(32)) (void)dpmn_gemm::x3_launch_kloop128(dz, g, ws, Ch, Ch, L, nchunks, S, (long)Ch * L, (long)Ch * Ch, as_stream(stream));
+    if (x3_on(32)) dpmn_gemm::x3_launch_kloop128(dz, g, ws, Ch, Ch, L, nchunks, S, (long)Ch * L, (long)Ch * Ch, as_stream(stream));
     else hipLaunchKernelGGL(k_gemm_kloop128, dim3((Ch / 128) * (Ch / 128) * S), dim3(256), 0, as_stream(stream), dz, g, ws, Ch, Ch, L, nchunks, S,
                        (long)Ch * L, (long)Ch * Ch);
     DPMN_CHECK_LAUNCH();
@@ -1507,8 +1454,7 @@ int dpmn_pointwise_wgrad_det_f32(const float* dz, const float* g, float* dw, int
   }
   EpiArgs e{nullptr, nullptr, nullptr, nullptr, ACT_NONE, 0.f, 0, (long)Ch * Ch};
   dim3 grid(cdiv(Ch, 64), cdiv(Ch, 96), S);
-  if (x3_on(8)) (void)dpmn_gemm::x3_launch_kloop(dz, L, g, L, ws, Ch, Ch, Ch, B * L, e, L,
-                     (long)Ch * L, (long)Ch * L, grid, as_stream(stream));
+  if (x3_on(8)) dpmn_gemm::x3_launch_kloop(dz, L, g, L, ws, Ch, Ch, Ch, B * L, e, L, (long)Ch * L, (long)Ch * L, grid, as_stream(stream));
   else hipLaunchKernelGGL(k_gemm_kloop, grid, dim3(256), 0, as_stream(stream), dz, L, g, L, ws, Ch, Ch, Ch, B * L, e, L,
                      (long)Ch * L, (long)Ch * L);
   DPMN_CHECK_LAUNCH();
@@ -1518,16 +1464,14 @@ int dpmn_pointwise_wgrad_det_f32(const float* dz, const float* g, float* dw, int
 int dpmn_pointwise_f32(const float* g, const float* w, const float* bias, float* z, int B, int Ch, int L,
                        dpmn_stream_t stream) {
   DPMN_REQUIRE(g && w && bias && z && Ch % 128 == 0 && L % 128 == 0, "pointwise: Ch and L must be multiples of 128");
-  static const int pw_bc = getenv("DPMN_PW_BC") ? atoi(getenv("DPMN_PW_BC")) : 192;
   ProfScope prof(PT_GEMM_PW, as_stream(stream), 2.0 * Ch * Ch * (double)L * B, 4.0 * (2.0 * B * Ch * (double)L + (double)Ch * Ch + Ch));
-  if (x3_on(4)) {
-    // fp32 product through six bf16 MFMAs of a three-term operand split (dpmn_set_compute_dtype(2), gemm_x3.hip)
-    if (dpmn_gemm::x3_launch_pw(g, w, bias, z, B, Ch, L, as_stream(stream)) != 0) return dpmn_set_error(DPMN_ERR_LAUNCH, "pointwise: bf16x3 launch failed");
-  } else if (g_dpmn_bf16 && Ch % 192 == 0)
+  if (x3_on(4))       // fp32 product through six bf16 MFMAs of a three-term operand split (dpmn_set_compute_dtype(2), gemm_x3.hip)
+    dpmn_gemm::x3_launch_pw(g, w, bias, z, B, Ch, L, as_stream(stream));
+  else if (g_dpmn_bf16 && Ch % 192 == 0)
     hipLaunchKernelGGL((k_gemm_pw_bf16<192>), dim3(L / 128, Ch / 192, B), dim3(256), 0, as_stream(stream), g, w, bias, z, Ch, L);
   else if (g_dpmn_bf16)
     hipLaunchKernelGGL((k_gemm_pw_bf16<128>), dim3(L / 128, Ch / 128, B), dim3(256), 0, as_stream(stream), g, w, bias, z, Ch, L);
-  else if (Ch % 192 == 0 && pw_bc == 192)
+  else if (Ch % 192 == 0)
     hipLaunchKernelGGL((k_gemm_pw<192>), dim3(L / 128, Ch / 192, B), dim3(256), 0, as_stream(stream), g, w, bias, z, Ch, L);
   else
     hipLaunchKernelGGL((k_gemm_pw<128>), dim3(L / 128, Ch / 128, B), dim3(256), 0, as_stream(stream), g, w, bias, z, Ch, L);

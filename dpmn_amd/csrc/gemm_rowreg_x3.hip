@@ -446,9 +446,9 @@ int x3_launch_rowreg(int K, int pro, int epi, const float* x, int ldx, const flo
   return -1;
 }
 
-int x3_launch_sk_mlp_in(const float* cat, const float* sel, int rows_per_image, const float* w_head, const float* b_head, const float* feats,
-                        const float* shortcut, float* x1, const float* ln_w, const float* ln_b, float eps, const float* w_fc1, const float* b_fc1,
-                        float* y, int M, int N, float* v_out, float* n2_out, float p_row, unsigned long long seed_row, int gx, hipStream_t st) {
+void x3_launch_sk_mlp_in(const float* cat, const float* sel, int rows_per_image, const float* w_head, const float* b_head, const float* feats,
+                         const float* shortcut, float* x1, const float* ln_w, const float* ln_b, float eps, const float* w_fc1, const float* b_fc1,
+                         float* y, int M, int N, float* v_out, float* n2_out, float p_row, unsigned long long seed_row, int gx, hipStream_t st) {
   constexpr int Cc = 96, CG = 32;
   const size_t smem = (size_t)3 * 96 * (Cc + 8) * 2 + (size_t)(3 * 96 + 96 * (Cc / 4) * 2) * sizeof(float);      // planes + pb + the fold's scratch (> proj_head)
   static bool attr_set = false;
@@ -463,6 +463,5 @@ int x3_launch_sk_mlp_in(const float* cat, const float* sel, int rows_per_image, 
   else
     hipLaunchKernelGGL((k_sk_mlp_in_x3<Cc, CG, false>), dim3(gx, N / 96), dim3(256), smem, st, cat, sel, rows_per_image, w_head, b_head, feats, shortcut,
                        x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N, v_out, n2_out, p_row, seed_row);
-  return 0;
 }
 }  // namespace dpmn_gemm

@@ -19,6 +19,6 @@ struct TnGroup {
 };
 // gemm_tn_x3.hip: the split partials of dW = dY^T X (+ db) on six bf16 MFMAs per tile -- the launches backward.hip k_gemm_tn_reg /
 // k_gemm_tn_reg_multi would get
-int x3_launch_tn(const float* dy, const float* x, int M, int N, int K, int rows, const float* db, float* part, dim3 grid, hipStream_t st);
-int x3_launch_tn_multi(const TnGroup& g, hipStream_t st);
+void x3_launch_tn(const float* dy, const float* x, int M, int N, int K, int rows, const float* db, float* part, dim3 grid, hipStream_t st);
+void x3_launch_tn_multi(const TnGroup& g, hipStream_t st);
 }  // namespace dpmn_gemm

@@ -8,7 +8,6 @@
 // kq groups exactly like a step of the fp32 kernel, and the pair (t, t + 1) of one column is one split (11 vector instructions -> the
 // three dwords of bf16 pairs the A / B operand registers want).  Per step and lane: 16 loads, 24 splits (264 VALU), 54 MFMAs.
 // Rows past the block's range lie beyond the buffer's num_records (zeros: h = m = l = 0), columns past N / K likewise.
-#include <cstdlib>
 #include "gemm_tn.h"
 
 namespace {
@@ -29,9 +28,9 @@ __device__ __forceinline__ Planes split_col(const f32x3 (&v)[8], int i) {
   return p;
 }
 
-template <int D>      // D: 32-row steps in flight
 __device__ __forceinline__ void tn_reg_x3_body(const float* __restrict__ dy, const float* __restrict__ x, int M, int N, int K, int rows_per_block,
                                                const float* __restrict__ db, float* __restrict__ part, int gx, int gy, int gz, int lid) {
+  constexpr int D = 1;      // 32-row steps in flight (the loops over D stay: hipcc allocates the flattened form differently)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave & 1, wk = wave >> 1;
   const int lr = lane & 15, kq = lane >> 4;
@@ -120,38 +119,29 @@ __device__ __forceinline__ void tn_reg_x3_body(const float* __restrict__ dy, con
   }
 }
 
-template <int D>
 __global__ __launch_bounds__(256, 2) void k_gemm_tn_reg_x3(const float* __restrict__ dy, const float* __restrict__ x, int M, int N, int K,
                                                             int rows_per_block, const float* __restrict__ db, float* __restrict__ part) {
-  tn_reg_x3_body<D>(dy, x, M, N, K, rows_per_block, db, part, gridDim.x, gridDim.y, gridDim.z,
-                    blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+  tn_reg_x3_body(dy, x, M, N, K, rows_per_block, db, part, gridDim.x, gridDim.y, gridDim.z,
+                 blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
 }
 
-template <int D>      // the grouped launch (backward.hip k_gemm_tn_reg_multi)
+// the grouped launch (backward.hip k_gemm_tn_reg_multi)
 __global__ __launch_bounds__(256, 2) void k_gemm_tn_reg_x3_multi(dpmn_gemm::TnGroup g) {
   int i = 0;
 #pragma unroll
   for (int j = 1; j < 8; ++j) i += (j < g.n && (int)blockIdx.x >= g.first[j]) ? 1 : 0;
   const dpmn_gemm::TnItem& t = g.it[i];
-  tn_reg_x3_body<D>(t.dy, t.x, t.M, t.N, t.K, t.rows, t.db, t.part, t.gx, t.gy, t.gz, (int)blockIdx.x - g.first[i]);
+  tn_reg_x3_body(t.dy, t.x, t.M, t.N, t.K, t.rows, t.db, t.part, t.gx, t.gy, t.gz, (int)blockIdx.x - g.first[i]);
 }
 }  // namespace
 
 namespace dpmn_gemm {
-static int x3_tn_depth() {
-  static const int depth = getenv("DPMN_X3_TN_DEPTH") ? atoi(getenv("DPMN_X3_TN_DEPTH")) : 1;
-  return depth;
+void x3_launch_tn_multi(const TnGroup& g, hipStream_t st) {
+  hipLaunchKernelGGL(k_gemm_tn_reg_x3_multi, dim3(g.first[g.n]), dim3(256), 0, st, g);
 }
-int x3_launch_tn_multi(const TnGroup& g, hipStream_t st) {
-  if (x3_tn_depth() == 2) hipLaunchKernelGGL(k_gemm_tn_reg_x3_multi<2>, dim3(g.first[g.n]), dim3(256), 0, st, g);
-  else hipLaunchKernelGGL(k_gemm_tn_reg_x3_multi<1>, dim3(g.first[g.n]), dim3(256), 0, st, g);
-  return 0;
-}
-int x3_launch_tn(const float* dy, const float* x, int M, int N, int K, int rows, const float* db, float* part, dim3 grid, hipStream_t st) {
+void x3_launch_tn(const float* dy, const float* x, int M, int N, int K, int rows, const float* db, float* part, dim3 grid, hipStream_t st) {
   // (one 32-row step in flight, three blocks per CU: 24.0 us per launch on average over a training step against 25.3 us with two
   //  steps in flight at two blocks per CU and 27.0 us for the fp32 kernel)
-  if (x3_tn_depth() == 2) hipLaunchKernelGGL(k_gemm_tn_reg_x3<2>, grid, dim3(256), 0, st, dy, x, M, N, K, rows, db, part);
-  else hipLaunchKernelGGL(k_gemm_tn_reg_x3<1>, grid, dim3(256), 0, st, dy, x, M, N, K, rows, db, part);
-  return 0;
+  hipLaunchKernelGGL(k_gemm_tn_reg_x3, grid, dim3(256), 0, st, dy, x, M, N, K, rows, db, part);
 }
 }  // namespace dpmn_gemm

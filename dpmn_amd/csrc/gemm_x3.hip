@@ -369,17 +369,15 @@ int cu_count() {
 }  // namespace
 
 namespace dpmn_gemm {
-int x3_launch_kloop(const float* x, int ldx, const float* w, int ldw, float* y, int ldy, int M, int N, int K, const EpiArgs& e, int kb_len,
-                    long x_bstride, long w_bstride, dim3 grid, hipStream_t st) {
+void x3_launch_kloop(const float* x, int ldx, const float* w, int ldw, float* y, int ldy, int M, int N, int K, const EpiArgs& e, int kb_len,
+                     long x_bstride, long w_bstride, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL(k_gemm_kloop_x3, grid, dim3(256), 0, st, x, ldx, w, ldw, y, ldy, M, N, K, e, kb_len, x_bstride, w_bstride);
-  return 0;
 }
-int x3_launch_kloop128(const float* x, const float* w, float* y, int M, int N, int L, int nchunks, int splits, long bstride, long zstride,
-                       hipStream_t st) {
+void x3_launch_kloop128(const float* x, const float* w, float* y, int M, int N, int L, int nchunks, int splits, long bstride, long zstride,
+                        hipStream_t st) {
   hipLaunchKernelGGL(k_gemm_kloop128_x3, dim3((M / 128) * (N / 128) * splits), dim3(256), 0, st, x, w, y, M, N, L, nchunks, splits, bstride, zstride);
-  return 0;
 }
-int x3_launch_pw(const float* g, const float* w, const float* bias, float* z, int B, int Ch, int L, hipStream_t st) {
+void x3_launch_pw(const float* g, const float* w, const float* bias, float* z, int B, int Ch, int L, hipStream_t st) {
   constexpr int LDP_ = 132, LDWB_ = 48;
   const int bc = Ch % 192 == 0 ? 192 : 128;
   const size_t smem = (size_t)2 * 3 * (16 * LDP_ * 4 + bc * LDWB_ * 2);
@@ -394,6 +392,5 @@ int x3_launch_pw(const float* g, const float* w, const float* bias, float* z, in
   const unsigned grid = (unsigned)(tiles < n_cu ? tiles : n_cu);
   if (bc == 192) hipLaunchKernelGGL((k_gemm_pw_bf16x3<192>), dim3(grid), dim3(512), smem, st, g, w, bias, z, Ch, L, B);
   else hipLaunchKernelGGL((k_gemm_pw_bf16x3<128>), dim3(grid), dim3(512), smem, st, g, w, bias, z, Ch, L, B);
-  return 0;
 }
 }  // namespace dpmn_gemm

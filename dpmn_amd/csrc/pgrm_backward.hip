@@ -140,7 +140,6 @@ int dpmn_pgrm_blocks_backward_leaf_f32(const dpmn_pgrm_weights* w, const dpmn_pg
   // Linear weight gradients collected while their operands stay live, launched as ONE grouped product (dpmn_gemm_tn_group_f32): a
   // product alone puts one short block on each CU; their arena slices are taken at collection time, so the group goes out before the
   // arena wraps
-  static const int tn_group = getenv("DPMN_BWD_TN_GROUP") ? atoi(getenv("DPMN_BWD_TN_GROUP")) : 1;
   dpmn_tn_item tn_items[8];
   int tn_n = 0;
   auto tn_flush = [&]() -> int {
@@ -172,8 +171,7 @@ int dpmn_pgrm_blocks_backward_leaf_f32(const dpmn_pgrm_weights* w, const dpmn_pg
 #define LINEAR_BWD(dy, x, w_t, dw, db, N_, K_, dx)                                                                   \
   do {                                                                                                             \
     RUN(take(dpmn_gemm_tn_partial_bytes(M, (N_), (K_))));                                                            \
-    if (tn_group) tn_items[tn_n++] = dpmn_tn_item{(dy), (x), (dw), (db), M, (N_), (K_), ws_ptr, ws_n};                \
-    else { LEAF(ls_); RUN(dpmn_gemm_tn_f32((dy), (x), (dw), (db), M, (N_), (K_), ws_ptr, ws_n, ls_)); }              \
+    tn_items[tn_n++] = dpmn_tn_item{(dy), (x), (dw), (db), M, (N_), (K_), ws_ptr, ws_n};                             \
     RUN(dpmn_linear_f32((dy), (w_t), nullptr, nullptr, nullptr, (dx), M, (K_), (N_), DPMN_ACT_NONE, 0.f, stream));     \
   } while (0)
 #define LN_BWD(x, dy, gamma, dx, dgamma, dbeta)                                                                      \
@@ -248,8 +246,7 @@ int dpmn_pgrm_blocks_backward_leaf_f32(const dpmn_pgrm_weights* w, const dpmn_pg
     }
     RUN(dpmn_sk_feats_grad_f32(dat, b.feats, s.dS, s.dfeats, M, L, C, stream));
     RUN(take(dpmn_gemm_tn_partial_bytes(M, C, C)));
-    if (tn_group) tn_items[tn_n++] = dpmn_tn_item{s.dfeats, b.cat, sink(g.sk_proj_w), sink(g.sk_proj_b), M, C, C, ws_ptr, ws_n};
-    else { LEAF(ls_); RUN(dpmn_gemm_tn_f32(s.dfeats, b.cat, sink(g.sk_proj_w), sink(g.sk_proj_b), M, C, C, ws_ptr, ws_n, ls_)); }
+    tn_items[tn_n++] = dpmn_tn_item{s.dfeats, b.cat, sink(g.sk_proj_w), sink(g.sk_proj_b), M, C, C, ws_ptr, ws_n};
     RUN(dpmn_linear_f32(s.dfeats, t.proj_t, nullptr, dcat, nullptr, s.dcat2, M, C, C, DPMN_ACT_NONE, 0.f, stream));
     // window attention: q / k / v recomputed, all window sizes on MFMA, bias-table gradients as per-block partial rows
     int win[4], shift[4];

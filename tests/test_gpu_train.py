@@ -144,11 +144,13 @@ def test_grouped_linear_weight_gradients_equal_the_single_calls_bitwise(dev):
     """dpmn_gemm_tn_group_f32 (the Linear weight gradients of one Swin block in ONE partial-sum launch, csrc/backward.hip
     k_gemm_tn_reg_multi / gemm_tn_x3.hip in mode 2) == the same products as dpmn_gemm_tn_f32 calls, bit for bit: the shapes of a PGRM
     block at B = 48 and B = 3 (fc2, fc1, SKConv proj, q, kv; the SKConv head K = 32 and a ragged row count keep their own launches),
-    with and without bias gradients, accumulating into non-zero gradients; two grouped runs equal."""
+    with and without bias gradients, accumulating into non-zero gradients; two grouped runs equal.  The last item (one 32-row split:
+    it cannot join the group) adds into the dW / db of an earlier grouped item: the sums stay in array order."""
     import ctypes as C
     from dpmn_amd._abi import lib, check, dptr, stream, TnItem
     shapes = [(49152, 96, 384, True), (49152, 384, 96, True), (49152, 96, 32, True), (49152, 96, 96, False), (49152, 96, 96, True),
-              (49152, 192, 96, True), (3072, 96, 384, True), (1001, 144, 48, True), (515, 16, 96, False)]
+              (49152, 192, 96, True), (3072, 96, 384, True), (1001, 144, 48, True), (515, 16, 96, False), (32, 96, 96, True)]
+    shared = {len(shapes) - 1: 4}        # item -> the earlier item whose dW / db it accumulates into
     ops_ = []
     for i, (M, N, K, with_db) in enumerate(shapes):
         ops_.append((u("gdy%d" % i, (M, N)).to(dev), u("gx%d" % i, (M, K)).to(dev), u("gdw%d" % i, (N, K)).to(dev),
@@ -156,9 +158,9 @@ def test_grouped_linear_weight_gradients_equal_the_single_calls_bitwise(dev):
 
     def single():
         out = []
-        for dy, x, dw0, db0 in ops_:
+        for i, (dy, x, dw0, db0) in enumerate(ops_):
             M, N, K = dy.shape[0], dy.shape[1], x.shape[1]
-            dw, db = dw0.clone(), None if db0 is None else db0.clone()
+            dw, db = out[shared[i]] if i in shared else (dw0.clone(), None if db0 is None else db0.clone())
             ws = torch.empty(lib.dpmn_gemm_tn_partial_bytes(M, N, K) // 4, device=dev)
             check(lib.dpmn_gemm_tn_f32(dptr(dy), dptr(x), dptr(dw), dptr(db, True), M, N, K, dptr(ws), ws.numel() * 4, stream()))
             out.append((dw, db))
@@ -169,7 +171,7 @@ def test_grouped_linear_weight_gradients_equal_the_single_calls_bitwise(dev):
         items, keep, out = (TnItem * len(ops_))(), [], []
         for i, (dy, x, dw0, db0) in enumerate(ops_):
             M, N, K = dy.shape[0], dy.shape[1], x.shape[1]
-            dw, db = dw0.clone(), None if db0 is None else db0.clone()
+            dw, db = out[shared[i]] if i in shared else (dw0.clone(), None if db0 is None else db0.clone())
             ws = torch.empty(lib.dpmn_gemm_tn_partial_bytes(M, N, K) // 4, device=dev)
             items[i] = TnItem(dptr(dy), dptr(x), dptr(dw), dptr(db, True), M, N, K, dptr(ws), ws.numel() * 4)
             keep.append(ws)
