@@ -43,33 +43,22 @@ __device__ __forceinline__ unsigned source_row(int t, int H, int W, int lgW, int
 }
 
 
-// xor-16 / xor-32 butterflies of the softmax / LayerNorm row reductions.  FA_PERMLANE: v_permlane16_swap / v_permlane32_swap (gfx950,
-// one VALU instruction) instead of ds_bpermute (a round trip through the LDS pipe); the sums and maxima are bitwise the same.
-#ifndef FA_PERMLANE
-#define FA_PERMLANE 1
-#endif
+// xor-16 / xor-32 butterflies of the softmax / LayerNorm row reductions: v_permlane16_swap / v_permlane32_swap (gfx950, one VALU
+// instruction) instead of ds_bpermute (a round trip through the LDS pipe); the sums and maxima are bitwise the same.
 typedef unsigned fa_u32x2 __attribute__((ext_vector_type(2)));
 // v (op) v[lane ^ D]: after the swap of a register with itself the two results hold (own, partner) in one half of every lane pair
 // and (partner, own) in the other -- the operation is commutative, so no select is needed
 template <int D>
 __device__ __forceinline__ float fa_xor_sum(float v) {
-#if FA_PERMLANE
   const unsigned u = __float_as_uint(v);
   const fa_u32x2 r = D == 16 ? __builtin_amdgcn_permlane16_swap(u, u, false, false) : __builtin_amdgcn_permlane32_swap(u, u, false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-#else
-  return v + __shfl_xor(v, D, 64);
-#endif
 }
 template <int D>
 __device__ __forceinline__ float fa_xor_max(float v) {
-#if FA_PERMLANE
   const unsigned u = __float_as_uint(v);
   const fa_u32x2 r = D == 16 ? __builtin_amdgcn_permlane16_swap(u, u, false, false) : __builtin_amdgcn_permlane32_swap(u, u, false, false);
   return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-#else
-  return fmaxf(v, __shfl_xor(v, D, 64));
-#endif
 }
 
 // mean and 1/sqrt(var + eps) of the 96-value row this lane shares with its 3 kq partners (two-pass, like nn.LayerNorm)
@@ -125,7 +114,7 @@ __device__ __forceinline__ int units_before(long c, int per, const int (&cs)[3])
 int fa_prepare(FusedAttnArgs& a, const float* tq, const float* tkv, const float* lnq_w, const float* lnq_b, const float* lnkv_w,
                const float* lnkv_b, float eps, const float* wq, const float* bq, const float* wkv, const float* bkv,
                const float* const* bias_tables, const int* windows, const int* shifts, int n_groups, int heads_per_group, int B, int H,
-               int W, int C, void* workspace, const int* cost_ws, int blocks_per_cu, long* blocks);
+               int W, int C, void* workspace, const int* cost_ws, long* blocks);
 void fa_fold(const FusedAttnArgs& a, hipStream_t st);      // k_attn_fold: the folded weights of this call into a.folded
 
 }  // namespace dpmn_fa

@@ -23,15 +23,7 @@
 //   5. O^T = V^T . P: B = P (registers), A = V^T read column-wise from the LDS copy of V (the only transpose).
 // Algorithmic work per unit: projections 2*64*96*96 = 1.18 MFLOP + attention 4*N*16 FLOP per (token, head); bytes: the unit's
 // 128 input rows (49 KB) + 8 KB of output -- the kernel is MFMA-bound (AI ~57 FLOP/B).
-#include <cstdlib>
 #include "attn_fused.h"
-
-#ifndef FA_SKIP
-#define FA_SKIP 0
-#endif
-#ifndef FA_SCHED
-#define FA_SCHED 2      // timing ablations only (tools/variants): 1 no LayerNorm, 2 no projection MFMAs, 4 no attention, 8 no barrier, 16 no row loads
-#endif
 
 #ifndef FA_TIMING
 #define FA_TIMING 0    // tools/fa_timeline.py: s_memtime stamps of the loop phases of wave 0 of the first 64 blocks
@@ -166,10 +158,8 @@ __device__ __forceinline__ void run_units(const FusedAttnArgs& a, int slot, int 
     }
     FA_STAMP(i - first, 0);
     float mq = 0.f, rq = 1.f, mk = 0.f, rk = 1.f;
-    if (!(FA_SKIP & 1)) {
-      row_stats(xq, a.eps, mq, rq);
-      row_stats(xkv, a.eps, mk, rk);
-    }
+    row_stats(xq, a.eps, mq, rq);
+    row_stats(xkv, a.eps, mk, rk);
     const float rqs = rq * QSCALE, nmq = -mq * rq, nmk = -mk * rk;     // (b' and rowsum(W') of the q rows are pre-scaled)
 
     FA_STAMP(i - first, 1);
@@ -177,8 +167,6 @@ __device__ __forceinline__ void run_units(const FusedAttnArgs& a, int slot, int 
     f32x4 qa[2], ka[2], va[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) { qa[h] = (f32x4){0.f, 0.f, 0.f, 0.f}; ka[h] = qa[h]; va[h] = qa[h]; }
-    if (FA_SKIP & 2) { qa[0] = xq[0] + xq[2]; qa[1] = xq[1] + xq[3]; ka[0] = xkv[0] + xq[4]; ka[1] = xkv[1] + xq[5]; va[0] = xkv[2] + xkv[4]; va[1] = xkv[3] + xkv[5]; }
-    else
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
       f32x4 wf[6];
@@ -195,7 +183,6 @@ __device__ __forceinline__ void run_units(const FusedAttnArgs& a, int slot, int 
       }
     }
     FA_STAMP(i - first, 2);
-#if FA_SCHED
     // issue order of the block above: the row statistics (vector ALU, independent of the MFMAs: they eat RAW rows) are
     // dealt into the shadows of the 144 projection MFMAs, two vector instructions behind each
 #pragma unroll
@@ -204,10 +191,9 @@ __device__ __forceinline__ void run_units(const FusedAttnArgs& a, int slot, int 
 #pragma unroll
       for (int m = 0; m < 24; ++m) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, FA_SCHED, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
       }
     }
-#endif
     // y = rstd * acc - (rstd * mean) * rowsum(W') + b'   (two fma per value; the q rows of b' / rowsum(W') / rstd carry
     // head_dim ** -0.5 (pgrm.py:230-231) times log2(e): the softmax below is exp2(s - max)).  v, k, q in turn: short live ranges.
 #pragma unroll
@@ -249,16 +235,10 @@ __device__ __forceinline__ void run_units(const FusedAttnArgs& a, int slot, int 
     }
     // ---- the row registers are dead: send for unit i+1 now, the loads fly during this unit's attention (and the partner
     // wave's projection).  The index is clamped, not predicated: a load inside a branch makes hipcc drain vmcnt(0) at the join.
-    if (!(FA_SKIP & 16)) load_rows<WS>(a, xcd, i + 1 < last ? i + 1 : i, shift, wave, lr, kq, xq, xkv);
+    load_rows<WS>(a, xcd, i + 1 < last ? i + 1 : i, shift, wave, lr, kq, xq, xkv);
     FA_STAMP(i - first, 3);
-    if (!(FA_SKIP & 8)) __syncthreads();
+    __syncthreads();
     FA_STAMP(i - first, 4);
-    if (FA_SKIP & 4) {
-      float* dst = a.out + ((size_t)b * L + t) * FC + FCG * g + 4 * kq;
-      *reinterpret_cast<f32x4*>(dst) = qa[0] + ka[0] + va[0];
-      *reinterpret_cast<f32x4*>(dst + 16) = qa[1] + ka[1] + va[1];
-      continue;
-    }
 
     unsigned masked = 0u;                  // bit (4 kt + r): key in another shift-mask region than my query (pgrm.py:240-243)
     if (shift > 0) {
@@ -352,7 +332,6 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_window_attn(FusedAttnArgs a) 
   const int ni = xcd < a.B ? (a.B - xcd + 7) / 8 : 0;
   const int per = ni * S;                  // units per slot on this XCD
   if (per == 0) return;
-  if (FA_SKIP & 64) return;
   const int* nb = a.nblk[ni == (a.B + 7) / 8 ? 0 : 1];
   if (nb[0] > 0) {
     // one slot per block: a block never changes the staged weights, and the units of a slot are dealt evenly (+-1) to its
@@ -389,8 +368,6 @@ extern "C" {
 int dpmn_ln_qkv_window_attn_supported(int C, int n_groups, int heads_per_group, const int* windows, int H, int W) {
   if (C != FC || n_groups != 3 || heads_per_group != 2 || !windows || (H * W) % 64 != 0) return 0;
   if ((H & (H - 1)) || (W & (W - 1)) || H < 8 || W < 8) return 0;      // index math uses shifts / masks (16x64 and 32x128 token grids)
-  static const int off = getenv("DPMN_ATTN_FUSED") && atoi(getenv("DPMN_ATTN_FUSED")) == 0;
-  if (off) return 0;
   for (int g = 0; g < 3; ++g) {
     const int ws = windows[g];
     if (!(ws == 2 || ws == 4 || ws == 8) || H % ws || W % ws) return 0;
@@ -407,7 +384,7 @@ void fa_fold(const FusedAttnArgs& a, hipStream_t st) { hipLaunchKernelGGL(k_attn
 int fa_prepare(FusedAttnArgs& a, const float* tq, const float* tkv, const float* lnq_w, const float* lnq_b, const float* lnkv_w,
                const float* lnkv_b, float eps, const float* wq, const float* bq, const float* wkv, const float* bkv,
                const float* const* bias_tables, const int* windows, const int* shifts, int n_groups, int heads_per_group, int B, int H,
-               int W, int C, void* workspace, const int* cost_ws, int blocks_per_cu, long* blocks_out) {
+               int W, int C, void* workspace, const int* cost_ws, long* blocks_out) {
   DPMN_REQUIRE(tq && tkv && lnq_w && lnq_b && lnkv_w && lnkv_b && wq && bq && wkv && bkv && bias_tables && windows && shifts,
                "ln_qkv_window_attn: null pointer");
   DPMN_REQUIRE(B > 0, "ln_qkv_window_attn: empty batch");
@@ -440,7 +417,7 @@ int fa_prepare(FusedAttnArgs& a, const float* tq, const float* tkv, const float*
     n_cu = prop.multiProcessorCount > 8 ? prop.multiProcessorCount / 8 * 8 : 8;
   }
   const long slabs = (long)B * (H * W / 64);
-  long blocks = (long)blocks_per_cu * n_cu;          // resident blocks per CU x CUs; a multiple of 8
+  long blocks = 2L * n_cu;          // 2 resident blocks per CU (78 KB of LDS each) x CUs; a multiple of 8
   const long need = ((3 * slabs + 7) / 8) * 8;
   if (blocks > need) blocks = need;
   {
@@ -463,8 +440,6 @@ int fa_prepare(FusedAttnArgs& a, const float* tq, const float* tkv, const float*
           if (best < 0 || key < best) { best = key; a.nblk[w][0] = n0; a.nblk[w][1] = n1; a.nblk[w][2] = n[2]; }
         }
     }
-    static const int contiguous = getenv("DPMN_FA_CONTIG") ? atoi(getenv("DPMN_FA_CONTIG")) : 0;
-    if (contiguous) a.nblk[0][0] = a.nblk[1][0] = 0;
   }
   *blocks_out = blocks;
   return DPMN_OK;
@@ -482,10 +457,9 @@ static int fused_attn_launch(const float* tq, const float* tkv, const float* lnq
                "ln_qkv_window_attn_train: q_out / kv_out must both be given or both be null (the recomputing backward needs neither), p_drop in [0, 1)");
   FusedAttnArgs a{};
   const int cost_ws[3] = {183, 151, 146};      // cycles / 100 per unit at B = 48 (tools/fa_timeline.py, round 3)
-  static const int bpc = getenv("DPMN_FA_BPC") ? atoi(getenv("DPMN_FA_BPC")) : 2;      // 2 resident blocks per CU (78 KB of LDS each)
   long blocks = 0;
   const int rc = fa_prepare(a, tq, tkv, lnq_w, lnq_b, lnkv_w, lnkv_b, eps, wq, bq, wkv, bkv, bias_tables, windows, shifts, n_groups,
-                            heads_per_group, B, H, W, C, workspace, cost_ws, bpc, &blocks);
+                            heads_per_group, B, H, W, C, workspace, cost_ws, &blocks);
   if (rc != DPMN_OK) return rc;
   a.q_out = q_out; a.kv_out = kv_out; a.p_drop = p_drop; a.inv_keep = train ? 1.0f / (1.0f - p_drop) : 1.0f; a.seed = seed;
   a.out = out;

@@ -15,7 +15,6 @@
 //   3. barrier; k, v -> LDS over the dead weights; q stays in registers (accumulator layout = B-operand layout of S^T = K Q^T);
 //   4. per (query tile, head): S^T over the key tiles of the query's window (16 / 4 / 1), + bias table + shift mask, softmax in
 //      exp2, O^T = V^T P with P fed from the accumulator registers, window-major write without un-roll (quirk Q1).
-#include <cstdlib>
 #include "common.h"
 
 namespace {
@@ -334,8 +333,6 @@ extern "C" {
 int dpmn_ln_qkv_window_attn_d32_supported(int C, int n_groups, int heads_per_group, const int* windows, int H, int W) {
   if (C != FC || n_groups != 3 || heads_per_group != 2 || !windows || (H * W) % SET != 0) return 0;
   if ((H & (H - 1)) || (W & (W - 1)) || H < 16 || W < 16) return 0;
-  static const int off = getenv("DPMN_ATTN_FUSED") && atoi(getenv("DPMN_ATTN_FUSED")) == 0;
-  if (off) return 0;
   for (int g = 0; g < 3; ++g) {
     const int ws = windows[g];
     if (!(ws == 4 || ws == 8 || ws == 16) || H % ws || W % ws) return 0;

@@ -18,28 +18,11 @@
 //     statistics of pass A;  dV^T = dO^T (P o M),  dK^T = Q'^T dS (A operands column-wise from LDS).
 // 8x8 windows: the unit is one window, 4 key / query tiles per pass (368 MFMAs per wave and unit with the projection);
 // 4x4 / 2x2: the wave's tile is self-contained (200 MFMAs), no block barrier is needed at all.
-#include <cstdlib>
 #include "attn_fused.h"
 
 using namespace dpmn_fa;
 
 namespace {
-
-#ifndef FAB_SCHED
-#define FAB_SCHED 1       // 1: the forward's issue pattern for the projection (row statistics in the MFMA shadows)
-#endif
-#ifndef FAB_HB
-#define FAB_HB 1          // scheduling barrier between the two heads of a pass
-#endif
-#ifndef FAB_HBB
-#define FAB_HBB 1         // the same in pass B
-#endif
-#ifndef FAB_QB
-#define FAB_QB 0          // 8x8: scheduling barrier between the query tiles of pass B (measured: 75.7 us with, 73.3 us without)
-#endif
-#ifndef FAB_SKIP
-#define FAB_SKIP 0        // timing ablations only (tools/build_variants.sh): 1 no pass A, 2 no pass B, 4 no projection MFMAs
-#endif
 
 #ifndef FAB_TIMING
 #define FAB_TIMING 0      // tools/fab_timeline.py: s_memtime stamps of the loop phases of wave 0 of every block
@@ -160,8 +143,6 @@ __device__ __forceinline__ void run_units_bwd(const FusedAttnArgs& a, int slot, 
     f32x4 qa[2], ka[2], va[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) { qa[h] = (f32x4){0.f, 0.f, 0.f, 0.f}; ka[h] = qa[h]; va[h] = qa[h]; }
-    if (FAB_SKIP & 4) { qa[0] = xq[0] + xq[2]; qa[1] = xq[1] + xq[3]; ka[0] = xkv[0] + xq[4]; ka[1] = xkv[1] + xq[5]; va[0] = xkv[2] + xkv[4]; va[1] = xkv[3] + xkv[5]; }
-    else
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
       f32x4 wf[6];
@@ -177,7 +158,7 @@ __device__ __forceinline__ void run_units_bwd(const FusedAttnArgs& a, int slot, 
         va[1] = mfma16(wf[5][s], xkv[c][s], va[1]);
       }
     }
-#if FAB_SCHED
+    // the forward's issue pattern: the row statistics go into the shadows of the projection MFMAs
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
       __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
@@ -187,7 +168,6 @@ __device__ __forceinline__ void run_units_bwd(const FusedAttnArgs& a, int slot, 
         __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
       }
     }
-#endif
     FAB_STAMP(i - first, 1);
     unit_sync<WS>();                       // the previous unit's pass B is done with the tiles
     FAB_STAMP(i - first, 2);
@@ -243,10 +223,9 @@ __device__ __forceinline__ void run_units_bwd(const FusedAttnArgs& a, int slot, 
         for (int r = 0; r < 4; ++r)
           maskedA |= (reg_s[(WS == 8 ? 16 * kt : 16 * wave) + 4 * kq + r] != my_reg ? 1u : 0u) << (4 * kt + r);
     }
-    if (!(FAB_SKIP & 1))
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      if (FAB_HB) __builtin_amdgcn_sched_barrier(0);   // one head at a time: interleaving the heads doubles the live score registers
+      __builtin_amdgcn_sched_barrier(0);   // one head at a time: interleaving the heads doubles the live score registers
       f32x4 sacc[KT], dpt[KT];
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) {
@@ -353,14 +332,12 @@ __device__ __forceinline__ void run_units_bwd(const FusedAttnArgs& a, int slot, 
       for (int h = 0; h < 2; ++h)
         zB[h] = drop_z0(a.seed, ((((unsigned long long)b * 3 + g) * 2 + h) * L + (t0 + (WS == 8 ? 0 : 16 * wave) + 4 * kq)) * N + (16 * wave + lr) % N);
     }
-    if (!(FAB_SKIP & 2))
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      if (FAB_HBB) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);      // one head at a time, as in pass A
       f32x4 dva0 = (f32x4){0.f, 0.f, 0.f, 0.f}, dka0 = dva0, dva1 = dva0, dka1 = dva0;
 #pragma unroll
       for (int qt = 0; qt < KT; ++qt) {
-        if (WS == 8 && FAB_QB) __builtin_amdgcn_sched_barrier(0);
         const int q0 = WS == 8 ? 16 * qt : 16 * wave;
         const f32x4 qf = *reinterpret_cast<const f32x4*>(Qs + (q0 + lr) * LDK + 16 * h + 4 * kq);
         const f32x4 gf = *reinterpret_cast<const f32x4*>(Gs + (q0 + lr) * LDK + 16 * h + 4 * kq);
@@ -490,18 +467,7 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_window_attn_bwd(FusedAttnArgs
 }
 
 
-#ifdef FAB_DIAG
-template <int WS>
-__global__ __launch_bounds__(256, 2) void k_fab_diag(FusedAttnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  run_units_bwd<WS, false>(a, 0, blockIdx.x & 7, blockIdx.x, blockIdx.x + 4, smem);
-}
-template __global__ void k_fab_diag<8>(FusedAttnArgs);
-template __global__ void k_fab_diag<4>(FusedAttnArgs);
-template __global__ void k_fab_diag<2>(FusedAttnArgs);
-#endif
-
-long bwd_grid(int B, int H, int W, int bpc) {
+long bwd_grid(int B, int H, int W) {
   static int n_cu = 0;
   if (!n_cu) {
     int dev = 0;
@@ -509,14 +475,9 @@ long bwd_grid(int B, int H, int W, int bpc) {
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
     n_cu = prop.multiProcessorCount > 8 ? prop.multiProcessorCount / 8 * 8 : 8;
   }
-  long blocks = (long)bpc * n_cu;
+  long blocks = 2L * n_cu;      // 2 resident blocks per CU, as in the forward (fa_prepare)
   const long need = ((3 * (long)B * (H * W / 64) + 7) / 8) * 8;
   return blocks > need ? need : blocks;
-}
-
-int bwd_bpc() {
-  static const int bpc = getenv("DPMN_FAB_BPC") ? atoi(getenv("DPMN_FAB_BPC")) : 2;
-  return bpc;
 }
 
 }  // namespace
@@ -525,7 +486,7 @@ extern "C" {
 
 int dpmn_ln_qkv_window_attn_bwd_part_rows(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return (int)bwd_grid(B, H, W, bwd_bpc());
+  return (int)bwd_grid(B, H, W);
 }
 
 int dpmn_ln_qkv_window_attn_bwd_f32(const float* tq, const float* tkv, const float* lnq_w, const float* lnq_b, const float* lnkv_w,
@@ -537,14 +498,12 @@ int dpmn_ln_qkv_window_attn_bwd_f32(const float* tq, const float* tkv, const flo
   DPMN_REQUIRE(dout && dq && dkv && dtable_parts, "ln_qkv_window_attn_bwd: null pointer");
   DPMN_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "ln_qkv_window_attn_bwd: p_drop outside [0, 1)");
   FusedAttnArgs a{};
-  static const int c8 = getenv("DPMN_FAB_COST8") ? atoi(getenv("DPMN_FAB_COST8")) : 330;
-  static const int c4 = getenv("DPMN_FAB_COST4") ? atoi(getenv("DPMN_FAB_COST4")) : 190;
-  const int cost_ws[3] = {c8, c4, c4};       // 368 / 200 / 200 MFMAs per wave and unit
+  const int cost_ws[3] = {330, 190, 190};       // 368 / 200 / 200 MFMAs per wave and unit
   long blocks = 0;
   const int rc = fa_prepare(a, tq, tkv, lnq_w, lnq_b, lnkv_w, lnkv_b, eps, wq, bq, wkv, bkv, bias_tables, windows, shifts, n_groups,
-                            heads_per_group, B, H, W, C, workspace, cost_ws, bwd_bpc(), &blocks);
+                            heads_per_group, B, H, W, C, workspace, cost_ws, &blocks);
   if (rc != DPMN_OK) return rc;
-  DPMN_REQUIRE(blocks == bwd_grid(B, H, W, bwd_bpc()), "ln_qkv_window_attn_bwd: grid size differs from dpmn_ln_qkv_window_attn_bwd_part_rows");
+  DPMN_REQUIRE(blocks == bwd_grid(B, H, W), "ln_qkv_window_attn_bwd: grid size differs from dpmn_ln_qkv_window_attn_bwd_part_rows");
   a.dout = dout; a.dq = dq; a.dkv = dkv; a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed;
   for (int s = 0; s < 3; ++s) {
     DPMN_REQUIRE(dtable_parts[a.gid[s]], "ln_qkv_window_attn_bwd: null table-gradient partial buffer");

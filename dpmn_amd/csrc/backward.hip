@@ -766,7 +766,7 @@ static int gemm_tn_impl(const float* dy, const float* x, float* dw, float* db, i
   // PGRM block: 96 / 192 / 384) and the byte offsets fit the buffer instructions
   ProfScope prof(PT_GEMM_TN, as_stream(stream), 2.0 * M * (double)N * K, 4.0 * ((double)M * N + (double)M * K + (double)splits * ((double)N * K + N)));
   const bool reg_ok = part && N % 48 == 0 && K % 48 == 0 && (size_t)rows * (N > K ? N : K) * 4 < (1ull << 31);
-  if (reg_ok && x3_on(64))       // mode 2: the same partials on six bf16 MFMAs per tile (gemm_tn_x3.hip)
+  if (reg_ok && g_dpmn_x3)       // mode 2: the same partials on six bf16 MFMAs per tile (gemm_tn_x3.hip)
     dpmn_gemm::x3_launch_tn(dy, x, M, N, K, rows, db, part, grid, as_stream(stream));
   else if (reg_ok)
     hipLaunchKernelGGL(k_gemm_tn_reg<8>, grid, dim3(256), 0, as_stream(stream), dy, x, M, N, K, rows, db, part);
@@ -802,7 +802,7 @@ int dpmn_gemm_tn_group_f32(const dpmn_tn_item* items, int n, dpmn_stream_t strea
     if (g.n == 0) return DPMN_OK;
     {
       ProfScope prof(PT_GEMM_TN, as_stream(stream), flops, bytes);
-      if (x3_on(64)) dpmn_gemm::x3_launch_tn_multi(g, as_stream(stream));
+      if (g_dpmn_x3) dpmn_gemm::x3_launch_tn_multi(g, as_stream(stream));
       else hipLaunchKernelGGL(k_gemm_tn_reg_multi<8>, dim3(g.first[g.n]), dim3(256), 0, as_stream(stream), g);
       DPMN_CHECK_LAUNCH();
     }

@@ -1,6 +1,5 @@
 // PGRM-specific backward kernels (autograd of model/pgrm.py in the reference): window attention, SKConv gate,
 // depthwise conv, elementwise helpers.  Linear / conv data- and weight-gradients use gemm.hip / conv*.hip / backward.hip.
-#include <cstdlib>
 #include "common.h"
 
 namespace {
@@ -597,11 +596,7 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
   r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
-#ifndef DWB_SKIP
-#define DWB_SKIP 0        // timing ablations only: 1 no GELU arithmetic, 2 no stencil arithmetic
-#endif
 __device__ __forceinline__ void gelu_both(float x, float& g, float& d) {
-  if (DWB_SKIP & 1) { g = x; d = 1.0f; return; }
   const float ax = fabsf(x * 0.70710678118654752440f);
   const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
   const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
@@ -715,8 +710,6 @@ __global__ __launch_bounds__(256, KEEP ? 2 : 1) void k_dwconv_bwd(const float* _
       const int yy = i / r4, x4 = (i - yy * r4) * 4;
       float a[4] = {0.f, 0.f, 0.f, 0.f};
       const float4 gc = *reinterpret_cast<const float4*>(tg + (yy + 1) * LD + 4 + x4);     // dg at the 4 output pixels
-      if (DWB_SKIP & 2) { a[0] = gc.x; a[1] = gc.y; a[2] = gc.z; a[3] = gc.w; aw[0] += gc.x; }
-      else
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky) {
         // dP[y][x] = sum_k dg[y - ky + 1][x - kx + 1] w[ky][kx] : dg row (yy + 2 - ky) of the halo tile, columns x4 - 1 .. x4 + 4
@@ -1211,9 +1204,8 @@ static int window_attn_bwd_impl(const float* q, const float* kv, const float* co
     const int ws = windows[g], sh = shifts[g];
     DPMN_REQUIRE(H % ws == 0 && W % ws == 0 && sh >= 0 && sh < ws, "window_attn_bwd: bad window / shift");
     int rc = DPMN_ERR_ARG;
-    static const int wb_mfma = getenv("DPMN_WATTN_MFMA") ? atoi(getenv("DPMN_WATTN_MFMA")) : 1;
     const long slabs = (long)B * (H * W / 64);
-    if (ws == 8 && D == 16 && wb_mfma) {
+    if (ws == 8 && D == 16) {
       if (rows_out) rows_out[g] = (int)slabs;
       if (p_drop > 0.f)
         hipLaunchKernelGGL((k_window_attn8_bwd_mfma<true>), dim3((unsigned)slabs), dim3(128), 0, st, q, kv, bias_tables[g],
@@ -1224,7 +1216,7 @@ static int window_attn_bwd_impl(const float* q, const float* kv, const float* co
       DPMN_CHECK_LAUNCH();
       continue;
     }
-    if (wb_mfma && ((ws == 16 && (D == 32 || D == 16)) || (ws == 8 && D == 32))) {
+    if ((ws == 16 && (D == 32 || D == 16)) || (ws == 8 && D == 32)) {
       // 256- / 64-token windows on the matrix cores (wattn_bwd_mfma.hip): one block per (window, head)
       rc = dpmn_wattn_bwd_mfma(ws, D, q, kv, bias_tables[g], dout, dq, dkv, dtables[g], B, H, W, C, g, sh, p_drop, seed, st, part_mode,
                                rows_out ? rows_out + g : nullptr);
@@ -1235,7 +1227,7 @@ static int window_attn_bwd_impl(const float* q, const float* kv, const float* co
 #define WB_CASE(WSV, DV) if (ws == WSV && D == DV) rc = p_drop > 0.f \
       ? launch_wattn_bwd<WSV, DV, true>(q, kv, bias_tables[g], dout, dq, dkv, dtables[g], B, H, W, C, g, sh, p_drop, seed, st, part_mode) \
       : launch_wattn_bwd<WSV, DV, false>(q, kv, bias_tables[g], dout, dq, dkv, dtables[g], B, H, W, C, g, sh, 0.f, 0ull, st, part_mode); else
-    WB_CASE(2, 16) WB_CASE(4, 16) WB_CASE(8, 16) WB_CASE(4, 32) WB_CASE(8, 32)
+    WB_CASE(2, 16) WB_CASE(4, 16) WB_CASE(4, 32)
     return dpmn_set_error(DPMN_ERR_ARG, "window_attn_bwd: unsupported (window, head_dim)");
 #undef WB_CASE
     if (rc != DPMN_OK) return rc;
@@ -1340,14 +1332,6 @@ int dpmn_sk_feats_grad_f32(const float* dout, const float* feats, const float* d
 }
 
 // KEEP variant: persistent, 2 blocks per CU (256 registers per wave for the prefetch), never more blocks than planes / 4
-// rows per band of the generic (non-KEEP) kernel: whole planes up to 32 x 32, 16-row bands above; DPMN_DW_BAND overrides (pgrm.hip has the twin)
-static int dwconv_bwd_band_rows(int r) {
-  static const int env = getenv("DPMN_DW_BAND") ? atoi(getenv("DPMN_DW_BAND")) : -1;
-  int rb = env >= 0 ? env : (r > 32 && r % 16 == 0 ? 16 : r);
-  if (rb <= 0 || rb > r || r % rb != 0) rb = r;
-  return rb;
-}
-
 static long dwconv_bwd_grid(long planes) {
   static int n_cu = 0;
   if (!n_cu) {
@@ -1355,8 +1339,7 @@ static long dwconv_bwd_grid(long planes) {
     hipDeviceProp_t prop;
     n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
   }
-  static const int bpc = getenv("DPMN_DWB_BPC") ? atoi(getenv("DPMN_DWB_BPC")) : 2;
-  const long want = (long)bpc * n_cu, need = (planes + 3) / 4;
+  const long want = 2L * n_cu, need = (planes + 3) / 4;
   return want < need ? want : need;
 }
 
@@ -1364,7 +1347,7 @@ int dpmn_dwconv3x3_bwd_f32(const float* P, const float* dg, const float* w, floa
                            dpmn_stream_t stream) {
   DPMN_REQUIRE(P && dg && w && dP && dw && db && r >= 4 && r <= 64 && r % 4 == 0, "dwconv_bwd: plane side must be a multiple of 4 in [4, 64]");
   const long planes = (long)B * Ch;
-  const int rb = dwconv_bwd_band_rows(r);
+  const int rb = dwconv_band_rows(r);
   const size_t smem = (size_t)8 * (rb + 2) * (r + 8) * 4;
   if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwconv_bwd<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   hipLaunchKernelGGL(k_dwconv_bwd<false>, dim3((unsigned)((planes * (r / rb) + 3) / 4)), dim3(256), smem, as_stream(stream), P, dg, w, dP, dw, db, Ch, r,
@@ -1380,7 +1363,7 @@ int dpmn_dwconv3x3_bwd_fused_f32(const float* P, const float* dg, const float* g
   DPMN_REQUIRE(!out_gelu_bwd || in_gelu, "dwconv_bwd_fused: out_gelu_bwd needs P to be the pre-activation (in_gelu)");
   const long planes = (long)B * Ch;
   const bool keep = in_gelu && out_gelu_bwd && gpre && r == 32;
-  const int rb = keep ? r : dwconv_bwd_band_rows(r);
+  const int rb = keep ? r : dwconv_band_rows(r);
   const size_t smem = (size_t)8 * (rb + 2) * (r + 8) * 4;
   // dP (9 taps) + dw (9 taps) = 36 FLOPs per element; P, dg (, gpre) read, dP written
   ProfScope prof(PT_DWCONV_BWD, as_stream(stream), 36.0 * planes * r * r, 4.0 * (gpre ? 4 : 3) * (double)planes * r * r);
@@ -1396,7 +1379,7 @@ int dpmn_dwconv3x3_bwd_fused_f32(const float* P, const float* dg, const float* g
 // workspace of the atomics-free variant: one [Ch * 9 | Ch] partial row per (image, band)
 size_t dpmn_dwconv3x3_bwd_det_bytes(int B, int Ch, int r) {
   if (B <= 0 || Ch <= 0 || r <= 0) return 0;
-  const int rb = dwconv_bwd_band_rows(r);      // (the whole-plane KEEP kernel of the 32 x 32 planes needs B rows: never more than this)
+  const int rb = dwconv_band_rows(r);      // (the whole-plane KEEP kernel of the 32 x 32 planes needs B rows: never more than this)
   return (size_t)B * (r / rb) * Ch * 10 * sizeof(float);
 }
 
@@ -1409,7 +1392,7 @@ int dpmn_dwconv3x3_bwd_fused_det_f32(const float* P, const float* dg, const floa
   if (dpmn_dwconv3x3_bwd_det_bytes(B, Ch, r) > ws_bytes) return dpmn_set_error(DPMN_ERR_WORKSPACE, "dwconv_bwd_fused_det: workspace too small (dpmn_dwconv3x3_bwd_det_bytes)");
   const long planes = (long)B * Ch;
   const bool keep = in_gelu && out_gelu_bwd && gpre && r == 32;
-  const int rb = keep ? r : dwconv_bwd_band_rows(r);
+  const int rb = keep ? r : dwconv_band_rows(r);
   const size_t smem = (size_t)8 * (rb + 2) * (r + 8) * 4;
   // dP (9 taps) + dw (9 taps) = 36 FLOPs per element; P, dg (, gpre) read, dP written
   ProfScope prof(PT_DWCONV_BWD, as_stream(stream), 36.0 * planes * r * r, 4.0 * (gpre ? 4 : 3) * (double)planes * r * r);

@@ -224,11 +224,6 @@ __device__ __forceinline__ void x3_split4t(const float4& v, uint2& h, uint2& m, 
   x3_split2t(v.x, v.y, h.x, m.x, l.x);
   x3_split2t(v.z, v.w, h.y, m.y, l.y);
 }
-// debugging / A-B switch: DPMN_X3_OFF bit mask of kernel families that keep the fp32 kernel in mode 2
-// (1 implicit-GEMM conv, 2 halo conv, 4 pointwise GEMM, 8 k-loop GEMM 64 x 96, 16 conv weight gradient, 32 k-loop GEMM 128 x 128,
-// 64 Linear weight gradient dY^T X, 128 whole-K token GEMMs with the rows in registers: k_gemm_rowreg, k_sk_mlp_in)
-int dpmn_x3_off_mask();
-static inline bool x3_on(int family_bit) { return g_dpmn_x3 && !(dpmn_x3_off_mask() & family_bit); }
 struct ProfScope {
   int slot;
   hipStream_t st;
@@ -247,3 +242,6 @@ inline void ProfScope::close() {
 }
 inline ProfScope::~ProfScope() { close(); }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// rows per band of the generic depthwise 3x3 kernels (pgrm.hip forward, backward_pgrm.hip backward and its workspace size):
+// whole planes up to 32 x 32, 16-row bands above (r a multiple of 16)
+static inline int dwconv_band_rows(int r) { return r > 32 && r % 16 == 0 ? 16 : r; }

@@ -698,7 +698,7 @@ int launch_halo(const ConvArgs& a, hipStream_t st) {
   // (the rule is per IMAGE -- 8-row tiles x 64-channel blocks of one image, 8 = the 384 blocks of the B = 48 forward -- so that a sample
   //  meets the same kernel family whatever batch it travels in: the bf16x3 and the fp32 kernel differ by fp32-class round-off, which
   //  a mask threshold downstream -- toMask, util.py:27-35 -- can turn into a flipped pixel)
-  if (x3_on(2) && KS == 3 && BN == 64 && blocks8 >= 8L * a.B) {
+  if (g_dpmn_x3 && KS == 3 && BN == 64 && blocks8 >= 8L * a.B) {
     ProfScope prof(PT_CONV_HALO, st, conv_flops(a), conv_bytes(a));
     if (dpmn_conv::x3_launch_halo(a, dim3(a.B * (a.Hin / 8) * (a.Win / 16), cdiv(a.Cout, BN)), st) != 0)
       return dpmn_set_error(DPMN_ERR_LAUNCH, "conv2d: bf16x3 halo launch failed");
@@ -822,7 +822,7 @@ int launch_conv(ConvArgs a, float* ws, size_t ws_bytes, hipStream_t st, unsigned
     simple = simple && (n_aff == 0 || n_aff == n_seg);       // mixed segments: the general UNI path
   // mode 2 ("f32 via bf16x3"): the 128 x 128 tile only -- the operand split of a 64 x 64 tile costs as many vector instructions as the
   // tile has MFMA cycles (measured 93 vs 88 us forward); 128 x 64 tiles lost to the fp32 64 x 64 tile too (73.7 vs 60.1 us)
-  if (x3_on(1) && simple && BM == 128 && BN == 128) {
+  if (g_dpmn_x3 && simple && BM == 128 && BN == 128) {
     if (dpmn_conv::x3_launch_igemm(n_aff != 0, a, grid, st) != 0) return dpmn_set_error(DPMN_ERR_LAUNCH, "conv2d: bf16x3 launch failed");
   } else
   if (g_dpmn_bf16 && simple && BM == BN && (BM == 128 || BM == 64)) {

@@ -195,15 +195,10 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(WgArgs a) {
   __syncthreads();
   int stage = 0;
   for (int m0 = m_lo; m0 < m_hi; m0 += BMc) {
-#ifdef WG_NOLOAD
-    const bool more = false;
-#else
     const bool more = m0 + BMc < m_hi;
-#endif
     if (more) gload(m0 + BMc);
     __builtin_amdgcn_sched_barrier(0);   // keep the loads' consumers (transform + LDS store) behind the MFMA block:
                                          // the scheduler otherwise hoists them, and their vmcnt(0), in front of it
-#ifndef WG_NOMFMA
 #pragma unroll
     for (int ks = 0; ks < BMc / 4; ++ks) {
       const int row = ks * 4 + kq;
@@ -228,7 +223,6 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(WgArgs a) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[i][j] = mfma16(av[i], bv[j], acc[i][j]);
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);
     if (WG_STAGES == 2) {
       // sstore writes the OTHER stage (its last readers passed the barrier of the previous chunk); the MFMA loop above read `stage`
@@ -277,11 +271,7 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(WgArgs a) {
       for (int r = 0; r < 4; ++r) {
         const int ii = kq * 4 + r;
         const int n = n_blk + (NI == 1 ? ii : (i >> 2) * 64 + ii * 4 + (i & 3));
-#ifdef WG_NOATOMIC
-        if (n < a.co_lim && acc[i][j][r] == 1.2345f) dst[(long)n * a.s_co] = 1.f;
-#else
         if (n < a.co_lim) atomicAdd(dst + (long)n * a.s_co, acc[i][j][r]);
-#endif
       }
   }
 }
@@ -865,7 +855,7 @@ static int launch_wgrad(const dpmn_conv_desc* d, const float* dy, float* dw, int
   if (p2) {
     for (a.lgW = 0; (1 << a.lgW) < a.Wp; ++a.lgW) {}
     for (a.lgHW = 0; (1 << a.lgHW) < a.Hp * a.Wp; ++a.lgHW) {}
-    if (x3_on(16) && bn != 16 && dpmn_conv::x3_wgrad_ok(a, bn, bk)) {
+    if (g_dpmn_x3 && bn != 16 && dpmn_conv::x3_wgrad_ok(a, bn, bk)) {
       if (dpmn_conv::x3_launch_wgrad(a, bn, bk, grid, as_stream(stream)) != 0) return dpmn_set_error(DPMN_ERR_LAUNCH, "conv2d_wgrad: bf16x3 launch failed");
     } else if (bn == 16) hipLaunchKernelGGL((k_conv_wgrad<16, 256, true>), grid, dim3(256), 0, as_stream(stream), a);
     else if (bn == 64 && bk == 128) hipLaunchKernelGGL((k_conv_wgrad<64, 128, true>), grid, dim3(256), 0, as_stream(stream), a);

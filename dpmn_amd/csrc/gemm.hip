@@ -1151,7 +1151,7 @@ int launch_rowreg(const float* x, int ldx, const float* w, float* y, int ldy, in
   }
   const int tiles = M / (EPI == 4 ? 32 : 16), ny = N / 96;      // work items of a wave (pairs of 16-row tiles under RR_EPI 4)
   // resident waves: LDS-limited blocks per CU x 4; every wave gets the same number of tiles when that divides evenly
-  const bool x3 = (PRO == PRO_NONE || PRO == PRO_LN) && (K == 96 || K == 192) && x3_on(128);
+  const bool x3 = (PRO == PRO_NONE || PRO == PRO_LN) && (K == 96 || K == 192) && g_dpmn_x3;
   // (mode 2: the weight planes are 1.5x the fp32 copy -- two blocks per CU at K = 96, one at K = 192 -- and a tile's MFMAs take 0.4x the
   //  time, so two tiles per wave are enough to overlap: 96 -> 384 at M = 49152 30.3 vs 33.2 us)
   const int per_cu = x3 ? (K <= 96 ? 2 : 1) : (smem <= 40 * 1024 ? 3 : (smem <= 80 * 1024 ? 2 : 1));
@@ -1291,7 +1291,7 @@ int dpmn_linear_f32(const float* x, const float* w, const float* bias, const flo
   DPMN_REQUIRE(K % 32 == 0, "linear: K must be a multiple of 32");
   dim3 grid(cdiv(M, 64), cdiv(N, 96));
   ProfScope prof(PT_GEMM_KLOOP, as_stream(stream), 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)M * N * (res1 ? 2 : 1) + (double)N * K));
-  if (x3_on(8)) dpmn_gemm::x3_launch_kloop(x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L, grid, as_stream(stream));
+  if (g_dpmn_x3) dpmn_gemm::x3_launch_kloop(x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L, grid, as_stream(stream));
   else hipLaunchKernelGGL(k_gemm_kloop, grid, dim3(256), 0, as_stream(stream), x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
@@ -1309,7 +1309,7 @@ int dpmn_linear_drop_f32(const float* x, const float* w, const float* bias, cons
   e.p_elem = p_elem; e.p_row = p_row; e.seed_elem = seed_elem; e.seed_row = seed_row; e.row_len = row_len;
   dim3 grid(cdiv(M, 64), cdiv(N, 96));
   ProfScope prof(PT_GEMM_KLOOP, as_stream(stream), 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)M * N * 2 + (double)N * K));
-  if (x3_on(8)) dpmn_gemm::x3_launch_kloop(x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L, grid, as_stream(stream));
+  if (g_dpmn_x3) dpmn_gemm::x3_launch_kloop(x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L, grid, as_stream(stream));
   else hipLaunchKernelGGL(k_gemm_kloop, grid, dim3(256), 0, as_stream(stream), x, K, w, K, y, N, M, N, K, e, 0, 0L, 0L);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
@@ -1395,7 +1395,7 @@ int dpmn_sk_mlp_in_drop_f32(const float* cat, const float* attn_vec, const float
                  4.0 * ((double)M * Cc * 4 + (double)M * N + (double)N * Cc + (double)Cc * CG));
 #define SKMLP_LAUNCH(SAVE_) hipLaunchKernelGGL((k_sk_mlp_in<Cc, CG, SAVE_>), dim3(gx, ny), dim3(256), smem, st, cat, attn_vec, rows_per_image, \
                                               w_head, b_head, feats, shortcut, x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N, v_out, n2_out, p_row, seed_row)
-  if (x3_on(128))
+  if (g_dpmn_x3)
     dpmn_gemm::x3_launch_sk_mlp_in(cat, attn_vec, rows_per_image, w_head, b_head, feats, shortcut, x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N,
                                    v_out, n2_out, p_row, seed_row, gx, st);
   else if (v_out) SKMLP_LAUNCH(true);
@@ -1414,7 +1414,7 @@ int dpmn_pointwise_wgrad_f32(const float* dz, const float* g, float* dw, int B, 
   DPMN_REQUIRE(dz && g && dw && L % 32 == 0 && Ch % 4 == 0, "pointwise_wgrad: bad arguments");
   EpiArgs e{nullptr, nullptr, nullptr, nullptr, ACT_NONE, 0.f, 1};   // split over (b, s), atomic accumulation
   dim3 grid(cdiv(Ch, 64), cdiv(Ch, 96), 32);
-  if (x3_on(8)) dpmn_gemm::x3_launch_kloop(dz, L, g, L, dw, Ch, Ch, Ch, B * L, e, L, (long)Ch * L, (long)Ch * L, grid, as_stream(stream));
+  if (g_dpmn_x3) dpmn_gemm::x3_launch_kloop(dz, L, g, L, dw, Ch, Ch, Ch, B * L, e, L, (long)Ch * L, (long)Ch * L, grid, as_stream(stream));
   else hipLaunchKernelGGL(k_gemm_kloop, grid, dim3(256), 0, as_stream(stream), dz, L, g, L, dw, Ch, Ch, Ch, B * L, e, L,
                      (long)Ch * L, (long)Ch * L);
   DPMN_CHECK_LAUNCH();
@@ -1446,7 +1446,7 @@ int dpmn_pointwise_wgrad_det_f32(const float* dz, const float* g, float* dw, int
   if (s128) {
     const int nchunks = B * (L / 32);
     ProfScope prof(PT_GEMM_KLOOP, as_stream(stream), 2.0 * Ch * (double)Ch * B * L, 4.0 * (2.0 * B * Ch * (double)L + (double)Ch * Ch));
-    if (x3_on(32)) dpmn_gemm::x3_launch_kloop128(dz, g, ws, Ch, Ch, L, nchunks, S, (long)Ch * L, (long)Ch * Ch, as_stream(stream));
+    if (g_dpmn_x3) dpmn_gemm::x3_launch_kloop128(dz, g, ws, Ch, Ch, L, nchunks, S, (long)Ch * L, (long)Ch * Ch, as_stream(stream));
     else hipLaunchKernelGGL(k_gemm_kloop128, dim3((Ch / 128) * (Ch / 128) * S), dim3(256), 0, as_stream(stream), dz, g, ws, Ch, Ch, L, nchunks, S,
                        (long)Ch * L, (long)Ch * Ch);
     DPMN_CHECK_LAUNCH();
@@ -1454,7 +1454,7 @@ int dpmn_pointwise_wgrad_det_f32(const float* dz, const float* g, float* dw, int
   }
   EpiArgs e{nullptr, nullptr, nullptr, nullptr, ACT_NONE, 0.f, 0, (long)Ch * Ch};
   dim3 grid(cdiv(Ch, 64), cdiv(Ch, 96), S);
-  if (x3_on(8)) dpmn_gemm::x3_launch_kloop(dz, L, g, L, ws, Ch, Ch, Ch, B * L, e, L, (long)Ch * L, (long)Ch * L, grid, as_stream(stream));
+  if (g_dpmn_x3) dpmn_gemm::x3_launch_kloop(dz, L, g, L, ws, Ch, Ch, Ch, B * L, e, L, (long)Ch * L, (long)Ch * L, grid, as_stream(stream));
   else hipLaunchKernelGGL(k_gemm_kloop, grid, dim3(256), 0, as_stream(stream), dz, L, g, L, ws, Ch, Ch, Ch, B * L, e, L,
                      (long)Ch * L, (long)Ch * L);
   DPMN_CHECK_LAUNCH();
@@ -1465,7 +1465,7 @@ int dpmn_pointwise_f32(const float* g, const float* w, const float* bias, float*
                        dpmn_stream_t stream) {
   DPMN_REQUIRE(g && w && bias && z && Ch % 128 == 0 && L % 128 == 0, "pointwise: Ch and L must be multiples of 128");
   ProfScope prof(PT_GEMM_PW, as_stream(stream), 2.0 * Ch * Ch * (double)L * B, 4.0 * (2.0 * B * Ch * (double)L + (double)Ch * Ch + Ch));
-  if (x3_on(4))       // fp32 product through six bf16 MFMAs of a three-term operand split (dpmn_set_compute_dtype(2), gemm_x3.hip)
+  if (g_dpmn_x3)       // fp32 product through six bf16 MFMAs of a three-term operand split (dpmn_set_compute_dtype(2), gemm_x3.hip)
     dpmn_gemm::x3_launch_pw(g, w, bias, z, B, Ch, L, as_stream(stream));
   else if (g_dpmn_bf16 && Ch % 192 == 0)
     hipLaunchKernelGGL((k_gemm_pw_bf16<192>), dim3(L / 128, Ch / 192, B), dim3(256), 0, as_stream(stream), g, w, bias, z, Ch, L);

@@ -8,7 +8,6 @@
 // Reference lines: PatchEmbed 419-426 (+prior_fusion 548), WindowAttention.forward 197-266,
 // SKConv gate 86-91, Mlp depthwise 34-36, tail 559-565, SwinTransformerBlock.forward 315-331,
 // PGRM.forward 546-565.
-#include <cstdlib>
 #include "common.h"
 
 namespace {
@@ -118,8 +117,8 @@ __global__ __launch_bounds__(256) void k_patch_embed_ln(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------- window attention
-// Work unit ("slab") = 64 consecutive window-major tokens of one (image, group): 1 window of 8x8,
-// 4 of 4x4, 16 of 2x2 (or a quarter of a 16x16 window's queries in the stress config).
+// Work unit ("slab") = 64 consecutive window-major tokens of one (image, group): 4 windows of 4x4 or 16 of 2x2 (head dim 16;
+// the other shapes run on the matrix cores below).
 // Block = 256 threads = 2 slabs x 2 heads, one wave per (slab, head), lane = query row.
 // K/V (and Q, for coalescing) of the slab's windows are staged in LDS: rows of CG floats; every lane
 // of a window reads the same K/V row at a time (LDS broadcast).  Softmax is online over 16-key chunks.
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(256) void k_window_attn(const float* __restrict__ q
   constexpr int N = WS * WS;
   constexpr int CG = 2 * D;
   constexpr int QROWS = 64;                     // queries per slab
-  constexpr int KROWS = (N > 64) ? N : 64;      // keys resident per slab (whole windows)
+  constexpr int KROWS = 64;                     // keys resident per slab (whole windows)
   constexpr int LDR = CG + 4;                   // padded row (floats)
   constexpr int TBL = (2 * WS - 1) * (2 * WS - 1);
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -142,15 +141,10 @@ __global__ __launch_bounds__(256) void k_window_attn(const float* __restrict__ q
   float* base = smem + ((TBL * 2 + 3) & ~3);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int slab_in_blk = wave >> 1, head = wave & 1;
-  // windows larger than a slab (16x16, stress config): the block's two slabs are halves of the SAME window (4 slabs per
-  // window, blocks take aligned pairs), so its K/V are staged once by all 256 threads and shared; Q rows are read straight
-  // from global memory by their lane (2 x 256 K/V rows of 64+4 floats = 139 KB of the CU's 160 KB LDS).
-  constexpr bool BIG = N > 64;
-  float* Qs = BIG ? base : base + slab_in_blk * (QROWS + 2 * KROWS) * LDR;
-  float* Ks = BIG ? base : Qs + QROWS * LDR;
+  float* Qs = base + slab_in_blk * (QROWS + 2 * KROWS) * LDR;
+  float* Ks = Qs + QROWS * LDR;
   float* Vs = Ks + KROWS * LDR;
-  int* reg_s = BIG ? reinterpret_cast<int*>(base + 2 * KROWS * LDR)
-                   : reinterpret_cast<int*>(base + 2 * (QROWS + 2 * KROWS) * LDR) + slab_in_blk * KROWS;
+  int* reg_s = reinterpret_cast<int*>(base + 2 * (QROWS + 2 * KROWS) * LDR) + slab_in_blk * KROWS;
 
   const int L = H * W;
   const int slabs_per_img = L / QROWS;
@@ -162,13 +156,12 @@ __global__ __launch_bounds__(256) void k_window_attn(const float* __restrict__ q
 
   for (int i = threadIdx.x; i < TBL * 2; i += 256) tbl[i] = bias_table[i];
 
-  // key range: whole windows covering the slab
-  const int k0 = (N > 64) ? (t0 / N) * N : t0;
+  const int k0 = t0;      // key range = the slab's own (whole) windows
   // ---- stage Q (64 rows), K, V (KROWS rows) of this slab: the 128 threads of the slab's two waves cooperate
   if (active) {
-    const int tl = BIG ? threadIdx.x : (threadIdx.x & 127);
+    const int tl = threadIdx.x & 127;
     constexpr int V4 = CG / 4;
-    for (int i = tl; i < KROWS * V4; i += (BIG ? 256 : 128)) {
+    for (int i = tl; i < KROWS * V4; i += 128) {
       const int r = i / V4, c4 = (i % V4) * 4;
       const int t = k0 + r;
       const int win = t / N, n = t % N;
@@ -178,7 +171,7 @@ __global__ __launch_bounds__(256) void k_window_attn(const float* __restrict__ q
       const size_t src = (size_t)b * L + sh * W + sw;
       *reinterpret_cast<float4*>(Ks + r * LDR + c4) = *reinterpret_cast<const float4*>(kv + src * 2 * C + g * CG + c4);
       *reinterpret_cast<float4*>(Vs + r * LDR + c4) = *reinterpret_cast<const float4*>(kv + src * 2 * C + C + g * CG + c4);
-      if (!BIG && t >= t0 && t < t0 + QROWS)
+      if (t >= t0 && t < t0 + QROWS)
         *reinterpret_cast<float4*>(Qs + (t - t0) * LDR + c4) = *reinterpret_cast<const float4*>(q + src * C + g * CG + c4);
       if (c4 == 0) {
         int rh = hr < H - WS ? 0 : (hr < H - shift ? 1 : 2);
@@ -193,17 +186,12 @@ __global__ __launch_bounds__(256) void k_window_attn(const float* __restrict__ q
   // ---- lane = query row
   const int tq = t0 + lane;
   const int nq = tq % N;
-  const int krow0 = (N > 64) ? 0 : (lane / N) * N;   // first key row (in Ks) of this lane's window
+  const int krow0 = (lane / N) * N;   // first key row (in Ks) of this lane's window
   const int iq = nq / WS, jq = nq % WS;
   const int my_reg = reg_s[tq - k0];
   float qv[D];
   const float scale = 1.0f / sqrtf((float)D);
   const float* qrow = Qs + lane * LDR + head * D;
-  if (BIG) {      // source token of window-major token tq in the rolled frame (same map as the K/V staging)
-    const int win = tq / N, wr = win / nWc, wc = win % nWc;
-    const int hr = wr * WS + nq / WS, wcol = wc * WS + nq % WS;
-    qrow = q + ((size_t)b * L + ((hr + shift) % H) * W + (wcol + shift) % W) * C + g * CG + head * D;
-  }
 #pragma unroll
   for (int d = 0; d < D; d += 4) {
     const float4 v = *reinterpret_cast<const float4*>(qrow + d);
@@ -585,9 +573,8 @@ int launch_window_attn_mfma(const float* q, const float* kv, const float* table,
 template <int WS, int D, bool DROP>
 int launch_window_attn(const float* q, const float* kv, const float* table, float* out, int B, int H, int W, int C, int g,
                        int shift, float p_drop, unsigned long long seed, hipStream_t st) {
-  constexpr int N = WS * WS, CG = 2 * D, KROWS = (N > 64) ? N : 64, LDR = CG + 4, TBL = (2 * WS - 1) * (2 * WS - 1);
-  const size_t smem = N > 64 ? (size_t)(((TBL * 2 + 3) & ~3) + 2 * KROWS * LDR) * 4 + KROWS * 4
-                             : (size_t)(((TBL * 2 + 3) & ~3) + 2 * (64 + 2 * KROWS) * LDR) * 4 + 2 * KROWS * 4;
+  constexpr int N = WS * WS, CG = 2 * D, KROWS = 64, LDR = CG + 4, TBL = (2 * WS - 1) * (2 * WS - 1);
+  const size_t smem = (size_t)(((TBL * 2 + 3) & ~3) + 2 * (64 + 2 * KROWS) * LDR) * 4 + 2 * KROWS * 4;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_window_attn<WS, D, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
@@ -832,14 +819,6 @@ __global__ void k_pack_conv_w(const float* __restrict__ w, float* __restrict__ w
 }  // namespace
 
 // ================================================================================== C ABI
-// rows per band of the generic depthwise kernels: whole planes up to 32 x 32, 16-row bands above (r a multiple of 16), DPMN_DW_BAND overrides
-static int dwconv_band_rows(int r) {
-  static const int env = getenv("DPMN_DW_BAND") ? atoi(getenv("DPMN_DW_BAND")) : -1;
-  int rb = env >= 0 ? env : (r > 32 && r % 16 == 0 ? 16 : r);
-  if (rb <= 0 || rb > r || r % rb != 0) rb = r;
-  return rb;
-}
-
 extern "C" {
 
 int dpmn_patch_embed_ln_f32(const float* img, int cin, const float* pf_w, const float* pf_b, const float* pe_w,
@@ -892,14 +871,13 @@ int dpmn_window_attn_drop_f32(const float* q, const float* kv, const float* cons
     DPMN_REQUIRE(H % ws == 0 && W % ws == 0, "window_attn: padding path (H or W not divisible by window) would crash the reference (quirk Q1)");
     DPMN_REQUIRE(sh >= 0 && sh < ws, "window_attn: shift must be in [0, window)");
     int rc = DPMN_ERR_ARG;
-    static const int wa_mfma = getenv("DPMN_WATTN_MFMA") ? atoi(getenv("DPMN_WATTN_MFMA")) : 1;
-    if (ws == 8 && D == 16 && wa_mfma) {
+    if (ws == 8 && D == 16) {
       rc = p_drop > 0.f ? launch_window_attn8_mfma<true>(q, kv, bias_tables[g], out, B, H, W, C, g, sh, p_drop, seed, st)
                         : launch_window_attn8_mfma<false>(q, kv, bias_tables[g], out, B, H, W, C, g, sh, 0.f, 0ull, st);
       if (rc != DPMN_OK) return rc;
       continue;
     }
-    if (D == 32 && wa_mfma && (ws == 4 || ws == 8 || ws == 16) && (H * W) % (ws == 16 ? 256 : 64) == 0) {
+    if (D == 32 && (ws == 4 || ws == 8 || ws == 16)) {
       if (p_drop > 0.f)
         rc = ws == 4 ? launch_window_attn_mfma<4, 32, true>(q, kv, bias_tables[g], out, B, H, W, C, g, sh, st, p_drop, seed)
                      : (ws == 8 ? launch_window_attn_mfma<8, 32, true>(q, kv, bias_tables[g], out, B, H, W, C, g, sh, st, p_drop, seed)
@@ -914,7 +892,7 @@ int dpmn_window_attn_drop_f32(const float* q, const float* kv, const float* cons
 #define WA_CASE(WSV, DV) if (ws == WSV && D == DV) rc = p_drop > 0.f \
       ? launch_window_attn<WSV, DV, true>(q, kv, bias_tables[g], out, B, H, W, C, g, sh, p_drop, seed, st) \
       : launch_window_attn<WSV, DV, false>(q, kv, bias_tables[g], out, B, H, W, C, g, sh, 0.f, 0ull, st); else
-    WA_CASE(2, 16) WA_CASE(4, 16) WA_CASE(8, 16) WA_CASE(4, 32) WA_CASE(8, 32) WA_CASE(16, 32)
+    WA_CASE(2, 16) WA_CASE(4, 16)
     return dpmn_set_error(DPMN_ERR_ARG, "window_attn: unsupported (window, head_dim); built: {2,4,8}x16, {4,8,16}x32");
 #undef WA_CASE
     if (rc != DPMN_OK) return rc;

@@ -10,7 +10,6 @@
 //             must survive until the caller's ordered-reduction flush (dpmn_reduce_defer_flush): dpmn_pgrm_blocks_backward_scratch_bytes
 //   arena     the slice allocator of the deferred reductions (train/pgrm_train.py _ws): *arena_used is advanced; when a request does
 //             not fit, the queued reductions are flushed (dpmn_reduce_defer_flush(0)) and the arena starts over, as the host code does
-#include <cstdlib>
 #include "common.h"
 #include <math.h>
 
@@ -186,7 +185,6 @@ int dpmn_pgrm_blocks_backward_leaf_f32(const dpmn_pgrm_weights* w, const dpmn_pg
     RUN(dpmn_layernorm_bwd_det_drop_f32((x), (dy), (gamma), 1e-5f, (dx), 1, (dgamma), (dbeta), M, C, ws_ptr, ws_n, (out2), (pe), (se), (pr), \
                                         (sr), (long)L * C, stream));                                                 \
   } while (0)
-  static const int fuse_masks = getenv("DPMN_BWD_FUSE_MASKS") ? atoi(getenv("DPMN_BWD_FUSE_MASKS")) : 1;
   bool dbr_ready = false;      // block 0's masked fc2 gradient was written by block 1's last LayerNorm backward
   float* dx2 = dtkv;
   for (int bi = 1; bi >= 0; --bi) {
@@ -224,15 +222,11 @@ int dpmn_pgrm_blocks_backward_leaf_f32(const dpmn_pgrm_weights* w, const dpmn_pg
     RUN(join());            // ... or on the leaf stream
     // x1 = tkv_in + DropPath(feats + V Wh^T + bh): the DropPath-masked gradient rides out of the LayerNorm2 backward
     const float* dat = dx1;
-    if (dpb > 0.f && fuse_masks) {
+    if (dpb > 0.f) {
       LN_BWD_DROP(b.x1, s.dn2, p.norm2_w, dx1, sink(g.norm2_w), sink(g.norm2_b), s.dat, 0.f, 0ull, dpb, sb[1]);
       dat = s.dat;
     } else {
       LN_BWD(b.x1, s.dn2, p.norm2_w, dx1, sink(g.norm2_w), sink(g.norm2_b));
-      if (dpb > 0.f) {
-        RUN(dpmn_dropout_f32(dx1, nullptr, s.dat, (long)M * C, (long)L * C, 0.f, 0ull, dpb, sb[1], stream));
-        dat = s.dat;
-      }
     }
     LINEAR_BWD(dat, b.V, t.head_t, sink(g.sk_head_w), sink(g.sk_head_b), C, cg, s.dV);
     float* dcat = dcat_zero[bi];
@@ -274,7 +268,7 @@ int dpmn_pgrm_blocks_backward_leaf_f32(const dpmn_pgrm_weights* w, const dpmn_pg
     // block 1's last step finishes dL/d(tokens behind block 0) = block 0's dx2: its Dropout / DropPath-masked copy (block 0's masks)
     // comes out of the same kernel
     const float dpb0 = drop ? drop->dp[0] : 0.f;
-    if (bi == 1 && fuse_masks && (pd > 0.f || dpb0 > 0.f)) {
+    if (bi == 1 && (pd > 0.f || dpb0 > 0.f)) {
       LN_BWD_DROP(tkv_in, s.dnrm, p.norm1_kv_w, dx1, sink(g.norm1_kv_w), sink(g.norm1_kv_b), s.dbr, pd, sd[2 + 3], dpb0, sd[2 + 4]);
       dbr_ready = true;
     } else {

@@ -1,7 +1,6 @@
 // Native driver for one PGRM forward: launches the fused kernels in order on one stream.
 // Replaces PGRM.forward / BasicLayer.forward / SwinTransformerBlock.forward / WindowAttention.forward
 // / SKConv.forward / Mlp.forward (pgrm.py:546-565, 375-384, 315-331, 184-271, 79-96, 29-41).
-#include <cstdlib>
 #include "common.h"
 #include <math.h>
 
@@ -98,24 +97,16 @@ int dpmn_pgrm_forward_f32(const dpmn_pgrm_weights* w, const float* x_q, int x_q_
     const int cg = C / w->n_groups;
     RUN(dpmn_sk_gate_f32(s.partial, (L + 31) / 32, L, p.sk_fc1_w, p.sk_fc1_b, p.sk_fc2_w, p.sk_fc2_b, s.avec, B, C,
                          w->n_groups, cg / 2, stream));
-    static const int skmlp = getenv("DPMN_SKMLP") ? atoi(getenv("DPMN_SKMLP")) : 1;
-    const bool fused_in = skmlp && dpmn_sk_mlp_in_supported(M, L, C, w->n_groups, Ch);
-    if (fused_in)      // select + proj_head + residuals -> x1 -> LayerNorm2 -> fc1 in one launch (gemm.hip k_sk_mlp_in)
+    if (dpmn_sk_mlp_in_supported(M, L, C, w->n_groups, Ch)) {      // select + proj_head + residuals -> x1 -> LayerNorm2 -> fc1 in one launch (gemm.hip k_sk_mlp_in)
       RUN(dpmn_sk_mlp_in_f32(s.cat, s.avec, p.sk_head_w, p.sk_head_b, s.feats, s.tkv, s.x1, p.norm2_w, p.norm2_b, 1e-5f, p.fc1_w, p.fc1_b,
                              s.y, nullptr, nullptr, M, L, C, w->n_groups, Ch, stream));
-    else
-    RUN(dpmn_sk_select_f32(s.cat, s.avec, p.sk_head_w, p.sk_head_b, s.feats, s.tkv, s.x1, M, L, C, w->n_groups, stream));
-    // fc1's GELU (pgrm.py:33): on load in the depthwise conv (HBM-bound, the erf is free there: fc1 48.7 -> 44.2 us, dwconv 36.6 -> 37.8 us), or (DPMN_GELU_ON_LOAD=0) in the epilogue of the MFMA-bound fc1 GEMM
-    static const int gelu_on_load = getenv("DPMN_GELU_ON_LOAD") ? atoi(getenv("DPMN_GELU_ON_LOAD")) : 1;
-    if (fused_in) {
-      RUN(dpmn_dwconv3x3_gelu_in_f32(s.y, p.dw_w, p.dw_b, s.g, B, Ch, r, stream));
-    } else if (gelu_on_load) {
-      RUN(dpmn_ln_linear_f32(s.x1, p.norm2_w, p.norm2_b, 1e-5f, p.fc1_w, p.fc1_b, s.y, M, Ch, C, DPMN_ACT_NONE, stream));
-      RUN(dpmn_dwconv3x3_gelu_in_f32(s.y, p.dw_w, p.dw_b, s.g, B, Ch, r, stream));
     } else {
-      RUN(dpmn_ln_linear_f32(s.x1, p.norm2_w, p.norm2_b, 1e-5f, p.fc1_w, p.fc1_b, s.y, M, Ch, C, DPMN_ACT_GELU, stream));
-      RUN(dpmn_dwconv3x3_gelu_f32(s.y, p.dw_w, p.dw_b, s.g, B, Ch, r, stream));
+      RUN(dpmn_sk_select_f32(s.cat, s.avec, p.sk_head_w, p.sk_head_b, s.feats, s.tkv, s.x1, M, L, C, w->n_groups, stream));
+      RUN(dpmn_ln_linear_f32(s.x1, p.norm2_w, p.norm2_b, 1e-5f, p.fc1_w, p.fc1_b, s.y, M, Ch, C, DPMN_ACT_NONE, stream));
     }
+    // fc1's GELU (pgrm.py:33) runs on load in the depthwise conv, not in the epilogue of the MFMA-bound fc1 GEMM (HBM-bound, the erf
+    // is free there: fc1 48.7 -> 44.2 us, dwconv 36.6 -> 37.8 us)
+    RUN(dpmn_dwconv3x3_gelu_in_f32(s.y, p.dw_w, p.dw_b, s.g, B, Ch, r, stream));
     RUN(dpmn_pointwise_f32(s.g, p.pw_w, p.pw_b, s.y, B, Ch, L, stream));
     RUN(dpmn_linear_f32(s.y, p.fc2_w, p.fc2_b, s.x1, nullptr, s.tkv, M, C, Ch, DPMN_ACT_NONE, 0.f, stream));
   }

@@ -7,7 +7,6 @@
 //     and the gate step of the query-embedding GRU (batch_first quirk Q5).
 // Token tensors here are (N, L, E) row-major (N = image, L = 26 text slots or 1024 pixels, E = 64):
 // the reference's (L, N, E) differs only by a transpose no kernel needs.
-#include <cstdlib>
 #include "common.h"
 
 namespace {
@@ -17,12 +16,11 @@ namespace {
 // seq s -> base pixel = (s / inner) * outer_stride + (s % inner) * inner_stride ; step t adds t*step_stride (pixels)
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-// PK: the recurrence's products as v_pk_fma_f32 (default) or, PK = false, as the same sums on scalar v_fma_f32.  The packed form is
-// NOT safe next to bf16 MFMA work of another stream: with a v_mfma_f32_16x16x32_bf16 kernel (mode 2 "f32 via bf16x3", mode 1 bf16)
-// resident on the same SIMDs, 7-25 % of the launches returned a few sequences off by 3e-3 -- never alone, never next to fp32-MFMA
-// kernels, never with scalar fmas (tools/dbg_victim.py: the recurrence on one stream, a bf16x3 conv on another; 0 / 240 vs 28-60 / 240
-// mismatching launches).  The launcher therefore takes the scalar form whenever the library is in a bf16-MFMA mode.
-template <int HID, bool PK = true>
+// The recurrence's products run as scalar v_fma_f32 on (r, z) / n operand pairs.  Packed v_pk_fma_f32 is NOT safe next to bf16 MFMA
+// work of another stream: with a v_mfma_f32_16x16x32_bf16 kernel (mode 2 "f32 via bf16x3", mode 1 bf16) resident on the same SIMDs,
+// 7-25 % of the launches returned a few sequences off by 3e-3 -- never alone, never next to fp32-MFMA kernels, never with scalar fmas
+// (tools/dbg_victim.py: the recurrence on one stream, a bf16x3 conv on another; 0 / 240 vs 28-60 / 240 mismatching launches).
+template <int HID>
 __global__ __launch_bounds__(256) void k_bigru(const float* gi, const float* w_hh /*(2,3H,H)*/,
                                                 const float* b_hh /*(2,3H)*/, const float* res,
                                                 float* out, int nseq, int T, int inner, long outer_stride,
@@ -33,8 +31,7 @@ __global__ __launch_bounds__(256) void k_bigru(const float* gi, const float* w_h
   const int dir = lane >> 5, j = lane & 31;
   const long s = (long)blockIdx.x * 4 + wave;
   if (s >= nseq) return;      // whole wave (no block-level barrier below: the hidden state goes through a wave-private LDS row)
-  // W_hh rows of this lane's hidden unit as PACKED pairs: (r, z) share the h_k operand (v_pk_fma_f32 with a broadcast), the n row is
-  // paired over k against (h_k, h_k+1): 48 packed fmas per step instead of 96 scalar ones on the step's critical path
+  // W_hh rows of this lane's hidden unit as pairs: (r, z) share the h_k operand, the n row is paired over k against (h_k, h_k+1)
   v2f wrz[HID], wnn[HID / 2];
   const float* wb = w_hh + (size_t)dir * 3 * HID * HID;
 #pragma unroll
@@ -80,10 +77,7 @@ __global__ __launch_bounds__(256) void k_bigru(const float* gi, const float* w_h
     gp += more ? gd : 0;
     rq += more ? rd : 0;
   };
-  auto pkfma = [](v2f a, v2f b, v2f c) -> v2f {
-    if (PK) return __builtin_elementwise_fma(a, b, c);
-    return v2f{fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y)};
-  };
+  auto pkfma = [](v2f a, v2f b, v2f c) -> v2f { return v2f{fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y)}; };
   auto step = [&](const float (&g4)[4], int t) {
     hs[wave][lane] = h;
     __builtin_amdgcn_wave_barrier();
@@ -137,25 +131,9 @@ __global__ __launch_bounds__(256) void k_bigru(const float* gi, const float* w_h
 }
 
 // ---------------------------------------------------------------------------------- tiny linear
-// y[m][n] = act((x[m][:] (+ add[m % add_rows][:])) . w[n][:] + b[n]) -- one thread per output; for problems of a few MFLOP
-__global__ void k_small_linear(const float* __restrict__ x, const float* __restrict__ add, int add_rows,
-                               const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ y, int M, int N,
-                               int K, int act, float slope) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)M * N) return;
-  const int m = idx / N, n = idx % N;
-  const float* xr = x + (size_t)m * K;
-  const float* ar = add ? add + (size_t)(m % add_rows) * K : nullptr;
-  const float* wr = w + (size_t)n * K;
-  float a = b ? b[n] : 0.f;
-  for (int k = 0; k < K; ++k) a += (xr[k] + (ar ? ar[k] : 0.f)) * wr[k];
-  y[idx] = apply_act(a, act, slope);
-}
-
-// The same product staged through LDS: a block owns 32 rows x 64 columns, x (+ add) and w arrive with coalesced loads in 64-deep
-// K chunks, a thread accumulates 8 rows of one column.  Every output is the same chain of multiply-then-add over k = 0 .. K-1 that
-// k_small_linear runs (bitwise-equal results); that kernel's per-thread walk over a weight ROW made every wave load 64 different
-// cache lines per k: 8 - 105 us per call on the 1248 x 64 x 64 products of the TATT interpreter (5 calls per batch).
+// y[m][n] = act((x[m][:] (+ add[m % add_rows][:])) . w[n][:] + b[n]) for problems of a few MFLOP, staged through LDS: a block owns
+// 32 rows x 64 columns, x (+ add) and w arrive with coalesced loads in 64-deep K chunks, a thread accumulates 8 rows of one column.
+// Every output is the same chain of multiply-then-add over k = 0 .. K-1, b[n] first.
 __global__ __launch_bounds__(256) void k_small_linear_tiled(const float* __restrict__ x, const float* __restrict__ add, int add_rows,
                                                              const float* __restrict__ w, const float* __restrict__ b,
                                                              float* __restrict__ y, int M, int N, int K, int act, float slope) {
@@ -446,14 +424,8 @@ int dpmn_bigru_f32(const float* gi, const float* w_hh, const float* b_hh, const 
   DPMN_REQUIRE(gi && w_hh && b_hh && out && nseq > 0 && T > 0 && inner > 0, "bigru: bad arguments");
   DPMN_REQUIRE(hidden == 32, "bigru: built for hidden_units=32 per direction (hd_u default, main.py:47)");
   ProfScope prof(PT_BIGRU, as_stream(stream), 2.0 * 2 * 3 * 32 * 32 * (double)nseq * T, 4.0 * (2 * 96 + 64 + 64) * (double)nseq * T);
-  static const int pk_env = getenv("DPMN_BIGRU_PK") ? atoi(getenv("DPMN_BIGRU_PK")) : -1;      // A/B switch: 1 / 0 force the packed / scalar form
-  const bool pk = pk_env >= 0 ? pk_env != 0 : !(g_dpmn_x3 || g_dpmn_bf16);
-  if (pk)
-    hipLaunchKernelGGL((k_bigru<32, true>), dim3((unsigned)((nseq + 3) / 4)), dim3(256), 0, as_stream(stream), gi, w_hh, b_hh, res, out,
-                       nseq, T, inner, outer_stride, inner_stride, step_stride);
-  else
-    hipLaunchKernelGGL((k_bigru<32, false>), dim3((unsigned)((nseq + 3) / 4)), dim3(256), 0, as_stream(stream), gi, w_hh, b_hh, res, out,
-                       nseq, T, inner, outer_stride, inner_stride, step_stride);
+  hipLaunchKernelGGL((k_bigru<32>), dim3((unsigned)((nseq + 3) / 4)), dim3(256), 0, as_stream(stream), gi, w_hh, b_hh, res, out,
+                     nseq, T, inner, outer_stride, inner_stride, step_stride);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }
@@ -461,13 +433,8 @@ int dpmn_bigru_f32(const float* gi, const float* w_hh, const float* b_hh, const 
 int dpmn_small_linear_f32(const float* x, const float* add, int add_rows, const float* w, const float* b, float* y, int M,
                           int N, int K, int act, float slope, dpmn_stream_t stream) {
   DPMN_REQUIRE(x && w && y && M > 0 && N > 0 && K > 0, "small_linear: bad arguments");
-  static const int tiled = getenv("DPMN_SMALL_LINEAR_TILED") ? atoi(getenv("DPMN_SMALL_LINEAR_TILED")) : 1;
-  if (tiled)
-    hipLaunchKernelGGL(k_small_linear_tiled, dim3((unsigned)((M + 31) / 32), (unsigned)((N + 63) / 64)), dim3(256), 0, as_stream(stream), x,
-                       add, add_rows > 0 ? add_rows : 1, w, b, y, M, N, K, act, slope);
-  else
-    hipLaunchKernelGGL(k_small_linear, dim3((unsigned)(((long)M * N + 255) / 256)), dim3(256), 0, as_stream(stream), x, add,
-                       add_rows > 0 ? add_rows : 1, w, b, y, M, N, K, act, slope);
+  hipLaunchKernelGGL(k_small_linear_tiled, dim3((unsigned)((M + 31) / 32), (unsigned)((N + 63) / 64)), dim3(256), 0, as_stream(stream), x,
+                     add, add_rows > 0 ? add_rows : 1, w, b, y, M, N, K, act, slope);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }

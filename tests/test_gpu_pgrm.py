@@ -220,9 +220,6 @@ def test_fused_ln_qkv_window_attention_vs_oracle(dev, B, shifts):
     lnq_w, lnq_b = u("lnq_w", (C,), 0.5, 1.5), u("lnq_b", (C,), -0.5, 0.5)
     lnk_w, lnk_b = u("lnk_w", (C,), 0.5, 1.5), u("lnk_b", (C,), -0.5, 0.5)
     tq, tkv = u("f_tq%d" % B, (B, H * W, C), -2, 3), u("f_tkv%d" % B, (B, H * W, C), -3, 2)
-    import os
-    if os.environ.get("DPMN_ATTN_FUSED") == "0":
-        pytest.skip("the fused kernel is switched off (DPMN_ATTN_FUSED=0)")
     assert ops.ln_qkv_window_attn_supported(C, [2, 4, 8], 2, H, W)
     q = F.linear(F.layer_norm(tq, (C,), lnq_w, lnq_b), sd["q.weight"], sd["q.bias"])
     kv = F.linear(F.layer_norm(tkv, (C,), lnk_w, lnk_b), sd["kv.weight"], sd["kv.bias"])
@@ -417,12 +414,9 @@ def test_basiclayer_stress_dims_vs_reference_golden_and_oracle(dev):
 def test_fused_attention_training_variant_vs_oracle_and_unfused(dev, B, shifts, p):
     """Training forward of the fused kernel (dpmn_ln_qkv_window_attn_train_f32): the saved q / kv equal Linear(LayerNorm(x)) of
     pgrm.py:188,194, and `cat` under attn_drop equals the oracle with the SAME counter-based masks (and the unfused DROP kernels)."""
-    import os
     from dpmn_amd import ops
     from oracle import pgrm as o
     from helpers import record, max_abs_err
-    if os.environ.get("DPMN_ATTN_FUSED") == "0":
-        pytest.skip("the fused kernel is switched off (DPMN_ATTN_FUSED=0)")
     H, W, C = 16, 64, 96
     g = load_golden("wattn_shift0" if shifts[0] == 0 else "wattn_shifted")
     sd = sd_from_manifest(g["manifest"], 21)

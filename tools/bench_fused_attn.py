@@ -22,5 +22,4 @@ for shifts in ([0, 0, 0], [1, 2, 4]):
         ops.ln_qkv_window_attn(tq, tkv, *ln, wq, bq, wkv, bkv, tables, [2, 4, 8], shifts, 2, H, W)
     torch.cuda.synchronize()
     r = _abi.profile_end()[0]
-    print("dbg=%s shifts=%s: %.1f us/launch  %.1f TFLOP/s" % (os.environ.get("DPMN_FUSED_DBG", "0"), shifts, r["total_ms"] * 1e3 / r["launches"],
-                                                          r["flops"] / (r["total_ms"] * 1e-3) / 1e12))
+    print("shifts=%s: %.1f us/launch  %.1f TFLOP/s" % (shifts, r["total_ms"] * 1e3 / r["launches"], r["flops"] / (r["total_ms"] * 1e-3) / 1e12))

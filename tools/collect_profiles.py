@@ -26,7 +26,7 @@ FAMILIES = [("k_conv_igemm<128, 128", "k_conv_igemm<128,128>"), ("k_conv_igemm<6
             ("k_gemm_wstat", "k_gemm_wstat|rowreg"), ("k_gemm_rowreg", "k_gemm_wstat|rowreg"), ("k_gemm_kloop", "k_gemm_kloop"),
             ("k_gemm_tn", "k_gemm_tn_reg"), ("k_affine_act_bwd", "k_affine_act_bwd"), ("k_ln_bwd", "k_ln_bwd"),
             ("k_window_attn_mfma<", "k_window_attn_mfma<4|8|16,32>"), ("k_conv_pack", "k_conv_pack_multi"), ("k_wgrad_unpack", "k_wgrad_unpack_multi"), ("k_dwconv_gelu", "k_dwconv_gelu"),
-            ("k_window_attn8_mfma", "k_window_attn8_mfma"), ("k_window_attn<", "k_window_attn<2|4|16>"), ("k_ln_qkv_window_attn_bwd", "k_ln_qkv_window_attn_bwd"), ("k_ln_qkv_window_attn", "k_ln_qkv_window_attn"),
+            ("k_window_attn8_mfma", "k_window_attn8_mfma"), ("k_window_attn<", "k_window_attn<2|4>"), ("k_ln_qkv_window_attn_bwd", "k_ln_qkv_window_attn_bwd"), ("k_ln_qkv_window_attn", "k_ln_qkv_window_attn"),
             ("k_bigru", "k_bigru"), ("k_mha32", "k_mha32")]
 
 

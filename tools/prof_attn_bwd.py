@@ -40,5 +40,4 @@ def timeit(fn, n=50):
 fwd = timeit(lambda: ops.ln_qkv_window_attn_train(*args, p_drop=pd, seed=3, save_qkv=False))
 fwd_s = timeit(lambda: ops.ln_qkv_window_attn_train(*args, p_drop=pd, seed=3, save_qkv=True))
 bwd = timeit(lambda: ops.ln_qkv_window_attn_bwd(*args, dout, p_drop=pd, seed=3, fold=fold[0]))
-print("shift %d drop %.2f env %s: forward %.1f us (saving q/kv %.1f us), backward %.1f us" % (
-    shifted, pd, {k: v for k, v in os.environ.items() if k.startswith("DPMN_FA")}, fwd, fwd_s, bwd))
+print("shift %d drop %.2f: forward %.1f us (saving q/kv %.1f us), backward %.1f us" % (shifted, pd, fwd, fwd_s, bwd))
