@@ -3,7 +3,8 @@
 Keeps the attribute names, the per-PGRM hyper-parameter string parsing (base.py:64-82, with a safe
 parser instead of eval()), ``generator_init`` (base.py:127-198) and the checkpoint format
 (base.py:328-373), and the CRNN recogniser of the word accuracy (``CRNN_init`` / ``parse_crnn_data``, base.py:411-425) on the
-native NativeCRNN.  Out of scope here: the ASTER / MORAN recognisers, pygame renderer.
+native NativeCRNN, the ASTER recogniser (``Aster_init`` / ``parse_aster_data``, base.py:427-450) on the native NativeASTER.  Out of
+scope here: the MORAN recogniser, pygame renderer.
 """
 import os
 
@@ -151,6 +152,36 @@ class TextBase(object):
         for p in model.parameters():
             p.requires_grad = False
         return model.eval()
+
+    def Aster_init(self, path=None):
+        """base.py:427-439: the ASTER recogniser from config.TRAIN.VAL.rec_pretrained (or `path`; the checkpoint's 'state_dict'),
+        here the native NativeASTER, frozen and in eval mode -> (aster, aster_info).  A missing or empty path raises."""
+        from ..model.aster import NativeASTER
+        from ..utils.labelmaps import AsterInfo
+        val = getattr(self.config.TRAIN, "VAL", None)
+        model_path = (getattr(val, "rec_pretrained", None) if val is not None else None) if path is None else path
+        if not model_path or not os.path.isfile(model_path):
+            raise FileNotFoundError("dpmn_amd: the ASTER recogniser needs its weights: config TRAIN.VAL.rec_pretrained (or the path "
+                                    "argument) names no file (%r)" % (model_path,))
+        aster_info = AsterInfo(getattr(self.config.TRAIN, "voc_type", None) or 'all')
+        aster = NativeASTER(arch='ResNet_ASTER', rec_num_classes=aster_info.rec_num_classes, sDim=512, attDim=512,
+                            max_len_labels=aster_info.max_len, eos=aster_info.char2id[aster_info.EOS], STN_ON=True)
+        aster.load_state_dict(torch.load(model_path, map_location='cpu')['state_dict'])
+        print('load pre_trained aster model from %s' % model_path)
+        aster = aster.to(self.device)
+        aster.info = aster_info
+        for p in aster.parameters():
+            p.requires_grad = False
+        return aster.eval(), aster_info
+
+    def parse_aster_data(self, imgs_input):
+        """base.py:441-450: images in [0, 1] -> the recogniser's input dict (images in [-1, 1], targets filled with ones)."""
+        from ..utils.labelmaps import AsterInfo
+        aster_info = AsterInfo(getattr(self.config.TRAIN, "voc_type", None) or 'all')
+        images_input = imgs_input.to(self.device)
+        batch_size = images_input.shape[0]
+        return {'images': images_input * 2 - 1, 'rec_targets': torch.IntTensor(batch_size, aster_info.max_len).fill_(1),
+                'rec_lengths': [aster_info.max_len] * batch_size}
 
     def parse_crnn_data(self, imgs_input):
         """base.py:419-425: bicubic resize to 32x100 and ITU-601 luma -> (B, 1, 32, 100), a view of the NHWC buffer NativeCRNN's

@@ -223,12 +223,13 @@ class TextSR(base.TextBase):
     def eval(self, model_list, val_loader, index=0, rec=None, aster_info=None, rec_list=None, model_psn=None, crnn_psn=None,
              text_prior_fn=None):
         """super_resolution.py:340-513.  PSNR/SSIM always; recognition accuracy (lines 453-493) only when `rec` reads the SR images
-        and the loader yields label strings as a 4th item: `rec` is the native CRNN (TextBase.CRNN_init, --rec crnn: its `read`) or
-        any callable images (B,3,H,W) -> list[str].  The reference's ASTER / MORAN recognisers are out of scope (SURVEY.md section 2
-        rows 16-17), so by default 'accuracy' is None ("not computed"), never a fake 0.0."""
+        and the loader yields label strings as a 4th item: `rec` is the native CRNN (TextBase.CRNN_init, --rec crnn: its `read`), the
+        native ASTER (TextBase.Aster_init, --rec aster: its `read`) or any callable images (B,3,H,W) -> list[str].  The reference's MORAN
+        recogniser is out of scope, and without a recogniser 'accuracy' is None ("not computed"), never a fake 0.0."""
         from ..utils.util import str_filt
         from ..model.crnn import NativeCRNN
-        reader = rec.read if isinstance(rec, NativeCRNN) else (rec if callable(rec) else None)
+        from ..model.aster import NativeASTER
+        reader = rec.read if isinstance(rec, (NativeCRNN, NativeASTER)) else (rec if callable(rec) else None)
         for m in model_list:
             m.eval()
         fn = text_prior_fn or self.default_text_prior()

@@ -703,3 +703,72 @@ def crnn_label_vecs(logits, B, T, n_class):
     out = torch.empty(B, n_class, 1, T, device=logits.device)
     check(lib.dpmn_crnn_label_vecs_f32(dptr(logits), logits.shape[1], n_class, dptr(out), B, T, stream()))
     return out
+
+
+# ------------------------------------------------------------------------------ native ASTER recogniser (csrc/aster.hip)
+def aster_prep(img, stn_h=32, stn_w=64):
+    """parse_aster_data + the STN head's bilinear (align_corners=True) resize for a batch: (B, >=3, H, W) in [0, 1] ->
+    (normalised NCHW (B, 3, H, W), NHWC (B, stn_h, stn_w, 4) with channel 3 zero)."""
+    B, Cc, H, W = img.shape
+    if Cc < 3:
+        raise _abi.DpmnError("aster_prep: channels 0..2 (RGB) are read, got %d channels" % Cc)
+    v, ptr, stride = _nchw_view(img)
+    norm = torch.empty(B, 3, H, W, device=img.device)
+    stn = torch.empty(B, stn_h, stn_w, 4, device=img.device)
+    check(lib.dpmn_aster_prep_f32(ptr, stride, dptr(norm), dptr(stn), B, H, W, stn_h, stn_w, stream()))
+    return norm, stn
+
+
+def subsample_nhwc(x, sy, sx):
+    """x[:, ::sy, ::sx, :] of an NHWC tensor as a contiguous tensor (the gather in front of a 1 x 1 conv with stride (sy, sx))."""
+    B, H, W, Cc = x.shape
+    y = torch.empty(B, (H - 1) // sy + 1, (W - 1) // sx + 1, Cc, device=x.device)
+    check(lib.dpmn_subsample_nhwc_f32(dptr(x), dptr(y), B, H, W, Cc, sy, sx, stream()))
+    return y
+
+
+def aster_dec_weights(tensors):
+    """dict name -> tensor (the fields of dpmn_aster_dec_weights) -> a filled _abi.AsterDecWeights; the caller keeps the tensors."""
+    w = _abi.AsterDecWeights()
+    for n in _abi.AsterDecWeights.NAMES:
+        setattr(w, n, dptr(tensors[n]))
+    return w
+
+
+def _i32(t, what):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise _abi.DpmnError("dpmn_amd: %s expects a contiguous int32 CUDA tensor" % what)
+    return t.data_ptr()
+
+
+def aster_decode_step(weights, feats, xproj, row_img, state, y_prev, n_class):
+    """One teacher-forced decoder step for R rows (row r attends to image row_img[r]) -> (logits (R, n_class), new state
+    (R, 512), alpha (R, T))."""
+    import ctypes as _C
+    R, T = state.shape[0], feats.shape[1]
+    if tuple(feats.shape) != tuple(xproj.shape) or feats.shape[2] != 512 or tuple(state.shape) != (R, 512) or row_img.numel() != R or y_prev.numel() != R:
+        raise _abi.DpmnError("aster_decode_step: feats / xproj (B, T, 512), state (R, 512), row_img / y_prev (R) expected")
+    dev = state.device
+    sproj, ctx, out = torch.empty(R, 512, device=dev), torch.empty(R, 512, device=dev), torch.empty(R, 512, device=dev)
+    alpha, logits = torch.empty(R, T, device=dev), torch.empty(R, n_class, device=dev)
+    check(lib.dpmn_aster_decode_step_f32(_C.byref(weights), dptr(feats), dptr(xproj), _i32(row_img, "aster_decode_step"), dptr(state),
+                                         _i32(y_prev, "aster_decode_step"), dptr(sproj), dptr(ctx), dptr(alpha), dptr(out), dptr(logits),
+                                         R, T, n_class, stream()))
+    return logits, out, alpha
+
+
+def aster_beam(weights, feats, xproj, beam, n_class, eos, steps):
+    """Beam search on the current stream -> ONE int32 buffer (3, steps, B * beam): emitted symbols, predecessor rows and the bits
+    of the float32 sequence scores of every step (one device-to-host copy serves the host backtracking)."""
+    import ctypes as _C
+    B, T, D = feats.shape
+    if tuple(xproj.shape) != (B, T, D) or D != 512:
+        raise _abi.DpmnError("aster_beam: feats and xproj (B, T, 512) expected")
+    R = B * beam
+    nb = lib.dpmn_aster_beam_workspace_bytes(B, beam)
+    ws = torch.empty(nb // 4, device=feats.device)
+    buf = torch.empty(3, steps, R, dtype=torch.int32, device=feats.device)
+    n = 4 * steps * R
+    check(lib.dpmn_aster_beam_f32(_C.byref(weights), dptr(feats), dptr(xproj), dptr(ws), nb, buf.data_ptr(), buf.data_ptr() + n,
+                                  buf.data_ptr() + 2 * n, B, T, beam, n_class, eos, steps, stream()))
+    return buf

@@ -393,6 +393,36 @@ int dpmn_maxpool2d_f32(const float* x, float* y, int B, int H, int W, int C, int
 int dpmn_bilstm_f32(const float* gx, const float* w_hh, float* out, float* c_state, int B, int T, int H, dpmn_stream_t stream);
 int dpmn_ctc_greedy_i32(const float* logits, int ld, int n_class, int* cls, int* length, int B, int T, dpmn_stream_t stream);
 int dpmn_crnn_label_vecs_f32(const float* logits, int ld, int n_class, float* out, int B, int T, dpmn_stream_t stream);
+
+/* ------------------------------------------------------------------ native ASTER recogniser (aster.hip; model/aster.py NativeASTER)
+ * aster_prep:      parse_aster_data (x * 2 - 1, interfaces/base.py:441-450) + F.interpolate(x, (Hs, Ws), bilinear,
+ *                  align_corners=True) (recognizer_builder.py:77): img (B, >=3, H, W) planes with batch stride img_stride (channels
+ *                  0..2 read) -> norm_nchw (B, 3, H, W), the normalised image the TPS samples, and stn_nhwc4 (B, Hs, Ws, 4), the
+ *                  STN head's input (channel 3 = 0).
+ * subsample_nhwc:  y (B, Ho, Wo, C) = x[:, ::sy, ::sx, :], Ho = (H - 1) / sy + 1: the gather in front of a 1 x 1 conv whose two
+ *                  strides differ (resnet_aster.py: (2, 1)); C % 4 == 0.
+ * The attention decoder (attention_recognition_head.py:187-268), widths sDim = attDim = xDim = 512, on fp32 MFMA in every compute
+ * mode.  dpmn_aster_dec_weights: s_w (512, 512) / s_b = sEmbed; w_w (512) / w_b (1) = wEmbed; E (n_class + 1, 1536) =
+ * tgt_embedding.weight W_ih[:, :512]^T + b_ih; wih_ctx (1536, 512) = W_ih[:, 512:] contiguous; whh (1536, 512), bhh (1536); fc_w
+ * (n_class, 512), fc_b.  feats (B, T, 512) encoder output, xproj (B, T, 512) = xEmbed(feats), both once per batch.
+ * aster_decode_step: one teacher-forced step for R rows: row r attends to image row_img[r]; state (R, 512) and y_prev (R) in,
+ *                  alpha (R, T), state_out (R, 512) and logits (R, n_class) out; sproj / ctx (R, 512) scratch.
+ * aster_beam:      beam search of `steps` steps (attention_recognition_head.py:68-122) for B images x beam rows, four launches per
+ *                  step, no host synchronisation: sym / pred / score (steps, B * beam) = emitted symbols, predecessor rows and
+ *                  sequence scores of every step (the backtracking runs on the host).  Among equal candidate scores the lower flat
+ *                  index beam * n_class + class wins.  ws: dpmn_aster_beam_workspace_bytes(B, beam). */
+typedef struct dpmn_aster_dec_weights {
+  const float *s_w, *s_b, *w_w, *w_b, *E, *wih_ctx, *whh, *bhh, *fc_w, *fc_b;
+} dpmn_aster_dec_weights;
+int dpmn_aster_prep_f32(const float* img, long img_stride, float* norm_nchw, float* stn_nhwc4, int B, int H, int W, int Hs, int Ws,
+                        dpmn_stream_t stream);
+int dpmn_subsample_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, int sy, int sx, dpmn_stream_t stream);
+size_t dpmn_aster_beam_workspace_bytes(int B, int beam);
+int dpmn_aster_decode_step_f32(const dpmn_aster_dec_weights* w, const float* feats, const float* xproj, const int* row_img,
+                               const float* state, const int* y_prev, float* sproj, float* ctx, float* alpha, float* state_out,
+                               float* logits, int R, int T, int n_class, dpmn_stream_t stream);
+int dpmn_aster_beam_f32(const dpmn_aster_dec_weights* w, const float* feats, const float* xproj, float* ws, size_t ws_bytes, int* sym,
+                        int* pred, float* score, int B, int T, int beam, int n_class, int eos, int steps, dpmn_stream_t stream);
 int dpmn_layernorm_std_f32(const float* x, const float* a2, const float* b2, float eps, float* y, long M, int C,
                            dpmn_stream_t stream);
 /* GPU half of the TextZoom collate (dataset/dataset.py:1266-1319 resizeNormalize, 2007-2013 alignCollate_realWTLAMask.__call__):

@@ -665,6 +665,210 @@ def gen_crnn_ctc():
     save("crnn_ctc", classes=cls.to(torch.int32), texts=np.array(texts), alphabet=np.array(conv.alphabet[:-1]))
 
 
+def _aster_reference():
+    """The reference's RecognizerBuilder on the CPU: its decoder calls .cuda() on fresh tensors, so torch.Tensor.cuda is the identity
+    while the returned `restore` has not been called."""
+    import types
+    for name in ("torchsnooper", "editdistance"):      # imported by the recogniser / utils.metrics, never called on this path
+        sys.modules.setdefault(name, types.ModuleType(name))
+    orig = torch.Tensor.cuda
+    torch.Tensor.cuda = lambda self, *a, **k: self
+    from model.recognizer.recognizer_builder import RecognizerBuilder
+    ref = RecognizerBuilder(arch='ResNet_ASTER', rec_num_classes=97, sDim=512, attDim=512, max_len_labels=100, eos=94, STN_ON=True).eval()
+
+    def restore():
+        torch.Tensor.cuda = orig
+    return ref, restore
+
+
+def _ref_aster_info(voc_type):
+    """What interfaces/base.py AsterInfo holds (lines 480-492), from the reference's get_vocabulary (importing interfaces.base itself
+    pulls in the LMDB data path)."""
+    import types
+    from utils.labelmaps import get_vocabulary
+    voc = get_vocabulary(voc_type, EOS='EOS', PADDING='PADDING', UNKNOWN='UNKNOWN')
+    return types.SimpleNamespace(voc_type=voc_type, EOS='EOS', PADDING='PADDING', UNKNOWN='UNKNOWN', max_len=100, voc=voc,
+                                 char2id=dict(zip(voc, range(len(voc)))), id2char=dict(zip(range(len(voc)), voc)), rec_num_classes=len(voc))
+
+
+ASTER_IDS = [3, 5, 18, 4, 7, 9, 0, 19]      # members of utils/aster_synth.py's image pool (chosen on the reference's own run, asserted below)
+ASTER_STEPS = [0, 5, 20]
+
+
+def _sample(t, n=256):
+    f = t.reshape(-1)
+    return f[::max(1, f.numel() // n)][:n].clone()
+
+
+def gen_aster():
+    """The ASTER recogniser (model/recognizer/) in eval mode on name-seeded weights (utils/aster_synth.py aster_fill_, seed 81) and
+    bar images: every stage of RecognizerBuilder.forward, the beam search re-run step by step on the reference's own DecoderUnit (the
+    candidate scores give the decision margins; its stored tensors backtrack to the reference's pred_rec), three teacher-forced
+    steps, the strings of get_str_list."""
+    import torch.nn.functional as F
+    from dpmn_amd.utils import aster_synth
+    ref, restore = _aster_reference()
+    from utils.metrics import get_str_list
+    AsterInfo = _ref_aster_info
+    try:
+        sd = ref.state_dict()
+        assert len(sd) == 384
+        aster_synth.aster_fill_(sd, 81)
+        sd = {k: v.clone() for k, v in sd.items()}
+        ref.load_state_dict(sd)
+        img = aster_synth.aster_images(ASTER_IDS)
+        n = img.shape[0]
+        x = img * 2 - 1
+        out = ref({'images': x, 'rec_targets': torch.IntTensor(n, 100).fill_(1), 'rec_lengths': [100] * n})
+        pred_rec = out['output']['pred_rec']
+        stn_in = F.interpolate(x, ref.tps_inputsize, mode='bilinear', align_corners=True)
+        _, ctrl = ref.stn_head(stn_in)
+        rect, _ = ref.tps(x, ctrl)
+        enc = ref.encoder
+        layers = [enc.layer0(rect)]
+        for li in range(1, 6):
+            layers.append(getattr(enc, "layer%d" % li)(layers[-1]))
+        feats = enc(rect).contiguous()
+        dec = ref.decoder.decoder
+        xproj = dec.attention_unit.xEmbed(feats.view(-1, 512)).view(n, -1, 512)
+        # the beam search step by step on the reference's DecoderUnit
+        K, C, eos, L = 5, 97, 94, 100
+        fi = feats.unsqueeze(1).expand(n, K, 25, 512).reshape(n * K, 25, 512).contiguous()
+        state = torch.zeros(1, n * K, 512)
+        pos = (torch.arange(n) * K).view(-1, 1)
+        seq = torch.full((n * K, 1), -float('inf'))
+        seq[::K] = 0.0
+        y = torch.full((n * K,), C, dtype=torch.long)
+        sym, pred, score, gaps, steps = [], [], [], [], {}
+        for i in range(L):
+            if i in ASTER_STEPS:
+                rows = torch.arange(2 * K)       # all beams of images 0 and 1 (their encoder features are stored in full)
+                s_in, y_in = state[0, rows].clone(), y[rows].clone()
+                alpha = dec.attention_unit(fi[:2 * K], s_in.unsqueeze(0))
+                lg, s_out = dec(fi[:2 * K], s_in.unsqueeze(0), y_in)
+                steps[i] = (s_in, y_in, lg, s_out[0], alpha)
+            o, state = dec(fi, state, y)
+            cand = (seq + F.log_softmax(o, dim=1)).view(n, -1)
+            top6 = cand.topk(6, 1)[0]
+            g = top6[:, :-1] - top6[:, 1:]
+            g[~torch.isfinite(g)] = float('inf')
+            gaps.append(g.min(1)[0])
+            top, idx = cand.topk(K, 1)
+            y = (idx % C).view(-1)
+            seq = top.view(-1, 1)
+            p = (idx // C + pos).view(-1)
+            state = state.index_select(1, p)
+            score.append(seq.view(-1).clone())
+            seq = seq.masked_fill(y.view(-1, 1).eq(eos), -float('inf'))
+            pred.append(p)
+            sym.append(y)
+        sym, pred, score, gaps = torch.stack(sym), torch.stack(pred), torch.stack(score), torch.stack(gaps)
+        from dpmn_amd.utils.labelmaps import beam_backtrack
+        assert (torch.from_numpy(beam_backtrack(sym.numpy(), pred.numpy(), score.numpy(), n, K, eos)) == pred_rec).all(), \
+            "the step-by-step run does not reproduce the reference's beam_search"
+        info = AsterInfo('all')
+        strings, _ = get_str_list(pred_rec, torch.ones_like(pred_rec), info)
+        margin = gaps.min(0)[0]
+        first_eos = [int((r == eos).nonzero()[0]) if (r == eos).any() else -1 for r in pred_rec]
+        assert len(set(strings)) >= 3, strings
+        assert sum(1 for e in first_eos if 1 <= e <= 30) * 2 >= n, first_eos
+        assert int((margin < 1e-3).sum()) * 4 <= n, margin.tolist()
+        # a beam other than the winner emits EOS before the last step (the winner accounts for at most one EOS of its image)
+        ended = [int((sym[:L - 1, b * K:(b + 1) * K] == eos).sum()) - (1 if 0 <= first_eos[b] < L - 1 else 0) for b in range(n)]
+        assert max(ended) >= 1, "no beam other than the winner ends early"
+        arrs = dict(ids=np.array(ASTER_IDS), manifest=manifest(sd), checksum=checksum(sd), vocabulary=np.array(info.voc),
+                    stn_input=stn_in[:, :, ::4, ::4].contiguous(), ctrl=ctrl, rectified=rect[:, :, ::4, ::5].contiguous(),
+                    encoder=feats[:, :, ::8].contiguous(), feats01=feats[:2].contiguous(), xproj01=xproj[:2, :, ::4].contiguous(), symbols=sym.to(torch.int32),
+                    predecessors=pred.to(torch.int32), scores=score, gaps=gaps, margin=margin, pred_rec=pred_rec.to(torch.int32),
+                    strings=np.array(strings), steps=np.array(ASTER_STEPS))
+        for li, t in enumerate(layers):
+            arrs["layer%d_sample" % li] = _sample(t)
+            arrs["layer%d_norm" % li] = np.array(float(t.double().norm()))
+        for i, (s_in, y_in, lg, s_out, alpha) in steps.items():
+            arrs.update({"step%d_state" % i: s_in, "step%d_y" % i: y_in.to(torch.int32), "step%d_logits" % i: lg, "step%d_new" % i: s_out,
+                         "step%d_alpha" % i: alpha})
+        save("aster", **arrs)
+    finally:
+        restore()
+
+
+def gen_aster_beam():
+    """Backtracking of the beam search (attention_recognition_head.py:124-184): the reference's own beam_search run on hand-made
+    decoder outputs -- a stand-in DecoderUnit that returns a table of per-(step, row) log-probabilities, so the stored symbols,
+    predecessors and scores are hand-made -- with EOS at step 0, mid-string and never, several beams ending at the same step and
+    exactly equal final scores.  Plus get_str_list's strings and the four vocabularies."""
+    ref, restore = _aster_reference()
+    from utils.metrics import get_str_list
+    from utils.labelmaps import get_vocabulary
+    AsterInfo = _ref_aster_info
+    try:
+        head = ref.decoder
+        B, K, C, eos, L = 6, 5, 97, 94, 100
+        rng = np.random.RandomState(5)
+        table = np.full((L, B * K, C), 1e-4)
+
+        def put(t, b, probs, rows=range(K), same=False):
+            for r in rows:       # rows of an image differ slightly unless `same`: exact score ties only where they are meant
+                for c, pr in probs.items():
+                    table[t, b * K + r, c] = pr if same else pr * (1.0 - 0.03 * r - 0.001 * (c % 7))
+        put(0, 0, {eos: 0.5, 10: 0.2, 11: 0.1, 12: 0.05})                       # image 0: EOS wins at step 0
+        for t in range(1, L):
+            put(t, 0, {int(rng.randint(0, 94)): 0.4, eos: 0.3})
+        for t in range(L):                                                      # image 1: EOS mid-string (step 4) on the best beam
+            put(t, 1, {20 + t % 7: 0.6, 30 + t % 5: 0.2, eos: 0.7 if t == 4 else 0.01})
+        for t in range(L):                                                      # image 2: never EOS
+            put(t, 2, {40 + t % 11: 0.5, 50 + t % 3: 0.3, eos: 1e-6})
+        put(0, 3, {10: 0.25, 11: 0.25, 12: 0.25, 13: 0.125, 14: 0.0625}, same=True)        # image 3: equal beams, all end at step 3 with equal scores
+        for t in range(1, L):
+            put(t, 3, {eos: 0.5, 15: 0.25} if t == 3 else {16 + t % 4: 0.5, 70: 0.25, eos: 1e-6}, same=t <= 3)      # (distinct scores at the last step)
+        for t in range(L):                                                      # image 4: several beams end at the same steps
+            put(t, 4, {eos: 0.3, 60: 0.3, 61: 0.2} if t in (2, 6) else {62 + t % 9: 0.45, 80: 0.35, eos: 1e-5})
+        for t in range(L):                                                      # image 5: random rows
+            for r in range(K):
+                put(t, 5, {int(c): float(v) for c, v in zip(rng.choice(C, 6, replace=False), rng.rand(6))}, rows=[r])
+        table = torch.from_numpy(np.log(table / table.sum(-1, keepdims=True))).float()
+        calls = []
+
+        class Stub(torch.nn.Module):
+            def forward(self, x, state, y_prev):
+                calls.append(1)
+                return table[len(calls) - 1], state
+        head.decoder = Stub()
+        pred_rec, _ = head.beam_search(torch.zeros(B, 25, 512), K, eos)
+        # the stored tensors of that run: the same loop on the table (no decoder state involved)
+        import torch.nn.functional as F
+        seq = torch.full((B * K, 1), -float('inf'))
+        seq[::K] = 0.0
+        pos = (torch.arange(B) * K).view(-1, 1)
+        sym, pred, score = [], [], []
+        for i in range(L):
+            cand = (seq.repeat(1, C) + F.log_softmax(table[i], dim=1)).view(B, -1)
+            top, idx = cand.topk(K, 1)
+            y = (idx % C).view(-1)
+            seq = top.view(-1, 1)
+            score.append(seq.view(-1).clone())
+            pred.append((idx // C + pos).view(-1))
+            seq = seq.masked_fill(y.view(-1, 1).eq(eos), -float('inf'))
+            sym.append(y)
+        sym, pred, score = torch.stack(sym), torch.stack(pred), torch.stack(score)
+        from dpmn_amd.utils.labelmaps import beam_backtrack
+        mine = torch.from_numpy(beam_backtrack(sym.numpy(), pred.numpy(), score.numpy(), B, K, eos))
+        assert (mine == pred_rec).all(), "numpy backtracking differs from the reference at images %s" % ((mine != pred_rec).any(1).nonzero().view(-1).tolist(),)
+        last = score[-1].view(B, K)
+        assert len(set(score[3, 3 * K:4 * K].tolist())) < K, "image 3 was built to end several beams with exactly equal scores"
+        info = AsterInfo('all')
+        strings, _ = get_str_list(pred_rec, torch.ones_like(pred_rec), info)
+        ids = torch.tensor([[10, 36, 62, 95, 96, 70, 94, 5] + [1] * 92, [94] + [3] * 99, list(range(94)) + [94] * 6, [96] * 100], dtype=torch.int64)
+        id_strings, _ = get_str_list(ids, torch.ones_like(ids), info)
+        save("aster_beam", symbols=sym.to(torch.int32), predecessors=pred.to(torch.int32), scores=score, pred_rec=pred_rec.to(torch.int32),
+             strings=np.array(strings), ids=ids.to(torch.int32), id_strings=np.array(id_strings),
+             **{"voc_" + v: np.array(get_vocabulary(v)) for v in ('digit', 'lower', 'upper', 'all')},
+             rec_num_classes=np.array([AsterInfo(v).rec_num_classes for v in ('digit', 'lower', 'upper', 'all')]))
+    finally:
+        restore()
+
+
+
 def gen_collate():
     """Data path: the reference's own `resizeNormalize` and `alignCollate_realWTLAMask.__call__`
     (dataset/dataset.py:1266-1319, 1966-2076) and `str_filt` (utils/util.py) run on five synthetic RGB images of ragged sizes
@@ -738,6 +942,8 @@ if __name__ == "__main__":
     which = sys.argv[1:] or ["all"]
     GENS["crnn"] = gen_crnn
     GENS["crnn_ctc"] = gen_crnn_ctc
+    GENS["aster"] = gen_aster
+    GENS["aster_beam"] = gen_aster_beam
     GENS["collate"] = gen_collate      # last: it installs extra import shims (lmdb, imgaug, torchvision.utils)
     for name, fn in GENS.items():
         if "all" in which or name in which:
