@@ -111,6 +111,11 @@ class DistillGrads(C.Structure):
                 ("dbn2_w", fp), ("dbn2_b", fp)]
 
 
+class MoranDecWeights(C.Structure):
+    NAMES = ("h2h_w", "h2h_b", "score_w", "E", "wih_ctx", "whh", "bhh", "gen_w", "gen_b")
+    _fields_ = [(n, fp) for n in NAMES]
+
+
 class AsterDecWeights(C.Structure):
     NAMES = ("s_w", "s_b", "w_w", "w_b", "E", "wih_ctx", "whh", "bhh", "fc_w", "fc_b")
     _fields_ = [(n, fp) for n in NAMES]
@@ -261,6 +266,10 @@ SIGNATURES = {
     "dpmn_aster_beam_workspace_bytes": (_sz, [_i, _i]),
     "dpmn_aster_decode_step_f32": (_i, [C.POINTER(AsterDecWeights), fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, _i, _i, _i, fp]),
     "dpmn_aster_beam_f32": (_i, [C.POINTER(AsterDecWeights), fp, fp, fp, _sz, fp, fp, fp, _i, _i, _i, _i, _i, _i, fp]),
+    "dpmn_moran_prep_f32": (_i, [fp, _l, fp, fp, _i, _i, _i, _i, _i, fp]),
+    "dpmn_moran_rectify_f32": (_i, [fp, fp, fp, fp, fp, fp, fp, fp, _i, _i, _i, _i, _i, fp]),
+    "dpmn_moran_split_nhwc_f32": (_i, [fp, fp, fp, _i, _i, _i, _i, _i, _i, fp]),
+    "dpmn_moran_decode_f32": (_i, [C.POINTER(MoranDecWeights), fp, fp, fp, fp, _i, _i, _i, _i, fp]),
     "dpmn_text_prior_compose_f32": (_i, [fp, fp, fp, fp, fp, _i, _i, _i, _i, _i, _i, _i, fp]),
     "dpmn_ln_qkv_window_attn_supported": (_i, [_i, _i, _i, _IP, _i, _i]),
     "dpmn_ln_qkv_window_attn_f32": (_i, [fp, fp, fp, fp, fp, fp, _f, fp, fp, fp, fp, _PP, _IP, _IP, _i, _i, fp, fp, _i, _i, _i, _i, _i, fp]),

@@ -3,8 +3,9 @@
 Keeps the attribute names, the per-PGRM hyper-parameter string parsing (base.py:64-82, with a safe
 parser instead of eval()), ``generator_init`` (base.py:127-198) and the checkpoint format
 (base.py:328-373), and the CRNN recogniser of the word accuracy (``CRNN_init`` / ``parse_crnn_data``, base.py:411-425) on the
-native NativeCRNN, the ASTER recogniser (``Aster_init`` / ``parse_aster_data``, base.py:427-450) on the native NativeASTER.  Out of
-scope here: the MORAN recogniser, pygame renderer.
+native NativeCRNN, the ASTER recogniser (``Aster_init`` / ``parse_aster_data``, base.py:427-450) on the native NativeASTER, the MORAN
+recogniser (``MORAN_init`` / ``parse_moran_data`` / ``converter_moran``, base.py:60-61, 375-409) on the native NativeMORAN.  Out of
+scope here: the pygame renderer.
 """
 import os
 
@@ -38,6 +39,8 @@ class TextBase(object):
         if not torch.cuda.is_available():
             raise RuntimeError("dpmn_amd: the DPMN hot path needs a MI355X (no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device())
+        from ..utils.labelmaps import MoranLabelConverter
+        self.converter_moran = MoranLabelConverter()       # base.py:60-61: digits + lowercase + '$'
         self.cal_psnr = ssim_psnr.calculate_psnr
         self.cal_ssim = ssim_psnr.SSIM()
         self.mask = self.args.mask
@@ -152,6 +155,38 @@ class TextBase(object):
         for p in model.parameters():
             p.requires_grad = False
         return model.eval()
+
+    def MORAN_init(self, path=None):
+        """base.py:375-394: MORAN(1, 37, 256, 32, 100, BidirDecoder=True) from config.TRAIN.VAL.moran_pretrained (or `path`; a plain
+        state dict, a DataParallel `module.` key prefix is stripped), here the native NativeMORAN, frozen and in eval mode.  A missing
+        or empty path raises: an untrained recogniser never produces an accuracy."""
+        from ..model.moran import NativeMORAN
+        val = getattr(self.config.TRAIN, "VAL", None)
+        model_path = (getattr(val, "moran_pretrained", None) if val is not None else None) if path is None else path
+        if not model_path or not os.path.isfile(model_path):
+            raise FileNotFoundError("dpmn_amd: the MORAN recogniser needs its weights: config TRAIN.VAL.moran_pretrained (or the path "
+                                    "argument) names no file (%r)" % (model_path,))
+        model = NativeMORAN(1, 37, 256, 32, 100, BidirDecoder=True)
+        print('loading pre-trained moran model from %s' % model_path)
+        state_dict = torch.load(model_path, map_location='cpu')
+        model.load_state_dict({k.replace("module.", ""): v for k, v in state_dict.items()})
+        model = model.to(self.device)
+        for p in model.parameters():
+            p.requires_grad = False
+        return model.eval()
+
+    def parse_moran_data(self, imgs_input):
+        """base.py:396-409: bicubic resize to 32x100 and ITU-601 luma (no normalisation) -> (tensor (B, 1, 32, 100), length (B) int32
+        = 20 decode steps per image, text, text): text is the encoding of '0' * 20 per image (B * 20 zeros, int64)."""
+        from ..model.moran import MAX_ITER, MORAN
+        batch_size = imgs_input.shape[0]
+        if imgs_input.is_cuda:
+            from .. import ops
+            tensor = ops.moran_prep(imgs_input.float(), 32, 100)[0]
+        else:
+            tensor = MORAN.parse_moran_data(imgs_input)
+        text, lens = self.converter_moran.encode(['0' * MAX_ITER] * batch_size)
+        return tensor, lens.to(torch.int32), text, text
 
     def Aster_init(self, path=None):
         """base.py:427-439: the ASTER recogniser from config.TRAIN.VAL.rec_pretrained (or `path`; the checkpoint's 'state_dict'),

@@ -224,12 +224,14 @@ class TextSR(base.TextBase):
              text_prior_fn=None):
         """super_resolution.py:340-513.  PSNR/SSIM always; recognition accuracy (lines 453-493) only when `rec` reads the SR images
         and the loader yields label strings as a 4th item: `rec` is the native CRNN (TextBase.CRNN_init, --rec crnn: its `read`), the
-        native ASTER (TextBase.Aster_init, --rec aster: its `read`) or any callable images (B,3,H,W) -> list[str].  The reference's MORAN
-        recogniser is out of scope, and without a recogniser 'accuracy' is None ("not computed"), never a fake 0.0."""
+        native ASTER (TextBase.Aster_init, --rec aster: its `read`), the native MORAN (TextBase.MORAN_init, --rec moran: its `read`, the
+        L2R decoder's strings cut at '$') or any callable images (B,3,H,W) -> list[str].  Without a recogniser 'accuracy' is None
+        ("not computed"), never a fake 0.0."""
         from ..utils.util import str_filt
         from ..model.crnn import NativeCRNN
         from ..model.aster import NativeASTER
-        reader = rec.read if isinstance(rec, (NativeCRNN, NativeASTER)) else (rec if callable(rec) else None)
+        from ..model.moran import NativeMORAN
+        reader = rec.read if isinstance(rec, (NativeCRNN, NativeASTER, NativeMORAN)) else (rec if callable(rec) else None)
         for m in model_list:
             m.eval()
         fn = text_prior_fn or self.default_text_prior()

@@ -772,3 +772,61 @@ def aster_beam(weights, feats, xproj, beam, n_class, eos, steps):
     check(lib.dpmn_aster_beam_f32(_C.byref(weights), dptr(feats), dptr(xproj), dptr(ws), nb, buf.data_ptr(), buf.data_ptr() + n,
                                   buf.data_ptr() + 2 * n, B, T, beam, n_class, eos, steps, stream()))
     return buf
+
+
+# ------------------------------------------------------------------------------ native MORAN recogniser (csrc/moran.hip)
+def moran_prep(img, out_h=32, out_w=100):
+    """parse_moran_data (base.py:396-402) for a batch: (B, >=3, H, W) in [0, 1] -> (luma plane (B, 1, out_h, out_w), the same as NHWC
+    (B, out_h, out_w, 4) with channels 1..3 zero)."""
+    B, Cc, H, W = img.shape
+    if Cc < 3:
+        raise _abi.DpmnError("moran_prep: channels 0..2 (RGB) are read, got %d channels" % Cc)
+    v, ptr, stride = _nchw_view(img)
+    plane = torch.empty(B, 1, out_h, out_w, device=img.device)
+    out = torch.empty(B, out_h, out_w, 4, device=img.device)
+    check(lib.dpmn_moran_prep_f32(ptr, stride, dptr(plane), dptr(out), B, H, W, out_h, out_w, stream()))
+    return plane, out
+
+
+def moran_rectify(omap, plane, grid_x, grid_y, acc=None):
+    """One pass of MORN behind its offset head: omap (B, Hm, Wm), plane (B, 1, H, W), acc = the running offsets (B, H, W) or None on
+    the first pass -> (new accumulated offsets, rectified plane (B, 1, H, W), rectified NHWC (B, H, W, 4))."""
+    B, _, H, W = plane.shape
+    if omap.dim() != 3 or omap.shape[0] != B or grid_x.numel() != W or grid_y.numel() != H or (acc is not None and tuple(acc.shape) != (B, H, W)):
+        raise _abi.DpmnError("moran_rectify: omap (B, Hm, Wm), plane (B, 1, H, W), grid_x (W), grid_y (H), acc (B, H, W) expected")
+    new = torch.empty(B, H, W, device=plane.device)
+    rect = torch.empty(B, 1, H, W, device=plane.device)
+    rect4 = torch.empty(B, H, W, 4, device=plane.device)
+    check(lib.dpmn_moran_rectify_f32(dptr(omap), dptr(plane), dptr(grid_x), dptr(grid_y), dptr(acc, True), dptr(new), dptr(rect),
+                                     dptr(rect4), B, H, W, omap.shape[1], omap.shape[2], stream()))
+    return new, rect, rect4
+
+
+def moran_split(x, sy, sx):
+    """x (B, H, W, 2 C) -> (x[:, ::sy, ::sx, :C], x[:, ::sy, ::sx, C:]) as contiguous tensors."""
+    B, H, W, C2 = x.shape
+    Cc = C2 // 2
+    y1 = torch.empty(B, (H - 1) // sy + 1, (W - 1) // sx + 1, Cc, device=x.device)
+    y2 = torch.empty_like(y1)
+    check(lib.dpmn_moran_split_nhwc_f32(dptr(x), dptr(y1), dptr(y2), B, H, W, Cc, sy, sx, stream()))
+    return y1, y2
+
+
+def moran_dec_weights(tensors):
+    """dict name -> tensor (the fields of dpmn_moran_dec_weights) -> a filled _abi.MoranDecWeights; the caller keeps the tensors."""
+    w = _abi.MoranDecWeights()
+    for n in _abi.MoranDecWeights.NAMES:
+        setattr(w, n, dptr(tensors[n]))
+    return w
+
+
+def moran_decode(weights, feats, fproj, steps, n_class):
+    """The greedy L2R decoder on the current stream: feats / fproj (B, T, 256) -> (logits (B, steps, n_class), ids (B, steps) int32)."""
+    import ctypes as _C
+    B, T, D = feats.shape
+    if tuple(fproj.shape) != (B, T, D) or D != 256:
+        raise _abi.DpmnError("moran_decode: feats and fproj (B, T, 256) expected")
+    logits = torch.empty(B, steps, n_class, device=feats.device)
+    ids = torch.empty(B, steps, dtype=torch.int32, device=feats.device)
+    check(lib.dpmn_moran_decode_f32(_C.byref(weights), dptr(feats), dptr(fproj), dptr(logits), ids.data_ptr(), B, T, steps, n_class, stream()))
+    return logits, ids

@@ -1,6 +1,7 @@
 """Host side of the ASTER recogniser's text handling: the vocabulary (reference utils/labelmaps.py get_vocabulary), `AsterInfo`
 (interfaces/base.py:480-492), the prediction half of get_str_list (utils/metrics.py:15-68) and the backtracking of the beam search
-(model/recognizer/attention_recognition_head.py:124-184) in numpy on the stored per-step tensors."""
+(model/recognizer/attention_recognition_head.py:124-184) in numpy on the stored per-step tensors.  And of the MORAN recogniser's: the
+label converter of interfaces/base.py:60-61 (utils/utils_moran.py strLabelConverterForAttention) and the cut at '$'."""
 import string
 
 import numpy as np
@@ -83,3 +84,40 @@ def beam_backtrack(symbols, predecessors, scores, batch_size, beam_width, eos):
         steps.append(cur)
     best = (_order_desc(s)[:, 0] + pos[:, 0])
     return np.stack([step[best] for step in reversed(steps)], 1).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ MORAN (reference utils/utils_moran.py)
+MORAN_ALPHABET = string.digits + string.ascii_lowercase + '$'      # base.py:60-61: joined with ':' and split again; '$' ends a string
+
+
+class MoranLabelConverter(object):
+    """strLabelConverterForAttention(alphabet, ':') of interfaces/base.py:61: class c <-> MORAN_ALPHABET[c]."""
+
+    def __init__(self, alphabet=MORAN_ALPHABET):
+        self.alphabet = list(alphabet)
+        self.dict = {c: i for i, c in enumerate(self.alphabet)}
+
+    def encode(self, text):
+        """str or list of str -> (LongTensor of the concatenated class ids, LongTensor of the lengths); case is ignored."""
+        import torch
+        texts = [text] if isinstance(text, str) else list(text)
+        return (torch.LongTensor([self.dict[c.lower()] for s in texts for c in s]), torch.LongTensor([len(s) for s in texts]))
+
+    def decode(self, t, length):
+        """flat class ids + lengths -> str (one length) or list of str."""
+        ids = np.asarray(t).reshape(-1).tolist()
+        lens = np.asarray(length).reshape(-1).tolist()
+        assert len(ids) == sum(lens), "texts with length: {} does not match declared length: {}".format(len(ids), sum(lens))
+        out, i = [], 0
+        for n in lens:
+            out.append(''.join(self.alphabet[c] for c in ids[i:i + n]))
+            i += n
+        return out[0] if len(lens) == 1 else out
+
+
+def moran_strings(ids):
+    """(B, L) class ids of the L2R decoder -> strings cut at the first '$' (super_resolution.py:458-459)."""
+    conv = MoranLabelConverter()
+    ids = np.asarray(ids)
+    texts = conv.decode(ids.reshape(-1), [ids.shape[1]] * ids.shape[0])
+    return [s.split('$')[0] for s in ([texts] if isinstance(texts, str) else texts)]

@@ -423,6 +423,33 @@ int dpmn_aster_decode_step_f32(const dpmn_aster_dec_weights* w, const float* fea
                                float* logits, int R, int T, int n_class, dpmn_stream_t stream);
 int dpmn_aster_beam_f32(const dpmn_aster_dec_weights* w, const float* feats, const float* xproj, float* ws, size_t ws_bytes, int* sym,
                         int* pred, float* score, int B, int T, int beam, int n_class, int eos, int steps, dpmn_stream_t stream);
+/* ------------------------------------------------------------------ native MORAN recogniser (moran.hip; model/moran.py NativeMORAN)
+ * moran_prep:      parse_moran_data (interfaces/base.py:396-402) = crnn_prep's bicubic resize + luma (no normalisation), written twice:
+ *                  plane (B, Ho, Wo), the image MORN's warp samples, and out_nhwc4 (B, Ho, Wo, 4), the input of the first convs.
+ * moran_rectify:   one pass of MORN behind its offset head (morn.py:63-71 / 74-82): omap (B, Hm, Wm) -> pool(relu(o)) -
+ *                  pool(relu(-o)) with MaxPool2d(2, 1) -> grid_sample (bilinear, zero padding, align_corners=False) on the identity
+ *                  grid grid_x (W) / grid_y (H) -> acc_out (B, H, W) = the offsets (acc_in null: the first pass) or acc_in + the
+ *                  offsets (a buffer of its own: the second pass costs no copy) -> rect (B, H, W) = grid_sample(plane, (grid_x, grid_y + acc_out)), also as
+ *                  rect_nhwc4 (B, H, W, 4), channel 0.
+ * moran_split_nhwc: x (B, H, W, 2 C) -> y1 = x[:, ::sy, ::sx, :C], y2 = x[:, ::sy, ::sx, C:], both (B, Ho, Wo, C), Ho = (H - 1) / sy
+ *                  + 1: separates conv1 | downsample of a residual stage's first block, run as one conv, and gathers the rows of
+ *                  the (2, 1) stages, run at stride 1; C % 4 == 0.
+ * moran_decode:    the greedy L2R attention decoder (asrn_res.py:127-144, test branch of AttentionCell), all `steps` steps in ONE
+ *                  launch, hidden = feature = embedding width 256, on fp32 MFMA in every compute mode.  dpmn_moran_dec_weights:
+ *                  h2h_w (256, 256) / h2h_b; score_w (256); E (n_class + 1, 768) = char_embeddings W_ih[:, 256:]^T + b_ih; wih_ctx
+ *                  (768, 256) = W_ih[:, :256] contiguous; whh (768, 256), bhh (768); gen_w (n_class, 256), gen_b.  feats (B, T, 256)
+ *                  BiLSTM output, fproj (B, T, 256) = i2h(feats), once per batch.  logits (B, steps, n_class), ids (B, steps) = the
+ *                  arg-max classes (equal logits: the lower class); the next embedding index is id + 1, the first one 0. */
+typedef struct dpmn_moran_dec_weights {
+  const float *h2h_w, *h2h_b, *score_w, *E, *wih_ctx, *whh, *bhh, *gen_w, *gen_b;
+} dpmn_moran_dec_weights;
+int dpmn_moran_prep_f32(const float* img, long img_stride, float* plane, float* out_nhwc4, int B, int H, int W, int Ho, int Wo,
+                        dpmn_stream_t stream);
+int dpmn_moran_rectify_f32(const float* omap, const float* plane, const float* grid_x, const float* grid_y, const float* acc_in,
+                           float* acc_out, float* rect, float* rect_nhwc4, int B, int H, int W, int Hm, int Wm, dpmn_stream_t stream);
+int dpmn_moran_split_nhwc_f32(const float* x, float* y1, float* y2, int B, int H, int W, int C, int sy, int sx, dpmn_stream_t stream);
+int dpmn_moran_decode_f32(const dpmn_moran_dec_weights* w, const float* feats, const float* fproj, float* logits, int* ids, int B, int T,
+                          int steps, int n_class, dpmn_stream_t stream);
 int dpmn_layernorm_std_f32(const float* x, const float* a2, const float* b2, float eps, float* y, long M, int C,
                            dpmn_stream_t stream);
 /* GPU half of the TextZoom collate (dataset/dataset.py:1266-1319 resizeNormalize, 2007-2013 alignCollate_realWTLAMask.__call__):

@@ -3,7 +3,8 @@
 
 `python main.py --arch tatt --mask --gradient --stu_iter_b1 3 --stu_iter_b2 3 ...` builds the same TextSR mission on the
 HIP-backed modules.  `--rec crnn` loads the native CRNN recogniser (config TRAIN.VAL.crnn_pretrained) for the word accuracy,
-`--rec aster` the native ASTER recogniser (config TRAIN.VAL.rec_pretrained, when set); MORAN is not built.  Without a TextZoom LMDB directory the loop is fed synthetic (images_hr, images_lr, label_vecs)
+`--rec aster` the native ASTER recogniser (config TRAIN.VAL.rec_pretrained, when set), `--rec moran` the native MORAN recogniser
+(config TRAIN.VAL.moran_pretrained, when set).  Without a TextZoom LMDB directory the loop is fed synthetic (images_hr, images_lr, label_vecs)
 batches of the real shapes -- `--synthetic_steps` of them -- and the text priors come from `TextSR.synthetic_text_prior()`;
 everything between the loader and the optimizer step is the real path.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
@@ -44,12 +45,15 @@ def synthetic_loader(batch_size, steps, seed, labels=False):
 def recogniser(mission, args):
     """--rec crnn: the native CRNN of config TRAIN.VAL.crnn_pretrained (TextBase.CRNN_init); --rec aster: the native ASTER of
     config TRAIN.VAL.rec_pretrained (TextBase.Aster_init) -> word accuracy in test / eval and best-model selection by accuracy.
-    --rec aster without configured weights and --rec moran: accuracy is not computed (None)."""
+    --rec moran: the native MORAN of config TRAIN.VAL.moran_pretrained (TextBase.MORAN_init).  --rec aster / --rec moran without
+    configured weights: accuracy is not computed (None)."""
     if args.rec == "crnn":
         return mission.CRNN_init()
     val = getattr(mission.config.TRAIN, "VAL", None)
     if args.rec == "aster" and val is not None and getattr(val, "rec_pretrained", None):
         return mission.Aster_init()[0]
+    if args.rec == "moran" and val is not None and getattr(val, "moran_pretrained", None):
+        return mission.MORAN_init()
     print("--rec %s: recogniser not built (only --rec crnn is); accuracy is not computed" % args.rec)
     return None
 

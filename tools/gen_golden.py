@@ -868,6 +868,126 @@ def gen_aster_beam():
         restore()
 
 
+MORAN_IDS = [0, 1, 10, 3, 5, 18, 31, 8]      # members of utils/moran_synth.py's image pool (chosen by gen_moran_pick on the reference's own run, asserted below)
+MORAN_MARGIN = 1e-3
+
+
+def _moran_reference():
+    from model.moran.moran import MORAN
+    from dpmn_amd.utils import moran_synth
+    ref = MORAN(1, 37, 256, 32, 100, BidirDecoder=True, inputDataType='torch.FloatTensor', CUDA=False).eval()
+    sd = ref.state_dict()
+    assert len(sd) == 427 and abs(sum(p.numel() for p in ref.parameters()) / 1e6 - 20.34) < 0.01
+    moran_synth.moran_fill_(sd, 91)
+    sd = {k: v.clone() for k, v in sd.items()}
+    ref.load_state_dict(sd)
+    return ref, sd
+
+
+def _moran_run(ref, img):
+    """parse_moran_data (base.py:396-409, restated: importing interfaces.base pulls in the LMDB data path) and the reference's eval
+    call (super_resolution.py:453-457) with debug=False, which gives the same predictions without the cv2 / colour drawing."""
+    import torch.nn.functional as F
+    n = img.shape[0]
+    x = F.interpolate(img, (32, 100), mode='bicubic')
+    gray = 0.299 * x[:, 0:1] + 0.587 * x[:, 1:2] + 0.114 * x[:, 2:3]
+    length = torch.IntTensor([20] * n)
+    text = torch.zeros(n * 20, dtype=torch.long)
+    preds, _ = ref(gray, length, text, text, test=True, debug=False)
+    return gray, length, preds.view(n, 20, 37)
+
+
+def gen_moran_pick():
+    """Prints, for every member of the image pool, the reference's string and smallest decision margin: MORAN_IDS is chosen from
+    this list (margin >= 1e-3, distinct strings, some cut by '$' and some not)."""
+    from dpmn_amd.utils import moran_synth
+    from dpmn_amd.utils.labelmaps import moran_strings
+    ref, _ = _moran_reference()
+    _, _, logits = _moran_run(ref, moran_synth.moran_images(moran_synth.POOL))
+    top2 = logits.topk(2, 2)[0]
+    margin = (top2[..., 0] - top2[..., 1]).min(1)[0]
+    ids = logits.max(2)[1]
+    for i, s in enumerate(moran_strings(ids.numpy())):
+        print("%2d margin %.2e  %-22r first $ %s" % (i, float(margin[i]), s, (ids[i] == 36).nonzero()[:1].view(-1).tolist()))
+
+
+def gen_moran():
+    """The MORAN recogniser (model/moran/) in eval mode (test=True) on name-seeded weights (utils/moran_synth.py moran_fill_, seed 91)
+    and 8 soft-bar images of 32 x 128: the prep output, the accumulated offsets after each of MORN's two passes and the rectified image
+    (morn.py:58-82 re-run on the reference's own members and checked against its forward), the ResNet and BiLSTM outputs, i2h(feats),
+    the 20 x 37 L2R logits with their ids and margins, the strings of the reference's converter."""
+    import string
+    import torch.nn.functional as F
+    from dpmn_amd.utils import moran_synth
+    from utils import utils_moran
+    ref, sd = _moran_reference()
+    img = moran_synth.moran_images(MORAN_IDS)
+    n = img.shape[0]
+    grab = {}
+    ref.ASRN.cnn.register_forward_hook(lambda m, i, o: grab.__setitem__("resnet", o.clone()))
+    ref.ASRN.rnn.register_forward_hook(lambda m, i, o: grab.__setitem__("rnn", o.clone()))
+    gray, length, logits = _moran_run(ref, img)
+    morn = ref.MORN
+    grid, gx, gy = morn.grid[:n], morn.grid_x[:n], morn.grid_y[:n]
+
+    def offs(x):
+        o = morn.cnn(x)
+        pool = morn.pool(F.relu(o)) - morn.pool(F.relu(-o))
+        return F.grid_sample(pool, grid).permute(0, 2, 3, 1).contiguous()
+    acc1 = offs(F.interpolate(gray, size=(32, 100), mode='bilinear'))
+    rect1 = F.grid_sample(gray, torch.cat([gx, gy + acc1], 3))
+    acc2 = acc1 + offs(rect1)
+    rect = F.grid_sample(gray, torch.cat([gx, gy + acc2], 3))
+    assert torch.equal(rect, morn(gray, True)), "the step-by-step MORN does not reproduce the reference's forward"
+    ids = logits.max(2)[1]
+    top2 = logits.topk(2, 2)[0]
+    margin = top2[..., 0] - top2[..., 1]
+    alphabet = ':'.join(string.digits + string.ascii_lowercase + '$')
+    conv = utils_moran.strLabelConverterForAttention(alphabet, ':')
+    sim = conv.decode(ids.reshape(-1), length)
+    strings = [s.split('$')[0] for s in sim]
+    # conditions on the fixture
+    assert len(set(strings)) >= 4, strings
+    assert any((r == 36).any() for r in ids) and any(not (r == 36).any() for r in ids), strings
+    assert float(margin.min()) >= MORAN_MARGIN, "decision margin %.2e: choose other MORAN_IDS (gen_moran_pick)" % float(margin.min())
+    amax = float(acc2.abs().max())
+    iy = ((gy + acc2 + 1) * 32 - 1) / 2      # grid_sample's source row (align_corners=False): every pixel keeps a tap inside the image
+    iy1 = ((gy + acc1 + 1) * 32 - 1) / 2
+    assert amax >= 0.05, "offsets trivially small: %.3f" % amax
+    assert float(min(iy.min(), iy1.min())) > -1.0 and float(max(iy.max(), iy1.max())) < 32.0, "a pixel samples wholly outside the image"
+    rnn = grab["rnn"]
+    i2h = ref.ASRN.attentionL2R.attention_cell.i2h(rnn)
+    assert float((img - img.half().float()).abs().max()) == 0.0      # fp16-representable by construction: stored losslessly in half the bytes
+    print("moran: strings %s, min margin %.2e, max |offset| %.3f, source rows %.2f .. %.2f" % (strings, float(margin.min()), amax, float(iy.min()), float(iy.max())))
+    save("moran", ids=np.array(MORAN_IDS), manifest=manifest(sd), checksum=checksum(sd), images=img.half(), prep=gray,
+         offsets1=acc1[..., 0].contiguous(), offsets2=acc2[..., 0].contiguous(), rectified=rect, resnet=grab["resnet"][:, ::4].contiguous(),
+         rnn=rnn.permute(1, 0, 2)[:, :, ::2].contiguous(), i2h=i2h.permute(1, 0, 2)[:, :, ::2].contiguous(), logits=logits,
+         pred_ids=ids.to(torch.int32), margin=margin, strings=np.array(strings), raw_strings=np.array(sim))
+
+
+def gen_moran_labels():
+    """The reference's own strLabelConverterForAttention.decode (utils/utils_moran.py:79-107) with the converter of base.py:60-61 on
+    flat id sequences of 20 per image, exactly as eval() calls it (super_resolution.py:457-459): '$' at position 0, at position 19,
+    nowhere, mid-string, every class once; plus a single sequence (the scalar-length branch)."""
+    import string
+    from utils import utils_moran
+    alphabet = ':'.join(string.digits + string.ascii_lowercase + '$')
+    conv = utils_moran.strLabelConverterForAttention(alphabet, ':')
+    L = 20
+    rows = [[36] + [5] * (L - 1),                              # '$' at position 0: empty string
+            list(range(10, 29)) + [36],                         # '$' at position 19
+            [(3 * i) % 36 for i in range(L)],                   # no '$' at all
+            [17, 14, 21, 21, 24, 36, 36, 1, 2, 36] + [0] * 10,  # cut mid-string, more '$' behind
+            list(range(0, 20)), list(range(17, 37))]            # every class once (two rows)
+    rng = np.random.RandomState(13)
+    for _ in range(6):
+        rows.append(rng.randint(0, 37, L).tolist())
+    ids = torch.tensor(rows, dtype=torch.int64)
+    texts = conv.decode(ids.reshape(-1), torch.IntTensor([L] * len(rows)))
+    single = conv.decode(ids[3], torch.IntTensor([L]))
+    save("moran_labels", ids=ids.to(torch.int32), texts=np.array(texts), cut=np.array([s.split('$')[0] for s in texts]),
+         single=np.array(single), alphabet=np.array(conv.alphabet))
+
 
 def gen_collate():
     """Data path: the reference's own `resizeNormalize` and `alignCollate_realWTLAMask.__call__`
@@ -944,7 +1064,11 @@ if __name__ == "__main__":
     GENS["crnn_ctc"] = gen_crnn_ctc
     GENS["aster"] = gen_aster
     GENS["aster_beam"] = gen_aster_beam
+    GENS["moran"] = gen_moran
+    GENS["moran_labels"] = gen_moran_labels
     GENS["collate"] = gen_collate      # last: it installs extra import shims (lmdb, imgaug, torchvision.utils)
     for name, fn in GENS.items():
         if "all" in which or name in which:
             fn()
+    if "moran_pick" in which:
+        gen_moran_pick()

@@ -45,6 +45,7 @@ def install():
                                trunc_normal_=torch.nn.init.trunc_normal_)
     _stub("IPython", embed=lambda *a, **k: None)
     _stub("cv2")
+    _stub("torchsnooper")      # imported at file scope by model/moran/morn.py, never called
     tv = _stub("torchvision")
     tv.models = _stub("torchvision.models")
     tv.transforms = _stub("torchvision.transforms")
