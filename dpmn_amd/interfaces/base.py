@@ -4,7 +4,8 @@ Keeps the attribute names, the per-PGRM hyper-parameter string parsing (base.py:
 parser instead of eval()), ``generator_init`` (base.py:127-198) and the checkpoint format
 (base.py:328-373), and the CRNN recogniser of the word accuracy (``CRNN_init`` / ``parse_crnn_data``, base.py:411-425) on the
 native NativeCRNN, the ASTER recogniser (``Aster_init`` / ``parse_aster_data``, base.py:427-450) on the native NativeASTER, the MORAN
-recogniser (``MORAN_init`` / ``parse_moran_data`` / ``converter_moran``, base.py:60-61, 375-409) on the native NativeMORAN.  Out of
+recogniser (``MORAN_init`` / ``parse_moran_data`` / ``converter_moran``, base.py:60-61, 375-409) on the native NativeMORAN, and the
+comparison images (``tripple_display`` / ``test_display``, base.py:275-326) on one ``ops.display_triple`` launch.  Out of
 scope here: the pygame renderer.
 """
 import os
@@ -223,6 +224,39 @@ class TextBase(object):
         first conv reads (dpmn_crnn_prep_f32; channels 0..2 of the input are read)."""
         from .. import ops
         return ops.crnn_prep(imgs_input.float(), 32, 100)[..., 0:1].permute(0, 3, 1, 2)
+
+    # ------------------------------------------------------------------ comparison images (base.py:275-326)
+    def _write_triples(self, out_dir, image_in, image_out, image_target, sel, names):
+        """The PNGs of the images `sel` under out_dir: ONE ops.display_triple launch, ONE device-to-host copy, PIL only encodes
+        (Image.fromarray(arr).save(path) is what torchvision's save_image ends in).  A later equal name overwrites an earlier one."""
+        if not sel:
+            return
+        from PIL import Image
+        from .. import ops
+        arr = ops.display_triple(image_in, image_out, image_target, sel).cpu().numpy()
+        os.makedirs(out_dir, exist_ok=True)
+        for a, name in zip(arr, names):
+            Image.fromarray(a).save(os.path.join(out_dir, name))
+
+    def tripple_display(self, image_in, image_out, image_target, pred_str_lr, pred_str_sr, label_strs, index):
+        """base.py:275-298: the first min(B, TRAIN.VAL.n_vis) images of the batch as <vis_dir>/<index>/<LR string>_<SR string>_
+        <label>_.png, each the bicubically enlarged LR input over the SR output over the HR target (channels 0..2)."""
+        from ..utils.display import image_name
+        val = getattr(self.config.TRAIN, "VAL", None)
+        n_vis = getattr(val, "n_vis", None) if val is not None else None
+        n = min(image_in.shape[0], 10 if n_vis is None else int(n_vis))      # (10: config/super_resolution.yaml)
+        names = [image_name(pred_str_lr[i], pred_str_sr[i], label_strs[i]) for i in range(n)]
+        self._write_triples(os.path.join(self.vis_dir, str(index)), image_in, image_out, image_target, list(range(n)), names)
+
+    def test_display(self, image_in, image_out, image_target, pred_str_lr, pred_str_sr, label_strs, str_filt):
+        """base.py:300-326: the images whose filtered SR string differs from the filtered label, as <vis_dir>/display/<filtered LR
+        string>_<filtered SR string>_<filtered label>_.png -> their number."""
+        from ..utils.display import image_name
+        sel = [i for i in range(image_in.shape[0]) if str_filt(pred_str_sr[i], 'lower') != str_filt(label_strs[i], 'lower')]
+        names = [image_name(str_filt(pred_str_lr[i], 'lower'), str_filt(pred_str_sr[i], 'lower'), str_filt(label_strs[i], 'lower'))
+                 for i in sel]
+        self._write_triples(os.path.join(self.vis_dir, 'display'), image_in, image_out, image_target, sel, names)
+        return len(sel)
 
     def save_checkpoint(self, netG_list, epoch, iters, best_acc_dict, best_model_info, is_best, converge_list,
                         recognizer=None, metric="sum", trainer=None):

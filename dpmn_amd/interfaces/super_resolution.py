@@ -221,12 +221,18 @@ class TextSR(base.TextBase):
 
     @torch.no_grad()
     def eval(self, model_list, val_loader, index=0, rec=None, aster_info=None, rec_list=None, model_psn=None, crnn_psn=None,
-             text_prior_fn=None):
+             text_prior_fn=None, display=False, display_failures=False):
         """super_resolution.py:340-513.  PSNR/SSIM always; recognition accuracy (lines 453-493) only when `rec` reads the SR images
         and the loader yields label strings as a 4th item: `rec` is the native CRNN (TextBase.CRNN_init, --rec crnn: its `read`), the
         native ASTER (TextBase.Aster_init, --rec aster: its `read`), the native MORAN (TextBase.MORAN_init, --rec moran: its `read`, the
         L2R decoder's strings cut at '$') or any callable images (B,3,H,W) -> list[str].  Without a recogniser 'accuracy' is None
-        ("not computed"), never a fake 0.0."""
+        ("not computed"), never a fake 0.0.
+        display=True (opt-in here; always on in the reference, line 505): after the loop the LAST batch's LR / SR / HR images are
+        written by tripple_display under <vis_dir>/<index>/, named by the recogniser's strings of the LR and SR batch and the label
+        (one extra recogniser call, on that batch's LR images; empty strings without a recogniser or labels).  display_failures=True
+        (test(display=True); the call the reference has commented out at line 762): test_display on EVERY batch -- one more
+        recogniser call per batch for the LR strings -- and their total under the key 'visualized'.  With both off nothing is
+        written, no extra recogniser call is made and the returned dict has the keys it always had."""
         from ..utils.util import str_filt
         from ..model.crnn import NativeCRNN
         from ..model.aster import NativeASTER
@@ -237,6 +243,7 @@ class TextSR(base.TextBase):
         fn = text_prior_fn or self.default_text_prior()
         psnr, ssim, n = [], [], 0
         n_correct, n_labelled = 0, 0
+        last, visualized = None, 0      # display: (images_lr, sr, images_hr, LR strings | None, SR strings | None, labels | None) of the last batch
         # the batches of an evaluation pass are independent: two of them in flight (RefinePipeline).  The loop is software-pipelined:
         # batch i + 1 is prepared and SUBMITTED before this stream waits for batch i and queues its metrics -- a lane is ordered
         # behind this stream at submit time, so metrics queued before the submit would chain the lanes one after the other
@@ -249,18 +256,25 @@ class TextSR(base.TextBase):
                 cached = self._eval_pipe = (key, RefinePipeline(self, model_list, model_psn, 2))
             pipe = cached[1]
 
-        def finish(sr, images_hr, labels):
-            nonlocal n, n_correct, n_labelled
+        def finish(sr, images_hr, labels, images_lr):
+            nonlocal n, n_correct, n_labelled, last, visualized
             if pipe is not None:
-                RefinePipeline.wait(sr)
+                RefinePipeline.wait(sr)      # (the display kernels below read sr on this stream: behind the batch's lane)
             p, s = ops.psnr_ssim(sr, images_hr)
             psnr.append(p)
             ssim.append(s)
             n += sr.shape[0]
+            preds_sr = preds_lr = None
             if reader is not None and labels is not None:      # (the host sync of the read: batch i + 1 is already submitted)
-                for pred, target in zip(reader(sr[:, :3]), labels):
+                preds_sr = reader(sr[:, :3])
+                for pred, target in zip(preds_sr, labels):
                     n_correct += int(pred == str_filt(target, 'lower'))
                 n_labelled += len(labels)
+                if display_failures:
+                    preds_lr = reader(images_lr[:, :3])
+                    visualized += self.test_display(images_lr, sr, images_hr, preds_lr, preds_sr, labels, str_filt)
+            if display:
+                last = (images_lr, sr, images_hr, preds_lr, preds_sr, labels)
 
         pending = None
         for data in val_loader:
@@ -275,15 +289,24 @@ class TextSR(base.TextBase):
                 sr = pipe.submit(images_lr, label_vecs, text_prior_fn=fn)
                 if pending is not None:
                     finish(*pending)
-                pending = (sr, images_hr, labels)
+                pending = (sr, images_hr, labels, images_lr)
             else:
-                finish(self.refine(model_list, model_psn, images_lr, label_vecs, fn), images_hr, labels)
+                finish(self.refine(model_list, model_psn, images_lr, label_vecs, fn), images_hr, labels, images_lr)
         if pending is not None:
             finish(*pending)
+        if display and last is not None:      # super_resolution.py:505, once per pass, on the last batch
+            images_lr, sr, images_hr, preds_lr, preds_sr, labels = last
+            blank = [''] * images_lr.shape[0]
+            if preds_lr is None and preds_sr is not None:
+                preds_lr = reader(images_lr[:, :3])      # super_resolution.py:461-489: the same recogniser on the LR batch
+            self.tripple_display(images_lr, sr, images_hr, preds_lr or blank, preds_sr or blank, labels if labels is not None else blank, index)
         psnr_avg = float(torch.stack(psnr).mean().item())
         ssim_avg = float(torch.stack(ssim).mean().item())
         accuracy = round(n_correct / n_labelled, 4) if n_labelled else None
-        return {'psnr': psnr, 'ssim': ssim, 'accuracy': accuracy, 'psnr_avg': round(psnr_avg, 6), 'ssim_avg': round(ssim_avg, 6)}
+        res = {'psnr': psnr, 'ssim': ssim, 'accuracy': accuracy, 'psnr_avg': round(psnr_avg, 6), 'ssim_avg': round(ssim_avg, 6)}
+        if display_failures:
+            res['visualized'] = visualized
+        return res
 
     # ------------------------------------------------------------------ training (super_resolution.py:113-278)
     def build_training(self, world_size=1, group=None):
@@ -522,7 +545,7 @@ class TextSR(base.TextBase):
         run.graph = graph
         return run
 
-    def train(self, loader=None, steps=None, val_loader=None, rec=None, epochs=None, sampler=None):
+    def train(self, loader=None, steps=None, val_loader=None, rec=None, epochs=None, sampler=None, display=False):
         """Training loop (super_resolution.py:125-337) over (images_hr, images_lr, label_vecs) batches (synthetic ones, or the
         TextZoom reader of dataset/textzoom.py through main.py).
         loader: a callable `loader(epoch) -> iterable` (a fresh pass per epoch), a re-iterable (list, DataLoader-like: walked
@@ -532,7 +555,8 @@ class TextSR(base.TextBase):
         eval + best-model checkpoint every VAL.valInterval when a val_loader is given (best = recognition accuracy when `rec`
         computes one, else PSNR), checkpoint.pth every saveInterval and at the end, epoch written to checkpoints and log.csv.
         Rank 0 writes the files; under ZeRO-1 every save waits for the step's parameter all-gather first (trainer.sync_params:
-        the gather runs asynchronously on RCCL's stream, a state_dict clone before it lands would tear the checkpoint)."""
+        the gather runs asynchronously on RCCL's stream, a state_dict clone before it lands would tear the checkpoint).
+        display=True: every evaluation pass writes its comparison images (eval(display=True), index = epoch; rank 0 only)."""
         dist = torch.distributed
         world = dist.get_world_size() if dist.is_initialized() else 1
         rank = dist.get_rank() if dist.is_initialized() else 0
@@ -613,7 +637,8 @@ class TextSR(base.TextBase):
                     trainer.sync_params()
                     current, psnr_d, ssim_d = {}, {}, {}
                     for data_name, vl in val_sets:
-                        md = self.eval(models, vl() if callable(vl) else vl, epoch, rec=rec, model_psn=psn, text_prior_fn=fn)
+                        md = self.eval(models, vl() if callable(vl) else vl, epoch, rec=rec, model_psn=psn, text_prior_fn=fn,
+                                       display=display and rank == 0)
                         converge.append({'iterator': it, 'acc': md['accuracy'], 'psnr': md['psnr_avg'], 'ssim': md['ssim_avg']})
                         score = md['accuracy'] if md['accuracy'] is not None else md['psnr_avg']
                         current[data_name], psnr_d[data_name], ssim_d[data_name] = float(score), md['psnr_avg'], md['ssim_avg']
@@ -656,11 +681,12 @@ class TextSR(base.TextBase):
             crnn = self._crnn_psn = load_crnn(path, self.device)
         return crnn.label_vecs(images_lr[:, :3])
 
-    def test(self, loader=None, rec=None):
+    def test(self, loader=None, rec=None, display=False):
         """super_resolution.py:515-775: PGRMs from model_best_{k}.pth, CMM from model_best_cmm.pth, PSN from model_{arch}.pth
-        under --resume (all required: there is no evaluation of untrained weights)."""
+        under --resume (all required: there is no evaluation of untrained weights).  display=True: the comparison images of the
+        last batch under <vis_dir>/0/ and those of every wrongly read image under <vis_dir>/display/ (their number: 'visualized')."""
         models, psn = self.build_models(testing=True)
         if loader is None:
             raise RuntimeError("dpmn_amd: pass a loader of (images_hr, images_lr, label_vecs) batches: "
                                "dataset.textzoom.sr_batches(self.get_test_data(dir)[1], device) or dpmn_amd.utils.synth.synth_batch")
-        return self.eval(models, loader, 0, rec=rec, model_psn=psn)
+        return self.eval(models, loader, 0, rec=rec, model_psn=psn, display=display, display_failures=display)

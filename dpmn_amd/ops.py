@@ -150,6 +150,61 @@ def collate_u8(img_u8, with_mask):
     return out
 
 
+_DISPLAY_TABLES = {}
+
+
+def _display_tables(insz, outsz, device):
+    """The device copy of utils.display.pil_bicubic_tables(insz, outsz), uploaded once per size pair and device."""
+    key = (insz, outsz, device.type, device.index)
+    t = _DISPLAY_TABLES.get(key)
+    if t is None:
+        from .utils.display import pil_bicubic_tables
+        t = _DISPLAY_TABLES[key] = torch.from_numpy(pil_bicubic_tables(insz, outsz).copy()).to(device)
+    return t
+
+
+def _display_planes(x, what):
+    """(tensor, pointer, batch stride, channel stride) of an NCHW fp32 CUDA tensor whose planes are contiguous."""
+    if not x.is_cuda:
+        raise _abi.DpmnError("display_triple: the comparison images are composed on the GPU (got a %s %s); there is no CPU "
+                             "fallback" % (x.device, what))
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] < 3:
+        raise _abi.DpmnError("display_triple: %s must be float32 (B, >= 3, H, W), got %s %s" % (what, x.dtype, tuple(x.shape)))
+    if x.stride()[2:] != (x.shape[3], 1) or x.stride(1) < x.shape[2] * x.shape[3] or (x.shape[0] > 1 and x.stride(0) < 3 * x.stride(1)):
+        x = x.contiguous()
+    return x, x.data_ptr(), max(x.stride(0), 3 * x.stride(1)), x.stride(1)      # (the batch stride of a batch of one is arbitrary)
+
+
+def display_triple(image_in, image_out, image_target, sel):
+    """The LR / SR / HR comparison images of tripple_display / test_display (base.py:275-326) for the images `sel` (a device int32
+    tensor or a list of indices) -> (n, 3 H, W, 3) uint8 on the device: rows [0, H) image_in (B, >=3, h, w) enlarged the way
+    ToPILImage + PIL's bicubic resize do, rows [H, 2H) image_out, rows [2H, 3H) image_target (B, >=3, H, W) quantised the way
+    save_image does; byte for byte the reference's file content.  Channels 0..2 are read in place (strides)."""
+    a, pa, abs_, acs = _display_planes(image_in, "image_in")
+    o, po, obs, ocs = _display_planes(image_out, "image_out")
+    t, pt, tbs, tcs = _display_planes(image_target, "image_target")
+    B, _, h, w = a.shape
+    H, W = t.shape[2:]
+    if o.shape[0] != B or t.shape[0] != B or tuple(o.shape[2:]) != (H, W):
+        raise _abi.DpmnError("display_triple: image_in (B, C, h, w), image_out and image_target (B, C, H, W) expected, got %s %s %s"
+                             % (tuple(a.shape), tuple(o.shape), tuple(t.shape)))
+    if h > H or w > W:
+        raise NotImplementedError("display_triple: the LR input is only enlarged (%d x %d -> %d x %d asked)" % (h, w, H, W))
+    if not torch.is_tensor(sel):
+        sel = [int(i) for i in sel]
+        if any(i < 0 or i >= B for i in sel):
+            raise IndexError("display_triple: sel %s outside the batch of %d" % (sel, B))
+        sel = torch.tensor(sel, dtype=torch.int32).to(a.device)
+    n = sel.numel()
+    out = torch.empty(n, 3 * H, W, 3, dtype=torch.uint8, device=a.device)
+    if n == 0:
+        return out
+    tab_h, tab_v = _display_tables(w, W, a.device), _display_tables(h, H, a.device)
+    check(lib.dpmn_display_triple_u8(pa, abs_, acs, po, obs, ocs, pt, tbs, tcs, _i32(sel, "display_triple"), n, tab_h.data_ptr(),
+                                     tab_v.data_ptr(), tab_h.shape[1] - 2, out.data_ptr(), B, h, w, H, W, stream()))
+    return out
+
+
 def maxpool(x, kh, kw, scale=None, shift=None):
     """nn.MaxPool2d((kh,kw), stride (kh,kw)) over NHWC; scale/shift: the producer's BatchNorm affine + ReLU applied on load."""
     B, H, W, Cc = x.shape

@@ -456,6 +456,20 @@ int dpmn_layernorm_std_f32(const float* x, const float* a2, const float* b2, flo
  * img (B, H, W, 3) uint8 = the PIL-resized RGB pixels, out (B, 3 + with_mask, H, W) = ToTensor (/255, CHW) and, with_mask, the mask
  * channel (PIL RGB -> L, threshold at the image's mean L: L > mean ? 0 : 1). */
 int dpmn_collate_u8_f32(const unsigned char* img, float* out, int B, int H, int W, int with_mask, dpmn_stream_t stream);
+/* The comparison images of an evaluation pass (display.hip; tripple_display / test_display, interfaces/base.py:275-326): for the n
+ * images sel[0..n) (device int32; an index outside [0, B) gives a black triple) out (n, 3 H, W, 3) uint8, HWC:
+ *   rows [0, H)    image_in (B, >=3, h, w): x.mul(255).byte() (ToPILImage; clamped to [0, 255] first) -> PIL's fixed-point bicubic
+ *                  resize to H x W: horizontal pass, uint8 intermediate, vertical pass, clip8((2^21 + sum in * k) >> 22)
+ *   rows [H, 2H)   image_out (B, >=3, H, W): x.mul(255).add_(0.5).clamp_(0, 255) truncated (save_image; two fp32 roundings, no FMA)
+ *   rows [2H, 3H)  image_target (B, >=3, H, W), the same
+ * Channels 0..2 are read through the batch / channel strides (in floats; planes are contiguous), so a channel-sliced view of a
+ * 4-channel masked batch needs no copy.  tab_h (W, 2 + ksize) / tab_v (H, 2 + ksize) device int32: per output column / row
+ * [first input index, taps, k_0 ..], 22 fraction bits, built on the host in float64 (utils/display.py pil_bicubic_tables);
+ * ksize = 5 (bicubic, h <= H and w <= W: the LR image is only enlarged).  W <= 2048. */
+int dpmn_display_triple_u8(const float* image_in, long in_batch_stride, long in_chan_stride, const float* image_out, long out_batch_stride,
+                           long out_chan_stride, const float* image_target, long tgt_batch_stride, long tgt_chan_stride, const int* sel,
+                           int n, const int* tab_h, const int* tab_v, int ksize, unsigned char* out, int B, int h, int w, int H, int W,
+                           dpmn_stream_t stream);
 
 /* rotation augmentation of the trainer (utils/util.py:37-58 torch_rotate_img; super_resolution.py:144-151, 358-365):
  * per-image affine with aspect-ratio jitter -> affine_grid (align_corners=False) -> bilinear grid_sample, zeros padding.

@@ -87,7 +87,7 @@ def main(config, args):
             loader = sr_batches(mission.get_test_data(args.test_data_dir)[1], mission.device, mission.mask)
         else:
             loader = synthetic_loader(bs, args.synthetic_steps, 1000 + rank, labels=rec is not None)
-        res = mission.test(loader, rec=rec)
+        res = mission.test(loader, rec=rec, display=args.vis_dir is not None and rank == 0)
         if rank == 0:
             with open(result_path, "a") as out:
                 csv.writer(out).writerow([args.rec, "synthetic", res["accuracy"], res["psnr_avg"], res["ssim_avg"]])
@@ -113,9 +113,11 @@ def main(config, args):
             val_loader = {name: (lambda v=vdl: sr_batches(v, mission.device, mission.mask))
                           for name, vdl in zip(subset_names(val_dirs), val_dls)} if val_dls else None
             mission.train(lambda epoch: sr_batches(dl, mission.device, mission.mask), epochs=config.TRAIN.epochs,
-                          sampler=getattr(mission, "train_sampler", None), val_loader=val_loader, rec=rec)
+                          sampler=getattr(mission, "train_sampler", None), val_loader=val_loader, rec=rec,
+                          display=args.vis_dir is not None)
         else:
-            mission.train(synthetic_loader(bs, args.synthetic_steps, 2000 + rank), steps=args.synthetic_steps, rec=rec)
+            mission.train(synthetic_loader(bs, args.synthetic_steps, 2000 + rank), steps=args.synthetic_steps, rec=rec,
+                          display=args.vis_dir is not None)
 
 
 def subset_names(val_dirs):

@@ -1057,6 +1057,85 @@ def gen_collate():
     save("collate", **out)
 
 
+def gen_display():
+    """The LR / SR / HR comparison images of tripple_display (interfaces/base.py:275-298) for ops.display_triple.  torchvision is
+    absent and the reference method cannot be imported, so the expected bytes come from PIL itself plus the two torchvision formulas
+    restated on torch CPU tensors: ToPILImage = x.mul(255).byte(), Image.resize((W, H), BICUBIC), ToTensor = / 255, make_grid(nrow=1,
+    padding=0) = vertical stack, save_image = x.mul(255).add_(0.5).clamp_(0, 255).to(uint8).  Inputs are stored (small or compressible):
+      a  B = 3, 4 channels, 16x64 -> 32x128: image 0 random, image 1 binary 0 / 1 (overshoot clipping in both passes), image 2 the
+         quantisation edges: SR / HR values k / 255 and (k + 0.5) / 255, LR values k / 255, each exact and one ulp up and down, all k
+      b  6x10 -> 16x24 (non-integer ratio)      c  64x256 -> 128x512 (config 4), blocky content so that the file stays small"""
+    from PIL import Image
+    from dpmn_amd.utils import display as dsp
+    rng = np.random.RandomState(20240611)
+    f32 = np.float32
+
+    def expected(lr, sr, hr, sel):
+        H, W = hr.shape[-2:]
+        out = []
+        for b in sel:
+            u8 = torch.from_numpy(lr[b, :3]).mul(255).byte().numpy().transpose(1, 2, 0)
+            big = np.asarray(Image.fromarray(np.ascontiguousarray(u8)).resize((W, H), Image.BICUBIC))
+            t_in = torch.from_numpy(np.ascontiguousarray(big.transpose(2, 0, 1))).float().div(255)
+            grid = torch.cat([t_in, torch.from_numpy(sr[b, :3]), torch.from_numpy(hr[b, :3])], 1)      # make_grid(nrow=1, padding=0)
+            out.append(grid.mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(torch.uint8).numpy())
+        return np.stack(out)
+
+    def ulps(v):
+        v = np.asarray(v, f32)
+        return np.concatenate([np.nextafter(v, f32(-1)), v, np.nextafter(v, f32(2))]).astype(f32)
+
+    k = np.arange(256, dtype=np.float64)
+    edge_lr = ulps((k / 255).astype(f32))                                                   # 768 values: the truncation boundary
+    edge_sr = np.concatenate([ulps((k / 255).astype(f32)), ulps(((k + 0.5) / 255).astype(f32))])      # 1536: the rounding boundary
+    lr = np.empty((3, 4, 16, 64), f32)
+    sr = np.empty((3, 4, 32, 128), f32)
+    hr = np.empty((3, 4, 32, 128), f32)
+    lr[:, 3], sr[:, 3], hr[:, 3] = 0.6, 0.3, 0.9            # a 4th channel that would show if it were read
+    lr[0, :3], sr[0, :3], hr[0, :3] = rng.rand(3, 16, 64), rng.rand(3, 32, 128), rng.rand(3, 32, 128)
+    lr[1, :3], sr[1, :3], hr[1, :3] = rng.randint(0, 2, (3, 16, 64)), rng.randint(0, 2, (3, 32, 128)), rng.randint(0, 2, (3, 32, 128))
+    for c in range(3):
+        plane = np.resize(np.roll(edge_lr, 37 * c), 16 * 64)
+        lr[2, c] = plane.reshape(16, 64)
+        sr[2, c] = np.resize(np.roll(edge_sr, 101 * c), 32 * 128).reshape(32, 128)
+        hr[2, c] = np.resize(np.roll(edge_sr[::-1], 53 * c), 32 * 128).reshape(32, 128)
+    for c in range(3):
+        assert np.isin(edge_lr, lr[2, c]).all() and np.isin(edge_sr, sr[2, c]).all() and np.isin(edge_sr, hr[2, c]).all()
+    # x * 255 + 0.5 rounded once (a fused multiply-add: exact in float64, then to fp32) gives other floats than the two roundings
+    # of save_image on some crafted values; recorded, not asserted on the bytes: next to (k + 0.5) / 255 both forms truncate to
+    # the same byte on every value tried, so the fixture pins the two-step form without depending on that
+    two = (edge_sr * f32(255) + f32(0.5))
+    one = (edge_sr.astype(np.float64) * 255.0 + 0.5).astype(f32)
+    n_fused_differs = int((two != one).sum())
+    # overshoot: unclipped sums of either pass below 0 / above 255 on the binary image
+    lo = hi = 0
+    u8 = dsp.quantize_lr(lr[1, :3]).transpose(1, 2, 0).astype(np.int64)
+    th, tv = dsp.pil_bicubic_tables(64, 128), dsp.pil_bicubic_tables(16, 32)
+    hor = np.stack([(1 << 21) + sum(u8[:, th[x, 0] + j] * int(th[x, 2 + j]) for j in range(th[x, 1])) for x in range(128)], 1) >> 22
+    lo, hi = lo + int((hor < 0).sum()), hi + int((hor > 255).sum())
+    hor = np.clip(hor, 0, 255)
+    ver = np.stack([(1 << 21) + sum(hor[tv[y, 0] + j] * int(tv[y, 2 + j]) for j in range(tv[y, 1])) for y in range(32)], 0) >> 22
+    lo, hi = lo + int((ver < 0).sum()), hi + int((ver > 255).sum())
+    assert lo >= 100 and hi >= 100, "the binary image clips too few overshoot pixels (%d below, %d above)" % (lo, hi)
+    sel_a = [2, 0]
+    exp_a = expected(lr, sr, hr, sel_a)
+    exp_all = expected(lr, sr, hr, [0, 1, 2])
+    assert not (exp_all[0] == exp_all[1]).all() and not (exp_all[1] == exp_all[2]).all() and not (exp_all[0] == exp_all[2]).all()
+    assert (exp_a[0] == exp_all[2]).all() and (exp_a[1] == exp_all[0]).all() and not (exp_a[0] == exp_a[1]).all()
+
+    lr_b, sr_b, hr_b = rng.rand(1, 3, 6, 10).astype(f32), rng.rand(1, 3, 16, 24).astype(f32), rng.rand(1, 3, 16, 24).astype(f32)
+    exp_b = expected(lr_b, sr_b, hr_b, [0])
+
+    def blocky(h, w, bs):      # uint8: random colours in bs x bs blocks (stored as uint8, the test divides by 255)
+        return np.kron(rng.randint(0, 256, (3, h // bs, w // bs)), np.ones((bs, bs), np.int64)).astype(np.uint8)
+    lr_c, sr_c, hr_c = blocky(64, 256, 4)[None], blocky(128, 512, 8)[None], blocky(128, 512, 8)[None]
+    exp_c = expected(*((a.astype(f32) / f32(255)) for a in (lr_c, sr_c, hr_c)), [0])
+    assert not (exp_c[0, :128] == exp_c[0, 128:256]).all()
+    save("display", a_lr=lr, a_sr=sr, a_hr=hr, a_sel=np.array(sel_a, np.int32), a_expected=exp_a,
+         b_lr=lr_b, b_sr=sr_b, b_hr=hr_b, b_expected=exp_b, c_lr_u8=lr_c, c_sr_u8=sr_c, c_hr_u8=hr_c, c_expected=exp_c,
+         edge_lr=edge_lr, edge_sr=edge_sr, n_fused_differs=np.array(n_fused_differs), overshoot=np.array([lo, hi]))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["all"]
@@ -1066,7 +1145,8 @@ if __name__ == "__main__":
     GENS["aster_beam"] = gen_aster_beam
     GENS["moran"] = gen_moran
     GENS["moran_labels"] = gen_moran_labels
-    GENS["collate"] = gen_collate      # last: it installs extra import shims (lmdb, imgaug, torchvision.utils)
+    GENS["display"] = gen_display
+    GENS["collate"] = gen_collate     # last: it installs extra import shims (lmdb, imgaug, torchvision.utils)
     for name, fn in GENS.items():
         if "all" in which or name in which:
             fn()
