@@ -256,7 +256,7 @@ SIGNATURES = {
     "dpmn_vl_tokens_f32": (_i, [fp, fp, fp, _i, _i, _i, _i, fp]),
     "dpmn_vl_pp_pool_f32": (_i, [fp, _i, fp, fp, fp, fp, _i, _i, _i, _i, _i, fp]),
     "dpmn_vl_decode_i32": (_i, [fp, fp, fp, _i, _i, _i, _i, fp]),
-    "dpmn_crnn_prep_f32": (_i, [fp, _l, fp, _i, _i, _i, _i, _i, fp]),
+    "dpmn_gray_prep_f32": (_i, [fp, _l, fp, fp, _i, _i, _i, _i, _i, fp]),
     "dpmn_maxpool2d_f32": (_i, [fp, fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, fp]),
     "dpmn_bilstm_f32": (_i, [fp, fp, fp, fp, _i, _i, _i, fp]),
     "dpmn_ctc_greedy_i32": (_i, [fp, _i, _i, fp, fp, _i, _i, fp]),
@@ -266,7 +266,6 @@ SIGNATURES = {
     "dpmn_aster_beam_workspace_bytes": (_sz, [_i, _i]),
     "dpmn_aster_decode_step_f32": (_i, [C.POINTER(AsterDecWeights), fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, _i, _i, _i, fp]),
     "dpmn_aster_beam_f32": (_i, [C.POINTER(AsterDecWeights), fp, fp, fp, _sz, fp, fp, fp, _i, _i, _i, _i, _i, _i, fp]),
-    "dpmn_moran_prep_f32": (_i, [fp, _l, fp, fp, _i, _i, _i, _i, _i, fp]),
     "dpmn_moran_rectify_f32": (_i, [fp, fp, fp, fp, fp, fp, fp, fp, _i, _i, _i, _i, _i, fp]),
     "dpmn_moran_split_nhwc_f32": (_i, [fp, fp, fp, _i, _i, _i, _i, _i, _i, fp]),
     "dpmn_moran_decode_f32": (_i, [C.POINTER(MoranDecWeights), fp, fp, fp, fp, _i, _i, _i, _i, fp]),

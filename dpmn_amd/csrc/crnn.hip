@@ -1,6 +1,6 @@
 // Kernels of the native CRNN recogniser (model/crnn.py NativeCRNN; reference model/crnn/crnn.py) that are not a conv / GEMM:
-//   k_crnn_prep       parse_crnn_data (base.py:419-425): torch's bicubic resize to Ho x Wo + ITU-601 luma, NHWC with 4 channels
-//                     (dpmn_moran_prep_f32: parse_moran_data is the same arithmetic; it also writes the luma as a plane)
+//   k_gray_prep       parse_crnn_data (base.py:419-425): torch's bicubic resize to Ho x Wo + ITU-601 luma, NHWC with 4 channels
+//                     (parse_moran_data is the same arithmetic; NativeMORAN also takes the luma as a plane)
 //   k_maxpool2d       nn.MaxPool2d(k, stride, padding) over NHWC with -inf padding (pooling2 / pooling3: (2,2), (2,1), (0,1))
 //   k_lstm_step       one time step of a bidirectional nn.LSTM, both directions and the whole batch in one launch: h W_hh^T on
 //                     fp32 MFMA with the cell update in the epilogue
@@ -32,7 +32,7 @@ __device__ __forceinline__ int cubic_src(int dst, int in, int out, float& t) {
 
 // one output pixel per thread: out[b][y][x] = (luma, 0, 0, 0); luma = 0.299 R + 0.587 G + 0.114 B of the bicubic samples; plane
 // (optional): the same luma as a (B, Ho, Wo) plane (parse_moran_data: the image MORN's warp samples)
-__global__ void k_crnn_prep(const float* __restrict__ img, long img_stride, float* __restrict__ out, float* __restrict__ plane, int B, int H,
+__global__ void k_gray_prep(const float* __restrict__ img, long img_stride, float* __restrict__ out, float* __restrict__ plane, int B, int H,
                             int W, int Ho, int Wo) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)B * Ho * Wo) return;
@@ -180,20 +180,11 @@ __global__ void k_crnn_label_vecs(const float* __restrict__ logits, int ld, int 
 
 extern "C" {
 
-int dpmn_crnn_prep_f32(const float* img, long img_stride, float* out_nhwc4, int B, int H, int W, int Ho, int Wo, dpmn_stream_t stream) {
-  DPMN_REQUIRE(img && out_nhwc4 && B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && img_stride >= 3L * H * W, "crnn_prep: bad arguments");
+int dpmn_gray_prep_f32(const float* img, long img_stride, float* plane, float* out_nhwc4, int B, int H, int W, int Ho, int Wo,
+                       dpmn_stream_t stream) {
+  DPMN_REQUIRE(img && out_nhwc4 && B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && img_stride >= 3L * H * W, "gray_prep: bad arguments");
   const long n = (long)B * Ho * Wo;
-  hipLaunchKernelGGL(k_crnn_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), img, img_stride, out_nhwc4,
-                     (float*)nullptr, B, H, W, Ho, Wo);
-  DPMN_CHECK_LAUNCH();
-  return DPMN_OK;
-}
-
-int dpmn_moran_prep_f32(const float* img, long img_stride, float* plane, float* out_nhwc4, int B, int H, int W, int Ho, int Wo,
-                        dpmn_stream_t stream) {
-  DPMN_REQUIRE(img && plane && out_nhwc4 && B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && img_stride >= 3L * H * W, "moran_prep: bad arguments");
-  const long n = (long)B * Ho * Wo;
-  hipLaunchKernelGGL(k_crnn_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), img, img_stride, out_nhwc4, plane, B, H,
+  hipLaunchKernelGGL(k_gray_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), img, img_stride, out_nhwc4, plane, B, H,
                      W, Ho, Wo);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;

@@ -1,5 +1,5 @@
 // Kernels of the native MORAN recogniser (model/moran.py NativeMORAN; reference model/moran/) that are not a conv / GEMM / pool /
-// BiLSTM (the prep kernel is k_crnn_prep with a second output, crnn.hip):
+// BiLSTM (the prep kernel is k_gray_prep with its plane output, crnn.hip):
 //   k_moran_rectify   one pass of MORN (morn.py:63-71 / 74-82) behind the offset head: pool(relu(o)) - pool(relu(-o)) with
 //                     MaxPool2d(2, 1) of the Hm x Wm offset map, grid_sample (bilinear, zero padding, align_corners=False) of it on the
 //                     identity grid, accumulation into the running offsets, and the zero-padded bilinear warp of the image along y

@@ -234,10 +234,8 @@ class TextSR(base.TextBase):
         recogniser call per batch for the LR strings -- and their total under the key 'visualized'.  With both off nothing is
         written, no extra recogniser call is made and the returned dict has the keys it always had."""
         from ..utils.util import str_filt
-        from ..model.crnn import NativeCRNN
-        from ..model.aster import NativeASTER
-        from ..model.moran import NativeMORAN
-        reader = rec.read if isinstance(rec, (NativeCRNN, NativeASTER, NativeMORAN)) else (rec if callable(rec) else None)
+        from ..model.native import PackedEval
+        reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
         for m in model_list:
             m.eval()
         fn = text_prior_fn or self.default_text_prior()

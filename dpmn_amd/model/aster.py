@@ -24,6 +24,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..utils.labelmaps import AsterInfo, beam_backtrack, ids_to_strings
 from . import packing
+from .native import PackedEval, bilstm_stack
 from .stn import TPSSpatialTransformer
 
 TPS_INPUT, TPS_OUTPUT, N_CTRL, TPS_MARGINS, BEAM = (32, 64), (32, 100), 20, (0.05, 0.05), 5
@@ -212,26 +213,19 @@ class ASTER(nn.Module):
         return ids_to_strings(rec.numpy(), info or AsterInfo('all'))
 
 
-class NativeASTER(ASTER):
+class NativeASTER(PackedEval, ASTER):
     """Drop-in for the reference's ASTER recogniser in eval mode, batched, on libdpmn_hip.so (module docstring); the torch layers
     hold the parameters and are never called."""
+
+    EVAL_ONLY = "dpmn_amd NativeASTER: only the eval-mode forward is built (BatchNorm folded, beam search)"
 
     def __init__(self, arch='ResNet_ASTER', rec_num_classes=97, sDim=512, attDim=512, max_len_labels=100, eos=94, STN_ON=True):
         super().__init__(arch, rec_num_classes, sDim, attDim, max_len_labels, eos, STN_ON)
         if sDim != 512 or attDim != 512 or max_len_labels != 100 or not (0 <= eos < rec_num_classes <= 128):
             raise NotImplementedError("dpmn_amd NativeASTER: built for sDim = attDim = 512, max_len_labels = 100, up to 128 classes")
         self.info = AsterInfo('all') if rec_num_classes == 97 else None
-        self._packed = None
 
-    def _check_eval(self):
-        if self.training:
-            raise RuntimeError("dpmn_amd NativeASTER: only the eval-mode forward is built (BatchNorm folded, beam search)")
-
-    def _packs(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters()) + tuple((b.data_ptr(), b._version) for b in self.buffers())
-        if self._packed is not None and self._packed[0] == key:
-            return self._packed[1]
-        sd = {k: v.detach() for k, v in self.state_dict().items()}
+    def _build_packs(self, sd):
         stn = []
         for i in range(6):
             p = "stn_head.stn_convnet.%d." % (2 * i)
@@ -244,11 +238,7 @@ class NativeASTER(ASTER):
                 p = "layer%d.%d." % (li + 1, bi)
                 down = fold(p + "downsample.0", p + "downsample.1") if bi == 0 else None
                 blocks.append((fold(p + "conv1", p + "bn1"), fold(p + "conv2", p + "bn2"), down, planes, stride if bi == 0 else (1, 1)))
-        rnn = []
-        for li in range(2):
-            g = lambda n: (sd["encoder.rnn.%s_l%d" % (n, li)], sd["encoder.rnn.%s_l%d_reverse" % (n, li)])
-            (wf, wr), (bif, bir), (bhf, bhr), (hf, hr) = g("weight_ih"), g("bias_ih"), g("bias_hh"), g("weight_hh")
-            rnn.append((torch.cat([wf, wr], 0).contiguous(), torch.cat([bif + bhf, bir + bhr], 0).contiguous(), torch.stack([hf, hr], 0).contiguous()))
+        rnn = [packing.pack_bilstm(sd, "encoder.rnn.", li) for li in range(2)]
         d = "decoder.decoder."
         w_ih, D = sd[d + "gru.weight_ih_l0"], self.attDim
         dec = {"s_w": sd[d + "attention_unit.sEmbed.weight"].contiguous(), "s_b": sd[d + "attention_unit.sEmbed.bias"].contiguous(),
@@ -256,21 +246,19 @@ class NativeASTER(ASTER):
                "E": ops.linear(sd[d + "tgt_embedding.weight"].contiguous(), w_ih[:, :D].contiguous(), sd[d + "gru.bias_ih_l0"].contiguous()),
                "wih_ctx": w_ih[:, D:].contiguous(), "whh": sd[d + "gru.weight_hh_l0"].contiguous(), "bhh": sd[d + "gru.bias_hh_l0"].contiguous(),
                "fc_w": sd[d + "fc.weight"].contiguous(), "fc_b": sd[d + "fc.bias"].contiguous()}
-        P = {"stn": stn, "fc1_t": sd["stn_head.stn_fc1.0.weight"].t().contiguous(), "layer0": fold("layer0.0", "layer0.1", cin_pad=4),
+        return {"stn": stn, "fc1_t": sd["stn_head.stn_fc1.0.weight"].t().contiguous(), "layer0": fold("layer0.0", "layer0.1", cin_pad=4),
              "blocks": blocks, "rnn": rnn, "dec": dec, "dec_abi": ops.aster_dec_weights(dec),
              "x_w": sd[d + "attention_unit.xEmbed.weight"].contiguous(), "x_b": sd[d + "attention_unit.xEmbed.bias"].contiguous()}
-        self._packed = (key, P)
-        return P
 
-    # ------------------------------------------------------------------ stages
+    # ------------------------------------------------------------------ stages (the packs as an optional last argument: PackedEval._packs)
     def prep(self, images):
         """(B, >=3, H, W) images in [0, 1] -> (normalised NCHW (B, 3, H, W), STN input NHWC (B, 32, 64, 4))."""
         return ops.aster_prep(images.float(), *TPS_INPUT)
 
     @torch.no_grad()
-    def rectify(self, norm, stn_in):
+    def rectify(self, norm, stn_in, P=None):
         """-> (control points (B, 20, 2), rectified image (B, 3, 32, 100))."""
-        P = self._packs()
+        P = P or self._packs()
         x = stn_in
         for i, (wp, bp, cout) in enumerate(P["stn"]):
             x = ops.conv2d([x], wp, bp, cout, 3, pad=1, epi_act="relu")
@@ -283,9 +271,9 @@ class NativeASTER(ASTER):
         return ctrl, rect
 
     @torch.no_grad()
-    def resnet(self, rect):
+    def resnet(self, rect, P=None):
         """rectified NCHW image -> [layer0 .. layer5 outputs], NHWC."""
-        P = self._packs()
+        P = P or self._packs()
         wp, bp = P["layer0"]
         x = ops.conv2d([ops.nchw_to_nhwc(rect.contiguous(), 4)], wp, bp, 32, 3, pad=1, epi_act="relu")
         outs, bi = [x], 0
@@ -301,44 +289,38 @@ class NativeASTER(ASTER):
         return outs
 
     @torch.no_grad()
-    def encode(self, rect):
+    def encode(self, rect, P=None):
         """rectified image -> encoder features (B, 25, 512)."""
-        P = self._packs()
-        f = self.resnet(rect)[-1]
-        if f.shape[1] != 1:
-            raise RuntimeError("dpmn_amd NativeASTER: the height of the conv features must be 1 (rectified height 32)")
-        B, T = f.shape[0], f.shape[2]
-        x = f.reshape(B * T, f.shape[3])
-        for w_ih, b, w_hh in P["rnn"]:
-            x = ops.bilstm(ops.linear(x, w_ih, b), w_hh, B, T)
-        return x.view(B, T, -1)
+        P = P or self._packs()
+        x, B, T = self.rows(self.resnet(rect, P)[-1])
+        return bilstm_stack(x, P["rnn"], B, T).view(B, T, -1)
 
-    def xproj(self, feats):
-        P = self._packs()
+    def xproj(self, feats, P=None):
+        P = P or self._packs()
         B, T, D = feats.shape
         return ops.linear(feats.reshape(B * T, D), P["x_w"], P["x_b"]).view(B, T, -1)
 
     @torch.no_grad()
-    def decode_step(self, feats, row_img, state, y_prev):
+    def decode_step(self, feats, row_img, state, y_prev, P=None):
         """One teacher-forced decoder step: row r attends to image row_img[r]; state (R, 512), y_prev (R) -> (logits (R, n_class),
         new state, alpha (R, T))."""
         self._check_eval()
-        P = self._packs()
+        P = P or self._packs()
         i32 = lambda t: t.to(device=feats.device, dtype=torch.int32).contiguous()
-        return ops.aster_decode_step(P["dec_abi"], feats.contiguous(), self.xproj(feats), i32(row_img), state.contiguous().float(), i32(y_prev),
+        return ops.aster_decode_step(P["dec_abi"], feats.contiguous(), self.xproj(feats, P), i32(row_img), state.contiguous().float(), i32(y_prev),
                                      self.rec_num_classes)
 
     @torch.no_grad()
-    def beam_search(self, feats, beam_width=BEAM, eos=None, return_stored=False):
+    def beam_search(self, feats, beam_width=BEAM, eos=None, return_stored=False, P=None):
         """-> pred_rec (B, 100) int64 on the host (+ the stored symbols / predecessors / scores, (100, B * 5) each)."""
         self._check_eval()
         if beam_width != BEAM:
             raise NotImplementedError("dpmn_amd NativeASTER: beam width 5 (recognizer_builder.py:24)")
         eos = self.eos if eos is None else eos
-        P = self._packs()
+        P = P or self._packs()
         feats = feats.contiguous()
         B = feats.shape[0]
-        buf = ops.aster_beam(P["dec_abi"], feats, self.xproj(feats), beam_width, self.rec_num_classes, eos, self.max_len_labels)
+        buf = ops.aster_beam(P["dec_abi"], feats, self.xproj(feats, P), beam_width, self.rec_num_classes, eos, self.max_len_labels)
         h = buf.cpu().numpy()
         s, p, sc = h[0].astype(np.int64), h[1].astype(np.int64), h[2].view(np.float32)
         rec = torch.from_numpy(beam_backtrack(s, p, sc, B, beam_width, eos))
@@ -349,8 +331,8 @@ class NativeASTER(ASTER):
     @torch.no_grad()
     def pred_rec(self, images):
         self._check_eval()
-        norm, stn_in = self.prep(images)
-        return self.beam_search(self.encode(self.rectify(norm, stn_in)[1]))
+        P = self._packs()
+        return self.beam_search(self.encode(self.rectify(*self.prep(images), P)[1], P), P=P)
 
     @torch.no_grad()
     def forward(self, input_dict):

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from . import packing
+from .native import PackedEval, bilstm_stack, frozen
 
 ALPHABET = "0123456789abcdefghijklmnopqrstuvwxyz"    # strLabelConverter (utils_crnn.py): class c > 0 -> ALPHABET[c - 1], 0 = CTC blank
 
@@ -82,9 +83,7 @@ def load_crnn(path, device):
     m = CRNN(32, 1, 37, 256).to(device)
     print('loading pretrained crnn model from %s' % path)
     m.load_state_dict(torch.load(path, map_location=device))
-    for p in m.parameters():
-        p.requires_grad = False
-    return m.eval()
+    return frozen(m)
 
 
 def decode_classes(cls, length):
@@ -92,84 +91,56 @@ def decode_classes(cls, length):
     return ["".join(ALPHABET[c - 1] for c in row[:n]) for row, n in zip(cls, length)]
 
 
-class NativeCRNN(CRNN):
+class NativeCRNN(PackedEval, CRNN):
     """Drop-in for the reference's CRNN(32, 1, 37, 256) in eval mode, batched, on libdpmn_hip.so: same constructor, module tree and
     state_dict keys as `CRNN` (the torch layers hold the parameters and are never called).
-      prep   dpmn_crnn_prep_f32: bicubic 32x100 + luma straight into the NHWC(4) layout of the first conv
+      prep   dpmn_gray_prep_f32: bicubic 32x100 + luma straight into the NHWC(4) layout of the first conv
       cnn    seven NHWC convs (dpmn_conv2d_nhwc_f32) with the eval BatchNorm folded and ReLU in the epilogue; pooling0/1 on
              dpmn_maxpool_f32, pooling2/3 ((2,2), (2,1), (0,1)) on dpmn_maxpool2d_f32
       rnn    per BidirectionalLSTM: one GEMM for the input projection of every step and both directions (b_ih + b_hh folded), the
              recurrence in dpmn_bilstm_f32, the embedding Linear on the GEMM path (37 classes padded to 40 rows)
       decode dpmn_ctc_greedy_i32 (arg-max, collapse, drop blank); dpmn_crnn_label_vecs_f32 for label_vecs.
-    Rows stay image-major (b*T + t) from the conv output to the logits; `forward` returns the reference's (T, B, 37) as a view."""
+    Rows stay image-major (b*T + t) from the conv output to the logits; `forward` returns the reference's (T, B, 37) as a view.
+    The stages take the packs as an optional last argument (PackedEval._packs)."""
 
     N_PAD = 40          # the GEMM path writes whole groups of 4 columns
+    EVAL_ONLY = "dpmn_amd NativeCRNN: only the eval-mode forward is built (BatchNorm folded)"
 
     def __init__(self, imgH=32, nc=1, nclass=37, nh=256, n_rnn=2, leakyRelu=False):
         super().__init__(imgH, nc, nclass, nh, n_rnn, leakyRelu)
         if imgH != 32 or nc != 1 or nh != 256 or leakyRelu:
             raise NotImplementedError("dpmn_amd NativeCRNN: built for CRNN(32, 1, nclass, 256) with ReLU (CRNN_init's recogniser)")
         self.nclass = nclass
-        self._packed = None
 
-    def _packs(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters()) + tuple((b.data_ptr(), b._version) for b in self.buffers())
-        if self._packed is not None and self._packed[0] == key:
-            return self._packed[1]
-        sd = {k: v.detach() for k, v in self.state_dict().items()}
+    def _build_packs(self, sd):
         convs = []
         for i in range(7):
             bn = packing.bn_tuple(sd, "cnn.batchnorm%d." % i) if i in (2, 4, 6) else None
             w = sd["cnn.conv%d.weight" % i]
             wp, bp = packing.pack_conv(w, sd["cnn.conv%d.bias" % i], bn, cin_pad=4 if i == 0 else None)
             convs.append((wp, bp, w.shape[0], w.shape[2], 0 if i == 6 else 1))
-        rnn = []
-        for li in range(2):
-            p = "rnn.%d." % li
-            w_ih = torch.cat([sd[p + "rnn.weight_ih_l0"], sd[p + "rnn.weight_ih_l0_reverse"]], 0).contiguous()
-            b_ih = torch.cat([sd[p + "rnn.bias_ih_l0"] + sd[p + "rnn.bias_hh_l0"],
-                              sd[p + "rnn.bias_ih_l0_reverse"] + sd[p + "rnn.bias_hh_l0_reverse"]], 0).contiguous()
-            w_hh = torch.stack([sd[p + "rnn.weight_hh_l0"], sd[p + "rnn.weight_hh_l0_reverse"]], 0).contiguous()
-            ew, eb = sd[p + "embedding.weight"], sd[p + "embedding.bias"]
-            n = (ew.shape[0] + 3) // 4 * 4
-            if n != ew.shape[0]:
-                ew = torch.cat([ew, ew.new_zeros(n - ew.shape[0], ew.shape[1])], 0)
-                eb = torch.cat([eb, eb.new_zeros(n - eb.shape[0])], 0)
-            rnn.append((w_ih, b_ih, w_hh, ew.contiguous(), eb.contiguous()))
-        P = {"convs": convs, "rnn": rnn}
-        self._packed = (key, P)
-        return P
-
-    def _check_eval(self):
-        if self.training:
-            raise RuntimeError("dpmn_amd NativeCRNN: only the eval-mode forward is built (BatchNorm folded)")
+        rnn = [packing.pack_bilstm(sd, "rnn.%d.rnn." % li) + packing.pad_rows4(sd["rnn.%d.embedding.weight" % li], sd["rnn.%d.embedding.bias" % li])
+               for li in range(2)]
+        return {"convs": convs, "rnn": rnn}
 
     @torch.no_grad()
-    def features(self, x_nhwc4):
+    def features(self, x_nhwc4, P=None):
         """The conv stack on NHWC input with 4 channels (channel 0 = gray) -> (B, 1, T, 512)."""
-        P = self._packs()
         x = x_nhwc4
-        for i, (wp, bp, cout, k, pad) in enumerate(P["convs"]):
+        for i, (wp, bp, cout, k, pad) in enumerate((P or self._packs())["convs"]):
             x = ops.conv2d([x], wp, bp, cout, k, pad=pad, epi_act="relu")
             if i in (0, 1):
                 x = ops.maxpool(x, 2, 2)
             elif i in (3, 5):
                 x = ops.maxpool2d(x, (2, 2), (2, 1), (0, 1))
-        if x.shape[1] != 1:
-            raise RuntimeError("dpmn_amd NativeCRNN: the height of conv must be 1 (input height 32)")
         return x
 
     @torch.no_grad()
-    def logits_rows(self, x_nhwc4):
+    def logits_rows(self, x_nhwc4, P=None):
         """(B*T, 40) logits, row b*T + t; columns >= nclass are zero padding."""
-        P = self._packs()
-        f = self.features(x_nhwc4)
-        B, T = f.shape[0], f.shape[2]
-        x = f.reshape(B * T, f.shape[3])
-        for w_ih, b_ih, w_hh, ew, eb in P["rnn"]:
-            gx = ops.linear(x, w_ih, b_ih)
-            x = ops.linear(ops.bilstm(gx, w_hh, B, T), ew, eb)
-        return x, B, T
+        P = P or self._packs()
+        x, B, T = self.rows(self.features(x_nhwc4, P))
+        return bilstm_stack(x, P["rnn"], B, T), B, T
 
     def forward(self, x_gray):
         """The reference's forward: x_gray (B, 1, 32, W) -> logits (T, B, nclass) (a view of the image-major rows)."""
@@ -187,7 +158,7 @@ class NativeCRNN(CRNN):
         """Recognised strings of (B, >=3, H, W) images: prep, CNN, BiLSTMs and greedy CTC decode on the current stream, then ONE
         device-to-host copy of the decoded classes and lengths."""
         self._check_eval()
-        rows, B, T = self.logits_rows(self.prep(images))
+        rows, B, T = self.logits_rows(self.prep(images), self._packs())
         buf, _, _ = ops.ctc_greedy(rows, B, T, self.nclass)
         h = buf.cpu().numpy()
         return decode_classes(h[:B * T].reshape(B, T), h[B * T:])
@@ -196,5 +167,5 @@ class NativeCRNN(CRNN):
     def label_vecs(self, images_lr3):
         """super_resolution.py:165-169 on the native path: (B, 37, 1, T) softmax of the logits."""
         self._check_eval()
-        rows, B, T = self.logits_rows(self.prep(images_lr3))
+        rows, B, T = self.logits_rows(self.prep(images_lr3), self._packs())
         return ops.crnn_label_vecs(rows, B, T, self.nclass)

@@ -8,7 +8,7 @@ branch of the attention, MORN's random "skip rectification" branch; the R2L deco
 reference's eval reads the L2R output only, super_resolution.py:455-459).
 
 `NativeMORAN` is the same module tree with all its arithmetic in libdpmn_hip.so (eval mode only):
-  prep     dpmn_moran_prep_f32: parse_moran_data (bicubic 32 x 100 + luma, no normalisation) as the plane the warp samples and as
+  prep     dpmn_gray_prep_f32: parse_moran_data (bicubic 32 x 100 + luma, no normalisation) as the plane the warp samples and as
            the NHWC(4) input of the first convs, one launch
   rectify  MORN: per pass dpmn_maxpool2d_f32 x 3 and five NHWC convs (BatchNorm folded, ReLU epilogue) down to the 1 x 4 x 12 offset
            map, then ONE dpmn_moran_rectify_f32 (signed (2, 1) max-pool, bilinear up-sampling, accumulation, zero-padded warp);
@@ -29,6 +29,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..utils.labelmaps import moran_strings
 from . import packing
+from .native import PackedEval, bilstm_stack
 
 MAX_ITER = 20                      # parse_moran_data (base.py:405): every image is decoded for 20 steps
 STAGES = ((32, 2, 3), (64, 2, 4), (128, (2, 1), 6), (256, (2, 1), 6), (512, (2, 1), 3))       # asrn_res.py:192-196
@@ -226,26 +227,19 @@ class MORAN(nn.Module):
         return moran_strings(self.stages(images)["ids"].cpu().numpy())
 
 
-class NativeMORAN(MORAN):
+class NativeMORAN(PackedEval, MORAN):
     """Drop-in for the reference's MORAN(1, 37, 256, 32, 100, BidirDecoder=True) in eval mode, batched, on libdpmn_hip.so (module
     docstring); the torch layers hold the parameters and are never called."""
+
+    EVAL_ONLY = "dpmn_amd NativeMORAN: only the eval-mode forward is built (BatchNorm folded, greedy decoder)"
 
     def __init__(self, nc=1, nclass=37, nh=256, targetH=32, targetW=100, BidirDecoder=True):
         if (nc, nclass, nh, targetH, targetW, bool(BidirDecoder)) != (1, 37, 256, 32, 100, True):
             raise NotImplementedError("dpmn_amd NativeMORAN: built for MORAN(1, 37, 256, 32, 100, BidirDecoder=True) (MORAN_init's "
                                       "recogniser), got (%r, %r, %r, %r, %r, BidirDecoder=%r)" % (nc, nclass, nh, targetH, targetW, BidirDecoder))
         super().__init__(nc, nclass, nh, targetH, targetW, BidirDecoder)
-        self._packed = None
 
-    def _check_eval(self):
-        if self.training:
-            raise RuntimeError("dpmn_amd NativeMORAN: only the eval-mode forward is built (BatchNorm folded, greedy decoder)")
-
-    def _packs(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters()) + tuple((b.data_ptr(), b._version) for b in self.buffers())
-        if self._packed is not None and self._packed[0] == key:
-            return self._packed[1]
-        sd = {k: v.detach() for k, v in self.state_dict().items()}
+    def _build_packs(self, sd):
         fold = lambda p, **kw: packing.pack_conv(sd[p + "0.weight"], sd[p + "0.bias"], packing.bn_tuple(sd, p + "1."), **kw)
         morn = []
         for i, ci in enumerate((1, 5, 9, 12, 15)):
@@ -262,13 +256,8 @@ class NativeMORAN(MORAN):
                     blocks.append(((torch.cat([w1, wd], 0).contiguous(), torch.cat([b1, bd], 0).contiguous()), c2, cout, stride))
                 else:
                     blocks.append((fold(p + "conv1."), c2, cout, None))
-        rnn = []
-        for li in range(2):
-            p = "ASRN.rnn.%d." % li
-            g = lambda n: (sd[p + "rnn.%s_l0" % n], sd[p + "rnn.%s_l0_reverse" % n])
-            (wf, wr), (bif, bir), (bhf, bhr), (hf, hr) = g("weight_ih"), g("bias_ih"), g("bias_hh"), g("weight_hh")
-            rnn.append((torch.cat([wf, wr], 0).contiguous(), torch.cat([bif + bhf, bir + bhr], 0).contiguous(), torch.stack([hf, hr], 0).contiguous(),
-                        sd[p + "embedding.weight"].contiguous(), sd[p + "embedding.bias"].contiguous()))
+        rnn = [packing.pack_bilstm(sd, "ASRN.rnn.%d.rnn." % li) + (sd["ASRN.rnn.%d.embedding.weight" % li].contiguous(),
+                                                                   sd["ASRN.rnn.%d.embedding.bias" % li].contiguous()) for li in range(2)]
         a = "ASRN.attentionL2R."
         w_ih, nh = sd[a + "attention_cell.rnn.weight_ih"], self.nh
         dec = {"h2h_w": sd[a + "attention_cell.h2h.weight"].contiguous(), "h2h_b": sd[a + "attention_cell.h2h.bias"].contiguous(),
@@ -277,11 +266,9 @@ class NativeMORAN(MORAN):
                "wih_ctx": w_ih[:, :nh].contiguous(), "whh": sd[a + "attention_cell.rnn.weight_hh"].contiguous(),
                "bhh": sd[a + "attention_cell.rnn.bias_hh"].contiguous(), "gen_w": sd[a + "generator.weight"].contiguous(),
                "gen_b": sd[a + "generator.bias"].contiguous()}
-        P = {"morn": morn, "block0": fold("ASRN.cnn.block0.", cin_pad=4), "blocks": blocks, "rnn": rnn, "dec": dec,
+        return {"morn": morn, "block0": fold("ASRN.cnn.block0.", cin_pad=4), "blocks": blocks, "rnn": rnn, "dec": dec,
              "dec_abi": ops.moran_dec_weights(dec), "i2h_w": sd[a + "attention_cell.i2h.weight"].contiguous(),
              "gx": self.MORN.grid[0, 0, :, 0].contiguous(), "gy": self.MORN.grid[0, :, 0, 1].contiguous()}
-        self._packed = (key, P)
-        return P
 
     # ------------------------------------------------------------------ stages
     # Every stage takes the packs as an optional last argument: the cache key of _packs() walks all ~640 parameters and buffers, so
@@ -329,14 +316,8 @@ class NativeMORAN(MORAN):
     @torch.no_grad()
     def bilstm(self, f, P=None):
         """ResNet output NHWC (B, 1, 25, 512) -> BiLSTM output (B, 25, 256)."""
-        P = P or self._packs()
-        if f.shape[1] != 1:
-            raise RuntimeError("dpmn_amd NativeMORAN: the height of conv must be 1 (rectified height 32)")
-        B, T = f.shape[0], f.shape[2]
-        x = f.reshape(B * T, f.shape[3])
-        for w_ih, b, w_hh, ew, eb in P["rnn"]:
-            x = ops.linear(ops.bilstm(ops.linear(x, w_ih, b), w_hh, B, T), ew, eb)
-        return x.view(B, T, -1)
+        x, B, T = self.rows(f)
+        return bilstm_stack(x, (P or self._packs())["rnn"], B, T).view(B, T, -1)
 
     def encode(self, rect_nhwc4, P=None):
         """rectified NHWC(4) image -> BiLSTM output (B, 25, 256)."""

@@ -59,6 +59,23 @@ def bn_tuple(mod_sd, prefix, eps=1e-5):
             mod_sd[prefix + "running_var"], eps)
 
 
+def pack_bilstm(sd, prefix, layer=0):
+    """Layer `layer` of the bidirectional nn.LSTM whose state-dict keys start with `prefix` -> (w_ih (8H, In), b (8H), w_hh
+    (2, 4H, H)), contiguous, in the layout ops.bilstm reads: [forward i f g o | backward i f g o], b = bias_ih + bias_hh."""
+    f, r = (lambda n: sd["%s%s_l%d" % (prefix, n, layer)]), (lambda n: sd["%s%s_l%d_reverse" % (prefix, n, layer)])
+    return (torch.cat([f("weight_ih"), r("weight_ih")], 0).contiguous(),
+            torch.cat([f("bias_ih") + f("bias_hh"), r("bias_ih") + r("bias_hh")], 0).contiguous(),
+            torch.stack([f("weight_hh"), r("weight_hh")], 0).contiguous())
+
+
+def pad_rows4(w, b):
+    """nn.Linear weight (N, K) and bias (N) with N zero-padded to a multiple of 4 (the GEMM path writes groups of 4 columns)."""
+    n = -w.shape[0] % 4
+    if n:
+        w, b = torch.cat([w, w.new_zeros(n, w.shape[1])], 0), torch.cat([b, b.new_zeros(n)], 0)
+    return w.contiguous(), b.contiguous()
+
+
 # ---------------------------------------------------------------------------------------- training: un-packing
 def unpack_conv(dwp, weight_shape, cin_pad=None):
     """inverse of pack_conv for the weight gradient: (Cout, Kp) -> (Cout, Cin, KH, KW)."""

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from .. import ops
 from . import packing
+from .native import PackedEval
 
 LAYERS = [3, 4, 6, 6, 3]
 PLANES = [32, 64, 128, 256, 512]
@@ -143,24 +144,21 @@ class _MLM_VRM(nn.Module):
         self.nclass = 37
 
 
-class VisionLAN(nn.Module):
+class VisionLAN(PackedEval, nn.Module):
     """Drop-in for ``model.VisionLAN.VisionLAN.VisionLAN(strides, input_shape)``; ``forward(input, label_pos, training_stp,
     Train_in=False)`` returns the reference's ``(output, out_length)`` pair for a whole batch; ``recognise(images)`` is the
     batched form the text-prior path uses (logits, classes, lengths stay on the GPU)."""
+
+    EVAL_ONLY = "dpmn_amd VisionLAN: only the eval-mode inference branch is built (see the module docstring)"
 
     def __init__(self, strides=((1, 1), (2, 2), (2, 2), (2, 2), (1, 1), (1, 1)), input_shape=(3, 64, 256)):
         super().__init__()
         self.backbone = _ResNet45(strides)
         self.input_shape = list(input_shape)
         self.MLM_VRM = _MLM_VRM()
-        self._packed = None
 
-    # ------------------------------------------------------------------ weight packs (rebuilt when a parameter moves or changes)
-    def _packs(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters()) + tuple((b.data_ptr(), b._version) for b in self.buffers())
-        if self._packed is not None and self._packed[0] == key:
-            return self._packed[1]
-        sd = {k: v.detach() for k, v in self.state_dict().items()}
+    # ------------------------------------------------------------------ weight packs (PackedEval._packs: rebuilt when a parameter moves or changes)
+    def _build_packs(self, sd):
         bn = lambda pre: packing.bn_tuple(sd, pre)
         P = {"conv1": packing.pack_conv(sd["backbone.conv1_new.weight"], None, bn("backbone.bn1."), cin_pad=4), "blocks": []}
         for li, n in enumerate(LAYERS):
@@ -201,14 +199,13 @@ class VisionLAN(nn.Module):
         P["we"], P["be"] = we, be
         P["w_vrm"], P["b_vrm"] = sd["MLM_VRM.Prediction.w_vrm.weight"].contiguous(), sd["MLM_VRM.Prediction.w_vrm.bias"].contiguous()
         P["Texp"] = {}
-        self._packed = (key, P)
         return P
 
     # ------------------------------------------------------------------ batched inference
     @torch.no_grad()
-    def features(self, x_nhwc4):
+    def features(self, x_nhwc4, P=None):
         """ResNet45 on NHWC input with 4 channels (channel 3 ignored: zero weights) -> (B, 8, 32, 512)."""
-        P = self._packs()
+        P = P or self._packs()
         w, b = P["conv1"]
         x = ops.conv2d([x_nhwc4], w, b, 32, 3, stride=self.backbone.strides[0][0], pad=1, epi_act="relu")
         for e in P["blocks"]:
@@ -219,8 +216,8 @@ class VisionLAN(nn.Module):
         return x
 
     @torch.no_grad()
-    def logits_from_features(self, feat):
-        P = self._packs()
+    def logits_from_features(self, feat, P=None):
+        P = P or self._packs()
         B = feat.shape[0]
         tok = ops.vl_tokens(feat, P["pos"])                       # (B, 256, 512), + positional table
         L, D = tok.shape[1], tok.shape[2]
@@ -242,11 +239,11 @@ class VisionLAN(nn.Module):
     def recognise(self, images):
         """images: (B, >=3, H, W) floats in [0, 1] at any size (resized like parse_visionlan_data), or NHWC4 (B, 64, 256, 4).
         Returns (logits (B, 26, 37), classes (B, 25) int32, lengths (B) int32), all on the GPU."""
-        if self.training:
-            raise RuntimeError("dpmn_amd VisionLAN: only the eval-mode inference branch is built (see the module docstring)")
+        self._check_eval()
         x = images if images.shape[-1] == 4 and images.dim() == 4 and images.shape[1] == self.input_shape[1] else \
             ops.vl_resize(images, self.input_shape[1], self.input_shape[2])
-        lg = self.logits_from_features(self.features(x))
+        P = self._packs()
+        lg = self.logits_from_features(self.features(x, P), P)
         cls, length = ops.vl_decode(lg, 25)
         return lg, cls, length
 

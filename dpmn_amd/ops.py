@@ -709,15 +709,20 @@ def text_prior_compose(cls, length, atlas, advance, out_h, out_w):
 
 
 # ------------------------------------------------------------------------------ native CRNN recogniser (csrc/crnn.hip)
-def crnn_prep(img, out_h=32, out_w=100):
-    """parse_crnn_data (base.py:419-425) for a batch: (B, >=3, H, W) -> NHWC (B, out_h, out_w, 4), channel 0 = luma, 1..3 zero."""
+def _gray_prep(name, img, out_h, out_w, with_plane):
     B, Cc, H, W = img.shape
     if Cc < 3:
-        raise _abi.DpmnError("crnn_prep: channels 0..2 (RGB) are read, got %d channels" % Cc)
+        raise _abi.DpmnError("%s: channels 0..2 (RGB) are read, got %d channels" % (name, Cc))
     v, ptr, stride = _nchw_view(img)
+    plane = torch.empty(B, 1, out_h, out_w, device=img.device) if with_plane else None
     out = torch.empty(B, out_h, out_w, 4, device=img.device)
-    check(lib.dpmn_crnn_prep_f32(ptr, stride, dptr(out), B, H, W, out_h, out_w, stream()))
-    return out
+    check(lib.dpmn_gray_prep_f32(ptr, stride, dptr(plane, allow_none=True), dptr(out), B, H, W, out_h, out_w, stream()))
+    return plane, out
+
+
+def crnn_prep(img, out_h=32, out_w=100):
+    """parse_crnn_data (base.py:419-425) for a batch: (B, >=3, H, W) -> NHWC (B, out_h, out_w, 4), channel 0 = luma, 1..3 zero."""
+    return _gray_prep("crnn_prep", img, out_h, out_w, False)[1]
 
 
 def maxpool2d(x, k, stride, pad=(0, 0)):
@@ -833,14 +838,7 @@ def aster_beam(weights, feats, xproj, beam, n_class, eos, steps):
 def moran_prep(img, out_h=32, out_w=100):
     """parse_moran_data (base.py:396-402) for a batch: (B, >=3, H, W) in [0, 1] -> (luma plane (B, 1, out_h, out_w), the same as NHWC
     (B, out_h, out_w, 4) with channels 1..3 zero)."""
-    B, Cc, H, W = img.shape
-    if Cc < 3:
-        raise _abi.DpmnError("moran_prep: channels 0..2 (RGB) are read, got %d channels" % Cc)
-    v, ptr, stride = _nchw_view(img)
-    plane = torch.empty(B, 1, out_h, out_w, device=img.device)
-    out = torch.empty(B, out_h, out_w, 4, device=img.device)
-    check(lib.dpmn_moran_prep_f32(ptr, stride, dptr(plane), dptr(out), B, H, W, out_h, out_w, stream()))
-    return plane, out
+    return _gray_prep("moran_prep", img, out_h, out_w, True)
 
 
 def moran_rectify(omap, plane, grid_x, grid_y, acc=None):

@@ -376,9 +376,11 @@ int dpmn_text_prior_compose_f32(const int* cls, const int* length, const float* 
                                 int n_glyph, int GH, int GW, int Ho, int Wo, dpmn_stream_t stream);
 
 /* ------------------------------------------------------------------ native CRNN recogniser (crnn.hip; model/crnn.py NativeCRNN)
- * crnn_prep:       parse_crnn_data (interfaces/base.py:419-425): img (B, >=3, H, W) planes with batch stride img_stride (channels
- *                  0..2 read) -> torch's bicubic resize to Ho x Wo (align_corners=False, A = -0.75, taps clamped to the border, no
- *                  antialias) -> 0.299 R + 0.587 G + 0.114 B, stored NHWC with 4 channels (channel 0 = luma, 1..3 = 0).
+ * gray_prep:       parse_crnn_data = parse_moran_data (interfaces/base.py:419-425, 396-402; no normalisation): img (B, >=3, H, W)
+ *                  planes with batch stride img_stride (channels 0..2 read) -> torch's bicubic resize to Ho x Wo
+ *                  (align_corners=False, A = -0.75, taps clamped to the border, no antialias) -> 0.299 R + 0.587 G + 0.114 B, stored
+ *                  as out_nhwc4 (B, Ho, Wo, 4), the input of the first convs (channel 0 = luma, 1..3 = 0), and, unless plane is
+ *                  null, as plane (B, Ho, Wo), the image MORN's warp samples.
  * maxpool2d:       nn.MaxPool2d((kh,kw), (sh,sw), (ph,pw)) over NHWC (C % 4 == 0), padding taps are -inf; y (B, Ho, Wo, C) with
  *                  Ho = (H + 2 ph - kh) / sh + 1, Wo likewise.
  * bilstm:          the recurrence of nn.LSTM(nIn, H, bidirectional=True), H = 256: gx (B*T, 8H) = x W_ih^T + b_ih + b_hh with row
@@ -387,7 +389,8 @@ int dpmn_text_prior_compose_f32(const int* cls, const int* length, const float* 
  * ctc_greedy:      rows b*T + t of logits (leading dimension ld) -> arg-max class per step (first maximum), repeats collapsed,
  *                  blank 0 dropped: cls (B, T) (zero beyond the length), length (B).
  * crnn_label_vecs: softmax over n_class of rows b*T + t -> out (B, n_class, 1, T) (CRNN.label_vecs). */
-int dpmn_crnn_prep_f32(const float* img, long img_stride, float* out_nhwc4, int B, int H, int W, int Ho, int Wo, dpmn_stream_t stream);
+int dpmn_gray_prep_f32(const float* img, long img_stride, float* plane, float* out_nhwc4, int B, int H, int W, int Ho, int Wo,
+                       dpmn_stream_t stream);
 int dpmn_maxpool2d_f32(const float* x, float* y, int B, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
                        dpmn_stream_t stream);
 int dpmn_bilstm_f32(const float* gx, const float* w_hh, float* out, float* c_state, int B, int T, int H, dpmn_stream_t stream);
@@ -424,8 +427,7 @@ int dpmn_aster_decode_step_f32(const dpmn_aster_dec_weights* w, const float* fea
 int dpmn_aster_beam_f32(const dpmn_aster_dec_weights* w, const float* feats, const float* xproj, float* ws, size_t ws_bytes, int* sym,
                         int* pred, float* score, int B, int T, int beam, int n_class, int eos, int steps, dpmn_stream_t stream);
 /* ------------------------------------------------------------------ native MORAN recogniser (moran.hip; model/moran.py NativeMORAN)
- * moran_prep:      parse_moran_data (interfaces/base.py:396-402) = crnn_prep's bicubic resize + luma (no normalisation), written twice:
- *                  plane (B, Ho, Wo), the image MORN's warp samples, and out_nhwc4 (B, Ho, Wo, 4), the input of the first convs.
+ * The prep is dpmn_gray_prep_f32 with its plane output (above).
  * moran_rectify:   one pass of MORN behind its offset head (morn.py:63-71 / 74-82): omap (B, Hm, Wm) -> pool(relu(o)) -
  *                  pool(relu(-o)) with MaxPool2d(2, 1) -> grid_sample (bilinear, zero padding, align_corners=False) on the identity
  *                  grid grid_x (W) / grid_y (H) -> acc_out (B, H, W) = the offsets (acc_in null: the first pass) or acc_in + the
@@ -443,8 +445,6 @@ int dpmn_aster_beam_f32(const dpmn_aster_dec_weights* w, const float* feats, con
 typedef struct dpmn_moran_dec_weights {
   const float *h2h_w, *h2h_b, *score_w, *E, *wih_ctx, *whh, *bhh, *gen_w, *gen_b;
 } dpmn_moran_dec_weights;
-int dpmn_moran_prep_f32(const float* img, long img_stride, float* plane, float* out_nhwc4, int B, int H, int W, int Ho, int Wo,
-                        dpmn_stream_t stream);
 int dpmn_moran_rectify_f32(const float* omap, const float* plane, const float* grid_x, const float* grid_y, const float* acc_in,
                            float* acc_out, float* rect, float* rect_nhwc4, int B, int H, int W, int Hm, int Wm, dpmn_stream_t stream);
 int dpmn_moran_split_nhwc_f32(const float* x, float* y1, float* y2, int B, int H, int W, int C, int sy, int sx, dpmn_stream_t stream);
