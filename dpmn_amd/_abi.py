@@ -282,6 +282,9 @@ SIGNATURES = {
     "dpmn_ln_qkv_window_attn_bwd_part_rows": (_i, [_i, _i, _i]),
     "dpmn_collate_u8_f32": (_i, [fp, fp, _i, _i, _i, _i, fp]),
     "dpmn_display_triple_u8": (_i, [fp, _l, _l, fp, _l, _l, fp, _l, _l, fp, _i, fp, fp, _i, fp, _i, _i, _i, _i, _i, fp]),
+    "dpmn_resize_ragged_workspace_bytes": (_sz, [_l, _i]),
+    "dpmn_resize_ragged_u8": (_i, [fp, _l, fp, _i, _i, fp, _i, _i, fp, _sz, fp]),
+    "dpmn_quantize_sr_u8": (_i, [fp, _l, _l, fp, _i, _i, _i, fp]),
     "dpmn_profile_tag_count": (_i, []),
     "dpmn_profile_hint_bytes": (_i, [C.c_double]),
     "dpmn_profile_tag_name": (C.c_char_p, [_i]),

@@ -1,0 +1,51 @@
+"""A directory of someone's own text crops as the LR input of the SR path (main.py --demo_dir, TextSR.demo): files in sorted name
+order, decoded with PIL, converted to RGB, packed as a ragged batch (utils/resize.py pack_ragged), uploaded once and resized to the
+model's LR size on the GPU (ops.resize_ragged_u8, byte for byte PIL's bicubic resize), then finished like a TextZoom batch
+(ops.collate_u8: ToTensor and the mask channel).  The host half (`host_batches`) needs no GPU.
+"""
+import os
+
+import numpy as np
+
+
+def host_batches(dir_, batch_size):
+    """Yields (names, packed, meta) per batch of at most batch_size images: the file names and utils.resize.pack_ragged of their RGB
+    pixels.  Regular files of `dir_` in sorted name order; a file PIL cannot open, or an image pack_ragged rejects, is skipped with
+    one printed line.  A directory without files raises."""
+    from PIL import Image
+    from ..utils.resize import MAX_PACKED_BYTES, check_image, pack_ragged
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("folder: batch_size must be positive, got %d" % batch_size)
+    files = sorted(f for f in os.listdir(dir_) if os.path.isfile(os.path.join(dir_, f)))
+    if not files:
+        raise FileNotFoundError("folder: %s holds no files" % dir_)
+    names, images, nbytes = [], [], 0
+    for f in files:
+        try:
+            with Image.open(os.path.join(dir_, f)) as im:
+                a = np.asarray(im.convert('RGB'), dtype=np.uint8)
+            check_image(a, f)
+        except Exception as e:      # whatever a decoder raises on a file that is not its format, or is damaged
+            print("folder: skipping %s (%s: %s)" % (f, type(e).__name__, e))
+            continue
+        if names and nbytes + a.size > MAX_PACKED_BYTES:      # pack_ragged's limit on a batch: this image starts the next one
+            yield (names,) + pack_ragged(images)
+            names, images, nbytes = [], [], 0
+        names.append(f)
+        images.append(a)
+        nbytes += a.size
+        if len(names) == batch_size:
+            yield (names,) + pack_ragged(images)
+            names, images, nbytes = [], [], 0
+    if names:
+        yield (names,) + pack_ragged(images)
+
+
+def folder_batches(dir_, batch_size, lr_size, mask, device):
+    """Yields (names, images_lr) per batch: images_lr (B, 3 + mask, h, w) float on `device`, (h, w) = lr_size = the config's
+    (height // scale, width // scale).  Per batch one upload of the packed pixels, the ragged resize and the collate kernel."""
+    from .. import ops
+    h, w = lr_size
+    for names, packed, meta in host_batches(dir_, batch_size):
+        yield names, ops.collate_u8(ops.resize_ragged_u8(packed.to(device, non_blocking=True), meta, h, w), mask)

@@ -112,17 +112,22 @@ def finish_on_gpu(images_u8, mask, device):
 class alignCollate_realWTLAMask(object):
     """collate_fn of the training loader (base.py:99-102); returns the 9-tuple of dataset.py:2076 with None in the positions of
     the YUV copies and the pseudo-LR batch.  gpu_finish=True (ours): positions 0 and 2 hold the resized uint8 (B, H, W, 3) pixels
-    and `sr_batches(loader, device)` finishes them on the GPU -- same values, bit for bit (tests/test_gpu_dataset.py)."""
+    and `sr_batches(loader, device)` finishes them on the GPU -- same values, bit for bit (tests/test_gpu_dataset.py).
+    gpu_resize=True (ours, opt-in): no PIL resize here either; positions 0 and 2 hold the utils.resize.pack_ragged pair (packed uint8
+    pixels of the decoded images, (B, 3) meta) and `sr_batches` resizes them on the GPU (ops.resize_ragged_u8, the same bytes as PIL's
+    bicubic resize; tests/test_gpu_resize.py) before it finishes them."""
 
     def __init__(self, imgH=64, imgW=256, down_sample_scale=4, keep_ratio=False, min_ratio=1, mask=False, alphabet=53, train=True,
-                 y_domain=False, gpu_finish=False):
+                 y_domain=False, gpu_finish=False, gpu_resize=False):
         self.imgH, self.imgW, self.down_sample_scale, self.mask = imgH, imgW, down_sample_scale, mask
-        self.gpu_finish = gpu_finish
+        self.gpu_finish, self.gpu_resize = gpu_finish, gpu_resize
         self.alphabet = "0123456789abcdefghijklmnopqrstuvwxyz"
         self.d2a = "-" + self.alphabet
         self.alsize = len(self.d2a)
         self.a2d = {ch: i for i, ch in enumerate(self.d2a)}
-        if gpu_finish:
+        if gpu_resize:
+            self.transform = self.transform2 = None
+        elif gpu_finish:
             self.transform = resizeU8((imgW, imgH))
             self.transform2 = resizeU8((imgW // down_sample_scale, imgH // down_sample_scale))
         else:
@@ -131,8 +136,14 @@ class alignCollate_realWTLAMask(object):
 
     def __call__(self, batch):
         images_HR, images_lr, _, _, label_strs = zip(*batch)
-        images_HR = torch.stack([self.transform(im) for im in images_HR], 0)
-        images_lr = torch.stack([self.transform2(im) for im in images_lr], 0)
+        if self.gpu_resize:      # (pin=False: a loader with pin_memory pins its batches itself, and workers must not open the GPU)
+            from ..utils.resize import pack_ragged
+            rgb = lambda im: np.asarray(im if im.mode == 'RGB' else im.convert('RGB'), dtype=np.uint8)
+            images_HR = pack_ragged([rgb(im) for im in images_HR], pin=False)
+            images_lr = pack_ragged([rgb(im) for im in images_lr], pin=False)
+        else:
+            images_HR = torch.stack([self.transform(im) for im in images_HR], 0)
+            images_lr = torch.stack([self.transform2(im) for im in images_lr], 0)
         max_len = 26
         label_batches, weighted_masks, weighted_tics = [], [], []
         for word in label_strs:
@@ -163,17 +174,35 @@ class alignCollate_realWTLAMask(object):
         return images_HR, None, images_lr, None, None, label_strs, label_rebatches, torch.tensor(weighted_masks).long(), torch.tensor(weighted_tics)
 
 
-def sr_batches(loader, device=None, mask=None):
+def resize_on_gpu(pair, size, mask, device):
+    """(packed, meta) of a gpu_resize collate -> (B, 3 + mask, H, W) float on `device`, size = (H, W): one upload of the decoded
+    pixels, the ragged bicubic resize and the collate kernel."""
+    from .. import ops
+    packed, meta = pair
+    return ops.collate_u8(ops.resize_ragged_u8(packed.to(device, non_blocking=True), meta, size[0], size[1]), mask)
+
+
+def sr_batches(loader, device=None, mask=None, size=None):
     """Adapter for TextSR.train / eval / test: (images_hr, images_lr, label_vecs, label_strs) per batch.  label_vecs is None: for
     --arch tatt the reference derives them from a CRNN on the LR image (super_resolution.py:165-169), not from the dataset.
     Batches of a gpu_finish collate (uint8 pixels) are finished on `device` here (default: the current GPU); mask=None takes the
-    collate function's own setting."""
+    collate function's own setting.  Batches of a gpu_resize collate (packed pixels of the decoded images) are resized here first;
+    size = (imgH, imgW, down_sample_scale), None takes the collate function's own."""
+    col = getattr(loader, "collate_fn", None)
     if mask is None:
-        mask = bool(getattr(getattr(loader, "collate_fn", None), "mask", True))
+        mask = bool(getattr(col, "mask", True))
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
     for data in loader:
         hr, lr = data[0], data[2]
-        if hr.dtype == torch.uint8:
+        if isinstance(hr, (tuple, list)):
+            if size is None:
+                if not hasattr(col, "imgH"):
+                    raise ValueError("sr_batches: a gpu_resize batch needs size=(imgH, imgW, down_sample_scale) or a loader whose "
+                                     "collate_fn carries them")
+                size = (col.imgH, col.imgW, col.down_sample_scale)
+            H, W, scale = size
+            hr, lr = resize_on_gpu(hr, (H, W), mask, device), resize_on_gpu(lr, (H // scale, W // scale), mask, device)
+        elif hr.dtype == torch.uint8:
             hr, lr = finish_on_gpu(hr, mask, device), finish_on_gpu(lr, mask, device)
         yield hr, lr, None, list(data[5])

@@ -77,11 +77,13 @@ class TextBase(object):
         self.drop_path_rate = parse_list(self.args.drop_path_rate)
 
     # ------------------------------------------------------------------ data (base.py:85-125)
-    def _loader(self, dirs, test, shuffle, drop_last, shard=False, gpu_finish=True):
+    def _loader(self, dirs, test, shuffle, drop_last, shard=False, gpu_finish=True, gpu_resize=False):
         """shard=True (training under torch.distributed): every rank walks its own 1/world of a per-epoch permutation
         (DistributedSampler, call `self.train_sampler.set_epoch(epoch)`) with batch_size // world samples per step, so the
         GLOBAL batch stays config.TRAIN.batch_size at the configured learning rate -- nn.DataParallel's scatter of one batch
-        over the GPUs (base.py:160-162), not world x batch_size."""
+        over the GPUs (base.py:160-162), not world x batch_size.
+        gpu_resize=True (or main.py --gpu_resize; needs gpu_finish): the collate packs the decoded pixels and the bicubic resize runs on
+        the GPU too (ops.resize_ragged_u8 in sr_batches), same bytes as PIL's."""
         from ..dataset import textzoom as tz
         cfg = self.config.TRAIN
         sets = [tz.lmdbDataset_real(root=d, voc_type=cfg.voc_type, max_len=cfg.max_len, test=test) for d in dirs]
@@ -97,7 +99,8 @@ class TextBase(object):
             ds, batch_size=bs, shuffle=shuffle and sampler is None, sampler=sampler, num_workers=int(cfg.workers), pin_memory=True,
             drop_last=drop_last,
             collate_fn=tz.alignCollate_realWTLAMask(imgH=cfg.height, imgW=cfg.width, down_sample_scale=cfg.down_sample_scale, mask=self.mask,
-                                                    gpu_finish=gpu_finish))      # True: ToTensor + mask channel on the GPU by sr_batches
+                                                    gpu_finish=gpu_finish,      # True: ToTensor + mask channel on the GPU by sr_batches
+                                                    gpu_resize=gpu_finish and (gpu_resize or bool(getattr(self.args, "gpu_resize", False)))))
         # (dataset/textzoom.py; uint8 pixels in the batch); False: the reference's float (B, 3 + mask, H, W) tensors for consumers that
         # iterate the loader themselves
         if shard:

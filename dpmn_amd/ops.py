@@ -205,6 +205,85 @@ def display_triple(image_in, image_out, image_target, sel):
     return out
 
 
+_RESIZE_TABLES = {}
+RESIZE_TABLES_MAX = 4096      # device tables of the ragged resize kept per (insz, outsz, device); the oldest are dropped beyond this
+
+
+def _resize_tables(pairs, device):
+    """{(insz, outsz): the device copy of utils.resize.pil_resample_tables(insz, outsz)} for the size pairs of one call: uploaded once
+    per pair and device.  Beyond RESIZE_TABLES_MAX entries the oldest ones that this call does not use are dropped, behind a device
+    synchronise: a launch queued on any stream may still read them."""
+    from .utils.resize import pil_resample_tables
+    keys = {p: (p[0], p[1], device.type, device.index) for p in pairs}
+    for (insz, outsz), key in keys.items():
+        if key not in _RESIZE_TABLES:
+            _RESIZE_TABLES[key] = torch.from_numpy(pil_resample_tables(insz, outsz).copy()).to(device)
+    if len(_RESIZE_TABLES) > RESIZE_TABLES_MAX:
+        torch.cuda.synchronize(device)
+        used = set(keys.values())
+        for key in [k for k in _RESIZE_TABLES if k not in used][:len(_RESIZE_TABLES) - RESIZE_TABLES_MAX]:      # (insertion order: oldest first)
+            del _RESIZE_TABLES[key]
+    return {p: _RESIZE_TABLES[key] for p, key in keys.items()}
+
+
+def _resize_ragged_plan(packed, meta, H, W):
+    """Checks and per-call device data of resize_ragged_u8 -> (B, largest h, items (B, 8) int64 on the device, workspace)."""
+    import numpy as np
+    if not torch.is_tensor(packed) or not packed.is_cuda or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise _abi.DpmnError("resize_ragged_u8: a contiguous 1-D uint8 CUDA tensor is required (the uploaded pack_ragged buffer); "
+                             "there is no CPU fallback")
+    m = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta)
+    if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] == 0 or m.dtype.kind not in "iu":
+        raise _abi.DpmnError("resize_ragged_u8: meta must be a non-empty integer (B, 3) array of (byte offset, h, w)")
+    m = m.astype(np.int64)
+    from .utils.resize import MAX_SIDE
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise _abi.DpmnError("resize_ragged_u8: output size %d x %d outside 1 .. %d" % (H, W, MAX_SIDE))
+    off, hs, ws = m[:, 0], m[:, 1], m[:, 2]
+    if hs.min() < 1 or ws.min() < 1 or hs.max() > MAX_SIDE or ws.max() > MAX_SIDE or off.min() < 0 or int((off + hs * ws * 3).max()) > packed.numel():
+        raise _abi.DpmnError("resize_ragged_u8: meta names an image outside the packed buffer or with a side outside 1 .. %d" % MAX_SIDE)
+    B, dev = m.shape[0], packed.device
+    items = np.empty((B, 8), np.int64)
+    items[:, :3] = m
+    items[:, 3] = np.concatenate(([0], np.cumsum(hs[:-1]))) * (W * 3)      # the ragged intermediate: h x W x 3 bytes per image
+    tabs = _resize_tables({(int(w), W) for w in ws} | {(int(h), H) for h in hs}, dev)
+    for b in range(B):
+        th, tv = tabs[(int(ws[b]), W)], tabs[(int(hs[b]), H)]
+        items[b, 4:] = th.data_ptr(), th.shape[1] - 2, tv.data_ptr(), tv.shape[1] - 2
+    mid = torch.empty(lib.dpmn_resize_ragged_workspace_bytes(int(hs.sum()), W), dtype=torch.uint8, device=dev)
+    return B, int(hs.max()), torch.from_numpy(items).to(dev), mid
+
+
+def resize_ragged_u8(packed, meta, H, W):
+    """PIL's bicubic resize of a ragged batch (csrc/resize.hip): packed = the device copy of utils.resize.pack_ragged's 1-D uint8
+    buffer, meta = its host (B, 3) integer array of (byte offset, h, w) -> (B, H, W, 3) uint8 on the device, byte for byte
+    np.asarray(Image.fromarray(img).resize((W, H), Image.BICUBIC)) per image.  Per call one (B, 8) int64 array is uploaded; the
+    coefficient tables live on the device per size pair."""
+    H, W = int(H), int(W)
+    B, max_h, items, mid = _resize_ragged_plan(packed, meta, H, W)
+    out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=packed.device)
+    check(lib.dpmn_resize_ragged_u8(packed.data_ptr(), packed.numel(), items.data_ptr(), B, max_h, out.data_ptr(), H, W,
+                                    mid.data_ptr(), mid.numel(), stream()))
+    return out
+
+
+def quantize_sr_u8(x):
+    """save_image's quantisation of channels 0..2 of x (B, >=3, H, W) float -> (B, H, W, 3) uint8 on the device = utils.display.
+    quantize_sr, the bytes of an SR image file.  The channels are read in place (strides)."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise _abi.DpmnError("quantize_sr_u8: the image files are quantised on the GPU (got a %s tensor); there is no CPU fallback"
+                             % (x.device if torch.is_tensor(x) else type(x).__name__))
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] < 3:
+        raise _abi.DpmnError("quantize_sr_u8: float32 (B, >= 3, H, W) expected, got %s %s" % (x.dtype, tuple(x.shape)))
+    B, _, H, W = x.shape
+    out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=x.device)
+    if out.numel() == 0:
+        return out
+    x, px, bs, cs = _display_planes(x, "x")
+    check(lib.dpmn_quantize_sr_u8(px, bs, cs, out.data_ptr(), B, H, W, stream()))
+    return out
+
+
 def maxpool(x, kh, kw, scale=None, shift=None):
     """nn.MaxPool2d((kh,kw), stride (kh,kw)) over NHWC; scale/shift: the producer's BatchNorm affine + ReLU applied on load."""
     B, H, W, Cc = x.shape

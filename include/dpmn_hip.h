@@ -470,6 +470,22 @@ int dpmn_display_triple_u8(const float* image_in, long in_batch_stride, long in_
                            long out_chan_stride, const float* image_target, long tgt_batch_stride, long tgt_chan_stride, const int* sel,
                            int n, const int* tab_h, const int* tab_v, int ksize, unsigned char* out, int B, int h, int w, int H, int W,
                            dpmn_stream_t stream);
+/* PIL's fixed-point bicubic resize of a RAGGED batch (resize.hip): B RGB uint8 images of B different sizes, packed back to back (HWC)
+ * in `packed` (packed_bytes bytes), each resized -- enlarged or shrunk, per axis -- to out (B, H, W, 3) uint8, byte for byte what
+ * Image.resize((W, H), BICUBIC) writes: horizontal pass, intermediate rounded and clipped to uint8, vertical pass, every pixel
+ * clip8((2^21 + sum in * k) >> 22) in int32.  Integer arithmetic only: independent of the compute mode.
+ * items: device int64 (B, 8), per image [byte offset in packed, h, w, byte offset of its h x W x 3 intermediate in the workspace,
+ * tab_h pointer, ksize_h, tab_v pointer, ksize_v]; tab_h (W, 2 + ksize_h) / tab_v (H, 2 + ksize_v) device int32 tables of the pairs
+ * (w, W) / (h, H): per output index [first input index, taps, k_0 ..], 22 fraction bits (utils/resize.py pil_resample_tables).  Sides
+ * 1 .. 8192; an image whose numbers do not fit the buffers is not read and comes out black.  max_h: the largest h (sizes the first
+ * launch).  workspace: dpmn_resize_ragged_workspace_bytes(sum of h over the batch, W) bytes.  Two launches. */
+size_t dpmn_resize_ragged_workspace_bytes(long sum_h, int W);
+int dpmn_resize_ragged_u8(const unsigned char* packed, long packed_bytes, const long long* items, int B, int max_h, unsigned char* out, int H,
+                          int W, unsigned char* workspace, size_t workspace_bytes, dpmn_stream_t stream);
+/* save_image's quantisation (x.mul(255).add_(0.5).clamp_(0, 255).to(uint8): two separately rounded fp32 operations, truncation,
+ * NaN -> 0) of channels 0..2 of x (B, >=3, H, W), read through its batch / channel strides (in floats; planes contiguous) ->
+ * out (B, H, W, 3) uint8: the bytes of an SR image file. */
+int dpmn_quantize_sr_u8(const float* x, long batch_stride, long chan_stride, unsigned char* out, int B, int H, int W, dpmn_stream_t stream);
 
 /* rotation augmentation of the trainer (utils/util.py:37-58 torch_rotate_img; super_resolution.py:144-151, 358-365):
  * per-image affine with aspect-ratio jitter -> affine_grid (align_corners=False) -> bilinear grid_sample, zeros padding.

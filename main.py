@@ -6,7 +6,8 @@ HIP-backed modules.  `--rec crnn` loads the native CRNN recogniser (config TRAIN
 `--rec aster` the native ASTER recogniser (config TRAIN.VAL.rec_pretrained, when set), `--rec moran` the native MORAN recogniser
 (config TRAIN.VAL.moran_pretrained, when set).  Without a TextZoom LMDB directory the loop is fed synthetic (images_hr, images_lr, label_vecs)
 batches of the real shapes -- `--synthetic_steps` of them -- and the text priors come from `TextSR.synthetic_text_prior()`;
-everything between the loader and the optimizer step is the real path.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
+everything between the loader and the optimizer step is the real path.  `--demo_dir DIR --resume CKPT` super-resolves a folder of images
+(any sizes; resized on the GPU) into `--demo_out`.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
 import argparse
 import csv
@@ -77,6 +78,21 @@ def main(config, args):
     bs = args.batch_size or config.TRAIN.batch_size
     os.makedirs(config.TRAIN.ckpt_dir, exist_ok=True)
     rec = recogniser(mission, args)
+    if getattr(args, "demo_dir", None):
+        # a folder of the user's own text crops -> one <stem>_sr.png per image and demo_result.csv (TextSR.demo); the trained models
+        # are loaded as for --test
+        if not mission.resume:
+            raise SystemExit("main.py: --demo_dir needs --resume <dir> holding the trained models (as --test does)")
+        if rank != 0:
+            return
+        from dpmn_amd.dataset.folder import folder_batches
+        models, psn = mission.build_models(testing=True)
+        scale = config.TRAIN.down_sample_scale
+        out_dir = getattr(args, "demo_out", None) or os.path.join(mission.vis_dir, "demo")
+        batches = folder_batches(args.demo_dir, bs, (config.TRAIN.height // scale, config.TRAIN.width // scale), mission.mask, mission.device)
+        rows = mission.demo(models, psn, batches, out_dir, rec=rec)
+        print("%d images super-resolved into %s" % (len(rows), out_dir))
+        return
     if args.test:
         result_path = os.path.join(config.TRAIN.ckpt_dir, "test_result.csv")
         if rank == 0 and not os.path.exists(result_path):
@@ -172,6 +188,11 @@ if __name__ == '__main__':
     parser.add_argument('--synthetic_prior', action='store_true', default=False,
                         help='seeded noise text priors instead of the VisionLAN + glyph-atlas prior of --tpg visionlan')
     parser.add_argument('--synthetic_steps', type=int, default=20, help='number of synthetic batches to run (no dataset reader here)')
+    parser.add_argument('--demo_dir', type=str, default=None,
+                        help='super-resolve every image of this directory with the models of --resume (no HR images, no metrics)')
+    parser.add_argument('--demo_out', type=str, default=None, help='where --demo_dir writes (default: <vis_dir>/demo)')
+    parser.add_argument('--gpu_resize', action='store_true', default=False,
+                        help='TextZoom loaders: the bicubic resize of the decoded images runs on the GPU (same bytes as PIL)')
     args = parser.parse_args()
     config_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config', 'super_resolution.yaml')
     config = AttrDict(yaml.load(open(config_path, 'r'), Loader=yaml.Loader))
