@@ -5,8 +5,10 @@ parser instead of eval()), ``generator_init`` (base.py:127-198) and the checkpoi
 (base.py:328-373), and the CRNN recogniser of the word accuracy (``CRNN_init`` / ``parse_crnn_data``, base.py:411-425) on the
 native NativeCRNN, the ASTER recogniser (``Aster_init`` / ``parse_aster_data``, base.py:427-450) on the native NativeASTER, the MORAN
 recogniser (``MORAN_init`` / ``parse_moran_data`` / ``converter_moran``, base.py:60-61, 375-409) on the native NativeMORAN, and the
-comparison images (``tripple_display`` / ``test_display``, base.py:275-326) on one ``ops.display_triple`` launch.  Out of
-scope here: the pygame renderer.
+comparison images (``tripple_display`` / ``test_display``, base.py:275-326) on one ``ops.display_triple`` launch.  Ours: the
+training-state file that lets an interrupted run continue (``write_train_state`` / ``read_train_state``, the structure fingerprint,
+``rng_capture`` / ``rng_restore``; used by ``TextSR.train(state_path=...)``).  Out of scope here: the pygame
+renderer.
 """
 import os
 
@@ -36,6 +38,80 @@ def _val_weights(config, key, path, what):
         raise FileNotFoundError("dpmn_amd: the %s recogniser needs its weights: config TRAIN.VAL.%s (or the path "
                                 "argument) names no file (%r)" % (what, key, model_path))
     return model_path
+
+
+# --------------------------------------------------------------------------------------------------- training state (ours)
+# One file that lets an interrupted run continue bit for bit (TextSR.train(state_path=...), main.py --train_state): every model's and
+# DistillModule's state_dict, the trainer's Adam state, the loop's bookkeeping and the random streams a step draws from.  The file
+# holds tensors and plain Python values only, so it loads with torch.load(weights_only=True).
+TRAIN_STATE_VERSION = 1
+FINGERPRINT_FIELDS = ("arch", "stu_iter_b1", "stu_iter_b2", "sr_share", "patch_size", "embed_dim", "depths", "num_heads", "window_size",
+                      "window_num", "mlp_ratio", "height", "width")
+
+
+def state_fingerprint(args, config):
+    """What decides the structure of the trained models: a state is only ever loaded into a run with the same values."""
+    fp = {k: getattr(args, k) for k in ("arch", "stu_iter_b1", "stu_iter_b2", "window_num")}
+    fp["sr_share"] = bool(args.sr_share)
+    for k in ("patch_size", "embed_dim", "depths", "num_heads", "window_size", "mlp_ratio"):
+        fp[k] = parse_list(getattr(args, k))
+    fp["height"], fp["width"] = int(config.TRAIN.height), int(config.TRAIN.width)
+    return fp
+
+
+def check_fingerprint(saved, current, path=""):
+    for k in FINGERPRINT_FIELDS:
+        if saved.get(k) != current.get(k):
+            raise ValueError("dpmn_amd: training state %s was written by a run with %s = %r, this run has %s = %r"
+                             % (path, k, saved.get(k), k, current.get(k)))
+
+
+def write_train_state(path, obj):
+    """Atomic: the bytes go to PATH.tmp in the same directory, are flushed and fsync'ed, and only then take PATH's name -- a save
+    that dies part-way leaves the previous file in place."""
+    tmp = path + ".tmp"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(tmp, "wb") as f:
+        torch.save(obj, f)
+        f.flush()
+        os.fsync(f.fileno())
+    os.replace(tmp, path)
+
+
+def read_train_state(path, fingerprint=None):
+    """The state at `path` (never PATH.tmp: a leftover of a save that died), on the CPU.  The format version and, when given, the
+    structure fingerprint are checked before the caller loads anything."""
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(state, dict) or state.get("version") != TRAIN_STATE_VERSION:
+        raise ValueError("dpmn_amd: %s is not a training state of format version %d (found %r)"
+                         % (path, TRAIN_STATE_VERSION, state.get("version") if isinstance(state, dict) else type(state).__name__))
+    if fingerprint is not None:
+        check_fingerprint(state["fingerprint"], fingerprint, path)
+    return state
+
+
+def rng_capture(device=None):
+    """The random streams a training step draws from: torch's CPU generator (train/pgrm_train.py draw_seeds: the Dropout / DropPath
+    seeds), numpy's global state (rotate_pair), Python's random, torch's device generator."""
+    import random
+    import numpy as np
+    kind, keys, pos, has_gauss, gauss = np.random.get_state()
+    ver, internal, gauss_next = random.getstate()
+    return {"torch": torch.get_rng_state(), "numpy": (kind, torch.from_numpy(keys.astype("int64")), int(pos), int(has_gauss), float(gauss)),
+            "python": (ver, tuple(internal), gauss_next),
+            "device": torch.cuda.get_rng_state(device) if device is not None and device.type == "cuda" else None}
+
+
+def rng_restore(state, device=None):
+    import random
+    import numpy as np
+    torch.set_rng_state(state["torch"])
+    kind, keys, pos, has_gauss, gauss = state["numpy"]
+    np.random.set_state((kind, keys.numpy().astype("uint32"), pos, has_gauss, gauss))
+    ver, internal, gauss_next = state["python"]
+    random.setstate((ver, tuple(internal), gauss_next))
+    if state.get("device") is not None and device is not None and device.type == "cuda":
+        torch.cuda.set_rng_state(state["device"], device)
 
 
 class TextBase(object):

@@ -587,7 +587,7 @@ class TextSR(base.TextBase):
         run.graph = graph
         return run
 
-    def train(self, loader=None, steps=None, val_loader=None, rec=None, epochs=None, sampler=None, display=False):
+    def train(self, loader=None, steps=None, val_loader=None, rec=None, epochs=None, sampler=None, display=False, state_path=None):
         """Training loop (super_resolution.py:125-337) over (images_hr, images_lr, label_vecs) batches (synthetic ones, or the
         TextZoom reader of dataset/textzoom.py through main.py).
         loader: a callable `loader(epoch) -> iterable` (a fresh pass per epoch), a re-iterable (list, DataLoader-like: walked
@@ -598,7 +598,12 @@ class TextSR(base.TextBase):
         computes one, else PSNR), checkpoint.pth every saveInterval and at the end, epoch written to checkpoints and log.csv.
         Rank 0 writes the files; under ZeRO-1 every save waits for the step's parameter all-gather first (trainer.sync_params:
         the gather runs asynchronously on RCCL's stream, a state_dict clone before it lands would tear the checkpoint).
-        display=True: every evaluation pass writes its comparison images (eval(display=True), index = epoch; rank 0 only)."""
+        display=True: every evaluation pass writes its comparison images (eval(display=True), index = epoch; rank 0 only).
+        state_path (main.py --train_state): ONE file that lets an interrupted run continue bit for bit (interfaces/base.py "training
+        state").  If it exists the run continues from it -- weights, BatchNorm statistics, Adam state, bookkeeping, the
+        random streams, the position inside the epoch -- else the run starts fresh; rank 0 rewrites it (atomically) after every
+        iteration that saved a checkpoint and at the end of the run.  `it` goes on counting and `steps` stays a total.  Without it
+        nothing is read or written beyond the files above."""
         dist = torch.distributed
         world = dist.get_world_size() if dist.is_initialized() else 1
         rank = dist.get_rank() if dist.is_initialized() else 0
@@ -632,6 +637,8 @@ class TextSR(base.TextBase):
             n_epochs = epochs if epochs is not None else int(getattr(cfg, "epochs", 1) or 1)
 
         def save(epoch, it, is_best, metric="sum"):
+            nonlocal dirty
+            dirty = True
             if rank == 0:
                 self.save_checkpoint(models, epoch, it, dict(best_hist, score=best), best_info, is_best, converge, None, metric=metric, trainer=trainer)
 
@@ -642,9 +649,70 @@ class TextSR(base.TextBase):
                     csv.writer(out).writerow(row)
 
         it, epoch, saved_at = 0, 0, -1
-        for epoch in range(n_epochs):
+        first_epoch, done, state, rng_epoch, dirty, loss, wrote_at = 0, 0, None, None, False, None, -1
+        if state_path is not None and os.path.isfile(state_path):
+            # continue: fingerprint first, then weights + BatchNorm statistics (written through the state_dicts: views of the trainer's
+            # parameter arena), Adam state, bookkeeping; the random streams follow in the epoch loop
+            state = base.read_train_state(state_path, base.state_fingerprint(self.args, self.config))
+            for m_, sd in zip(models + distill, state["models"] + state["distill"]):
+                m_.load_state_dict(sd)
+            trainer.load_state_dict(state["trainer"])
+            lp = state["loop"]
+            it, first_epoch, done, saved_at = lp["it"], lp["epoch"], lp["done"], lp["saved_at"]
+            best, best_hist, best_info, converge = lp["best"], dict(lp["best_hist"]), lp["best_info"], list(lp["converge"])
+            epoch, wrote_at = first_epoch, it
+            if rank == 0 and lp["log_rows"] is not None and os.path.isfile(log_path):
+                with open(log_path, newline="") as f:      # rows of evaluations after the state was written: they will be written again
+                    rows = f.readlines()
+                if len(rows) > lp["log_rows"]:
+                    with open(log_path, "w", newline="") as f:
+                        f.writelines(rows[:lp["log_rows"]])
+            if rank == 0:
+                print("continuing from %s: epoch %d, iter %d" % (state_path, first_epoch, it))
+
+        def restore_rng(which):
+            per_rank = state["rng"]
+            if rank < len(per_rank):
+                base.rng_restore(per_rank[rank][which], self.device)
+            elif which == "now":      # (a larger world than the one that wrote the state: no exact continuation is promised)
+                from ..utils.util import set_seed
+                seed = (self.rank_seed if getattr(self, "rank_seed", None) is not None else rank) + 7919 * it
+                print("rank %d: no random-number state in %s (written by %d ranks), re-seeded with %d" % (rank, state_path, len(per_rank), seed))
+                set_seed(seed)
+
+        def write_state():
+            """Collective: the trainer's ZeRO-1 shards and every rank's random-number state are gathered; rank 0 writes."""
+            tsd = trainer.state_dict()
+            rng = {"epoch_start": rng_epoch, "now": base.rng_capture(self.device)}
+            per_rank = [rng]
+            if world > 1:
+                per_rank = [None] * world
+                dist.all_gather_object(per_rank, rng)
+            if rank != 0:
+                return
+            log_rows = None
+            if os.path.isfile(log_path):
+                with open(log_path, newline="") as f:
+                    log_rows = len(f.readlines())
+            cpu_sd = lambda m_: {k: v.detach().cpu() for k, v in m_.state_dict().items()}
+            base.write_train_state(state_path, {
+                "version": base.TRAIN_STATE_VERSION, "fingerprint": base.state_fingerprint(self.args, self.config), "world": world,
+                "models": [cpu_sd(m_) for m_ in models], "distill": [cpu_sd(m_) for m_ in distill], "trainer": tsd, "rng": per_rank,
+                "loop": dict(loop_state(), log_rows=log_rows)})
+
+        def loop_state():
+            return {"epoch": epoch, "it": it, "done": done, "saved_at": saved_at, "best": best, "best_hist": dict(best_hist),
+                    "best_info": best_info, "converge": list(converge)}
+
+        for epoch in range(first_epoch, n_epochs):
             if sampler is not None and hasattr(sampler, "set_epoch"):
                 sampler.set_epoch(epoch)
+            resumed = state is not None and epoch == first_epoch
+            if resumed:
+                restore_rng("epoch_start")      # a shuffling loader draws its permutation when its iterator is made: the same one again
+            if state_path is not None:
+                rng_epoch = base.rng_capture(self.device)
+            done = 0
             def on_device(data):
                 hr, lr = data[0].to(self.device), data[1].to(self.device)
                 lv = data[2].to(self.device) if len(data) > 2 and data[2] is not None else None
@@ -652,6 +720,12 @@ class TextSR(base.TextBase):
                     lv = self.label_vecs_from_crnn(lr)
                 return hr, lr, lv
             batches = iter(passes(epoch))
+            if resumed:
+                while done < lp["done"] and next(batches, None) is not None:      # the batches this epoch already trained on
+                    done += 1
+                restore_rng("now")
+                if steps is not None and it >= steps:
+                    break
             nxt = next(batches, None)
             nxt = on_device(nxt) if nxt is not None else None
             handle = None
@@ -670,6 +744,7 @@ class TextSR(base.TextBase):
                     nxt = next(batches, None)
                     nxt = on_device(nxt) if nxt is not None else None
                 it += 1
+                done += 1
                 if it % cfg.displayInterval == 0 and rank == 0:
                     print('Epoch: [%d] iter %d | Loss: %f' % (epoch, it, float(loss)))
                 if val_sets and it % val_int == 0:
@@ -703,14 +778,30 @@ class TextSR(base.TextBase):
                 if it % cfg.saveInterval == 0:
                     save(epoch, it, False)
                     saved_at = it
+                if (state_path is not None and (it % cfg.saveInterval == 0 or (val_sets and it % val_int == 0))
+                        and not (steps is not None and it >= steps)):      # (the last requested step: the write at the end of the run follows)
+                    # once per iteration, after ALL of its bookkeeping: the file never holds half an evaluation.  Whether a "best"
+                    # save happened is rank 0's call (BatchNorm statistics, hence scores, are per rank) and the write is a collective
+                    flag = [dirty]
+                    if world > 1:
+                        dist.broadcast_object_list(flag, src=0)
+                    if flag[0]:
+                        write_state()
+                        wrote_at = it
+                    dirty = False
                 if steps is not None and it >= steps:
                     break
             if steps is not None and it >= steps:
                 break
-        if saved_at != it:
+        final_save = saved_at != it
+        if final_save:
             save(epoch, it, False)
+            saved_at = it
+        if state_path is not None and rng_epoch is not None and (final_save or wrote_at != it):      # (rng_epoch None: no epoch was entered)
+            write_state()
         trainer.sync_params()
         self.trainer = trainer
+        self.last_loss, self.loop_state = loss, loop_state()      # (the last step's loss, None if no step ran; the bookkeeping as a state holds it)
         return models, distill
 
     def label_vecs_from_crnn(self, images_lr):

@@ -596,6 +596,81 @@ class Trainer:
             g.v.copy_(v)
         self.invalidate_packs()
 
+    # ------------------------------------------------------------------ training state (continue an interrupted run)
+    def _moment_layout(self):
+        """Per model index, in that model's parameters() order: [(group index, offset in the group's range, numel)].  The arenas hold the
+        models in backward order, a segmented model's parameters in segment order, every view padded to ALIGN and every group to the
+        world size; none of that shows in a saved state."""
+        where = {}
+        for gi, g in enumerate(self.groups):
+            for bkt, off in zip(g.buckets, g.offsets):
+                for prm, po, k in bkt.param_slices():
+                    where[id(prm)] = (gi, off + po, k)
+        return [[where[id(p)] for p in b.module.parameters()] for b in self.buckets]
+
+    def _join_updates(self):
+        """Nothing may still be writing parameters or moments: the ZeRO-1 parameter all-gathers and the early-optimizer stream."""
+        self.sync_params()
+        if self.opt_stream is not None:
+            torch.cuda.current_stream(self.flat_p.device).wait_stream(self.opt_stream)
+
+    def state_dict(self):
+        """Adam's state in a layout that depends on neither world size nor group plan nor padding: {'t': step count, 'm' / 'v': per model
+        index ONE unpadded fp32 CPU vector, the exp_avg / exp_avg_sq of that model's parameters() concatenated in order}.
+        Under ZeRO-1 this is a COLLECTIVE on the trainer's process group (every rank calls it): each rank owns 1/world of every group's
+        moments; the shards are assembled by an integer all-reduce(SUM) of the bit patterns into a zero-filled vector (exact, and the
+        one collective both gloo and RCCL offer for device tensors).  The vectors are left on rank 0; other ranks get 'm' = 'v' = None."""
+        self._join_updates()
+        full = []
+        for g in self.groups:
+            if not g.zero1:
+                full.append((g.m, g.v))
+                continue
+            mv = torch.zeros(2, g.n, device=g.m.device)
+            mv[0, g.lo:g.lo + g.shard_n] = g.m
+            mv[1, g.lo:g.lo + g.shard_n] = g.v
+            dist.all_reduce(mv.view(torch.int32), op=dist.ReduceOp.SUM, group=g.pg)
+            full.append((mv[0], mv[1]))
+        if self.zero1 and dist.get_rank(self.groups[0].pg) != 0:
+            return dict(t=self.t, m=None, v=None)
+        out = dict(t=self.t, m=[], v=[])
+        for slices in self._moment_layout():
+            for key, which in (("m", 0), ("v", 1)):
+                out[key].append(torch.cat([full[gi][which][o:o + k] for gi, o, k in slices]).cpu())
+        return out
+
+    def load_state_dict(self, sd):
+        """Inverse of state_dict() for ANY world size / group plan: every rank reads the world-independent vectors and keeps the part of
+        each group it owns (padding stays zero, as a run leaves it: padded gradients are zero).  Parameters are not part of this state;
+        they are restored through the models' state_dicts, which are views of the parameter arena."""
+        layout = self._moment_layout()
+        for key in ("m", "v"):
+            if sd.get(key) is None or len(sd[key]) != len(layout):
+                raise ValueError("dpmn_amd Trainer.load_state_dict: the state holds %s '%s' vectors, this trainer has %d models"
+                                 % ("no" if sd.get(key) is None else len(sd[key]), key, len(layout)))
+            for i, slices in enumerate(layout):
+                want = sum(k for _, _, k in slices)
+                if sd[key][i].numel() != want:
+                    raise ValueError("dpmn_amd Trainer.load_state_dict: model %d: '%s' has %d elements, the model's parameters have %d"
+                                     % (i, key, sd[key][i].numel(), want))
+        self._join_updates()
+        dev = self.flat_p.device
+        vec = {key: [t_.to(dev, torch.float32).reshape(-1) for t_ in sd[key]] for key in ("m", "v")}
+        starts = [[sum(k for _, _, k in slices[:j]) for j in range(len(slices))] for slices in layout]
+        for gi, g in enumerate(self.groups):
+            for key, shard in (("m", g.m), ("v", g.v)):
+                full = torch.zeros(g.n, device=dev)
+                for i, slices in enumerate(layout):
+                    for (gj, o, k), a in zip(slices, starts[i]):
+                        if gj == gi:
+                            full[o:o + k] = vec[key][i][a:a + k]
+                shard.copy_(full[g.lo:g.lo + g.shard_n])
+        self.t = int(sd["t"])
+        if self.t_dev is not None:
+            self.t_dev.fill_(float(self.t))
+        self.invalidate_packs()
+        self.pack_cache.fresh = -1      # the registered weight packs are re-made at their next request, whatever step they were made in
+
     def arm_early_step(self):
         """The caller promises that Trainer.step() follows the backward pass it is about to start (TextSR.train_step): groups may
         then be stepped as soon as their gradients are complete (DPMN_EARLY_OPT), and a module's backward may return while its leaf

@@ -7,7 +7,8 @@ HIP-backed modules.  `--rec crnn` loads the native CRNN recogniser (config TRAIN
 (config TRAIN.VAL.moran_pretrained, when set).  Without a TextZoom LMDB directory the loop is fed synthetic (images_hr, images_lr, label_vecs)
 batches of the real shapes -- `--synthetic_steps` of them -- and the text priors come from `TextSR.synthetic_text_prior()`;
 everything between the loader and the optimizer step is the real path.  `--demo_dir DIR --resume CKPT` super-resolves a folder of images
-(any sizes; resized on the GPU) into `--demo_out`.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
+(any sizes; resized on the GPU) into `--demo_out`.  `--train_state PATH` makes a training run continuable: the same command line starts the
+run or, when PATH exists, continues it bit for bit.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
 import argparse
 import csv
@@ -130,10 +131,11 @@ def main(config, args):
                           for name, vdl in zip(subset_names(val_dirs), val_dls)} if val_dls else None
             mission.train(lambda epoch: sr_batches(dl, mission.device, mission.mask), epochs=config.TRAIN.epochs,
                           sampler=getattr(mission, "train_sampler", None), val_loader=val_loader, rec=rec,
-                          display=args.vis_dir is not None)
+                          display=args.vis_dir is not None, state_path=getattr(args, "train_state", None))
         else:
-            mission.train(synthetic_loader(bs, args.synthetic_steps, 2000 + rank), steps=args.synthetic_steps, rec=rec,
-                          display=args.vis_dir is not None)
+            # (a callable, not a one-shot generator: a run continued from --train_state walks the epoch again up to where it stopped)
+            mission.train(lambda epoch: synthetic_loader(bs, args.synthetic_steps, 2000 + rank), steps=args.synthetic_steps, rec=rec,
+                          display=args.vis_dir is not None, epochs=1, state_path=getattr(args, "train_state", None))
 
 
 def subset_names(val_dirs):
@@ -193,6 +195,9 @@ if __name__ == '__main__':
     parser.add_argument('--demo_out', type=str, default=None, help='where --demo_dir writes (default: <vis_dir>/demo)')
     parser.add_argument('--gpu_resize', action='store_true', default=False,
                         help='TextZoom loaders: the bicubic resize of the decoded images runs on the GPU (same bytes as PIL)')
+    parser.add_argument('--train_state', type=str, default=None,
+                        help='one file that holds everything needed to continue the training run exactly: if it exists the run '
+                             'continues from it, otherwise it starts fresh; rewritten at every checkpoint save and at the end')
     args = parser.parse_args()
     config_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config', 'super_resolution.yaml')
     config = AttrDict(yaml.load(open(config_path, 'r'), Loader=yaml.Loader))
