@@ -2,10 +2,15 @@
 order, decoded with PIL, converted to RGB, packed as a ragged batch (utils/resize.py pack_ragged), uploaded once and resized to the
 model's LR size on the GPU (ops.resize_ragged_u8, byte for byte PIL's bicubic resize), then finished like a TextZoom batch
 (ops.collate_u8: ToTensor and the mask channel).  The host half (`host_batches`) needs no GPU.
+`FolderHR`: the same kind of directory as the HR images of a TRAINING set (main.py --train_hr_dir): the LR images are synthesised on
+the GPU (dataset/textzoom.py, alignCollate_realWTLAMask(degrade=True) and sr_batches), so training needs neither LMDB nor LR images.
 """
 import os
 
 import numpy as np
+import torch
+
+LABELS_FILE = "labels.txt"
 
 
 def host_batches(dir_, batch_size):
@@ -49,3 +54,50 @@ def folder_batches(dir_, batch_size, lr_size, mask, device):
     h, w = lr_size
     for names, packed, meta in host_batches(dir_, batch_size):
         yield names, ops.collate_u8(ops.resize_ragged_u8(packed.to(device, non_blocking=True), meta, h, w), mask)
+
+
+class FolderHR(torch.utils.data.Dataset):
+    """The images of a directory as the HR images of a training set: items (img_HR, img_HR, None, None, label) like
+    textzoom.lmdbDataset_real(manmade_degrade=True) -- the HR image stands in the LR position.  Regular files of `dir_` in sorted name
+    order, as host_batches walks them; a file PIL cannot open, or whose sides pack_ragged rejects, is skipped with one printed line
+    (checked once, here, from the file's header; an image that then fails to decode raises in __getitem__).  Labels: an optional
+    `labels.txt` in the directory with lines `file name<TAB>word` (not an image itself); a file without a line, or a directory
+    without the file, gets " " (what the LMDB reader gives a missing label).  A directory without usable images raises."""
+
+    def __init__(self, dir_, voc_type='upper'):
+        super().__init__()
+        from PIL import Image
+        from ..utils.resize import MAX_SIDE
+        self.dir, self.voc_type = dir_, voc_type
+        files = sorted(f for f in os.listdir(dir_) if os.path.isfile(os.path.join(dir_, f)) and f != LABELS_FILE)
+        self.labels = {}
+        if os.path.isfile(os.path.join(dir_, LABELS_FILE)):
+            with open(os.path.join(dir_, LABELS_FILE), encoding="utf-8") as fh:
+                for line in fh:
+                    name, tab, word = line.rstrip("\r\n").partition("\t")
+                    if tab:
+                        self.labels[name] = word
+        self.files = []
+        for f in files:
+            try:
+                with Image.open(os.path.join(dir_, f)) as im:
+                    w, h = im.size
+                if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+                    raise ValueError("%d x %d, sides outside 1 .. %d" % (h, w, MAX_SIDE))
+            except Exception as e:      # whatever a decoder raises on a file that is not its format, or is damaged
+                print("folder: skipping %s (%s: %s)" % (f, type(e).__name__, e))
+                continue
+            self.files.append(f)
+        if not self.files:
+            raise FileNotFoundError("folder: %s holds no usable images" % dir_)
+
+    def __len__(self):
+        return len(self.files)
+
+    def __getitem__(self, index):
+        from PIL import Image
+        from ..utils.util import str_filt
+        f = self.files[index]
+        with Image.open(os.path.join(self.dir, f)) as im:
+            img = im.convert('RGB')
+        return img, img, None, None, str_filt(self.labels.get(f, " "), self.voc_type)

@@ -8,7 +8,9 @@ interfaces/base.py:85-125 wires into the training / evaluation loaders, restrict
 Host code by nature (JPEG / PNG decode and PIL resampling are what the reference does too); PIL is the same library the
 reference calls, so `resizeNormalize` is not a restatement of an algorithm but the same calls.  Left out, with the positions
 kept in the collated tuple: the YUV copies (cv2.cvtColor, read by nothing on the SR path), imgaug augmenters (constructed but
-never applied by these classes), cutblur / manmade degradation (off in interfaces/base.py).  `lmdb` itself is imported lazily:
+never applied by these classes).  Manmade degradation and cutblur (dataset.py:422-489, 622-637; main.py --manmade_degrade / --cutblur)
+do not run per image on the host here: the dataset hands out the HR image in the LR position, the collate function packs the HR pixels
+once and `sr_batches` synthesises the LR batch on the GPU (ops.degrade_ragged_u8, then the ragged resize).  `lmdb` itself is imported lazily:
 it is not installed in the build image, so the reader is exercised in tests/ through an injected environment object with the
 same `begin().get(key)` protocol, over images encoded the way TextZoom stores them.
 """
@@ -41,8 +43,9 @@ class lmdbDataset_real(torch.utils.data.Dataset):
     def __init__(self, root=None, voc_type='upper', max_len=100, test=False, cutblur=False, manmade_degrade=False, rotate=None,
                  env=None):
         super().__init__()
-        if cutblur or manmade_degrade:
-            raise NotImplementedError("dpmn_amd lmdbDataset_real: cutblur / manmade_degrade are off on the SR path (base.py:85-125)")
+        if cutblur and not manmade_degrade:
+            raise ValueError("dpmn_amd lmdbDataset_real: cutblur needs manmade_degrade (the reference's cutblur mixes LR and HR pixels "
+                             "column by column, which needs equal native sizes; paired TextZoom crops do not have them)")
         if env is None:
             try:
                 import lmdb
@@ -54,6 +57,8 @@ class lmdbDataset_real(torch.utils.data.Dataset):
         with self.env.begin(write=False) as txn:
             self.nSamples = int(txn.get(b'num-samples'))
         self.voc_type, self.max_len, self.test = voc_type, max_len, test
+        # manmade_degrade: image_lr-* is not read, the HR image stands in the LR position (degraded on the GPU by sr_batches)
+        self.manmade_degrade, self.cb_flag = bool(manmade_degrade), bool(cutblur)
 
     def __len__(self):
         return self.nSamples
@@ -64,7 +69,7 @@ class lmdbDataset_real(torch.utils.data.Dataset):
         with self.env.begin(write=False) as txn:
             try:
                 img_HR = buf2PIL(txn, b'image_hr-%09d' % index, 'RGB')
-                img_lr = buf2PIL(txn, b'image_lr-%09d' % index, 'RGB')
+                img_lr = img_HR if self.manmade_degrade else buf2PIL(txn, b'image_lr-%09d' % index, 'RGB')
                 word = txn.get(b'label-%09d' % index)
                 word = " " if word is None else str(word.decode())
             except IOError:
@@ -115,12 +120,21 @@ class alignCollate_realWTLAMask(object):
     and `sr_batches(loader, device)` finishes them on the GPU -- same values, bit for bit (tests/test_gpu_dataset.py).
     gpu_resize=True (ours, opt-in): no PIL resize here either; positions 0 and 2 hold the utils.resize.pack_ragged pair (packed uint8
     pixels of the decoded images, (B, 3) meta) and `sr_batches` resizes them on the GPU (ops.resize_ragged_u8, the same bytes as PIL's
-    bicubic resize; tests/test_gpu_resize.py) before it finishes them."""
+    bicubic resize; tests/test_gpu_resize.py) before it finishes them.
+    degrade=True (ours, needs gpu_resize): the LR images are synthesised from the HR images -- the HR pixels are packed ONCE, position
+    2 carries the same pair as position 0 and `sr_batches` degrades them on the GPU (ops.degrade_ragged_u8; cutblur=True: with the
+    reference's cutblur).  The random draws happen in sr_batches, in the main process, not in the loader's workers."""
 
     def __init__(self, imgH=64, imgW=256, down_sample_scale=4, keep_ratio=False, min_ratio=1, mask=False, alphabet=53, train=True,
-                 y_domain=False, gpu_finish=False, gpu_resize=False):
+                 y_domain=False, gpu_finish=False, gpu_resize=False, degrade=False, cutblur=False):
+        if degrade and not gpu_resize:
+            raise ValueError("alignCollate_realWTLAMask: degrade=True needs gpu_resize=True (the LR images are made on the GPU from the "
+                             "packed HR pixels)")
+        if cutblur and not degrade:
+            raise ValueError("alignCollate_realWTLAMask: cutblur=True needs degrade=True (cutblur replaces columns of the LR image by the "
+                             "HR image's, which needs equal native sizes; paired TextZoom crops do not have them)")
         self.imgH, self.imgW, self.down_sample_scale, self.mask = imgH, imgW, down_sample_scale, mask
-        self.gpu_finish, self.gpu_resize = gpu_finish, gpu_resize
+        self.gpu_finish, self.gpu_resize, self.degrade, self.cutblur = gpu_finish, gpu_resize, bool(degrade), bool(cutblur)
         self.alphabet = "0123456789abcdefghijklmnopqrstuvwxyz"
         self.d2a = "-" + self.alphabet
         self.alsize = len(self.d2a)
@@ -140,7 +154,7 @@ class alignCollate_realWTLAMask(object):
             from ..utils.resize import pack_ragged
             rgb = lambda im: np.asarray(im if im.mode == 'RGB' else im.convert('RGB'), dtype=np.uint8)
             images_HR = pack_ragged([rgb(im) for im in images_HR], pin=False)
-            images_lr = pack_ragged([rgb(im) for im in images_lr], pin=False)
+            images_lr = images_HR if self.degrade else pack_ragged([rgb(im) for im in images_lr], pin=False)
         else:
             images_HR = torch.stack([self.transform(im) for im in images_HR], 0)
             images_lr = torch.stack([self.transform2(im) for im in images_lr], 0)
@@ -182,18 +196,45 @@ def resize_on_gpu(pair, size, mask, device):
     return ops.collate_u8(ops.resize_ragged_u8(packed.to(device, non_blocking=True), meta, size[0], size[1]), mask)
 
 
+def degrade_on_gpu(pair, size, scale, mask, device, cutblur=False, rng=None):
+    """(packed, meta) of a degrade collate (the HR pixels) -> (images_hr (B, 3 + mask, H, W), images_lr (B, 3 + mask, H / scale,
+    W / scale)) float on `device`, size = (H, W): one upload, the degradation of the ragged batch at the images' own sizes
+    (ops.degrade_ragged_u8: the parameters of utils.degrade.draw_params and one 63-bit noise seed, both drawn from `rng`, Python's
+    `random` by default), the two ragged resizes and the collate kernel."""
+    import random
+    from .. import ops
+    from ..utils.degrade import draw_params
+    rng = random if rng is None else rng
+    packed, meta = pair
+    params = draw_params(meta.shape[0], cutblur=cutblur, hr_widths=[int(w) for w in meta[:, 2]], rng=rng)
+    seed = rng.getrandbits(63)
+    packed = packed.to(device, non_blocking=True)
+    low = ops.degrade_ragged_u8(packed, meta, params, seed=seed)
+    H, W = size
+    return (ops.collate_u8(ops.resize_ragged_u8(packed, meta, H, W), mask),
+            ops.collate_u8(ops.resize_ragged_u8(low, meta, H // scale, W // scale), mask))
+
+
 def sr_batches(loader, device=None, mask=None, size=None):
     """Adapter for TextSR.train / eval / test: (images_hr, images_lr, label_vecs, label_strs) per batch.  label_vecs is None: for
     --arch tatt the reference derives them from a CRNN on the LR image (super_resolution.py:165-169), not from the dataset.
     Batches of a gpu_finish collate (uint8 pixels) are finished on `device` here (default: the current GPU); mask=None takes the
     collate function's own setting.  Batches of a gpu_resize collate (packed pixels of the decoded images) are resized here first;
-    size = (imgH, imgW, down_sample_scale), None takes the collate function's own."""
+    size = (imgH, imgW, down_sample_scale), None takes the collate function's own.  Batches of a degrade collate (the HR pixels in both
+    positions) get their LR images here (degrade_on_gpu).  The randomness of a pass comes from ONE 63-bit draw from Python's `random`
+    when the pass starts, in the main process; batch j then draws from random.Random(that key + j).  TextSR.train fetches a batch
+    before it writes the training state of the step before it, so per-batch draws from the global stream would be repeated after a
+    continuation; keyed by (pass, batch) a continued run (--train_state restores the stream the key came from) sees exactly the LR
+    images the uninterrupted run saw."""
+    import random
     col = getattr(loader, "collate_fn", None)
     if mask is None:
         mask = bool(getattr(col, "mask", True))
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-    for data in loader:
+    degrade = bool(getattr(col, "degrade", False))
+    pass_key = random.getrandbits(63) if degrade else None
+    for j, data in enumerate(loader):
         hr, lr = data[0], data[2]
         if isinstance(hr, (tuple, list)):
             if size is None:
@@ -202,7 +243,10 @@ def sr_batches(loader, device=None, mask=None, size=None):
                                      "collate_fn carries them")
                 size = (col.imgH, col.imgW, col.down_sample_scale)
             H, W, scale = size
-            hr, lr = resize_on_gpu(hr, (H, W), mask, device), resize_on_gpu(lr, (H // scale, W // scale), mask, device)
+            if degrade:
+                hr, lr = degrade_on_gpu(hr, (H, W), scale, mask, device, cutblur=col.cutblur, rng=random.Random(pass_key + j))
+            else:
+                hr, lr = resize_on_gpu(hr, (H, W), mask, device), resize_on_gpu(lr, (H // scale, W // scale), mask, device)
         elif hr.dtype == torch.uint8:
             hr, lr = finish_on_gpu(hr, mask, device), finish_on_gpu(lr, mask, device)
         yield hr, lr, None, list(data[5])

@@ -46,7 +46,8 @@ def _val_weights(config, key, path, what):
 # holds tensors and plain Python values only, so it loads with torch.load(weights_only=True).
 TRAIN_STATE_VERSION = 1
 FINGERPRINT_FIELDS = ("arch", "stu_iter_b1", "stu_iter_b2", "sr_share", "patch_size", "embed_dim", "depths", "num_heads", "window_size",
-                      "window_num", "mlp_ratio", "height", "width")
+                      "window_num", "mlp_ratio", "height", "width", "manmade_degrade", "cutblur", "train_hr_dir")
+DATA_FIELDS = ("manmade_degrade", "cutblur", "train_hr_dir")      # booleans; a state written before they existed has them off
 
 
 def state_fingerprint(args, config):
@@ -56,12 +57,20 @@ def state_fingerprint(args, config):
     for k in ("patch_size", "embed_dim", "depths", "num_heads", "window_size", "mlp_ratio"):
         fp[k] = parse_list(getattr(args, k))
     fp["height"], fp["width"] = int(config.TRAIN.height), int(config.TRAIN.width)
+    # where the LR images come from: a run with synthesised LR images only continues a run of the same kind
+    fp["manmade_degrade"], fp["cutblur"] = degrade_flags(args)
+    fp["train_hr_dir"] = bool(getattr(args, "train_hr_dir", None))
     return fp
+
+
+def degrade_flags(args):
+    """(manmade_degrade, cutblur) of the training loader: --train_hr_dir implies --manmade_degrade."""
+    return bool(getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None)), bool(getattr(args, "cutblur", False))
 
 
 def check_fingerprint(saved, current, path=""):
     for k in FINGERPRINT_FIELDS:
-        if saved.get(k) != current.get(k):
+        if (bool(saved.get(k)) != bool(current.get(k))) if k in DATA_FIELDS else (saved.get(k) != current.get(k)):
             raise ValueError("dpmn_amd: training state %s was written by a run with %s = %r, this run has %s = %r"
                              % (path, k, saved.get(k), k, current.get(k)))
 
@@ -153,16 +162,29 @@ class TextBase(object):
         self.drop_path_rate = parse_list(self.args.drop_path_rate)
 
     # ------------------------------------------------------------------ data (base.py:85-125)
-    def _loader(self, dirs, test, shuffle, drop_last, shard=False, gpu_finish=True, gpu_resize=False):
+    def _loader(self, dirs, test, shuffle, drop_last, shard=False, gpu_finish=True, gpu_resize=False, degrade=False, cutblur=False,
+                hr_dir=None):
         """shard=True (training under torch.distributed): every rank walks its own 1/world of a per-epoch permutation
         (DistributedSampler, call `self.train_sampler.set_epoch(epoch)`) with batch_size // world samples per step, so the
         GLOBAL batch stays config.TRAIN.batch_size at the configured learning rate -- nn.DataParallel's scatter of one batch
         over the GPUs (base.py:160-162), not world x batch_size.
         gpu_resize=True (or main.py --gpu_resize; needs gpu_finish): the collate packs the decoded pixels and the bicubic resize runs on
-        the GPU too (ops.resize_ragged_u8 in sr_batches), same bytes as PIL's."""
+        the GPU too (ops.resize_ragged_u8 in sr_batches), same bytes as PIL's.
+        degrade=True (get_train_data with main.py --manmade_degrade; never for validation or test data): the LR images are synthesised
+        from the HR images on the GPU (ops.degrade_ragged_u8 in sr_batches; cutblur=True: with cutblur), which needs gpu_finish and
+        turns gpu_resize on.  hr_dir (--train_hr_dir): a folder of HR images instead of the LMDBs of `dirs` (dataset/folder.py
+        FolderHR), always degraded."""
         from ..dataset import textzoom as tz
         cfg = self.config.TRAIN
-        sets = [tz.lmdbDataset_real(root=d, voc_type=cfg.voc_type, max_len=cfg.max_len, test=test) for d in dirs]
+        degrade = bool(degrade or hr_dir)
+        if degrade and not gpu_finish:
+            raise ValueError("dpmn_amd: manmade_degrade makes the LR images on the GPU: it needs gpu_finish=True")
+        if hr_dir:
+            from ..dataset.folder import FolderHR
+            sets = [FolderHR(hr_dir, voc_type=cfg.voc_type)]
+        else:
+            sets = [tz.lmdbDataset_real(root=d, voc_type=cfg.voc_type, max_len=cfg.max_len, test=test, cutblur=cutblur,
+                                        manmade_degrade=degrade) for d in dirs]
         ds = torch.utils.data.ConcatDataset(sets)
         dist = torch.distributed
         world = dist.get_world_size() if (shard and dist.is_initialized()) else 1
@@ -176,7 +198,8 @@ class TextBase(object):
             drop_last=drop_last,
             collate_fn=tz.alignCollate_realWTLAMask(imgH=cfg.height, imgW=cfg.width, down_sample_scale=cfg.down_sample_scale, mask=self.mask,
                                                     gpu_finish=gpu_finish,      # True: ToTensor + mask channel on the GPU by sr_batches
-                                                    gpu_resize=gpu_finish and (gpu_resize or bool(getattr(self.args, "gpu_resize", False)))))
+                                                    gpu_resize=gpu_finish and (gpu_resize or degrade or bool(getattr(self.args, "gpu_resize", False))),
+                                                    degrade=degrade, cutblur=cutblur))
         # (dataset/textzoom.py; uint8 pixels in the batch); False: the reference's float (B, 3 + mask, H, W) tensors for consumers that
         # iterate the loader themselves
         if shard:
@@ -185,9 +208,13 @@ class TextBase(object):
 
     def get_train_data(self):
         cfg = self.config.TRAIN
+        degrade, cutblur = degrade_flags(self.args)
+        hr_dir = getattr(self.args, "train_hr_dir", None)
+        if hr_dir:
+            return self._loader([], False, True, True, shard=True, degrade=True, cutblur=cutblur, hr_dir=hr_dir)
         if not isinstance(cfg.train_data_dir, list):
             raise TypeError('check trainRoot')
-        return self._loader(cfg.train_data_dir, False, True, True, shard=True)
+        return self._loader(cfg.train_data_dir, False, True, True, shard=True, degrade=degrade, cutblur=cutblur)
 
     def get_val_data(self):
         pairs = [self.get_test_data(d) for d in self.config.TRAIN.VAL.val_data_dir]

@@ -669,6 +669,12 @@ class TextSR(base.TextBase):
                         f.writelines(rows[:lp["log_rows"]])
             if rank == 0:
                 print("continuing from %s: epoch %d, iter %d" % (state_path, first_epoch, it))
+            # the frozen CRNN behind TATT's label_vecs is built on first use, and building a module draws its initial weights from
+            # torch's generator: in the run that wrote the state that happened before its first step, so here it has to happen before
+            # the random streams are restored, not after (a shuffling loader's next permutation comes from that generator)
+            if self.args.arch in ('tatt', 'tpgsr') and getattr(self, "_crnn_psn", None) is None and os.path.isfile(self._psn_crnn_path() or ""):
+                from ..model.crnn import load_crnn
+                self._crnn_psn = load_crnn(self._psn_crnn_path(), self.device)
 
         def restore_rng(which):
             per_rank = state["rng"]
@@ -810,9 +816,11 @@ class TextSR(base.TextBase):
         crnn = getattr(self, "_crnn_psn", None)
         if crnn is None:
             from ..model.crnn import load_crnn
-            path = os.path.join(self.resume, "recognizer_best_crnn.pth") if self.resume and os.path.isdir(self.resume) else None
-            crnn = self._crnn_psn = load_crnn(path, self.device)
+            crnn = self._crnn_psn = load_crnn(self._psn_crnn_path(), self.device)
         return crnn.label_vecs(images_lr[:, :3])
+
+    def _psn_crnn_path(self):
+        return os.path.join(self.resume, "recognizer_best_crnn.pth") if self.resume and os.path.isdir(self.resume) else None
 
     def test(self, loader=None, rec=None, display=False):
         """super_resolution.py:515-775: PGRMs from model_best_{k}.pth, CMM from model_best_cmm.pth, PSN from model_{arch}.pth

@@ -267,6 +267,92 @@ def resize_ragged_u8(packed, meta, H, W):
     return out
 
 
+DEGRADE_TILE = 32      # csrc/degrade.hip DG_TILE
+
+
+def _degrade_plan(packed, meta, what):
+    """Checks and per-call host data of degrade_ragged_u8 / degrade_noise -> (meta as int64 (B, 3), items (B, 4) int64 [byte offset, h,
+    w, first tile], tiles (n_tiles, 3) int32 [image, tile row, tile column]); packed: the device buffer or its size in bytes."""
+    import numpy as np
+    from .utils.resize import MAX_SIDE
+    m = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta)
+    if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] == 0 or m.shape[0] > 65535 or m.dtype.kind not in "iu":
+        raise _abi.DpmnError("%s: meta must be a non-empty integer (B, 3) array of (byte offset, h, w), B <= 65535" % what)
+    m = m.astype(np.int64)
+    off, hs, ws = m[:, 0], m[:, 1], m[:, 2]
+    nbytes = packed if isinstance(packed, int) else packed.numel()
+    if hs.min() < 1 or ws.min() < 1 or hs.max() > MAX_SIDE or ws.max() > MAX_SIDE or off.min() < 0 or int((off + hs * ws * 3).max()) > nbytes:
+        raise _abi.DpmnError("%s: meta names an image outside the packed buffer or with a side outside 1 .. %d" % (what, MAX_SIDE))
+    th, tw = -(-hs // DEGRADE_TILE), -(-ws // DEGRADE_TILE)
+    first = np.concatenate(([0], np.cumsum(th * tw)))
+    if first[-1] >= 2 ** 31:
+        raise _abi.DpmnError("%s: the batch has more than 2^31 - 1 tiles" % what)
+    tiles = np.empty((int(first[-1]), 3), np.int32)
+    for b in range(m.shape[0]):
+        t = tiles[first[b]:first[b + 1]]
+        t[:, 0] = b
+        t[:, 1] = np.repeat(np.arange(th[b]), tw[b])
+        t[:, 2] = np.tile(np.arange(tw[b]), th[b])
+    return m, np.concatenate((m, first[:-1, None]), axis=1), tiles
+
+
+def degrade_ragged_u8(packed, meta, params, z=None, seed=0):
+    """Synthetic LR images of a ragged batch (csrc/degrade.hip): packed = the device copy of utils.resize.pack_ragged's buffer (the HR
+    pixels), meta = its (B, 3) integer array, params = the (B, 16) rows of utils.degrade.draw_params -> the degraded images in the same
+    packed layout (a new 1-D uint8 device tensor), per image utils.degrade.degrade_u8 in fp32.  z: a device float32 tensor of
+    packed.numel() standard-normal values (the noise of byte i at index i), or None: generated in the kernel from `seed` (the field
+    degrade_noise(seed, meta) returns).  The same arguments give the same bytes on every run."""
+    import numpy as np
+    if not torch.is_tensor(packed) or not packed.is_cuda or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise _abi.DpmnError("degrade_ragged_u8: a contiguous 1-D uint8 CUDA tensor is required (the uploaded pack_ragged buffer); "
+                             "there is no CPU fallback")
+    m, items, tiles = _degrade_plan(packed, meta, "degrade_ragged_u8")
+    B, dev = m.shape[0], packed.device
+    p = np.ascontiguousarray(params.cpu().numpy() if torch.is_tensor(params) else params, dtype=np.float32)
+    if p.shape != (B, 16):
+        raise _abi.DpmnError("degrade_ragged_u8: params must be (%d, 16), got %s" % (B, p.shape))
+    if not (np.isin(p[:, [0, 10]], (3, 5)).all() and np.isin(p[p[:, 5] == 0][:, 6], (3, 5)).all() and np.isin(p[:, 5], (0, 1)).all()
+            and (p[:, [1, 11]] > 0).all() and (p[p[:, 5] == 0][:, 7] > 0).all() and (p[p[:, 5] == 1][:, 8:10] > 0).all()
+            and (p[:, 3:5] >= 0).all() and np.isin(p[:, 14], (0, 1, 2)).all() and np.isfinite(p).all()):
+        raise _abi.DpmnError("degrade_ragged_u8: a params row is outside its domain (kernel sizes 3 / 5, positive sigmas, "
+                             "non-negative noise factors, nr_mode 0 / 1, cut_side 0 / 1 / 2)")
+    if z is not None and (not torch.is_tensor(z) or not z.is_cuda or z.dtype != torch.float32 or z.dim() != 1 or not z.is_contiguous()
+                          or z.numel() != packed.numel() or z.device != dev):
+        raise _abi.DpmnError("degrade_ragged_u8: z must be a contiguous float32 tensor of packed.numel() values on the device of packed")
+    # one upload: items, params and tiles in one int64 buffer (params / tiles reinterpreted on the device)
+    n_tiles = tiles.shape[0]
+    host = np.zeros(B * 4 + B * 8 + (n_tiles * 3 + 1) // 2, np.int64)
+    host[:B * 4] = items.reshape(-1)
+    host[B * 4:B * 12].view(np.float32)[:] = p.reshape(-1)
+    host[B * 12:].view(np.int32)[:n_tiles * 3] = tiles.reshape(-1)
+    d = torch.from_numpy(host).to(dev)
+    out = torch.zeros_like(packed)      # (bytes of the buffer that belong to no image stay 0)
+    ws = torch.empty(lib.dpmn_degrade_ragged_workspace_bytes(n_tiles), dtype=torch.uint8, device=dev)
+    check(lib.dpmn_degrade_ragged_u8(packed.data_ptr(), packed.numel(), d.data_ptr(), d[B * 12:].data_ptr(), n_tiles, d[B * 4:].data_ptr(),
+                                     None if z is None else z.data_ptr(), int(seed) & (2 ** 64 - 1), B, out.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), stream()))
+    return out
+
+
+def degrade_noise(seed, meta, device=None):
+    """The standard-normal field degrade_ragged_u8(..., z=None, seed=seed) uses for the images of `meta` -> float32 on the device,
+    one value per packed byte ((meta[-1] offset + h * w * 3) values)."""
+    import numpy as np
+    if not torch.cuda.is_available():
+        raise _abi.DpmnError("degrade_noise: the field is generated on the GPU; there is no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise _abi.DpmnError("degrade_noise: the field is generated on the GPU (got device %s); there is no CPU fallback" % dev)
+    m = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta).astype(np.int64)
+    nbytes = int((m[:, 0] + m[:, 1] * m[:, 2] * 3).max()) if m.ndim == 2 and m.shape[0] and m.shape[1] == 3 else 0
+    m, items, _ = _degrade_plan(nbytes, meta, "degrade_noise")
+    out = torch.zeros(nbytes, dtype=torch.float32, device=dev)
+    d = torch.from_numpy(items).to(dev)
+    check(lib.dpmn_degrade_noise_f32(int(seed) & (2 ** 64 - 1), d.data_ptr(), nbytes, m.shape[0],
+                                     int((m[:, 1] * m[:, 2]).max()), out.data_ptr(), stream()))
+    return out
+
+
 def quantize_sr_u8(x):
     """save_image's quantisation of channels 0..2 of x (B, >=3, H, W) float -> (B, H, W, 3) uint8 on the device = utils.display.
     quantize_sr, the bytes of an SR image file.  The channels are read in place (strides)."""

@@ -486,6 +486,24 @@ int dpmn_resize_ragged_u8(const unsigned char* packed, long packed_bytes, const 
  * NaN -> 0) of channels 0..2 of x (B, >=3, H, W), read through its batch / channel strides (in floats; planes contiguous) ->
  * out (B, H, W, 3) uint8: the bytes of an SR image file. */
 int dpmn_quantize_sr_u8(const float* x, long batch_stride, long chan_stride, unsigned char* out, int B, int H, int W, dpmn_stream_t stream);
+/* Synthetic LR images from HR images (degrade.hip; dataset/dataset.py:422-489 degradation, :622-637 cutblur) for a RAGGED batch in the
+ * packed layout of dpmn_resize_ragged_u8; packed_out has the same layout (every image keeps its size; not in place).  Per image:
+ * Gaussian pre-blur -> shot / read noise (skipped when the pre-blurred image's mean is above 252) -> clip, round half to even ->
+ * Gaussian or d = 7 bilateral noise reduction on the 8-bit values -> unsharp mask, clip, truncate -> cutblur; BORDER_REFLECT_101 at the
+ * image's borders in every filter (the semantics of utils/degrade.py degrade_u8, in fp32).
+ * items: device int64 (B, 4), per image [byte offset in packed, h, w, index of its first tile]; tiles: device int32 (n_tiles, 3), per
+ * 32 x 32 tile [image, tile row, tile column], an image's tiles contiguous in row-major order; params: device float (B, 16), the rows of
+ * utils/degrade.py draw_params.  z_or_null: device float, one standard-normal value per packed byte (same offsets), or NULL: generated in
+ * the kernel from (seed, image, pixel, channel) -- the field dpmn_degrade_noise_f32 writes.  Sides 1 .. 8192; an image or tile whose
+ * numbers do not fit the buffers is neither read nor written.  workspace: dpmn_degrade_ragged_workspace_bytes(n_tiles) bytes (the
+ * per-tile sums of the mean test, added in a fixed order: the same bytes on every run).  Two launches. */
+size_t dpmn_degrade_ragged_workspace_bytes(int n_tiles);
+int dpmn_degrade_ragged_u8(const unsigned char* packed_in, long packed_bytes, const long long* items, const int* tiles, int n_tiles,
+                           const float* params, const float* z_or_null, unsigned long long seed, int B, unsigned char* packed_out,
+                           void* workspace, size_t workspace_bytes, dpmn_stream_t stream);
+/* out: device float, one value per packed byte; max_pixels: the largest h * w (sizes the launch) */
+int dpmn_degrade_noise_f32(unsigned long long seed, const long long* items, long packed_bytes, int B, int max_pixels, float* out,
+                           dpmn_stream_t stream);
 
 /* rotation augmentation of the trainer (utils/util.py:37-58 torch_rotate_img; super_resolution.py:144-151, 358-365):
  * per-image affine with aspect-ratio jitter -> affine_grid (align_corners=False) -> bilinear grid_sample, zeros padding.

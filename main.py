@@ -8,7 +8,8 @@ HIP-backed modules.  `--rec crnn` loads the native CRNN recogniser (config TRAIN
 batches of the real shapes -- `--synthetic_steps` of them -- and the text priors come from `TextSR.synthetic_text_prior()`;
 everything between the loader and the optimizer step is the real path.  `--demo_dir DIR --resume CKPT` super-resolves a folder of images
 (any sizes; resized on the GPU) into `--demo_out`.  `--train_state PATH` makes a training run continuable: the same command line starts the
-run or, when PATH exists, continues it bit for bit.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
+run or, when PATH exists, continues it bit for bit.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
+(`--cutblur`: with the reference's cutblur on top); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
 import argparse
 import csv
@@ -61,6 +62,12 @@ def recogniser(mission, args):
 
 
 def main(config, args):
+    if getattr(args, "cutblur", False) and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None)):
+        raise SystemExit("main.py: --cutblur needs --manmade_degrade (or --train_hr_dir): it mixes columns of the HR image into the "
+                         "synthesised LR image")
+    hr_dir = getattr(args, "train_hr_dir", None)
+    if hr_dir and not os.path.isdir(hr_dir):
+        raise SystemExit("main.py: --train_hr_dir %s is not a directory" % hr_dir)
     import torch
     import torch.distributed as dist
     from dpmn_amd.interfaces.super_resolution import TextSR
@@ -116,7 +123,7 @@ def main(config, args):
             with open(log_path, "w+") as out:
                 csv.writer(out).writerow(["epoch", "dataset", "accuracy", "psnr_avg", "ssim_avg", "best", "best_sum"])
         dirs = config.TRAIN.train_data_dir or []
-        if dirs and all(os.path.isdir(d) for d in dirs):                   # TextZoom LMDBs from the config, like base.py:85-103
+        if hr_dir or (dirs and all(os.path.isdir(d) for d in dirs)):       # TextZoom LMDBs from the config, like base.py:85-103, or --train_hr_dir
             from dpmn_amd.dataset.textzoom import sr_batches
             world = dist.get_world_size() if dist.is_initialized() else 1
             if bs % world != 0 or bs // world < 2:
@@ -198,6 +205,14 @@ if __name__ == '__main__':
     parser.add_argument('--train_state', type=str, default=None,
                         help='one file that holds everything needed to continue the training run exactly: if it exists the run '
                              'continues from it, otherwise it starts fresh; rewritten at every checkpoint save and at the end')
+    parser.add_argument('--manmade_degrade', action='store_true', default=False,
+                        help='training: the LR images are synthesised from the HR images on the GPU (blur, noise, noise reduction, '
+                             'sharpening) instead of read from the LMDB')
+    parser.add_argument('--cutblur', action='store_true', default=False,
+                        help='with --manmade_degrade: columns on one side of a random cut of the synthesised LR image are the HR image\'s')
+    parser.add_argument('--train_hr_dir', type=str, default=None,
+                        help='train from this folder of HR images (optional labels.txt: file name<TAB>word); implies --manmade_degrade, '
+                             'needs no LMDB')
     args = parser.parse_args()
     config_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config', 'super_resolution.yaml')
     config = AttrDict(yaml.load(open(config_path, 'r'), Loader=yaml.Loader))
