@@ -10,23 +10,11 @@
 // neither pass keeps a band in LDS: two launches and a global intermediate serve every size pair with one code path.  A few hundred
 // KB per batch: launch-bound work, nothing here is tuned for throughput.
 // k_quantize_sr    save_image's quantisation of an NCHW float batch -> (B, H, W, 3) uint8, the bytes of the SR image files.
-#include "common.h"
+#include "u8_pixel.h"
 
 namespace {
 
-constexpr int RESIZE_THREADS = 256;
-constexpr int RESIZE_PRECISION_BITS = 22;         // PIL Resample.c: 32 - 8 - 2
-constexpr int RESIZE_MAX_SIDE = 8192;
-constexpr int RESIZE_MAX_KSIZE = 2 * 2 * RESIZE_MAX_SIDE + 1;      // 8192 -> 1
 constexpr int RESIZE_ITEM_WORDS = 8;
-
-__device__ __forceinline__ unsigned char clip8(int acc) { return (unsigned char)min(max(acc >> RESIZE_PRECISION_BITS, 0), 255); }
-
-// save_image: x.mul(255).add_(0.5).clamp_(0, 255).to(uint8) -- two separately rounded fp32 operations (__fmul_rn / __fadd_rn never
-// contract), then truncation; fmaxf drops a NaN: 0.  The formula of display.hip's SR / HR rows.
-__device__ __forceinline__ unsigned char quant_sr(float x) {
-  return (unsigned char)(int)fminf(fmaxf(__fadd_rn(__fmul_rn(x, 255.0f), 0.5f), 0.0f), 255.0f);
-}
 
 // One image of the batch as the kernels see it (include/dpmn_hip.h dpmn_resize_ragged_u8: 8 int64 per image).
 struct Item {

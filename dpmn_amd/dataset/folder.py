@@ -1,7 +1,8 @@
 """A directory of someone's own text crops as the LR input of the SR path (main.py --demo_dir, TextSR.demo): files in sorted name
 order, decoded with PIL, converted to RGB, packed as a ragged batch (utils/resize.py pack_ragged), uploaded once and resized to the
 model's LR size on the GPU (ops.resize_ragged_u8, byte for byte PIL's bicubic resize), then finished like a TextZoom batch
-(ops.collate_u8: ToTensor and the mask channel).  The host half (`host_batches`) needs no GPU.
+(ops.collate_u8: ToTensor and the mask channel).  The host half (`host_batches`) needs no GPU.  `folder_window_batches` (main.py
+--demo_tile) keeps the aspect ratio of wide images: every image as overlapping windows of the LR size (ops.resize_windows_u8).
 `FolderHR`: the same kind of directory as the HR images of a TRAINING set (main.py --train_hr_dir): the LR images are synthesised on
 the GPU (dataset/textzoom.py, alignCollate_realWTLAMask(degrade=True) and sr_batches), so training needs neither LMDB nor LR images.
 """
@@ -13,10 +14,11 @@ import torch
 LABELS_FILE = "labels.txt"
 
 
-def host_batches(dir_, batch_size):
+def host_batches(dir_, batch_size, check=None):
     """Yields (names, packed, meta) per batch of at most batch_size images: the file names and utils.resize.pack_ragged of their RGB
-    pixels.  Regular files of `dir_` in sorted name order; a file PIL cannot open, or an image pack_ragged rejects, is skipped with
-    one printed line.  A directory without files raises."""
+    pixels.  Regular files of `dir_` in sorted name order; a file PIL cannot open, or an image pack_ragged rejects (check: a callable
+    (image, name) in place of utils.resize.check_image, which raises for an image it rejects), is skipped with one printed line.  A
+    directory without files raises."""
     from PIL import Image
     from ..utils.resize import MAX_PACKED_BYTES, check_image, pack_ragged
     batch_size = int(batch_size)
@@ -30,7 +32,7 @@ def host_batches(dir_, batch_size):
         try:
             with Image.open(os.path.join(dir_, f)) as im:
                 a = np.asarray(im.convert('RGB'), dtype=np.uint8)
-            check_image(a, f)
+            (check or check_image)(a, f)
         except Exception as e:      # whatever a decoder raises on a file that is not its format, or is damaged
             print("folder: skipping %s (%s: %s)" % (f, type(e).__name__, e))
             continue
@@ -54,6 +56,21 @@ def folder_batches(dir_, batch_size, lr_size, mask, device):
     h, w = lr_size
     for names, packed, meta in host_batches(dir_, batch_size):
         yield names, ops.collate_u8(ops.resize_ragged_u8(packed.to(device, non_blocking=True), meta, h, w), mask)
+
+
+def folder_window_batches(dir_, batch_size, lr_size, mask, device):
+    """folder_batches for wide images (main.py --demo_tile): yields (names, plan, images_lr) per batch of at most batch_size files.
+    Every image is resized to the LR height with its aspect ratio kept and cut into overlapping windows of lr_size
+    (ops.resize_windows_u8; utils/tile.py): images_lr (T, 3 + mask, h, w) float on `device` holds the T windows of the batch, plan
+    their (image, x0) -- what ops.stitch_windows_u8 needs to put the SR windows together again.  An image of aspect w : h or less is
+    one window, the image folder_batches yields.  An image whose line would be wider than utils.resize.MAX_SIDE is skipped with one
+    printed line."""
+    from .. import ops
+    from ..utils.tile import check_line
+    h, w = lr_size
+    for names, packed, meta in host_batches(dir_, batch_size, check=lambda a, f: check_line(a, (h, w), f)):
+        windows, plan = ops.resize_windows_u8(packed.to(device, non_blocking=True), meta, h, w)
+        yield names, plan, ops.collate_u8(windows, mask)
 
 
 class FolderHR(torch.utils.data.Dataset):

@@ -307,7 +307,7 @@ class TextSR(base.TextBase):
         return res
 
     @torch.no_grad()
-    def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None):
+    def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None):
         """Super-resolve someone's own images (ours; main.py --demo_dir): batches yields (names, images_lr) as
         dataset.folder.folder_batches does.  Per batch `refine` (label_vecs from the frozen CRNN for tatt / tpgsr, as in eval), then
         save_image's quantisation on the GPU (ops.quantize_sr_u8), ONE device-to-host copy and one <stem>_sr.png per input under
@@ -315,8 +315,13 @@ class TextSR(base.TextBase):
         out_dir/demo_result.csv: a header and one row file, lr_string, sr_string per image (empty strings without one).  A name whose
         stem is taken (a.png after a.jpg) keeps its extension: a.png_sr.png.  Returns the rows.
         A batch of ONE image changes SKConv's squeeze() semantics (quirk Q3; base.py _loader guards the loaders against it): it runs
-        with the image repeated and the duplicate's output dropped."""
-        from PIL import Image
+        with the image repeated and the duplicate's output dropped.
+        tile=True (main.py --demo_tile): batches yields (names, plan, images_lr) as dataset.folder.folder_window_batches does -- every
+        image as overlapping LR windows of its line.  The windows of a batch go through `refine` in chunks of at most `chunk` windows
+        (default: the batch size; a chunk of one window is repeated as above, label_vecs per window), ops.stitch_windows_u8 blends the
+        SR windows of an image on the GPU, and <stem>_sr.png is scale * lr_h high and scale * w_line wide.  lr_string / sr_string are
+        then the reads of the image's WINDOWS joined with '|': a recogniser sees lr_w columns at a time and neighbouring windows
+        overlap, so this is not a transcription of the line.  An image of one window is written as without tile."""
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
         for m in model_list:
@@ -324,6 +329,10 @@ class TextSR(base.TextBase):
         fn = text_prior_fn or self.default_text_prior()
         os.makedirs(out_dir, exist_ok=True)
         rows, taken = [], set()
+        if tile:
+            for names, pixels, preds_lr, preds_sr in self._demo_windows(model_list, model_psn, batches, fn, reader, chunk):
+                self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken)
+            batches = ()
         for names, images_lr in batches:
             n = len(names)
             images_lr = images_lr.to(self.device)
@@ -335,20 +344,55 @@ class TextSR(base.TextBase):
             blank = [''] * n
             preds_lr = reader(images_lr[:n, :3]) if reader is not None else blank
             preds_sr = reader(sr[:, :3]) if reader is not None else blank
-            for name, a, s_lr, s_sr in zip(names, pixels, preds_lr, preds_sr):
-                out_name = os.path.splitext(name)[0] + "_sr.png"
-                if out_name in taken:
-                    out_name = name + "_sr.png"
-                while out_name in taken:
-                    out_name = "_" + out_name
-                taken.add(out_name)
-                Image.fromarray(a).save(os.path.join(out_dir, out_name))
-                rows.append([name, str(s_lr), str(s_sr)])
+            self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken)
         with open(os.path.join(out_dir, "demo_result.csv"), "w", newline="") as out:
             w = csv.writer(out)
             w.writerow(["file", "lr_string", "sr_string"])
             w.writerows(rows)
         return rows
+
+    @staticmethod
+    def _demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken):
+        """demo: one <stem>_sr.png per image of a batch and its row."""
+        from PIL import Image
+        for name, a, s_lr, s_sr in zip(names, pixels, preds_lr, preds_sr):
+            out_name = os.path.splitext(name)[0] + "_sr.png"
+            if out_name in taken:
+                out_name = name + "_sr.png"
+            while out_name in taken:
+                out_name = "_" + out_name
+            taken.add(out_name)
+            Image.fromarray(a).save(os.path.join(out_dir, out_name))
+            rows.append([name, str(s_lr), str(s_sr)])
+
+    def _demo_windows(self, model_list, model_psn, batches, fn, reader, chunk):
+        """demo(tile=True): per batch (names, plan, images_lr) of windows -> (names, one (H, W_b, 3) uint8 array per image, the LR
+        reads, the SR reads), the reads of an image's windows joined with '|'."""
+        chunk = max(int(chunk if chunk is not None else self.batch_size), 1)
+        for names, plan, images_lr in batches:
+            images_lr = images_lr.to(self.device)
+            T = images_lr.shape[0]
+            srs, reads_lr, reads_sr = [], [], []
+            for lo in range(0, T, chunk):
+                x = images_lr[lo:lo + chunk]
+                n = x.shape[0]
+                if n == 1:
+                    x = torch.cat([x, x], 0)
+                label_vecs = self.label_vecs_from_crnn(x) if self.args.arch in ('tatt', 'tpgsr') else None
+                sr = self.refine(model_list, model_psn, x, label_vecs, fn)[:n]
+                srs.append(sr)
+                if reader is not None:
+                    reads_lr += [str(s) for s in reader(x[:n, :3])]
+                    reads_sr += [str(s) for s in reader(sr[:, :3])]
+            packed, meta = ops.stitch_windows_u8(srs[0] if len(srs) == 1 else torch.cat(srs, 0), plan, scale=self.scale_factor)
+            flat = packed.cpu().numpy()
+            pixels = [flat[off:off + h * w * 3].reshape(h, w, 3) for off, h, w in meta]
+            preds_lr, preds_sr = [[] for _ in names], [[] for _ in names]
+            if reader is not None:
+                for (b, _), s_lr, s_sr in zip(plan, reads_lr, reads_sr):
+                    preds_lr[b].append(s_lr)
+                    preds_sr[b].append(s_sr)
+            yield names, pixels, ['|'.join(p) for p in preds_lr], ['|'.join(p) for p in preds_sr]
 
     # ------------------------------------------------------------------ training (super_resolution.py:113-278)
     def build_training(self, world_size=1, group=None):

@@ -370,6 +370,121 @@ def quantize_sr_u8(x):
     return out
 
 
+def _resize_windows_plan(packed, meta, lr_h, lr_w):
+    """Checks and per-call host data of resize_windows_u8 -> (plan, host): plan = utils.tile's list of (image, x0) per window, host = the
+    arrays of one call as numpy: items (B, 10) int64, windows (T, 2) int32, tables (1-D int32: the coefficient tables of the call's
+    size pairs, each once) and the sums that size the workspace and the launches (_resize_windows_run)."""
+    import numpy as np
+    from .utils.resize import MAX_SIDE, pil_resample_tables
+    from .utils.tile import line_width, window_plan
+    if not torch.is_tensor(packed) or not packed.is_cuda or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise _abi.DpmnError("resize_windows_u8: a contiguous 1-D uint8 CUDA tensor is required (the uploaded pack_ragged buffer); "
+                             "there is no CPU fallback")
+    m = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta)
+    if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] == 0 or m.shape[0] > 65535 or m.dtype.kind not in "iu":
+        raise _abi.DpmnError("resize_windows_u8: meta must be a non-empty integer (B, 3) array of (byte offset, h, w), B <= 65535")
+    m = m.astype(np.int64)
+    if not (1 <= lr_h <= MAX_SIDE and 2 <= lr_w <= MAX_SIDE):
+        raise _abi.DpmnError("resize_windows_u8: window size %d x %d outside 1 .. %d" % (lr_h, lr_w, MAX_SIDE))
+    off, hs, ws = m[:, 0], m[:, 1], m[:, 2]
+    if hs.min() < 1 or ws.min() < 1 or hs.max() > MAX_SIDE or ws.max() > MAX_SIDE or off.min() < 0 or int((off + hs * ws * 3).max()) > packed.numel():
+        raise _abi.DpmnError("resize_windows_u8: meta names an image outside the packed buffer or with a side outside 1 .. %d" % MAX_SIDE)
+    try:
+        wl = np.array([line_width(int(h), int(w), lr_h, lr_w) for h, w in zip(hs, ws)], np.int64)
+    except ValueError as e:
+        raise _abi.DpmnError("resize_windows_u8: %s" % e) from e
+    B = m.shape[0]
+    plan = [(b, x0) for b in range(B) for x0 in window_plan(int(wl[b]), lr_w)]
+    # the tables travel with the call (one upload): line widths make far more distinct size pairs than the device cache of
+    # resize_ragged_u8 is sized for, and a batch reads each of its tables once
+    tabs, chunks, n_ints = {}, [], 0
+    for pair in [(int(w), int(l)) for w, l in zip(ws, wl)] + [(int(h), lr_h) for h in hs]:
+        if pair not in tabs:
+            t = pil_resample_tables(*pair)
+            tabs[pair] = (n_ints, t.shape[1] - 2)
+            chunks.append(t.reshape(-1))
+            n_ints += t.size
+    items = np.empty((B, 10), np.int64)
+    items[:, :3] = m
+    items[:, 3] = wl
+    mid = hs * wl * 3
+    items[:, 4] = np.concatenate(([0], np.cumsum(mid[:-1])))                                   # the ragged intermediate: h x w_line x 3
+    items[:, 5] = int(mid.sum()) + np.concatenate(([0], np.cumsum(wl[:-1]))) * (lr_h * 3)      # behind it the lines: lr_h x w_line x 3
+    for b in range(B):
+        items[b, 6:8] = tabs[(int(ws[b]), int(wl[b]))]
+        items[b, 8:10] = tabs[(int(hs[b]), lr_h)]
+    host = dict(items=items, windows=np.asarray(plan, np.int32).reshape(-1, 2), tables=np.concatenate(chunks), lr_size=(lr_h, lr_w),
+                sum_h_w_line=int((hs * wl).sum()), sum_w_line=int(wl.sum()), max_mid_bytes=int(mid.max()), max_w_line=int(wl.max()))
+    return plan, host
+
+
+def _resize_windows_run(packed, host):
+    """One upload of the host arrays of _resize_windows_plan (items, windows and tables in one int64 buffer) and the three launches."""
+    import numpy as np
+    items, windows, tables, (lr_h, lr_w) = host["items"], host["windows"], host["tables"], host["lr_size"]
+    B, T, dev = items.shape[0], windows.shape[0], packed.device
+    n_win = (T * 2 + 1) // 2
+    buf = np.zeros(B * 10 + n_win + (tables.size + 1) // 2, np.int64)
+    buf[:B * 10] = items.reshape(-1)
+    buf[B * 10:B * 10 + n_win].view(np.int32)[:T * 2] = windows.reshape(-1)
+    buf[B * 10 + n_win:].view(np.int32)[:tables.size] = tables
+    d = torch.from_numpy(buf).to(dev)
+    ws = torch.empty(lib.dpmn_resize_windows_workspace_bytes(host["sum_h_w_line"], host["sum_w_line"], lr_h), dtype=torch.uint8, device=dev)
+    out = torch.empty(T, lr_h, lr_w, 3, dtype=torch.uint8, device=dev)
+    check(lib.dpmn_resize_windows_u8(packed.data_ptr(), packed.numel(), d.data_ptr(), B, d[B * 10 + n_win:].data_ptr(), tables.size,
+                                     d[B * 10:].data_ptr(), T, host["max_mid_bytes"], host["max_w_line"], out.data_ptr(), lr_h, lr_w,
+                                     ws.data_ptr(), ws.numel(), stream()))
+    return out
+
+
+def resize_windows_u8(packed, meta, lr_h, lr_w):
+    """A ragged batch of images as overlapping windows of the model's LR size (csrc/tile.hip): packed / meta as resize_ragged_u8 takes
+    them -> (windows (T, lr_h, lr_w, 3) uint8 on the device, plan).  Every image is resized to the height lr_h and its own width
+    (utils.tile.line_width; byte for byte Image.resize((w_line, lr_h), BICUBIC)) once and cut at utils.tile.window_plan's starts; plan is
+    the list of (image, x0) per window that stitch_windows_u8 takes.  = utils.tile.resize_windows_np.  Per call one buffer is uploaded:
+    the items, the windows and the coefficient tables of the call's size pairs."""
+    plan, host = _resize_windows_plan(packed, meta, int(lr_h), int(lr_w))
+    return _resize_windows_run(packed, host), plan
+
+
+def stitch_windows_u8(sr, plan, scale=2):
+    """The SR windows of resize_windows_u8's plan back into one image per input (csrc/tile.hip): sr (T, >= 3, H, scale * lr_w) float32
+    on the device, channels 0..2 read in place -> (packed, meta): a 1-D uint8 device tensor holding the SR lines back to back (HWC) and
+    the host int64 (B, 3) array of (byte offset, H, scale * w_line) per image, the layout of utils.resize.pack_ragged.  Every window is
+    quantised with save_image's rule and overlapping windows are blended in integers = utils.tile.stitch_np, byte for byte."""
+    import numpy as np
+    from .utils.tile import plan_lines
+    if not torch.is_tensor(sr) or not sr.is_cuda:
+        raise _abi.DpmnError("stitch_windows_u8: the windows are stitched on the GPU (got a %s tensor); there is no CPU fallback"
+                             % (sr.device if torch.is_tensor(sr) else type(sr).__name__))
+    scale = int(scale)
+    if sr.dtype != torch.float32 or sr.dim() != 4 or sr.shape[1] < 3 or sr.shape[0] != len(plan) or sr.shape[0] == 0 or scale < 1 or \
+            sr.shape[3] % scale or sr.shape[3] < 2 * scale:
+        raise _abi.DpmnError("stitch_windows_u8: float32 (T, >= 3, H, scale * lr_w) windows and a plan of T entries expected, got %s %s "
+                             "and %d" % (sr.dtype, tuple(sr.shape), len(plan)))
+    T, _, H, sr_w = sr.shape
+    try:
+        lines = plan_lines(plan, sr_w // scale)
+    except ValueError as e:
+        raise _abi.DpmnError("stitch_windows_u8: %s" % e) from e
+    B = len(lines)
+    if B > 65535:
+        raise _abi.DpmnError("stitch_windows_u8: more than 65535 images")
+    meta = np.empty((B, 3), np.int64)
+    meta[:, 1], meta[:, 2] = H, [scale * l[2] for l in lines]
+    sizes = meta[:, 1] * meta[:, 2] * 3
+    meta[:, 0] = np.concatenate(([0], np.cumsum(sizes[:-1])))
+    buf = np.zeros(B * 4 + T, np.int64)
+    buf[:B * 4].reshape(B, 4)[:] = [(off, l[2], l[0], l[1]) for off, l in zip(meta[:, 0], lines)]
+    buf[B * 4:].view(np.int32)[:] = np.asarray(plan, np.int32).reshape(-1)
+    d = torch.from_numpy(buf).to(sr.device)
+    out = torch.zeros(int(sizes.sum()), dtype=torch.uint8, device=sr.device)
+    x, px, bs, cs = _display_planes(sr, "sr")
+    check(lib.dpmn_stitch_windows_u8(px, bs, cs, T, H, sr_w, scale, d.data_ptr(), B, d[B * 4:].data_ptr(), max(l[2] for l in lines),
+                                     out.data_ptr(), out.numel(), stream()))
+    return out, meta
+
+
 def maxpool(x, kh, kw, scale=None, shift=None):
     """nn.MaxPool2d((kh,kw), stride (kh,kw)) over NHWC; scale/shift: the producer's BatchNorm affine + ReLU applied on load."""
     B, H, W, Cc = x.shape

@@ -504,6 +504,30 @@ int dpmn_degrade_ragged_u8(const unsigned char* packed_in, long packed_bytes, co
 /* out: device float, one value per packed byte; max_pixels: the largest h * w (sizes the launch) */
 int dpmn_degrade_noise_f32(unsigned long long seed, const long long* items, long packed_bytes, int B, int max_pixels, float* out,
                            dpmn_stream_t stream);
+/* A wide text line as overlapping windows of the model's LR size (tile.hip; utils/tile.py holds the plan arithmetic and the numpy
+ * restatement).  resize_windows: a RAGGED batch in the packed layout of dpmn_resize_ragged_u8 -> every image resized with PIL's
+ * fixed-point bicubic (the arithmetic of dpmn_resize_ragged_u8, byte for byte Image.resize((w_line, lr_h), BICUBIC)) to the height lr_h
+ * and ITS OWN width w_line >= lr_w, once, then cut: out (T, lr_h, lr_w, 3) uint8, window t = columns [x0, x0 + lr_w) of the line of its
+ * image.  items: device int64 (B, 10), per image [byte offset in packed, h, w, w_line, byte offset of its h x w_line x 3 intermediate in
+ * the workspace, byte offset of its lr_h x w_line x 3 line in the workspace, offset of its (w -> w_line) table in `tables` (in ints),
+ * ksize_h, offset of its (h -> lr_h) table, ksize_v]; tables: device int32, table_ints values, the rows of utils/resize.py
+ * pil_resample_tables back to back; windows: device int32 (T, 2) [image, x0].  Sides 1 .. 8192.  An image whose numbers do not fit the
+ * buffers is not read, and its windows -- like a window whose image or x0 is out of range -- come out black.  max_mid_bytes: the largest
+ * h * w_line * 3, max_w_line: the largest w_line (they size the launches).  workspace: dpmn_resize_windows_workspace_bytes(sum of
+ * h * w_line, sum of w_line, lr_h) bytes.  Three launches. */
+size_t dpmn_resize_windows_workspace_bytes(long sum_h_w_line, long sum_w_line, int lr_h);
+int dpmn_resize_windows_u8(const unsigned char* packed, long packed_bytes, const long long* items, int B, const int* tables, long table_ints,
+                           const int* windows, int T, long max_mid_bytes, int max_w_line, unsigned char* out, int lr_h, int lr_w,
+                           unsigned char* workspace, size_t workspace_bytes, dpmn_stream_t stream);
+/* stitch_windows: the SR windows sr (T, >= 3, H, sr_w) float, sr_w = scale * lr_w, channels 0..2 read through the batch / channel strides
+ * as dpmn_quantize_sr_u8 reads them -> the SR lines, ragged and packed: per image H x scale * w_line x 3 uint8 at its byte offset in out.
+ * Every window is quantised with save_image's rule; an output byte is (sum wgt * q + W / 2) / W over the windows of its image that cover
+ * its column, in integers, with wgt = min(L, R, sr_w / 2) at column j of a window (L = j + 1, or sr_w / 2 in the image's first window;
+ * R = sr_w - j, or sr_w / 2 in its last) and W the sum of the weights.  lines: device int64 (B, 4), per image [byte offset in out,
+ * w_line, first window, windows]; windows: device int32 (T, 2) [image, x0].  A line whose numbers do not fit the buffers is not written;
+ * a window that names another image or starts outside the line is skipped.  One launch, no atomics: every byte has one owner. */
+int dpmn_stitch_windows_u8(const float* sr, long batch_stride, long chan_stride, int T, int H, int sr_w, int scale, const long long* lines, int B,
+                           const int* windows, int max_w_line, unsigned char* out, long out_bytes, dpmn_stream_t stream);
 
 /* rotation augmentation of the trainer (utils/util.py:37-58 torch_rotate_img; super_resolution.py:144-151, 358-365):
  * per-image affine with aspect-ratio jitter -> affine_grid (align_corners=False) -> bilinear grid_sample, zeros padding.

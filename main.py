@@ -7,7 +7,8 @@ HIP-backed modules.  `--rec crnn` loads the native CRNN recogniser (config TRAIN
 (config TRAIN.VAL.moran_pretrained, when set).  Without a TextZoom LMDB directory the loop is fed synthetic (images_hr, images_lr, label_vecs)
 batches of the real shapes -- `--synthetic_steps` of them -- and the text priors come from `TextSR.synthetic_text_prior()`;
 everything between the loader and the optimizer step is the real path.  `--demo_dir DIR --resume CKPT` super-resolves a folder of images
-(any sizes; resized on the GPU) into `--demo_out`.  `--train_state PATH` makes a training run continuable: the same command line starts the
+(any sizes; resized on the GPU) into `--demo_out`; with `--demo_tile` a wide image keeps its aspect ratio and goes through the model in
+overlapping windows.  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
 (`--cutblur`: with the reference's cutblur on top); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
@@ -65,6 +66,8 @@ def main(config, args):
     if getattr(args, "cutblur", False) and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None)):
         raise SystemExit("main.py: --cutblur needs --manmade_degrade (or --train_hr_dir): it mixes columns of the HR image into the "
                          "synthesised LR image")
+    if getattr(args, "demo_tile", False) and not getattr(args, "demo_dir", None):
+        raise SystemExit("main.py: --demo_tile needs --demo_dir: it super-resolves the wide images of that folder in overlapping windows")
     hr_dir = getattr(args, "train_hr_dir", None)
     if hr_dir and not os.path.isdir(hr_dir):
         raise SystemExit("main.py: --train_hr_dir %s is not a directory" % hr_dir)
@@ -93,12 +96,18 @@ def main(config, args):
             raise SystemExit("main.py: --demo_dir needs --resume <dir> holding the trained models (as --test does)")
         if rank != 0:
             return
-        from dpmn_amd.dataset.folder import folder_batches
+        from dpmn_amd.dataset.folder import folder_batches, folder_window_batches
         models, psn = mission.build_models(testing=True)
         scale = config.TRAIN.down_sample_scale
         out_dir = getattr(args, "demo_out", None) or os.path.join(mission.vis_dir, "demo")
-        batches = folder_batches(args.demo_dir, bs, (config.TRAIN.height // scale, config.TRAIN.width // scale), mission.mask, mission.device)
-        rows = mission.demo(models, psn, batches, out_dir, rec=rec)
+        lr_size = (config.TRAIN.height // scale, config.TRAIN.width // scale)
+        if getattr(args, "demo_tile", False):
+            # wide images keep their aspect ratio: overlapping LR windows per image, one stitched <stem>_sr.png (utils/tile.py)
+            batches = folder_window_batches(args.demo_dir, bs, lr_size, mission.mask, mission.device)
+            rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=True, chunk=bs)
+        else:
+            batches = folder_batches(args.demo_dir, bs, lr_size, mission.mask, mission.device)
+            rows = mission.demo(models, psn, batches, out_dir, rec=rec)
         print("%d images super-resolved into %s" % (len(rows), out_dir))
         return
     if args.test:
@@ -200,6 +209,9 @@ if __name__ == '__main__':
     parser.add_argument('--demo_dir', type=str, default=None,
                         help='super-resolve every image of this directory with the models of --resume (no HR images, no metrics)')
     parser.add_argument('--demo_out', type=str, default=None, help='where --demo_dir writes (default: <vis_dir>/demo)')
+    parser.add_argument('--demo_tile', action='store_true', default=False,
+                        help='with --demo_dir: an image wider than the LR aspect keeps its aspect ratio and is super-resolved in '
+                             'overlapping windows that are blended into one image')
     parser.add_argument('--gpu_resize', action='store_true', default=False,
                         help='TextZoom loaders: the bicubic resize of the decoded images runs on the GPU (same bytes as PIL)')
     parser.add_argument('--train_state', type=str, default=None,
