@@ -16,7 +16,7 @@
 // an element-wise pass reads dword l + const, a per-pixel pass dword 3 l + const -- both conflict-free on 32 banks.  Launch- and
 // latency-bound work on a few hundred KB per batch; nothing here is tuned for throughput.
 //   k_degrade_noise    the standard-normal field the fused path generates for z == NULL, written out (tests; same device function)
-#include "common.h"
+#include "u8_pixel.h"
 
 namespace {
 
@@ -26,7 +26,6 @@ constexpr int DG_R_PRE = 2, DG_R_NR = 3, DG_R_SHP = 2;      // largest radius pe
 constexpr int DG_HALO = DG_R_PRE + DG_R_NR + DG_R_SHP;
 constexpr int DG_SIDE = DG_TILE + 2 * DG_HALO;              // 46
 constexpr int DG_BUF = DG_SIDE * DG_SIDE * 3;
-constexpr int DG_MAX_SIDE = 8192;
 constexpr int DG_PARAMS = 16;
 constexpr int DG_COLOR = 3 * 255 + 1;                        // |dR| + |dG| + |dB|
 constexpr int DG_SPACE = (2 * DG_R_NR + 1) * (2 * DG_R_NR + 1);
@@ -113,7 +112,7 @@ __device__ __forceinline__ Item load_item(const long long* __restrict__ items, i
   Item it;
   const long long h = p[1], w = p[2], ft = p[3];
   it.off = p[0];
-  it.ok = h >= 1 && h <= DG_MAX_SIDE && w >= 1 && w <= DG_MAX_SIDE && it.off >= 0 && it.off <= packed_bytes - h * w * 3 && ft >= 0 && ft < n_tiles;
+  it.ok = h >= 1 && h <= RESIZE_MAX_SIDE && w >= 1 && w <= RESIZE_MAX_SIDE && it.off >= 0 && it.off <= packed_bytes - h * w * 3 && ft >= 0 && ft < n_tiles;
   it.h = (int)h; it.w = (int)w; it.first_tile = (int)ft;
   it.tiles_x = it.ok ? (it.w + DG_TILE - 1) / DG_TILE : 0;
   it.tiles = it.ok ? it.tiles_x * ((it.h + DG_TILE - 1) / DG_TILE) : 0;
@@ -281,7 +280,7 @@ k_degrade_noise(unsigned long long seed, const long long* __restrict__ items, lo
   const int b = blockIdx.y;
   const long long* p = items + (size_t)b * 4;
   const long long off = p[0], h = p[1], w = p[2];
-  if (h < 1 || h > DG_MAX_SIDE || w < 1 || w > DG_MAX_SIDE || off < 0 || off > packed_bytes - h * w * 3) return;
+  if (h < 1 || h > RESIZE_MAX_SIDE || w < 1 || w > RESIZE_MAX_SIDE || off < 0 || off > packed_bytes - h * w * 3) return;
   const long total = (long)(h * w * 3);
   for (long i = (long)blockIdx.x * DG_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * DG_THREADS) {
     const int pixel = (int)(i / 3);

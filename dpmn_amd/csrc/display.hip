@@ -5,28 +5,15 @@
 //                                         rows [2H, 3H) the HR target, save_image's quantisation
 // Every stage of the reference is integer arithmetic or a single fp32 operation: the bytes equal the reference's file content.
 // Runs a handful of times per evaluation: nothing here is tuned for throughput.
-#include "common.h"
+#include "u8_pixel.h"
 
 namespace {
 
 constexpr int DISPLAY_THREADS = 256;
 constexpr int DISPLAY_LDS_BYTES = 48 * 1024;      // horizontal-pass intermediate of one row band (uint8, HWC)
-constexpr int DISPLAY_PRECISION_BITS = 22;        // PIL Resample.c: 32 - 8 - 2
 constexpr int DISPLAY_MAX_KSIZE = 5;              // bicubic, scale <= 1: ceil(2) * 2 + 1 taps
 
-// ToPILImage on a float tensor: x.mul(255).byte() -- one fp32 multiply, then truncation.  Outside [0, 255] the reference's cast is
-// undefined: clamped here (fmaxf drops a NaN: 0).
-__device__ __forceinline__ int quant_lr(float x) { return (int)fminf(fmaxf(__fmul_rn(x, 255.0f), 0.0f), 255.0f); }
-
-// save_image: x.mul(255).add_(0.5).clamp_(0, 255).to(uint8) -- two separately rounded fp32 operations.  A fused multiply-add rounds
-// once and lands on the other side of an integer boundary for inputs next to (k + 0.5) / 255: __fmul_rn / __fadd_rn never contract.
-__device__ __forceinline__ unsigned char quant_sr(float x) {
-  return (unsigned char)(int)fminf(fmaxf(__fadd_rn(__fmul_rn(x, 255.0f), 0.5f), 0.0f), 255.0f);
-}
-
-__device__ __forceinline__ unsigned char clip8(int acc) { return (unsigned char)min(max(acc >> DISPLAY_PRECISION_BITS, 0), 255); }
-
-// Tables (utils/display.py pil_bicubic_tables): per output index 2 + ksize int32 = [first input index, n taps, k_0 .. k_{ksize-1}],
+// Tables (utils/resize.py pil_resample_tables): per output index 2 + ksize int32 = [first input index, n taps, k_0 .. k_{ksize-1}],
 // 22 fraction bits.  Block (band, j): output rows [band * band_rows, +band_rows) of all three sections of selected image j.
 //   phase 1  the horizontal pass of the input rows this band's vertical pass reads -> LDS (uint8, HWC, at most lds_rows rows)
 //   phase 2  the vertical pass from LDS -> section 0
@@ -55,22 +42,15 @@ k_display_triple(const float* __restrict__ in, long in_bs, long in_cs, const flo
   const float* pin = in + (size_t)b * in_bs;
   for (int i = threadIdx.x; i < (y_hi - y_lo) * row_bytes; i += DISPLAY_THREADS) {
     const int row = i / row_bytes, rem = i - row * row_bytes, x = rem / 3, c = rem - x * 3;
-    const int* t = tab_h + (size_t)x * tstride;
-    const int x0 = min(max(t[0], 0), w - 1), n = min(min(t[1], ksize), w - x0);
-    const float* p = pin + (size_t)c * in_cs + (size_t)(y_lo + row) * w + x0;
-    int acc = 1 << (DISPLAY_PRECISION_BITS - 1);
-    for (int k = 0; k < n; ++k) acc += quant_lr(p[k]) * t[2 + k];
-    s_hor[i] = clip8(acc);
+    const float* p = pin + (size_t)c * in_cs + (size_t)(y_lo + row) * w;
+    s_hor[i] = resample_u8(tab_h + (size_t)x * tstride, ksize, 0, w, [p](int k) { return quant_lr(p[k]); });
   }
   __syncthreads();
   for (int i = threadIdx.x; i < (r1 - r0) * row_bytes; i += DISPLAY_THREADS) {
     const int row = i / row_bytes, rem = i - row * row_bytes;
-    const int* t = tab_v + (size_t)(r0 + row) * tstride;
-    const int y0 = min(max(t[0], y_lo), y_hi - 1), n = min(min(t[1], ksize), y_hi - y0);
-    const unsigned char* p = s_hor + (y0 - y_lo) * row_bytes + rem;
-    int acc = 1 << (DISPLAY_PRECISION_BITS - 1);
-    for (int k = 0; k < n; ++k) acc += (int)p[k * row_bytes] * t[2 + k];
-    o[(size_t)(r0 + row) * row_bytes + rem] = clip8(acc);
+    const unsigned char* p = s_hor + rem;
+    o[(size_t)(r0 + row) * row_bytes + rem] =
+        resample_u8(tab_v + (size_t)(r0 + row) * tstride, ksize, y_lo, y_hi, [=](int y) { return (int)p[(y - y_lo) * row_bytes]; });
   }
   const float* psr = sr + (size_t)b * sr_bs;
   const float* phr = hr + (size_t)b * hr_bs;

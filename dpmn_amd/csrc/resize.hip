@@ -45,19 +45,7 @@ k_resize_hor(const unsigned char* __restrict__ packed, long packed_bytes, const 
              long mid_bytes, int W) {
   const Item it = load_item(items, blockIdx.y, packed_bytes, mid_bytes, W);
   if (!it.ok) return;
-  const unsigned char* src = packed + it.in_off;
-  unsigned char* dst = mid + it.mid_off;
-  const int row_bytes = W * 3, tstride = 2 + it.ksize_h;
-  const long total = (long)it.h * row_bytes;
-  for (long i = (long)blockIdx.x * RESIZE_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * RESIZE_THREADS) {
-    const int row = (int)(i / row_bytes), rem = (int)(i - (long)row * row_bytes), x = rem / 3, c = rem - x * 3;
-    const int* t = it.tab_h + (size_t)x * tstride;
-    const int x0 = min(max(t[0], 0), it.w - 1), n = min(min(t[1], it.ksize_h), it.w - x0);
-    const unsigned char* p = src + ((size_t)row * it.w + x0) * 3 + c;
-    int acc = 1 << (RESIZE_PRECISION_BITS - 1);
-    for (int k = 0; k < n; ++k) acc += (int)p[3 * k] * t[2 + k];
-    dst[i] = clip8(acc);
-  }
+  resample_hor_u8(packed + it.in_off, it.h, it.w, mid + it.mid_off, W, it.tab_h, it.ksize_h);
 }
 
 // block (x, b): RESIZE_THREADS of the H x W x 3 output bytes of image b
@@ -73,13 +61,8 @@ k_resize_ver(const unsigned char* __restrict__ mid, long mid_bytes, long packed_
     o[i] = 0;
     return;
   }
-  const int row = i / row_bytes, rem = i - row * row_bytes;
-  const int* t = it.tab_v + (size_t)row * (2 + it.ksize_v);
-  const int y0 = min(max(t[0], 0), it.h - 1), n = min(min(t[1], it.ksize_v), it.h - y0);
-  const unsigned char* p = mid + it.mid_off + (size_t)y0 * row_bytes + rem;
-  int acc = 1 << (RESIZE_PRECISION_BITS - 1);
-  for (int k = 0; k < n; ++k) acc += (int)p[(size_t)k * row_bytes] * t[2 + k];
-  o[i] = clip8(acc);
+  const int row = i / row_bytes;
+  o[i] = resample_ver_u8(mid + it.mid_off, it.h, row_bytes, i - row * row_bytes, row, it.tab_v, it.ksize_v);
 }
 
 __global__ void __launch_bounds__(RESIZE_THREADS)

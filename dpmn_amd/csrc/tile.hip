@@ -50,19 +50,7 @@ k_line_hor(const unsigned char* __restrict__ packed, long packed_bytes, const lo
            long table_ints, unsigned char* __restrict__ ws, long ws_bytes, int lr_h, int lr_w) {
   const LineItem it = load_line_item(items, blockIdx.y, packed_bytes, tables, table_ints, ws_bytes, lr_h, lr_w);
   if (!it.ok) return;
-  const unsigned char* src = packed + it.in_off;
-  unsigned char* dst = ws + it.mid_off;
-  const int row_bytes = it.w_line * 3, tstride = 2 + it.ksize_h;
-  const long total = (long)it.h * row_bytes;
-  for (long i = (long)blockIdx.x * RESIZE_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * RESIZE_THREADS) {
-    const int row = (int)(i / row_bytes), rem = (int)(i - (long)row * row_bytes), x = rem / 3, c = rem - x * 3;
-    const int* t = it.tab_h + (size_t)x * tstride;
-    const int x0 = min(max(t[0], 0), it.w - 1), n = min(min(t[1], it.ksize_h), it.w - x0);
-    const unsigned char* p = src + ((size_t)row * it.w + x0) * 3 + c;
-    int acc = 1 << (RESIZE_PRECISION_BITS - 1);
-    for (int k = 0; k < n; ++k) acc += (int)p[3 * k] * t[2 + k];
-    dst[i] = clip8(acc);
-  }
+  resample_hor_u8(packed + it.in_off, it.h, it.w, ws + it.mid_off, it.w_line, it.tab_h, it.ksize_h);
 }
 
 // block (x, b): a grid-stride walk over the lr_h x w_line_b x 3 line bytes of image b
@@ -73,16 +61,11 @@ k_line_ver(long packed_bytes, const long long* __restrict__ items, const int* __
   if (!it.ok) return;
   const unsigned char* mid = ws + it.mid_off;
   unsigned char* dst = ws + it.line_off;
-  const int row_bytes = it.w_line * 3, tstride = 2 + it.ksize_v;
+  const int row_bytes = it.w_line * 3;
   const long total = (long)lr_h * row_bytes;
   for (long i = (long)blockIdx.x * RESIZE_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * RESIZE_THREADS) {
-    const int row = (int)(i / row_bytes), rem = (int)(i - (long)row * row_bytes);
-    const int* t = it.tab_v + (size_t)row * tstride;
-    const int y0 = min(max(t[0], 0), it.h - 1), n = min(min(t[1], it.ksize_v), it.h - y0);
-    const unsigned char* p = mid + (size_t)y0 * row_bytes + rem;
-    int acc = 1 << (RESIZE_PRECISION_BITS - 1);
-    for (int k = 0; k < n; ++k) acc += (int)p[(size_t)k * row_bytes] * t[2 + k];
-    dst[i] = clip8(acc);
+    const int row = (int)(i / row_bytes);
+    dst[i] = resample_ver_u8(mid, it.h, row_bytes, (int)(i - (long)row * row_bytes), row, it.tab_v, it.ksize_v);
   }
 }
 

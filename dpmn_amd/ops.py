@@ -150,19 +150,6 @@ def collate_u8(img_u8, with_mask):
     return out
 
 
-_DISPLAY_TABLES = {}
-
-
-def _display_tables(insz, outsz, device):
-    """The device copy of utils.display.pil_bicubic_tables(insz, outsz), uploaded once per size pair and device."""
-    key = (insz, outsz, device.type, device.index)
-    t = _DISPLAY_TABLES.get(key)
-    if t is None:
-        from .utils.display import pil_bicubic_tables
-        t = _DISPLAY_TABLES[key] = torch.from_numpy(pil_bicubic_tables(insz, outsz).copy()).to(device)
-    return t
-
-
 def _display_planes(x, what):
     """(tensor, pointer, batch stride, channel stride) of an NCHW fp32 CUDA tensor whose planes are contiguous."""
     if not x.is_cuda:
@@ -199,14 +186,15 @@ def display_triple(image_in, image_out, image_target, sel):
     out = torch.empty(n, 3 * H, W, 3, dtype=torch.uint8, device=a.device)
     if n == 0:
         return out
-    tab_h, tab_v = _display_tables(w, W, a.device), _display_tables(h, H, a.device)
+    tabs = _resize_tables({(w, W), (h, H)}, a.device)
+    tab_h, tab_v = tabs[(w, W)], tabs[(h, H)]
     check(lib.dpmn_display_triple_u8(pa, abs_, acs, po, obs, ocs, pt, tbs, tcs, _i32(sel, "display_triple"), n, tab_h.data_ptr(),
                                      tab_v.data_ptr(), tab_h.shape[1] - 2, out.data_ptr(), B, h, w, H, W, stream()))
     return out
 
 
 _RESIZE_TABLES = {}
-RESIZE_TABLES_MAX = 4096      # device tables of the ragged resize kept per (insz, outsz, device); the oldest are dropped beyond this
+RESIZE_TABLES_MAX = 4096      # device tables kept per (insz, outsz, device); the oldest are dropped beyond this
 
 
 def _resize_tables(pairs, device):
@@ -226,22 +214,33 @@ def _resize_tables(pairs, device):
     return {p: _RESIZE_TABLES[key] for p, key in keys.items()}
 
 
+def _ragged_batch(packed, meta, what):
+    """The checks every op on a pack_ragged batch shares -> meta as an int64 (B, 3) numpy array of (byte offset, h, w).  packed: the device buffer, or its size in bytes where the op only writes (degrade_noise)."""
+    import numpy as np
+    from .utils.resize import MAX_SIDE
+    if not isinstance(packed, int) and (not torch.is_tensor(packed) or not packed.is_cuda or packed.dtype != torch.uint8 or packed.dim() != 1
+                                        or not packed.is_contiguous()):
+        raise _abi.DpmnError("%s: a contiguous 1-D uint8 CUDA tensor is required (the uploaded pack_ragged buffer); there is no CPU "
+                             "fallback" % what)
+    m = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta)
+    if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] == 0 or m.shape[0] > 65535 or m.dtype.kind not in "iu":
+        raise _abi.DpmnError("%s: meta must be a non-empty integer (B, 3) array of (byte offset, h, w), B <= 65535" % what)
+    m = m.astype(np.int64)
+    off, hs, ws = m[:, 0], m[:, 1], m[:, 2]
+    nbytes = packed if isinstance(packed, int) else packed.numel()
+    if hs.min() < 1 or ws.min() < 1 or hs.max() > MAX_SIDE or ws.max() > MAX_SIDE or off.min() < 0 or int((off + hs * ws * 3).max()) > nbytes:
+        raise _abi.DpmnError("%s: meta names an image outside the packed buffer or with a side outside 1 .. %d" % (what, MAX_SIDE))
+    return m
+
+
 def _resize_ragged_plan(packed, meta, H, W):
     """Checks and per-call device data of resize_ragged_u8 -> (B, largest h, items (B, 8) int64 on the device, workspace)."""
     import numpy as np
-    if not torch.is_tensor(packed) or not packed.is_cuda or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
-        raise _abi.DpmnError("resize_ragged_u8: a contiguous 1-D uint8 CUDA tensor is required (the uploaded pack_ragged buffer); "
-                             "there is no CPU fallback")
-    m = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta)
-    if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] == 0 or m.dtype.kind not in "iu":
-        raise _abi.DpmnError("resize_ragged_u8: meta must be a non-empty integer (B, 3) array of (byte offset, h, w)")
-    m = m.astype(np.int64)
     from .utils.resize import MAX_SIDE
+    m = _ragged_batch(packed, meta, "resize_ragged_u8")
     if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
         raise _abi.DpmnError("resize_ragged_u8: output size %d x %d outside 1 .. %d" % (H, W, MAX_SIDE))
-    off, hs, ws = m[:, 0], m[:, 1], m[:, 2]
-    if hs.min() < 1 or ws.min() < 1 or hs.max() > MAX_SIDE or ws.max() > MAX_SIDE or off.min() < 0 or int((off + hs * ws * 3).max()) > packed.numel():
-        raise _abi.DpmnError("resize_ragged_u8: meta names an image outside the packed buffer or with a side outside 1 .. %d" % MAX_SIDE)
+    hs, ws = m[:, 1], m[:, 2]
     B, dev = m.shape[0], packed.device
     items = np.empty((B, 8), np.int64)
     items[:, :3] = m
@@ -274,15 +273,8 @@ def _degrade_plan(packed, meta, what):
     """Checks and per-call host data of degrade_ragged_u8 / degrade_noise -> (meta as int64 (B, 3), items (B, 4) int64 [byte offset, h,
     w, first tile], tiles (n_tiles, 3) int32 [image, tile row, tile column]); packed: the device buffer or its size in bytes."""
     import numpy as np
-    from .utils.resize import MAX_SIDE
-    m = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta)
-    if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] == 0 or m.shape[0] > 65535 or m.dtype.kind not in "iu":
-        raise _abi.DpmnError("%s: meta must be a non-empty integer (B, 3) array of (byte offset, h, w), B <= 65535" % what)
-    m = m.astype(np.int64)
-    off, hs, ws = m[:, 0], m[:, 1], m[:, 2]
-    nbytes = packed if isinstance(packed, int) else packed.numel()
-    if hs.min() < 1 or ws.min() < 1 or hs.max() > MAX_SIDE or ws.max() > MAX_SIDE or off.min() < 0 or int((off + hs * ws * 3).max()) > nbytes:
-        raise _abi.DpmnError("%s: meta names an image outside the packed buffer or with a side outside 1 .. %d" % (what, MAX_SIDE))
+    m = _ragged_batch(packed, meta, what)
+    hs, ws = m[:, 1], m[:, 2]
     th, tw = -(-hs // DEGRADE_TILE), -(-ws // DEGRADE_TILE)
     first = np.concatenate(([0], np.cumsum(th * tw)))
     if first[-1] >= 2 ** 31:
@@ -303,9 +295,6 @@ def degrade_ragged_u8(packed, meta, params, z=None, seed=0):
     packed.numel() standard-normal values (the noise of byte i at index i), or None: generated in the kernel from `seed` (the field
     degrade_noise(seed, meta) returns).  The same arguments give the same bytes on every run."""
     import numpy as np
-    if not torch.is_tensor(packed) or not packed.is_cuda or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
-        raise _abi.DpmnError("degrade_ragged_u8: a contiguous 1-D uint8 CUDA tensor is required (the uploaded pack_ragged buffer); "
-                             "there is no CPU fallback")
     m, items, tiles = _degrade_plan(packed, meta, "degrade_ragged_u8")
     B, dev = m.shape[0], packed.device
     p = np.ascontiguousarray(params.cpu().numpy() if torch.is_tensor(params) else params, dtype=np.float32)
@@ -377,18 +366,10 @@ def _resize_windows_plan(packed, meta, lr_h, lr_w):
     import numpy as np
     from .utils.resize import MAX_SIDE, pil_resample_tables
     from .utils.tile import line_width, window_plan
-    if not torch.is_tensor(packed) or not packed.is_cuda or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
-        raise _abi.DpmnError("resize_windows_u8: a contiguous 1-D uint8 CUDA tensor is required (the uploaded pack_ragged buffer); "
-                             "there is no CPU fallback")
-    m = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta)
-    if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] == 0 or m.shape[0] > 65535 or m.dtype.kind not in "iu":
-        raise _abi.DpmnError("resize_windows_u8: meta must be a non-empty integer (B, 3) array of (byte offset, h, w), B <= 65535")
-    m = m.astype(np.int64)
+    m = _ragged_batch(packed, meta, "resize_windows_u8")
     if not (1 <= lr_h <= MAX_SIDE and 2 <= lr_w <= MAX_SIDE):
         raise _abi.DpmnError("resize_windows_u8: window size %d x %d outside 1 .. %d" % (lr_h, lr_w, MAX_SIDE))
-    off, hs, ws = m[:, 0], m[:, 1], m[:, 2]
-    if hs.min() < 1 or ws.min() < 1 or hs.max() > MAX_SIDE or ws.max() > MAX_SIDE or off.min() < 0 or int((off + hs * ws * 3).max()) > packed.numel():
-        raise _abi.DpmnError("resize_windows_u8: meta names an image outside the packed buffer or with a side outside 1 .. %d" % MAX_SIDE)
+    hs, ws = m[:, 1], m[:, 2]
     try:
         wl = np.array([line_width(int(h), int(w), lr_h, lr_w) for h, w in zip(hs, ws)], np.int64)
     except ValueError as e:

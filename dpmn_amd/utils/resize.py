@@ -1,22 +1,25 @@
 """Host side of the ragged-batch resize (``ops.resize_ragged_u8``, csrc/resize.hip): PIL's fixed-point bicubic resample for ANY pair
 of sizes -- the coefficient tables, a numpy restatement of the two passes (the CPU reference of the kernel) and the packing of a
-batch of images of different sizes into one buffer.  ``utils/display.py`` holds the enlarging case (5 taps) that the comparison
-images use; shrinking is the same algorithm of libImaging/Resample.c with the support widened by the scale factor:
-ksize = 2 * ceil(2 * scale) + 1 taps.  No GPU needed: importable on any machine.
+batch of images of different sizes into one buffer.  The one owner of the resample core: the comparison images (``utils/display.py``,
+enlarging only: 5 taps) and the window cutter (``utils/tile.py``) take it from here.
+
+PIL's ``Image.resize((W, H), BICUBIC)`` on uint8 (libImaging/Resample.c) is two passes, horizontal first, the intermediate rounded
+to uint8.  Per output index: a window [xmin, xmin + n) of input pixels and n weights of the a = -0.5 cubic over a support of
+2 * max(scale, 1), normalised in double and converted to int with 22 fraction bits; a pixel is clip8((2^21 + sum in * k) >> 22).
+Shrinking widens the support by the scale factor: ksize = 2 * ceil(2 * scale) + 1 taps.  No GPU needed: importable on any machine.
 """
 import functools
 import math
 
 import numpy as np
 
-from .display import PRECISION_BITS, _resample_axis0
-
+PRECISION_BITS = 32 - 8 - 2      # Resample.c: 8 bits of pixel, 2 bits of head room for the overshoot of the cubic
 MAX_SIDE = 8192               # per image side; 255 * sum |k| + 2^21 stays far below 2^31 for every pair up to here (tests/test_resize.py)
 MAX_PACKED_BYTES = 2 ** 31 - 1
 
 
 def _bicubic(x, a=-0.5):
-    """display._bicubic on an array, the same operations in the same order per branch."""
+    """Resample.c's bicubic_filter on an array, the same operations in the same order per branch."""
     x = np.abs(x)
     near = ((a + 2.0) * x - (a + 3.0)) * x * x + 1
     far = (((x - 5) * x + 8) * x - 4) * a
@@ -28,7 +31,7 @@ def pil_resample_tables(insz, outsz):
     """precompute_coeffs + normalize_coeffs_8bpc of Resample.c for one axis and any positive sizes -> int32 (outsz, 2 + ksize),
     read-only: per output index [xmin, n, k_0 .. k_{ksize-1}] (k_j = 0 for j >= n), 22 fraction bits.  Float64 in PIL's operation
     order: the weight sum grows tap by tap, each tap is divided by it, then rounded with +-0.5.  Vectorised over the output index
-    (a loop over the taps only).  For insz <= outsz the rows are display.pil_bicubic_tables(insz, outsz)."""
+    (a loop over the taps only); tests/helpers.py restates it per index.  Cached per size pair."""
     insz, outsz = int(insz), int(outsz)
     if insz < 1 or outsz < 1:
         raise ValueError("pil_resample_tables: sizes must be positive, got %d -> %d" % (insz, outsz))
@@ -58,14 +61,27 @@ def pil_resample_tables(insz, outsz):
     return tab
 
 
+def resample_axis0(img, tab):
+    """One pass along axis 0 of a uint8 array with a table of pil_resample_tables (int64 accumulation: no assumption on the sums)."""
+    src = img.astype(np.int64)
+    out = np.empty((tab.shape[0],) + img.shape[1:], np.uint8)
+    for xx in range(tab.shape[0]):
+        xmin, n = int(tab[xx, 0]), int(tab[xx, 1])
+        k = tab[xx, 2:2 + n].astype(np.int64).reshape((n,) + (1,) * (img.ndim - 1))
+        acc = (1 << (PRECISION_BITS - 1)) + (src[xmin:xmin + n] * k).sum(0)
+        out[xx] = np.clip(acc >> PRECISION_BITS, 0, 255)
+    return out
+
+
 def pil_resize_u8(img, out_h, out_w):
     """img (h, w[, C]) uint8 -> (out_h, out_w[, C]) uint8 = np.asarray(Image.fromarray(img).resize((out_w, out_h), BICUBIC)) for any
     sizes, bit for bit (tests/test_resize.py): horizontal pass, uint8 intermediate, vertical pass; an axis whose sizes are equal goes
-    through its (identity) table like any other.  The CPU reference of ops.resize_ragged_u8."""
+    through its (identity) table like any other.  The CPU reference of ops.resize_ragged_u8 and of the LR rows of
+    ops.display_triple."""
     img = np.ascontiguousarray(img, np.uint8)
     h, w = img.shape[:2]
-    hor = np.swapaxes(_resample_axis0(np.swapaxes(img, 0, 1), pil_resample_tables(w, out_w)), 0, 1)
-    return _resample_axis0(hor, pil_resample_tables(h, out_h))
+    hor = np.swapaxes(resample_axis0(np.swapaxes(img, 0, 1), pil_resample_tables(w, out_w)), 0, 1)
+    return resample_axis0(hor, pil_resample_tables(h, out_h))
 
 
 def check_image(im, what="image"):

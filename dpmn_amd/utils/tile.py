@@ -9,8 +9,8 @@ windows of an image are consecutive, their starts do not decrease, the first is 
 """
 import numpy as np
 
-from .display import _resample_axis0, quantize_sr
-from .resize import MAX_SIDE, check_image, pil_resample_tables
+from .display import quantize_sr
+from .resize import MAX_SIDE, check_image, pil_resize_u8
 
 LR_H, LR_W = 16, 64
 STRIDE = 48               # the largest step between two windows: neighbours share at least lr_w - STRIDE = 16 LR columns
@@ -69,15 +69,12 @@ def plan_lines(plan, lr_w=LR_W):
 
 def resize_windows_np(images, lr_size=(LR_H, LR_W)):
     """A list of (h, w, 3) uint8 images -> (windows (T, lr_h, lr_w, 3) uint8, plan): every image resized to (lr_h, line_width) =
-    np.asarray(Image.fromarray(img).resize((w_line, lr_h), BICUBIC)) -- horizontal pass, uint8 intermediate, vertical pass with the
-    tables of pil_resample_tables -- and cut at window_plan's starts.  The CPU reference of ops.resize_windows_u8."""
+    np.asarray(Image.fromarray(img).resize((w_line, lr_h), BICUBIC)) (resize.pil_resize_u8) and cut at window_plan's starts.  The CPU reference of ops.resize_windows_u8."""
     lr_h, lr_w = lr_size
     windows, plan = [], []
     for b, im in enumerate(images):
         h, w, w_line = check_line(im, lr_size, "image %d" % b)
-        img = np.ascontiguousarray(im, np.uint8)
-        hor = np.swapaxes(_resample_axis0(np.swapaxes(img, 0, 1), pil_resample_tables(w, w_line)), 0, 1)
-        line = _resample_axis0(hor, pil_resample_tables(h, lr_h))
+        line = pil_resize_u8(im, lr_h, w_line)
         for x0 in window_plan(w_line, lr_w):
             windows.append(line[:, x0:x0 + lr_w])
             plan.append((b, x0))

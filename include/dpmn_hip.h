@@ -464,7 +464,7 @@ int dpmn_collate_u8_f32(const unsigned char* img, float* out, int B, int H, int 
  *   rows [2H, 3H)  image_target (B, >=3, H, W), the same
  * Channels 0..2 are read through the batch / channel strides (in floats; planes are contiguous), so a channel-sliced view of a
  * 4-channel masked batch needs no copy.  tab_h (W, 2 + ksize) / tab_v (H, 2 + ksize) device int32: per output column / row
- * [first input index, taps, k_0 ..], 22 fraction bits, built on the host in float64 (utils/display.py pil_bicubic_tables);
+ * [first input index, taps, k_0 ..], 22 fraction bits, built on the host in float64 (utils/resize.py pil_resample_tables);
  * ksize = 5 (bicubic, h <= H and w <= W: the LR image is only enlarged).  W <= 2048. */
 int dpmn_display_triple_u8(const float* image_in, long in_batch_stride, long in_chan_stride, const float* image_out, long out_batch_stride,
                            long out_chan_stride, const float* image_target, long tgt_batch_stride, long tgt_chan_stride, const int* sel,

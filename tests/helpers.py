@@ -1,4 +1,5 @@
 """Shared test helpers: rebuild synthetic state dicts from a golden manifest."""
+import math
 import os
 
 import numpy as np
@@ -250,3 +251,43 @@ def max_abs_err(a, b):
 def l2_rel(a, b):
     a, b = torch.as_tensor(a).float().cpu().double(), torch.as_tensor(b).float().cpu().double()
     return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+def _bicubic(x, a=-0.5):
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def pil_bicubic_tables(insz, outsz):
+    """precompute_coeffs + normalize_coeffs_8bpc of Resample.c for one axis, one output index at a time in Python floats -> int32
+    (outsz, 2 + ksize): per output index [xmin, n, k_0 .. k_{ksize-1}] (k_j = 0 for j >= n).  The independent restatement that
+    dpmn_amd.utils.resize.pil_resample_tables (vectorised) is compared against."""
+    insz, outsz = int(insz), int(outsz)
+    if insz < 1 or outsz < 1:
+        raise ValueError("pil_bicubic_tables: sizes must be positive, got %d -> %d" % (insz, outsz))
+    scale = filterscale = float(insz) / outsz
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support = 2.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    tab = np.zeros((outsz, 2 + ksize), np.int32)
+    for xx in range(outsz):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), insz) - xmin
+        k = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for w in k:
+            ww += w
+        if ww != 0.0:
+            k = [w / ww for w in k]
+        tab[xx, 0], tab[xx, 1] = xmin, xmax
+        for x, w in enumerate(k):
+            tab[xx, 2 + x] = int(-0.5 + w * (1 << 22)) if w < 0 else int(0.5 + w * (1 << 22))
+    tab.setflags(write=False)
+    return tab

@@ -1,11 +1,11 @@
-"""CPU checks of the comparison-image path (dpmn_amd/utils/display.py; tripple_display / test_display, interfaces/base.py:275-326 of
-the reference): the coefficient tables the kernel reads reproduce PIL's bicubic resize exactly, the / 255 round trip of the enlarged
+"""CPU checks of the comparison-image path (dpmn_amd/utils/display.py on the resample core of utils/resize.py; tripple_display /
+test_display, interfaces/base.py:275-326 of the reference): the coefficient tables the kernel reads reproduce PIL's bicubic resize exactly, the / 255 round trip of the enlarged
 LR image is the identity, the file-name rule, and the fixture tests/golden/display.npz against the numpy restatement."""
 import numpy as np
 import pytest
 import torch
 
-from dpmn_amd.utils import display as dsp
+from dpmn_amd.utils import display as dsp, resize
 from helpers import load_golden
 
 CASES = [(16, 64, 32, 128),       # config 1
@@ -20,14 +20,14 @@ def test_tables_through_numpy_two_pass_equal_pil_resize(h, w, H, W):
     rng = np.random.RandomState(h * 1000 + W)
     for img in (rng.randint(0, 256, (h, w, 3)).astype(np.uint8), (rng.randint(0, 2, (h, w, 3)) * 255).astype(np.uint8)):
         ref = np.asarray(Image.fromarray(img).resize((W, H), Image.BICUBIC))
-        got = dsp.pil_bicubic_resize_u8(img, H, W)
+        got = resize.pil_resize_u8(img, H, W)
         assert got.shape == ref.shape and got.dtype == np.uint8
         assert int((got != ref).sum()) == 0
 
 
 def test_tables_layout_bounds_and_cache():
     for insz, outsz in ((16, 32), (64, 128), (6, 16), (10, 24), (16, 16), (256, 512)):
-        t = dsp.pil_bicubic_tables(insz, outsz)
+        t = resize.pil_resample_tables(insz, outsz)
         assert t.dtype == np.int32 and t.shape == (outsz, 7) and not t.flags.writeable
         assert (t[:, 0] >= 0).all() and (t[:, 1] >= 1).all() and (t[:, 0] + t[:, 1] <= insz).all()
         assert (np.diff(t[:, 0]) >= 0).all() and (np.diff(t[:, 0] + t[:, 1]) >= 0).all()      # the kernel's row bands rely on it
@@ -35,11 +35,9 @@ def test_tables_layout_bounds_and_cache():
             assert (row[2 + row[1]:] == 0).all()
             assert abs(int(row[2:].sum()) - (1 << 22)) <= 4            # normalised weights, 22 fraction bits
             assert 255 * int(np.abs(row[2:].astype(np.int64)).sum()) + (1 << 21) < 2 ** 31      # int32 accumulation is enough
-        assert dsp.pil_bicubic_tables(insz, outsz) is t
-    eq = dsp.pil_bicubic_tables(16, 16)
+        assert resize.pil_resample_tables(insz, outsz) is t
+    eq = resize.pil_resample_tables(16, 16)
     assert all(int(eq[i, 2 + i - eq[i, 0]]) == 1 << 22 for i in range(16))      # equal size: the identity
-    with pytest.raises(NotImplementedError):
-        dsp.pil_bicubic_tables(32, 16)
 
 
 def test_div255_round_trip_is_the_identity():

@@ -10,7 +10,7 @@ import torch
 from PIL import Image
 
 from dpmn_amd.utils import display, resize
-from helpers import load_golden
+from helpers import load_golden, record
 from test_dataset import _fake_env
 from test_resize import PAIRS, images, pil_resize
 
@@ -75,6 +75,36 @@ def test_single_image_batch_and_rejections(dev, ragged):
         ops.resize_ragged_u8(packed.to(dev)[:-1], meta, 32, 128)            # the meta points past the buffer
     with pytest.raises(_abi.DpmnError):
         ops.quantize_sr_u8(torch.zeros(1, 3, 4, 4))
+
+
+def test_resize_windows_and_display_share_one_pass(dev):
+    """One resample pass serves three ops: each image, random and 0 / 255 (overshoot clipped in both passes), -> 16 x 64 through
+    ops.resize_ragged_u8, ops.resize_windows_u8 (line_width == 64: one window per image) and rows [0, 16) of ops.display_triple on
+    (u8 + 0.25) / 255, which quantize_lr maps back to u8.  16 x 64 goes through the identity tables.  Every result equals
+    utils.resize.pil_resize_u8, byte for byte."""
+    from dpmn_amd import ops
+    from dpmn_amd.utils.tile import line_width
+    H, W = 16, 64
+    shapes = [(9, 30), (3, 5), (16, 64)]
+    assert [line_width(h, w, H, W) for h, w in shapes] == [W] * 3
+    k = np.arange(256, dtype=np.uint8)
+    assert np.array_equal(display.quantize_lr((k.astype(np.float32) + np.float32(0.25)) / np.float32(255)), k)
+    differing = 0
+    for kind in (0, 1):
+        imgs = [images(s, 70 + i)[kind] for i, s in enumerate(shapes)]
+        refs = np.stack([resize.pil_resize_u8(a, H, W) for a in imgs])
+        packed, meta = resize.pack_ragged(imgs)
+        packed = packed.to(dev)
+        ragged = ops.resize_ragged_u8(packed, meta, H, W).cpu().numpy()
+        windows, plan = ops.resize_windows_u8(packed, meta, H, W)
+        assert plan == [(b, 0) for b in range(len(imgs))]
+        zeros = torch.zeros(1, 3, H, W, device=dev)
+        triple = np.stack([ops.display_triple(((torch.from_numpy(a).to(dev).float() + 0.25) / 255).permute(2, 0, 1)[None], zeros, zeros,
+                                              [0])[0, :H].cpu().numpy() for a in imgs])
+        for got in (ragged, windows.cpu().numpy(), triple):
+            assert got.shape == refs.shape and got.dtype == np.uint8
+            differing += int((got != refs).sum())
+    assert record("resize", "one pass: bytes differing from pil_resize_u8 (ragged, windows, display; 3 images x 2 kinds)", differing, 0) == 0
 
 
 @pytest.mark.parametrize("mask", [True, False])

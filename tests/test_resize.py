@@ -6,7 +6,8 @@ import pytest
 import torch
 from PIL import Image
 
-from dpmn_amd.utils import display, resize
+from dpmn_amd.utils import resize
+from helpers import pil_bicubic_tables
 
 # (h, w) -> (H, W): shrinking and enlarging on either axis, mixed, extreme aspect ratios, one pixel, equal sizes
 PAIRS = [((43, 157), (32, 128)), ((19, 73), (16, 64)), ((55, 185), (32, 128)), ((23, 85), (16, 64)), ((7, 300), (16, 64)),
@@ -33,8 +34,9 @@ def test_pil_resize_u8_equals_pil(src, dst):
 
 
 def test_tables_equal_the_enlarging_tables_and_are_monotone_and_bounded():
-    for insz, outsz in [(1, 1), (1, 16), (5, 32), (16, 16), (16, 32), (19, 64), (64, 64), (64, 128), (73, 128)]:
-        assert np.array_equal(resize.pil_resample_tables(insz, outsz), display.pil_bicubic_tables(insz, outsz))
+    """The vectorised tables against the per-index restatement of Resample.c (helpers.pil_bicubic_tables), then their invariants."""
+    for insz, outsz in [(1, 1), (1, 16), (5, 32), (16, 16), (16, 32), (19, 64), (64, 64), (64, 128), (73, 128), (157, 128), (8192, 1)]:
+        assert np.array_equal(resize.pil_resample_tables(insz, outsz), pil_bicubic_tables(insz, outsz))
     sizes = sorted({s for pair in PAIRS for s in pair[0]} | {2, 3, 8192})      # 8192 -> 1: the widest kernel pack_ragged admits
     for insz in sizes:
         for outsz in ((1, 128) if insz == 8192 else (1, 16, 32, 64, 128)):

@@ -1066,7 +1066,7 @@ def gen_display():
          quantisation edges: SR / HR values k / 255 and (k + 0.5) / 255, LR values k / 255, each exact and one ulp up and down, all k
       b  6x10 -> 16x24 (non-integer ratio)      c  64x256 -> 128x512 (config 4), blocky content so that the file stays small"""
     from PIL import Image
-    from dpmn_amd.utils import display as dsp
+    from dpmn_amd.utils import display as dsp, resize as rsz
     rng = np.random.RandomState(20240611)
     f32 = np.float32
 
@@ -1110,7 +1110,7 @@ def gen_display():
     # overshoot: unclipped sums of either pass below 0 / above 255 on the binary image
     lo = hi = 0
     u8 = dsp.quantize_lr(lr[1, :3]).transpose(1, 2, 0).astype(np.int64)
-    th, tv = dsp.pil_bicubic_tables(64, 128), dsp.pil_bicubic_tables(16, 32)
+    th, tv = rsz.pil_resample_tables(64, 128), rsz.pil_resample_tables(16, 32)
     hor = np.stack([(1 << 21) + sum(u8[:, th[x, 0] + j] * int(th[x, 2 + j]) for j in range(th[x, 1])) for x in range(128)], 1) >> 22
     lo, hi = lo + int((hor < 0).sum()), hi + int((hor > 255).sum())
     hor = np.clip(hor, 0, 255)
