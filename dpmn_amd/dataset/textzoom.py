@@ -10,7 +10,9 @@ reference calls, so `resizeNormalize` is not a restatement of an algorithm but t
 kept in the collated tuple: the YUV copies (cv2.cvtColor, read by nothing on the SR path), imgaug augmenters (constructed but
 never applied by these classes).  Manmade degradation and cutblur (dataset.py:422-489, 622-637; main.py --manmade_degrade / --cutblur)
 do not run per image on the host here: the dataset hands out the HR image in the LR position, the collate function packs the HR pixels
-once and `sr_batches` synthesises the LR batch on the GPU (ops.degrade_ragged_u8, then the ragged resize).  `lmdb` itself is imported lazily:
+once and `sr_batches` synthesises the LR batch on the GPU (ops.degrade_ragged_u8, then the ragged resize).  The JPEG stage the reference
+left commented out on the resized image (dataset.py:559 JPEG_compress, :1298-1300; main.py --jpeg_degrade) runs there too, on the resized
+uint8 LR batch (ops.jpeg_roundtrip_u8), with a quality drawn per image.  `lmdb` itself is imported lazily:
 it is not installed in the build image, so the reader is exercised in tests/ through an injected environment object with the
 same `begin().get(key)` protocol, over images encoded the way TextZoom stores them.
 """
@@ -123,16 +125,28 @@ class alignCollate_realWTLAMask(object):
     bicubic resize; tests/test_gpu_resize.py) before it finishes them.
     degrade=True (ours, needs gpu_resize): the LR images are synthesised from the HR images -- the HR pixels are packed ONCE, position
     2 carries the same pair as position 0 and `sr_batches` degrades them on the GPU (ops.degrade_ragged_u8; cutblur=True: with the
-    reference's cutblur).  The random draws happen in sr_batches, in the main process, not in the loader's workers."""
+    reference's cutblur).  The random draws happen in sr_batches, in the main process, not in the loader's workers.
+    jpeg=(lo, hi, prob) (ours, needs degrade): with probability prob a synthesised LR image, after its resize, goes through a JPEG of a
+    quality drawn from lo .. hi (ops.jpeg_roundtrip_u8; the reference's JPEG_compress, dataset.py:559, fixes 40)."""
 
     def __init__(self, imgH=64, imgW=256, down_sample_scale=4, keep_ratio=False, min_ratio=1, mask=False, alphabet=53, train=True,
-                 y_domain=False, gpu_finish=False, gpu_resize=False, degrade=False, cutblur=False):
+                 y_domain=False, gpu_finish=False, gpu_resize=False, degrade=False, cutblur=False, jpeg=None):
         if degrade and not gpu_resize:
             raise ValueError("alignCollate_realWTLAMask: degrade=True needs gpu_resize=True (the LR images are made on the GPU from the "
                              "packed HR pixels)")
         if cutblur and not degrade:
             raise ValueError("alignCollate_realWTLAMask: cutblur=True needs degrade=True (cutblur replaces columns of the LR image by the "
                              "HR image's, which needs equal native sizes; paired TextZoom crops do not have them)")
+        if jpeg is not None and not degrade:
+            raise ValueError("alignCollate_realWTLAMask: jpeg=(lo, hi, prob) needs degrade=True (the JPEG artefacts are put on the LR "
+                             "images that are synthesised on the GPU; paired TextZoom LR crops are used as they are)")
+        if jpeg is not None:
+            lo, hi, prob = jpeg
+            if not (1 <= int(lo) <= int(hi) <= 100 and 0.0 <= float(prob) <= 1.0):
+                raise ValueError("alignCollate_realWTLAMask: jpeg=(lo, hi, prob) needs 1 <= lo <= hi <= 100 and 0 <= prob <= 1, got %r"
+                                 % (jpeg,))
+            jpeg = (int(lo), int(hi), float(prob))
+        self.jpeg = jpeg
         self.imgH, self.imgW, self.down_sample_scale, self.mask = imgH, imgW, down_sample_scale, mask
         self.gpu_finish, self.gpu_resize, self.degrade, self.cutblur = gpu_finish, gpu_resize, bool(degrade), bool(cutblur)
         self.alphabet = "0123456789abcdefghijklmnopqrstuvwxyz"
@@ -196,11 +210,13 @@ def resize_on_gpu(pair, size, mask, device):
     return ops.collate_u8(ops.resize_ragged_u8(packed.to(device, non_blocking=True), meta, size[0], size[1]), mask)
 
 
-def degrade_on_gpu(pair, size, scale, mask, device, cutblur=False, rng=None):
+def degrade_on_gpu(pair, size, scale, mask, device, cutblur=False, rng=None, jpeg=None):
     """(packed, meta) of a degrade collate (the HR pixels) -> (images_hr (B, 3 + mask, H, W), images_lr (B, 3 + mask, H / scale,
     W / scale)) float on `device`, size = (H, W): one upload, the degradation of the ragged batch at the images' own sizes
     (ops.degrade_ragged_u8: the parameters of utils.degrade.draw_params and one 63-bit noise seed, both drawn from `rng`, Python's
-    `random` by default), the two ragged resizes and the collate kernel."""
+    `random` by default), the two ragged resizes and the collate kernel.  jpeg = (lo, hi, prob): the resized LR batch, and only it,
+    goes through ops.jpeg_roundtrip_u8 with the qualities of utils.jpeg.draw_jpeg, drawn from `rng` AFTER the draws above; with
+    jpeg=None not one more draw is made."""
     import random
     from .. import ops
     from ..utils.degrade import draw_params
@@ -211,8 +227,11 @@ def degrade_on_gpu(pair, size, scale, mask, device, cutblur=False, rng=None):
     packed = packed.to(device, non_blocking=True)
     low = ops.degrade_ragged_u8(packed, meta, params, seed=seed)
     H, W = size
-    return (ops.collate_u8(ops.resize_ragged_u8(packed, meta, H, W), mask),
-            ops.collate_u8(ops.resize_ragged_u8(low, meta, H // scale, W // scale), mask))
+    low = ops.resize_ragged_u8(low, meta, H // scale, W // scale)
+    if jpeg is not None:
+        from ..utils.jpeg import draw_jpeg
+        ops.jpeg_roundtrip_u8(low, draw_jpeg(meta.shape[0], jpeg[0], jpeg[1], jpeg[2], rng=rng), out=low)
+    return ops.collate_u8(ops.resize_ragged_u8(packed, meta, H, W), mask), ops.collate_u8(low, mask)
 
 
 def sr_batches(loader, device=None, mask=None, size=None):
@@ -244,7 +263,8 @@ def sr_batches(loader, device=None, mask=None, size=None):
                 size = (col.imgH, col.imgW, col.down_sample_scale)
             H, W, scale = size
             if degrade:
-                hr, lr = degrade_on_gpu(hr, (H, W), scale, mask, device, cutblur=col.cutblur, rng=random.Random(pass_key + j))
+                hr, lr = degrade_on_gpu(hr, (H, W), scale, mask, device, cutblur=col.cutblur, rng=random.Random(pass_key + j),
+                                            jpeg=getattr(col, "jpeg", None))
             else:
                 hr, lr = resize_on_gpu(hr, (H, W), mask, device), resize_on_gpu(lr, (H // scale, W // scale), mask, device)
         elif hr.dtype == torch.uint8:

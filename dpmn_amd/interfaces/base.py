@@ -17,6 +17,7 @@ import torch
 from ..model import pgrm, cmm, tsrn, tatt, tbsrn
 from ..model.native import frozen as _frozen
 from ..utils import ssim_psnr
+from ..utils.jpeg import jpeg_setting
 
 
 def parse_list(s):
@@ -46,8 +47,9 @@ def _val_weights(config, key, path, what):
 # holds tensors and plain Python values only, so it loads with torch.load(weights_only=True).
 TRAIN_STATE_VERSION = 1
 FINGERPRINT_FIELDS = ("arch", "stu_iter_b1", "stu_iter_b2", "sr_share", "patch_size", "embed_dim", "depths", "num_heads", "window_size",
-                      "window_num", "mlp_ratio", "height", "width", "manmade_degrade", "cutblur", "train_hr_dir")
-DATA_FIELDS = ("manmade_degrade", "cutblur", "train_hr_dir")      # booleans; a state written before they existed has them off
+                      "window_num", "mlp_ratio", "height", "width", "manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade")
+# booleans, and jpeg_degrade: None or [lo, hi, prob]; a state written before they existed has them off
+DATA_FIELDS = ("manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade")
 
 
 def state_fingerprint(args, config):
@@ -60,6 +62,8 @@ def state_fingerprint(args, config):
     # where the LR images come from: a run with synthesised LR images only continues a run of the same kind
     fp["manmade_degrade"], fp["cutblur"] = degrade_flags(args)
     fp["train_hr_dir"] = bool(getattr(args, "train_hr_dir", None))
+    jpeg = jpeg_setting(args)
+    fp["jpeg_degrade"] = None if jpeg is None else list(jpeg)
     return fp
 
 
@@ -68,9 +72,16 @@ def degrade_flags(args):
     return bool(getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None)), bool(getattr(args, "cutblur", False))
 
 
+def _data_field(v):
+    """A DATA_FIELDS value as it is compared: off (absent, None, False) -> None, a flag -> True, a setting -> its values."""
+    if not v:
+        return None
+    return True if isinstance(v, bool) else list(v)
+
+
 def check_fingerprint(saved, current, path=""):
     for k in FINGERPRINT_FIELDS:
-        if (bool(saved.get(k)) != bool(current.get(k))) if k in DATA_FIELDS else (saved.get(k) != current.get(k)):
+        if (_data_field(saved.get(k)) != _data_field(current.get(k))) if k in DATA_FIELDS else (saved.get(k) != current.get(k)):
             raise ValueError("dpmn_amd: training state %s was written by a run with %s = %r, this run has %s = %r"
                              % (path, k, saved.get(k), k, current.get(k)))
 
@@ -163,7 +174,7 @@ class TextBase(object):
 
     # ------------------------------------------------------------------ data (base.py:85-125)
     def _loader(self, dirs, test, shuffle, drop_last, shard=False, gpu_finish=True, gpu_resize=False, degrade=False, cutblur=False,
-                hr_dir=None):
+                hr_dir=None, jpeg=None):
         """shard=True (training under torch.distributed): every rank walks its own 1/world of a per-epoch permutation
         (DistributedSampler, call `self.train_sampler.set_epoch(epoch)`) with batch_size // world samples per step, so the
         GLOBAL batch stays config.TRAIN.batch_size at the configured learning rate -- nn.DataParallel's scatter of one batch
@@ -173,7 +184,8 @@ class TextBase(object):
         degrade=True (get_train_data with main.py --manmade_degrade; never for validation or test data): the LR images are synthesised
         from the HR images on the GPU (ops.degrade_ragged_u8 in sr_batches; cutblur=True: with cutblur), which needs gpu_finish and
         turns gpu_resize on.  hr_dir (--train_hr_dir): a folder of HR images instead of the LMDBs of `dirs` (dataset/folder.py
-        FolderHR), always degraded."""
+        FolderHR), always degraded.  jpeg=(lo, hi, prob) (--jpeg_degrade / --jpeg_prob; with degrade, training data only): JPEG
+        artefacts on the synthesised LR images (ops.jpeg_roundtrip_u8 in sr_batches)."""
         from ..dataset import textzoom as tz
         cfg = self.config.TRAIN
         degrade = bool(degrade or hr_dir)
@@ -199,7 +211,7 @@ class TextBase(object):
             collate_fn=tz.alignCollate_realWTLAMask(imgH=cfg.height, imgW=cfg.width, down_sample_scale=cfg.down_sample_scale, mask=self.mask,
                                                     gpu_finish=gpu_finish,      # True: ToTensor + mask channel on the GPU by sr_batches
                                                     gpu_resize=gpu_finish and (gpu_resize or degrade or bool(getattr(self.args, "gpu_resize", False))),
-                                                    degrade=degrade, cutblur=cutblur))
+                                                    degrade=degrade, cutblur=cutblur, jpeg=jpeg))
         # (dataset/textzoom.py; uint8 pixels in the batch); False: the reference's float (B, 3 + mask, H, W) tensors for consumers that
         # iterate the loader themselves
         if shard:
@@ -210,11 +222,12 @@ class TextBase(object):
         cfg = self.config.TRAIN
         degrade, cutblur = degrade_flags(self.args)
         hr_dir = getattr(self.args, "train_hr_dir", None)
+        jpeg = jpeg_setting(self.args)
         if hr_dir:
-            return self._loader([], False, True, True, shard=True, degrade=True, cutblur=cutblur, hr_dir=hr_dir)
+            return self._loader([], False, True, True, shard=True, degrade=True, cutblur=cutblur, hr_dir=hr_dir, jpeg=jpeg)
         if not isinstance(cfg.train_data_dir, list):
             raise TypeError('check trainRoot')
-        return self._loader(cfg.train_data_dir, False, True, True, shard=True, degrade=degrade, cutblur=cutblur)
+        return self._loader(cfg.train_data_dir, False, True, True, shard=True, degrade=degrade, cutblur=cutblur, jpeg=jpeg)
 
     def get_val_data(self):
         pairs = [self.get_test_data(d) for d in self.config.TRAIN.VAL.val_data_dir]

@@ -342,6 +342,43 @@ def degrade_noise(seed, meta, device=None):
     return out
 
 
+def jpeg_roundtrip_u8(images_u8, quality, out=None):
+    """JPEG artefacts (csrc/jpeg.hip): images_u8 = a contiguous (B, h, w, 3) uint8 RGB batch on the device, quality = B integers (a
+    sequence or a tensor), 1 .. 100 per image or 0 for "leave this image alone" -> a new (B, h, w, 3) uint8 device tensor, per image
+    byte for byte utils.jpeg.jpeg_roundtrip_u8 = what PIL reads back after save(format='JPEG', quality=q).  Sides 1 .. 1024.  out:
+    the tensor to write instead of a new one; `images_u8` itself runs in place.  The qualities are uploaded (B int32) per call unless
+    they already are an int32 tensor on the device; nothing synchronises."""
+    import numpy as np
+    from .utils.jpeg import MAX_SIDE
+    if not torch.is_tensor(images_u8) or not images_u8.is_cuda:
+        raise _abi.DpmnError("jpeg_roundtrip_u8: the round trip runs on the GPU (got %s); there is no CPU fallback"
+                             % (images_u8.device if torch.is_tensor(images_u8) else type(images_u8).__name__))
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3 or not images_u8.is_contiguous():
+        raise _abi.DpmnError("jpeg_roundtrip_u8: a contiguous uint8 (B, h, w, 3) tensor is required, got %s %s"
+                             % (images_u8.dtype, tuple(images_u8.shape)))
+    B, h, w, _ = images_u8.shape
+    if not (1 <= B <= 65535 and 1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise _abi.DpmnError("jpeg_roundtrip_u8: 1 <= B <= 65535 and sides 1 .. %d, got %s" % (MAX_SIDE, tuple(images_u8.shape)))
+    dev = images_u8.device
+    q = np.asarray(quality.cpu() if torch.is_tensor(quality) else quality)
+    if q.shape != (B,) or q.dtype.kind not in "iu":
+        raise _abi.DpmnError("jpeg_roundtrip_u8: quality must be %d integers, got shape %s %s" % (B, q.shape, q.dtype))
+    if q.min() < 0 or q.max() > 100:
+        raise _abi.DpmnError("jpeg_roundtrip_u8: a quality is outside 0 .. 100 (0: the image is left alone)")
+    if torch.is_tensor(quality) and quality.device == dev and quality.dtype == torch.int32 and quality.is_contiguous():
+        qd = quality
+    else:
+        qd = torch.from_numpy(np.ascontiguousarray(q, dtype=np.int32)).to(dev)
+    if out is None:
+        out = torch.empty_like(images_u8)
+    elif (not torch.is_tensor(out) or out.device != dev or out.dtype != torch.uint8 or out.shape != images_u8.shape
+          or not out.is_contiguous()):
+        raise _abi.DpmnError("jpeg_roundtrip_u8: out must be a contiguous uint8 tensor of the input's shape on its device")
+    ws = torch.empty(lib.dpmn_jpeg_roundtrip_workspace_bytes(B, h, w), dtype=torch.uint8, device=dev)
+    check(lib.dpmn_jpeg_roundtrip_u8(images_u8.data_ptr(), out.data_ptr(), qd.data_ptr(), B, h, w, ws.data_ptr(), ws.numel(), stream()))
+    return out
+
+
 def quantize_sr_u8(x):
     """save_image's quantisation of channels 0..2 of x (B, >=3, H, W) float -> (B, H, W, 3) uint8 on the device = utils.display.
     quantize_sr, the bytes of an SR image file.  The channels are read in place (strides)."""

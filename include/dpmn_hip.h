@@ -504,6 +504,15 @@ int dpmn_degrade_ragged_u8(const unsigned char* packed_in, long packed_bytes, co
 /* out: device float, one value per packed byte; max_pixels: the largest h * w (sizes the launch) */
 int dpmn_degrade_noise_f32(unsigned long long seed, const long long* items, long packed_bytes, int B, int max_pixels, float* out,
                            dpmn_stream_t stream);
+/* JPEG artefacts (jpeg.hip; dataset/dataset.py:559 JPEG_compress): a UNIFORM batch in (B, h, w, 3) uint8 RGB -> out, every image as it
+ * is read back after a baseline JPEG of its own quality was written: 4:2:0, the standard tables scaled by quality (force_baseline), the
+ * islow DCT both ways, fancy upsampling -- byte for byte utils/jpeg.py jpeg_roundtrip_u8, i.e. PIL's save(quality = q) and open on
+ * libjpeg(-turbo); integer arithmetic throughout.  quality: device int32, B entries, 1 .. 100 (larger counts as 100); <= 0 leaves the image
+ * alone (its bytes are copied).  Sides 1 .. 1024, B <= 65535.  out may be in (in place).  workspace: dpmn_jpeg_roundtrip_workspace_bytes
+ * (B, h, w) bytes, 8-byte aligned (the decoded Y, Cb, Cr planes).  Two launches, nothing synchronises. */
+size_t dpmn_jpeg_roundtrip_workspace_bytes(int B, int h, int w);
+int dpmn_jpeg_roundtrip_u8(const unsigned char* in, unsigned char* out, const int* quality, int B, int h, int w, void* workspace,
+                           size_t workspace_bytes, dpmn_stream_t stream);
 /* A wide text line as overlapping windows of the model's LR size (tile.hip; utils/tile.py holds the plan arithmetic and the numpy
  * restatement).  resize_windows: a RAGGED batch in the packed layout of dpmn_resize_ragged_u8 -> every image resized with PIL's
  * fixed-point bicubic (the arithmetic of dpmn_resize_ragged_u8, byte for byte Image.resize((w_line, lr_h), BICUBIC)) to the height lr_h

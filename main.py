@@ -10,7 +10,7 @@ everything between the loader and the optimizer step is the real path.  `--demo_
 (any sizes; resized on the GPU) into `--demo_out`; with `--demo_tile` a wide image keeps its aspect ratio and goes through the model in
 overlapping windows.  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
-(`--cutblur`: with the reference's cutblur on top); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
+(`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
 import argparse
 import csv
@@ -66,6 +66,14 @@ def main(config, args):
     if getattr(args, "cutblur", False) and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None)):
         raise SystemExit("main.py: --cutblur needs --manmade_degrade (or --train_hr_dir): it mixes columns of the HR image into the "
                          "synthesised LR image")
+    from dpmn_amd.utils.jpeg import jpeg_setting
+    try:
+        jpeg = jpeg_setting(args)
+    except ValueError as e:
+        raise SystemExit("main.py: %s" % e)
+    if jpeg is not None and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None)):
+        raise SystemExit("main.py: --jpeg_degrade needs --manmade_degrade (or --train_hr_dir): the JPEG artefacts are put on the "
+                         "synthesised LR images")
     if getattr(args, "demo_tile", False) and not getattr(args, "demo_dir", None):
         raise SystemExit("main.py: --demo_tile needs --demo_dir: it super-resolves the wide images of that folder in overlapping windows")
     hr_dir = getattr(args, "train_hr_dir", None)
@@ -222,6 +230,11 @@ if __name__ == '__main__':
                              'sharpening) instead of read from the LMDB')
     parser.add_argument('--cutblur', action='store_true', default=False,
                         help='with --manmade_degrade: columns on one side of a random cut of the synthesised LR image are the HR image\'s')
+    parser.add_argument('--jpeg_degrade', type=str, default=None, metavar='LO,HI',
+                        help='with --manmade_degrade: a synthesised LR image goes through a JPEG of a quality drawn from LO .. HI '
+                             '(1 .. 100, for example 30,95; 40,40 is the fixed quality of the reference\'s helper) with probability '
+                             '--jpeg_prob')
+    parser.add_argument('--jpeg_prob', type=float, default=0.5, help='with --jpeg_degrade: the probability of the JPEG stage per image')
     parser.add_argument('--train_hr_dir', type=str, default=None,
                         help='train from this folder of HR images (optional labels.txt: file name<TAB>word); implies --manmade_degrade, '
                              'needs no LMDB')
