@@ -5,6 +5,9 @@ model's LR size on the GPU (ops.resize_ragged_u8, byte for byte PIL's bicubic re
 --demo_tile) keeps the aspect ratio of wide images: every image as overlapping windows of the LR size (ops.resize_windows_u8).
 `FolderHR`: the same kind of directory as the HR images of a TRAINING set (main.py --train_hr_dir): the LR images are synthesised on
 the GPU (dataset/textzoom.py, alignCollate_realWTLAMask(degrade=True) and sr_batches), so training needs neither LMDB nor LR images.
+`box_batches` / `box_region_batches` / `box_window_batches` (main.py --demo_boxes): a directory of WHOLE photos and a directory of box
+files (one quadrilateral per word, utils/quad.py); every region is rectified on the GPU (ops.quad_crop_u8) and then takes the path of a
+crop of the folder.
 """
 import os
 
@@ -71,6 +74,99 @@ def folder_window_batches(dir_, batch_size, lr_size, mask, device):
     for names, packed, meta in host_batches(dir_, batch_size, check=lambda a, f: check_line(a, (h, w), f)):
         windows, plan = ops.resize_windows_u8(packed.to(device, non_blocking=True), meta, h, w)
         yield names, plan, ops.collate_u8(windows, mask)
+
+
+def box_batches(dir_, box_dir, batch_size, check=None):
+    """The host half of the box path: yields (region names, labels, packed, meta, regions) per batch -- packed / meta =
+    utils.resize.pack_ragged of the batch's photos, regions = the list of (photo index in the batch, h, w, coeffs) that
+    ops.quad_crop_u8 takes (utils.quad: quad_size and quad_coeffs of every quadrilateral), names and labels one per region.
+    The photos are the regular files of `dir_` in sorted name order, as host_batches walks them (files named *.txt are passed over, so
+    the box files may lie beside the photos).  The boxes of name.ext are read from box_dir/<stem>.txt, or else box_dir/gt_<stem>.txt
+    (utils.quad.read_boxes' format).  A region is named <stem>_<k>, k = the number of its line among the file's non-empty lines from 0,
+    as 3 digits; a line that is skipped keeps its number.  A photo without a box file, without a usable region, or that PIL cannot
+    open is skipped with one printed line; so is a region that utils.quad.check_quad, quad_coeffs or `check` (a callable (h, w, name)
+    that raises ValueError for a region size it rejects) refuses, naming the photo and the line.  A photo is never split: a batch
+    closes once it holds at least batch_size regions, or once the next photo would exceed utils.resize.MAX_PACKED_BYTES.  A directory
+    without files raises."""
+    from PIL import Image
+    from ..utils.quad import check_quad, numbered_boxes, quad_coeffs, quad_size
+    from ..utils.resize import MAX_PACKED_BYTES, check_image, pack_ragged
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("folder: batch_size must be positive, got %d" % batch_size)
+    files = sorted(f for f in os.listdir(dir_) if os.path.isfile(os.path.join(dir_, f)))
+    if not files:
+        raise FileNotFoundError("folder: %s holds no files" % dir_)
+    names, labels, images, regions, nbytes = [], [], [], [], 0
+    for f in files:
+        stem = os.path.splitext(f)[0]
+        if f.lower().endswith(".txt"):
+            continue
+        box_file = next((p for p in (os.path.join(box_dir, stem + ".txt"), os.path.join(box_dir, "gt_" + stem + ".txt")) if os.path.isfile(p)), None)
+        if box_file is None:
+            print("folder: skipping %s (no box file %s.txt or gt_%s.txt in %s)" % (f, stem, stem, box_dir))
+            continue
+        found = []
+        for k, lineno, quad, label in numbered_boxes(box_file):
+            try:
+                check_quad(quad)
+                h, w = quad_size(quad)
+                coeffs = quad_coeffs(quad, w, h)
+                if check is not None:
+                    check(h, w, "%s_%03d" % (stem, k))
+            except ValueError as e:
+                print("folder: skipping a region of %s (%s line %d: %s)" % (f, os.path.basename(box_file), lineno, e))
+                continue
+            found.append(("%s_%03d" % (stem, k), label, h, w, coeffs))
+        if not found:
+            print("folder: skipping %s (no usable region in %s)" % (f, os.path.basename(box_file)))
+            continue
+        try:
+            with Image.open(os.path.join(dir_, f)) as im:
+                a = np.asarray(im.convert('RGB'), dtype=np.uint8)
+            check_image(a, f)
+        except Exception as e:      # whatever a decoder raises on a file that is not its format, or is damaged
+            print("folder: skipping %s (%s: %s)" % (f, type(e).__name__, e))
+            continue
+        if images and nbytes + a.size > MAX_PACKED_BYTES:      # pack_ragged's limit on a batch: this photo starts the next one
+            yield (names, labels) + pack_ragged(images) + (regions,)
+            names, labels, images, regions, nbytes = [], [], [], [], 0
+        for name, label, h, w, coeffs in found:
+            names.append(name)
+            labels.append(label)
+            regions.append((len(images), h, w, coeffs))
+        images.append(a)
+        nbytes += a.size
+        if len(names) >= batch_size:
+            yield (names, labels) + pack_ragged(images) + (regions,)
+            names, labels, images, regions, nbytes = [], [], [], [], 0
+    if names:
+        yield (names, labels) + pack_ragged(images) + (regions,)
+
+
+def box_region_batches(dir_, box_dir, batch_size, lr_size, mask, device):
+    """folder_batches for whole photos with box files (main.py --demo_boxes): yields (region names, labels, images_lr) per batch of
+    box_batches, images_lr (R, 3 + mask, h, w) float on `device`, (h, w) = lr_size.  Per batch one upload of the packed photos, then
+    the rectification of every region at its own size (ops.quad_crop_u8), the ragged resize to the LR size and the collate kernel."""
+    from .. import ops
+    h, w = lr_size
+    for names, labels, packed, meta, regions in box_batches(dir_, box_dir, batch_size):
+        crops, crop_meta = ops.quad_crop_u8(packed.to(device, non_blocking=True), meta, regions)
+        yield names, labels, ops.collate_u8(ops.resize_ragged_u8(crops, crop_meta, h, w), mask)
+
+
+def box_window_batches(dir_, box_dir, batch_size, lr_size, mask, device):
+    """folder_window_batches for whole photos with box files (main.py --demo_boxes --demo_tile): yields (region names, labels, plan,
+    images_lr) per batch of box_batches -- every rectified region keeps its aspect ratio and is cut into overlapping windows of lr_size
+    (ops.resize_windows_u8), plan as folder_window_batches yields it, over the batch's regions.  A region whose line would be wider than
+    utils.resize.MAX_SIDE (utils.tile.line_width of the REGION's size, not the photo's) is skipped with one printed line."""
+    from .. import ops
+    from ..utils.tile import line_width
+    h, w = lr_size
+    for names, labels, packed, meta, regions in box_batches(dir_, box_dir, batch_size, check=lambda rh, rw, name: line_width(rh, rw, h, w)):
+        crops, crop_meta = ops.quad_crop_u8(packed.to(device, non_blocking=True), meta, regions)
+        windows, plan = ops.resize_windows_u8(crops, crop_meta, h, w)
+        yield names, labels, plan, ops.collate_u8(windows, mask)
 
 
 class FolderHR(torch.utils.data.Dataset):

@@ -307,7 +307,7 @@ class TextSR(base.TextBase):
         return res
 
     @torch.no_grad()
-    def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None):
+    def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None, boxes=False):
         """Super-resolve someone's own images (ours; main.py --demo_dir): batches yields (names, images_lr) as
         dataset.folder.folder_batches does.  Per batch `refine` (label_vecs from the frozen CRNN for tatt / tpgsr, as in eval), then
         save_image's quantisation on the GPU (ops.quantize_sr_u8), ONE device-to-host copy and one <stem>_sr.png per input under
@@ -321,7 +321,13 @@ class TextSR(base.TextBase):
         (default: the batch size; a chunk of one window is repeated as above, label_vecs per window), ops.stitch_windows_u8 blends the
         SR windows of an image on the GPU, and <stem>_sr.png is scale * lr_h high and scale * w_line wide.  lr_string / sr_string are
         then the reads of the image's WINDOWS joined with '|': a recogniser sees lr_w columns at a time and neighbouring windows
-        overlap, so this is not a transcription of the line.  An image of one window is written as without tile."""
+        overlap, so this is not a transcription of the line.  An image of one window is written as without tile.
+        boxes=True (main.py --demo_boxes): the inputs are the text regions of whole photos; batches yields (names, labels, images_lr)
+        as dataset.folder.box_region_batches does -- with tile=True (names, labels, plan, images_lr) as box_window_batches does --
+        names being the region names <stem>_<k>.  A photo is never split, so a batch may hold more regions than the batch size: they
+        go through `refine` in chunks of at most `chunk` (default: the batch size; a chunk of one is repeated as above).  One
+        <stem>_<k>_sr.png per region; demo_result.csv then has the header file, box, label, lr_string, sr_string: the photo's stem,
+        the region's number k, its transcription from the box file.  Without boxes nothing changes."""
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
         for m in model_list:
@@ -329,7 +335,14 @@ class TextSR(base.TextBase):
         fn = text_prior_fn or self.default_text_prior()
         os.makedirs(out_dir, exist_ok=True)
         rows, taken = [], set()
-        if tile:
+        if boxes:
+            labels = []
+            for names, pixels, preds_lr, preds_sr in self._demo_regions(model_list, model_psn, batches, fn, reader, chunk, tile, labels):
+                self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken)
+            # <stem>_<k>.png, lr, sr -> stem, k, label, lr, sr
+            rows = [r[0][:-4].rsplit("_", 1) + [label] + r[1:] for r, label in zip(rows, labels)]
+            batches = ()
+        elif tile:
             for names, pixels, preds_lr, preds_sr in self._demo_windows(model_list, model_psn, batches, fn, reader, chunk):
                 self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken)
             batches = ()
@@ -347,7 +360,7 @@ class TextSR(base.TextBase):
             self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken)
         with open(os.path.join(out_dir, "demo_result.csv"), "w", newline="") as out:
             w = csv.writer(out)
-            w.writerow(["file", "lr_string", "sr_string"])
+            w.writerow(["file", "box", "label", "lr_string", "sr_string"] if boxes else ["file", "lr_string", "sr_string"])
             w.writerows(rows)
         return rows
 
@@ -364,6 +377,33 @@ class TextSR(base.TextBase):
             taken.add(out_name)
             Image.fromarray(a).save(os.path.join(out_dir, out_name))
             rows.append([name, str(s_lr), str(s_sr)])
+
+    def _demo_regions(self, model_list, model_psn, batches, fn, reader, chunk, tile, labels_out):
+        """demo(boxes=True): per batch of regions -> (names, one (H, W_r, 3) uint8 array per region, the LR reads, the SR reads); the
+        regions' labels are appended to labels_out.  tile: the batches carry a plan and go through _demo_windows."""
+        if tile:
+            def windows():
+                for names, labels, plan, images_lr in batches:
+                    labels_out.extend(labels)
+                    yield names, plan, images_lr
+            yield from self._demo_windows(model_list, model_psn, windows(), fn, reader, chunk)
+            return
+        chunk = max(int(chunk if chunk is not None else self.batch_size), 1)
+        for names, labels, images_lr in batches:
+            labels_out.extend(labels)
+            images_lr = images_lr.to(self.device)
+            pixels, preds_lr, preds_sr = [], [], []
+            for lo in range(0, images_lr.shape[0], chunk):
+                x = images_lr[lo:lo + chunk]
+                n = x.shape[0]
+                if n == 1:
+                    x = torch.cat([x, x], 0)
+                label_vecs = self.label_vecs_from_crnn(x) if self.args.arch in ('tatt', 'tpgsr') else None
+                sr = self.refine(model_list, model_psn, x, label_vecs, fn)[:n]
+                pixels.append(ops.quantize_sr_u8(sr).cpu().numpy())
+                preds_lr += list(reader(x[:n, :3])) if reader is not None else [''] * n
+                preds_sr += list(reader(sr[:, :3])) if reader is not None else [''] * n
+            yield names, [a for p in pixels for a in p], preds_lr, preds_sr
 
     def _demo_windows(self, model_list, model_psn, batches, fn, reader, chunk):
         """demo(tile=True): per batch (names, plan, images_lr) of windows -> (names, one (H, W_b, 3) uint8 array per image, the LR

@@ -503,6 +503,78 @@ def stitch_windows_u8(sr, plan, scale=2):
     return out, meta
 
 
+QUAD_TILE = (8, 32)      # csrc/quad.hip QUAD_TILE_H, QUAD_TILE_W
+
+
+def _quad_crop_plan(packed, meta, regions):
+    """Checks and per-call host data of quad_crop_u8 -> host: the arrays of one call as numpy -- table (R, 14) int64 [byte offset of the
+    photo, H, W, byte offset of the region in the output, h, w, the bits of the 8 float64 coefficients], tiles (n_tiles, 3) int32
+    [region, tile row, tile column], meta (R, 3) int64 (byte offset, h, w) of the output, and its size in bytes (_quad_crop_run)."""
+    import numpy as np
+    from .utils.resize import MAX_PACKED_BYTES, MAX_SIDE
+    m = _ragged_batch(packed, meta, "quad_crop_u8")
+    R = len(regions)
+    table = np.empty((R, 14), np.int64)
+    for r, reg in enumerate(regions):
+        try:
+            b, h, w, coeffs = reg
+            b, h, w = int(b), int(h), int(w)
+            a = np.asarray(coeffs, np.float64).reshape(-1)
+        except (TypeError, ValueError) as e:
+            raise _abi.DpmnError("quad_crop_u8: region %d is not (photo index, h, w, 8 coefficients): %s" % (r, e)) from e
+        if not (0 <= b < m.shape[0] and 1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE and a.size == 8 and np.isfinite(a).all()):
+            raise _abi.DpmnError("quad_crop_u8: region %d names a photo outside the batch of %d, a side outside 1 .. %d or does not "
+                                 "carry 8 finite coefficients" % (r, m.shape[0], MAX_SIDE))
+        table[r, :3] = m[b]
+        table[r, 4:6] = h, w
+        table[r, 6:] = a.view(np.int64)
+    sizes = table[:, 4] * table[:, 5] * 3
+    first = np.concatenate(([0], np.cumsum(sizes)))
+    if first[-1] > MAX_PACKED_BYTES:
+        raise _abi.DpmnError("quad_crop_u8: the regions hold more than 2^31 - 1 bytes")
+    table[:, 3] = first[:-1]
+    th, tw = -(-table[:, 4] // QUAD_TILE[0]), -(-table[:, 5] // QUAD_TILE[1])
+    tfirst = np.concatenate(([0], np.cumsum(th * tw)))
+    tiles = np.empty((int(tfirst[-1]), 3), np.int32)
+    for r in range(R):
+        t = tiles[tfirst[r]:tfirst[r + 1]]
+        t[:, 0] = r
+        t[:, 1] = np.repeat(np.arange(th[r]), tw[r])
+        t[:, 2] = np.tile(np.arange(tw[r]), th[r])
+    return dict(table=table, tiles=tiles, meta=np.ascontiguousarray(table[:, 3:6]), out_bytes=int(first[-1]))
+
+
+def _quad_crop_run(packed, host):
+    """One upload of the host arrays of _quad_crop_plan (the region table and the tiles in one int64 buffer) and the launch ->
+    (the packed regions, the library's return code): the output exists whatever the code says."""
+    import numpy as np
+    table, tiles = np.ascontiguousarray(host["table"], dtype=np.int64), np.ascontiguousarray(host["tiles"], dtype=np.int32)
+    R, n_tiles, dev = table.shape[0], tiles.shape[0], packed.device
+    out = torch.zeros(host["out_bytes"], dtype=torch.uint8, device=dev)
+    if R == 0:
+        return out, lib.dpmn_quad_crop_u8(packed.data_ptr(), packed.numel(), None, None, 0, None, 0, None, 0, stream())
+    buf = np.zeros(R * 14 + (n_tiles * 3 + 1) // 2, np.int64)
+    buf[:R * 14] = table.reshape(-1)
+    buf[R * 14:].view(np.int32)[:n_tiles * 3] = tiles.reshape(-1)
+    d = torch.from_numpy(buf).to(dev)
+    return out, lib.dpmn_quad_crop_u8(packed.data_ptr(), packed.numel(), d.data_ptr(), table.ctypes.data, R, d[R * 14:].data_ptr(), n_tiles,
+                                      out.data_ptr(), out.numel(), stream())
+
+
+def quad_crop_u8(packed, meta, regions):
+    """The text regions of a ragged batch of photos, rectified (csrc/quad.hip): packed / meta as resize_ragged_u8 takes them (the
+    uploaded utils.resize.pack_ragged buffer of the photos and its (B, 3) array), regions = a list of (photo index, h, w, coeffs), coeffs
+    the 8 float64 coefficients of utils.quad.quad_coeffs -> (packed_regions, region_meta): a 1-D uint8 device tensor holding the R
+    regions back to back as (h, w, 3) and the host int64 (R, 3) array of (byte offset, h, w) per region -- the layout of pack_ragged,
+    what resize_ragged_u8 and resize_windows_u8 take.  Per region byte for byte np.asarray(Image.fromarray(photo).transform((w, h),
+    Image.PERSPECTIVE, coeffs, Image.BICUBIC)) = utils.quad.quad_crop_np, in float64.  A region may reach outside its photo (black
+    there).  An empty list gives empty outputs and launches nothing.  Per call one buffer is uploaded: the region table and the tiles."""
+    host = _quad_crop_plan(packed, meta, list(regions))
+    out, code = _quad_crop_run(packed, host)
+    check(code)
+    return out, host["meta"]
+
+
 def maxpool(x, kh, kw, scale=None, shift=None):
     """nn.MaxPool2d((kh,kw), stride (kh,kw)) over NHWC; scale/shift: the producer's BatchNorm affine + ReLU applied on load."""
     B, H, W, Cc = x.shape

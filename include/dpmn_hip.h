@@ -537,6 +537,21 @@ int dpmn_resize_windows_u8(const unsigned char* packed, long packed_bytes, const
  * a window that names another image or starts outside the line is skipped.  One launch, no atomics: every byte has one owner. */
 int dpmn_stitch_windows_u8(const float* sr, long batch_stride, long chan_stride, int T, int H, int sr_w, int scale, const long long* lines, int B,
                            const int* windows, int max_w_line, unsigned char* out, long out_bytes, dpmn_stream_t stream);
+/* The text regions of whole photos, rectified (quad.hip; utils/quad.py holds the box reader, the coefficients and the numpy restatement):
+ * a RAGGED batch of photos in the packed layout of dpmn_resize_ragged_u8 and R regions -> every region as an upright h x w x 3 uint8
+ * rectangle at its byte offset in out (the same packed layout), byte for byte PIL's Image.transform((w, h), PERSPECTIVE, coeffs,
+ * BICUBIC): per output pixel (x, y) the source position sx = (a0 xin + a1 yin + a2) / (a6 xin + a7 yin + 1), sy likewise from a3 a4 a5,
+ * at xin = x + 0.5, yin = y + 0.5; black outside 0 <= sx < W, 0 <= sy < H; else the 4 x 4 bicubic of Geometry.c around (sx - 0.5,
+ * sy - 0.5) with the columns clipped to the photo, the first row clipped and a later row outside the photo repeating the row before it;
+ * the byte is the value clamped to 0 .. 255 and truncated.  float64, plain * + / in that order: independent of the compute mode.
+ * regions: device int64 (R, 14), per region [byte offset of its photo in packed, H, W, byte offset of the region in out, h, w, the bits
+ * of the 8 float64 coefficients a0 .. a7]; regions_host: the same table in HOST memory (the entry point checks it, the kernel checks
+ * the device copy); tiles: device int32 (n_tiles, 3), per 32 x 8 tile (w x h) [region, tile row, tile column]: one block per tile, one
+ * thread per pixel.  Sides 1 .. 8192.  A region whose photo does not fit packed or has such a side is not read and comes out black, one
+ * whose own extent does not fit out is not written, and the call then returns DPMN_ERR_ARG after the launch -- the other regions are
+ * computed.  A tile that names no region or lies outside its region writes nothing.  R = 0 launches nothing.  One launch. */
+int dpmn_quad_crop_u8(const unsigned char* packed, long packed_bytes, const long long* regions, const long long* regions_host /* HOST array */,
+                      int R, const int* tiles, int n_tiles, unsigned char* out, long out_bytes, dpmn_stream_t stream);
 
 /* rotation augmentation of the trainer (utils/util.py:37-58 torch_rotate_img; super_resolution.py:144-151, 358-365):
  * per-image affine with aspect-ratio jitter -> affine_grid (align_corners=False) -> bilinear grid_sample, zeros padding.

@@ -8,7 +8,8 @@ HIP-backed modules.  `--rec crnn` loads the native CRNN recogniser (config TRAIN
 batches of the real shapes -- `--synthetic_steps` of them -- and the text priors come from `TextSR.synthetic_text_prior()`;
 everything between the loader and the optimizer step is the real path.  `--demo_dir DIR --resume CKPT` super-resolves a folder of images
 (any sizes; resized on the GPU) into `--demo_out`; with `--demo_tile` a wide image keeps its aspect ratio and goes through the model in
-overlapping windows.  `--train_state PATH` makes a training run continuable: the same command line starts the
+overlapping windows; with `--demo_boxes BOXDIR` the folder holds whole photos and BOXDIR one text file of quadrilaterals per photo, each
+rectified on the GPU and super-resolved as a crop of its own.  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
 (`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
@@ -62,6 +63,9 @@ def recogniser(mission, args):
     return None
 
 
+DEMO_BOXES_NEEDS_DIR = "main.py: --demo_boxes needs --demo_dir: the photos whose regions the box files name are read from that folder"
+
+
 def main(config, args):
     if getattr(args, "cutblur", False) and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None)):
         raise SystemExit("main.py: --cutblur needs --manmade_degrade (or --train_hr_dir): it mixes columns of the HR image into the "
@@ -76,6 +80,8 @@ def main(config, args):
                          "synthesised LR images")
     if getattr(args, "demo_tile", False) and not getattr(args, "demo_dir", None):
         raise SystemExit("main.py: --demo_tile needs --demo_dir: it super-resolves the wide images of that folder in overlapping windows")
+    if getattr(args, "demo_boxes", None) and not getattr(args, "demo_dir", None):
+        raise SystemExit(DEMO_BOXES_NEEDS_DIR)
     hr_dir = getattr(args, "train_hr_dir", None)
     if hr_dir and not os.path.isdir(hr_dir):
         raise SystemExit("main.py: --train_hr_dir %s is not a directory" % hr_dir)
@@ -104,11 +110,22 @@ def main(config, args):
             raise SystemExit("main.py: --demo_dir needs --resume <dir> holding the trained models (as --test does)")
         if rank != 0:
             return
-        from dpmn_amd.dataset.folder import folder_batches, folder_window_batches
+        from dpmn_amd.dataset.folder import box_region_batches, box_window_batches, folder_batches, folder_window_batches
         models, psn = mission.build_models(testing=True)
         scale = config.TRAIN.down_sample_scale
         out_dir = getattr(args, "demo_out", None) or os.path.join(mission.vis_dir, "demo")
         lr_size = (config.TRAIN.height // scale, config.TRAIN.width // scale)
+        box_dir = getattr(args, "demo_boxes", None)
+        if box_dir:
+            # whole photos and one box file per photo: every quadrilateral is rectified on the GPU (utils/quad.py), then goes the way
+            # of a crop of the folder -- one <stem>_<k>_sr.png per region
+            if not os.path.isdir(box_dir):
+                raise SystemExit("main.py: --demo_boxes %s is not a directory" % box_dir)
+            tile = bool(getattr(args, "demo_tile", False))
+            batches = (box_window_batches if tile else box_region_batches)(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device)
+            rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True)
+            print("%d regions super-resolved into %s" % (len(rows), out_dir))
+            return
         if getattr(args, "demo_tile", False):
             # wide images keep their aspect ratio: overlapping LR windows per image, one stitched <stem>_sr.png (utils/tile.py)
             batches = folder_window_batches(args.demo_dir, bs, lr_size, mission.mask, mission.device)
@@ -220,6 +237,10 @@ if __name__ == '__main__':
     parser.add_argument('--demo_tile', action='store_true', default=False,
                         help='with --demo_dir: an image wider than the LR aspect keeps its aspect ratio and is super-resolved in '
                              'overlapping windows that are blended into one image')
+    parser.add_argument('--demo_boxes', type=str, default=None, metavar='BOXDIR',
+                        help='with --demo_dir: the folder holds whole photos, and BOXDIR one text file per photo (<stem>.txt or '
+                             'gt_<stem>.txt, lines x1,y1,x2,y2,x3,y3,x4,y4[,transcription], corners clockwise from top-left); every '
+                             'quadrilateral is rectified on the GPU and super-resolved (combines with --demo_tile)')
     parser.add_argument('--gpu_resize', action='store_true', default=False,
                         help='TextZoom loaders: the bicubic resize of the decoded images runs on the GPU (same bytes as PIL)')
     parser.add_argument('--train_state', type=str, default=None,
@@ -239,6 +260,8 @@ if __name__ == '__main__':
                         help='train from this folder of HR images (optional labels.txt: file name<TAB>word); implies --manmade_degrade, '
                              'needs no LMDB')
     args = parser.parse_args()
+    if args.demo_boxes and not args.demo_dir:
+        parser.error(DEMO_BOXES_NEEDS_DIR[len("main.py: "):])
     config_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config', 'super_resolution.yaml')
     config = AttrDict(yaml.load(open(config_path, 'r'), Loader=yaml.Loader))
     main(config, args)
