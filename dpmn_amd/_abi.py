@@ -294,6 +294,7 @@ SIGNATURES = {
     "dpmn_resize_windows_u8": (_i, [fp, _l, fp, _i, fp, _l, fp, _i, _l, _i, fp, _i, _i, fp, _sz, fp]),
     "dpmn_stitch_windows_u8": (_i, [fp, _l, _l, _i, _i, _i, _i, fp, _i, fp, _i, fp, _l, fp]),
     "dpmn_quad_crop_u8": (_i, [fp, _l, fp, fp, _i, fp, _i, fp, _l, fp]),
+    "dpmn_paste_regions_u8": (_i, [fp, _i, _i, fp, _l, fp, fp, _i, fp, _i, fp, _i, fp]),
     "dpmn_profile_tag_count": (_i, []),
     "dpmn_profile_hint_bytes": (_i, [C.c_double]),
     "dpmn_profile_tag_name": (C.c_char_p, [_i]),

@@ -8,7 +8,7 @@
 // double division is correctly rounded), the result truncated to a byte.  Neighbouring threads of a tile row read neighbouring source
 // pixels (a text region is at most mildly slanted, so a row of 32 pixels touches a few source rows); the 48 bytes of a pixel's taps
 // come through L1 / L2 -- no LDS staging.  A few hundred KB per batch: launch-bound work, nothing here is tuned for throughput.
-#include "u8_pixel.h"
+#include "quad_sample.h"
 
 namespace {
 
@@ -23,15 +23,6 @@ __host__ __device__ inline int quad_region_state(const long long* p, long packed
   if (!(h >= 1 && h <= RESIZE_MAX_SIDE && w >= 1 && w <= RESIZE_MAX_SIDE && out_off >= 0 && out_off <= out_bytes - h * w * 3)) return 0;
   if (!(H >= 1 && H <= RESIZE_MAX_SIDE && W >= 1 && W <= RESIZE_MAX_SIDE && in_off >= 0 && in_off <= packed_bytes - H * W * 3)) return 1;
   return 2;
-}
-
-// Geometry.c BICUBIC: the cubic through four values at the fraction d, in its operation order
-__device__ __forceinline__ double cubic(double v1, double v2, double v3, double v4, double d) {
-  const double p1 = v2;
-  const double p2 = -v1 + v3;
-  const double p3 = 2 * (v1 - v2) + v3 - v4;
-  const double p4 = -v1 + v2 - v3 + v4;
-  return p1 + d * (p2 + d * (p3 + d * p4));
 }
 
 __global__ void __launch_bounds__(QUAD_TILE_W * QUAD_TILE_H)
@@ -60,32 +51,7 @@ k_quad_crop(const unsigned char* __restrict__ packed, long packed_bytes, const l
     double sy = (a3 * xin + a4 * yin + a5) / den;
     // (a NaN compares false: outside; nothing becomes an integer before this test)
     if (sx >= 0.0 && sx < (double)W && sy >= 0.0 && sy < (double)H) {
-      sx -= 0.5;
-      sy -= 0.5;
-      const double fx = floor(sx), fy = floor(sy);
-      const double dx = sx - fx, dy = sy - fy;
-      const int ix = (int)fx, iy = (int)fy;      // -1 .. W - 1, -1 .. H - 1
-      const int c0 = min(max(ix - 1, 0), W - 1) * 3, c1 = min(max(ix, 0), W - 1) * 3, c2 = min(max(ix + 1, 0), W - 1) * 3,
-                c3 = min(max(ix + 2, 0), W - 1) * 3;
-      const unsigned char* src = packed + p[0];
-      const size_t row_bytes = (size_t)W * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        double v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int row = iy - 1 + k;
-          // the first row is clipped; a later row outside the photo repeats the value of the row before it
-          if (k == 0 || (row >= 0 && row < H)) {
-            const unsigned char* q = src + (size_t)min(max(row, 0), H - 1) * row_bytes + c;
-            v[k] = cubic((double)q[c0], (double)q[c1], (double)q[c2], (double)q[c3], dx);
-          } else {
-            v[k] = v[k - 1];
-          }
-        }
-        const double val = cubic(v[0], v[1], v[2], v[3], dy);
-        px[c] = val <= 0.0 ? 0 : val >= 255.0 ? 255 : (unsigned char)(int)val;
-      }
+      bicubic_sample_u8(packed + p[0], H, W, sx, sy, px);
     }
   }
   dst[0] = px[0];

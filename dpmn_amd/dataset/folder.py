@@ -7,7 +7,8 @@ model's LR size on the GPU (ops.resize_ragged_u8, byte for byte PIL's bicubic re
 the GPU (dataset/textzoom.py, alignCollate_realWTLAMask(degrade=True) and sr_batches), so training needs neither LMDB nor LR images.
 `box_batches` / `box_region_batches` / `box_window_batches` (main.py --demo_boxes): a directory of WHOLE photos and a directory of box
 files (one quadrilateral per word, utils/quad.py); every region is rectified on the GPU (ops.quad_crop_u8) and then takes the path of a
-crop of the folder.
+crop of the folder.  With photos=True (main.py --demo_paste) the two generators also hand out the uploaded photos and the
+quadrilaterals, which TextSR.demo(paste=True) needs to put the SR regions back (utils/paste.py).
 """
 import os
 
@@ -76,7 +77,7 @@ def folder_window_batches(dir_, batch_size, lr_size, mask, device):
         yield names, plan, ops.collate_u8(windows, mask)
 
 
-def box_batches(dir_, box_dir, batch_size, check=None):
+def box_batches(dir_, box_dir, batch_size, check=None, quads=False):
     """The host half of the box path: yields (region names, labels, packed, meta, regions) per batch -- packed / meta =
     utils.resize.pack_ragged of the batch's photos, regions = the list of (photo index in the batch, h, w, coeffs) that
     ops.quad_crop_u8 takes (utils.quad: quad_size and quad_coeffs of every quadrilateral), names and labels one per region.
@@ -87,7 +88,8 @@ def box_batches(dir_, box_dir, batch_size, check=None):
     open is skipped with one printed line; so is a region that utils.quad.check_quad, quad_coeffs or `check` (a callable (h, w, name)
     that raises ValueError for a region size it rejects) refuses, naming the photo and the line.  A photo is never split: a batch
     closes once it holds at least batch_size regions, or once the next photo would exceed utils.resize.MAX_PACKED_BYTES.  A directory
-    without files raises."""
+    without files raises.  quads=True: every tuple gains a last item, the float64 (4, 2) quadrilateral of every region in photo
+    coordinates (the default leaves the tuples as they are)."""
     from PIL import Image
     from ..utils.quad import check_quad, numbered_boxes, quad_coeffs, quad_size
     from ..utils.resize import MAX_PACKED_BYTES, check_image, pack_ragged
@@ -97,7 +99,7 @@ def box_batches(dir_, box_dir, batch_size, check=None):
     files = sorted(f for f in os.listdir(dir_) if os.path.isfile(os.path.join(dir_, f)))
     if not files:
         raise FileNotFoundError("folder: %s holds no files" % dir_)
-    names, labels, images, regions, nbytes = [], [], [], [], 0
+    names, labels, images, regions, corners, nbytes = [], [], [], [], [], 0
     for f in files:
         stem = os.path.splitext(f)[0]
         if f.lower().endswith(".txt"):
@@ -117,7 +119,7 @@ def box_batches(dir_, box_dir, batch_size, check=None):
             except ValueError as e:
                 print("folder: skipping a region of %s (%s line %d: %s)" % (f, os.path.basename(box_file), lineno, e))
                 continue
-            found.append(("%s_%03d" % (stem, k), label, h, w, coeffs))
+            found.append(("%s_%03d" % (stem, k), label, h, w, coeffs, quad))
         if not found:
             print("folder: skipping %s (no usable region in %s)" % (f, os.path.basename(box_file)))
             continue
@@ -129,44 +131,59 @@ def box_batches(dir_, box_dir, batch_size, check=None):
             print("folder: skipping %s (%s: %s)" % (f, type(e).__name__, e))
             continue
         if images and nbytes + a.size > MAX_PACKED_BYTES:      # pack_ragged's limit on a batch: this photo starts the next one
-            yield (names, labels) + pack_ragged(images) + (regions,)
-            names, labels, images, regions, nbytes = [], [], [], [], 0
-        for name, label, h, w, coeffs in found:
+            yield (names, labels) + pack_ragged(images) + ((regions, corners) if quads else (regions,))
+            names, labels, images, regions, corners, nbytes = [], [], [], [], [], 0
+        for name, label, h, w, coeffs, quad in found:
             names.append(name)
             labels.append(label)
             regions.append((len(images), h, w, coeffs))
+            corners.append(quad)
         images.append(a)
         nbytes += a.size
         if len(names) >= batch_size:
-            yield (names, labels) + pack_ragged(images) + (regions,)
-            names, labels, images, regions, nbytes = [], [], [], [], 0
+            yield (names, labels) + pack_ragged(images) + ((regions, corners) if quads else (regions,))
+            names, labels, images, regions, corners, nbytes = [], [], [], [], [], 0
     if names:
-        yield (names, labels) + pack_ragged(images) + (regions,)
+        yield (names, labels) + pack_ragged(images) + ((regions, corners) if quads else (regions,))
 
 
-def box_region_batches(dir_, box_dir, batch_size, lr_size, mask, device):
+def box_region_batches(dir_, box_dir, batch_size, lr_size, mask, device, photos=False):
     """folder_batches for whole photos with box files (main.py --demo_boxes): yields (region names, labels, images_lr) per batch of
     box_batches, images_lr (R, 3 + mask, h, w) float on `device`, (h, w) = lr_size.  Per batch one upload of the packed photos, then
-    the rectification of every region at its own size (ops.quad_crop_u8), the ragged resize to the LR size and the collate kernel."""
+    the rectification of every region at its own size (ops.quad_crop_u8), the ragged resize to the LR size and the collate kernel.
+    photos=True (main.py --demo_paste): every tuple gains a last item (packed, meta, owners, quads) -- the batch's photos as uploaded
+    (the pack_ragged buffer on `device` and its host meta), and per region the index of its photo in the batch and its quadrilateral."""
     from .. import ops
     h, w = lr_size
-    for names, labels, packed, meta, regions in box_batches(dir_, box_dir, batch_size):
-        crops, crop_meta = ops.quad_crop_u8(packed.to(device, non_blocking=True), meta, regions)
-        yield names, labels, ops.collate_u8(ops.resize_ragged_u8(crops, crop_meta, h, w), mask)
+    for names, labels, packed, meta, regions, *quads in box_batches(dir_, box_dir, batch_size, quads=photos):
+        packed = packed.to(device, non_blocking=True)
+        crops, crop_meta = ops.quad_crop_u8(packed, meta, regions)
+        images_lr = ops.collate_u8(ops.resize_ragged_u8(crops, crop_meta, h, w), mask)
+        if photos:
+            yield names, labels, images_lr, (packed, meta, [r[0] for r in regions], quads[0])
+        else:
+            yield names, labels, images_lr
 
 
-def box_window_batches(dir_, box_dir, batch_size, lr_size, mask, device):
+def box_window_batches(dir_, box_dir, batch_size, lr_size, mask, device, photos=False):
     """folder_window_batches for whole photos with box files (main.py --demo_boxes --demo_tile): yields (region names, labels, plan,
     images_lr) per batch of box_batches -- every rectified region keeps its aspect ratio and is cut into overlapping windows of lr_size
     (ops.resize_windows_u8), plan as folder_window_batches yields it, over the batch's regions.  A region whose line would be wider than
-    utils.resize.MAX_SIDE (utils.tile.line_width of the REGION's size, not the photo's) is skipped with one printed line."""
+    utils.resize.MAX_SIDE (utils.tile.line_width of the REGION's size, not the photo's) is skipped with one printed line.
+    photos=True: a last item as box_region_batches yields it."""
     from .. import ops
     from ..utils.tile import line_width
     h, w = lr_size
-    for names, labels, packed, meta, regions in box_batches(dir_, box_dir, batch_size, check=lambda rh, rw, name: line_width(rh, rw, h, w)):
-        crops, crop_meta = ops.quad_crop_u8(packed.to(device, non_blocking=True), meta, regions)
+    for names, labels, packed, meta, regions, *quads in box_batches(dir_, box_dir, batch_size, check=lambda rh, rw, name: line_width(rh, rw, h, w),
+                                                                    quads=photos):
+        packed = packed.to(device, non_blocking=True)
+        crops, crop_meta = ops.quad_crop_u8(packed, meta, regions)
         windows, plan = ops.resize_windows_u8(crops, crop_meta, h, w)
-        yield names, labels, plan, ops.collate_u8(windows, mask)
+        images_lr = ops.collate_u8(windows, mask)
+        if photos:
+            yield names, labels, plan, images_lr, (packed, meta, [r[0] for r in regions], quads[0])
+        else:
+            yield names, labels, plan, images_lr
 
 
 class FolderHR(torch.utils.data.Dataset):

@@ -307,7 +307,8 @@ class TextSR(base.TextBase):
         return res
 
     @torch.no_grad()
-    def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None, boxes=False):
+    def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None, boxes=False, paste=False,
+             feather=1.0):
         """Super-resolve someone's own images (ours; main.py --demo_dir): batches yields (names, images_lr) as
         dataset.folder.folder_batches does.  Per batch `refine` (label_vecs from the frozen CRNN for tatt / tpgsr, as in eval), then
         save_image's quantisation on the GPU (ops.quantize_sr_u8), ONE device-to-host copy and one <stem>_sr.png per input under
@@ -327,7 +328,15 @@ class TextSR(base.TextBase):
         names being the region names <stem>_<k>.  A photo is never split, so a batch may hold more regions than the batch size: they
         go through `refine` in chunks of at most `chunk` (default: the batch size; a chunk of one is repeated as above).  One
         <stem>_<k>_sr.png per region; demo_result.csv then has the header file, box, label, lr_string, sr_string: the photo's stem,
-        the region's number k, its transcription from the box file.  Without boxes nothing changes."""
+        the region's number k, its transcription from the box file.  Without boxes nothing changes.
+        paste=True (main.py --demo_paste; needs boxes=True): the batches come from the same generators with photos=True, so every tuple
+        ends with the batch's uploaded photos and quadrilaterals.  Once a batch's regions are super-resolved, each of its photos is
+        enlarged by the scale factor on the GPU (ops.resize_ragged_u8 at the photo's own target size: PIL's bytes), its SR regions --
+        the very bytes of the <stem>_<k>_sr.png files, still on the device -- are pasted into their quadrilaterals in box-file order
+        (ops.paste_regions_u8, utils/paste.py; feather: the width of the blended edge in SR pixels, 0 for a hard edge), and the photo
+        is copied to the host once and written as <stem>_photo_sr.png.  A photo whose enlarged side would exceed
+        utils.resize.MAX_SIDE gets one printed line and no photo output; its regions are written.  The rows and demo_result.csv do
+        not change."""
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
         for m in model_list:
@@ -335,15 +344,20 @@ class TextSR(base.TextBase):
         fn = text_prior_fn or self.default_text_prior()
         os.makedirs(out_dir, exist_ok=True)
         rows, taken = [], set()
+        if paste and not boxes:
+            raise ValueError("demo: paste=True needs boxes=True (the quadrilaterals the SR regions are pasted into come from the box files)")
         if boxes:
             labels = []
-            for names, pixels, preds_lr, preds_sr in self._demo_regions(model_list, model_psn, batches, fn, reader, chunk, tile, labels):
+            for names, pixels, preds_lr, preds_sr, photos in self._demo_regions(model_list, model_psn, batches, fn, reader, chunk, tile, labels,
+                                                                                 float(feather) if paste else None):
                 self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken)
+                self._demo_write(out_dir, [stem + "_photo.png" for stem, _ in photos], [a for _, a in photos], [''] * len(photos),
+                                 [''] * len(photos), [], taken)
             # <stem>_<k>.png, lr, sr -> stem, k, label, lr, sr
             rows = [r[0][:-4].rsplit("_", 1) + [label] + r[1:] for r, label in zip(rows, labels)]
             batches = ()
         elif tile:
-            for names, pixels, preds_lr, preds_sr in self._demo_windows(model_list, model_psn, batches, fn, reader, chunk):
+            for names, pixels, preds_lr, preds_sr, _ in self._demo_windows(model_list, model_psn, batches, fn, reader, chunk):
                 self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken)
             batches = ()
         for names, images_lr in batches:
@@ -378,21 +392,28 @@ class TextSR(base.TextBase):
             Image.fromarray(a).save(os.path.join(out_dir, out_name))
             rows.append([name, str(s_lr), str(s_sr)])
 
-    def _demo_regions(self, model_list, model_psn, batches, fn, reader, chunk, tile, labels_out):
-        """demo(boxes=True): per batch of regions -> (names, one (H, W_r, 3) uint8 array per region, the LR reads, the SR reads); the
-        regions' labels are appended to labels_out.  tile: the batches carry a plan and go through _demo_windows."""
+    def _demo_regions(self, model_list, model_psn, batches, fn, reader, chunk, tile, labels_out, feather=None):
+        """demo(boxes=True): per batch of regions -> (names, one (H, W_r, 3) uint8 array per region, the LR reads, the SR reads, the
+        pasted photos); the regions' labels are appended to labels_out.  tile: the batches carry a plan and go through _demo_windows.
+        feather: None, or demo(paste=True)'s -- the batches then end with the photos item and the pasted photos are _demo_paste's list
+        (empty otherwise)."""
+        paste = feather is not None
         if tile:
+            held = []
+
             def windows():
-                for names, labels, plan, images_lr in batches:
+                for names, labels, plan, images_lr, *photos in batches:
                     labels_out.extend(labels)
+                    held[:] = photos
                     yield names, plan, images_lr
-            yield from self._demo_windows(model_list, model_psn, windows(), fn, reader, chunk)
+            for names, pixels, preds_lr, preds_sr, device in self._demo_windows(model_list, model_psn, windows(), fn, reader, chunk):
+                yield names, pixels, preds_lr, preds_sr, self._demo_paste(names, held[0], device[0], device[1], feather) if paste else []
             return
         chunk = max(int(chunk if chunk is not None else self.batch_size), 1)
-        for names, labels, images_lr in batches:
+        for names, labels, images_lr, *photos in batches:
             labels_out.extend(labels)
             images_lr = images_lr.to(self.device)
-            pixels, preds_lr, preds_sr = [], [], []
+            pixels, preds_lr, preds_sr, on_device = [], [], [], []
             for lo in range(0, images_lr.shape[0], chunk):
                 x = images_lr[lo:lo + chunk]
                 n = x.shape[0]
@@ -400,14 +421,56 @@ class TextSR(base.TextBase):
                     x = torch.cat([x, x], 0)
                 label_vecs = self.label_vecs_from_crnn(x) if self.args.arch in ('tatt', 'tpgsr') else None
                 sr = self.refine(model_list, model_psn, x, label_vecs, fn)[:n]
-                pixels.append(ops.quantize_sr_u8(sr).cpu().numpy())
+                q = ops.quantize_sr_u8(sr)
+                pixels.append(q.cpu().numpy())
+                if paste:
+                    on_device.append(q)
                 preds_lr += list(reader(x[:n, :3])) if reader is not None else [''] * n
                 preds_sr += list(reader(sr[:, :3])) if reader is not None else [''] * n
-            yield names, [a for p in pixels for a in p], preds_lr, preds_sr
+            pasted = []
+            if paste:
+                # the quantised regions of the batch, all H x W x 3: flat, they are pack_ragged's layout
+                q = on_device[0] if len(on_device) == 1 else torch.cat(on_device, 0)
+                R, H, W = q.shape[:3]
+                pasted = self._demo_paste(names, photos[0], q.reshape(-1), [(r * H * W * 3, H, W) for r in range(R)], feather)
+            yield names, [a for p in pixels for a in p], preds_lr, preds_sr, pasted
+
+    def _demo_paste(self, names, photos, sr_packed, sr_meta, feather):
+        """demo(paste=True): the photos of one batch with their SR regions pasted back -> [(stem, (scale * H, scale * W, 3) uint8
+        array)] in batch order.  photos = (packed, meta, owners, quads) as dataset.folder.box_region_batches(photos=True) yields it;
+        sr_packed / sr_meta hold the batch's SR regions on the device, one per name, in pack_ragged's layout.  Per photo: the enlargement
+        (ops.resize_ragged_u8 with a batch of one), ops.paste_regions_u8 with the photo's regions in box-file order, one copy to the
+        host.  A photo too large to enlarge, or a region utils.paste.paste_coeffs refuses, is passed over with one printed line."""
+        import numpy as np
+        from ..utils.paste import paste_coeffs
+        from ..utils.resize import MAX_SIDE
+        packed, meta, owners, quads = photos
+        meta = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta).astype(np.int64).reshape(-1, 3)
+        sr_meta = np.asarray(sr_meta, np.int64).reshape(-1, 3)
+        s = int(self.scale_factor)
+        out = []
+        for b, (_, H, W) in enumerate(meta.tolist()):
+            mine = [r for r, o in enumerate(owners) if o == b]
+            if not mine:
+                continue
+            stem = names[mine[0]].rsplit("_", 1)[0]
+            if s * H > MAX_SIDE or s * W > MAX_SIDE:
+                print("demo: no pasted photo for %s (%d x %d times %d: a side above %d is not resized)" % (stem, H, W, s, MAX_SIDE))
+                continue
+            regions = []
+            for r in mine:
+                try:
+                    regions.append((r, paste_coeffs(quads[r], s, int(sr_meta[r, 2]), int(sr_meta[r, 1])), feather))
+                except ValueError as e:
+                    print("demo: region %s is not pasted (%s)" % (names[r], e))
+            photo2 = ops.resize_ragged_u8(packed, meta[b:b + 1], s * H, s * W)[0]
+            out.append((stem, ops.paste_regions_u8(photo2, sr_packed, sr_meta, regions).cpu().numpy()))
+        return out
 
     def _demo_windows(self, model_list, model_psn, batches, fn, reader, chunk):
         """demo(tile=True): per batch (names, plan, images_lr) of windows -> (names, one (H, W_b, 3) uint8 array per image, the LR
-        reads, the SR reads), the reads of an image's windows joined with '|'."""
+        reads, the SR reads, (packed, meta)), the reads of an image's windows joined with '|'; packed / meta: the stitched lines as
+        ops.stitch_windows_u8 returns them, still on the device."""
         chunk = max(int(chunk if chunk is not None else self.batch_size), 1)
         for names, plan, images_lr in batches:
             images_lr = images_lr.to(self.device)
@@ -432,7 +495,7 @@ class TextSR(base.TextBase):
                 for (b, _), s_lr, s_sr in zip(plan, reads_lr, reads_sr):
                     preds_lr[b].append(s_lr)
                     preds_sr[b].append(s_sr)
-            yield names, pixels, ['|'.join(p) for p in preds_lr], ['|'.join(p) for p in preds_sr]
+            yield names, pixels, ['|'.join(p) for p in preds_lr], ['|'.join(p) for p in preds_sr], (packed, meta)
 
     # ------------------------------------------------------------------ training (super_resolution.py:113-278)
     def build_training(self, world_size=1, group=None):

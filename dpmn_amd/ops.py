@@ -575,6 +575,100 @@ def quad_crop_u8(packed, meta, regions):
     return out, host["meta"]
 
 
+PASTE_TILE = (8, 32)      # csrc/paste.hip PASTE_TILE_H, PASTE_TILE_W
+PASTE_MAX_TILES = 2 ** 31 - 1      # one block per tile in the grid's x dimension
+
+
+def _paste_regions_plan(photo2, sr_packed, sr_meta, regions):
+    """Checks and per-call host data of paste_regions_u8 -> host: the arrays of one call as numpy -- table (R, 12) int64 [byte offset of
+    the SR image, h_s, w_s, the bits of the float64 feather, the bits of the 8 float64 coefficients], tiles (n_tiles, 4) int32 [tile
+    row, tile column, first, count] in row-major tile order and list (n_list) int32: per tile the regions whose grown bounding box
+    (utils.paste.region_box) meets it, in the order of `regions` (_paste_regions_run)."""
+    import numpy as np
+    from .utils.paste import region_box
+    from .utils.resize import MAX_SIDE
+    what = "paste_regions_u8"
+    if not torch.is_tensor(photo2) or not photo2.is_cuda:
+        raise _abi.DpmnError("%s: the regions are pasted on the GPU (got a %s photo); there is no CPU fallback"
+                             % (what, photo2.device if torch.is_tensor(photo2) else type(photo2).__name__))
+    if photo2.dtype != torch.uint8 or photo2.dim() != 3 or photo2.shape[2] != 3 or not photo2.is_contiguous():
+        raise _abi.DpmnError("%s: a contiguous (H2, W2, 3) uint8 photo expected, got %s %s" % (what, photo2.dtype, tuple(photo2.shape)))
+    H2, W2 = int(photo2.shape[0]), int(photo2.shape[1])
+    if not (1 <= H2 <= MAX_SIDE and 1 <= W2 <= MAX_SIDE):
+        raise _abi.DpmnError("%s: the photo is %d x %d, sides outside 1 .. %d" % (what, H2, W2, MAX_SIDE))
+    m = _ragged_batch(sr_packed, sr_meta, what)
+    if sr_packed.device != photo2.device:
+        raise _abi.DpmnError("%s: the photo is on %s, the SR images on %s" % (what, photo2.device, sr_packed.device))
+    lo, hi = photo2.data_ptr(), photo2.data_ptr() + photo2.numel()
+    if sr_packed.data_ptr() < hi and lo < sr_packed.data_ptr() + sr_packed.numel():
+        raise _abi.DpmnError("%s: the photo and the SR buffer share storage (the photo is written while the SR images are read)" % what)
+    R = len(regions)
+    table = np.empty((R, 12), np.int64)
+    th, tw = PASTE_TILE
+    ntx = -(-W2 // tw)
+    ids, owners = [], []
+    for r, reg in enumerate(regions):
+        try:
+            k, coeffs, feather = reg
+            k, feather = int(k), float(feather)
+            a = np.asarray(coeffs, np.float64).reshape(-1)
+        except (TypeError, ValueError) as e:
+            raise _abi.DpmnError("%s: region %d is not (SR index, 8 coefficients, feather): %s" % (what, r, e)) from e
+        if not (0 <= k < m.shape[0] and a.size == 8 and np.isfinite(a).all() and np.isfinite(feather)):
+            raise _abi.DpmnError("%s: region %d names an SR image outside the batch of %d or does not carry 8 finite coefficients and a "
+                                 "finite feather" % (what, r, m.shape[0]))
+        table[r, :3] = m[k]
+        table[r, 3] = np.float64(feather).view(np.int64)
+        table[r, 4:] = a.view(np.int64)
+        x0, y0, x1, y1 = region_box(a, int(m[k, 2]), int(m[k, 1]), H2, W2)
+        if x1 <= x0 or y1 <= y0:
+            continue
+        rows, cols = np.arange(y0 // th, (y1 - 1) // th + 1, dtype=np.int64), np.arange(x0 // tw, (x1 - 1) // tw + 1, dtype=np.int64)
+        ids.append((rows[:, None] * ntx + cols[None, :]).reshape(-1))
+        owners.append(np.full(rows.size * cols.size, r, np.int32))
+    if not ids:
+        return dict(table=table, tiles=np.empty((0, 4), np.int32), list=np.empty(0, np.int32), size=(H2, W2))
+    ids, owners = np.concatenate(ids), np.concatenate(owners)
+    order = np.argsort(ids, kind="stable")      # by tile; within a tile the order of `regions` stays
+    uniq, first, count = np.unique(ids[order], return_index=True, return_counts=True)
+    if uniq.size > PASTE_MAX_TILES or ids.size > PASTE_MAX_TILES:
+        raise _abi.DpmnError("%s: the regions meet %d tiles (%d list entries), more than fit one launch" % (what, uniq.size, ids.size))
+    tiles = np.stack([uniq // ntx, uniq % ntx, first, count], axis=1).astype(np.int32)
+    return dict(table=table, tiles=tiles, list=np.ascontiguousarray(owners[order]), size=(H2, W2))
+
+
+def _paste_regions_run(photo2, sr_packed, host):
+    """One upload of the host arrays of _paste_regions_plan (the region table, the tiles and the region list in one int64 buffer) and the
+    launch -> the library's return code."""
+    import numpy as np
+    table, tiles, lst = (np.ascontiguousarray(host[k], dtype=t) for k, t in (("table", np.int64), ("tiles", np.int32), ("list", np.int32)))
+    R, n_tiles, n_list = table.shape[0], tiles.shape[0], lst.size
+    H2, W2 = host["size"]
+    if R == 0 or n_tiles == 0:
+        return 0
+    n_tile_words = (n_tiles * 4 + 1) // 2
+    buf = np.zeros(R * 12 + n_tile_words + (n_list + 1) // 2, np.int64)
+    buf[:R * 12] = table.reshape(-1)
+    buf[R * 12:R * 12 + n_tile_words].view(np.int32)[:n_tiles * 4] = tiles.reshape(-1)
+    buf[R * 12 + n_tile_words:].view(np.int32)[:n_list] = lst
+    d = torch.from_numpy(buf).to(photo2.device)
+    return lib.dpmn_paste_regions_u8(photo2.data_ptr(), H2, W2, sr_packed.data_ptr(), sr_packed.numel(), d.data_ptr(), table.ctypes.data, R,
+                                     d[R * 12:].data_ptr(), n_tiles, d[R * 12 + n_tile_words:].data_ptr(), n_list, stream())
+
+
+def paste_regions_u8(photo2, sr_packed, sr_meta, regions):
+    """The SR regions of one photo pasted back into the enlarged photo (csrc/paste.hip): photo2 a contiguous (H2, W2, 3) uint8 CUDA
+    tensor, modified IN PLACE and returned; sr_packed / sr_meta the SR images in utils.resize.pack_ragged's layout (what
+    stitch_windows_u8 returns; a contiguous quantize_sr_u8 output viewed flat has it too); regions a list of (SR index, coeffs, feather),
+    coeffs the 8 float64 coefficients of utils.paste.paste_coeffs, applied in list order -> byte for byte utils.paste.paste_regions_np,
+    in float64.  The host bins the regions into the 8 x 32 tiles of the photo that their grown bounding boxes meet; only those tiles are
+    launched, one thread per pixel, so no byte has two owners.  An empty list launches nothing.  Per call one buffer is uploaded: the
+    region table, the tiles and the per-tile region list."""
+    host = _paste_regions_plan(photo2, sr_packed, sr_meta, list(regions))
+    check(_paste_regions_run(photo2, sr_packed, host))
+    return photo2
+
+
 def maxpool(x, kh, kw, scale=None, shift=None):
     """nn.MaxPool2d((kh,kw), stride (kh,kw)) over NHWC; scale/shift: the producer's BatchNorm affine + ReLU applied on load."""
     B, H, W, Cc = x.shape

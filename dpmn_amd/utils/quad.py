@@ -124,23 +124,19 @@ def _cubic(v1, v2, v3, v4, d):
     return p1 + d * (p2 + d * (p3 + d * p4))
 
 
-def quad_crop_one(photo, h, w, coeffs):
-    """One region of quad_crop_np: photo (H, W, 3) uint8 -> (h, w, 3) uint8."""
-    H, W = check_image(photo, "photo")
-    h, w = int(h), int(w)
-    a = np.asarray(coeffs, np.float64).reshape(-1)
-    if a.size != 8 or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
-        raise ValueError("quad_crop: 8 coefficients and sides 1 .. %d expected, got %d and %d x %d" % (MAX_SIDE, a.size, h, w))
-    src = np.asarray(photo).astype(np.float64)
-    xin = (np.arange(w, dtype=np.float64) + 0.5)[None, :]
-    yin = (np.arange(h, dtype=np.float64) + 0.5)[:, None]
+def perspective_sample(src, xin, yin, coeffs):
+    """The sampling core of quad_crop_one, shared with utils/paste.py: src (H, W, 3) float64, xin (1, w) and yin (h, 1) the centres of
+    the output pixels, coeffs the 8 coefficients -> (bytes (h, w, 3) uint8, inside (h, w) bool, sx, sy): the source position of every
+    pixel BEFORE the -0.5 shift, whether it lies in 0 <= sx < W, 0 <= sy < H, and the truncated bicubic sample there (black outside)."""
+    H, W = src.shape[:2]
+    a = coeffs
     with np.errstate(all="ignore"):
         den = a[6] * xin + a[7] * yin + 1
-        sx = (a[0] * xin + a[1] * yin + a[2]) / den
-        sy = (a[3] * xin + a[4] * yin + a[5]) / den
-        inside = (sx >= 0) & (sx < W) & (sy >= 0) & (sy < H)      # (a NaN compares false: outside)
-        sx = np.where(inside, sx, 0.5) - 0.5
-        sy = np.where(inside, sy, 0.5) - 0.5
+        sx0 = (a[0] * xin + a[1] * yin + a[2]) / den
+        sy0 = (a[3] * xin + a[4] * yin + a[5]) / den
+        inside = (sx0 >= 0) & (sx0 < W) & (sy0 >= 0) & (sy0 < H)      # (a NaN compares false: outside)
+        sx = np.where(inside, sx0, 0.5) - 0.5
+        sy = np.where(inside, sy0, 0.5) - 0.5
     ix, iy = np.floor(sx), np.floor(sy)
     dx, dy = (sx - ix)[..., None], (sy - iy)[..., None]
     ix, iy = ix.astype(np.int64), iy.astype(np.int64)
@@ -155,7 +151,19 @@ def quad_crop_one(photo, h, w, coeffs):
     v = _cubic(*rows, dy)
     out = np.where(v <= 0, 0.0, np.where(v >= 255, 255.0, v)).astype(np.uint8)      # (truncation, as Geometry.c casts)
     out[~inside] = 0
-    return out
+    return out, inside, sx0, sy0
+
+
+def quad_crop_one(photo, h, w, coeffs):
+    """One region of quad_crop_np: photo (H, W, 3) uint8 -> (h, w, 3) uint8."""
+    check_image(photo, "photo")
+    h, w = int(h), int(w)
+    a = np.asarray(coeffs, np.float64).reshape(-1)
+    if a.size != 8 or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError("quad_crop: 8 coefficients and sides 1 .. %d expected, got %d and %d x %d" % (MAX_SIDE, a.size, h, w))
+    xin = (np.arange(w, dtype=np.float64) + 0.5)[None, :]
+    yin = (np.arange(h, dtype=np.float64) + 0.5)[:, None]
+    return perspective_sample(np.asarray(photo).astype(np.float64), xin, yin, a)[0]
 
 
 def quad_crop_np(images, regions):

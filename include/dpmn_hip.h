@@ -552,6 +552,24 @@ int dpmn_stitch_windows_u8(const float* sr, long batch_stride, long chan_stride,
  * computed.  A tile that names no region or lies outside its region writes nothing.  R = 0 launches nothing.  One launch. */
 int dpmn_quad_crop_u8(const unsigned char* packed, long packed_bytes, const long long* regions, const long long* regions_host /* HOST array */,
                       int R, const int* tiles, int n_tiles, unsigned char* out, long out_bytes, dpmn_stream_t stream);
+/* The SR regions pasted back into their enlarged photo (paste.hip; utils/paste.py holds the coefficients, the mask and the numpy
+ * restatement): photo, H2 x W2 x 3 uint8, is modified IN PLACE; sr holds the SR images in the packed layout of dpmn_resize_ragged_u8.
+ * Per region, in table order, and per pixel (X, Y) of the photo: sx = (a0 xin + a1 yin + a2) / (a6 xin + a7 yin + 1), sy likewise from
+ * a3 a4 a5, at xin = X + 0.5, yin = Y + 0.5; the pixel is touched only where 0 <= sx < w_s and 0 <= sy < h_s; the source byte is
+ * dpmn_quad_crop_u8's bicubic sample of the SR image; the mask m is 255 for feather <= 0, else with d = min(sx, w_s - sx, sy, h_s - sy)
+ * and t = d / feather it is 255 for t >= 1 and floor(t * 255 + 0.5) below; the byte becomes ((t >> 8) + t) >> 8 with
+ * t = dst * (255 - m) + src * m + 128 (PIL's Image.paste with an L mask).  float64, plain * + / in that order: independent of the
+ * compute mode.  regions: device int64 (R, 12), per region [byte offset of its SR image in sr, h_s, w_s, the bits of the float64
+ * feather, the bits of the 8 float64 coefficients a0 .. a7]; regions_host: the same table in HOST memory (the entry point checks it and
+ * refuses the call before the launch when an SR image does not fit sr or has a side outside 1 .. 8192; the kernel checks the device
+ * copy and skips such a region).  tiles: device int32 (n_tiles, 4), per 32 x 8 tile (w x h) of the photo [tile row, tile column, first,
+ * count]: its regions are list[first .. first + count), device int32 (n_list) indices into the table, applied in that order.  Every
+ * tile at most once: one block per tile, one thread per pixel, each byte of the photo has one owner.  A tile outside the photo or
+ * whose slice leaves the list writes nothing; a list entry outside the table is skipped.  photo and sr must not overlap.  R = 0 or
+ * n_tiles = 0 launches nothing.  One launch. */
+int dpmn_paste_regions_u8(unsigned char* photo, int H2, int W2, const unsigned char* sr, long sr_bytes, const long long* regions,
+                          const long long* regions_host /* HOST array */, int R, const int* tiles, int n_tiles, const int* list, int n_list,
+                          dpmn_stream_t stream);
 
 /* rotation augmentation of the trainer (utils/util.py:37-58 torch_rotate_img; super_resolution.py:144-151, 358-365):
  * per-image affine with aspect-ratio jitter -> affine_grid (align_corners=False) -> bilinear grid_sample, zeros padding.

@@ -9,7 +9,9 @@ batches of the real shapes -- `--synthetic_steps` of them -- and the text priors
 everything between the loader and the optimizer step is the real path.  `--demo_dir DIR --resume CKPT` super-resolves a folder of images
 (any sizes; resized on the GPU) into `--demo_out`; with `--demo_tile` a wide image keeps its aspect ratio and goes through the model in
 overlapping windows; with `--demo_boxes BOXDIR` the folder holds whole photos and BOXDIR one text file of quadrilaterals per photo, each
-rectified on the GPU and super-resolved as a crop of its own.  `--train_state PATH` makes a training run continuable: the same command line starts the
+rectified on the GPU and super-resolved as a crop of its own; with `--demo_paste` on top every photo is also enlarged by the scale factor on
+the GPU, its SR regions are warped back into their quadrilaterals and blended in (`--demo_paste_feather F`: the width of the blended edge
+in SR pixels, 0 for a hard edge), and written as `<stem>_photo_sr.png`.  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
 (`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
@@ -64,6 +66,18 @@ def recogniser(mission, args):
 
 
 DEMO_BOXES_NEEDS_DIR = "main.py: --demo_boxes needs --demo_dir: the photos whose regions the box files name are read from that folder"
+DEMO_PASTE_NEEDS_BOXES = "main.py: --demo_paste needs --demo_boxes: the SR regions are pasted back into the quadrilaterals that the box files name"
+DEMO_PASTE_FEATHER = "main.py: --demo_paste_feather must be a finite number >= 0 (the width of the blended edge in SR pixels; 0: a hard edge)"
+
+
+def paste_feather(args):
+    """--demo_paste_feather as a float, checked; 1.0 when the flag is absent."""
+    import math
+    f = getattr(args, "demo_paste_feather", None)
+    f = 1.0 if f is None else float(f)
+    if not (math.isfinite(f) and f >= 0):
+        raise ValueError(DEMO_PASTE_FEATHER[len("main.py: "):])
+    return f
 
 
 def main(config, args):
@@ -82,6 +96,12 @@ def main(config, args):
         raise SystemExit("main.py: --demo_tile needs --demo_dir: it super-resolves the wide images of that folder in overlapping windows")
     if getattr(args, "demo_boxes", None) and not getattr(args, "demo_dir", None):
         raise SystemExit(DEMO_BOXES_NEEDS_DIR)
+    if getattr(args, "demo_paste", False) and not getattr(args, "demo_boxes", None):
+        raise SystemExit(DEMO_PASTE_NEEDS_BOXES)
+    try:
+        feather = paste_feather(args)
+    except ValueError as e:
+        raise SystemExit("main.py: %s" % e)
     hr_dir = getattr(args, "train_hr_dir", None)
     if hr_dir and not os.path.isdir(hr_dir):
         raise SystemExit("main.py: --train_hr_dir %s is not a directory" % hr_dir)
@@ -122,8 +142,14 @@ def main(config, args):
             if not os.path.isdir(box_dir):
                 raise SystemExit("main.py: --demo_boxes %s is not a directory" % box_dir)
             tile = bool(getattr(args, "demo_tile", False))
-            batches = (box_window_batches if tile else box_region_batches)(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device)
-            rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True)
+            make = box_window_batches if tile else box_region_batches
+            if getattr(args, "demo_paste", False):
+                # every photo enlarged and its SR regions pasted back into their quadrilaterals: <stem>_photo_sr.png (utils/paste.py)
+                batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device, photos=True)
+                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, paste=True, feather=feather)
+            else:
+                batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device)
+                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True)
             print("%d regions super-resolved into %s" % (len(rows), out_dir))
             return
         if getattr(args, "demo_tile", False):
@@ -241,6 +267,13 @@ if __name__ == '__main__':
                         help='with --demo_dir: the folder holds whole photos, and BOXDIR one text file per photo (<stem>.txt or '
                              'gt_<stem>.txt, lines x1,y1,x2,y2,x3,y3,x4,y4[,transcription], corners clockwise from top-left); every '
                              'quadrilateral is rectified on the GPU and super-resolved (combines with --demo_tile)')
+    parser.add_argument('--demo_paste', action='store_true', default=False,
+                        help='with --demo_boxes: every photo is also enlarged by the scale factor and its super-resolved regions are '
+                             'pasted back into their quadrilaterals on the GPU: one <stem>_photo_sr.png per photo (combines with '
+                             '--demo_tile and --rec)')
+    parser.add_argument('--demo_paste_feather', type=float, default=1.0, metavar='F',
+                        help='with --demo_paste: the width, in SR pixels, of the edge over which a pasted region is blended into the '
+                             'photo (>= 0; 0 gives a hard edge)')
     parser.add_argument('--gpu_resize', action='store_true', default=False,
                         help='TextZoom loaders: the bicubic resize of the decoded images runs on the GPU (same bytes as PIL)')
     parser.add_argument('--train_state', type=str, default=None,
@@ -262,6 +295,12 @@ if __name__ == '__main__':
     args = parser.parse_args()
     if args.demo_boxes and not args.demo_dir:
         parser.error(DEMO_BOXES_NEEDS_DIR[len("main.py: "):])
+    if args.demo_paste and not args.demo_boxes:
+        parser.error(DEMO_PASTE_NEEDS_BOXES[len("main.py: "):])
+    try:
+        paste_feather(args)
+    except ValueError as e:
+        parser.error(str(e))
     config_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config', 'super_resolution.yaml')
     config = AttrDict(yaml.load(open(config_path, 'r'), Loader=yaml.Loader))
     main(config, args)
