@@ -8,7 +8,9 @@ the GPU (dataset/textzoom.py, alignCollate_realWTLAMask(degrade=True) and sr_bat
 `box_batches` / `box_region_batches` / `box_window_batches` (main.py --demo_boxes): a directory of WHOLE photos and a directory of box
 files (one quadrilateral per word, utils/quad.py); every region is rectified on the GPU (ops.quad_crop_u8) and then takes the path of a
 crop of the folder.  With photos=True (main.py --demo_paste) the two generators also hand out the uploaded photos and the
-quadrilaterals, which TextSR.demo(paste=True) needs to put the SR regions back (utils/paste.py).
+quadrilaterals, which TextSR.demo(paste=True) needs to put the SR regions back (utils/paste.py).  With polygons=True (main.py
+--demo_polygons) a line of a box file may name a curved word by a polygon of more than 4 points (utils/poly.py): it is rectified strip
+by strip (ops.poly_crop_u8) into the same packed buffer as the quadrilaterals (ops.crop_regions_u8).
 """
 import os
 
@@ -77,7 +79,7 @@ def folder_window_batches(dir_, batch_size, lr_size, mask, device):
         yield names, plan, ops.collate_u8(windows, mask)
 
 
-def box_batches(dir_, box_dir, batch_size, check=None, quads=False):
+def box_batches(dir_, box_dir, batch_size, check=None, quads=False, polygons=False):
     """The host half of the box path: yields (region names, labels, packed, meta, regions) per batch -- packed / meta =
     utils.resize.pack_ragged of the batch's photos, regions = the list of (photo index in the batch, h, w, coeffs) that
     ops.quad_crop_u8 takes (utils.quad: quad_size and quad_coeffs of every quadrilateral), names and labels one per region.
@@ -89,8 +91,14 @@ def box_batches(dir_, box_dir, batch_size, check=None, quads=False):
     that raises ValueError for a region size it rejects) refuses, naming the photo and the line.  A photo is never split: a batch
     closes once it holds at least batch_size regions, or once the next photo would exceed utils.resize.MAX_PACKED_BYTES.  A directory
     without files raises.  quads=True: every tuple gains a last item, the float64 (4, 2) quadrilateral of every region in photo
-    coordinates (the default leaves the tuples as they are)."""
+    coordinates (the default leaves the tuples as they are).
+    polygons=True: the box files are read with utils.poly.numbered_polygons.  A line of 4 points is the quadrilateral it is without the
+    flag, with the same region; a line of more points is a polygon, checked with utils.poly.check_polygon, and its region is (photo
+    index, h, w, cells) of polygon_plan and polygon_cells -- what ops.poly_crop_u8 takes, ops.crop_regions_u8 a list of both kinds.  A
+    polygon that check_polygon, polygon_plan or `check` refuses is skipped like a refused quadrilateral; with quads=True a polygon's
+    item is its float64 (2k, 2) points."""
     from PIL import Image
+    from ..utils.poly import check_polygon, numbered_polygons, polygon_cells, polygon_plan
     from ..utils.quad import check_quad, numbered_boxes, quad_coeffs, quad_size
     from ..utils.resize import MAX_PACKED_BYTES, check_image, pack_ragged
     batch_size = int(batch_size)
@@ -109,11 +117,16 @@ def box_batches(dir_, box_dir, batch_size, check=None, quads=False):
             print("folder: skipping %s (no box file %s.txt or gt_%s.txt in %s)" % (f, stem, stem, box_dir))
             continue
         found = []
-        for k, lineno, quad, label in numbered_boxes(box_file):
+        for k, lineno, quad, label in (numbered_polygons if polygons else numbered_boxes)(box_file):
             try:
-                check_quad(quad)
-                h, w = quad_size(quad)
-                coeffs = quad_coeffs(quad, w, h)
+                if len(quad) > 4:      # (polygons only: a curved line, its cells in the place of the 8 coefficients)
+                    check_polygon(quad)
+                    h, w, xs = polygon_plan(quad)
+                    coeffs = polygon_cells(quad, h, xs)
+                else:
+                    check_quad(quad)
+                    h, w = quad_size(quad)
+                    coeffs = quad_coeffs(quad, w, h)
                 if check is not None:
                     check(h, w, "%s_%03d" % (stem, k))
             except ValueError as e:
@@ -147,17 +160,18 @@ def box_batches(dir_, box_dir, batch_size, check=None, quads=False):
         yield (names, labels) + pack_ragged(images) + ((regions, corners) if quads else (regions,))
 
 
-def box_region_batches(dir_, box_dir, batch_size, lr_size, mask, device, photos=False):
+def box_region_batches(dir_, box_dir, batch_size, lr_size, mask, device, photos=False, polygons=False):
     """folder_batches for whole photos with box files (main.py --demo_boxes): yields (region names, labels, images_lr) per batch of
     box_batches, images_lr (R, 3 + mask, h, w) float on `device`, (h, w) = lr_size.  Per batch one upload of the packed photos, then
     the rectification of every region at its own size (ops.quad_crop_u8), the ragged resize to the LR size and the collate kernel.
     photos=True (main.py --demo_paste): every tuple gains a last item (packed, meta, owners, quads) -- the batch's photos as uploaded
-    (the pack_ragged buffer on `device` and its host meta), and per region the index of its photo in the batch and its quadrilateral."""
+    (the pack_ragged buffer on `device` and its host meta), and per region the index of its photo in the batch and its quadrilateral.
+    polygons=True (main.py --demo_polygons): box_batches' -- polygons are rectified too (ops.crop_regions_u8), in box-file order."""
     from .. import ops
     h, w = lr_size
-    for names, labels, packed, meta, regions, *quads in box_batches(dir_, box_dir, batch_size, quads=photos):
+    for names, labels, packed, meta, regions, *quads in box_batches(dir_, box_dir, batch_size, quads=photos, polygons=polygons):
         packed = packed.to(device, non_blocking=True)
-        crops, crop_meta = ops.quad_crop_u8(packed, meta, regions)
+        crops, crop_meta = (ops.crop_regions_u8 if polygons else ops.quad_crop_u8)(packed, meta, regions)
         images_lr = ops.collate_u8(ops.resize_ragged_u8(crops, crop_meta, h, w), mask)
         if photos:
             yield names, labels, images_lr, (packed, meta, [r[0] for r in regions], quads[0])
@@ -165,19 +179,19 @@ def box_region_batches(dir_, box_dir, batch_size, lr_size, mask, device, photos=
             yield names, labels, images_lr
 
 
-def box_window_batches(dir_, box_dir, batch_size, lr_size, mask, device, photos=False):
+def box_window_batches(dir_, box_dir, batch_size, lr_size, mask, device, photos=False, polygons=False):
     """folder_window_batches for whole photos with box files (main.py --demo_boxes --demo_tile): yields (region names, labels, plan,
     images_lr) per batch of box_batches -- every rectified region keeps its aspect ratio and is cut into overlapping windows of lr_size
     (ops.resize_windows_u8), plan as folder_window_batches yields it, over the batch's regions.  A region whose line would be wider than
     utils.resize.MAX_SIDE (utils.tile.line_width of the REGION's size, not the photo's) is skipped with one printed line.
-    photos=True: a last item as box_region_batches yields it."""
+    photos=True: a last item as box_region_batches yields it.  polygons=True: as box_region_batches takes it."""
     from .. import ops
     from ..utils.tile import line_width
     h, w = lr_size
     for names, labels, packed, meta, regions, *quads in box_batches(dir_, box_dir, batch_size, check=lambda rh, rw, name: line_width(rh, rw, h, w),
-                                                                    quads=photos):
+                                                                    quads=photos, polygons=polygons):
         packed = packed.to(device, non_blocking=True)
-        crops, crop_meta = ops.quad_crop_u8(packed, meta, regions)
+        crops, crop_meta = (ops.crop_regions_u8 if polygons else ops.quad_crop_u8)(packed, meta, regions)
         windows, plan = ops.resize_windows_u8(crops, crop_meta, h, w)
         images_lr = ops.collate_u8(windows, mask)
         if photos:

@@ -336,7 +336,9 @@ class TextSR(base.TextBase):
         (ops.paste_regions_u8, utils/paste.py; feather: the width of the blended edge in SR pixels, 0 for a hard edge), and the photo
         is copied to the host once and written as <stem>_photo_sr.png.  A photo whose enlarged side would exceed
         utils.resize.MAX_SIDE gets one printed line and no photo output; its regions are written.  The rows and demo_result.csv do
-        not change."""
+        not change.
+        Batches made with polygons=True (main.py --demo_polygons) need nothing here: a rectified polygon (utils/poly.py) is a region
+        like any other, with or without tile.  With paste=True the polygons' SR regions are written as files but not pasted."""
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
         for m in model_list:
@@ -440,7 +442,9 @@ class TextSR(base.TextBase):
         array)] in batch order.  photos = (packed, meta, owners, quads) as dataset.folder.box_region_batches(photos=True) yields it;
         sr_packed / sr_meta hold the batch's SR regions on the device, one per name, in pack_ragged's layout.  Per photo: the enlargement
         (ops.resize_ragged_u8 with a batch of one), ops.paste_regions_u8 with the photo's regions in box-file order, one copy to the
-        host.  A photo too large to enlarge, or a region utils.paste.paste_coeffs refuses, is passed over with one printed line."""
+        host.  A photo too large to enlarge, or a region utils.paste.paste_coeffs refuses, is passed over with one printed line.  The
+        regions of polygons (more than 4 points: the batches were made with polygons=True) are not pasted -- one printed line per photo
+        gives their count."""
         import numpy as np
         from ..utils.paste import paste_coeffs
         from ..utils.resize import MAX_SIDE
@@ -457,8 +461,14 @@ class TextSR(base.TextBase):
             if s * H > MAX_SIDE or s * W > MAX_SIDE:
                 print("demo: no pasted photo for %s (%d x %d times %d: a side above %d is not resized)" % (stem, H, W, s, MAX_SIDE))
                 continue
+            curved = [r for r in mine if len(quads[r]) > 4]
+            if curved:
+                print("demo: %d polygon region%s of %s not pasted (only quadrilaterals are warped back)"
+                      % (len(curved), "" if len(curved) == 1 else "s", stem))
             regions = []
             for r in mine:
+                if r in curved:
+                    continue
                 try:
                     regions.append((r, paste_coeffs(quads[r], s, int(sr_meta[r, 2]), int(sr_meta[r, 1])), feather))
                 except ValueError as e:

@@ -506,6 +506,21 @@ def stitch_windows_u8(sr, plan, scale=2):
 QUAD_TILE = (8, 32)      # csrc/quad.hip QUAD_TILE_H, QUAD_TILE_W
 
 
+def _region_tiles(hs, ws):
+    """The tile table of quad_crop_u8 and poly_crop_u8: int32 (n_tiles, 3) [region, tile row, tile column], every QUAD_TILE tile of every
+    h x w region, region after region in row-major tile order."""
+    import numpy as np
+    th, tw = -(-hs // QUAD_TILE[0]), -(-ws // QUAD_TILE[1])
+    tfirst = np.concatenate(([0], np.cumsum(th * tw)))
+    tiles = np.empty((int(tfirst[-1]), 3), np.int32)
+    for r in range(len(hs)):
+        t = tiles[tfirst[r]:tfirst[r + 1]]
+        t[:, 0] = r
+        t[:, 1] = np.repeat(np.arange(th[r]), tw[r])
+        t[:, 2] = np.tile(np.arange(tw[r]), th[r])
+    return tiles
+
+
 def _quad_crop_plan(packed, meta, regions):
     """Checks and per-call host data of quad_crop_u8 -> host: the arrays of one call as numpy -- table (R, 14) int64 [byte offset of the
     photo, H, W, byte offset of the region in the output, h, w, the bits of the 8 float64 coefficients], tiles (n_tiles, 3) int32
@@ -533,24 +548,18 @@ def _quad_crop_plan(packed, meta, regions):
     if first[-1] > MAX_PACKED_BYTES:
         raise _abi.DpmnError("quad_crop_u8: the regions hold more than 2^31 - 1 bytes")
     table[:, 3] = first[:-1]
-    th, tw = -(-table[:, 4] // QUAD_TILE[0]), -(-table[:, 5] // QUAD_TILE[1])
-    tfirst = np.concatenate(([0], np.cumsum(th * tw)))
-    tiles = np.empty((int(tfirst[-1]), 3), np.int32)
-    for r in range(R):
-        t = tiles[tfirst[r]:tfirst[r + 1]]
-        t[:, 0] = r
-        t[:, 1] = np.repeat(np.arange(th[r]), tw[r])
-        t[:, 2] = np.tile(np.arange(tw[r]), th[r])
-    return dict(table=table, tiles=tiles, meta=np.ascontiguousarray(table[:, 3:6]), out_bytes=int(first[-1]))
+    return dict(table=table, tiles=_region_tiles(table[:, 4], table[:, 5]), meta=np.ascontiguousarray(table[:, 3:6]), out_bytes=int(first[-1]))
 
 
-def _quad_crop_run(packed, host):
+def _quad_crop_run(packed, host, out=None):
     """One upload of the host arrays of _quad_crop_plan (the region table and the tiles in one int64 buffer) and the launch ->
-    (the packed regions, the library's return code): the output exists whatever the code says."""
+    (the packed regions, the library's return code): the output exists whatever the code says.  out: a zeroed buffer of
+    host["out_bytes"] bytes that the regions are written into (crop_regions_u8: shared with poly_crop_u8's regions)."""
     import numpy as np
     table, tiles = np.ascontiguousarray(host["table"], dtype=np.int64), np.ascontiguousarray(host["tiles"], dtype=np.int32)
     R, n_tiles, dev = table.shape[0], tiles.shape[0], packed.device
-    out = torch.zeros(host["out_bytes"], dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.zeros(host["out_bytes"], dtype=torch.uint8, device=dev)
     if R == 0:
         return out, lib.dpmn_quad_crop_u8(packed.data_ptr(), packed.numel(), None, None, 0, None, 0, None, 0, stream())
     buf = np.zeros(R * 14 + (n_tiles * 3 + 1) // 2, np.int64)
@@ -573,6 +582,112 @@ def quad_crop_u8(packed, meta, regions):
     out, code = _quad_crop_run(packed, host)
     check(code)
     return out, host["meta"]
+
+
+POLY_MAX_CELLS = 31      # csrc/poly.hip POLY_MAX_CELLS = utils.poly.MAX_POLY_SIDE - 1; its tiles are QUAD_TILE's
+
+
+def _poly_crop_plan(packed, meta, regions):
+    """Checks and per-call host data of poly_crop_u8 -> host: the arrays of one call as numpy -- table (R, 8) int64 [byte offset of the
+    photo, H, W, byte offset of the region in the output, h, w, first cell, cell count], cells (C, 10) int64 [x0, x1, the bits of the 8
+    float64 coefficients], tiles (n_tiles, 3) int32 [region, tile row, tile column], meta (R, 3) int64 (byte offset, h, w) of the
+    output, and its size in bytes (_poly_crop_run)."""
+    import numpy as np
+    from .utils.poly import check_cells
+    from .utils.resize import MAX_PACKED_BYTES, MAX_SIDE
+    m = _ragged_batch(packed, meta, "poly_crop_u8")
+    R = len(regions)
+    table, cells = np.empty((R, 8), np.int64), []
+    for r, reg in enumerate(regions):
+        try:
+            b, h, w, reg_cells = reg
+            b, h, w = int(b), int(h), int(w)
+            if not (0 <= b < m.shape[0] and 1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+                raise ValueError("it names a photo outside the batch of %d or a side outside 1 .. %d" % (m.shape[0], MAX_SIDE))
+            bounds, coeffs = check_cells(h, w, reg_cells)
+            if not np.isfinite(coeffs).all():
+                raise ValueError("a coefficient is not finite")
+        except (TypeError, ValueError) as e:
+            raise _abi.DpmnError("poly_crop_u8: region %d is not (photo index, h, w, cells (x0, x1, 8 coefficients)): %s" % (r, e)) from e
+        table[r, :3] = m[b]
+        table[r, 4:] = h, w, sum(c.shape[0] for c in cells), bounds.shape[0]
+        cells.append(np.concatenate([bounds, coeffs.view(np.int64)], axis=1))
+    sizes = table[:, 4] * table[:, 5] * 3
+    first = np.concatenate(([0], np.cumsum(sizes)))
+    if first[-1] > MAX_PACKED_BYTES:
+        raise _abi.DpmnError("poly_crop_u8: the regions hold more than 2^31 - 1 bytes")
+    table[:, 3] = first[:-1]
+    return dict(table=table, cells=np.concatenate(cells) if cells else np.empty((0, 10), np.int64), tiles=_region_tiles(table[:, 4], table[:, 5]),
+                meta=np.ascontiguousarray(table[:, 3:6]), out_bytes=int(first[-1]))
+
+
+def _poly_crop_run(packed, host, out=None):
+    """One upload of the host arrays of _poly_crop_plan (the region table, the cells and the tiles in one int64 buffer) and the launch
+    -> (the packed regions, the library's return code): the output exists whatever the code says.  out: as _quad_crop_run takes it."""
+    import numpy as np
+    table, cells, tiles = (np.ascontiguousarray(host[k], dtype=t) for k, t in (("table", np.int64), ("cells", np.int64), ("tiles", np.int32)))
+    R, C, n_tiles, dev = table.shape[0], cells.shape[0], tiles.shape[0], packed.device
+    if out is None:
+        out = torch.zeros(host["out_bytes"], dtype=torch.uint8, device=dev)
+    if R == 0:
+        return out, lib.dpmn_poly_crop_u8(packed.data_ptr(), packed.numel(), None, None, 0, None, None, 0, None, 0, None, 0, stream())
+    buf = np.zeros(R * 8 + C * 10 + (n_tiles * 3 + 1) // 2, np.int64)
+    buf[:R * 8] = table.reshape(-1)
+    buf[R * 8:R * 8 + C * 10] = cells.reshape(-1)
+    buf[R * 8 + C * 10:].view(np.int32)[:n_tiles * 3] = tiles.reshape(-1)
+    d = torch.from_numpy(buf).to(dev)
+    return out, lib.dpmn_poly_crop_u8(packed.data_ptr(), packed.numel(), d.data_ptr(), table.ctypes.data, R, d[R * 8:].data_ptr(),
+                                      cells.ctypes.data, C, d[R * 8 + C * 10:].data_ptr(), n_tiles, out.data_ptr(), out.numel(), stream())
+
+
+def poly_crop_u8(packed, meta, regions):
+    """Curved text regions of a ragged batch of photos, rectified (csrc/poly.hip): packed / meta as resize_ragged_u8 takes them,
+    regions = a list of (photo index, h, w, cells), cells the list of (x0, x1, 8 float64 coefficients) of utils.poly.polygon_cells -- at
+    most POLY_MAX_CELLS, their bounds ascending from 0 to w without a gap -> (packed_regions, region_meta) in quad_crop_u8's layout, what
+    resize_ragged_u8 and resize_windows_u8 take.  Per region byte for byte np.asarray(Image.fromarray(photo).transform((w, h),
+    Image.MESH, cells, Image.BICUBIC)) = utils.poly.poly_crop_np, in float64.  A region may reach outside its photo (black there).  An
+    empty list gives empty outputs and launches nothing.  Per call one buffer is uploaded: the region table, the cells and the tiles."""
+    host = _poly_crop_plan(packed, meta, list(regions))
+    out, code = _poly_crop_run(packed, host)
+    check(code)
+    return out, host["meta"]
+
+
+def _has_cells(region):
+    """Whether a region's 4th item is poly_crop_u8's list of cells (x0, x1, coefficients) and not quad_crop_u8's 8 coefficients."""
+    g = region[3] if isinstance(region, (tuple, list)) and len(region) == 4 else None
+    return isinstance(g, (tuple, list)) and len(g) > 0 and isinstance(g[0], (tuple, list))
+
+
+def crop_regions_u8(packed, meta, regions):
+    """quad_crop_u8 and poly_crop_u8 over one list (dataset/folder.py with polygons=True): a region whose 4th item is a list of cells is
+    rectified as a polygon, any other as a quadrilateral, and the regions lie in list order in ONE packed buffer -> (packed_regions,
+    region_meta) as either op returns them.  Each kernel is launched once over its own regions with the byte offsets of the shared
+    buffer in its table: no region is copied.  A list without polygons is quad_crop_u8 (and one without quadrilaterals poly_crop_u8)."""
+    import numpy as np
+    from .utils.resize import MAX_PACKED_BYTES
+    regions = list(regions)
+    poly = [_has_cells(r) for r in regions]
+    if not any(poly):
+        return quad_crop_u8(packed, meta, regions)
+    if all(poly):
+        return poly_crop_u8(packed, meta, regions)
+    hosts = [plan(packed, meta, [r for r, p in zip(regions, poly) if p == want])
+             for plan, want in ((_quad_crop_plan, False), (_poly_crop_plan, True))]
+    out_meta = np.empty((len(regions), 3), np.int64)
+    for host, want in zip(hosts, (False, True)):
+        out_meta[[i for i, p in enumerate(poly) if p == want], 1:] = host["meta"][:, 1:]
+    sizes = out_meta[:, 1] * out_meta[:, 2] * 3
+    out_meta[:, 0] = np.concatenate(([0], np.cumsum(sizes[:-1])))
+    total = int(sizes.sum())
+    if total > MAX_PACKED_BYTES:
+        raise _abi.DpmnError("crop_regions_u8: the regions hold more than 2^31 - 1 bytes")
+    out = torch.zeros(total, dtype=torch.uint8, device=packed.device)
+    for host, want, run in zip(hosts, (False, True), (_quad_crop_run, _poly_crop_run)):
+        host["table"][:, 3] = out_meta[[i for i, p in enumerate(poly) if p == want], 0]
+        host["out_bytes"] = total
+        check(run(packed, host, out)[1])
+    return out, out_meta
 
 
 PASTE_TILE = (8, 32)      # csrc/paste.hip PASTE_TILE_H, PASTE_TILE_W

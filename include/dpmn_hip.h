@@ -570,6 +570,23 @@ int dpmn_quad_crop_u8(const unsigned char* packed, long packed_bytes, const long
 int dpmn_paste_regions_u8(unsigned char* photo, int H2, int W2, const unsigned char* sr, long sr_bytes, const long long* regions,
                           const long long* regions_host /* HOST array */, int R, const int* tiles, int n_tiles, const int* list, int n_list,
                           dpmn_stream_t stream);
+/* Curved text regions of whole photos, rectified (poly.hip; utils/poly.py holds the polygon reader, the cells and the numpy
+ * restatement): dpmn_quad_crop_u8's layouts, but a region is a polygon cut into strips -- byte for byte PIL's Image.transform((w, h),
+ * MESH, cells, BICUBIC).  A cell is the columns x0 <= x < x1 of its region and 8 coefficients of PIL's bilinear QUAD transform; per
+ * output pixel (x, y) in that cell: xin = (x - x0) + 0.5, yin = y + 0.5, sx = a0 + a1 xin + a2 yin + a3 xin yin, sy likewise from
+ * a4 .. a7; black outside 0 <= sx < W, 0 <= sy < H, else dpmn_quad_crop_u8's bicubic sample.  float64, plain * + in that order:
+ * independent of the compute mode.  regions: device int64 (R, 8), per region [byte offset of its photo in packed, H, W, byte offset of
+ * the region in out, h, w, first cell, cell count]; cells: device int64 (n_cells, 10), per cell [x0, x1, the bits of the 8 float64
+ * coefficients a0 .. a7]; regions_host, cells_host: the same tables in HOST memory (the entry point checks them, the kernel checks the
+ * device copies); tiles: device int32 (n_tiles, 3), per 32 x 8 tile (w x h) [region, tile row, tile column]: one block per tile, one
+ * thread per pixel, which searches its region's cell bounds.  Sides 1 .. 8192, 1 .. 31 cells per region, their bounds ascending from 0
+ * to w without a gap.  A region whose photo does not fit packed, whose cells leave the cell table or whose bounds are not such is not
+ * read and comes out black, one whose own extent does not fit out is not written, and the call then returns DPMN_ERR_ARG after the
+ * launch -- the other regions are computed.  A tile that names no region or lies outside its region writes nothing.  R = 0 launches
+ * nothing.  One launch. */
+int dpmn_poly_crop_u8(const unsigned char* packed, long packed_bytes, const long long* regions, const long long* regions_host /* HOST array */,
+                      int R, const long long* cells, const long long* cells_host /* HOST array */, int n_cells, const int* tiles, int n_tiles,
+                      unsigned char* out, long out_bytes, dpmn_stream_t stream);
 
 /* rotation augmentation of the trainer (utils/util.py:37-58 torch_rotate_img; super_resolution.py:144-151, 358-365):
  * per-image affine with aspect-ratio jitter -> affine_grid (align_corners=False) -> bilinear grid_sample, zeros padding.

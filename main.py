@@ -11,12 +11,15 @@ everything between the loader and the optimizer step is the real path.  `--demo_
 overlapping windows; with `--demo_boxes BOXDIR` the folder holds whole photos and BOXDIR one text file of quadrilaterals per photo, each
 rectified on the GPU and super-resolved as a crop of its own; with `--demo_paste` on top every photo is also enlarged by the scale factor on
 the GPU, its SR regions are warped back into their quadrilaterals and blended in (`--demo_paste_feather F`: the width of the blended edge
-in SR pixels, 0 for a hard edge), and written as `<stem>_photo_sr.png`.  `--train_state PATH` makes a training run continuable: the same command line starts the
+in SR pixels, 0 for a hard edge), and written as `<stem>_photo_sr.png`; with `--demo_polygons` a line of a box file may also name a curved
+word by a polygon (2k points, k along the top edge and k along the bottom, as CTW1500 and Total-Text write them), which is straightened
+strip by strip on the GPU (polygon regions are written as files but not pasted).  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
 (`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
 import argparse
 import csv
+import functools
 import os
 
 import yaml
@@ -67,6 +70,7 @@ def recogniser(mission, args):
 
 DEMO_BOXES_NEEDS_DIR = "main.py: --demo_boxes needs --demo_dir: the photos whose regions the box files name are read from that folder"
 DEMO_PASTE_NEEDS_BOXES = "main.py: --demo_paste needs --demo_boxes: the SR regions are pasted back into the quadrilaterals that the box files name"
+DEMO_POLYGONS_NEEDS_BOXES = "main.py: --demo_polygons needs --demo_boxes: the polygons of curved words are read from the box files"
 DEMO_PASTE_FEATHER = "main.py: --demo_paste_feather must be a finite number >= 0 (the width of the blended edge in SR pixels; 0: a hard edge)"
 
 
@@ -98,6 +102,8 @@ def main(config, args):
         raise SystemExit(DEMO_BOXES_NEEDS_DIR)
     if getattr(args, "demo_paste", False) and not getattr(args, "demo_boxes", None):
         raise SystemExit(DEMO_PASTE_NEEDS_BOXES)
+    if getattr(args, "demo_polygons", False) and not getattr(args, "demo_boxes", None):
+        raise SystemExit(DEMO_POLYGONS_NEEDS_BOXES)
     try:
         feather = paste_feather(args)
     except ValueError as e:
@@ -143,6 +149,9 @@ def main(config, args):
                 raise SystemExit("main.py: --demo_boxes %s is not a directory" % box_dir)
             tile = bool(getattr(args, "demo_tile", False))
             make = box_window_batches if tile else box_region_batches
+            if getattr(args, "demo_polygons", False):
+                # a line of more than 4 points is a curved word, straightened strip by strip (utils/poly.py)
+                make = functools.partial(make, polygons=True)
             if getattr(args, "demo_paste", False):
                 # every photo enlarged and its SR regions pasted back into their quadrilaterals: <stem>_photo_sr.png (utils/paste.py)
                 batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device, photos=True)
@@ -271,6 +280,12 @@ if __name__ == '__main__':
                         help='with --demo_boxes: every photo is also enlarged by the scale factor and its super-resolved regions are '
                              'pasted back into their quadrilaterals on the GPU: one <stem>_photo_sr.png per photo (combines with '
                              '--demo_tile and --rec)')
+    parser.add_argument('--demo_polygons', action='store_true', default=False,
+                        help='with --demo_boxes: a line of a box file may hold a polygon of 2k points (k along the top edge, then k '
+                             'along the bottom edge, clockwise; CTW1500 / Total-Text style, at most 32 per edge) for a curved word, '
+                             'which is straightened strip by strip on the GPU.  Everything after the leading numbers is the '
+                             'transcription (a leading #### is stripped); lines of 4 points are read as without the flag.  With '
+                             '--demo_paste the polygon regions are written but not pasted')
     parser.add_argument('--demo_paste_feather', type=float, default=1.0, metavar='F',
                         help='with --demo_paste: the width, in SR pixels, of the edge over which a pasted region is blended into the '
                              'photo (>= 0; 0 gives a hard edge)')
@@ -297,6 +312,8 @@ if __name__ == '__main__':
         parser.error(DEMO_BOXES_NEEDS_DIR[len("main.py: "):])
     if args.demo_paste and not args.demo_boxes:
         parser.error(DEMO_PASTE_NEEDS_BOXES[len("main.py: "):])
+    if args.demo_polygons and not args.demo_boxes:
+        parser.error(DEMO_POLYGONS_NEEDS_BOXES[len("main.py: "):])
     try:
         paste_feather(args)
     except ValueError as e:
