@@ -11,36 +11,18 @@
 // depend on the schedule.  float64 throughout, in the operation order of the restatement: plain * + / (the library is built with
 // -ffp-contract=off, and the double division is correctly rounded).  The work is proportional to the area the boxes cover, not to the
 // photo's; the taps come through L1 / L2 as in quad.hip.
-#include "quad_sample.h"
+#include "paste_common.h"
 
 namespace {
 
-constexpr int PASTE_REGION_WORDS = 12;
-constexpr int PASTE_TILE_WORDS = 4;
-constexpr int PASTE_TILE_W = 32, PASTE_TILE_H = 8;
-
-// One region as the kernel sees it (include/dpmn_hip.h dpmn_paste_regions_u8: 12 int64 per region).  The numbers are data from the
-// caller: a region whose SR image does not fit the packed buffer, or has a side outside 1 .. 8192, is not read.  The host entry point
-// applies the same test to its copy of the table and refuses the call.
-__host__ __device__ inline bool paste_region_ok(const long long* p, long sr_bytes) {
-  const long long off = p[0], h = p[1], w = p[2];
-  return h >= 1 && h <= RESIZE_MAX_SIDE && w >= 1 && w <= RESIZE_MAX_SIDE && off >= 0 && off <= sr_bytes - h * w * 3;
-}
-
-// Image.paste with an L mask on uint8 (libImaging/Paste.c BLEND8 of this Pillow): dst, src, m in 0 .. 255
-__device__ __forceinline__ int blend8(int dst, int src, int m) {
-  const int t = dst * (255 - m) + src * m + 128;
-  return ((t >> 8) + t) >> 8;
-}
+constexpr int PASTE_REGION_WORDS = 12;      // include/dpmn_hip.h dpmn_paste_regions_u8: 12 int64 per region
 
 __global__ void __launch_bounds__(PASTE_TILE_W * PASTE_TILE_H)
 k_paste_regions(unsigned char* __restrict__ photo, int H2, int W2, const unsigned char* __restrict__ sr, long sr_bytes,
                 const long long* __restrict__ regions, int R, const int* __restrict__ tiles, const int* __restrict__ list, int n_list) {
   const int* t = tiles + (size_t)blockIdx.x * PASTE_TILE_WORDS;
+  if (!paste_tile_ok(t, H2, W2, n_list)) return;
   const int tile_row = t[0], tile_col = t[1], first = t[2], count = t[3];
-  // (the tile is data from the caller: one outside the photo, or whose slice leaves the list, writes nothing)
-  if (tile_row < 0 || tile_col < 0 || tile_row > (H2 - 1) / PASTE_TILE_H || tile_col > (W2 - 1) / PASTE_TILE_W) return;
-  if (first < 0 || count < 0 || first > n_list - count) return;
   const int x = tile_col * PASTE_TILE_W + (int)threadIdx.x, y = tile_row * PASTE_TILE_H + (int)threadIdx.y;
   if (x >= W2 || y >= H2) return;
   unsigned char* dst = photo + ((size_t)y * W2 + x) * 3;
@@ -60,22 +42,7 @@ k_paste_regions(unsigned char* __restrict__ photo, int H2, int W2, const unsigne
     const double den = a6 * xin + a7 * yin + 1;
     const double sx = (a0 * xin + a1 * yin + a2) / den;
     const double sy = (a3 * xin + a4 * yin + a5) / den;
-    // (a NaN compares false: outside; nothing becomes an integer before this test)
-    if (!(sx >= 0.0 && sx < (double)w_s && sy >= 0.0 && sy < (double)h_s)) continue;
-    int m = 255;
-    if (feather > 0.0) {
-      // the distance of the source position to the nearest edge of the SR rectangle, in SR pixels: 0 <= d, so 0 <= m
-      const double d = fmin(fmin(sx, (double)w_s - sx), fmin(sy, (double)h_s - sy));
-      const double f = d / feather;
-      m = f >= 1.0 ? 255 : (int)floor(f * 255 + 0.5);
-      m = min(max(m, 0), 255);
-    }
-    unsigned char px[3];
-    bicubic_sample_u8(sr + p[0], h_s, w_s, sx, sy, px);
-    b0 = blend8(b0, px[0], m);
-    b1 = blend8(b1, px[1], m);
-    b2 = blend8(b2, px[2], m);
-    touched = true;
+    touched |= paste_sample_blend(sr + p[0], h_s, w_s, sx, sy, feather, b0, b1, b2);
   }
   if (touched) {
     dst[0] = (unsigned char)b0;

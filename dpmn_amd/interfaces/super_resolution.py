@@ -308,7 +308,7 @@ class TextSR(base.TextBase):
 
     @torch.no_grad()
     def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None, boxes=False, paste=False,
-             feather=1.0):
+             feather=1.0, paste_polygons=False):
         """Super-resolve someone's own images (ours; main.py --demo_dir): batches yields (names, images_lr) as
         dataset.folder.folder_batches does.  Per batch `refine` (label_vecs from the frozen CRNN for tatt / tpgsr, as in eval), then
         save_image's quantisation on the GPU (ops.quantize_sr_u8), ONE device-to-host copy and one <stem>_sr.png per input under
@@ -338,7 +338,10 @@ class TextSR(base.TextBase):
         utils.resize.MAX_SIDE gets one printed line and no photo output; its regions are written.  The rows and demo_result.csv do
         not change.
         Batches made with polygons=True (main.py --demo_polygons) need nothing here: a rectified polygon (utils/poly.py) is a region
-        like any other, with or without tile.  With paste=True the polygons' SR regions are written as files but not pasted."""
+        like any other, with or without tile.  With paste=True the polygons' SR regions are written as files but not pasted, unless
+        paste_polygons=True (main.py --demo_paste_polygons; needs paste=True): every strip of a polygon's SR region then goes back into
+        its piece of the enlarged photo by the inverse of the strip's bilinear map (utils/paste_poly.py), and quadrilaterals and
+        polygons are pasted from one list in box-file order (ops.paste_mixed_u8).  The region files and demo_result.csv do not change."""
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
         for m in model_list:
@@ -348,10 +351,12 @@ class TextSR(base.TextBase):
         rows, taken = [], set()
         if paste and not boxes:
             raise ValueError("demo: paste=True needs boxes=True (the quadrilaterals the SR regions are pasted into come from the box files)")
+        if paste_polygons and not paste:
+            raise ValueError("demo: paste_polygons=True needs paste=True (the polygons are pasted into the photo that paste=True writes)")
         if boxes:
             labels = []
             for names, pixels, preds_lr, preds_sr, photos in self._demo_regions(model_list, model_psn, batches, fn, reader, chunk, tile, labels,
-                                                                                 float(feather) if paste else None):
+                                                                                 float(feather) if paste else None, bool(paste_polygons)):
                 self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken)
                 self._demo_write(out_dir, [stem + "_photo.png" for stem, _ in photos], [a for _, a in photos], [''] * len(photos),
                                  [''] * len(photos), [], taken)
@@ -394,11 +399,11 @@ class TextSR(base.TextBase):
             Image.fromarray(a).save(os.path.join(out_dir, out_name))
             rows.append([name, str(s_lr), str(s_sr)])
 
-    def _demo_regions(self, model_list, model_psn, batches, fn, reader, chunk, tile, labels_out, feather=None):
+    def _demo_regions(self, model_list, model_psn, batches, fn, reader, chunk, tile, labels_out, feather=None, paste_polygons=False):
         """demo(boxes=True): per batch of regions -> (names, one (H, W_r, 3) uint8 array per region, the LR reads, the SR reads, the
         pasted photos); the regions' labels are appended to labels_out.  tile: the batches carry a plan and go through _demo_windows.
         feather: None, or demo(paste=True)'s -- the batches then end with the photos item and the pasted photos are _demo_paste's list
-        (empty otherwise)."""
+        (empty otherwise); paste_polygons: demo's."""
         paste = feather is not None
         if tile:
             held = []
@@ -409,7 +414,8 @@ class TextSR(base.TextBase):
                     held[:] = photos
                     yield names, plan, images_lr
             for names, pixels, preds_lr, preds_sr, device in self._demo_windows(model_list, model_psn, windows(), fn, reader, chunk):
-                yield names, pixels, preds_lr, preds_sr, self._demo_paste(names, held[0], device[0], device[1], feather) if paste else []
+                yield names, pixels, preds_lr, preds_sr, (self._demo_paste(names, held[0], device[0], device[1], feather, paste_polygons)
+                                                            if paste else [])
             return
         chunk = max(int(chunk if chunk is not None else self.batch_size), 1)
         for names, labels, images_lr, *photos in batches:
@@ -434,19 +440,23 @@ class TextSR(base.TextBase):
                 # the quantised regions of the batch, all H x W x 3: flat, they are pack_ragged's layout
                 q = on_device[0] if len(on_device) == 1 else torch.cat(on_device, 0)
                 R, H, W = q.shape[:3]
-                pasted = self._demo_paste(names, photos[0], q.reshape(-1), [(r * H * W * 3, H, W) for r in range(R)], feather)
+                pasted = self._demo_paste(names, photos[0], q.reshape(-1), [(r * H * W * 3, H, W) for r in range(R)], feather,
+                                          paste_polygons)
             yield names, [a for p in pixels for a in p], preds_lr, preds_sr, pasted
 
-    def _demo_paste(self, names, photos, sr_packed, sr_meta, feather):
+    def _demo_paste(self, names, photos, sr_packed, sr_meta, feather, paste_polygons=False):
         """demo(paste=True): the photos of one batch with their SR regions pasted back -> [(stem, (scale * H, scale * W, 3) uint8
         array)] in batch order.  photos = (packed, meta, owners, quads) as dataset.folder.box_region_batches(photos=True) yields it;
         sr_packed / sr_meta hold the batch's SR regions on the device, one per name, in pack_ragged's layout.  Per photo: the enlargement
         (ops.resize_ragged_u8 with a batch of one), ops.paste_regions_u8 with the photo's regions in box-file order, one copy to the
         host.  A photo too large to enlarge, or a region utils.paste.paste_coeffs refuses, is passed over with one printed line.  The
         regions of polygons (more than 4 points: the batches were made with polygons=True) are not pasted -- one printed line per photo
-        gives their count."""
+        gives their count -- unless paste_polygons: a polygon then joins the photo's list with its strip table
+        (utils.paste_poly.strip_table; one it refuses gets a refused quadrilateral's printed line) and the list goes through
+        ops.paste_mixed_u8."""
         import numpy as np
         from ..utils.paste import paste_coeffs
+        from ..utils.paste_poly import strip_table
         from ..utils.resize import MAX_SIDE
         packed, meta, owners, quads = photos
         meta = np.asarray(meta.cpu() if torch.is_tensor(meta) else meta).astype(np.int64).reshape(-1, 3)
@@ -462,19 +472,21 @@ class TextSR(base.TextBase):
                 print("demo: no pasted photo for %s (%d x %d times %d: a side above %d is not resized)" % (stem, H, W, s, MAX_SIDE))
                 continue
             curved = [r for r in mine if len(quads[r]) > 4]
-            if curved:
+            if curved and not paste_polygons:
                 print("demo: %d polygon region%s of %s not pasted (only quadrilaterals are warped back)"
                       % (len(curved), "" if len(curved) == 1 else "s", stem))
             regions = []
             for r in mine:
-                if r in curved:
+                if r in curved and not paste_polygons:
                     continue
                 try:
-                    regions.append((r, paste_coeffs(quads[r], s, int(sr_meta[r, 2]), int(sr_meta[r, 1])), feather))
+                    shape = strip_table if r in curved else paste_coeffs
+                    regions.append((r, shape(quads[r], s, int(sr_meta[r, 2]), int(sr_meta[r, 1])), feather))
                 except ValueError as e:
                     print("demo: region %s is not pasted (%s)" % (names[r], e))
             photo2 = ops.resize_ragged_u8(packed, meta[b:b + 1], s * H, s * W)[0]
-            out.append((stem, ops.paste_regions_u8(photo2, sr_packed, sr_meta, regions).cpu().numpy()))
+            op = ops.paste_mixed_u8 if paste_polygons else ops.paste_regions_u8
+            out.append((stem, op(photo2, sr_packed, sr_meta, regions).cpu().numpy()))
         return out
 
     def _demo_windows(self, model_list, model_psn, batches, fn, reader, chunk):

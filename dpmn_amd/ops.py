@@ -694,15 +694,10 @@ PASTE_TILE = (8, 32)      # csrc/paste.hip PASTE_TILE_H, PASTE_TILE_W
 PASTE_MAX_TILES = 2 ** 31 - 1      # one block per tile in the grid's x dimension
 
 
-def _paste_regions_plan(photo2, sr_packed, sr_meta, regions):
-    """Checks and per-call host data of paste_regions_u8 -> host: the arrays of one call as numpy -- table (R, 12) int64 [byte offset of
-    the SR image, h_s, w_s, the bits of the float64 feather, the bits of the 8 float64 coefficients], tiles (n_tiles, 4) int32 [tile
-    row, tile column, first, count] in row-major tile order and list (n_list) int32: per tile the regions whose grown bounding box
-    (utils.paste.region_box) meets it, in the order of `regions` (_paste_regions_run)."""
-    import numpy as np
-    from .utils.paste import region_box
+def _paste_inputs(photo2, sr_packed, sr_meta, what):
+    """The checks that the paste ops share -> (H2, W2, the SR images' int64 (B, 3) meta): a contiguous (H2, W2, 3) uint8 photo on the
+    device, the SR images in pack_ragged's layout on the same device, and no storage shared between the two."""
     from .utils.resize import MAX_SIDE
-    what = "paste_regions_u8"
     if not torch.is_tensor(photo2) or not photo2.is_cuda:
         raise _abi.DpmnError("%s: the regions are pasted on the GPU (got a %s photo); there is no CPU fallback"
                              % (what, photo2.device if torch.is_tensor(photo2) else type(photo2).__name__))
@@ -717,11 +712,48 @@ def _paste_regions_plan(photo2, sr_packed, sr_meta, regions):
     lo, hi = photo2.data_ptr(), photo2.data_ptr() + photo2.numel()
     if sr_packed.data_ptr() < hi and lo < sr_packed.data_ptr() + sr_packed.numel():
         raise _abi.DpmnError("%s: the photo and the SR buffer share storage (the photo is written while the SR images are read)" % what)
+    return H2, W2, m
+
+
+def _box_tile_ids(box, W2):
+    """The row-major numbers of the PASTE_TILE tiles that a box (x0, y0, x1, y1) of the photo meets (none for an empty box)."""
+    import numpy as np
+    x0, y0, x1, y1 = box
+    if x1 <= x0 or y1 <= y0:
+        return np.empty(0, np.int64)
+    th, tw = PASTE_TILE
+    rows, cols = np.arange(y0 // th, (y1 - 1) // th + 1, dtype=np.int64), np.arange(x0 // tw, (x1 - 1) // tw + 1, dtype=np.int64)
+    return (rows[:, None] * -(-W2 // tw) + cols[None, :]).reshape(-1)
+
+
+def _paste_tiles(ids, W2, what):
+    """ids: per region the numbers of the tiles it meets -> (tiles (n_tiles, 4) int32 [tile row, tile column, first, count] in
+    row-major tile order, list (n_list) int32: per tile its regions in the order of the regions)."""
+    import numpy as np
+    owners = [np.full(t.size, r, np.int32) for r, t in enumerate(ids) if t.size]
+    if not owners:
+        return np.empty((0, 4), np.int32), np.empty(0, np.int32)
+    ids, owners = np.concatenate([t for t in ids if t.size]), np.concatenate(owners)
+    ntx = -(-W2 // PASTE_TILE[1])
+    order = np.argsort(ids, kind="stable")      # by tile; within a tile the order of the regions stays
+    uniq, first, count = np.unique(ids[order], return_index=True, return_counts=True)
+    if uniq.size > PASTE_MAX_TILES or ids.size > PASTE_MAX_TILES:
+        raise _abi.DpmnError("%s: the regions meet %d tiles (%d list entries), more than fit one launch" % (what, uniq.size, ids.size))
+    return np.stack([uniq // ntx, uniq % ntx, first, count], axis=1).astype(np.int32), np.ascontiguousarray(owners[order])
+
+
+def _paste_regions_plan(photo2, sr_packed, sr_meta, regions):
+    """Checks and per-call host data of paste_regions_u8 -> host: the arrays of one call as numpy -- table (R, 12) int64 [byte offset of
+    the SR image, h_s, w_s, the bits of the float64 feather, the bits of the 8 float64 coefficients], tiles (n_tiles, 4) int32 [tile
+    row, tile column, first, count] in row-major tile order and list (n_list) int32: per tile the regions whose grown bounding box
+    (utils.paste.region_box) meets it, in the order of `regions` (_paste_regions_run)."""
+    import numpy as np
+    from .utils.paste import region_box
+    what = "paste_regions_u8"
+    H2, W2, m = _paste_inputs(photo2, sr_packed, sr_meta, what)
     R = len(regions)
     table = np.empty((R, 12), np.int64)
-    th, tw = PASTE_TILE
-    ntx = -(-W2 // tw)
-    ids, owners = [], []
+    ids = []
     for r, reg in enumerate(regions):
         try:
             k, coeffs, feather = reg
@@ -735,21 +767,9 @@ def _paste_regions_plan(photo2, sr_packed, sr_meta, regions):
         table[r, :3] = m[k]
         table[r, 3] = np.float64(feather).view(np.int64)
         table[r, 4:] = a.view(np.int64)
-        x0, y0, x1, y1 = region_box(a, int(m[k, 2]), int(m[k, 1]), H2, W2)
-        if x1 <= x0 or y1 <= y0:
-            continue
-        rows, cols = np.arange(y0 // th, (y1 - 1) // th + 1, dtype=np.int64), np.arange(x0 // tw, (x1 - 1) // tw + 1, dtype=np.int64)
-        ids.append((rows[:, None] * ntx + cols[None, :]).reshape(-1))
-        owners.append(np.full(rows.size * cols.size, r, np.int32))
-    if not ids:
-        return dict(table=table, tiles=np.empty((0, 4), np.int32), list=np.empty(0, np.int32), size=(H2, W2))
-    ids, owners = np.concatenate(ids), np.concatenate(owners)
-    order = np.argsort(ids, kind="stable")      # by tile; within a tile the order of `regions` stays
-    uniq, first, count = np.unique(ids[order], return_index=True, return_counts=True)
-    if uniq.size > PASTE_MAX_TILES or ids.size > PASTE_MAX_TILES:
-        raise _abi.DpmnError("%s: the regions meet %d tiles (%d list entries), more than fit one launch" % (what, uniq.size, ids.size))
-    tiles = np.stack([uniq // ntx, uniq % ntx, first, count], axis=1).astype(np.int32)
-    return dict(table=table, tiles=tiles, list=np.ascontiguousarray(owners[order]), size=(H2, W2))
+        ids.append(_box_tile_ids(region_box(a, int(m[k, 2]), int(m[k, 1]), H2, W2), W2))
+    tiles, lst = _paste_tiles(ids, W2, what)
+    return dict(table=table, tiles=tiles, list=lst, size=(H2, W2))
 
 
 def _paste_regions_run(photo2, sr_packed, host):
@@ -781,6 +801,85 @@ def paste_regions_u8(photo2, sr_packed, sr_meta, regions):
     region table, the tiles and the per-tile region list."""
     host = _paste_regions_plan(photo2, sr_packed, sr_meta, list(regions))
     check(_paste_regions_run(photo2, sr_packed, host))
+    return photo2
+
+
+PASTE_KIND_PERSPECTIVE, PASTE_KIND_POLYGON = 0, 1      # csrc/paste_poly.hip KIND_*
+
+
+def _paste_mixed_plan(photo2, sr_packed, sr_meta, regions):
+    """Checks and per-call host data of paste_mixed_u8 -> host: the arrays of one call as numpy -- table (R, 13) int64 [byte offset of
+    the SR image, h_s, w_s, the bits of the float64 feather, kind, then the bits of the 8 float64 coefficients (a quadrilateral) or
+    first strip, strip count and zeros (a polygon)], strips (S, 14) int64 [the bits of the 10 float64 of a strip of
+    utils.paste_poly.strip_table, its strip_box x0, y0, x1, y1], tiles and list as _paste_regions_plan makes them: a quadrilateral
+    lies in the tiles that its region_box meets, a polygon in those that the box of at least one of its strips meets
+    (_paste_mixed_run)."""
+    import numpy as np
+    from .utils.paste import region_box
+    from .utils.paste_poly import _strips, is_polygon_region, strip_box
+    what = "paste_mixed_u8"
+    H2, W2, m = _paste_inputs(photo2, sr_packed, sr_meta, what)
+    R = len(regions)
+    table, strips, n_strips, ids = np.zeros((R, 13), np.int64), [], 0, []
+    for r, reg in enumerate(regions):
+        try:
+            k, shape, feather = reg
+            k, feather = int(k), float(feather)
+            curved = is_polygon_region(reg)
+            a = _strips(shape, "strips") if curved else np.asarray(shape, np.float64).reshape(-1)
+        except (TypeError, ValueError) as e:
+            raise _abi.DpmnError("%s: region %d is not (SR index, 8 coefficients or strips, feather): %s" % (what, r, e)) from e
+        if not (0 <= k < m.shape[0] and (curved or a.size == 8) and np.isfinite(a).all() and np.isfinite(feather)):
+            raise _abi.DpmnError("%s: region %d names an SR image outside the batch of %d or does not carry 8 finite coefficients (or "
+                                 "finite strips) and a finite feather" % (what, r, m.shape[0]))
+        table[r, :3] = m[k]
+        table[r, 3] = np.float64(feather).view(np.int64)
+        if curved:
+            boxes = np.array([strip_box(s, H2, W2) for s in a], np.int64)
+            table[r, 4:7] = PASTE_KIND_POLYGON, n_strips, a.shape[0]
+            strips.append(np.concatenate([np.ascontiguousarray(a).view(np.int64), boxes], axis=1))
+            n_strips += a.shape[0]
+            ids.append(np.unique(np.concatenate([_box_tile_ids(b, W2) for b in boxes.tolist()])))
+        else:
+            table[r, 4] = PASTE_KIND_PERSPECTIVE
+            table[r, 5:] = a.view(np.int64)
+            ids.append(_box_tile_ids(region_box(a, int(m[k, 2]), int(m[k, 1]), H2, W2), W2))
+    tiles, lst = _paste_tiles(ids, W2, what)
+    return dict(table=table, strips=np.concatenate(strips) if strips else np.empty((0, 14), np.int64), tiles=tiles, list=lst, size=(H2, W2))
+
+
+def _paste_mixed_run(photo2, sr_packed, host):
+    """One upload of the host arrays of _paste_mixed_plan (the region table, the strips, the tiles and the region list in one int64
+    buffer) and the launch -> the library's return code."""
+    import numpy as np
+    table, strips, tiles, lst = (np.ascontiguousarray(host[k], dtype=t) for k, t in
+                                 (("table", np.int64), ("strips", np.int64), ("tiles", np.int32), ("list", np.int32)))
+    R, S, n_tiles, n_list = table.shape[0], strips.shape[0], tiles.shape[0], lst.size
+    H2, W2 = host["size"]
+    if R == 0 or n_tiles == 0:
+        return 0
+    n_tile_words = (n_tiles * 4 + 1) // 2
+    at_strips, at_tiles = R * 13, R * 13 + S * 14
+    buf = np.zeros(at_tiles + n_tile_words + (n_list + 1) // 2, np.int64)
+    buf[:at_strips] = table.reshape(-1)
+    buf[at_strips:at_tiles] = strips.reshape(-1)
+    buf[at_tiles:at_tiles + n_tile_words].view(np.int32)[:n_tiles * 4] = tiles.reshape(-1)
+    buf[at_tiles + n_tile_words:].view(np.int32)[:n_list] = lst
+    d = torch.from_numpy(buf).to(photo2.device)
+    return lib.dpmn_paste_mixed_u8(photo2.data_ptr(), H2, W2, sr_packed.data_ptr(), sr_packed.numel(), d.data_ptr(), table.ctypes.data, R,
+                                   d[at_strips:].data_ptr() if S else None, S, d[at_tiles:].data_ptr(), n_tiles,
+                                   d[at_tiles + n_tile_words:].data_ptr(), n_list, stream())
+
+
+def paste_mixed_u8(photo2, sr_packed, sr_meta, regions):
+    """Quadrilaterals and polygons pasted back into the enlarged photo in one list (csrc/paste_poly.hip): photo2, sr_packed / sr_meta as
+    paste_regions_u8 takes them; regions ONE list in paste order whose items are paste_regions_u8's (SR index, coeffs, feather) or
+    (SR index, strips, feather) with the float64 (n, 10) strips of utils.paste_poly.strip_table -> byte for byte
+    utils.paste_poly.paste_mixed_np, in float64; photo2 is modified IN PLACE and returned.  The tiles, the launch and the one owner per
+    byte are paste_regions_u8's; within a polygon a thread tries only the strips whose box holds its pixel.  An empty list launches
+    nothing.  Per call one buffer is uploaded: the region table, the strips, the tiles and the per-tile region list."""
+    host = _paste_mixed_plan(photo2, sr_packed, sr_meta, list(regions))
+    check(_paste_mixed_run(photo2, sr_packed, host))
     return photo2
 
 

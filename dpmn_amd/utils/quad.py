@@ -124,17 +124,12 @@ def _cubic(v1, v2, v3, v4, d):
     return p1 + d * (p2 + d * (p3 + d * p4))
 
 
-def perspective_sample(src, xin, yin, coeffs):
-    """The sampling core of quad_crop_one, shared with utils/paste.py: src (H, W, 3) float64, xin (1, w) and yin (h, 1) the centres of
-    the output pixels, coeffs the 8 coefficients -> (bytes (h, w, 3) uint8, inside (h, w) bool, sx, sy): the source position of every
-    pixel BEFORE the -0.5 shift, whether it lies in 0 <= sx < W, 0 <= sy < H, and the truncated bicubic sample there (black outside)."""
+def bicubic_at(src, sx0, sy0, inside):
+    """The sampling of perspective_sample for source positions found elsewhere (utils/paste_poly.py): src (H, W, 3) float64, sx0 / sy0
+    (h, w) the source positions BEFORE the -0.5 shift, inside (h, w) bool -> the truncated bicubic sample (h, w, 3) uint8, black where
+    the pixel is not inside (sx0 / sy0 are not read there)."""
     H, W = src.shape[:2]
-    a = coeffs
     with np.errstate(all="ignore"):
-        den = a[6] * xin + a[7] * yin + 1
-        sx0 = (a[0] * xin + a[1] * yin + a[2]) / den
-        sy0 = (a[3] * xin + a[4] * yin + a[5]) / den
-        inside = (sx0 >= 0) & (sx0 < W) & (sy0 >= 0) & (sy0 < H)      # (a NaN compares false: outside)
         sx = np.where(inside, sx0, 0.5) - 0.5
         sy = np.where(inside, sy0, 0.5) - 0.5
     ix, iy = np.floor(sx), np.floor(sy)
@@ -151,7 +146,21 @@ def perspective_sample(src, xin, yin, coeffs):
     v = _cubic(*rows, dy)
     out = np.where(v <= 0, 0.0, np.where(v >= 255, 255.0, v)).astype(np.uint8)      # (truncation, as Geometry.c casts)
     out[~inside] = 0
-    return out, inside, sx0, sy0
+    return out
+
+
+def perspective_sample(src, xin, yin, coeffs):
+    """The sampling core of quad_crop_one, shared with utils/paste.py: src (H, W, 3) float64, xin (1, w) and yin (h, 1) the centres of
+    the output pixels, coeffs the 8 coefficients -> (bytes (h, w, 3) uint8, inside (h, w) bool, sx, sy): the source position of every
+    pixel BEFORE the -0.5 shift, whether it lies in 0 <= sx < W, 0 <= sy < H, and the truncated bicubic sample there (black outside)."""
+    H, W = src.shape[:2]
+    a = coeffs
+    with np.errstate(all="ignore"):
+        den = a[6] * xin + a[7] * yin + 1
+        sx0 = (a[0] * xin + a[1] * yin + a[2]) / den
+        sy0 = (a[3] * xin + a[4] * yin + a[5]) / den
+        inside = (sx0 >= 0) & (sx0 < W) & (sy0 >= 0) & (sy0 < H)      # (a NaN compares false: outside)
+    return bicubic_at(src, sx0, sy0, inside), inside, sx0, sy0
 
 
 def quad_crop_one(photo, h, w, coeffs):

@@ -13,7 +13,8 @@ rectified on the GPU and super-resolved as a crop of its own; with `--demo_paste
 the GPU, its SR regions are warped back into their quadrilaterals and blended in (`--demo_paste_feather F`: the width of the blended edge
 in SR pixels, 0 for a hard edge), and written as `<stem>_photo_sr.png`; with `--demo_polygons` a line of a box file may also name a curved
 word by a polygon (2k points, k along the top edge and k along the bottom, as CTW1500 and Total-Text write them), which is straightened
-strip by strip on the GPU (polygon regions are written as files but not pasted).  `--train_state PATH` makes a training run continuable: the same command line starts the
+strip by strip on the GPU (polygon regions are written as files; `--demo_paste_polygons` on top of `--demo_paste` also warps them back into
+the photo, strip by strip, in box-file order with the quadrilaterals).  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
 (`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
@@ -71,6 +72,8 @@ def recogniser(mission, args):
 DEMO_BOXES_NEEDS_DIR = "main.py: --demo_boxes needs --demo_dir: the photos whose regions the box files name are read from that folder"
 DEMO_PASTE_NEEDS_BOXES = "main.py: --demo_paste needs --demo_boxes: the SR regions are pasted back into the quadrilaterals that the box files name"
 DEMO_POLYGONS_NEEDS_BOXES = "main.py: --demo_polygons needs --demo_boxes: the polygons of curved words are read from the box files"
+DEMO_PASTE_POLYGONS_NEEDS = ("main.py: --demo_paste_polygons needs --demo_paste and --demo_polygons: it pastes the SR regions of the polygons "
+                             "that --demo_polygons reads into the photo that --demo_paste writes")
 DEMO_PASTE_FEATHER = "main.py: --demo_paste_feather must be a finite number >= 0 (the width of the blended edge in SR pixels; 0: a hard edge)"
 
 
@@ -104,6 +107,8 @@ def main(config, args):
         raise SystemExit(DEMO_PASTE_NEEDS_BOXES)
     if getattr(args, "demo_polygons", False) and not getattr(args, "demo_boxes", None):
         raise SystemExit(DEMO_POLYGONS_NEEDS_BOXES)
+    if getattr(args, "demo_paste_polygons", False) and not (getattr(args, "demo_paste", False) and getattr(args, "demo_polygons", False)):
+        raise SystemExit(DEMO_PASTE_POLYGONS_NEEDS)
     try:
         feather = paste_feather(args)
     except ValueError as e:
@@ -155,7 +160,9 @@ def main(config, args):
             if getattr(args, "demo_paste", False):
                 # every photo enlarged and its SR regions pasted back into their quadrilaterals: <stem>_photo_sr.png (utils/paste.py)
                 batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device, photos=True)
-                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, paste=True, feather=feather)
+                # (--demo_paste_polygons: the polygons too, strip by strip, in box-file order with the quadrilaterals: utils/paste_poly.py)
+                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, paste=True, feather=feather,
+                                    paste_polygons=bool(getattr(args, "demo_paste_polygons", False)))
             else:
                 batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device)
                 rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True)
@@ -285,7 +292,10 @@ if __name__ == '__main__':
                              'along the bottom edge, clockwise; CTW1500 / Total-Text style, at most 32 per edge) for a curved word, '
                              'which is straightened strip by strip on the GPU.  Everything after the leading numbers is the '
                              'transcription (a leading #### is stripped); lines of 4 points are read as without the flag.  With '
-                             '--demo_paste the polygon regions are written but not pasted')
+                             '--demo_paste the polygon regions are written but not pasted (see --demo_paste_polygons)')
+    parser.add_argument('--demo_paste_polygons', action='store_true', default=False,
+                        help='with --demo_paste and --demo_polygons: the super-resolved polygon regions are pasted back too, every strip '
+                             'through the inverse of its bilinear map, in box-file order with the quadrilaterals')
     parser.add_argument('--demo_paste_feather', type=float, default=1.0, metavar='F',
                         help='with --demo_paste: the width, in SR pixels, of the edge over which a pasted region is blended into the '
                              'photo (>= 0; 0 gives a hard edge)')
@@ -314,6 +324,8 @@ if __name__ == '__main__':
         parser.error(DEMO_PASTE_NEEDS_BOXES[len("main.py: "):])
     if args.demo_polygons and not args.demo_boxes:
         parser.error(DEMO_POLYGONS_NEEDS_BOXES[len("main.py: "):])
+    if args.demo_paste_polygons and not (args.demo_paste and args.demo_polygons):
+        parser.error(DEMO_PASTE_POLYGONS_NEEDS[len("main.py: "):])
     try:
         paste_feather(args)
     except ValueError as e:
