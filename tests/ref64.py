@@ -2,7 +2,12 @@
 the CPU, one function per operation, written from the operation's definition with elementwise arithmetic, matmul, exp / tanh / sqrt and
 reductions only -- no torch.nn / torch.nn.functional call, so that a mistake in one of them cannot hide behind the library routine it
 would share with the fp32 comparison.  tests/test_ref64.py pins each of them to an independent statement of the same operation.
-Every function takes tensors of any float dtype and returns float64."""
+Every function takes tensors of any float dtype and returns float64.
+
+The second half holds the references of the small BACKWARD kernels (csrc/backward_pgrm.hip, backward.hip, the tail of conv_bwd.hip):
+the gradient formulas written out by hand from the forward definition (plus torch.erf for the exact GELU), pinned in
+tests/test_ref64.py to torch.autograd of an independent forward in double.  They take `dtype` (default float64): the same formula
+evaluated with dtype=torch.float32 is the fp32 CPU evaluation that tests/test_gpu_small_backward.py derives its tolerances from."""
 import math
 
 import torch
@@ -170,3 +175,249 @@ def maxpool_affine_relu(x, kh, kw, scale=None, shift=None):
         x = torch.clamp(x * scale + shift, min=0.0)
     B, H, W, C = x.shape
     return x.reshape(B, H // kh, kh, W // kw, kw, C).amax((2, 4))
+
+
+# ====================================================================================================================
+# backward kernels: every function below evaluates in `dtype` (float64: the reference; float32: the tolerance yardstick)
+def _c(x, dtype):
+    return None if x is None else torch.as_tensor(x).detach().cpu().to(dtype)
+
+
+def _cdf(x):
+    """standard normal CDF"""
+    return 0.5 * (1.0 + torch.erf(x * (1.0 / math.sqrt(2.0))))
+
+
+def gelu(x, dtype=torch.float64):
+    """exact (erf) GELU x Phi(x)"""
+    x = _c(x, dtype)
+    return x * _cdf(x)
+
+
+def gelu_grad(x, dtype=torch.float64):
+    """GELU'(x) = Phi(x) + x phi(x)"""
+    x = _c(x, dtype)
+    return _cdf(x) + x * torch.exp(-0.5 * x * x) * (1.0 / math.sqrt(2.0 * math.pi))
+
+
+def sk_select(cat, A, L, dtype=torch.float64):
+    """V[m, c] = sum_g A[b, g, c] cat[m, g cg + c], b = m // L: cat (B L, G cg), A (B, G, cg) -> (B L, cg)"""
+    cat, A = _c(cat, dtype), _c(A, dtype)
+    B, G, cg = A.shape
+    return (cat.reshape(B, L, G, cg) * A[:, None]).sum(2).reshape(B * L, cg)
+
+
+def sk_select_bwd(cat, A, dV, L, rows_per_block=32, dtype=torch.float64):
+    """Backward of sk_select for the cotangent dV (B L, cg): dcat[m, g cg + c] = A[b, g, c] dV[m, c]; dA[b, g, c] = sum over the image's
+    tokens of cat[m, g cg + c] dV[m, c].  Returns (dcat (B L, G cg), dA (B, G, cg), parts (ceil(L / rows_per_block), B, G cg)): parts[k]
+    is the share of dA of token rows [k rows_per_block, (k + 1) rows_per_block) of every image; they add up to dA."""
+    cat, A, dV = _c(cat, dtype), _c(A, dtype), _c(dV, dtype)
+    B, G, cg = A.shape
+    dv = dV.reshape(B, L, 1, cg)
+    prod = cat.reshape(B, L, G, cg) * dv
+    dcat = (A[:, None] * dv).reshape(B * L, G * cg)
+    parts = torch.stack([prod[:, r0:r0 + rows_per_block].sum(1).reshape(B, G * cg) for r0 in range(0, L, rows_per_block)])
+    return dcat, prod.sum(1), parts
+
+
+def sk_pool(partial, parts_per_image, L, dtype=torch.float64):
+    """S[b] = sum of image b's partial column sums / L: partial (B parts_per_image, C) -> (B, C)"""
+    partial = _c(partial, dtype)
+    return partial.reshape(-1, parts_per_image, partial.shape[1]).sum(1) / L
+
+
+def sk_gate(S, fc1_w, fc1_b, fc2_w, fc2_b, G, dtype=torch.float64):
+    """A = softmax over g of (fc2 GELU(fc1 S + b1) + b2) viewed (B, G, C / G): S (B, C), fc1 (dmid, C), fc2 (C, dmid)"""
+    S, fc1_w, fc1_b, fc2_w, fc2_b = (_c(t, dtype) for t in (S, fc1_w, fc1_b, fc2_w, fc2_b))
+    z = gelu(S @ fc1_w.t() + fc1_b, dtype)
+    logit = (z @ fc2_w.t() + fc2_b).reshape(S.shape[0], G, -1)
+    return _softmax(logit.transpose(1, 2)).transpose(1, 2).contiguous()
+
+
+def sk_gate_bwd(partial, parts_per_image, L, fc1_w, fc1_b, fc2_w, A, dA, dtype=torch.float64):
+    """Backward of sk_gate(sk_pool(partial)) for the cotangent dA (B, G, cg), with the forward's A given.  Softmax over g:
+    dlogit = A (dA - sum_g A dA); fc2: dfc2_w = dlogit^T Z, dfc2_b = sum_b dlogit, dZ = dlogit fc2_w; GELU: dzp = dZ GELU'(zp);
+    fc1: dfc1_w = dzp^T S, dfc1_b = sum_b dzp, dS = dzp fc1_w.  Returns a dict with those five gradients (summed over the images) and
+    the per-image rows wpart2 (B, C dmid + C) = [dfc2_w | dfc2_b], wpart1 (B, dmid C + dmid) = [dfc1_w | dfc1_b] they are the sums of."""
+    fc1_w, fc1_b, fc2_w, A, dA = (_c(t, dtype) for t in (fc1_w, fc1_b, fc2_w, A, dA))
+    S = sk_pool(partial, parts_per_image, L, dtype)
+    B, C = S.shape
+    zp = S @ fc1_w.t() + fc1_b
+    Z = gelu(zp, dtype)
+    dl = (A * (dA - (A * dA).sum(1, keepdim=True))).reshape(B, C)
+    dzp = (dl @ fc2_w) * gelu_grad(zp, dtype)
+    w2 = dl[:, :, None] * Z[:, None, :]            # (B, C, dmid)
+    w1 = dzp[:, :, None] * S[:, None, :]           # (B, dmid, C)
+    return {"dS": dzp @ fc1_w, "dfc2_w": w2.sum(0), "dfc2_b": dl.sum(0), "dfc1_w": w1.sum(0), "dfc1_b": dzp.sum(0),
+            "wpart2": torch.cat([w2.reshape(B, -1), dl], 1), "wpart1": torch.cat([w1.reshape(B, -1), dzp], 1),
+            "S": S, "zp": zp, "dl": dl, "dZ": dl @ fc2_w}
+
+
+def sk_feats_grad(dout, feats, dS, L, dtype=torch.float64):
+    """dfeats = dout + GELU'(feats) dS[b] / L: the gradient of feats (B L, C) when it feeds dout directly and S = mean_l GELU(feats)"""
+    dout, feats, dS = _c(dout, dtype), _c(feats, dtype), _c(dS, dtype)
+    B, C = dS.shape
+    return dout + (gelu_grad(feats, dtype).reshape(B, L, C) * dS[:, None] / L).reshape(B * L, C)
+
+
+def dwconv3x3_bwd(P, dg, w, gpre=None, in_gelu=False, out_gelu_bwd=False, mask=None, dtype=torch.float64):
+    """Backward of the depthwise 3 x 3 cross-correlation with zero padding, y[b, c, i, j] = sum_k w[c, ky, kx] x[b, c, i + ky - 1, j + kx - 1]
+    (+ bias), on planes P, dg (B, Ch, r, r), w (Ch, 3, 3).  The conv input is x = P, GELU(P) with in_gelu, times the dropout `mask`
+    (0 or 1 / (1 - p)) when given.  With gpre (the conv output, whose GELU was the layer output) the incoming gradient is
+    dy = dg GELU'(gpre), else dy = dg.  dw[c, k] = sum dy x shifted, db[c] = sum dy, dx[i, j] = sum_k dy[i - ky + 1, j - kx + 1] w[ky, kx];
+    dP = dx (mask) (GELU'(P) with out_gelu_bwd: the gradient of the pre-activation).  Returns (dP, dw (Ch, 9), db (Ch))."""
+    P, dg, w, gpre, mask = (_c(t, dtype) for t in (P, dg, w, gpre, mask))
+    B, Ch, r, _ = P.shape
+    w = w.reshape(Ch, 9)
+    x = gelu(P, dtype) if in_gelu else P
+    if mask is not None:
+        x = x * mask.reshape(P.shape)
+    dy = dg if gpre is None else dg * gelu_grad(gpre, dtype)
+    xp, dyp = P.new_zeros(B, Ch, r + 2, r + 2), P.new_zeros(B, Ch, r + 2, r + 2)
+    xp[:, :, 1:-1, 1:-1] = x
+    dyp[:, :, 1:-1, 1:-1] = dy
+    dw = torch.stack([(dy * xp[:, :, ky:ky + r, kx:kx + r]).sum((0, 2, 3)) for ky in range(3) for kx in range(3)], 1)
+    dx = torch.zeros_like(P)
+    for ky in range(3):
+        for kx in range(3):
+            dx = dx + w[:, 3 * ky + kx].reshape(1, Ch, 1, 1) * dyp[:, :, 2 - ky:2 - ky + r, 2 - kx:2 - kx + r]
+    if mask is not None:
+        dx = dx * mask.reshape(P.shape)
+    if out_gelu_bwd:
+        dx = dx * gelu_grad(P, dtype)
+    return dx, dw, dy.sum((0, 2, 3))
+
+
+ACT_CODES = {"none": 0, "gelu": 1, "relu": 2, "leaky02": 3, "leaky001": 4, "mish": 5, "prelu": 6, "tanh": 7, "sigmoid": 8}
+
+
+def act(x, code, slope=0.0, dtype=torch.float64):
+    """The activation codes of the GEMM / conv epilogues: identity, exact GELU, ReLU, LeakyReLU(0.2), LeakyReLU(0.01),
+    mish x tanh(softplus x), PReLU with one `slope`, tanh, sigmoid.  The leaky family is x for x > 0 and slope x otherwise."""
+    x = _c(x, dtype)
+    leaky = {2: 0.0, 3: 0.2, 4: 0.01, 6: slope}
+    if code == 0:
+        return x.clone()
+    if code == 1:
+        return gelu(x, dtype)
+    if code in leaky:
+        return torch.where(x > 0, x, leaky[code] * x)
+    if code == 5:
+        return x * torch.tanh(torch.log1p(torch.exp(x)))
+    if code == 7:
+        return torch.tanh(x)
+    if code == 8:
+        return _sigmoid(x)
+    raise ValueError(code)
+
+
+def act_grad(pre, code, slope=0.0, dtype=torch.float64):
+    """d act(pre) / d pre.  At the kink pre == 0 the leaky family takes the NEGATIVE side's slope (the convention of torch.autograd for
+    relu / leaky_relu / prelu).  mish' = tanh(sp) + pre (1 - tanh(sp)^2) sigmoid(pre), sp = softplus(pre)."""
+    x = _c(pre, dtype)
+    leaky = {2: 0.0, 3: 0.2, 4: 0.01, 6: slope}
+    if code == 0:
+        return torch.ones_like(x)
+    if code == 1:
+        return gelu_grad(x, dtype)
+    if code in leaky:
+        return torch.where(x > 0, torch.ones_like(x), torch.full_like(x, leaky[code]))
+    if code == 5:
+        th = torch.tanh(torch.log1p(torch.exp(x)))
+        return th + x * (1.0 - th * th) * _sigmoid(x)
+    if code == 7:
+        return 1.0 - torch.tanh(x) ** 2
+    if code == 8:
+        s = _sigmoid(x)
+        return s * (1.0 - s)
+    raise ValueError(code)
+
+
+def axpby(x, z, y, a, b, accumulate, dtype=torch.float64):
+    """a x (+ b z) (+ y when accumulate)"""
+    x, z, y = _c(x, dtype), _c(z, dtype), _c(y, dtype)
+    v = a * x if z is None else a * x + b * z
+    return y + v if accumulate else v
+
+
+def rowsum_mod(x, mod, dtype=torch.float64):
+    """out[j] = sum of the row sums of the rows r with r % mod == j: x (k mod, cols) -> (mod,)"""
+    x = _c(x, dtype)
+    return x.reshape(-1, mod, x.shape[1]).sum((0, 2))
+
+
+def rows_reduce(part, NK, N, dtype=torch.float64):
+    """rows of NK + N floats added over the rows: -> (dw (NK,), db (N,))"""
+    part = _c(part, dtype)
+    return part[:, :NK].sum(0), part[:, NK:NK + N].sum(0)
+
+
+def colsum(dy, dtype=torch.float64):
+    return _c(dy, dtype).sum(0)
+
+
+def _shuffle2(c1):
+    """NHWC (B, H, W, 12) -> NCHW (B, 3, 2 H, 2 W): out[b, c, Y, X] = c1[b, Y // 2, X // 2, 4 c + 2 (Y % 2) + X % 2] (PixelShuffle(2))"""
+    B, H, W, _ = c1.shape
+    return c1.reshape(B, H, W, 3, 2, 2).permute(0, 3, 1, 4, 2, 5).reshape(B, 3, 2 * H, 2 * W)
+
+
+def _unshuffle2(g):
+    B, _, Ho, Wo = g.shape
+    return g.reshape(B, 3, Ho // 2, 2, Wo // 2, 2).permute(0, 2, 4, 1, 3, 5).reshape(B, Ho // 2, Wo // 2, 12)
+
+
+def tail_elem(c1, wl, residuals, dtype=torch.float64):
+    """PGRM tail: out = LeakyReLU_0.01(PixelShuffle2(c1)) wl[0] + sum_{i >= 1} residuals[i] wl[i] -- residuals[0] is SKIPPED (quirk Q11 of
+    the source: the loop over the residuals starts at 1) and wl[0] weighs the shuffled branch.  c1 NHWC (B, H, W, 12), wl[i] (3, 2 H, 2 W),
+    residuals[i] (B, 3, 2 H, 2 W)."""
+    c1 = _c(c1, dtype)
+    v = _shuffle2(c1)
+    out = torch.where(v > 0, v, 0.01 * v) * _c(wl[0], dtype)
+    for i in range(1, len(residuals)):
+        out = out + _c(residuals[i], dtype) * _c(wl[i], dtype)
+    return out
+
+
+def tail_elem_bwd(dout, c1, wl, residuals, dtype=torch.float64):
+    """Backward of tail_elem -> (dc1 NHWC, [dwl_i], [dres_i]); dres[0] is None (residual 0 takes no part).  The LeakyReLU slope at
+    c1 == 0 is the negative side's 0.01."""
+    dout, c1 = _c(dout, dtype), _c(c1, dtype)
+    v = _shuffle2(c1)
+    w0 = _c(wl[0], dtype)
+    dc1 = _unshuffle2(dout * w0 * torch.where(v > 0, torch.ones_like(v), torch.full_like(v, 0.01)))
+    dwl = [(dout * torch.where(v > 0, v, 0.01 * v)).sum(0)]
+    dres = [None]
+    for i in range(1, len(residuals)):
+        dwl.append((dout * _c(residuals[i], dtype)).sum(0))
+        dres.append(dout * _c(wl[i], dtype))
+    return dc1, dwl, dres
+
+
+def se_gate_bwd(x, dg, fc1_w, fc1_b, fc2_w, fc2_b, dtype=torch.float64):
+    """Backward of g = x (1 + w), w = sigmoid(fc2 relu(fc1 mean_p x + b1) + b2), x / dg (B, P, C): with D[b, c] = sum_p dg x,
+    dlogit = D w (1 - w), dfc2 = dlogit^T h / sum_b dlogit, dh = (dlogit fc2_w) [h > 0], dfc1 = dh^T S / sum_b dh, dS = dh fc1_w,
+    dx = dg (1 + w) + dS / P.  Returns (dx, dfc1_w, dfc1_b, dfc2_w, dfc2_b)."""
+    x, dg, fc1_w, fc1_b, fc2_w, fc2_b = (_c(t, dtype) for t in (x, dg, fc1_w, fc1_b, fc2_w, fc2_b))
+    B, P, C = x.shape
+    S = x.sum(1) / P
+    pre = S @ fc1_w.t() + fc1_b
+    h = torch.clamp(pre, min=0.0)
+    w = _sigmoid(h @ fc2_w.t() + fc2_b)
+    dlog = (dg * x).sum(1) * w * (1.0 - w)
+    dh = (dlog @ fc2_w) * (pre > 0).to(dtype)
+    dx = dg * (1.0 + w)[:, None] + (dh @ fc1_w)[:, None] / P
+    return dx, dh.t() @ S, dh.sum(0), dlog.t() @ h, dlog.sum(0)
+
+
+def l1_loss(a, b, inv_count, dtype=torch.float64):
+    """inv_count sum |a - b| -> (1,)"""
+    return ((_c(a, dtype) - _c(b, dtype)).abs().sum() * inv_count).reshape(1)
+
+
+def l1_loss_bwd(a, b, grad_scale, inv_count, extra_a=None, dtype=torch.float64):
+    """da = grad_scale inv_count sign(a - b) (+ extra_a), db = -grad_scale inv_count sign(a - b).  At a tie a == b the subgradient
+    taken is 0 -- sign(0) = 0, the convention of torch.sign and so of torch's own L1 loss backward."""
+    a, b, extra_a = _c(a, dtype), _c(b, dtype), _c(extra_a, dtype)
+    g = float(grad_scale) * inv_count * torch.sign(a - b)
+    return (g if extra_a is None else g + extra_a), -g

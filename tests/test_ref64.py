@@ -170,3 +170,161 @@ def test_maxpool_affine_relu_vs_f_max_pool2d(B, H, W, C, kh, kw):
     assert torch.equal(got, ref)
     ref = F.max_pool2d(F.relu(nchw(x * s + t)), (kh, kw)).permute(0, 2, 3, 1).contiguous()
     close(ref64.maxpool_affine_relu(x, kh, kw, s, t), ref, "maxpool_affine_relu")
+
+
+# ====================================================================================================================
+# the hand-written gradients of the backward references against torch.autograd of an independent forward, in double
+def leaf(name, shape, lo=-1.0, hi=1.0):
+    return u(name, shape, lo, hi).requires_grad_(True)
+
+
+def test_gelu_and_its_derivative_vs_f_gelu():
+    x = leaf("gx", (501,), -6, 6)
+    y = F.gelu(x)
+    close(ref64.gelu(x), y.detach(), "gelu")
+    close(ref64.gelu_grad(x), torch.autograd.grad(y.sum(), x)[0], "gelu_grad")
+
+
+@pytest.mark.parametrize("B,L,C,G", [(2, 37, 96, 3), (1, 1, 64, 1), (3, 33, 192, 2)])
+def test_sk_select_and_backward_vs_autograd(B, L, C, G):
+    cg = C // G
+    cat, A, dV = leaf("cat", (B * L, C)), leaf("A", (B, G, cg)), u("dV", (B * L, cg))
+    V = torch.einsum("bgc,blgc->blc", A, cat.reshape(B, L, G, cg)).reshape(B * L, cg)
+    gcat, gA = torch.autograd.grad(V, (cat, A), dV)
+    close(ref64.sk_select(cat, A, L), V.detach(), "sk_select")
+    dcat, dA, parts = ref64.sk_select_bwd(cat, A, dV, L)
+    close(dcat, gcat, "sk_select_bwd dcat")
+    close(dA, gA, "sk_select_bwd dA")
+    assert parts.shape == ((L + 31) // 32, B, C)
+    close(parts.sum(0).reshape(B, G, cg), gA, "sk_select_bwd partial rows")
+
+
+@pytest.mark.parametrize("B,C,G,dmid,ppi,L", [(3, 96, 3, 24, 7, 200), (1, 192, 2, 48, 1, 9), (2, 96, 2, 8, 9, 64)])
+def test_sk_gate_backward_vs_autograd(B, C, G, dmid, ppi, L):
+    partial = leaf("part", (B * ppi, C), 0.0, 20.0)
+    w1, b1 = leaf("w1", (dmid, C), -0.2, 0.2), leaf("b1", (dmid,), -0.3, 0.3)
+    w2, b2 = leaf("w2", (C, dmid), -0.5, 0.5), leaf("b2", (C,), -0.3, 0.3)
+    dA = u("dA", (B, G, C // G))
+    S = partial.reshape(B, ppi, C).sum(1) / L
+    S.retain_grad()
+    A = torch.softmax(F.linear(F.gelu(F.linear(S, w1, b1)), w2, b2).reshape(B, G, C // G), 1)
+    A.backward(dA)
+    close(ref64.sk_pool(partial, ppi, L), S.detach(), "sk_pool")
+    close(ref64.sk_gate(S, w1, b1, w2, b2, G), A.detach(), "sk_gate")
+    r = ref64.sk_gate_bwd(partial, ppi, L, w1, b1, w2, A, dA)
+    for key, g in (("dS", S.grad), ("dfc1_w", w1.grad), ("dfc1_b", b1.grad), ("dfc2_w", w2.grad), ("dfc2_b", b2.grad)):
+        close(r[key], g, "sk_gate_bwd " + key)
+    close(r["wpart2"].sum(0), torch.cat([w2.grad.reshape(-1), b2.grad]), "sk_gate_bwd wpart2")
+    close(r["wpart1"].sum(0), torch.cat([w1.grad.reshape(-1), b1.grad]), "sk_gate_bwd wpart1")
+
+
+@pytest.mark.parametrize("B,L,C", [(3, 5, 97), (1, 1, 96)])
+def test_sk_feats_grad_vs_autograd(B, L, C):
+    feats, dout, dS = leaf("feats", (B * L, C), -6, 6), u("dout", (B * L, C)), u("dS", (B, C))
+    loss = (feats * dout).sum() + (F.gelu(feats).reshape(B, L, C).mean(1) * dS).sum()
+    close(ref64.sk_feats_grad(dout, feats, dS, L), torch.autograd.grad(loss, feats)[0], "sk_feats_grad")
+
+
+@pytest.mark.parametrize("with_mask", [False, True])
+@pytest.mark.parametrize("gp,in_gelu,out_gelu", [(False, False, False), (True, False, False), (True, True, False), (True, True, True)])
+@pytest.mark.parametrize("B,Ch,r", [(2, 3, 4), (1, 5, 12)])
+def test_dwconv3x3_backward_vs_autograd(B, Ch, r, gp, in_gelu, out_gelu, with_mask):
+    P, w, bias = leaf("P", (B, Ch, r, r), -3, 3), leaf("w", (Ch, 3, 3)), leaf("bias", (Ch,))
+    dg = u("dg", (B, Ch, r, r))
+    mask = (u("m", (B, Ch, r, r), 0, 1) > 0.3).double() / 0.7 if with_mask else None
+    a = F.gelu(P) if in_gelu else P
+    if not out_gelu:
+        a = a.detach().requires_grad_(True)      # the kernel then returns the gradient of the conv's (unmasked) input
+    x = a * mask if with_mask else a
+    y = F.conv2d(x, w[:, None], bias, padding=1, groups=Ch)
+    out = F.gelu(y) if gp else y
+    gin, gw, gb = torch.autograd.grad(out, (P if out_gelu else a, w, bias), dg)
+    dP, dw, db = ref64.dwconv3x3_bwd(P, dg, w, y if gp else None, in_gelu, out_gelu, mask)
+    close(dP, gin, "dwconv3x3_bwd dP")
+    close(dw, gw.reshape(Ch, 9), "dwconv3x3_bwd dw")
+    close(db, gb, "dwconv3x3_bwd db")
+
+
+def _torch_act(x, name, slope):
+    return {"none": lambda v: v * 1.0, "gelu": F.gelu, "relu": F.relu, "leaky02": lambda v: F.leaky_relu(v, 0.2),
+            "leaky001": lambda v: F.leaky_relu(v, 0.01), "mish": F.mish, "prelu": lambda v: F.prelu(v, torch.tensor([slope], dtype=v.dtype)),
+            "tanh": torch.tanh, "sigmoid": torch.sigmoid}[name](x)
+
+
+@pytest.mark.parametrize("name", sorted(ref64.ACT_CODES))
+def test_act_and_its_derivative_vs_torch(name):
+    code, slope = ref64.ACT_CODES[name], 0.25
+    with torch.no_grad():
+        x0 = u("ax", (400,), -6, 6)
+        x0[::50] = 0.0                       # the kink: value 0, slope of the negative side
+    x = x0.requires_grad_(True)
+    y = _torch_act(x, name, slope)
+    close(ref64.act(x, code, slope), y.detach(), "act " + name)
+    close(ref64.act_grad(x, code, slope), torch.autograd.grad(y.sum(), x)[0], "act_grad " + name)
+
+
+def test_elementwise_and_reduction_references():
+    x, z, y = u("x", (257,)), u("z", (257,)), u("y", (257,))
+    close(ref64.axpby(x, z, y, 0.5, -2.0, True), torch.add(torch.add(y, x, alpha=0.5), z, alpha=-2.0), "axpby accumulate")
+    close(ref64.axpby(x, None, y, 0.5, -2.0, False), 0.5 * x, "axpby z = None, overwrite")
+    m = u("m", (35, 13))
+    want = torch.zeros(7, dtype=torch.float64).index_add_(0, torch.arange(35) % 7, m.sum(1))
+    close(ref64.rowsum_mod(m, 7), want, "rowsum_mod")
+    close(ref64.colsum(m), torch.ones(1, 35, dtype=torch.float64).mm(m)[0], "colsum")
+    dw, db = ref64.rows_reduce(m, 9, 4)
+    close(dw, sum(m[i, :9] for i in range(35)), "rows_reduce dw")
+    close(db, sum(m[i, 9:] for i in range(35)), "rows_reduce db")
+    assert ref64.rows_reduce(m, 13, 0)[1].numel() == 0
+
+
+@pytest.mark.parametrize("B,H,W,n", [(3, 2, 3, 4), (1, 2, 3, 0), (2, 4, 2, 1)])
+def test_tail_elem_and_backward_vs_autograd(B, H, W, n):
+    with torch.no_grad():
+        c0 = u("c1", (B, H, W, 12))
+        c0.reshape(-1)[::7] = 0.0
+    c1 = c0.requires_grad_(True)
+    wl = [leaf("wl%d" % i, (3, 2 * H, 2 * W)) for i in range(max(n, 1))]
+    res = [leaf("res%d" % i, (B, 3, 2 * H, 2 * W)) for i in range(n)]
+    dout = u("dout", (B, 3, 2 * H, 2 * W))
+    out = F.leaky_relu(F.pixel_shuffle(c1.permute(0, 3, 1, 2), 2), 0.01) * wl[0]
+    for i in range(1, n):                    # residual 0 is skipped
+        out = out + res[i] * wl[i]
+    out.backward(dout)
+    close(ref64.tail_elem(c1, wl, res), out.detach(), "tail_elem")
+    dc1, dwl, dres = ref64.tail_elem_bwd(dout, c1, wl, res)
+    close(dc1, c1.grad, "tail_elem_bwd dc1")
+    assert len(dwl) == max(n, 1) and len(dres) == max(n, 1) and dres[0] is None and (n == 0 or res[0].grad is None)
+    for i in range(max(n, 1)):
+        close(dwl[i], wl[i].grad, "tail_elem_bwd dwl %d" % i)
+    for i in range(1, n):
+        close(dres[i], res[i].grad, "tail_elem_bwd dres %d" % i)
+
+
+@pytest.mark.parametrize("B,P,C,Cm", [(3, 7, 32, 32), (1, 1, 64, 32)])
+def test_se_gate_backward_vs_autograd(B, P, C, Cm):
+    x, dg = leaf("x", (B, P, C), -2, 2), u("dg", (B, P, C))
+    w1, b1, w2, b2 = leaf("w1", (Cm, C), -0.3, 0.3), leaf("b1", (Cm,)), leaf("w2", (C, Cm), -0.5, 0.5), leaf("b2", (C,))
+    gate = torch.sigmoid(F.linear(F.relu(F.linear(x.mean(1), w1, b1)), w2, b2))
+    g = x * (1.0 + gate[:, None])
+    close(ref64.se_gate(x, w1, b1, w2, b2), g.detach(), "se_gate")
+    g.backward(dg)
+    for got, want, what in zip(ref64.se_gate_bwd(x, dg, w1, b1, w2, b2), (x.grad, w1.grad, b1.grad, w2.grad, b2.grad), ("dx", "dfc1_w", "dfc1_b", "dfc2_w", "dfc2_b")):
+        close(got, want, "se_gate_bwd " + what)
+
+
+@pytest.mark.parametrize("with_extra", [False, True])
+def test_l1_loss_and_backward_vs_autograd(with_extra):
+    n = 257
+    with torch.no_grad():
+        a0, b0 = u("a", (n,)), u("b", (n,))
+        b0[::5] = a0[::5]                    # exact ties: sign(0) = 0
+    a, b = a0.requires_grad_(True), b0.requires_grad_(True)
+    extra = u("extra", (n,)) if with_extra else None
+    loss = F.l1_loss(a, b, reduction="sum") / n
+    close(ref64.l1_loss(a, b, 1.0 / n), loss.detach().reshape(1), "l1_loss")
+    total = 0.7 * loss + ((a * extra).sum() if with_extra else 0.0)
+    total.backward()
+    da, db = ref64.l1_loss_bwd(a, b, 0.7, 1.0 / n, extra)
+    assert bool((da[::5] == (extra[::5] if with_extra else 0.0)).all()) and bool((db[::5] == 0).all())
+    close(da, a.grad, "l1_loss_bwd da")
+    close(db, b.grad, "l1_loss_bwd db")
