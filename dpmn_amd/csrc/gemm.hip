@@ -343,7 +343,12 @@ __global__ __launch_bounds__(256) void k_gemm_kloop(const float* __restrict__ x,
   const int cps = (nk_all + gridDim.z - 1) / gridDim.z;      // K chunks per split (grid.z > 1 only with e.atomic)
   const int kt0 = bz * cps;
   const int nk = min(nk_all, kt0 + cps);
-  if (kt0 >= nk) return;
+  if (kt0 >= nk) {
+    // a split without k-chunks (fewer chunks than splits, or the rounded-up share leaves the last splits empty): nothing to add with
+    // atomics, but in store mode the caller's reduce reads this split's slab -- store the zero tile (no loads: kt0 lies past K)
+    if (e.zstride != 0 && !e.atomic) epilogue<3, 2>(acc, m_blk + wm * 32, n_blk + wn * 48, M, N, ldy, y, e, nullptr, BN, n_blk);
+    return;
+  }
   KL_GLOAD(a, kt0 * BK);
   KL_GLOAD(b, min(kt0 + 1, nk - 1) * BK);
   KL_SSTORE(a, 0);

@@ -205,7 +205,10 @@ __global__ __launch_bounds__(256, 3) void k_gemm_kloop_x3(const float* __restric
   const int cps = (nk_all + gridDim.z - 1) / gridDim.z;
   const int kt0 = bz * cps;
   const int nk = min(nk_all, kt0 + cps);
-  if (kt0 >= nk) return;
+  if (kt0 >= nk) {      // a split without k-chunks: in store mode its slab is still read by the caller's reduce (as k_gemm_kloop)
+    if (e.zstride != 0 && !e.atomic) epilogue<3, 2>(acc, m_blk + wm * 32, n_blk + wn * 48, M, N, ldy, y, e, nullptr, BN, n_blk);
+    return;
+  }
   gload(kt0 * BK);
   sstore();
   __syncthreads();

@@ -421,3 +421,66 @@ def l1_loss_bwd(a, b, grad_scale, inv_count, extra_a=None, dtype=torch.float64):
     a, b, extra_a = _c(a, dtype), _c(b, dtype), _c(extra_a, dtype)
     g = float(grad_scale) * inv_count * torch.sign(a - b)
     return (g if extra_a is None else g + extra_a), -g
+
+
+# ====================================================================================================================
+# GEMM family (csrc/gemm.hip and its bf16x3 twins, dpmn_gemm_tn_f32): written from each operation's definition; `dtype` as above
+def linear(x, w, bias=None, res1=None, res2=None, act_code=0, slope=0.0, pro=None, dtype=torch.float64):
+    """y = act(pro(x) w^T + bias) + res1 + res2 (the residuals AFTER the activation): x (M, K), w (N, K).  `pro`, the prologue on x:
+    None; ("add", addv): x + addv; ("cat2", x2): the channel concatenation [x | x2]; ("ln", gamma, beta, eps): nn.LayerNorm over the
+    row, two passes (mean, then the mean of the squared deviations)."""
+    x, w, bias, res1, res2 = (_c(t, dtype) for t in (x, w, bias, res1, res2))
+    if pro is not None and pro[0] == "add":
+        x = x + _c(pro[1], dtype)
+    elif pro is not None and pro[0] == "cat2":
+        x = torch.cat([x, _c(pro[1], dtype)], 1)
+    elif pro is not None and pro[0] == "ln":
+        x = _ln(x, _c(pro[1], dtype), _c(pro[2], dtype), pro[3])
+    elif pro is not None:
+        raise ValueError(pro[0])
+    y = x @ w.t()
+    if bias is not None:
+        y = y + bias
+    y = act(y, act_code, slope, dtype)
+    if res1 is not None:
+        y = y + res1
+    if res2 is not None:
+        y = y + res2
+    return y
+
+
+def linear_drop(x, w, bias, res, mask_elem, mask_row, dtype=torch.float64):
+    """y = res + ((x w^T + bias) mask_elem) mask_row: the Linear's output times the element mask, then the per-sample mask (each 0 or
+    1 / (1 - p), already expanded to (M, N); None: that factor is off), the residual last -- the order of dpmn_dropout_f32."""
+    y = linear(x, w, bias, dtype=dtype)
+    if mask_elem is not None:
+        y = y * _c(mask_elem, dtype)
+    if mask_row is not None:
+        y = y * _c(mask_row, dtype)
+    return _c(res, dtype) + y
+
+
+def sk_proj(cat, w, bias, rows=32, dtype=torch.float64):
+    """feats = cat w^T + bias and partial[i] = sum of GELU(feats[m]) over the rows m in [rows i, rows i + rows) below M:
+    -> (feats (M, C), partial (ceil(M / rows), C))"""
+    feats = linear(cat, w, bias, dtype=dtype)
+    g = gelu(feats, dtype)
+    return feats, torch.stack([g[r0:r0 + rows].sum(0) for r0 in range(0, feats.shape[0], rows)])
+
+
+def pointwise(g, w, bias, dtype=torch.float64):
+    """z[b] = w g[b] + bias[:, None]: g (B, Ch, L), w (Ch, Ch)"""
+    g, w, bias = _c(g, dtype), _c(w, dtype), _c(bias, dtype)
+    return w @ g + bias[None, :, None]
+
+
+def pointwise_wgrad(dz, g, dtype=torch.float64):
+    """dw = sum_b dz[b] g[b]^T: the weight gradient of pointwise for the cotangent dz (B, Ch, L) -> (Ch, Ch)"""
+    dz, g = _c(dz, dtype), _c(g, dtype)
+    return (dz @ g.transpose(1, 2)).sum(0)
+
+
+def gemm_tn(dy, x, dtype=torch.float64):
+    """dW = dy^T x, db = column sums of dy: the nn.Linear weight / bias gradient for dy (M, N), x (M, K) -> ((N, K), (N,))"""
+    dy, x = _c(dy, dtype), _c(x, dtype)
+    return dy.t() @ x, dy.sum(0)

@@ -328,3 +328,63 @@ def test_l1_loss_and_backward_vs_autograd(with_extra):
     assert bool((da[::5] == (extra[::5] if with_extra else 0.0)).all()) and bool((db[::5] == 0).all())
     close(da, a.grad, "l1_loss_bwd da")
     close(db, b.grad, "l1_loss_bwd db")
+
+
+# ====================================================================================================================
+# GEMM family references
+@pytest.mark.parametrize("name", ["none", "gelu", "leaky02", "prelu"])
+@pytest.mark.parametrize("M,N,K", [(5, 8, 32), (33, 100, 96)])
+def test_linear_vs_f_linear(M, N, K, name):
+    code, slope = ref64.ACT_CODES[name], 0.25
+    x, w, b, r1, r2 = u("lx", (M, K)), u("lw", (N, K), -0.3, 0.3), u("lb", (N,)), u("lr1", (M, N)), u("lr2", (M, N))
+    pre = F.linear(x, w, b)
+    close(ref64.linear(x, w), F.linear(x, w), "linear")
+    close(ref64.linear(x, w, b, None, None, code, slope), _torch_act(pre, name, slope), "linear bias " + name)
+    close(ref64.linear(x, w, b, r1, None, code, slope), _torch_act(pre, name, slope) + r1, "linear res1 " + name)
+    close(ref64.linear(x, w, b, r1, r2, code, slope), _torch_act(pre, name, slope) + r1 + r2, "linear res1 res2 " + name)
+    close(ref64.linear(x, w, None, r1, None, code, slope), _torch_act(F.linear(x, w), name, slope) + r1, "linear no bias " + name)
+
+
+@pytest.mark.parametrize("M,N,K", [(5, 8, 32), (33, 100, 96)])
+def test_linear_prologues_vs_functional(M, N, K):
+    x, w, b = u("px", (M, K)), u("pw", (N, K), -0.3, 0.3), u("pb", (N,))
+    addv = u("padd", (M, K))
+    close(ref64.linear(x, w, b, act_code=1, pro=("add", addv)), F.gelu(F.linear(x + addv, w, b)), "add prologue")
+    k1 = K // 4 + 4
+    close(ref64.linear(x[:, :k1].contiguous(), w, b, act_code=1, pro=("cat2", x[:, k1:].contiguous())), F.gelu(F.linear(x, w, b)), "cat2 prologue")
+    xo = x + 3.0 * u("prow", (M, 1))
+    gm, bt = u("pg", (K,), 0.5, 1.5), u("pbeta", (K,))
+    close(ref64.linear(xo, w, b, act_code=1, pro=("ln", gm, bt, 1e-5)), F.gelu(F.linear(F.layer_norm(xo, (K,), gm, bt, 1e-5), w, b)), "ln prologue")
+
+
+def test_linear_drop_and_sk_proj_vs_functional():
+    M, N, K = 12, 8, 32
+    x, w, b, res = u("dx", (M, K)), u("dw", (N, K), -0.3, 0.3), u("db", (N,)), u("dres", (M, N))
+    me = (u("dme", (M, N), 0, 1) > 0.3).double() / 0.7
+    mr = ((u("dmr", (M, 1), 0, 1) > 0.25).double() / 0.75).expand(M, N)
+    close(ref64.linear_drop(x, w, b, res, me, mr), res + F.linear(x, w, b) * me * mr, "linear_drop")
+    close(ref64.linear_drop(x, w, b, res, None, mr), res + F.linear(x, w, b) * mr, "linear_drop row mask only")
+    M = 70
+    cat = u("scat", (M, K), -3, 3)
+    feats, part = ref64.sk_proj(cat, w, b)
+    close(feats, F.linear(cat, w, b), "sk_proj feats")
+    assert part.shape == (3, N)
+    want = torch.zeros(3, N, dtype=torch.float64).index_add_(0, torch.arange(M) // 32, F.gelu(F.linear(cat, w, b)))
+    close(part, want, "sk_proj partial column sums")
+
+
+@pytest.mark.parametrize("B,Ch,L", [(3, 8, 32), (1, 12, 64)])
+def test_pointwise_and_wgrad_vs_conv1d_autograd(B, Ch, L):
+    g, w, bias, dz = leaf("pwg", (B, Ch, L)), leaf("pww", (Ch, Ch)), leaf("pwb", (Ch,)), u("pwdz", (B, Ch, L))
+    z = F.conv1d(g, w[:, :, None], bias)
+    close(ref64.pointwise(g, w, bias), z.detach(), "pointwise")
+    close(ref64.pointwise_wgrad(dz, g), torch.autograd.grad(z, w, dz)[0], "pointwise_wgrad")
+
+
+@pytest.mark.parametrize("M,N,K", [(1, 4, 8), (37, 12, 20)])
+def test_gemm_tn_vs_autograd(M, N, K):
+    x, w, b, dy = u("tx", (M, K)), leaf("tw", (N, K)), leaf("tb", (N,)), u("tdy", (M, N))
+    gw, gb = torch.autograd.grad(F.linear(x, w, b), (w, b), dy)
+    dW, db = ref64.gemm_tn(dy, x)
+    close(dW, gw, "gemm_tn dW")
+    close(db, gb, "gemm_tn db")
