@@ -778,6 +778,29 @@ __global__ void k_adam_clip(float* __restrict__ p, const float* __restrict__ g, 
   m[i] = mi; v[i] = vi;
   p[i] -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
 }
+// k_adam_clip + the exponential moving average of the parameters in the same pass: e = d*e + (1-d)*p_new.  The parameter and moment
+// expressions are k_adam_clip's own, token for token (same FMA contraction: p, m, v come out bitwise equal); the average is one more
+// read-modify-write by the thread that holds p_new, 8 extra bytes per parameter where a pass of its own would move 12.
+__global__ void k_adam_clip_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ e, const float* __restrict__ normsq, float max_norm, float lr, float b1, float b2,
+                                float eps, float bc1, float bc2_sqrt, float d, long n, const float* __restrict__ step_dev) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (step_dev) {      // step count lives on the device (hipGraph replay: host scalars are frozen at capture time)
+    const float t = step_dev[0];
+    bc1 = 1.f - powf(b1, t);
+    bc2_sqrt = sqrtf(1.f - powf(b2, t));
+  }
+  float coef = 1.f;
+  if (max_norm > 0.f) { coef = max_norm / (sqrtf(normsq[0]) + 1e-6f); coef = coef < 1.f ? coef : 1.f; }
+  const float gi = g[i] * coef;
+  const float mi = b1 * m[i] + (1.f - b1) * gi;
+  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  m[i] = mi; v[i] = vi;
+  const float pi = p[i] - (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
+  p[i] = pi;
+  e[i] = d * e[i] + (1.f - d) * pi;
+}
 
 }  // namespace
 
@@ -1109,6 +1132,21 @@ int dpmn_adam_clip_f32(float* param, const float* grad, float* exp_avg, float* e
   const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
   hipLaunchKernelGGL(k_adam_clip, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq,
                      grad_normsq, max_norm, lr, beta1, beta2, eps, bc1, bc2s, n, step_dev);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+int dpmn_adam_clip_ema_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, const float* grad_normsq,
+                           float max_norm, float lr, float beta1, float beta2, float eps, int step, const float* step_dev,
+                           float ema_decay, long n, dpmn_stream_t stream) {
+  DPMN_REQUIRE(param && grad && exp_avg && exp_avg_sq && ema && n > 0 && (step >= 1 || step_dev), "adam_clip_ema: bad arguments");
+  DPMN_REQUIRE(ema_decay > 0.f && ema_decay < 1.f, "adam_clip_ema: ema_decay must lie in (0, 1)");
+  if (step < 1) step = 1;
+  DPMN_REQUIRE(max_norm <= 0.f || grad_normsq, "adam_clip_ema: grad_normsq required when clipping");
+  const float bc1 = 1.f - powf(beta1, (float)step);
+  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+  hipLaunchKernelGGL(k_adam_clip_ema, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad, exp_avg,
+                     exp_avg_sq, ema, grad_normsq, max_norm, lr, beta1, beta2, eps, bc1, bc2s, ema_decay, n, step_dev);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }

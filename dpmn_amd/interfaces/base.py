@@ -47,13 +47,15 @@ def _val_weights(config, key, path, what):
 # holds tensors and plain Python values only, so it loads with torch.load(weights_only=True).
 TRAIN_STATE_VERSION = 1
 FINGERPRINT_FIELDS = ("arch", "stu_iter_b1", "stu_iter_b2", "sr_share", "patch_size", "embed_dim", "depths", "num_heads", "window_size",
-                      "window_num", "mlp_ratio", "height", "width", "manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade")
-# booleans, and jpeg_degrade: None or [lo, hi, prob]; a state written before they existed has them off
-DATA_FIELDS = ("manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade")
+                      "window_num", "mlp_ratio", "height", "width", "manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema")
+# booleans, jpeg_degrade: None or [lo, hi, prob], and ema: None or the decay of the averaged weights; a state written before they
+# existed has them off
+DATA_FIELDS = ("manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema")
 
 
-def state_fingerprint(args, config):
-    """What decides the structure of the trained models: a state is only ever loaded into a run with the same values."""
+def state_fingerprint(args, config, ema=None):
+    """What decides the structure of the trained models: a state is only ever loaded into a run with the same values.
+    ema: the decay TextSR.train(ema_decay=...) averages the weights with (main.py --ema), None = off."""
     fp = {k: getattr(args, k) for k in ("arch", "stu_iter_b1", "stu_iter_b2", "window_num")}
     fp["sr_share"] = bool(args.sr_share)
     for k in ("patch_size", "embed_dim", "depths", "num_heads", "window_size", "mlp_ratio"):
@@ -64,6 +66,8 @@ def state_fingerprint(args, config):
     fp["train_hr_dir"] = bool(getattr(args, "train_hr_dir", None))
     jpeg = jpeg_setting(args)
     fp["jpeg_degrade"] = None if jpeg is None else list(jpeg)
+    # the averaged weights are part of the trainer's state: a run with them only continues a run that kept them, at the same decay
+    fp["ema"] = None if ema is None else float(ema)
     return fp
 
 
@@ -76,7 +80,7 @@ def _data_field(v):
     """A DATA_FIELDS value as it is compared: off (absent, None, False) -> None, a flag -> True, a setting -> its values."""
     if not v:
         return None
-    return True if isinstance(v, bool) else list(v)
+    return v if isinstance(v, (bool, float)) else list(v)
 
 
 def check_fingerprint(saved, current, path=""):

@@ -8,6 +8,7 @@ glyph-atlas pipeline of interfaces/text_prior.py (--re
 --synthetic_prior.  On real TextZoom data (dataset/textzoom.py) --arch tatt gets its label_vecs from the frozen CRNN mirror
 (model/crnn.py, super_resolution.py:165-169).
 """
+import contextlib
 import csv
 import os
 
@@ -521,7 +522,8 @@ class TextSR(base.TextBase):
 
     # ------------------------------------------------------------------ training (super_resolution.py:113-278)
     def build_training(self, world_size=1, group=None):
-        """models (PGRMs + CMM), frozen PSN, DistillModules, ImageLoss and the flat-bucket clip+Adam / all-reduce trainer."""
+        """models (PGRMs + CMM), frozen PSN, DistillModules, ImageLoss and the flat-bucket clip+Adam / all-reduce trainer.
+        self.ema_decay (set by train(ema_decay=...), or by the caller before this call): the trainer also averages the weights."""
         from ..loss.image_loss import ImageLoss
         from ..model.distill_module import DistillModule
         from ..train.optim import Trainer
@@ -530,7 +532,8 @@ class TextSR(base.TextBase):
         distill = [DistillModule().to(self.device) for _ in range(b1 + b2 - 2)]
         crit = ImageLoss(gradient=self.args.gradient, loss_weight=[1, 1])
         cfg = self.config.TRAIN
-        trainer = Trainer(models + distill, lr=cfg.lr, beta1=cfg.beta1, max_norm=0.25, world_size=world_size, group=group)
+        trainer = Trainer(models + distill, lr=cfg.lr, beta1=cfg.beta1, max_norm=0.25, world_size=world_size, group=group,
+                          ema_decay=getattr(self, "ema_decay", None))
         for m in models + distill:
             m.train()
             for p in m.parameters():
@@ -756,7 +759,8 @@ class TextSR(base.TextBase):
         run.graph = graph
         return run
 
-    def train(self, loader=None, steps=None, val_loader=None, rec=None, epochs=None, sampler=None, display=False, state_path=None):
+    def train(self, loader=None, steps=None, val_loader=None, rec=None, epochs=None, sampler=None, display=False, state_path=None,
+              ema_decay=None):
         """Training loop (super_resolution.py:125-337) over (images_hr, images_lr, label_vecs) batches (synthetic ones, or the
         TextZoom reader of dataset/textzoom.py through main.py).
         loader: a callable `loader(epoch) -> iterable` (a fresh pass per epoch), a re-iterable (list, DataLoader-like: walked
@@ -772,10 +776,17 @@ class TextSR(base.TextBase):
         state").  If it exists the run continues from it -- weights, BatchNorm statistics, Adam state, bookkeeping, the
         random streams, the position inside the epoch -- else the run starts fresh; rank 0 rewrites it (atomically) after every
         iteration that saved a checkpoint and at the end of the run.  `it` goes on counting and `steps` stays a total.  Without it
-        nothing is read or written beyond the files above."""
+        nothing is read or written beyond the files above.
+        ema_decay (main.py --ema, 0 < d < 1): the trainer keeps an exponential moving average of the weights, e = d * e + (1 - d) * p
+        after every step, started as a copy of the weights the models are built with (BasicSR's ema_decay).  Every validation pass
+        runs under the averaged weights (Trainer.ema_weights(); the BatchNorm statistics stay the live ones) and the best-model
+        checkpoints written from it hold them -- they are what was scored; checkpoint.pth keeps the live weights, the state file
+        carries the average, and a state only continues a run with the same setting."""
         dist = torch.distributed
         world = dist.get_world_size() if dist.is_initialized() else 1
         rank = dist.get_rank() if dist.is_initialized() else 0
+        self.ema_decay = ema_decay
+        fingerprint = base.state_fingerprint(self.args, self.config, ema=ema_decay)
         models, psn, distill, crit, trainer = self.build_training(world)
         if getattr(self, "rank_seed", None) is not None:      # models are built (and broadcast): now diverge the per-rank RNG
             from ..utils.util import set_seed
@@ -822,7 +833,7 @@ class TextSR(base.TextBase):
         if state_path is not None and os.path.isfile(state_path):
             # continue: fingerprint first, then weights + BatchNorm statistics (written through the state_dicts: views of the trainer's
             # parameter arena), Adam state, bookkeeping; the random streams follow in the epoch loop
-            state = base.read_train_state(state_path, base.state_fingerprint(self.args, self.config))
+            state = base.read_train_state(state_path, fingerprint)
             for m_, sd in zip(models + distill, state["models"] + state["distill"]):
                 m_.load_state_dict(sd)
             trainer.load_state_dict(state["trainer"])
@@ -871,7 +882,7 @@ class TextSR(base.TextBase):
                     log_rows = len(f.readlines())
             cpu_sd = lambda m_: {k: v.detach().cpu() for k, v in m_.state_dict().items()}
             base.write_train_state(state_path, {
-                "version": base.TRAIN_STATE_VERSION, "fingerprint": base.state_fingerprint(self.args, self.config), "world": world,
+                "version": base.TRAIN_STATE_VERSION, "fingerprint": fingerprint, "world": world,
                 "models": [cpu_sd(m_) for m_ in models], "distill": [cpu_sd(m_) for m_ in distill], "trainer": tsd, "rng": per_rank,
                 "loop": dict(loop_state(), log_rows=log_rows)})
 
@@ -927,29 +938,31 @@ class TextSR(base.TextBase):
                     # per data_name -- and the best model overall by the SUM of the subsets' scores (score = recognition accuracy
                     # when `rec` computes one, as in the reference; PSNR otherwise, e.g. without --rec crnn)
                     trainer.sync_params()
-                    current, psnr_d, ssim_d = {}, {}, {}
-                    for data_name, vl in val_sets:
-                        md = self.eval(models, vl() if callable(vl) else vl, epoch, rec=rec, model_psn=psn, text_prior_fn=fn,
-                                       display=display and rank == 0)
-                        converge.append({'iterator': it, 'acc': md['accuracy'], 'psnr': md['psnr_avg'], 'ssim': md['ssim_avg']})
-                        score = md['accuracy'] if md['accuracy'] is not None else md['psnr_avg']
-                        current[data_name], psnr_d[data_name], ssim_d[data_name] = float(score), md['psnr_avg'], md['ssim_avg']
-                        new_best = data_name not in best_hist or score > best_hist[data_name]
-                        if new_best:
-                            best_hist[data_name] = float(score)
-                            best_hist['epoch'] = epoch
-                            best_info = {'accuracy': md['accuracy'], 'psnr': md['psnr_avg'], 'ssim': md['ssim_avg']}
-                            if len(val_sets) > 1:
-                                save(epoch, it, True, data_name)
-                        log_row([epoch, data_name, md['accuracy'], md['psnr_avg'], md['ssim_avg']] + (["best_%s" % data_name] if new_best else []))
-                    for m_ in models + distill:
-                        m_.train()
-                    total = sum(current.values())
-                    if best is None or total > best:
-                        best = total
-                        best_info = {'accuracy': dict(current, epoch=epoch), 'psnr': psnr_d, 'ssim': ssim_d}
-                        save(epoch, it, True)
-                        log_row([epoch, "", "", "", "", "", "best_sum"])
+                    # with the average on, the pass scores the averaged weights, and the best-model files written inside it hold them
+                    with (trainer.ema_weights() if ema_decay is not None else contextlib.nullcontext()):
+                        current, psnr_d, ssim_d = {}, {}, {}
+                        for data_name, vl in val_sets:
+                            md = self.eval(models, vl() if callable(vl) else vl, epoch, rec=rec, model_psn=psn, text_prior_fn=fn,
+                                           display=display and rank == 0)
+                            converge.append({'iterator': it, 'acc': md['accuracy'], 'psnr': md['psnr_avg'], 'ssim': md['ssim_avg']})
+                            score = md['accuracy'] if md['accuracy'] is not None else md['psnr_avg']
+                            current[data_name], psnr_d[data_name], ssim_d[data_name] = float(score), md['psnr_avg'], md['ssim_avg']
+                            new_best = data_name not in best_hist or score > best_hist[data_name]
+                            if new_best:
+                                best_hist[data_name] = float(score)
+                                best_hist['epoch'] = epoch
+                                best_info = {'accuracy': md['accuracy'], 'psnr': md['psnr_avg'], 'ssim': md['ssim_avg']}
+                                if len(val_sets) > 1:
+                                    save(epoch, it, True, data_name)
+                            log_row([epoch, data_name, md['accuracy'], md['psnr_avg'], md['ssim_avg']] + (["best_%s" % data_name] if new_best else []))
+                        for m_ in models + distill:
+                            m_.train()
+                        total = sum(current.values())
+                        if best is None or total > best:
+                            best = total
+                            best_info = {'accuracy': dict(current, epoch=epoch), 'psnr': psnr_d, 'ssim': ssim_d}
+                            save(epoch, it, True)
+                            log_row([epoch, "", "", "", "", "", "best_sum"])
                 if it % cfg.saveInterval == 0:
                     save(epoch, it, False)
                     saved_at = it

@@ -30,6 +30,7 @@ zero-fills or adds a per-parameter gradient tensor.  A module invoked several ti
 call; the bucket is ready when as many backward calls have finished as forward calls were made.  Every other module
 keeps ordinary post-accumulate-grad hooks.
 """
+import contextlib
 import os
 import torch
 import torch.distributed as dist
@@ -62,6 +63,30 @@ def _adam_clip(p, g, m, v, normsq, max_norm, lr, beta1, beta2, eps, step, step_d
         raise RuntimeError("dpmn_amd: the optimizer kernels run on the GPU only")
     check(lib.dpmn_adam_clip_f32(dptr(p), dptr(g), dptr(m), dptr(v), dptr(normsq), max_norm, lr, beta1, beta2, eps, step,
                                  dptr(step_dev, True), p.numel(), stream()))
+
+
+def _adam_clip_ema(p, g, m, v, e, normsq, max_norm, lr, beta1, beta2, eps, step, step_dev, ema_decay):
+    """_adam_clip plus, in the same kernel, the exponential moving average of the parameters: e = d * e + (1 - d) * p_new
+    (csrc/conv_bwd.hip k_adam_clip_ema; p, m, v come out bitwise as from _adam_clip)."""
+    if not p.is_cuda:
+        raise RuntimeError("dpmn_amd: the optimizer kernels run on the GPU only")
+    check(lib.dpmn_adam_clip_ema_f32(dptr(p), dptr(g), dptr(m), dptr(v), dptr(e), dptr(normsq), max_norm, lr, beta1, beta2, eps, step,
+                                     dptr(step_dev, True), ema_decay, p.numel(), stream()))
+
+
+def ema_reference(e, p_new, ema_decay):
+    """float64 restatement of one update of the average (the tests' reference): d * e + (1 - d) * p_new with d the fp32 value the
+    kernel receives, every operation exact in float64 for fp32 operands up to the final sum."""
+    d = float(torch.tensor(ema_decay, dtype=torch.float32))
+    return d * e.double() + (1.0 - d) * p_new.double()
+
+
+def _update(p, g, m, v, e, normsq, max_norm, lr, beta1, beta2, eps, step, step_dev, ema_decay):
+    """clip + Adam of one range, fused with the average when there is one"""
+    if ema_decay is None:
+        _adam_clip(p, g, m, v, normsq, max_norm, lr, beta1, beta2, eps, step, step_dev)
+    else:
+        _adam_clip_ema(p, g, m, v, e, normsq, max_norm, lr, beta1, beta2, eps, step, step_dev, ema_decay)
 
 
 class FlatBucket:
@@ -102,7 +127,7 @@ class FlatBucket:
         self.n = n
         self.normsq = torch.zeros(1, device=dev)
         self.part = torch.empty(1024, device=dev)
-        self.m = self.v = None          # allocated on first stand-alone step(); a CommGroup owns them otherwise
+        self.m = self.v = self.e = None # allocated on first stand-alone step(); a CommGroup owns them otherwise
         self.group = None
         self.uses = 0                   # direct mode: forward calls of the module in this step ...
         self.done = 0                   # ... and backward calls that have finished
@@ -201,14 +226,17 @@ class FlatBucket:
         if self.group is not None:
             self.group.launched = False
 
-    def step(self, step, lr, beta1, beta2=0.999, eps=1e-8, max_norm=0.25, step_dev=None):
-        """clip + Adam over the whole bucket (single-process semantics)."""
+    def step(self, step, lr, beta1, beta2=0.999, eps=1e-8, max_norm=0.25, step_dev=None, ema_decay=None):
+        """clip + Adam over the whole bucket (single-process semantics).  ema_decay: also keep the exponential moving average of the
+        parameters in self.e (it starts as a copy of the parameters before the first such step)."""
         if self.m is None:
             self.m = torch.zeros_like(self.flat_p)
             self.v = torch.zeros_like(self.flat_p)
+        if ema_decay is not None and self.e is None:
+            self.e = self.flat_p.clone()
         self._wait_ready_event()
         _sumsq(self.flat_g, self.normsq, self.part)
-        _adam_clip(self.flat_p, self.flat_g, self.m, self.v, self.normsq, max_norm, lr, beta1, beta2, eps, step, step_dev)
+        _update(self.flat_p, self.flat_g, self.m, self.v, self.e, self.normsq, max_norm, lr, beta1, beta2, eps, step, step_dev, ema_decay)
 
 
 class SegmentedBucket:
@@ -309,6 +337,7 @@ class CommGroup:
             self.g_shard = self.flat_g
         self.m = torch.zeros(self.shard_n, device=dev)
         self.v = torch.zeros(self.shard_n, device=dev)
+        self.e = None       # Trainer(ema_decay=...): the average of the owned shard of flat_p (Trainer.reset_ema)
         self.normsq = torch.zeros(len(buckets), device=dev)
         self.part = torch.empty(1024, device=dev)
         self.launched = False
@@ -390,11 +419,11 @@ class CommGroup:
         b = min(self.offsets[i] + self.buckets[i].n, self.lo + self.shard_n)
         return (a - self.lo, b - a) if b > a else (0, 0)
 
-    def step(self, step, lr, beta1, beta2=0.999, eps=1e-8, max_norm=0.25, step_dev=None):
+    def step(self, step, lr, beta1, beta2=0.999, eps=1e-8, max_norm=0.25, step_dev=None, ema_decay=None):
         self.step_norms()
         if self.zero1:
             dist.all_reduce(self.normsq, op=dist.ReduceOp.SUM, group=self.pg)     # len(buckets) floats
-        self.step_update(step, lr, beta1, beta2, eps, max_norm, step_dev)
+        self.step_update(step, lr, beta1, beta2, eps, max_norm, step_dev, ema_decay)
 
     def step_norms(self, zero=True):
         """First half of step(): wait for the exchanged gradients, ||g||^2 of the part of every member this rank owns into self.normsq
@@ -414,14 +443,16 @@ class CommGroup:
             if k:
                 _sumsq(self.g_shard[o:o + k], self.normsq[i:i + 1], self.part)
 
-    def step_update(self, step, lr, beta1, beta2=0.999, eps=1e-8, max_norm=0.25, step_dev=None):
-        """Second half of step(): clip + Adam on the owned shard with the (all-reduced) norms, then the parameter all-gather."""
+    def step_update(self, step, lr, beta1, beta2=0.999, eps=1e-8, max_norm=0.25, step_dev=None, ema_decay=None):
+        """Second half of step(): clip + Adam (+ the average, ema_decay) on the owned shard with the (all-reduced) norms, then the
+        parameter all-gather."""
         owned = [self._owned(i) for i in range(len(self.buckets))]
         p_shard = self.flat_p[self.lo:self.lo + self.shard_n]
         for i, (o, k) in enumerate(owned):
             if k:
-                _adam_clip(p_shard[o:o + k], self.g_shard[o:o + k], self.m[o:o + k], self.v[o:o + k], self.normsq[i:i + 1],
-                           max_norm, lr, beta1, beta2, eps, step, step_dev)
+                _update(p_shard[o:o + k], self.g_shard[o:o + k], self.m[o:o + k], self.v[o:o + k],
+                        None if ema_decay is None else self.e[o:o + k], self.normsq[i:i + 1], max_norm, lr, beta1, beta2, eps, step,
+                        step_dev, ema_decay)
         if self.zero1:
             self.param_work = dist.all_gather_into_tensor(self.flat_p, p_shard, group=self.pg, async_op=True)
 
@@ -439,7 +470,14 @@ class Trainer:
     """zero_grad / gradient exchange / clip+Adam over a list of models, in the reference's order."""
 
     def __init__(self, models, lr=1e-3, beta1=0.5, max_norm=0.25, world_size=1, group=None, zero1=None, group_mb=16.0,
-                 force_collectives=False):
+                 force_collectives=False, ema_decay=None):
+        """ema_decay (0 < d < 1): every group also keeps `e`, the exponential moving average of its (shard of the) parameters, updated
+        by the optimizer kernel itself: e = d * e + (1 - d) * p_new after every step, started as a copy of the parameters
+        (reset_ema).  ema_weights() puts the averaged weights into the models for an evaluation.  None: nothing is allocated."""
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:       # (NaN fails both comparisons)
+            raise ValueError("dpmn_amd Trainer: ema_decay must lie in (0, 1), got %r" % (ema_decay,))
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self._ema_live = None       # inside ema_weights(): the live parameters
         self.lr, self.beta1, self.max_norm = lr, beta1, max_norm
         self.world = world_size
         multi = world_size > 1 or force_collectives      # force_collectives: run the RCCL calls at world size 1 (1-GPU box check)
@@ -534,6 +572,8 @@ class Trainer:
         if self.early:
             for g in self.groups:
                 g.early_cb = self._early_step
+        if self.ema_decay is not None:
+            self.reset_ema()        # (after the broadcast: the average starts from rank 0's parameters on every rank)
 
     @staticmethod
     def _backward_order(models):
@@ -552,6 +592,7 @@ class Trainer:
 
     def zero_grad(self):
         from ..model import packing
+        self._no_step_under_ema_weights()
         self.disarm()       # a previous backward whose step() never came: join its side-stream gradients before the zero fill
         self.flat_g.zero_()
         for b in self.buckets:
@@ -584,7 +625,8 @@ class Trainer:
     def state_snapshot(self):
         """Everything a step mutates in the optimizer (used to undo hipGraph warm-up steps)."""
         return dict(p=self.flat_p.clone(), t=self.t, t_dev=None if self.t_dev is None else self.t_dev.clone(),
-                    mv=[(g.m.clone(), g.v.clone()) for g in self.groups])
+                    mv=[(g.m.clone(), g.v.clone()) for g in self.groups],
+                    e=None if self.ema_decay is None else [g.e.clone() for g in self.groups])
 
     def state_restore(self, snap):
         self.flat_p.copy_(snap["p"])
@@ -594,7 +636,62 @@ class Trainer:
         for g, (m, v) in zip(self.groups, snap["mv"]):
             g.m.copy_(m)
             g.v.copy_(v)
+        if self.ema_decay is not None:
+            for g, e in zip(self.groups, snap["e"]):
+                g.e.copy_(e)
         self.invalidate_packs()
+
+    # ------------------------------------------------------------------ averaged weights (ema_decay)
+    def reset_ema(self):
+        """(Re)start the average as a copy of the current parameters -- what the constructor does; call it after writing weights
+        into the models in place.  Every group copies the shard of flat_p it owns, so the padding stays zero."""
+        if self.ema_decay is None:
+            raise RuntimeError("dpmn_amd Trainer: reset_ema() needs a trainer built with ema_decay")
+        self._join_updates()
+        for g in self.groups:
+            g.e = g.flat_p[g.lo:g.lo + g.shard_n].clone()
+
+    def _full(self, g, shards):
+        """The whole-range vectors behind a group's per-rank shards, stacked.  Under ZeRO-1 a COLLECTIVE: each rank owns 1/world of the
+        range; the shards are assembled by an integer all-reduce(SUM) of the bit patterns into a zero-filled buffer (exact, and the
+        one collective both gloo and RCCL offer for device tensors)."""
+        if not g.zero1:
+            return shards
+        buf = torch.zeros(len(shards), g.n, device=g.m.device)
+        for r, s_ in enumerate(shards):
+            buf[r, g.lo:g.lo + g.shard_n] = s_
+        dist.all_reduce(buf.view(torch.int32), op=dist.ReduceOp.SUM, group=g.pg)
+        return list(buf.unbind(0))
+
+    def _no_step_under_ema_weights(self):
+        if self._ema_live is not None:
+            raise RuntimeError("dpmn_amd Trainer: no training step inside ema_weights() -- the models hold the averaged weights")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """with trainer.ema_weights(): the models' parameters ARE the averaged weights (evaluate, save a checkpoint); on exit the
+        live parameters are back bit for bit.  BatchNorm running statistics are buffers, not parameters: the live ones stay.
+        Under ZeRO-1 a collective on the trainer's process group (every rank enters): each rank contributes the shard of the
+        average it owns.  Weight packs made from the other set of weights are dropped on entry and on exit.  Does not nest, and a
+        training step inside raises."""
+        if self.ema_decay is None:
+            raise RuntimeError("dpmn_amd Trainer: ema_weights() needs a trainer built with ema_decay")
+        if self._ema_live is not None:
+            raise RuntimeError("dpmn_amd Trainer: ema_weights() does not nest")
+        self._join_updates()
+        live = self.flat_p.clone()
+        for g in self.groups:
+            g.flat_p.copy_(self._full(g, [g.e])[0])
+        self._ema_live = live
+        self.invalidate_packs()
+        self.pack_cache.fresh = -1
+        try:
+            yield self
+        finally:
+            self.flat_p.copy_(live)
+            self._ema_live = None
+            self.invalidate_packs()
+            self.pack_cache.fresh = -1
 
     # ------------------------------------------------------------------ training state (continue an interrupted run)
     def _moment_layout(self):
@@ -616,26 +713,19 @@ class Trainer:
 
     def state_dict(self):
         """Adam's state in a layout that depends on neither world size nor group plan nor padding: {'t': step count, 'm' / 'v': per model
-        index ONE unpadded fp32 CPU vector, the exp_avg / exp_avg_sq of that model's parameters() concatenated in order}.
+        index ONE unpadded fp32 CPU vector, the exp_avg / exp_avg_sq of that model's parameters() concatenated in order}; with
+        ema_decay also 'e', the averaged weights in the same layout (without it the key does not exist).
         Under ZeRO-1 this is a COLLECTIVE on the trainer's process group (every rank calls it): each rank owns 1/world of every group's
         moments; the shards are assembled by an integer all-reduce(SUM) of the bit patterns into a zero-filled vector (exact, and the
         one collective both gloo and RCCL offer for device tensors).  The vectors are left on rank 0; other ranks get 'm' = 'v' = None."""
         self._join_updates()
-        full = []
-        for g in self.groups:
-            if not g.zero1:
-                full.append((g.m, g.v))
-                continue
-            mv = torch.zeros(2, g.n, device=g.m.device)
-            mv[0, g.lo:g.lo + g.shard_n] = g.m
-            mv[1, g.lo:g.lo + g.shard_n] = g.v
-            dist.all_reduce(mv.view(torch.int32), op=dist.ReduceOp.SUM, group=g.pg)
-            full.append((mv[0], mv[1]))
+        keys = ("m", "v") + (("e",) if self.ema_decay is not None else ())      # 'e': the averaged weights, in the same layout
+        full = [self._full(g, [getattr(g, key) for key in keys]) for g in self.groups]
         if self.zero1 and dist.get_rank(self.groups[0].pg) != 0:
-            return dict(t=self.t, m=None, v=None)
-        out = dict(t=self.t, m=[], v=[])
+            return dict(dict(t=self.t), **{key: None for key in keys})
+        out = dict(dict(t=self.t), **{key: [] for key in keys})
         for slices in self._moment_layout():
-            for key, which in (("m", 0), ("v", 1)):
+            for which, key in enumerate(keys):
                 out[key].append(torch.cat([full[gi][which][o:o + k] for gi, o, k in slices]).cpu())
         return out
 
@@ -644,7 +734,11 @@ class Trainer:
         each group it owns (padding stays zero, as a run leaves it: padded gradients are zero).  Parameters are not part of this state;
         they are restored through the models' state_dicts, which are views of the parameter arena."""
         layout = self._moment_layout()
-        for key in ("m", "v"):
+        keys = ("m", "v") + (("e",) if self.ema_decay is not None else ())      # (a trainer without the average ignores a state's 'e')
+        if self.ema_decay is not None and sd.get("e") is None:
+            raise ValueError("dpmn_amd Trainer.load_state_dict: this trainer averages its weights (ema_decay = %g) and the state holds "
+                             "no 'e' vectors: it was written by a run without the average" % self.ema_decay)
+        for key in keys:
             if sd.get(key) is None or len(sd[key]) != len(layout):
                 raise ValueError("dpmn_amd Trainer.load_state_dict: the state holds %s '%s' vectors, this trainer has %d models"
                                  % ("no" if sd.get(key) is None else len(sd[key]), key, len(layout)))
@@ -655,10 +749,11 @@ class Trainer:
                                      % (i, key, sd[key][i].numel(), want))
         self._join_updates()
         dev = self.flat_p.device
-        vec = {key: [t_.to(dev, torch.float32).reshape(-1) for t_ in sd[key]] for key in ("m", "v")}
+        vec = {key: [t_.to(dev, torch.float32).reshape(-1) for t_ in sd[key]] for key in keys}
         starts = [[sum(k for _, _, k in slices[:j]) for j in range(len(slices))] for slices in layout]
         for gi, g in enumerate(self.groups):
-            for key, shard in (("m", g.m), ("v", g.v)):
+            for key in keys:
+                shard = getattr(g, key)
                 full = torch.zeros(g.n, device=dev)
                 for i, slices in enumerate(layout):
                     for (gj, o, k), a in zip(slices, starts[i]):
@@ -677,6 +772,7 @@ class Trainer:
         gradients are still being written on a side stream (the bucket's ready_event covers them; Trainer.step / the gradient
         exchange wait for it).  Without this call a backward never touches the parameters and every gradient is complete in the
         order of the stream the backward ran on."""
+        self._no_step_under_ema_weights()
         self._armed = self.early
         for b in self.buckets:
             b.lazy_join = True      # a backward may leave leaf gradients on a side stream behind bucket.ready_event (train/cmm_train.py)
@@ -701,11 +797,12 @@ class Trainer:
                 self.opt_stream.wait_event(ev)
                 b.ready_event = None
         with torch.cuda.stream(self.opt_stream):
-            g.step(self.t + 1, self.lr, self.beta1, max_norm=self.max_norm, step_dev=None)
+            g.step(self.t + 1, self.lr, self.beta1, max_norm=self.max_norm, step_dev=None, ema_decay=self.ema_decay)
         g.stepped = True
 
     def step(self):
         from ..model import packing
+        self._no_step_under_ema_weights()
         self.t += 1
         if self.t_dev is not None:
             self.t_dev.add_(1.0)
@@ -726,10 +823,10 @@ class Trainer:
             for idx in self.seg_slots:       # per-MODEL clip of a model exchanged in segments: every segment reads the model's norm
                 self.normsq_all.index_copy_(0, idx, self.normsq_all.index_select(0, idx).sum().expand(idx.numel()).contiguous())
             for g in pending:
-                g.step_update(self.t, self.lr, self.beta1, max_norm=self.max_norm, step_dev=self.t_dev)
+                g.step_update(self.t, self.lr, self.beta1, max_norm=self.max_norm, step_dev=self.t_dev, ema_decay=self.ema_decay)
         else:
             for g in pending:
-                g.step(self.t, self.lr, self.beta1, max_norm=self.max_norm, step_dev=self.t_dev)
+                g.step(self.t, self.lr, self.beta1, max_norm=self.max_norm, step_dev=self.t_dev, ema_decay=self.ema_decay)
         self.disarm()       # (every ready_event was consumed by the group steps above: nothing left to wait for)
         if early:
             torch.cuda.current_stream(self.flat_p.device).wait_stream(self.opt_stream)

@@ -910,6 +910,11 @@ int dpmn_adam_clip_f32(float* param, const float* grad, float* exp_avg, float* e
                        float max_norm, float lr, float beta1, float beta2, float eps, int step,
                        const float* step_dev /* optional device scalar overriding `step` (hipGraph replay) */, long n,
                        dpmn_stream_t stream);
+/* the same update (param, exp_avg, exp_avg_sq bitwise those of dpmn_adam_clip_f32) plus, in the same pass, the exponential moving
+ * average of the parameters: ema = ema_decay * ema + (1 - ema_decay) * param_new, 0 < ema_decay < 1 (a host scalar) */
+int dpmn_adam_clip_ema_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                           const float* grad_normsq, float max_norm, float lr, float beta1, float beta2, float eps, int step,
+                           const float* step_dev, float ema_decay, long n, dpmn_stream_t stream);
 
 /* ------------------------------------------------------------------ PGRM module (pgrm_forward.hip) */
 typedef struct {

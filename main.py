@@ -15,7 +15,8 @@ in SR pixels, 0 for a hard edge), and written as `<stem>_photo_sr.png`; with `--
 word by a polygon (2k points, k along the top edge and k along the bottom, as CTW1500 and Total-Text write them), which is straightened
 strip by strip on the GPU (polygon regions are written as files; `--demo_paste_polygons` on top of `--demo_paste` also warps them back into
 the photo, strip by strip, in box-file order with the quadrilaterals).  `--train_state PATH` makes a training run continuable: the same command line starts the
-run or, when PATH exists, continues it bit for bit.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
+run or, when PATH exists, continues it bit for bit.  `--ema DECAY` keeps an exponential moving average of the trained weights; the
+validation passes score it and the best-model checkpoints hold it.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
 (`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
 import argparse
@@ -214,11 +215,22 @@ def main(config, args):
                           for name, vdl in zip(subset_names(val_dirs), val_dls)} if val_dls else None
             mission.train(lambda epoch: sr_batches(dl, mission.device, mission.mask), epochs=config.TRAIN.epochs,
                           sampler=getattr(mission, "train_sampler", None), val_loader=val_loader, rec=rec,
-                          display=args.vis_dir is not None, state_path=getattr(args, "train_state", None))
+                          display=args.vis_dir is not None, state_path=getattr(args, "train_state", None), ema_decay=getattr(args, "ema", None))
         else:
             # (a callable, not a one-shot generator: a run continued from --train_state walks the epoch again up to where it stopped)
             mission.train(lambda epoch: synthetic_loader(bs, args.synthetic_steps, 2000 + rank), steps=args.synthetic_steps, rec=rec,
-                          display=args.vis_dir is not None, epochs=1, state_path=getattr(args, "train_state", None))
+                          display=args.vis_dir is not None, epochs=1, state_path=getattr(args, "train_state", None), ema_decay=getattr(args, "ema", None))
+
+
+def ema_decay_arg(text):
+    """--ema DECAY: a float with 0 < DECAY < 1 (NaN fails both comparisons)"""
+    try:
+        d = float(text)
+    except ValueError:
+        d = float("nan")
+    if not 0.0 < d < 1.0:
+        raise argparse.ArgumentTypeError("--ema must be a decay with 0 < DECAY < 1, got %r" % text)
+    return d
 
 
 def subset_names(val_dirs):
@@ -304,6 +316,10 @@ if __name__ == '__main__':
     parser.add_argument('--train_state', type=str, default=None,
                         help='one file that holds everything needed to continue the training run exactly: if it exists the run '
                              'continues from it, otherwise it starts fresh; rewritten at every checkpoint save and at the end')
+    parser.add_argument('--ema', type=ema_decay_arg, default=None, metavar='DECAY',
+                        help='training: keep an exponential moving average of the weights (0 < DECAY < 1, for example 0.999); every '
+                             'validation pass scores the averaged weights and the best-model checkpoints hold them, checkpoint.pth '
+                             'keeps the live ones, --train_state carries the average')
     parser.add_argument('--manmade_degrade', action='store_true', default=False,
                         help='training: the LR images are synthesised from the HR images on the GPU (blur, noise, noise reduction, '
                              'sharpening) instead of read from the LMDB')
