@@ -127,10 +127,13 @@ class alignCollate_realWTLAMask(object):
     2 carries the same pair as position 0 and `sr_batches` degrades them on the GPU (ops.degrade_ragged_u8; cutblur=True: with the
     reference's cutblur).  The random draws happen in sr_batches, in the main process, not in the loader's workers.
     jpeg=(lo, hi, prob) (ours, needs degrade): with probability prob a synthesised LR image, after its resize, goes through a JPEG of a
-    quality drawn from lo .. hi (ops.jpeg_roundtrip_u8; the reference's JPEG_compress, dataset.py:559, fixes 40)."""
+    quality drawn from lo .. hi (ops.jpeg_roundtrip_u8; the reference's JPEG_compress, dataset.py:559, fixes 40).
+    render=(words, atlases) (ours, needs degrade; main.py --train_words, dataset/words.py WordsHR): the batch holds no image at all --
+    positions 0 and 2 are None and `sr_batches` renders the HR images on the GPU (ops.render_words_u8) from the words and parameters
+    it draws per batch; `render` is then True and `words` / `atlases` carry the pair."""
 
     def __init__(self, imgH=64, imgW=256, down_sample_scale=4, keep_ratio=False, min_ratio=1, mask=False, alphabet=53, train=True,
-                 y_domain=False, gpu_finish=False, gpu_resize=False, degrade=False, cutblur=False, jpeg=None):
+                 y_domain=False, gpu_finish=False, gpu_resize=False, degrade=False, cutblur=False, jpeg=None, render=None):
         if degrade and not gpu_resize:
             raise ValueError("alignCollate_realWTLAMask: degrade=True needs gpu_resize=True (the LR images are made on the GPU from the "
                              "packed HR pixels)")
@@ -147,6 +150,11 @@ class alignCollate_realWTLAMask(object):
                                  % (jpeg,))
             jpeg = (int(lo), int(hi), float(prob))
         self.jpeg = jpeg
+        if render is not None and not degrade:
+            raise ValueError("alignCollate_realWTLAMask: render=(words, atlases) needs degrade=True (the rendered HR images have no LR "
+                             "partner: it is synthesised on the GPU)")
+        self.render = render is not None
+        self.words, self.atlases = (list(render[0]), render[1]) if self.render else (None, None)
         self.imgH, self.imgW, self.down_sample_scale, self.mask = imgH, imgW, down_sample_scale, mask
         self.gpu_finish, self.gpu_resize, self.degrade, self.cutblur = gpu_finish, gpu_resize, bool(degrade), bool(cutblur)
         self.alphabet = "0123456789abcdefghijklmnopqrstuvwxyz"
@@ -164,7 +172,9 @@ class alignCollate_realWTLAMask(object):
 
     def __call__(self, batch):
         images_HR, images_lr, _, _, label_strs = zip(*batch)
-        if self.gpu_resize:      # (pin=False: a loader with pin_memory pins its batches itself, and workers must not open the GPU)
+        if self.render:          # (nothing to pack: sr_batches renders the batch on the GPU)
+            images_HR = images_lr = None
+        elif self.gpu_resize:      # (pin=False: a loader with pin_memory pins its batches itself, and workers must not open the GPU)
             from ..utils.resize import pack_ragged
             rgb = lambda im: np.asarray(im if im.mode == 'RGB' else im.convert('RGB'), dtype=np.uint8)
             images_HR = pack_ragged([rgb(im) for im in images_HR], pin=False)
@@ -211,7 +221,8 @@ def resize_on_gpu(pair, size, mask, device):
 
 
 def degrade_on_gpu(pair, size, scale, mask, device, cutblur=False, rng=None, jpeg=None):
-    """(packed, meta) of a degrade collate (the HR pixels) -> (images_hr (B, 3 + mask, H, W), images_lr (B, 3 + mask, H / scale,
+    """(packed, meta) of a degrade collate (the HR pixels; packed on the host, or already on `device`: a rendered batch of
+    ops.render_words_u8) -> (images_hr (B, 3 + mask, H, W), images_lr (B, 3 + mask, H / scale,
     W / scale)) float on `device`, size = (H, W): one upload, the degradation of the ragged batch at the images' own sizes
     (ops.degrade_ragged_u8: the parameters of utils.degrade.draw_params and one 63-bit noise seed, both drawn from `rng`, Python's
     `random` by default), the two ragged resizes and the collate kernel.  jpeg = (lo, hi, prob): the resized LR batch, and only it,
@@ -244,7 +255,9 @@ def sr_batches(loader, device=None, mask=None, size=None):
     when the pass starts, in the main process; batch j then draws from random.Random(that key + j).  TextSR.train fetches a batch
     before it writes the training state of the step before it, so per-batch draws from the global stream would be repeated after a
     continuation; keyed by (pass, batch) a continued run (--train_state restores the stream the key came from) sees exactly the LR
-    images the uninterrupted run saw."""
+    images the uninterrupted run saw.  Batches of a render collate (main.py --train_words) hold no image: from the batch's stream come
+    FIRST the words and render parameters (utils.render.draw_render, one sample per item of the batch), THEN exactly the draws of
+    degrade_on_gpu; the HR images are rendered on the GPU (ops.render_words_u8) and the yielded labels are the drawn words."""
     import random
     col = getattr(loader, "collate_fn", None)
     if mask is None:
@@ -253,9 +266,21 @@ def sr_batches(loader, device=None, mask=None, size=None):
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
     degrade = bool(getattr(col, "degrade", False))
     pass_key = random.getrandbits(63) if degrade else None
+    render = degrade and bool(getattr(col, "render", False))
     for j, data in enumerate(loader):
         hr, lr = data[0], data[2]
-        if isinstance(hr, (tuple, list)):
+        labels = list(data[5])
+        if render:
+            from .. import ops
+            from ..utils.render import draw_render
+            if size is None:
+                size = (col.imgH, col.imgW, col.down_sample_scale)
+            H, W, scale = size
+            rng = random.Random(pass_key + j)
+            labels, cls, lens, params = draw_render(col.words, col.atlases.n_fonts, rng, n=len(labels))
+            hr, lr = degrade_on_gpu(ops.render_words_u8(cls, lens, params, col.atlases, device=device), (H, W), scale, mask, device,
+                                    cutblur=col.cutblur, rng=rng, jpeg=getattr(col, "jpeg", None))
+        elif isinstance(hr, (tuple, list)):
             if size is None:
                 if not hasattr(col, "imgH"):
                     raise ValueError("sr_batches: a gpu_resize batch needs size=(imgH, imgW, down_sample_scale) or a loader whose "
@@ -269,4 +294,4 @@ def sr_batches(loader, device=None, mask=None, size=None):
                 hr, lr = resize_on_gpu(hr, (H, W), mask, device), resize_on_gpu(lr, (H // scale, W // scale), mask, device)
         elif hr.dtype == torch.uint8:
             hr, lr = finish_on_gpu(hr, mask, device), finish_on_gpu(lr, mask, device)
-        yield hr, lr, None, list(data[5])
+        yield hr, lr, None, labels

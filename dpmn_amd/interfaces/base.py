@@ -47,15 +47,16 @@ def _val_weights(config, key, path, what):
 # holds tensors and plain Python values only, so it loads with torch.load(weights_only=True).
 TRAIN_STATE_VERSION = 1
 FINGERPRINT_FIELDS = ("arch", "stu_iter_b1", "stu_iter_b2", "sr_share", "patch_size", "embed_dim", "depths", "num_heads", "window_size",
-                      "window_num", "mlp_ratio", "height", "width", "manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema")
-# booleans, jpeg_degrade: None or [lo, hi, prob], and ema: None or the decay of the averaged weights; a state written before they
-# existed has them off
-DATA_FIELDS = ("manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema")
+                      "window_num", "mlp_ratio", "height", "width", "manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema", "train_words")
+# booleans, jpeg_degrade: None or [lo, hi, prob], ema: None or the decay of the averaged weights, and train_words: None or the dict of
+# utils.render.words_setting (crc32 of the word list, sorted font names, epoch size); a state written before they existed has them off
+DATA_FIELDS = ("manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema", "train_words")
 
 
-def state_fingerprint(args, config, ema=None):
+def state_fingerprint(args, config, ema=None, train_words=None):
     """What decides the structure of the trained models: a state is only ever loaded into a run with the same values.
-    ema: the decay TextSR.train(ema_decay=...) averages the weights with (main.py --ema), None = off."""
+    ema: the decay TextSR.train(ema_decay=...) averages the weights with (main.py --ema), None = off.
+    train_words: the setting TextSR.train(train_words=...) renders its HR images from (main.py --train_words), None = off."""
     fp = {k: getattr(args, k) for k in ("arch", "stu_iter_b1", "stu_iter_b2", "window_num")}
     fp["sr_share"] = bool(args.sr_share)
     for k in ("patch_size", "embed_dim", "depths", "num_heads", "window_size", "mlp_ratio"):
@@ -68,18 +69,23 @@ def state_fingerprint(args, config, ema=None):
     fp["jpeg_degrade"] = None if jpeg is None else list(jpeg)
     # the averaged weights are part of the trainer's state: a run with them only continues a run that kept them, at the same decay
     fp["ema"] = None if ema is None else float(ema)
+    # the word list, fonts and epoch size decide which HR images a step sees: a run rendered from words only continues its like
+    fp["train_words"] = None if not train_words else {k: (list(v) if isinstance(v, (list, tuple)) else v) for k, v in dict(train_words).items()}
     return fp
 
 
 def degrade_flags(args):
-    """(manmade_degrade, cutblur) of the training loader: --train_hr_dir implies --manmade_degrade."""
-    return bool(getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None)), bool(getattr(args, "cutblur", False))
+    """(manmade_degrade, cutblur) of the training loader: --train_hr_dir and --train_words imply --manmade_degrade."""
+    return (bool(getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None) or getattr(args, "train_words", None)),
+            bool(getattr(args, "cutblur", False)))
 
 
 def _data_field(v):
     """A DATA_FIELDS value as it is compared: off (absent, None, False) -> None, a flag -> True, a setting -> its values."""
     if not v:
         return None
+    if isinstance(v, dict):
+        return sorted((k, list(x) if isinstance(x, (list, tuple)) else x) for k, x in v.items())
     return v if isinstance(v, (bool, float)) else list(v)
 
 
@@ -178,7 +184,7 @@ class TextBase(object):
 
     # ------------------------------------------------------------------ data (base.py:85-125)
     def _loader(self, dirs, test, shuffle, drop_last, shard=False, gpu_finish=True, gpu_resize=False, degrade=False, cutblur=False,
-                hr_dir=None, jpeg=None):
+                hr_dir=None, jpeg=None, words=None):
         """shard=True (training under torch.distributed): every rank walks its own 1/world of a per-epoch permutation
         (DistributedSampler, call `self.train_sampler.set_epoch(epoch)`) with batch_size // world samples per step, so the
         GLOBAL batch stays config.TRAIN.batch_size at the configured learning rate -- nn.DataParallel's scatter of one batch
@@ -189,13 +195,18 @@ class TextBase(object):
         from the HR images on the GPU (ops.degrade_ragged_u8 in sr_batches; cutblur=True: with cutblur), which needs gpu_finish and
         turns gpu_resize on.  hr_dir (--train_hr_dir): a folder of HR images instead of the LMDBs of `dirs` (dataset/folder.py
         FolderHR), always degraded.  jpeg=(lo, hi, prob) (--jpeg_degrade / --jpeg_prob; with degrade, training data only): JPEG
-        artefacts on the synthesised LR images (ops.jpeg_roundtrip_u8 in sr_batches)."""
+        artefacts on the synthesised LR images (ops.jpeg_roundtrip_u8 in sr_batches).  words=(words, atlases, epoch size)
+        (--train_words): no image data at all -- dataset/words.py WordsHR, the HR images are rendered on the GPU by sr_batches
+        (ops.render_words_u8), always degraded."""
         from ..dataset import textzoom as tz
         cfg = self.config.TRAIN
-        degrade = bool(degrade or hr_dir)
+        degrade = bool(degrade or hr_dir or words)
         if degrade and not gpu_finish:
             raise ValueError("dpmn_amd: manmade_degrade makes the LR images on the GPU: it needs gpu_finish=True")
-        if hr_dir:
+        if words:
+            from ..dataset.words import WordsHR
+            sets = [WordsHR(words[0], words[2])]
+        elif hr_dir:
             from ..dataset.folder import FolderHR
             sets = [FolderHR(hr_dir, voc_type=cfg.voc_type)]
         else:
@@ -215,18 +226,25 @@ class TextBase(object):
             collate_fn=tz.alignCollate_realWTLAMask(imgH=cfg.height, imgW=cfg.width, down_sample_scale=cfg.down_sample_scale, mask=self.mask,
                                                     gpu_finish=gpu_finish,      # True: ToTensor + mask channel on the GPU by sr_batches
                                                     gpu_resize=gpu_finish and (gpu_resize or degrade or bool(getattr(self.args, "gpu_resize", False))),
-                                                    degrade=degrade, cutblur=cutblur, jpeg=jpeg))
+                                                    degrade=degrade, cutblur=cutblur, jpeg=jpeg,
+                                                    render=(words[0], words[1]) if words else None))
         # (dataset/textzoom.py; uint8 pixels in the batch); False: the reference's float (B, 3 + mask, H, W) tensors for consumers that
         # iterate the loader themselves
         if shard:
             self.train_sampler = sampler
         return ds, loader
 
-    def get_train_data(self):
+    def get_train_data(self, train_words=None):
+        """train_words (main.py --train_words): (words, atlases, epoch size) -- the filtered word list, utils.render.build_atlases of
+        the fonts and the number of samples that counts as one epoch; the training set is then rendered from it."""
         cfg = self.config.TRAIN
         degrade, cutblur = degrade_flags(self.args)
         hr_dir = getattr(self.args, "train_hr_dir", None)
         jpeg = jpeg_setting(self.args)
+        if train_words is not None:
+            if hr_dir:
+                raise ValueError("dpmn_amd: train_words and train_hr_dir are two sources of the HR images; give one")
+            return self._loader([], False, True, True, shard=True, degrade=True, cutblur=cutblur, jpeg=jpeg, words=tuple(train_words))
         if hr_dir:
             return self._loader([], False, True, True, shard=True, degrade=True, cutblur=cutblur, hr_dir=hr_dir, jpeg=jpeg)
         if not isinstance(cfg.train_data_dir, list):

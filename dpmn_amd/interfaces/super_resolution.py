@@ -760,7 +760,7 @@ class TextSR(base.TextBase):
         return run
 
     def train(self, loader=None, steps=None, val_loader=None, rec=None, epochs=None, sampler=None, display=False, state_path=None,
-              ema_decay=None):
+              ema_decay=None, train_words=None):
         """Training loop (super_resolution.py:125-337) over (images_hr, images_lr, label_vecs) batches (synthetic ones, or the
         TextZoom reader of dataset/textzoom.py through main.py).
         loader: a callable `loader(epoch) -> iterable` (a fresh pass per epoch), a re-iterable (list, DataLoader-like: walked
@@ -781,12 +781,15 @@ class TextSR(base.TextBase):
         after every step, started as a copy of the weights the models are built with (BasicSR's ema_decay).  Every validation pass
         runs under the averaged weights (Trainer.ema_weights(); the BatchNorm statistics stay the live ones) and the best-model
         checkpoints written from it hold them -- they are what was scored; checkpoint.pth keeps the live weights, the state file
-        carries the average, and a state only continues a run with the same setting."""
+        carries the average, and a state only continues a run with the same setting.
+        train_words (main.py --train_words): the setting of a run whose HR images are rendered from a word list
+        (utils.render.words_setting: crc32 of the list, font names, epoch size; the loader itself comes from
+        get_train_data(train_words=...)).  It only goes into the state's fingerprint: a state continues a run with the same setting."""
         dist = torch.distributed
         world = dist.get_world_size() if dist.is_initialized() else 1
         rank = dist.get_rank() if dist.is_initialized() else 0
         self.ema_decay = ema_decay
-        fingerprint = base.state_fingerprint(self.args, self.config, ema=ema_decay)
+        fingerprint = base.state_fingerprint(self.args, self.config, ema=ema_decay, train_words=train_words)
         models, psn, distill, crit, trainer = self.build_training(world)
         if getattr(self, "rank_seed", None) is not None:      # models are built (and broadcast): now diverge the per-rank RNG
             from ..utils.util import set_seed

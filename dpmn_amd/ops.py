@@ -342,6 +342,71 @@ def degrade_noise(seed, meta, device=None):
     return out
 
 
+RENDER_TILE = (8, 128)      # csrc/render.hip RD_TILE_H, RD_TILE_W
+
+
+def render_words_u8(words_cls, lengths, params, atlases, device=None, out=None):
+    """HR text crops of a batch of words (csrc/render.hip; main.py --train_words): words_cls (B, 25) integer glyph classes, lengths (B),
+    params (B, 24) = what utils.render.draw_render returns, atlases = utils.render.build_atlases(...) -> (packed, meta): the images
+    back to back in a 1-D uint8 device tensor and the int64 (B, 3) host tensor of (byte offset, h, w) -- the pair
+    utils.resize.pack_ragged gives for the same images (utils.render.render_meta computes the sizes), byte for byte
+    utils.render.render_u8 per image, ready for degrade_ragged_u8 and resize_ragged_u8.  One launch; the atlases live on the device
+    per Atlases object.  out: a contiguous 1-D uint8 device tensor of at least the packed size to write into (bytes outside the images'
+    extents are left alone; the first returned item is then `out` itself)."""
+    import numpy as np
+    from .utils import render as rd
+    if not torch.cuda.is_available():
+        raise _abi.DpmnError("render_words_u8: the images are rendered on the GPU; there is no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise _abi.DpmnError("render_words_u8: the images are rendered on the GPU (got device %s); there is no CPU fallback" % dev)
+    to_np = lambda a: a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    try:
+        cls, lens, p = rd.check_render(to_np(words_cls), to_np(lengths), to_np(params), atlases)
+        m = rd.render_meta(cls, lens, p, atlases)
+    except ValueError as e:
+        raise _abi.DpmnError("render_words_u8: %s" % e)
+    B = m.shape[0]
+    nbytes = int(m[-1, 0] + m[-1, 1] * m[-1, 2] * 3)
+    if B > 65535 or nbytes > 2 ** 31 - 1:
+        raise _abi.DpmnError("render_words_u8: at most 65535 images and 2^31 - 1 bytes per batch")
+    th, tw = -(-m[:, 1] // RENDER_TILE[0]), -(-m[:, 2] // RENDER_TILE[1])
+    first = np.concatenate(([0], np.cumsum(th * tw)))
+    n_tiles = int(first[-1])
+    tiles = np.empty((n_tiles, 3), np.int32)
+    for b in range(B):
+        t = tiles[first[b]:first[b + 1]]
+        t[:, 0] = b
+        t[:, 1] = np.repeat(np.arange(th[b]), tw[b])
+        t[:, 2] = np.tile(np.arange(tw[b]), th[b])
+    # one upload: meta + first tile, params, classes, lengths and tiles in one int64 buffer (the int32 parts reinterpreted on the device)
+    o_par, o_cls = B * 4, B * 4 + B * rd.N_PARAMS
+    o_len = o_cls + (B * rd.MAX_LEN + 1) // 2
+    o_til = o_len + (B + 1) // 2
+    host = np.zeros(o_til + (n_tiles * 3 + 1) // 2, np.int64)
+    host[:o_par] = np.concatenate((m, first[:-1, None]), axis=1).reshape(-1)
+    host[o_par:o_cls] = p.reshape(-1)
+    host[o_cls:o_len].view(np.int32)[:B * rd.MAX_LEN] = cls.reshape(-1)
+    host[o_len:o_til].view(np.int32)[:B] = lens
+    host[o_til:].view(np.int32)[:n_tiles * 3] = tiles.reshape(-1)
+    d = torch.from_numpy(host).to(dev)
+    key = (dev.type, dev.index)
+    if key not in atlases._device:
+        atlases._device[key] = (torch.from_numpy(atlases.alpha).to(dev), torch.from_numpy(atlases.advance).to(dev),
+                                torch.from_numpy(atlases.height).to(dev))
+    alpha, adv, hts = atlases._device[key]
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif (not torch.is_tensor(out) or out.device != dev or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous()
+          or out.numel() < nbytes):
+        raise _abi.DpmnError("render_words_u8: out must be a contiguous 1-D uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+    hp = host.ctypes.data
+    check(lib.dpmn_render_words_u8(d[o_cls:].data_ptr(), d[o_len:].data_ptr(), d[o_par:].data_ptr(), alpha.data_ptr(), adv.data_ptr(),
+                                   hts.data_ptr(), d.data_ptr(), d[o_til:].data_ptr(), n_tiles, out.data_ptr(), out.numel(), B,
+                                   atlases.n_fonts, alpha.shape[3], alpha.shape[4], hp + 8 * o_cls, hp + 8 * o_len, hp + 8 * o_par, hp, stream()))
+    return out, torch.from_numpy(m)
+
+
 def jpeg_roundtrip_u8(images_u8, quality, out=None):
     """JPEG artefacts (csrc/jpeg.hip): images_u8 = a contiguous (B, h, w, 3) uint8 RGB batch on the device, quality = B integers (a
     sequence or a tensor), 1 .. 100 per image or 0 for "leave this image alone" -> a new (B, h, w, 3) uint8 device tensor, per image

@@ -513,6 +513,21 @@ int dpmn_degrade_noise_f32(unsigned long long seed, const long long* items, long
 size_t dpmn_jpeg_roundtrip_workspace_bytes(int B, int h, int w);
 int dpmn_jpeg_roundtrip_u8(const unsigned char* in, unsigned char* out, const int* quality, int B, int h, int w, void* workspace,
                            size_t workspace_bytes, dpmn_stream_t stream);
+/* HR text crops from strings (render.hip; main.py --train_words): B words laid out of a glyph atlas into a RAGGED batch written straight
+ * into the packed layout of dpmn_resize_ragged_u8 (the images back to back, HWC), byte for byte utils/render.py render_u8 -- scaled
+ * advances, shear, integer bilinear alpha (Q16), flat or gradient background with grain, integer blend.  classes: device int32 (B, 25),
+ * the glyph classes of every word (0 .. 36); lengths: device int32 (B), 1 .. 25; params: device int64 (B, 24), the rows of
+ * utils/render.py draw_render; atlas_u8: device uint8 (n_fonts, 2, 37, GH, GW) alpha, advance: device int32 (n_fonts, 2, 37), atlas_h:
+ * device int32 (n_fonts), the base height of every atlas (<= GH); meta: device int64 (B, 4), per image [byte offset in out_packed, h, w,
+ * index of its first tile] with the sizes of utils/render.py render_meta; tiles: device int32 (n_tiles, 3), per 8 x 128 tile [image,
+ * tile row, tile column].  host_classes / host_lengths / host_params / host_meta: the caller's HOST copies of the same four arrays;
+ * they are checked before the launch: B <= 0, a length above 25, a class outside the atlas, a font index out of range, a side above
+ * 8192 or an image outside the out_bytes of out_packed is an error.  The kernel clamps what it reads all the same and writes only inside
+ * the images' extents.  One launch. */
+int dpmn_render_words_u8(const int* classes, const int* lengths, const long long* params, const unsigned char* atlas_u8, const int* advance,
+                         const int* atlas_h, const long long* meta, const int* tiles, int n_tiles, unsigned char* out_packed, long out_bytes,
+                         int B, int n_fonts, int GH, int GW, const int* host_classes, const int* host_lengths, const long long* host_params,
+                         const long long* host_meta, dpmn_stream_t stream);
 /* A wide text line as overlapping windows of the model's LR size (tile.hip; utils/tile.py holds the plan arithmetic and the numpy
  * restatement).  resize_windows: a RAGGED batch in the packed layout of dpmn_resize_ragged_u8 -> every image resized with PIL's
  * fixed-point bicubic (the arithmetic of dpmn_resize_ragged_u8, byte for byte Image.resize((w_line, lr_h), BICUBIC)) to the height lr_h

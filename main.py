@@ -17,7 +17,7 @@ strip by strip on the GPU (polygon regions are written as files; `--demo_paste_p
 the photo, strip by strip, in box-file order with the quadrilaterals).  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--ema DECAY` keeps an exponential moving average of the trained weights; the
 validation passes score it and the best-model checkpoints hold it.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
-(`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
+(`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB); `--train_words FILE` trains from a word list alone: the HR images are rendered on the GPU (`--train_words_fonts DIR`: in the fonts of a directory; `--train_words_epoch N`: samples per epoch).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
 import argparse
 import csv
@@ -88,8 +88,51 @@ def paste_feather(args):
     return f
 
 
+TRAIN_WORDS_OR_HR_DIR = ("main.py: --train_words and --train_hr_dir are two sources of the HR training images (a word list rendered on the "
+                         "GPU, a folder of images); give one of them")
+TRAIN_WORDS_FONTS_NEEDS = "main.py: --train_words_fonts needs --train_words: the fonts are those the words are rendered in"
+
+
+def train_words_source(args, voc_type):
+    """--train_words FILE [--train_words_fonts DIR] [--train_words_epoch N] -> (words, atlases, epoch size), or None without the flag.
+    Every problem is a SystemExit of one line: the two-sources conflict, a missing file, a file without a usable word, a font directory
+    without a usable font, an epoch size below 1."""
+    path, fonts = getattr(args, "train_words", None), getattr(args, "train_words_fonts", None)
+    if not path:
+        if fonts:
+            raise SystemExit(TRAIN_WORDS_FONTS_NEEDS)
+        return None
+    if getattr(args, "train_hr_dir", None):
+        raise SystemExit(TRAIN_WORDS_OR_HR_DIR)
+    from dpmn_amd.utils import render
+    epoch = getattr(args, "train_words_epoch", None)
+    epoch = render.DEFAULT_EPOCH if epoch is None else int(epoch)
+    if epoch < 1:
+        raise SystemExit("main.py: --train_words_epoch must be a positive number of samples, got %d" % epoch)
+    if not os.path.isfile(path):
+        raise SystemExit("main.py: --train_words %s is not a file" % path)
+    words = render.read_words(path, voc_type)
+    files = None
+    if fonts:
+        if not os.path.isdir(fonts):
+            raise SystemExit("main.py: --train_words_fonts %s is not a directory" % fonts)
+        files = render.font_files(fonts)
+        if not files:
+            raise SystemExit("main.py: --train_words_fonts %s holds no *.ttf / *.otf file" % fonts)
+    try:
+        atlases = render.build_atlases(files)
+    except ValueError:
+        raise SystemExit("main.py: --train_words_fonts %s holds no font that PIL can open" % fonts)
+    return words, atlases, epoch
+
+
 def main(config, args):
-    if getattr(args, "cutblur", False) and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None)):
+    words_on = bool(getattr(args, "train_words", None))
+    if words_on and getattr(args, "train_hr_dir", None):
+        raise SystemExit(TRAIN_WORDS_OR_HR_DIR)
+    if getattr(args, "train_words_fonts", None) and not words_on:
+        raise SystemExit(TRAIN_WORDS_FONTS_NEEDS)
+    if getattr(args, "cutblur", False) and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None) or words_on):
         raise SystemExit("main.py: --cutblur needs --manmade_degrade (or --train_hr_dir): it mixes columns of the HR image into the "
                          "synthesised LR image")
     from dpmn_amd.utils.jpeg import jpeg_setting
@@ -97,7 +140,7 @@ def main(config, args):
         jpeg = jpeg_setting(args)
     except ValueError as e:
         raise SystemExit("main.py: %s" % e)
-    if jpeg is not None and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None)):
+    if jpeg is not None and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None) or words_on):
         raise SystemExit("main.py: --jpeg_degrade needs --manmade_degrade (or --train_hr_dir): the JPEG artefacts are put on the "
                          "synthesised LR images")
     if getattr(args, "demo_tile", False) and not getattr(args, "demo_dir", None):
@@ -117,6 +160,8 @@ def main(config, args):
     hr_dir = getattr(args, "train_hr_dir", None)
     if hr_dir and not os.path.isdir(hr_dir):
         raise SystemExit("main.py: --train_hr_dir %s is not a directory" % hr_dir)
+    # (the word list is read and the atlases are rasterised before anything touches the GPU: a bad file ends the run here)
+    words = train_words_source(args, getattr(getattr(config, "TRAIN", None), "voc_type", None) or "upper") if words_on else None
     import torch
     import torch.distributed as dist
     from dpmn_amd.interfaces.super_resolution import TextSR
@@ -200,13 +245,18 @@ def main(config, args):
             with open(log_path, "w+") as out:
                 csv.writer(out).writerow(["epoch", "dataset", "accuracy", "psnr_avg", "ssim_avg", "best", "best_sum"])
         dirs = config.TRAIN.train_data_dir or []
-        if hr_dir or (dirs and all(os.path.isdir(d) for d in dirs)):       # TextZoom LMDBs from the config, like base.py:85-103, or --train_hr_dir
+        if words or hr_dir or (dirs and all(os.path.isdir(d) for d in dirs)):       # TextZoom LMDBs from the config, like base.py:85-103, --train_hr_dir or --train_words
             from dpmn_amd.dataset.textzoom import sr_batches
             world = dist.get_world_size() if dist.is_initialized() else 1
             if bs % world != 0 or bs // world < 2:
                 raise SystemExit("main.py: batch_size %d does not shard over %d ranks in per-rank batches of >= 2 images (the global batch "
                                  "stays batch_size: nn.DataParallel's scatter, base.py:160-162)" % (bs, world))
-            dl = mission.get_train_data()[1]           # per-rank shard of a per-epoch permutation (DistributedSampler)
+            # per-rank shard of a per-epoch permutation (DistributedSampler); --train_words: of the epoch's sample numbers
+            dl = (mission.get_train_data(train_words=words) if words else mission.get_train_data())[1]
+            words_fp = None
+            if words:
+                from dpmn_amd.utils.render import words_setting
+                words_fp = words_setting(*words)
             val_dirs = (config.TRAIN.VAL or {}).get("val_data_dir") or []
             val_dls = mission.get_val_data()[1] if val_dirs and all(os.path.isdir(d) for d in val_dirs) else []
             # eval every VAL.valInterval over every validation subset + best-model checkpoints (super_resolution.py:283-337)
@@ -215,7 +265,8 @@ def main(config, args):
                           for name, vdl in zip(subset_names(val_dirs), val_dls)} if val_dls else None
             mission.train(lambda epoch: sr_batches(dl, mission.device, mission.mask), epochs=config.TRAIN.epochs,
                           sampler=getattr(mission, "train_sampler", None), val_loader=val_loader, rec=rec,
-                          display=args.vis_dir is not None, state_path=getattr(args, "train_state", None), ema_decay=getattr(args, "ema", None))
+                          display=args.vis_dir is not None, state_path=getattr(args, "train_state", None), ema_decay=getattr(args, "ema", None),
+                          train_words=words_fp)
         else:
             # (a callable, not a one-shot generator: a run continued from --train_state walks the epoch again up to where it stopped)
             mission.train(lambda epoch: synthetic_loader(bs, args.synthetic_steps, 2000 + rank), steps=args.synthetic_steps, rec=rec,
@@ -333,7 +384,19 @@ if __name__ == '__main__':
     parser.add_argument('--train_hr_dir', type=str, default=None,
                         help='train from this folder of HR images (optional labels.txt: file name<TAB>word); implies --manmade_degrade, '
                              'needs no LMDB')
+    parser.add_argument('--train_words', type=str, default=None, metavar='FILE',
+                        help='train from this word list alone (one word per line, UTF-8): the HR images are rendered on the GPU in random '
+                             'fonts, sizes, colours, spacing and shear, every sample with its true label; implies --manmade_degrade, needs '
+                             'no image data; not together with --train_hr_dir')
+    parser.add_argument('--train_words_fonts', type=str, default=None, metavar='DIR',
+                        help='with --train_words: every *.ttf / *.otf of this directory is a font (default: PIL\'s built-in font)')
+    parser.add_argument('--train_words_epoch', type=int, default=10000, metavar='N',
+                        help='with --train_words: the number of rendered samples that counts as one epoch')
     args = parser.parse_args()
+    if args.train_words and args.train_hr_dir:
+        parser.error(TRAIN_WORDS_OR_HR_DIR[len("main.py: "):])
+    if args.train_words_fonts and not args.train_words:
+        parser.error(TRAIN_WORDS_FONTS_NEEDS[len("main.py: "):])
     if args.demo_boxes and not args.demo_dir:
         parser.error(DEMO_BOXES_NEEDS_DIR[len("main.py: "):])
     if args.demo_paste and not args.demo_boxes:
