@@ -9,6 +9,7 @@
 // SKConv gate 86-91, Mlp depthwise 34-36, tail 559-565, SwinTransformerBlock.forward 315-331,
 // PGRM.forward 546-565.
 #include "common.h"
+#include <atomic>
 
 namespace {
 
@@ -16,7 +17,7 @@ namespace {
 // One wave = 16 tokens; lane -> (token = l>>2, part = l&3).  Each lane produces C/4 embedding channels of its
 // token; with the fused prior_fusion conv3x3 (2->3, pad 1) each lane first evaluates ONE of the 2x2 patch pixels
 // and the four lanes of a token exchange results by shuffle.  pe weights sit in LDS transposed ([k][c]) so the
-// four parts read distinct banks.
+// four parts read distinct banks.  The finished rows leave through a wave-private LDS tile as contiguous 1 KB stores (end of the kernel).
 template <int C, int PATCH, bool FUSE>
 __global__ __launch_bounds__(256) void k_patch_embed_ln(const float* __restrict__ img, int cin, const float* __restrict__ pf_w,
                                                          const float* __restrict__ pf_b, const float* __restrict__ pe_w,
@@ -29,6 +30,8 @@ __global__ __launch_bounds__(256) void k_patch_embed_ln(const float* __restrict_
   static_assert(!FUSE || PATCH == 2, "fused prior conv assumes 2x2 patches (one pixel per lane of the token quad)");
   __shared__ __attribute__((aligned(16))) float wt[KP * C];
   __shared__ float pfw[3 * 2 * 9 + 3];
+  constexpr int LDT = C + 4;
+  __shared__ __attribute__((aligned(16))) float stg[4 * 16 * LDT];   // per wave: 16 finished token rows on their way out
   for (int i = threadIdx.x; i < KP * C; i += 256) wt[(i % KP) * C + i / KP] = pe_w[i];   // pe_w (C, KP) -> [k][c]
   if (FUSE && threadIdx.x < 57) pfw[threadIdx.x] = threadIdx.x < 54 ? pf_w[threadIdx.x] : pf_b[threadIdx.x - 54];
   __syncthreads();
@@ -99,8 +102,12 @@ __global__ __launch_bounds__(256) void k_patch_embed_ln(const float* __restrict_
   for (int i = 0; i < CQ; ++i) { const float d = o[i] - mean; q += d * d; }
   q += xshfl<1>(q); q += xshfl<2>(q);
   const float rstd = 1.0f / sqrtf(q * (1.0f / C) + 1e-5f);
-  if (!valid) return;
-  float* dst = tok + (size_t)token * C + part * CQ;
+  // A lane's six float4 of a token row sit 96 bytes from its neighbour's: stored from the registers, a wave instruction touches 64 partial
+  // lines and the write path moved 1.9 x the token bytes (35 MB for 18.9 MB at B = 48).  The wave's 16 finished rows go through a
+  // wave-private LDS tile instead (rows padded by one float4 against bank conflicts) and leave as 16 C contiguous floats, 1 KB per store
+  // instruction.  Lanes of a token past the end computed the last token again; the row count below keeps them out of memory.
+  const int wave = threadIdx.x >> 6;
+  float* sw = stg + wave * 16 * LDT;
   const float ik = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.f;
 #pragma unroll
   for (int i = 0; i < CQ; i += 4) {
@@ -112,7 +119,18 @@ __global__ __launch_bounds__(256) void k_patch_embed_ln(const float* __restrict_
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] *= drop_scale_z(z0 + (unsigned long long)r * DROP_PHI, p_drop, ik);
     }
-    *reinterpret_cast<float4*>(dst + i) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(sw + (lane >> 2) * LDT + c) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the tile is private to the wave: no block barrier
+  const long tok0 = (long)blockIdx.x * 64 + wave * 16;
+  const long left = ntok - tok0;
+  const int nfl = (left >= 16 ? 16 : (left > 0 ? (int)left : 0)) * C;   // floats of this wave's rows that exist
+  float* dst = tok + (size_t)tok0 * C;
+#pragma unroll
+  for (int it = 0; it < C / 16; ++it) {
+    const int idx = (it * 64 + lane) * 4;
+    const int row = idx / C, col = idx - row * C;
+    if (idx < nfl) *reinterpret_cast<float4*>(dst + idx) = *reinterpret_cast<const float4*>(sw + row * LDT + col);
   }
 }
 
@@ -590,45 +608,78 @@ int launch_window_attn(const float* q, const float* kv, const float* table, floa
 
 // ---------------------------------------------------------------------------------- SK gate
 // per image: S = mean_t GELU(feats) (from per-block partials) -> fc1 -> GELU -> fc2 -> softmax over groups
-__global__ void k_sk_gate(const float* __restrict__ partial, int parts_per_image, int L, const float* __restrict__ fc1_w,
+// One block of 512 threads per image, and a pure latency chain: so every global read of the block is requested before anything is
+// waited for.  Waves 0-3 sum the partials as FOUR chains per channel (chain q adds partials q, q + 4, ... in that order, chain 0 the
+// leftover ones behind its own; S = ((s0 + s1) + (s2 + s3)) / L -- the grouping a single thread per channel used before, same
+// bits), each chain's loads issued together; waves 4-7 meanwhile copy both weight matrices and both biases into LDS, twelve loads
+// per lane in flight (clamped index, predicated LDS store: no branch around a load), so that the two Linear layers read LDS.
+constexpr int SKG_T = 512, SKG_STAGE = 12;
+__global__ __launch_bounds__(SKG_T) void k_sk_gate(const float* __restrict__ partial, int parts_per_image, int L, const float* __restrict__ fc1_w,
                           const float* __restrict__ fc1_b, const float* __restrict__ fc2_w, const float* __restrict__ fc2_b,
                           float* __restrict__ attn_vec, int C, int G, int dmid) {
   extern __shared__ float sm[];
-  float* S = sm;            // [C]
-  float* Z = sm + C;        // [dmid]
-  float* A = Z + dmid;      // [C]
-  const int b = blockIdx.x;
-  // latency-bound (one block per image): keep several independent loads in flight instead of one dependent chain
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    const float* pp = partial + (size_t)b * parts_per_image * C + c;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int p = 0;
-    for (; p + 4 <= parts_per_image; p += 4) {
-      s0 += pp[(size_t)p * C]; s1 += pp[(size_t)(p + 1) * C]; s2 += pp[(size_t)(p + 2) * C]; s3 += pp[(size_t)(p + 3) * C];
+  float* S = sm;                 // [C]
+  float* Z = sm + C;             // [dmid]
+  float* A = Z + dmid;           // [C]
+  float* Q = A + C;              // [4][C] the four chains
+  float* W1 = Q + 4 * C;         // [dmid][C] | [C][dmid] | fc1_b [dmid] | fc2_b [C], one flat index space
+  const int nw = dmid * C;
+  float* W2 = W1 + nw;
+  float* B1 = W2 + nw;
+  float* B2 = B1 + dmid;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (tid < SKG_T / 2) {
+    const int p4 = parts_per_image & ~3;
+    for (int i = tid; i < 4 * C; i += SKG_T / 2) {
+      const int q = i / C, c = i - q * C;
+      const float* pp = partial + (size_t)b * parts_per_image * C + c;
+      float s = 0.f;
+#pragma unroll 8
+      for (int p = q; p < p4; p += 4) s += pp[(size_t)p * C];
+      if (q == 0)
+        for (int p = p4; p < parts_per_image; ++p) s += pp[(size_t)p * C];
+      Q[i] = s;
     }
-    for (; p < parts_per_image; ++p) s0 += pp[(size_t)p * C];
-    S[c] = ((s0 + s1) + (s2 + s3)) / (float)L;
+  } else {
+    const int n = 2 * nw + dmid + C, t = tid - SKG_T / 2;
+    for (int i0 = t; i0 < n; i0 += SKG_STAGE * (SKG_T / 2)) {
+      float v[SKG_STAGE];
+#pragma unroll
+      for (int u = 0; u < SKG_STAGE; ++u) {
+        int i = i0 + u * (SKG_T / 2);
+        i = i < n ? i : n - 1;
+        const float* src = i < nw ? fc1_w + i : (i < 2 * nw ? fc2_w + (i - nw) : (i < 2 * nw + dmid ? fc1_b + (i - 2 * nw) : fc2_b + (i - 2 * nw - dmid)));
+        v[u] = *src;
+      }
+#pragma unroll
+      for (int u = 0; u < SKG_STAGE; ++u) {
+        const int i = i0 + u * (SKG_T / 2);
+        if (i < n) W1[i] = v[u];
+      }
+    }
   }
+  __syncthreads();
+  for (int c = tid; c < C; c += SKG_T) S[c] = ((Q[c] + Q[C + c]) + (Q[2 * C + c] + Q[3 * C + c])) / (float)L;
   __syncthreads();
   // fc1: 8 lanes per output, each sums an eighth of the C products, then a 3-step shuffle reduction
-  for (int j0 = 0; j0 < dmid; j0 += blockDim.x / 8) {
-    const int j = j0 + threadIdx.x / 8, part = threadIdx.x & 7;
+  for (int j0 = 0; j0 < dmid; j0 += SKG_T / 8) {
+    const int j = j0 + tid / 8, part = tid & 7;
     float a = 0.f;
     if (j < dmid)
-      for (int c = part; c < C; c += 8) a += fc1_w[j * C + c] * S[c];
+      for (int c = part; c < C; c += 8) a += W1[j * C + c] * S[c];
     a += xshfl<1>(a); a += xshfl<2>(a); a += xshfl<4>(a);
-    if (j < dmid && part == 0) Z[j] = gelu_erf(a + fc1_b[j]);
+    if (j < dmid && part == 0) Z[j] = gelu_erf(a + B1[j]);
   }
   __syncthreads();
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    float a = fc2_b[c];
+  for (int c = tid; c < C; c += SKG_T) {
+    float a = B2[c];
 #pragma unroll 8
-    for (int j = 0; j < dmid; ++j) a += fc2_w[c * dmid + j] * Z[j];
+    for (int j = 0; j < dmid; ++j) a += W2[c * dmid + j] * Z[j];
     A[c] = a;
   }
   __syncthreads();
   const int cg = C / G;
-  for (int c = threadIdx.x; c < cg; c += blockDim.x) {
+  for (int c = tid; c < cg; c += SKG_T) {
     float mx = -INFINITY;
     for (int g = 0; g < G; ++g) mx = fmaxf(mx, A[g * cg + c]);
     float den = 0.f;
@@ -642,16 +693,14 @@ __global__ void k_sk_gate(const float* __restrict__ partial, int parts_per_image
 // apply_gelu: 0 = g holds the conv output, 1 = g holds GELU(conv), 2 = g holds the conv output AND g2 holds GELU(conv) (the
 // training forward keeps the pre-activation for the backward: one pass instead of conv + a separate activation kernel);
 // in_gelu: the input is a pre-activation, GELU is applied on the way into the LDS tile (fc1's GELU, pgrm.py:33)
-// R32: 32 x 32 planes (the Mlp of the 16 x 64 -> 32 x 128 stacks) -- exactly four float4 per lane: all four loads are issued before the
-// first GELU, no tail predicate
-// generic path (!R32): a wave takes a BAND of rb rows of a plane (rb = r: the whole plane) with one halo row above and below,
+// 32 x 32 planes (the Mlp of the 16 x 64 -> 32 x 128 stacks) take k_dwconv_gelu_r32 below; this is the kernel of every other size:
+// a wave takes a BAND of rb rows of a plane (rb = r: the whole plane) with one halo row above and below,
 // re-read (and re-activated) from the neighbouring bands -- 64 x 64 planes (the stress stack) as whole-plane tiles need 19 KB of LDS per
 // wave, 8 waves per CU, and ran at 0.34 of the HBM rate; 16-row bands need 5 KB
-template <bool R32>
 __global__ __launch_bounds__(256) void k_dwconv_gelu(const float* __restrict__ y, const float* __restrict__ w,
                                                       const float* __restrict__ bias, float* __restrict__ g, int Ch, int r,
-                                                      long planes, int apply_gelu, float* __restrict__ g2 = nullptr, int in_gelu = 0,
-                                                      float p_drop = 0.f, unsigned long long seed = 0ull, int rb = 0) {
+                                                      long planes, int apply_gelu, float* __restrict__ g2, int in_gelu,
+                                                      float p_drop, unsigned long long seed, int rb) {
   // p_drop > 0 (with in_gelu): nn.Dropout between fc1's GELU and the conv (pgrm.py:34) -- the mask is a pure function of
   // (seed, element index), so it is applied on load instead of through a materialised activated tensor
   const float inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
@@ -659,33 +708,28 @@ __global__ __launch_bounds__(256) void k_dwconv_gelu(const float* __restrict__ y
   // 16-byte aligned for float4 traffic (global loads / stores and the centre taps); r % 4 == 0
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (R32 || rb <= 0) rb = r;
+  if (rb <= 0) rb = r;
   const int nb = r / rb;
   const long vplane = (long)blockIdx.x * 4 + wave;
-  const long plane = R32 ? vplane : vplane / nb;
-  const int y0 = R32 ? 0 : (int)(vplane % nb) * rb;
+  const long plane = vplane / nb;
+  const int y0 = (int)(vplane % nb) * rb;
   const bool valid = plane < planes;
   const int c = valid ? (int)(plane % Ch) : 0;
   const int LD = r + 8, r4 = r >> 2;
   float* t = sm + wave * (rb + 2) * LD;
   if (valid) {
     const float* src = y + plane * r * r;
-    float4 pre[R32 ? 4 : 1];
-    if (R32) {
-#pragma unroll
-      for (int it = 0; it < 4; ++it) pre[it] = *reinterpret_cast<const float4*>(src + 4 * (lane + 64 * it));
-    }
-    // R32: tile rows 1 .. r hold the plane, rows 0 and r + 1 the zero halo; bands: tile row j holds plane row y0 - 1 + j
-    const int nld = R32 ? 256 : (rb + 2) * r4;
+    // tile row j holds plane row y0 - 1 + j
+    const int nld = (rb + 2) * r4;
 #pragma unroll 4
-    for (int it = 0; it < (R32 ? 4 : (nld + 63) / 64); ++it) {
+    for (int it = 0; it < (nld + 63) / 64; ++it) {
       const int i = lane + 64 * it;
-      if (!R32 && i >= nld) break;
+      if (i >= nld) break;
       const int j = i / r4, x4 = (i - j * r4) * 4;
-      const int yy = R32 ? j : y0 - 1 + j;
+      const int yy = y0 - 1 + j;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (R32 || (yy >= 0 && yy < r)) {
-        v = R32 ? pre[R32 ? it : 0] : *reinterpret_cast<const float4*>(src + yy * r + x4);
+      if (yy >= 0 && yy < r) {
+        v = *reinterpret_cast<const float4*>(src + yy * r + x4);
         if (in_gelu) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
         if (p_drop > 0.f) {
           const unsigned long long e0 = (unsigned long long)(plane * r * r + yy * r + x4);
@@ -694,10 +738,8 @@ __global__ __launch_bounds__(256) void k_dwconv_gelu(const float* __restrict__ y
           v.z *= drop_scale_z(z0 + 2 * DROP_PHI, p_drop, inv_keep); v.w *= drop_scale_z(z0 + 3 * DROP_PHI, p_drop, inv_keep);
         }
       }
-      *reinterpret_cast<float4*>(t + (R32 ? j + 1 : j) * LD + 4 + x4) = v;
+      *reinterpret_cast<float4*>(t + j * LD + 4 + x4) = v;
     }
-    if (R32)
-      for (int i = lane; i < LD; i += 64) { t[i] = 0.f; t[(r + 1) * LD + i] = 0.f; }       // top / bottom halo rows
     for (int i = lane; i < rb + 2; i += 64) { t[i * LD + 3] = 0.f; t[i * LD + 4 + r] = 0.f; }   // left / right halo columns
   }
   // the tile is private to the wave (LDS operations of one wave execute in order): no block barrier
@@ -733,6 +775,99 @@ __global__ __launch_bounds__(256) void k_dwconv_gelu(const float* __restrict__ y
     }
     *reinterpret_cast<float4*>(dst + yy * r + x4) = make_float4(a[0], a[1], a[2], a[3]);
   }
+}
+
+// 32 x 32 planes, streaming form: a wave walks planes wave, wave + nw, wave + 2 nw, ... (nw = waves of the grid; the launcher sizes the grid
+// so that every wave gets the same count) with the NEXT plane's four float4 in registers while it commits, convolves and stores
+// this one.  The prefetch is issued before the stores of the current plane and consumed after them: vmcnt retires in order, so the
+// wait in front of the next commit leaves the stores outstanding.  Straight-line body (MODE is a template parameter, the prefetch
+// of the last plane is peeled off, not predicated), weights by scalar loads (the plane index is wave-uniform): no join after a
+// branch with a memory operation, hence no vmcnt(0) drain ("What hipcc's waitcnt insertion needs").
+// Per element the operations and their order are those of k_dwconv_gelu: same bits.  MODE = apply_gelu of that kernel.
+template <int MODE, bool MORE>
+__device__ __forceinline__ void dwconv32_plane(float* __restrict__ t, float4 (&pre)[4], const float* __restrict__ y, const float* __restrict__ w,
+                                               const float* __restrict__ bias, float* __restrict__ g, float* __restrict__ g2, int Ch,
+                                               int plane, int next, int lane, int in_gelu, float p_drop, float inv_keep,
+                                               unsigned long long seed) {
+  constexpr int LD = 40;
+  const int c = plane % Ch;
+  float k[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) k[i] = w[c * 9 + i];
+  const float bv = bias[c];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int i = lane + 64 * it;
+    const int j = i >> 3, x4 = (i & 7) * 4;
+    float4 v = pre[it];
+    if (in_gelu) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
+    if (p_drop > 0.f) {
+      const unsigned long long z0 = drop_z0(seed, (unsigned long long)plane * 1024 + 4 * i);
+      v.x *= drop_scale_z(z0, p_drop, inv_keep); v.y *= drop_scale_z(z0 + DROP_PHI, p_drop, inv_keep);
+      v.z *= drop_scale_z(z0 + 2 * DROP_PHI, p_drop, inv_keep); v.w *= drop_scale_z(z0 + 3 * DROP_PHI, p_drop, inv_keep);
+    }
+    *reinterpret_cast<float4*>(t + (j + 1) * LD + 4 + x4) = v;
+  }
+  if (MORE) {
+    const float* src = y + (size_t)next * 1024;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) pre[it] = *reinterpret_cast<const float4*>(src + 4 * (lane + 64 * it));
+  }
+  // the tile is private to the wave (LDS operations of one wave execute in order): no block barrier
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  float* dst = g + (size_t)plane * 1024;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int i = lane + 64 * it;
+    const int yy = i >> 3, x4 = (i & 7) * 4;
+    float a[4] = {bv, bv, bv, bv};
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const float* p = t + (yy + ky) * LD + 4 + x4;
+      const float4 m = *reinterpret_cast<const float4*>(p);
+      const float l = p[-1], rr = p[4];
+      const float k0 = k[ky * 3], k1 = k[ky * 3 + 1], k2 = k[ky * 3 + 2];
+      a[0] += k0 * l + k1 * m.x + k2 * m.y;
+      a[1] += k0 * m.x + k1 * m.y + k2 * m.z;
+      a[2] += k0 * m.y + k1 * m.z + k2 * m.w;
+      a[3] += k0 * m.z + k1 * m.w + k2 * rr;
+    }
+    if (MODE == 2) {
+      *reinterpret_cast<float4*>(dst + 4 * i) = make_float4(a[0], a[1], a[2], a[3]);
+      *reinterpret_cast<float4*>(g2 + (size_t)plane * 1024 + 4 * i) = make_float4(gelu_erf(a[0]), gelu_erf(a[1]), gelu_erf(a[2]), gelu_erf(a[3]));
+    } else {
+      if (MODE == 1) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] = gelu_erf(a[q]);
+      }
+      *reinterpret_cast<float4*>(dst + 4 * i) = make_float4(a[0], a[1], a[2], a[3]);
+    }
+  }
+  // the next commit overwrites the tile these reads came from (same wave, in order)
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_dwconv_gelu_r32(const float* __restrict__ y, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, float* __restrict__ g, float* __restrict__ g2,
+                                                          int Ch, int planes, int in_gelu, float p_drop, unsigned long long seed) {
+  constexpr int LD = 40;
+  __shared__ __attribute__((aligned(16))) float sm[4 * 34 * LD];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const float inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
+  const int nw = (int)gridDim.x * 4;
+  int plane = (int)blockIdx.x * 4 + wave;
+  if (plane >= planes) return;                   // wave-uniform; the kernel has no block barrier
+  float* t = sm + wave * 34 * LD;
+  // zero halo, written once: rows 0 and 33, columns 3 and 36 (the commits only touch rows 1 .. 32, columns 4 .. 35)
+  for (int i = lane; i < LD; i += 64) { t[i] = 0.f; t[33 * LD + i] = 0.f; }
+  if (lane < 34) { t[lane * LD + 3] = 0.f; t[lane * LD + 36] = 0.f; }
+  float4 pre[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) pre[it] = *reinterpret_cast<const float4*>(y + (size_t)plane * 1024 + 4 * (lane + 64 * it));
+  for (int next = plane + nw; next < planes; plane = next, next += nw)
+    dwconv32_plane<MODE, true>(t, pre, y, w, bias, g, g2, Ch, plane, next, lane, in_gelu, p_drop, inv_keep, seed);
+  dwconv32_plane<MODE, false>(t, pre, y, w, bias, g, g2, Ch, plane, plane, lane, in_gelu, p_drop, inv_keep, seed);
 }
 
 // ---------------------------------------------------------------------------------- tail
@@ -906,8 +1041,56 @@ int dpmn_sk_gate_f32(const float* colsum_partials, int parts_per_image, int L, c
   DPMN_REQUIRE(colsum_partials && fc1_w && fc1_b && fc2_w && fc2_b && attn_vec, "sk_gate: null pointer");
   // quirk Q3: at B = 1 the reference's feats_S.squeeze() also drops the batch axis, but the later .view(bs, M, channel, 1, 1)
   // restores it -- same arithmetic as B >= 2 (pinned by the B = 1 stress golden), so no restriction here
-  hipLaunchKernelGGL(k_sk_gate, dim3(B), dim3(128), (size_t)(2 * C + dmid) * 4, as_stream(stream), colsum_partials,
+  DPMN_REQUIRE(B >= 1 && parts_per_image >= 1 && L >= 1 && C >= 1 && dmid >= 1 && groups >= 1 && C % groups == 0, "sk_gate: bad shape");
+  // S, Z, A, four chains, both weight matrices and biases: the kernel reads fc1 / fc2 from LDS only, so 2 C dmid floats must fit (C = 96 /
+  // 192 with dmid = C / 6: 15 / 55 KB).  A gate too large for that (C = 768 at dmid = C / 6 would be) is an error, not a slower path: no model of
+  // the project has one, and the kernel before this one, which read the weights from global memory, accepted it.
+  const size_t smem = ((size_t)7 * C + 2 * dmid + (size_t)2 * dmid * C) * 4;
+  DPMN_REQUIRE(smem <= 160 * 1024, "sk_gate: fc1 / fc2 do not fit in LDS");
+  if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_gate), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  hipLaunchKernelGGL(k_sk_gate, dim3(B), dim3(SKG_T), smem, as_stream(stream), colsum_partials,
                      parts_per_image, L, fc1_w, fc1_b, fc2_w, fc2_b, attn_vec, C, groups, dmid);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+// One launch path for the four entry points.  apply_gelu / in_gelu as in k_dwconv_gelu.  32 x 32 planes take the streaming kernel on a
+// grid of at most 7 blocks per CU (21.8 KB of LDS each) in which every wave walks the same number of planes (the last ones one
+// less when the count does not divide); every other plane size takes k_dwconv_gelu on whole planes or 16-row bands.
+static unsigned dwconv32_grid(long planes) {
+  static std::atomic<int> cus[64];                 // CU count per device ordinal, read once each (relaxed: every writer stores the same value)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  int n_cu = cus[dev].load(std::memory_order_relaxed);
+  if (n_cu < 1) {
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
+    cus[dev].store(n_cu, std::memory_order_relaxed);
+  }
+  const long cap = 7L * n_cu * 4;                  // resident waves (3, 4 and 6 blocks per CU measured slower or equal)
+  const long per = (planes + cap - 1) / cap;       // planes per wave
+  const long waves = (planes + per - 1) / per;
+  return (unsigned)((waves + 3) / 4);
+}
+
+static int launch_dwconv(const float* y, const float* w, const float* bias, float* g, float* g2, int apply_gelu, int in_gelu, float p_drop,
+                         unsigned long long seed, int B, int Ch, int r, hipStream_t st) {
+  const long planes = (long)B * Ch;
+  DPMN_REQUIRE(planes >= 1 && planes <= (1L << 30), "dwconv: B * Ch out of range");
+  if (r == 32) {
+    const dim3 grid(dwconv32_grid(planes));
+#define DW32(MODE) hipLaunchKernelGGL(k_dwconv_gelu_r32<MODE>, grid, dim3(256), 0, st, y, w, bias, g, g2, Ch, (int)planes, in_gelu, p_drop, seed)
+    if (apply_gelu == 2) DW32(2);
+    else if (apply_gelu == 1) DW32(1);
+    else DW32(0);
+#undef DW32
+  } else {
+    const int rb = dwconv_band_rows(r);
+    const long vplanes = planes * (r / rb);
+    const size_t smem = (size_t)4 * (rb + 2) * (r + 8) * 4;
+    if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwconv_gelu), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL(k_dwconv_gelu, dim3((unsigned)((vplanes + 3) / 4)), dim3(256), smem, st, y, w, bias, g, Ch, r, planes, apply_gelu, g2,
+                       in_gelu, p_drop, seed, rb);
+  }
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }
@@ -915,65 +1098,27 @@ int dpmn_sk_gate_f32(const float* colsum_partials, int parts_per_image, int L, c
 int dpmn_dwconv3x3_gelu_f32(const float* y, const float* w, const float* bias, float* g, int B, int Ch, int r,
                             dpmn_stream_t stream) {
   DPMN_REQUIRE(y && w && bias && g && r >= 4 && r <= 64 && r % 4 == 0, "dwconv: plane side must be a multiple of 4 in [4, 64]");
-  const long planes = (long)B * Ch;
-  const int rb = dwconv_band_rows(r);
-  const long vplanes = planes * (r / rb);
-  const size_t smem = (size_t)4 * (rb + 2) * (r + 8) * 4;
-  if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwconv_gelu<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  ProfScope prof(PT_DWCONV_GELU, as_stream(stream), 18.0 * planes * r * r, 8.0 * planes * r * r);
-  if (r == 32) hipLaunchKernelGGL(k_dwconv_gelu<true>, dim3((unsigned)((planes + 3) / 4)), dim3(256), smem, as_stream(stream), y, w, bias, g, Ch, r, planes, 1);
-  else hipLaunchKernelGGL(k_dwconv_gelu<false>, dim3((unsigned)((vplanes + 3) / 4)), dim3(256), smem, as_stream(stream), y, w, bias, g, Ch, r, planes, 1,
-                     static_cast<float*>(nullptr), 0, 0.f, 0ull, rb);
-  DPMN_CHECK_LAUNCH();
-  return DPMN_OK;
+  ProfScope prof(PT_DWCONV_GELU, as_stream(stream), 18.0 * B * Ch * r * r, 8.0 * B * Ch * r * r);
+  return launch_dwconv(y, w, bias, g, nullptr, 1, 0, 0.f, 0ull, B, Ch, r, as_stream(stream));
 }
 
 // y holds fc1's PRE-activation: its GELU (pgrm.py:33) is applied on the way into the LDS tile -- once per element, in a kernel that
 // waits on HBM anyway -- instead of in the epilogue of the MFMA-bound fc1 GEMM
 int dpmn_dwconv3x3_gelu_in_f32(const float* y, const float* w, const float* bias, float* g, int B, int Ch, int r, dpmn_stream_t stream) {
   DPMN_REQUIRE(y && w && bias && g && r >= 4 && r <= 64 && r % 4 == 0, "dwconv: plane side must be a multiple of 4 in [4, 64]");
-  const long planes = (long)B * Ch;
-  const int rb = dwconv_band_rows(r);
-  const long vplanes = planes * (r / rb);
-  const size_t smem = (size_t)4 * (rb + 2) * (r + 8) * 4;
-  if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwconv_gelu<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  ProfScope prof(PT_DWCONV_GELU, as_stream(stream), 18.0 * planes * r * r, 8.0 * planes * r * r);
-  if (r == 32) hipLaunchKernelGGL(k_dwconv_gelu<true>, dim3((unsigned)((planes + 3) / 4)), dim3(256), smem, as_stream(stream), y, w, bias, g, Ch, r, planes, 1,
-                     static_cast<float*>(nullptr), 1, 0.f, 0ull);
-  else hipLaunchKernelGGL(k_dwconv_gelu<false>, dim3((unsigned)((vplanes + 3) / 4)), dim3(256), smem, as_stream(stream), y, w, bias, g, Ch, r, planes, 1,
-                     static_cast<float*>(nullptr), 1, 0.f, 0ull, rb);
-  DPMN_CHECK_LAUNCH();
-  return DPMN_OK;
+  ProfScope prof(PT_DWCONV_GELU, as_stream(stream), 18.0 * B * Ch * r * r, 8.0 * B * Ch * r * r);
+  return launch_dwconv(y, w, bias, g, nullptr, 1, 1, 0.f, 0ull, B, Ch, r, as_stream(stream));
 }
 
 int dpmn_dwconv3x3_f32(const float* y, const float* w, const float* bias, float* g, int B, int Ch, int r, dpmn_stream_t stream) {
   DPMN_REQUIRE(y && w && bias && g && r >= 4 && r <= 64 && r % 4 == 0, "dwconv: plane side must be a multiple of 4 in [4, 64]");
-  const long planes = (long)B * Ch;
-  const int rb = dwconv_band_rows(r);
-  const long vplanes = planes * (r / rb);
-  const size_t smem = (size_t)4 * (rb + 2) * (r + 8) * 4;
-  if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwconv_gelu<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (r == 32) hipLaunchKernelGGL(k_dwconv_gelu<true>, dim3((unsigned)((planes + 3) / 4)), dim3(256), smem, as_stream(stream), y, w, bias, g, Ch, r, planes, 0);
-  else hipLaunchKernelGGL(k_dwconv_gelu<false>, dim3((unsigned)((vplanes + 3) / 4)), dim3(256), smem, as_stream(stream), y, w, bias, g, Ch, r, planes, 0,
-                     static_cast<float*>(nullptr), 0, 0.f, 0ull, rb);
-  DPMN_CHECK_LAUNCH();
-  return DPMN_OK;
+  return launch_dwconv(y, w, bias, g, nullptr, 0, 0, 0.f, 0ull, B, Ch, r, as_stream(stream));
 }
 
 int dpmn_dwconv3x3_train_f32(const float* y, const float* w, const float* bias, float* gpre, float* g, int in_gelu, float p_drop,
                              unsigned long long seed, int B, int Ch, int r, dpmn_stream_t stream) {
   DPMN_REQUIRE(y && w && bias && gpre && g && r >= 4 && r <= 64 && r % 4 == 0, "dwconv_train: plane side must be a multiple of 4 in [4, 64]");
-  const long planes = (long)B * Ch;
-  const int rb = dwconv_band_rows(r);
-  const long vplanes = planes * (r / rb);
-  const size_t smem = (size_t)4 * (rb + 2) * (r + 8) * 4;
-  if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwconv_gelu<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (r == 32) hipLaunchKernelGGL(k_dwconv_gelu<true>, dim3((unsigned)((planes + 3) / 4)), dim3(256), smem, as_stream(stream), y, w, bias, gpre, Ch, r, planes, 2, g,
-                     in_gelu, p_drop, seed);
-  else hipLaunchKernelGGL(k_dwconv_gelu<false>, dim3((unsigned)((vplanes + 3) / 4)), dim3(256), smem, as_stream(stream), y, w, bias, gpre, Ch, r, planes, 2, g,
-                     in_gelu, p_drop, seed, rb);
-  DPMN_CHECK_LAUNCH();
-  return DPMN_OK;
+  return launch_dwconv(y, w, bias, gpre, g, 2, in_gelu, p_drop, seed, B, Ch, r, as_stream(stream));
 }
 
 int dpmn_pgrm_tail_f32(const float* tokens, const float* w0, const float* b0, const float* w1, const float* b1,
