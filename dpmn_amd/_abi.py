@@ -296,7 +296,6 @@ SIGNATURES = {
     "dpmn_resize_windows_u8": (_i, [fp, _l, fp, _i, fp, _l, fp, _i, _l, _i, fp, _i, _i, fp, _sz, fp]),
     "dpmn_stitch_windows_u8": (_i, [fp, _l, _l, _i, _i, _i, _i, fp, _i, fp, _i, fp, _l, fp]),
     "dpmn_quad_crop_u8": (_i, [fp, _l, fp, fp, _i, fp, _i, fp, _l, fp]),
-    "dpmn_paste_regions_u8": (_i, [fp, _i, _i, fp, _l, fp, fp, _i, fp, _i, fp, _i, fp]),
     "dpmn_paste_mixed_u8": (_i, [fp, _i, _i, fp, _l, fp, fp, _i, fp, _i, fp, _i, fp, _i, fp]),
     "dpmn_poly_crop_u8": (_i, [fp, _l, fp, fp, _i, fp, fp, _i, fp, _i, fp, _l, fp]),
     "dpmn_profile_tag_count": (_i, []),

@@ -1,27 +1,77 @@
-// Quadrilaterals and polygons pasted back into their enlarged photo in ONE list (utils/paste_poly.py fixes the semantics; main.py
-// --demo_paste_polygons): paste.hip's launch with a second kind of region.  dpmn_paste_mixed_u8: one H2 x W2 x 3 uint8 photo, modified
-// IN PLACE, the SR images in resize.hip's packed layout, R regions and a strip table.  A perspective region is paste.hip's: 8
-// coefficients from the photo to its SR image.  A polygon region names a slice of the strip table; a strip is a four-cornered piece of
-// the photo, the SR columns it covers and its bounding box, and the pixel's source position is the INVERSE of the strip's bilinear map:
-//   k_paste_mixed     block = one 32 x 8 tile of the PHOTO that at least one region's box meets, one thread per pixel: it walks the
-//                     tile's regions in list order.  Perspective: paste.hip's arithmetic.  Polygon: it walks the region's strips,
-//                     skips a strip whose box does not hold the pixel (integers, before any float64 work), solves the strip's
-//                     quadratic for the rest and stops at the first strip with 0 <= u < 1, 0 <= v < 1.  Then for either kind the
-//                     inside test, feather mask, bicubic sample and blend of paste_common.h.  The three running bytes stay in
-//                     registers and are written once.
+// The super-resolved text regions pasted back into their enlarged photo, quadrilaterals and polygons in ONE list (utils/paste.py and
+// utils/paste_poly.py fix the semantics; main.py --demo_paste, --demo_paste_polygons): the inverse of quad.hip.  dpmn_paste_mixed_u8:
+// one H2 x W2 x 3 uint8 photo, modified IN PLACE, the SR images in resize.hip's packed layout, R regions and a strip table.  A
+// perspective region carries the 8 coefficients of PIL's perspective transform from the photo to its SR image: per region, in list
+// order, Image.paste(SR.transform((W2, H2), PERSPECTIVE, coeffs, BICUBIC), mask) with the mask of utils/paste.py.  A polygon region
+// names a slice of the strip table; a strip is a four-cornered piece of the photo, the SR columns it covers and its bounding box, and
+// the pixel's source position is the INVERSE of the strip's bilinear map:
+//   k_paste_mixed     block = one 32 x 8 tile of the PHOTO that at least one region's box meets (the tile table names it and its slice
+//                     of the flat region list), one thread per pixel: it walks the tile's regions in list order.  Perspective: the
+//                     pixel's centre through the transform.  Polygon: it walks the region's strips, skips a strip whose box does not
+//                     hold the pixel (integers, before any float64 work), solves the strip's quadratic for the rest and stops at the
+//                     first strip with 0 <= u < 1, 0 <= v < 1.  Then for either kind the inside test, feather mask, bicubic sample
+//                     (quad_sample.h) and PIL's integer blend.  The three running bytes stay in registers and are written once.
 // No byte of the photo has two owners, and a thread reads its pixel before it writes it: in place is safe and the result does not
-// depend on the schedule.  float64 throughout, in the operation order of the restatement: plain * + - /, and sqrt (the library is built
+// depend on the schedule.  float64 throughout, in the operation order of the restatements: plain * + - /, and sqrt (the library is built
 // with -ffp-contract=off and without fast-math: the double division and square root are the device library's correctly rounded ones).
-#include "paste_common.h"
+// The work is proportional to the area the boxes cover, not to the photo's; the taps come through L1 / L2 as in quad.hip.
+#include "quad_sample.h"
 
 namespace {
+
+constexpr int PASTE_TILE_WORDS = 4;
+constexpr int PASTE_TILE_W = 32, PASTE_TILE_H = 8;
+
+// The first three words of a region record: [byte offset of the SR image, h_s, w_s].  The numbers are data from the caller: a region
+// whose SR image does not fit the packed buffer, or has a side outside 1 .. 8192, is not read.  The host entry point applies the same
+// test to its copy of the table and refuses the call.
+__host__ __device__ inline bool paste_region_ok(const long long* p, long sr_bytes) {
+  const long long off = p[0], h = p[1], w = p[2];
+  return h >= 1 && h <= RESIZE_MAX_SIDE && w >= 1 && w <= RESIZE_MAX_SIDE && off >= 0 && off <= sr_bytes - h * w * 3;
+}
+
+// A tile record [tile row, tile column, first, count] -> whether it lies in the photo and its slice in the region list (the tile is
+// data from the caller: one outside the photo, or whose slice leaves the list, writes nothing)
+__device__ __forceinline__ bool paste_tile_ok(const int* t, int H2, int W2, int n_list) {
+  const int tile_row = t[0], tile_col = t[1], first = t[2], count = t[3];
+  if (tile_row < 0 || tile_col < 0 || tile_row > (H2 - 1) / PASTE_TILE_H || tile_col > (W2 - 1) / PASTE_TILE_W) return false;
+  return first >= 0 && count >= 0 && first <= n_list - count;
+}
+
+// Image.paste with an L mask on uint8 (libImaging/Paste.c BLEND8 of this Pillow): dst, src, m in 0 .. 255
+__device__ __forceinline__ int blend8(int dst, int src, int m) {
+  const int t = dst * (255 - m) + src * m + 128;
+  return ((t >> 8) + t) >> 8;
+}
+
+// One region at one pixel, the source position (sx, sy) given: nothing where it lies outside the h_s x w_s SR image (a NaN compares
+// false: outside; nothing becomes an integer before this test), else the feather mask, the bicubic sample and the blend into the three
+// running bytes.  Returns whether the pixel was touched.
+__device__ __forceinline__ bool paste_sample_blend(const unsigned char* __restrict__ sr_image, int h_s, int w_s, double sx, double sy,
+                                                   double feather, int& b0, int& b1, int& b2) {
+  if (!(sx >= 0.0 && sx < (double)w_s && sy >= 0.0 && sy < (double)h_s)) return false;
+  int m = 255;
+  if (feather > 0.0) {
+    // the distance of the source position to the nearest edge of the SR rectangle, in SR pixels: 0 <= d, so 0 <= m
+    const double d = fmin(fmin(sx, (double)w_s - sx), fmin(sy, (double)h_s - sy));
+    const double f = d / feather;
+    m = f >= 1.0 ? 255 : (int)floor(f * 255 + 0.5);
+    m = min(max(m, 0), 255);
+  }
+  unsigned char px[3];
+  bicubic_sample_u8(sr_image, h_s, w_s, sx, sy, px);
+  b0 = blend8(b0, px[0], m);
+  b1 = blend8(b1, px[1], m);
+  b2 = blend8(b2, px[2], m);
+  return true;
+}
 
 constexpr int MIXED_REGION_WORDS = 13;      // include/dpmn_hip.h dpmn_paste_mixed_u8: 13 int64 per region
 constexpr int MIXED_STRIP_WORDS = 14;       //                                          14 int64 per strip
 constexpr int MIXED_MAX_STRIPS = 31;        // utils.poly.MAX_POLY_SIDE - 1
 constexpr long long KIND_PERSPECTIVE = 0, KIND_POLYGON = 1;
 
-// One region as the kernel sees it: paste_common.h's test of its SR image, a known kind, and for a polygon a slice of 1 .. 31 strips
+// One region as the kernel sees it: paste_region_ok's test of its SR image, a known kind, and for a polygon a slice of 1 .. 31 strips
 // inside the strip table.  The host entry point applies the same test to its copy of the table and refuses the call.
 __host__ __device__ inline bool mixed_region_ok(const long long* p, long sr_bytes, int n_strips) {
   if (!paste_region_ok(p, sr_bytes)) return false;

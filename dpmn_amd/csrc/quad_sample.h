@@ -1,4 +1,4 @@
-// What the warping kernels share (quad.hip, poly.hip, and paste.hip / paste_poly.hip through paste_common.h): the 4 x 4 bicubic sample
+// What the warping kernels share (quad.hip, poly.hip and paste_poly.hip): the 4 x 4 bicubic sample
 // of PIL's Image.transform (libImaging/Geometry.c) on an RGB uint8 image, float64 in the operation order of utils/quad.py's restatement.
 #pragma once
 #include "u8_pixel.h"

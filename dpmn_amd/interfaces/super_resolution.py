@@ -334,7 +334,7 @@ class TextSR(base.TextBase):
         ends with the batch's uploaded photos and quadrilaterals.  Once a batch's regions are super-resolved, each of its photos is
         enlarged by the scale factor on the GPU (ops.resize_ragged_u8 at the photo's own target size: PIL's bytes), its SR regions --
         the very bytes of the <stem>_<k>_sr.png files, still on the device -- are pasted into their quadrilaterals in box-file order
-        (ops.paste_regions_u8, utils/paste.py; feather: the width of the blended edge in SR pixels, 0 for a hard edge), and the photo
+        (ops.paste_mixed_u8, utils/paste.py; feather: the width of the blended edge in SR pixels, 0 for a hard edge), and the photo
         is copied to the host once and written as <stem>_photo_sr.png.  A photo whose enlarged side would exceed
         utils.resize.MAX_SIDE gets one printed line and no photo output; its regions are written.  The rows and demo_result.csv do
         not change.
@@ -449,12 +449,11 @@ class TextSR(base.TextBase):
         """demo(paste=True): the photos of one batch with their SR regions pasted back -> [(stem, (scale * H, scale * W, 3) uint8
         array)] in batch order.  photos = (packed, meta, owners, quads) as dataset.folder.box_region_batches(photos=True) yields it;
         sr_packed / sr_meta hold the batch's SR regions on the device, one per name, in pack_ragged's layout.  Per photo: the enlargement
-        (ops.resize_ragged_u8 with a batch of one), ops.paste_regions_u8 with the photo's regions in box-file order, one copy to the
+        (ops.resize_ragged_u8 with a batch of one), ops.paste_mixed_u8 with the photo's regions in box-file order, one copy to the
         host.  A photo too large to enlarge, or a region utils.paste.paste_coeffs refuses, is passed over with one printed line.  The
         regions of polygons (more than 4 points: the batches were made with polygons=True) are not pasted -- one printed line per photo
         gives their count -- unless paste_polygons: a polygon then joins the photo's list with its strip table
-        (utils.paste_poly.strip_table; one it refuses gets a refused quadrilateral's printed line) and the list goes through
-        ops.paste_mixed_u8."""
+        (utils.paste_poly.strip_table; one it refuses gets a refused quadrilateral's printed line)."""
         import numpy as np
         from ..utils.paste import paste_coeffs
         from ..utils.paste_poly import strip_table
@@ -486,8 +485,7 @@ class TextSR(base.TextBase):
                 except ValueError as e:
                     print("demo: region %s is not pasted (%s)" % (names[r], e))
             photo2 = ops.resize_ragged_u8(packed, meta[b:b + 1], s * H, s * W)[0]
-            op = ops.paste_mixed_u8 if paste_polygons else ops.paste_regions_u8
-            out.append((stem, op(photo2, sr_packed, sr_meta, regions).cpu().numpy()))
+            out.append((stem, ops.paste_mixed_u8(photo2, sr_packed, sr_meta, regions).cpu().numpy()))
         return out
 
     def _demo_windows(self, model_list, model_psn, batches, fn, reader, chunk):

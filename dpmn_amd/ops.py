@@ -214,6 +214,42 @@ def _resize_tables(pairs, device):
     return {p: _RESIZE_TABLES[key] for p, key in keys.items()}
 
 
+def _pack(*arrays):
+    """Several contiguous int64 / int32 / float32 numpy arrays in ONE zeroed int64 buffer, each at the next 8-byte boundary ->
+    (buffer, the int64 word at which each array starts)."""
+    import numpy as np
+    if any(a.dtype not in (np.int64, np.int32, np.float32) or not a.flags.c_contiguous for a in arrays):
+        raise TypeError("_pack: contiguous int64, int32 or float32 arrays expected")
+    starts = np.cumsum([0] + [(a.nbytes + 7) // 8 for a in arrays])
+    buf = np.zeros(int(starts[-1]), np.int64)
+    for a, at in zip(arrays, starts):
+        buf[at:at + (a.nbytes + 7) // 8].view(a.dtype)[:a.size] = a.reshape(-1)
+    return buf, [int(at) for at in starts[:-1]]
+
+
+def _upload(dev, *arrays):
+    """The host arrays of one call in one upload (_pack's buffer) -> (the device tensor, then per array the device pointer of its start,
+    None for an empty one).  The tensor must outlive the launches that read it: the caller keeps it until they are queued."""
+    buf, starts = _pack(*arrays)
+    d = torch.from_numpy(buf).to(dev)
+    return (d,) + tuple(d.data_ptr() + 8 * at if a.size else None for a, at in zip(arrays, starts))
+
+
+def _tile_table(hs, ws, tile_h, tile_w):
+    """Every tile_h x tile_w tile of every h x w image, image after image in row-major tile order -> (tiles (n_tiles, 3) int32 [image,
+    tile row, tile column], first (len + 1) int64: the tiles of image i are first[i] .. first[i + 1])."""
+    import numpy as np
+    th, tw = -(-hs // tile_h), -(-ws // tile_w)
+    first = np.concatenate(([0], np.cumsum(th * tw))).astype(np.int64)
+    tiles = np.empty((int(first[-1]), 3), np.int32)
+    for i in range(len(hs)):
+        t = tiles[first[i]:first[i + 1]]
+        t[:, 0] = i
+        t[:, 1] = np.repeat(np.arange(th[i]), tw[i])
+        t[:, 2] = np.tile(np.arange(tw[i]), th[i])
+    return tiles, first
+
+
 def _ragged_batch(packed, meta, what):
     """The checks every op on a pack_ragged batch shares -> meta as an int64 (B, 3) numpy array of (byte offset, h, w).  packed: the device buffer, or its size in bytes where the op only writes (degrade_noise)."""
     import numpy as np
@@ -275,16 +311,9 @@ def _degrade_plan(packed, meta, what):
     import numpy as np
     m = _ragged_batch(packed, meta, what)
     hs, ws = m[:, 1], m[:, 2]
-    th, tw = -(-hs // DEGRADE_TILE), -(-ws // DEGRADE_TILE)
-    first = np.concatenate(([0], np.cumsum(th * tw)))
-    if first[-1] >= 2 ** 31:
+    if int((-(-hs // DEGRADE_TILE) * -(-ws // DEGRADE_TILE)).sum()) >= 2 ** 31:      # (before the table is allocated)
         raise _abi.DpmnError("%s: the batch has more than 2^31 - 1 tiles" % what)
-    tiles = np.empty((int(first[-1]), 3), np.int32)
-    for b in range(m.shape[0]):
-        t = tiles[first[b]:first[b + 1]]
-        t[:, 0] = b
-        t[:, 1] = np.repeat(np.arange(th[b]), tw[b])
-        t[:, 2] = np.tile(np.arange(tw[b]), th[b])
+    tiles, first = _tile_table(hs, ws, DEGRADE_TILE, DEGRADE_TILE)
     return m, np.concatenate((m, first[:-1, None]), axis=1), tiles
 
 
@@ -310,14 +339,10 @@ def degrade_ragged_u8(packed, meta, params, z=None, seed=0):
         raise _abi.DpmnError("degrade_ragged_u8: z must be a contiguous float32 tensor of packed.numel() values on the device of packed")
     # one upload: items, params and tiles in one int64 buffer (params / tiles reinterpreted on the device)
     n_tiles = tiles.shape[0]
-    host = np.zeros(B * 4 + B * 8 + (n_tiles * 3 + 1) // 2, np.int64)
-    host[:B * 4] = items.reshape(-1)
-    host[B * 4:B * 12].view(np.float32)[:] = p.reshape(-1)
-    host[B * 12:].view(np.int32)[:n_tiles * 3] = tiles.reshape(-1)
-    d = torch.from_numpy(host).to(dev)
+    d, d_items, d_params, d_tiles = _upload(dev, items, p, tiles)
     out = torch.zeros_like(packed)      # (bytes of the buffer that belong to no image stay 0)
     ws = torch.empty(lib.dpmn_degrade_ragged_workspace_bytes(n_tiles), dtype=torch.uint8, device=dev)
-    check(lib.dpmn_degrade_ragged_u8(packed.data_ptr(), packed.numel(), d.data_ptr(), d[B * 12:].data_ptr(), n_tiles, d[B * 4:].data_ptr(),
+    check(lib.dpmn_degrade_ragged_u8(packed.data_ptr(), packed.numel(), d_items, d_tiles, n_tiles, d_params,
                                      None if z is None else z.data_ptr(), int(seed) & (2 ** 64 - 1), B, out.data_ptr(), ws.data_ptr(),
                                      ws.numel(), stream()))
     return out
@@ -370,25 +395,11 @@ def render_words_u8(words_cls, lengths, params, atlases, device=None, out=None):
     nbytes = int(m[-1, 0] + m[-1, 1] * m[-1, 2] * 3)
     if B > 65535 or nbytes > 2 ** 31 - 1:
         raise _abi.DpmnError("render_words_u8: at most 65535 images and 2^31 - 1 bytes per batch")
-    th, tw = -(-m[:, 1] // RENDER_TILE[0]), -(-m[:, 2] // RENDER_TILE[1])
-    first = np.concatenate(([0], np.cumsum(th * tw)))
-    n_tiles = int(first[-1])
-    tiles = np.empty((n_tiles, 3), np.int32)
-    for b in range(B):
-        t = tiles[first[b]:first[b + 1]]
-        t[:, 0] = b
-        t[:, 1] = np.repeat(np.arange(th[b]), tw[b])
-        t[:, 2] = np.tile(np.arange(tw[b]), th[b])
-    # one upload: meta + first tile, params, classes, lengths and tiles in one int64 buffer (the int32 parts reinterpreted on the device)
-    o_par, o_cls = B * 4, B * 4 + B * rd.N_PARAMS
-    o_len = o_cls + (B * rd.MAX_LEN + 1) // 2
-    o_til = o_len + (B + 1) // 2
-    host = np.zeros(o_til + (n_tiles * 3 + 1) // 2, np.int64)
-    host[:o_par] = np.concatenate((m, first[:-1, None]), axis=1).reshape(-1)
-    host[o_par:o_cls] = p.reshape(-1)
-    host[o_cls:o_len].view(np.int32)[:B * rd.MAX_LEN] = cls.reshape(-1)
-    host[o_len:o_til].view(np.int32)[:B] = lens
-    host[o_til:].view(np.int32)[:n_tiles * 3] = tiles.reshape(-1)
+    tiles, first = _tile_table(m[:, 1], m[:, 2], *RENDER_TILE)
+    n_tiles = tiles.shape[0]
+    # one upload: meta + first tile, params, classes, lengths and tiles in one int64 buffer (the int32 parts reinterpreted on the
+    # device); the entry point also reads the host copy
+    host, (o_meta, o_par, o_cls, o_len, o_til) = _pack(np.concatenate((m, first[:-1, None]), axis=1), p, cls, lens, tiles)
     d = torch.from_numpy(host).to(dev)
     key = (dev.type, dev.index)
     if key not in atlases._device:
@@ -400,10 +411,11 @@ def render_words_u8(words_cls, lengths, params, atlases, device=None, out=None):
     elif (not torch.is_tensor(out) or out.device != dev or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous()
           or out.numel() < nbytes):
         raise _abi.DpmnError("render_words_u8: out must be a contiguous 1-D uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
-    hp = host.ctypes.data
-    check(lib.dpmn_render_words_u8(d[o_cls:].data_ptr(), d[o_len:].data_ptr(), d[o_par:].data_ptr(), alpha.data_ptr(), adv.data_ptr(),
-                                   hts.data_ptr(), d.data_ptr(), d[o_til:].data_ptr(), n_tiles, out.data_ptr(), out.numel(), B,
-                                   atlases.n_fonts, alpha.shape[3], alpha.shape[4], hp + 8 * o_cls, hp + 8 * o_len, hp + 8 * o_par, hp, stream()))
+    dp, hp = d.data_ptr(), host.ctypes.data
+    check(lib.dpmn_render_words_u8(dp + 8 * o_cls, dp + 8 * o_len, dp + 8 * o_par, alpha.data_ptr(), adv.data_ptr(),
+                                   hts.data_ptr(), dp + 8 * o_meta, dp + 8 * o_til, n_tiles, out.data_ptr(), out.numel(), B,
+                                   atlases.n_fonts, alpha.shape[3], alpha.shape[4], hp + 8 * o_cls, hp + 8 * o_len, hp + 8 * o_par,
+                                   hp + 8 * o_meta, stream()))
     return out, torch.from_numpy(m)
 
 
@@ -503,19 +515,13 @@ def _resize_windows_plan(packed, meta, lr_h, lr_w):
 
 def _resize_windows_run(packed, host):
     """One upload of the host arrays of _resize_windows_plan (items, windows and tables in one int64 buffer) and the three launches."""
-    import numpy as np
     items, windows, tables, (lr_h, lr_w) = host["items"], host["windows"], host["tables"], host["lr_size"]
     B, T, dev = items.shape[0], windows.shape[0], packed.device
-    n_win = (T * 2 + 1) // 2
-    buf = np.zeros(B * 10 + n_win + (tables.size + 1) // 2, np.int64)
-    buf[:B * 10] = items.reshape(-1)
-    buf[B * 10:B * 10 + n_win].view(np.int32)[:T * 2] = windows.reshape(-1)
-    buf[B * 10 + n_win:].view(np.int32)[:tables.size] = tables
-    d = torch.from_numpy(buf).to(dev)
+    d, d_items, d_windows, d_tables = _upload(dev, items, windows, tables)
     ws = torch.empty(lib.dpmn_resize_windows_workspace_bytes(host["sum_h_w_line"], host["sum_w_line"], lr_h), dtype=torch.uint8, device=dev)
     out = torch.empty(T, lr_h, lr_w, 3, dtype=torch.uint8, device=dev)
-    check(lib.dpmn_resize_windows_u8(packed.data_ptr(), packed.numel(), d.data_ptr(), B, d[B * 10 + n_win:].data_ptr(), tables.size,
-                                     d[B * 10:].data_ptr(), T, host["max_mid_bytes"], host["max_w_line"], out.data_ptr(), lr_h, lr_w,
+    check(lib.dpmn_resize_windows_u8(packed.data_ptr(), packed.numel(), d_items, B, d_tables, tables.size,
+                                     d_windows, T, host["max_mid_bytes"], host["max_w_line"], out.data_ptr(), lr_h, lr_w,
                                      ws.data_ptr(), ws.numel(), stream()))
     return out
 
@@ -557,13 +563,11 @@ def stitch_windows_u8(sr, plan, scale=2):
     meta[:, 1], meta[:, 2] = H, [scale * l[2] for l in lines]
     sizes = meta[:, 1] * meta[:, 2] * 3
     meta[:, 0] = np.concatenate(([0], np.cumsum(sizes[:-1])))
-    buf = np.zeros(B * 4 + T, np.int64)
-    buf[:B * 4].reshape(B, 4)[:] = [(off, l[2], l[0], l[1]) for off, l in zip(meta[:, 0], lines)]
-    buf[B * 4:].view(np.int32)[:] = np.asarray(plan, np.int32).reshape(-1)
-    d = torch.from_numpy(buf).to(sr.device)
+    d, d_lines, d_windows = _upload(sr.device, np.array([(off, l[2], l[0], l[1]) for off, l in zip(meta[:, 0], lines)], np.int64),
+                                    np.asarray(plan, np.int32).reshape(-1, 2))
     out = torch.zeros(int(sizes.sum()), dtype=torch.uint8, device=sr.device)
     x, px, bs, cs = _display_planes(sr, "sr")
-    check(lib.dpmn_stitch_windows_u8(px, bs, cs, T, H, sr_w, scale, d.data_ptr(), B, d[B * 4:].data_ptr(), max(l[2] for l in lines),
+    check(lib.dpmn_stitch_windows_u8(px, bs, cs, T, H, sr_w, scale, d_lines, B, d_windows, max(l[2] for l in lines),
                                      out.data_ptr(), out.numel(), stream()))
     return out, meta
 
@@ -574,16 +578,7 @@ QUAD_TILE = (8, 32)      # csrc/quad.hip QUAD_TILE_H, QUAD_TILE_W
 def _region_tiles(hs, ws):
     """The tile table of quad_crop_u8 and poly_crop_u8: int32 (n_tiles, 3) [region, tile row, tile column], every QUAD_TILE tile of every
     h x w region, region after region in row-major tile order."""
-    import numpy as np
-    th, tw = -(-hs // QUAD_TILE[0]), -(-ws // QUAD_TILE[1])
-    tfirst = np.concatenate(([0], np.cumsum(th * tw)))
-    tiles = np.empty((int(tfirst[-1]), 3), np.int32)
-    for r in range(len(hs)):
-        t = tiles[tfirst[r]:tfirst[r + 1]]
-        t[:, 0] = r
-        t[:, 1] = np.repeat(np.arange(th[r]), tw[r])
-        t[:, 2] = np.tile(np.arange(tw[r]), th[r])
-    return tiles
+    return _tile_table(hs, ws, *QUAD_TILE)[0]
 
 
 def _quad_crop_plan(packed, meta, regions):
@@ -627,11 +622,8 @@ def _quad_crop_run(packed, host, out=None):
         out = torch.zeros(host["out_bytes"], dtype=torch.uint8, device=dev)
     if R == 0:
         return out, lib.dpmn_quad_crop_u8(packed.data_ptr(), packed.numel(), None, None, 0, None, 0, None, 0, stream())
-    buf = np.zeros(R * 14 + (n_tiles * 3 + 1) // 2, np.int64)
-    buf[:R * 14] = table.reshape(-1)
-    buf[R * 14:].view(np.int32)[:n_tiles * 3] = tiles.reshape(-1)
-    d = torch.from_numpy(buf).to(dev)
-    return out, lib.dpmn_quad_crop_u8(packed.data_ptr(), packed.numel(), d.data_ptr(), table.ctypes.data, R, d[R * 14:].data_ptr(), n_tiles,
+    d, d_table, d_tiles = _upload(dev, table, tiles)
+    return out, lib.dpmn_quad_crop_u8(packed.data_ptr(), packed.numel(), d_table, table.ctypes.data, R, d_tiles, n_tiles,
                                       out.data_ptr(), out.numel(), stream())
 
 
@@ -696,13 +688,9 @@ def _poly_crop_run(packed, host, out=None):
         out = torch.zeros(host["out_bytes"], dtype=torch.uint8, device=dev)
     if R == 0:
         return out, lib.dpmn_poly_crop_u8(packed.data_ptr(), packed.numel(), None, None, 0, None, None, 0, None, 0, None, 0, stream())
-    buf = np.zeros(R * 8 + C * 10 + (n_tiles * 3 + 1) // 2, np.int64)
-    buf[:R * 8] = table.reshape(-1)
-    buf[R * 8:R * 8 + C * 10] = cells.reshape(-1)
-    buf[R * 8 + C * 10:].view(np.int32)[:n_tiles * 3] = tiles.reshape(-1)
-    d = torch.from_numpy(buf).to(dev)
-    return out, lib.dpmn_poly_crop_u8(packed.data_ptr(), packed.numel(), d.data_ptr(), table.ctypes.data, R, d[R * 8:].data_ptr(),
-                                      cells.ctypes.data, C, d[R * 8 + C * 10:].data_ptr(), n_tiles, out.data_ptr(), out.numel(), stream())
+    d, d_table, d_cells, d_tiles = _upload(dev, table, cells, tiles)
+    return out, lib.dpmn_poly_crop_u8(packed.data_ptr(), packed.numel(), d_table, table.ctypes.data, R, d_cells,
+                                      cells.ctypes.data, C, d_tiles, n_tiles, out.data_ptr(), out.numel(), stream())
 
 
 def poly_crop_u8(packed, meta, regions):
@@ -755,7 +743,7 @@ def crop_regions_u8(packed, meta, regions):
     return out, out_meta
 
 
-PASTE_TILE = (8, 32)      # csrc/paste.hip PASTE_TILE_H, PASTE_TILE_W
+PASTE_TILE = (8, 32)      # csrc/paste_poly.hip PASTE_TILE_H, PASTE_TILE_W
 PASTE_MAX_TILES = 2 ** 31 - 1      # one block per tile in the grid's x dimension
 
 
@@ -807,82 +795,20 @@ def _paste_tiles(ids, W2, what):
     return np.stack([uniq // ntx, uniq % ntx, first, count], axis=1).astype(np.int32), np.ascontiguousarray(owners[order])
 
 
-def _paste_regions_plan(photo2, sr_packed, sr_meta, regions):
-    """Checks and per-call host data of paste_regions_u8 -> host: the arrays of one call as numpy -- table (R, 12) int64 [byte offset of
-    the SR image, h_s, w_s, the bits of the float64 feather, the bits of the 8 float64 coefficients], tiles (n_tiles, 4) int32 [tile
-    row, tile column, first, count] in row-major tile order and list (n_list) int32: per tile the regions whose grown bounding box
-    (utils.paste.region_box) meets it, in the order of `regions` (_paste_regions_run)."""
-    import numpy as np
-    from .utils.paste import region_box
-    what = "paste_regions_u8"
-    H2, W2, m = _paste_inputs(photo2, sr_packed, sr_meta, what)
-    R = len(regions)
-    table = np.empty((R, 12), np.int64)
-    ids = []
-    for r, reg in enumerate(regions):
-        try:
-            k, coeffs, feather = reg
-            k, feather = int(k), float(feather)
-            a = np.asarray(coeffs, np.float64).reshape(-1)
-        except (TypeError, ValueError) as e:
-            raise _abi.DpmnError("%s: region %d is not (SR index, 8 coefficients, feather): %s" % (what, r, e)) from e
-        if not (0 <= k < m.shape[0] and a.size == 8 and np.isfinite(a).all() and np.isfinite(feather)):
-            raise _abi.DpmnError("%s: region %d names an SR image outside the batch of %d or does not carry 8 finite coefficients and a "
-                                 "finite feather" % (what, r, m.shape[0]))
-        table[r, :3] = m[k]
-        table[r, 3] = np.float64(feather).view(np.int64)
-        table[r, 4:] = a.view(np.int64)
-        ids.append(_box_tile_ids(region_box(a, int(m[k, 2]), int(m[k, 1]), H2, W2), W2))
-    tiles, lst = _paste_tiles(ids, W2, what)
-    return dict(table=table, tiles=tiles, list=lst, size=(H2, W2))
-
-
-def _paste_regions_run(photo2, sr_packed, host):
-    """One upload of the host arrays of _paste_regions_plan (the region table, the tiles and the region list in one int64 buffer) and the
-    launch -> the library's return code."""
-    import numpy as np
-    table, tiles, lst = (np.ascontiguousarray(host[k], dtype=t) for k, t in (("table", np.int64), ("tiles", np.int32), ("list", np.int32)))
-    R, n_tiles, n_list = table.shape[0], tiles.shape[0], lst.size
-    H2, W2 = host["size"]
-    if R == 0 or n_tiles == 0:
-        return 0
-    n_tile_words = (n_tiles * 4 + 1) // 2
-    buf = np.zeros(R * 12 + n_tile_words + (n_list + 1) // 2, np.int64)
-    buf[:R * 12] = table.reshape(-1)
-    buf[R * 12:R * 12 + n_tile_words].view(np.int32)[:n_tiles * 4] = tiles.reshape(-1)
-    buf[R * 12 + n_tile_words:].view(np.int32)[:n_list] = lst
-    d = torch.from_numpy(buf).to(photo2.device)
-    return lib.dpmn_paste_regions_u8(photo2.data_ptr(), H2, W2, sr_packed.data_ptr(), sr_packed.numel(), d.data_ptr(), table.ctypes.data, R,
-                                     d[R * 12:].data_ptr(), n_tiles, d[R * 12 + n_tile_words:].data_ptr(), n_list, stream())
-
-
-def paste_regions_u8(photo2, sr_packed, sr_meta, regions):
-    """The SR regions of one photo pasted back into the enlarged photo (csrc/paste.hip): photo2 a contiguous (H2, W2, 3) uint8 CUDA
-    tensor, modified IN PLACE and returned; sr_packed / sr_meta the SR images in utils.resize.pack_ragged's layout (what
-    stitch_windows_u8 returns; a contiguous quantize_sr_u8 output viewed flat has it too); regions a list of (SR index, coeffs, feather),
-    coeffs the 8 float64 coefficients of utils.paste.paste_coeffs, applied in list order -> byte for byte utils.paste.paste_regions_np,
-    in float64.  The host bins the regions into the 8 x 32 tiles of the photo that their grown bounding boxes meet; only those tiles are
-    launched, one thread per pixel, so no byte has two owners.  An empty list launches nothing.  Per call one buffer is uploaded: the
-    region table, the tiles and the per-tile region list."""
-    host = _paste_regions_plan(photo2, sr_packed, sr_meta, list(regions))
-    check(_paste_regions_run(photo2, sr_packed, host))
-    return photo2
-
-
 PASTE_KIND_PERSPECTIVE, PASTE_KIND_POLYGON = 0, 1      # csrc/paste_poly.hip KIND_*
 
 
-def _paste_mixed_plan(photo2, sr_packed, sr_meta, regions):
-    """Checks and per-call host data of paste_mixed_u8 -> host: the arrays of one call as numpy -- table (R, 13) int64 [byte offset of
+def _paste_mixed_plan(photo2, sr_packed, sr_meta, regions, what="paste_mixed_u8", polygons=True):
+    """Checks and per-call host data of the paste ops -> host: the arrays of one call as numpy -- table (R, 13) int64 [byte offset of
     the SR image, h_s, w_s, the bits of the float64 feather, kind, then the bits of the 8 float64 coefficients (a quadrilateral) or
     first strip, strip count and zeros (a polygon)], strips (S, 14) int64 [the bits of the 10 float64 of a strip of
-    utils.paste_poly.strip_table, its strip_box x0, y0, x1, y1], tiles and list as _paste_regions_plan makes them: a quadrilateral
-    lies in the tiles that its region_box meets, a polygon in those that the box of at least one of its strips meets
-    (_paste_mixed_run)."""
+    utils.paste_poly.strip_table, its strip_box x0, y0, x1, y1], tiles (n_tiles, 4) int32 [tile row, tile column, first, count] in
+    row-major tile order and list (n_list) int32: per tile the regions that meet it, in the order of `regions` -- a quadrilateral
+    lies in the tiles that its grown bounding box (utils.paste.region_box) meets, a polygon in those that the box of at least one of
+    its strips meets (_paste_mixed_run).  polygons=False (paste_regions_u8): every item must carry 8 coefficients."""
     import numpy as np
     from .utils.paste import region_box
     from .utils.paste_poly import _strips, is_polygon_region, strip_box
-    what = "paste_mixed_u8"
     H2, W2, m = _paste_inputs(photo2, sr_packed, sr_meta, what)
     R = len(regions)
     table, strips, n_strips, ids = np.zeros((R, 13), np.int64), [], 0, []
@@ -890,13 +816,14 @@ def _paste_mixed_plan(photo2, sr_packed, sr_meta, regions):
         try:
             k, shape, feather = reg
             k, feather = int(k), float(feather)
-            curved = is_polygon_region(reg)
+            curved = polygons and is_polygon_region(reg)
             a = _strips(shape, "strips") if curved else np.asarray(shape, np.float64).reshape(-1)
         except (TypeError, ValueError) as e:
-            raise _abi.DpmnError("%s: region %d is not (SR index, 8 coefficients or strips, feather): %s" % (what, r, e)) from e
+            raise _abi.DpmnError("%s: region %d is not (SR index, %s, feather): %s"
+                                 % (what, r, "8 coefficients or strips" if polygons else "8 coefficients", e)) from e
         if not (0 <= k < m.shape[0] and (curved or a.size == 8) and np.isfinite(a).all() and np.isfinite(feather)):
-            raise _abi.DpmnError("%s: region %d names an SR image outside the batch of %d or does not carry 8 finite coefficients (or "
-                                 "finite strips) and a finite feather" % (what, r, m.shape[0]))
+            raise _abi.DpmnError("%s: region %d names an SR image outside the batch of %d or does not carry 8 finite coefficients %sand a "
+                                 "finite feather" % (what, r, m.shape[0], "(or finite strips) " if polygons else ""))
         table[r, :3] = m[k]
         table[r, 3] = np.float64(feather).view(np.int64)
         if curved:
@@ -919,21 +846,25 @@ def _paste_mixed_run(photo2, sr_packed, host):
     import numpy as np
     table, strips, tiles, lst = (np.ascontiguousarray(host[k], dtype=t) for k, t in
                                  (("table", np.int64), ("strips", np.int64), ("tiles", np.int32), ("list", np.int32)))
-    R, S, n_tiles, n_list = table.shape[0], strips.shape[0], tiles.shape[0], lst.size
     H2, W2 = host["size"]
-    if R == 0 or n_tiles == 0:
+    if table.shape[0] == 0 or tiles.shape[0] == 0:
         return 0
-    n_tile_words = (n_tiles * 4 + 1) // 2
-    at_strips, at_tiles = R * 13, R * 13 + S * 14
-    buf = np.zeros(at_tiles + n_tile_words + (n_list + 1) // 2, np.int64)
-    buf[:at_strips] = table.reshape(-1)
-    buf[at_strips:at_tiles] = strips.reshape(-1)
-    buf[at_tiles:at_tiles + n_tile_words].view(np.int32)[:n_tiles * 4] = tiles.reshape(-1)
-    buf[at_tiles + n_tile_words:].view(np.int32)[:n_list] = lst
-    d = torch.from_numpy(buf).to(photo2.device)
-    return lib.dpmn_paste_mixed_u8(photo2.data_ptr(), H2, W2, sr_packed.data_ptr(), sr_packed.numel(), d.data_ptr(), table.ctypes.data, R,
-                                   d[at_strips:].data_ptr() if S else None, S, d[at_tiles:].data_ptr(), n_tiles,
-                                   d[at_tiles + n_tile_words:].data_ptr(), n_list, stream())
+    d, d_table, d_strips, d_tiles, d_list = _upload(photo2.device, table, strips, tiles, lst)
+    return lib.dpmn_paste_mixed_u8(photo2.data_ptr(), H2, W2, sr_packed.data_ptr(), sr_packed.numel(), d_table, table.ctypes.data,
+                                   table.shape[0], d_strips, strips.shape[0], d_tiles, tiles.shape[0], d_list, lst.size, stream())
+
+
+def paste_regions_u8(photo2, sr_packed, sr_meta, regions):
+    """The SR regions of one photo pasted back into the enlarged photo (csrc/paste_poly.hip): photo2 a contiguous (H2, W2, 3) uint8 CUDA
+    tensor, modified IN PLACE and returned; sr_packed / sr_meta the SR images in utils.resize.pack_ragged's layout (what
+    stitch_windows_u8 returns; a contiguous quantize_sr_u8 output viewed flat has it too); regions a list of (SR index, coeffs, feather),
+    coeffs the 8 float64 coefficients of utils.paste.paste_coeffs, applied in list order -> byte for byte utils.paste.paste_regions_np,
+    in float64.  The host bins the regions into the 8 x 32 tiles of the photo that their grown bounding boxes meet; only those tiles are
+    launched, one thread per pixel, so no byte has two owners.  An empty list launches nothing.  Per call one buffer is uploaded: the
+    region table, the tiles and the per-tile region list.  paste_mixed_u8 without polygons: an item that carries strips is refused."""
+    host = _paste_mixed_plan(photo2, sr_packed, sr_meta, list(regions), what="paste_regions_u8", polygons=False)
+    check(_paste_mixed_run(photo2, sr_packed, host))
+    return photo2
 
 
 def paste_mixed_u8(photo2, sr_packed, sr_meta, regions):

@@ -567,42 +567,33 @@ int dpmn_stitch_windows_u8(const float* sr, long batch_stride, long chan_stride,
  * computed.  A tile that names no region or lies outside its region writes nothing.  R = 0 launches nothing.  One launch. */
 int dpmn_quad_crop_u8(const unsigned char* packed, long packed_bytes, const long long* regions, const long long* regions_host /* HOST array */,
                       int R, const int* tiles, int n_tiles, unsigned char* out, long out_bytes, dpmn_stream_t stream);
-/* The SR regions pasted back into their enlarged photo (paste.hip; utils/paste.py holds the coefficients, the mask and the numpy
- * restatement): photo, H2 x W2 x 3 uint8, is modified IN PLACE; sr holds the SR images in the packed layout of dpmn_resize_ragged_u8.
- * Per region, in table order, and per pixel (X, Y) of the photo: sx = (a0 xin + a1 yin + a2) / (a6 xin + a7 yin + 1), sy likewise from
- * a3 a4 a5, at xin = X + 0.5, yin = Y + 0.5; the pixel is touched only where 0 <= sx < w_s and 0 <= sy < h_s; the source byte is
- * dpmn_quad_crop_u8's bicubic sample of the SR image; the mask m is 255 for feather <= 0, else with d = min(sx, w_s - sx, sy, h_s - sy)
- * and t = d / feather it is 255 for t >= 1 and floor(t * 255 + 0.5) below; the byte becomes ((t >> 8) + t) >> 8 with
- * t = dst * (255 - m) + src * m + 128 (PIL's Image.paste with an L mask).  float64, plain * + / in that order: independent of the
- * compute mode.  regions: device int64 (R, 12), per region [byte offset of its SR image in sr, h_s, w_s, the bits of the float64
- * feather, the bits of the 8 float64 coefficients a0 .. a7]; regions_host: the same table in HOST memory (the entry point checks it and
- * refuses the call before the launch when an SR image does not fit sr or has a side outside 1 .. 8192; the kernel checks the device
- * copy and skips such a region).  tiles: device int32 (n_tiles, 4), per 32 x 8 tile (w x h) of the photo [tile row, tile column, first,
- * count]: its regions are list[first .. first + count), device int32 (n_list) indices into the table, applied in that order.  Every
- * tile at most once: one block per tile, one thread per pixel, each byte of the photo has one owner.  A tile outside the photo or
- * whose slice leaves the list writes nothing; a list entry outside the table is skipped.  photo and sr must not overlap.  R = 0 or
- * n_tiles = 0 launches nothing.  One launch. */
-int dpmn_paste_regions_u8(unsigned char* photo, int H2, int W2, const unsigned char* sr, long sr_bytes, const long long* regions,
-                          const long long* regions_host /* HOST array */, int R, const int* tiles, int n_tiles, const int* list, int n_list,
-                          dpmn_stream_t stream);
-/* Quadrilaterals and polygons pasted back in ONE list (paste_poly.hip; utils/paste_poly.py holds the strip table, the inverse of a
- * strip and the numpy restatement): dpmn_paste_regions_u8 with a second kind of region, for the curved text that dpmn_poly_crop_u8
- * straightened strip by strip.  regions: device int64 (R, 13), per region [byte offset of its SR image in sr, h_s, w_s, the bits of the
- * float64 feather, kind, 8 words]: kind 0 is a perspective region and the 8 words are the bits of a0 .. a7, exactly
- * dpmn_paste_regions_u8's region; kind 1 is a polygon and the words are [first strip, strip count, 6 unused].  strips: device int64
- * (n_strips, 14), per strip [the bits of 10 float64: the corners NW, NE, SE, SW as (x, y) in the ENLARGED photo and the SR columns
- * c0, c1 that the strip covers; then its box x0, y0, x1, y1 in pixels of the photo, x1 and y1 exclusive].  A polygon region at pixel
- * (X, Y): the strips are walked in table order; one whose box does not hold the pixel is skipped; for the others, with
+/* The SR regions pasted back into their enlarged photo, quadrilaterals and polygons in ONE list (paste_poly.hip; utils/paste.py and
+ * utils/paste_poly.py hold the coefficients, the mask, the strip table, the inverse of a strip and the numpy restatements): photo,
+ * H2 x W2 x 3 uint8, is modified IN PLACE; sr holds the SR images in the packed layout of dpmn_resize_ragged_u8.  The regions are
+ * applied in table order; each gives a pixel (X, Y) of the photo a source position (sx, sy) in its SR image or none.
+ * regions: device int64 (R, 13), per region [byte offset of its SR image in sr, h_s, w_s, the bits of the float64 feather, kind,
+ * 8 words].  kind 0 is a perspective region and the 8 words are the bits of the float64 coefficients a0 .. a7:
+ * sx = (a0 xin + a1 yin + a2) / (a6 xin + a7 yin + 1), sy likewise from a3 a4 a5, at xin = X + 0.5, yin = Y + 0.5.  kind 1 is a polygon,
+ * the curved text that dpmn_poly_crop_u8 straightened strip by strip, and the words are [first strip, strip count, 6 unused].
+ * strips: device int64 (n_strips, 14), per strip [the bits of 10 float64: the corners NW, NE, SE, SW as (x, y) in the ENLARGED photo
+ * and the SR columns c0, c1 that the strip covers; then its box x0, y0, x1, y1 in pixels of the photo, x1 and y1 exclusive].  A polygon
+ * region at pixel (X, Y): the strips are walked in table order; one whose box does not hold the pixel is skipped; for the others, with
  * P = (X + 0.5, Y + 0.5), E = NE - NW, F = SW - NW, G = SE - SW - NE + NW, Hv = P - NW and cross(a, b) = ax by - ay bx:
  * A = cross(G, F), B = cross(Hv, G) + cross(E, F), C = cross(Hv, E), r = sqrt(B * B - 4 * A * C), v = (-2 * C) / (B + r) if B >= 0 else
  * (-B + r) / (2 * A), D = E + v * G, N = Hv - v * F, u = N.x / D.x if |D.x| >= |D.y| else N.y / D.y; the first strip with 0 <= u < 1 and
  * 0 <= v < 1 claims the pixel (a NaN compares false) and gives sx = c0 + u * (c1 - c0), sy = v * h_s; a pixel no strip claims is not
- * touched.  From (sx, sy) on both kinds are dpmn_paste_regions_u8's pixel: the test against the SR rectangle, the feather mask, the
- * bicubic sample, the blend.  float64, plain * + - / and the correctly rounded sqrt in that order.  regions_host: the region table in
- * HOST memory; the entry point refuses the call before the launch when an SR image does not fit sr or has a side outside 1 .. 8192, a
- * kind is neither 0 nor 1 or a polygon's strips (1 .. 31) leave the strip table; the kernel checks the device copy and skips such a
- * region.  The strips hold no index: a strip of any numbers claims pixels or none.  tiles, list: as dpmn_paste_regions_u8 takes them.
- * photo and sr must not overlap.  R = 0 or n_tiles = 0 launches nothing.  One launch. */
+ * touched.  From (sx, sy) on both kinds: the pixel is touched only where 0 <= sx < w_s and 0 <= sy < h_s; the source byte is
+ * dpmn_quad_crop_u8's bicubic sample of the SR image; the mask m is 255 for feather <= 0, else with d = min(sx, w_s - sx, sy,
+ * h_s - sy) and t = d / feather it is 255 for t >= 1 and floor(t * 255 + 0.5) below; the byte becomes ((t >> 8) + t) >> 8 with
+ * t = dst * (255 - m) + src * m + 128 (PIL's Image.paste with an L mask).  float64, plain * + - / and the correctly rounded sqrt in that
+ * order: independent of the compute mode.  regions_host: the region table in HOST memory; the entry point refuses the call before the
+ * launch when an SR image does not fit sr or has a side outside 1 .. 8192, a kind is neither 0 nor 1 or a polygon's strips (1 .. 31)
+ * leave the strip table; the kernel checks the device copy and skips such a region.  The strips hold no index: a strip of any numbers
+ * claims pixels or none.  tiles: device int32 (n_tiles, 4), per 32 x 8 tile (w x h) of the photo [tile row, tile column, first, count]:
+ * its regions are list[first .. first + count), device int32 (n_list) indices into the table, applied in that order.  Every tile at
+ * most once: one block per tile, one thread per pixel, each byte of the photo has one owner.  A tile outside the photo or whose slice
+ * leaves the list writes nothing; a list entry outside the table is skipped.  photo and sr must not overlap.  R = 0 or n_tiles = 0
+ * launches nothing.  One launch. */
 int dpmn_paste_mixed_u8(unsigned char* photo, int H2, int W2, const unsigned char* sr, long sr_bytes, const long long* regions,
                         const long long* regions_host /* HOST array */, int R, const long long* strips, int n_strips, const int* tiles,
                         int n_tiles, const int* list, int n_list, dpmn_stream_t stream);

@@ -1,4 +1,4 @@
-"""csrc/paste.hip against the numpy restatement of dpmn_amd/utils/paste.py, byte for byte: ops.paste_regions_u8 (one enlarged photo,
+"""csrc/paste_poly.hip's perspective regions against the numpy restatement of dpmn_amd/utils/paste.py, byte for byte: ops.paste_regions_u8 (one enlarged photo,
 the SR images in pack_ragged's layout and a list of regions -> the photo with the regions pasted, in place), its rejections, and the
 paste path on top of it: TextSR.demo(boxes=True, paste=True) and main.py --demo_paste."""
 import os
@@ -85,7 +85,7 @@ def test_paste_regions_equals_the_restatement(dev, scene, feather):
     for k, c, _ in regions[feather]:
         x0, y0, x1, y1 = paste.region_box(c, SR_SIZES[k][1], SR_SIZES[k][0], H2, W2)
         met |= {(r, col) for r in range(y0 // TILE_H, -(-y1 // TILE_H)) for col in range(x0 // TILE_W, -(-x1 // TILE_W)) if x1 > x0 and y1 > y0}
-    host = ops._paste_regions_plan(torch.from_numpy(photo2).to(dev), packed, meta, regions[feather])
+    host = ops._paste_mixed_plan(torch.from_numpy(photo2).to(dev), packed, meta, regions[feather], what="paste_regions_u8", polygons=False)
     assert {(int(t[0]), int(t[1])) for t in host["tiles"]} == met and host["tiles"].shape[0] == len(met)
     assert (0, 0) in met and (5, 2) not in met and len(met) < 18
     for r in range(6):
@@ -142,14 +142,32 @@ def test_rejections_and_the_empty_list(dev, scene):
             pytest.fail("call %d was accepted" % i)
     # the library refuses the same numbers when they reach it past the wrapper: nothing is launched, the photo stays
     d = fresh()
-    host = ops._paste_regions_plan(d, packed, meta, regs)
+    host = ops._paste_mixed_plan(d, packed, meta, regs, what="paste_regions_u8", polygons=False)
     host["table"] = host["table"].copy()
     host["table"][2, 0] = packed.numel() - 32 * 200 * 3 + 1      # the SR image of region 2 ends one byte past the buffer
-    code = ops._paste_regions_run(d, packed, host)
+    code = ops._paste_mixed_run(d, packed, host)
     torch.cuda.synchronize()
     assert code == -1 and np.array_equal(d.cpu().numpy(), photo2)
-    with pytest.raises(_abi.DpmnError, match="paste_regions"):
+    with pytest.raises(_abi.DpmnError, match="paste_mixed"):
         _abi.check(code)
+
+
+def test_a_polygon_item_is_refused_under_the_name_paste_regions_u8(dev, scene):
+    """paste_regions_u8 shares paste_mixed_u8's plan and kernel but takes quadrilaterals only: an item that carries a strip table is
+    refused under its own name before anything is launched."""
+    from dpmn_amd import _abi, ops
+    from dpmn_amd.utils import paste_poly
+    from test_poly import ARC_DOWN
+    photo2, srs, regions, _ = scene
+    packed, meta = resize.pack_ragged(srs)
+    strips = paste_poly.strip_table(ARC_DOWN, SCALE, SR_SIZES[1][1], SR_SIZES[1][0])
+    assert strips.ndim == 2 and strips.shape[1] == 10 and paste_poly.is_polygon_region((1, strips, 0.0))
+    d = torch.from_numpy(photo2).to(dev)
+    for regs in ([(1, strips, 0.0)], regions[0.0][:2] + [(1, strips, 0.0)]):
+        with pytest.raises(_abi.DpmnError, match="paste_regions_u8"):
+            ops.paste_regions_u8(d, packed.to(dev), meta, regs)
+        torch.cuda.synchronize()
+        assert np.array_equal(d.cpu().numpy(), photo2)
 
 
 def _png(path):

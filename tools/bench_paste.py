@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""What pasting the SR regions back into their photo (main.py --demo_paste, csrc/paste.hip) costs on one MI355X: prints ONE JSON line.
+"""What pasting the SR regions back into their photo (main.py --demo_paste, csrc/paste_poly.hip) costs on one MI355X: prints ONE JSON line.
 
 One photo of 1536 x 2048, enlarged by 2, and --regions slanted regions whose SR images are 32 x 128 go through
-  paste_us         -- dpmn_paste_regions_u8 alone (one launch), the table, the tiles and the list already on the device
+  paste_us         -- dpmn_paste_mixed_u8 alone (one launch), the table, the tiles and the list already on the device
   enlarge_paste_ms -- what TextSR.demo does per photo: ops.resize_ragged_u8 of the uploaded photo at its own target size, then
                       ops.paste_regions_u8 (host binning, one upload, launch), synchronised; the photo and the SR images are on the device
   pil_ms           -- the same work with PIL on the host: Image.resize(BICUBIC), then per region Image.transform(PERSPECTIVE, BICUBIC) of
@@ -83,12 +83,12 @@ def main():
 
     # the launch alone: everything it reads is uploaded once (pasting again and again over the same photo: the same work each time)
     photo2 = enlarge()
-    host = ops._paste_regions_plan(photo2, sr_packed, sr_meta, regions)
+    host = ops._paste_mixed_plan(photo2, sr_packed, sr_meta, regions, what="paste_regions_u8", polygons=False)
     table, tiles, lst = host["table"], host["tiles"], host["list"]
     R, n_tiles, n_list = table.shape[0], tiles.shape[0], lst.size
     d_table, d_tiles, d_list = torch.from_numpy(table).to(dev), torch.from_numpy(tiles).to(dev), torch.from_numpy(lst).to(dev)
-    call = lambda: check(lib.dpmn_paste_regions_u8(photo2.data_ptr(), H2, W2, sr_packed.data_ptr(), sr_packed.numel(), d_table.data_ptr(),
-                                                   table.ctypes.data, R, d_tiles.data_ptr(), n_tiles, d_list.data_ptr(), n_list, stream()))
+    call = lambda: check(lib.dpmn_paste_mixed_u8(photo2.data_ptr(), H2, W2, sr_packed.data_ptr(), sr_packed.numel(), d_table.data_ptr(),
+                                                 table.ctypes.data, R, None, 0, d_tiles.data_ptr(), n_tiles, d_list.data_ptr(), n_list, stream()))
     for _ in range(10):
         call()
     t = []

@@ -5,10 +5,9 @@ One enlarged photo of 2048 x 2048 and --regions 14-point arcs (k = 7) of about 4
 next to as many slanted quadrilaterals of the same area with the same SR images, in one run:
   mixed_polygons_us  -- dpmn_paste_mixed_u8 alone on the arcs (one launch), every table already on the device
   mixed_quads_us     -- dpmn_paste_mixed_u8 alone on the quadrilaterals: the same kernel on its perspective branch
-  regions_quads_us   -- dpmn_paste_regions_u8 alone on the quadrilaterals (csrc/paste.hip)
   ops_*_ms           -- ops.paste_mixed_u8 / ops.paste_regions_u8 as the demo calls them (host plan, one upload, launch), synchronised
   numpy_polygons_ms  -- utils.paste_poly.paste_mixed_np on the host, the arcs
-The kernels are timed with HIP events around --kernel-reps back-to-back calls after 10 warm-up calls, --reps times, the three
+The kernels are timed with HIP events around --kernel-reps back-to-back calls after 10 warm-up calls, --reps times, the two
 alternating: median, best and spread = (max - min) / median over the repetitions; the ops figures are medians of --reps runs after 2
 warm-up runs, the numpy figure the median of 3.  *_px_inside counts the pixels a region claims; differing_bytes the bytes of the GPU's
 photo that differ from the restatement's (expected: 0).  The measurement runs in a child process under a time limit of its own
@@ -96,16 +95,8 @@ def main():
                                                            table.ctypes.data, table.shape[0], d[1].data_ptr() if S else None, S,
                                                            d[2].data_ptr(), n_tiles, d[3].data_ptr(), n_list, stream()))
 
-    def regions_call(regions):
-        host = ops._paste_regions_plan(work, sr_packed, sr_meta, regions)
-        table = host["table"]
-        d = [torch.from_numpy(np.ascontiguousarray(host[k])).to(dev) for k in ("table", "tiles", "list")]
-        return host, lambda: check(lib.dpmn_paste_regions_u8(work.data_ptr(), H2, W2, sr_packed.data_ptr(), sr_packed.numel(), d[0].data_ptr(),
-                                                             table.ctypes.data, table.shape[0], d[1].data_ptr(), host["tiles"].shape[0],
-                                                             d[2].data_ptr(), host["list"].size, stream()))
-
-    # the launches alone (pasting again and again over the same photo: the same work each time), the three alternating
-    calls = {"mixed_polygons": mixed_call(polys), "mixed_quads": mixed_call(quads), "regions_quads": regions_call(quads)}
+    # the launches alone (pasting again and again over the same photo: the same work each time), the two alternating
+    calls = {"mixed_polygons": mixed_call(polys), "mixed_quads": mixed_call(quads)}
     times = {k: [] for k in calls}
     for _, call in calls.values():
         for _ in range(10):
