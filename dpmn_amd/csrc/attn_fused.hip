@@ -409,13 +409,7 @@ int fa_prepare(FusedAttnArgs& a, const float* tq, const float* tkv, const float*
   }
   DPMN_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "ln_qkv_window_attn: workspace (dpmn_ln_qkv_window_attn_workspace_bytes, 16-byte aligned) missing");
   a.folded = static_cast<float*>(workspace);
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return dpmn_set_error(DPMN_ERR_LAUNCH, "ln_qkv_window_attn: device query failed");
-    n_cu = prop.multiProcessorCount > 8 ? prop.multiProcessorCount / 8 * 8 : 8;
-  }
+  const int cus = dpmn_cu_count(), n_cu = cus > 8 ? cus / 8 * 8 : 8;
   const long slabs = (long)B * (H * W / 64);
   long blocks = 2L * n_cu;          // 2 resident blocks per CU (78 KB of LDS each) x CUs; a multiple of 8
   const long need = ((3 * slabs + 7) / 8) * 8;
@@ -464,20 +458,19 @@ static int fused_attn_launch(const float* tq, const float* tkv, const float* lnq
   a.q_out = q_out; a.kv_out = kv_out; a.p_drop = p_drop; a.inv_keep = train ? 1.0f / (1.0f - p_drop) : 1.0f; a.seed = seed;
   a.out = out;
   const size_t smem = (size_t)(FOLD_STRIDE + 4 * 64 * LDK + 2 * 64) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ln_qkv_window_attn<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ln_qkv_window_attn<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
   const double tokens = (double)B * H * W;
   double attn = 0.0;
   for (int g = 0; g < 3; ++g) attn += 4.0 * windows[g] * windows[g] * FD * 2 * tokens;
   hipStream_t st = as_stream(stream);
   if (refold) fa_fold(a, st);
   ProfScope prof(PT_ATTN_FUSED, st, 2.0 * tokens * FC * (3 * FC) + attn, 4.0 * (3.0 * tokens * FC + 3.0 * FC * FC));
-  if (train) hipLaunchKernelGGL(k_ln_qkv_window_attn<true>, dim3((unsigned)blocks), dim3(256), smem, st, a);
-  else hipLaunchKernelGGL(k_ln_qkv_window_attn<false>, dim3((unsigned)blocks), dim3(256), smem, st, a);
+  if (train) {
+    dpmn_lds_optin<k_ln_qkv_window_attn<true>>(smem);
+    hipLaunchKernelGGL(k_ln_qkv_window_attn<true>, dim3((unsigned)blocks), dim3(256), smem, st, a);
+  } else {
+    dpmn_lds_optin<k_ln_qkv_window_attn<false>>(smem);
+    hipLaunchKernelGGL(k_ln_qkv_window_attn<false>, dim3((unsigned)blocks), dim3(256), smem, st, a);
+  }
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }

@@ -365,19 +365,9 @@ int dpmn_ln_qkv_window_attn_d32_f32(const float* tq, const float* tkv, const flo
     DPMN_REQUIRE(shifts[g] >= 0 && shifts[g] < windows[g] && bias_tables[g], "ln_qkv_window_attn_d32: bad shift / null bias table");
     a.gid[s] = g; a.ws[s] = windows[g]; a.shift[s] = shifts[g]; a.table[s] = bias_tables[g];
   }
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return dpmn_set_error(DPMN_ERR_LAUNCH, "ln_qkv_window_attn_d32: device query failed");
-    n_cu = prop.multiProcessorCount > 8 ? prop.multiProcessorCount / 8 * 8 : 8;
-  }
+  const int cus = dpmn_cu_count(), n_cu = cus > 8 ? cus / 8 * 8 : 8;
   const size_t smem = (size_t)(FOLD + SET) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ln_qkv_window_attn192), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_ln_qkv_window_attn192>(smem);
   hipStream_t st = as_stream(stream);
   if (refold) hipLaunchKernelGGL(k_attn192_fold, dim3(NF + 1, 3), dim3(64), 0, st, a);
   const double tokens = (double)B * H * W;

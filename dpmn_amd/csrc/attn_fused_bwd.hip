@@ -468,13 +468,7 @@ __global__ __launch_bounds__(256, 2) void k_ln_qkv_window_attn_bwd(FusedAttnArgs
 
 
 long bwd_grid(int B, int H, int W) {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-    n_cu = prop.multiProcessorCount > 8 ? prop.multiProcessorCount / 8 * 8 : 8;
-  }
+  const int cus = dpmn_cu_count(), n_cu = cus > 8 ? cus / 8 * 8 : 8;
   long blocks = 2L * n_cu;      // 2 resident blocks per CU, as in the forward (fa_prepare)
   const long need = ((3 * (long)B * (H * W / 64) + 7) / 8) * 8;
   return blocks > need ? need : blocks;
@@ -510,20 +504,19 @@ int dpmn_ln_qkv_window_attn_bwd_f32(const float* tq, const float* tkv, const flo
     a.tpart[s] = dtable_parts[a.gid[s]];
   }
   const size_t smem = (size_t)(FOLD_STRIDE + 4 * 64 * LDK + STAT + 64) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ln_qkv_window_attn_bwd<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ln_qkv_window_attn_bwd<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
   const double tokens = (double)B * H * W;
   double attn = 0.0;
   for (int g = 0; g < 3; ++g) attn += 14.0 * windows[g] * windows[g] * FD * 2 * tokens;   // 7 products of 2 N d FLOP per (token, head)
   hipStream_t st = as_stream(stream);
   if (refold) fa_fold(a, st);
   ProfScope prof(PT_ATTN_FUSED_BWD, st, 2.0 * tokens * FC * (3 * FC) + attn, 4.0 * (6.0 * tokens * FC + 3.0 * FC * FC));
-  if (p_drop > 0.f) hipLaunchKernelGGL(k_ln_qkv_window_attn_bwd<true>, dim3((unsigned)blocks), dim3(256), smem, st, a);
-  else hipLaunchKernelGGL(k_ln_qkv_window_attn_bwd<false>, dim3((unsigned)blocks), dim3(256), smem, st, a);
+  if (p_drop > 0.f) {
+    dpmn_lds_optin<k_ln_qkv_window_attn_bwd<true>>(smem);
+    hipLaunchKernelGGL(k_ln_qkv_window_attn_bwd<true>, dim3((unsigned)blocks), dim3(256), smem, st, a);
+  } else {
+    dpmn_lds_optin<k_ln_qkv_window_attn_bwd<false>>(smem);
+    hipLaunchKernelGGL(k_ln_qkv_window_attn_bwd<false>, dim3((unsigned)blocks), dim3(256), smem, st, a);
+  }
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }

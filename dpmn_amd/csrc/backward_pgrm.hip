@@ -396,11 +396,7 @@ int launch_wattn_bwd(const float* q, const float* kv, const float* tbl, const fl
                      int B, int H, int W, int C, int g, int shift, float p_drop, unsigned long long seed, hipStream_t st, int part_mode = 0) {
   constexpr int CG = 2 * D, LDR = CG + 4, TBL = (2 * WS - 1) * (2 * WS - 1);
   const size_t smem = (size_t)(3 * ((TBL * 2 + 3) & ~3) + 2 * (4 * 64 * LDR + 6 * 64)) * 4 + 2 * 64 * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_window_attn_bwd<WS, D, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_window_attn_bwd<WS, D, DROP>>(smem);
   const long slabs = (long)B * (H * W / 64);
   hipLaunchKernelGGL((k_window_attn_bwd<WS, D, DROP>), dim3((unsigned)((slabs + 1) / 2)), dim3(256), smem, st, q, kv, tbl, dout, dq, dkv,
                      dtable, B, H, W, C, g, shift, p_drop, seed, part_mode);
@@ -1333,13 +1329,7 @@ int dpmn_sk_feats_grad_f32(const float* dout, const float* feats, const float* d
 
 // KEEP variant: persistent, 2 blocks per CU (256 registers per wave for the prefetch), never more blocks than planes / 4
 static long dwconv_bwd_grid(long planes) {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  const long want = 2L * n_cu, need = (planes + 3) / 4;
+  const long want = 2L * dpmn_cu_count(), need = (planes + 3) / 4;
   return want < need ? want : need;
 }
 
@@ -1349,7 +1339,7 @@ int dpmn_dwconv3x3_bwd_f32(const float* P, const float* dg, const float* w, floa
   const long planes = (long)B * Ch;
   const int rb = dwconv_band_rows(r);
   const size_t smem = (size_t)8 * (rb + 2) * (r + 8) * 4;
-  if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwconv_bwd<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  dpmn_lds_optin<k_dwconv_bwd<false>>(smem);
   hipLaunchKernelGGL(k_dwconv_bwd<false>, dim3((unsigned)((planes * (r / rb) + 3) / 4)), dim3(256), smem, as_stream(stream), P, dg, w, dP, dw, db, Ch, r,
                      planes, static_cast<const float*>(nullptr), 0, 0, 0.f, 0ull, static_cast<float*>(nullptr), rb);
   DPMN_CHECK_LAUNCH();
@@ -1367,11 +1357,15 @@ int dpmn_dwconv3x3_bwd_fused_f32(const float* P, const float* dg, const float* g
   const size_t smem = (size_t)8 * (rb + 2) * (r + 8) * 4;
   // dP (9 taps) + dw (9 taps) = 36 FLOPs per element; P, dg (, gpre) read, dP written
   ProfScope prof(PT_DWCONV_BWD, as_stream(stream), 36.0 * planes * r * r, 4.0 * (gpre ? 4 : 3) * (double)planes * r * r);
-  if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwconv_bwd<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (keep) hipLaunchKernelGGL(k_dwconv_bwd<true>, dim3((unsigned)dwconv_bwd_grid(planes)), dim3(256), smem, as_stream(stream), P, dg, w, dP, dw, db, Ch, r,
-                     planes, gpre, in_gelu, out_gelu_bwd, p_drop, seed);
-  else hipLaunchKernelGGL(k_dwconv_bwd<false>, dim3((unsigned)((planes * (r / rb) + 3) / 4)), dim3(256), smem, as_stream(stream), P, dg, w, dP, dw, db, Ch, r,
-                     planes, gpre, in_gelu, out_gelu_bwd, p_drop, seed, static_cast<float*>(nullptr), rb);
+  if (keep) {
+    dpmn_lds_optin<k_dwconv_bwd<true>>(smem);
+    hipLaunchKernelGGL(k_dwconv_bwd<true>, dim3((unsigned)dwconv_bwd_grid(planes)), dim3(256), smem, as_stream(stream), P, dg, w, dP, dw, db, Ch, r,
+                       planes, gpre, in_gelu, out_gelu_bwd, p_drop, seed);
+  } else {
+    dpmn_lds_optin<k_dwconv_bwd<false>>(smem);
+    hipLaunchKernelGGL(k_dwconv_bwd<false>, dim3((unsigned)((planes * (r / rb) + 3) / 4)), dim3(256), smem, as_stream(stream), P, dg, w, dP, dw, db, Ch, r,
+                       planes, gpre, in_gelu, out_gelu_bwd, p_drop, seed, static_cast<float*>(nullptr), rb);
+  }
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }
@@ -1396,11 +1390,15 @@ int dpmn_dwconv3x3_bwd_fused_det_f32(const float* P, const float* dg, const floa
   const size_t smem = (size_t)8 * (rb + 2) * (r + 8) * 4;
   // dP (9 taps) + dw (9 taps) = 36 FLOPs per element; P, dg (, gpre) read, dP written
   ProfScope prof(PT_DWCONV_BWD, as_stream(stream), 36.0 * planes * r * r, 4.0 * (gpre ? 4 : 3) * (double)planes * r * r);
-  if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwconv_bwd<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (keep) hipLaunchKernelGGL(k_dwconv_bwd<true>, dim3((unsigned)dwconv_bwd_grid(planes)), dim3(256), smem, as_stream(stream), P, dg, w, dP, dw, db, Ch, r,
-                     planes, gpre, in_gelu, out_gelu_bwd, p_drop, seed, ws);
-  else hipLaunchKernelGGL(k_dwconv_bwd<false>, dim3((unsigned)((planes * (r / rb) + 3) / 4)), dim3(256), smem, as_stream(stream), P, dg, w, dP, dw, db, Ch, r,
-                     planes, gpre, in_gelu, out_gelu_bwd, p_drop, seed, ws, rb);
+  if (keep) {
+    dpmn_lds_optin<k_dwconv_bwd<true>>(smem);
+    hipLaunchKernelGGL(k_dwconv_bwd<true>, dim3((unsigned)dwconv_bwd_grid(planes)), dim3(256), smem, as_stream(stream), P, dg, w, dP, dw, db, Ch, r,
+                       planes, gpre, in_gelu, out_gelu_bwd, p_drop, seed, ws);
+  } else {
+    dpmn_lds_optin<k_dwconv_bwd<false>>(smem);
+    hipLaunchKernelGGL(k_dwconv_bwd<false>, dim3((unsigned)((planes * (r / rb) + 3) / 4)), dim3(256), smem, as_stream(stream), P, dg, w, dP, dw, db, Ch, r,
+                       planes, gpre, in_gelu, out_gelu_bwd, p_drop, seed, ws, rb);
+  }
   DPMN_CHECK_LAUNCH();
   prof.close();      // (the row reduction below is not part of the family)
   return dpmn_rows_reduce_f32(ws, dw, db, Ch * 9, Ch, B * (r / rb), stream);

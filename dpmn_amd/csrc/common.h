@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include "../../include/dpmn_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -175,6 +176,24 @@ __device__ __forceinline__ float drop_scale(unsigned long long seed, unsigned lo
 }
 
 static inline hipStream_t as_stream(dpmn_stream_t s) { return (hipStream_t)s; }
+
+// Per-device launch state.  Both helpers key a fixed table of relaxed atomics by the CURRENT device's ordinal (racing writers store
+// the same value; no mutex); an ordinal outside the table is not cached.
+constexpr int DPMN_MAX_DEVICES = 64;
+// CUs of the current device, 256 when the query fails.  Rounding to a grid stays with the caller.
+int dpmn_cu_count();
+// Opt Kernel in to `bytes` of dynamic LDS on the current device: hipFuncSetAttribute acts on that device's copy of the kernel, so the
+// largest count already set is kept per kernel AND per device, and the call is made only for more than that.  A failure is not
+// recorded (the next launch retries) and not reported here: the launch that follows fails and DPMN_CHECK_LAUNCH returns it.
+template <auto Kernel>
+inline void dpmn_lds_optin(size_t bytes) {
+  static std::atomic<int> set[DPMN_MAX_DEVICES];
+  int dev = -1;
+  const bool keyed = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < DPMN_MAX_DEVICES;
+  if (keyed && (int)bytes <= set[dev].load(std::memory_order_relaxed)) return;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess && keyed)
+    set[dev].store((int)bytes, std::memory_order_relaxed);
+}
 
 // In-pipeline kernel timing (include/dpmn_hip.h dpmn_profile_*; runtime.hip).  A ProfScope placed around ONE kernel launch
 // brackets it with a pair of HIP events on the launch stream while profiling is armed for its tag, and carries the launch's

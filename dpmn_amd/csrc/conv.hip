@@ -657,11 +657,7 @@ template <int KS, int TH>
 int launch_halo_c4(const ConvArgs& a, hipStream_t st) {
   constexpr int NPX = (TH + KS - 1) * (16 + KS - 1);
   const size_t smem = (size_t)(NPX + 2 * 48) * LDK * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_halo_c4<KS, TH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_conv_halo_c4<KS, TH>>(smem);
   dim3 grid(a.B * (a.Hin / TH) * cdiv(a.Win, 13));
   ProfScope prof(PT_CONV_HALO_C4, st, conv_flops(a), conv_bytes(a));
   hipLaunchKernelGGL((k_conv_halo_c4<KS, TH>), grid, dim3(256), smem, st, a);
@@ -675,11 +671,7 @@ int launch_halo_th(const ConvArgs& a, hipStream_t st) {
     if (g_dpmn_bf16) return launch_halo_th<KS, BN, TH, true>(a, st);
   constexpr int NPX = (TH + KS - 1) * (16 + KS - 1);
   const size_t smem = (size_t)(NPX + 2 * BN) * (BF ? (BK + 8) / 2 : LDK) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_halo<KS, BN, TH, BF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_conv_halo<KS, BN, TH, BF>>(smem);
   dim3 grid(a.B * (a.Hin / TH) * (a.Win / 16), cdiv(a.Cout, BN));
   ProfScope prof(PT_CONV_HALO, st, conv_flops(a), conv_bytes(a));
   hipLaunchKernelGGL((k_conv_halo<KS, BN, TH, BF>), grid, dim3(256), smem, st, a);
@@ -725,15 +717,16 @@ int launch_conv_sk(const ConvArgs& a, float* ws, size_t ws_bytes, unsigned* cnt,
              ((size_t)a.B * a.Hin * a.Win + (size_t)(abs(a.pad_y) + a.KH * abs(a.dil_y) + 2) * a.Win) * a.cseg[i] * 4 < (1ull << 31);
   }
   if (!simple || (n_aff != 0 && n_aff != n_seg)) return -1;
-  static int capacity = 0;      // resident workgroups of the device (2 per CU by LDS and registers)
-  if (!capacity) {
-    int dev = 0, cus = 0, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_conv_igemm_sk<128, 128, 2, 2, false>), 256, 0);
-    capacity = (cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 2);
-    if (getenv("DPMN_SK_BLOCKS")) capacity = atoi(getenv("DPMN_SK_BLOCKS"));      // experiment / test knob
-  }
+  // resident workgroups of the current device: its CUs x the blocks per CU (2 by LDS and registers), which the kernel's resource use
+  // and the one architecture the library is built for decide, not the device -- so that part is asked once
+  static const int per_cu = [] {
+    int n = 0;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&k_conv_igemm_sk<128, 128, 2, 2, false>), 256, 0);
+    return n > 0 ? n : 2;
+  }();
+  static const bool sk_forced = getenv("DPMN_SK_BLOCKS") != nullptr;      // experiment / test knob
+  static const int sk_blocks = sk_forced ? atoi(getenv("DPMN_SK_BLOCKS")) : 0;
+  const int capacity = sk_forced ? sk_blocks : dpmn_cu_count() * per_cu;
   const int M = a.B * a.Hp * a.Wp;
   const int nph = a.nphase > 1 ? a.nphase : 1;
   SkArgs sk{};

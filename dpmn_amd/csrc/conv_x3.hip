@@ -20,11 +20,7 @@ int x3_launch_igemm(bool aff, const ConvArgs& a, dim3 grid, hipStream_t st) {
 int x3_launch_halo(const ConvArgs& a, dim3 grid, hipStream_t st) {
   constexpr int NPX = (8 + 2) * (16 + 2);
   const size_t smem = (size_t)(3 * NPX + 2 * 3 * 64) * ((BK + 8) / 2) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_halo_x3<3, 64, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_conv_halo_x3<3, 64, 8>>(smem);
   hipLaunchKernelGGL((k_conv_halo_x3<3, 64, 8>), grid, dim3(256), smem, st, a);
   return 0;
 }

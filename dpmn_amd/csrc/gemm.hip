@@ -1149,11 +1149,6 @@ template <int K, int PRO, int EPI>
 int launch_rowreg(const float* x, int ldx, const float* w, float* y, int ldy, int M, int N, const ProArgs& p, const EpiArgs& e,
                   hipStream_t st) {
   const size_t smem = (size_t)(96 * (K + PAD) + 2 * 96 + (PRO == PRO_LN ? 96 * (K / 4) * 2 : 0)) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_rowreg<K, PRO, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
   const int tiles = M / (EPI == 4 ? 32 : 16), ny = N / 96;      // work items of a wave (pairs of 16-row tiles under RR_EPI 4)
   // resident waves: LDS-limited blocks per CU x 4; every wave gets the same number of tiles when that divides evenly
   const bool x3 = (PRO == PRO_NONE || PRO == PRO_LN) && (K == 96 || K == 192) && g_dpmn_x3;
@@ -1175,6 +1170,7 @@ int launch_rowreg(const float* x, int ldx, const float* w, float* y, int ldy, in
       return DPMN_OK;
     }
   }
+  dpmn_lds_optin<k_gemm_rowreg<K, PRO, EPI>>(smem);
   hipLaunchKernelGGL((k_gemm_rowreg<K, PRO, EPI>), dim3(gx, ny), dim3(256), smem, st, x, ldx, w, y, ldy, M, N, p, e);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
@@ -1210,11 +1206,7 @@ int launch_wholeK_th(const float* x, int ldx, const float* w, float* y, int ldy,
                      const EpiArgs& e, hipStream_t st, int target_blocks) {
   constexpr int BM = TH / 8;
   const size_t smem = (size_t)((WS_BN + BM) * (K + PAD) + (TH / 64) * WS_BN + 2 * K) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_wstat<K, PRO, TH, FULL, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_gemm_wstat<K, PRO, TH, FULL, EPI>>(smem);
   const int tiles = cdiv(M, BM), ny = cdiv(N, WS_BN);
   int gx = target_blocks / ny;
   if (gx < 1) gx = 1;
@@ -1384,12 +1376,6 @@ int dpmn_sk_mlp_in_drop_f32(const float* cat, const float* attn_vec, const float
                "sk_mlp_in: built for dim 96, three window groups, whole 16-token tiles (dpmn_sk_mlp_in_supported)");
   constexpr int Cc = 96, CG = 32;
   const size_t smem = (size_t)(96 * (Cc + PAD) + 3 * 96 + 96 * (CG + PAD)) * sizeof(float);      // 53376 B: proj_head is the larger tenant of its region
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_mlp_in<Cc, CG, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_mlp_in<Cc, CG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
   const int tiles = M / 16, ny = N / 96;
   int gx = 512 / ny;      // two resident blocks per CU
   if (gx < 1) gx = 1;
@@ -1398,8 +1384,12 @@ int dpmn_sk_mlp_in_drop_f32(const float* cat, const float* attn_vec, const float
   // algorithmic work of the two products; compulsory bytes: cat, feats, shortcut in, x1 and y out, both weight matrices
   ProfScope prof(PT_GEMM_WSTAT_LN, st, 2.0 * M * ((double)N * Cc + (double)Cc * CG),
                  4.0 * ((double)M * Cc * 4 + (double)M * N + (double)N * Cc + (double)Cc * CG));
-#define SKMLP_LAUNCH(SAVE_) hipLaunchKernelGGL((k_sk_mlp_in<Cc, CG, SAVE_>), dim3(gx, ny), dim3(256), smem, st, cat, attn_vec, rows_per_image, \
-                                              w_head, b_head, feats, shortcut, x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N, v_out, n2_out, p_row, seed_row)
+#define SKMLP_LAUNCH(SAVE_)                                                                                                              \
+  do {                                                                                                                                   \
+    dpmn_lds_optin<k_sk_mlp_in<Cc, CG, SAVE_>>(smem);                                                                                    \
+    hipLaunchKernelGGL((k_sk_mlp_in<Cc, CG, SAVE_>), dim3(gx, ny), dim3(256), smem, st, cat, attn_vec, rows_per_image, w_head, b_head,   \
+                       feats, shortcut, x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N, v_out, n2_out, p_row, seed_row);                     \
+  } while (0)
   if (g_dpmn_x3)
     dpmn_gemm::x3_launch_sk_mlp_in(cat, attn_vec, rows_per_image, w_head, b_head, feats, shortcut, x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N,
                                    v_out, n2_out, p_row, seed_row, gx, st);

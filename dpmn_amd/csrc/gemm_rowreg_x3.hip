@@ -411,11 +411,7 @@ __global__ __launch_bounds__(256, 2) void k_sk_mlp_in_x3(const float* __restrict
 template <int K, int PRO, int EPI>
 int launch_rr(const float* x, int ldx, const float* w, float* y, int ldy, int M, int N, const ProArgs& p, const EpiArgs& e, int gx, hipStream_t st) {
   const size_t smem = (size_t)3 * 96 * (K + 8) * 2 + (size_t)(2 * 96 + (PRO == PRO_LN ? 96 * (K / 4) * 2 : 0)) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_rowreg_x3<K, PRO, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_gemm_rowreg_x3<K, PRO, EPI>>(smem);
   hipLaunchKernelGGL((k_gemm_rowreg_x3<K, PRO, EPI>), dim3(gx, N / 96), dim3(256), smem, st, x, ldx, w, y, ldy, M, N, p, e);
   return 0;
 }
@@ -451,17 +447,14 @@ void x3_launch_sk_mlp_in(const float* cat, const float* sel, int rows_per_image,
                          float* y, int M, int N, float* v_out, float* n2_out, float p_row, unsigned long long seed_row, int gx, hipStream_t st) {
   constexpr int Cc = 96, CG = 32;
   const size_t smem = (size_t)3 * 96 * (Cc + 8) * 2 + (size_t)(3 * 96 + 96 * (Cc / 4) * 2) * sizeof(float);      // planes + pb + the fold's scratch (> proj_head)
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_mlp_in_x3<Cc, CG, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_mlp_in_x3<Cc, CG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
-  if (v_out)
+  if (v_out) {
+    dpmn_lds_optin<k_sk_mlp_in_x3<Cc, CG, true>>(smem);
     hipLaunchKernelGGL((k_sk_mlp_in_x3<Cc, CG, true>), dim3(gx, N / 96), dim3(256), smem, st, cat, sel, rows_per_image, w_head, b_head, feats, shortcut,
                        x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N, v_out, n2_out, p_row, seed_row);
-  else
+  } else {
+    dpmn_lds_optin<k_sk_mlp_in_x3<Cc, CG, false>>(smem);
     hipLaunchKernelGGL((k_sk_mlp_in_x3<Cc, CG, false>), dim3(gx, N / 96), dim3(256), smem, st, cat, sel, rows_per_image, w_head, b_head, feats, shortcut,
                        x1, ln_w, ln_b, eps, w_fc1, b_fc1, y, M, N, v_out, n2_out, p_row, seed_row);
+  }
 }
 }  // namespace dpmn_gemm

@@ -359,16 +359,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_kloop128_x3(const float* __rest
       *reinterpret_cast<f32x4*>(y + (size_t)(m_blk + wm * 64 + j * 16 + lr) * N + n_blk + wn * 64 + i * 16 + kq * 4) = acc[i][j];
 }
 
-int cu_count() {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  return n_cu;
-}
-
 }  // namespace
 
 namespace dpmn_gemm {
@@ -384,16 +374,15 @@ void x3_launch_pw(const float* g, const float* w, const float* bias, float* z, i
   constexpr int LDP_ = 132, LDWB_ = 48;
   const int bc = Ch % 192 == 0 ? 192 : 128;
   const size_t smem = (size_t)2 * 3 * (16 * LDP_ * 4 + bc * LDWB_ * 2);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_pw_bf16x3<192>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 3 * (16 * LDP_ * 4 + 192 * LDWB_ * 2));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_pw_bf16x3<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 3 * (16 * LDP_ * 4 + 128 * LDWB_ * 2));
-    attr_set = true;
-  }
   const long tiles = (long)(L / 128) * (Ch / bc) * B;
-  const int n_cu = cu_count();
+  const int n_cu = dpmn_cu_count();
   const unsigned grid = (unsigned)(tiles < n_cu ? tiles : n_cu);
-  if (bc == 192) hipLaunchKernelGGL((k_gemm_pw_bf16x3<192>), dim3(grid), dim3(512), smem, st, g, w, bias, z, Ch, L, B);
-  else hipLaunchKernelGGL((k_gemm_pw_bf16x3<128>), dim3(grid), dim3(512), smem, st, g, w, bias, z, Ch, L, B);
+  if (bc == 192) {
+    dpmn_lds_optin<k_gemm_pw_bf16x3<192>>(smem);
+    hipLaunchKernelGGL((k_gemm_pw_bf16x3<192>), dim3(grid), dim3(512), smem, st, g, w, bias, z, Ch, L, B);
+  } else {
+    dpmn_lds_optin<k_gemm_pw_bf16x3<128>>(smem);
+    hipLaunchKernelGGL((k_gemm_pw_bf16x3<128>), dim3(grid), dim3(512), smem, st, g, w, bias, z, Ch, L, B);
+  }
 }
 }  // namespace dpmn_gemm

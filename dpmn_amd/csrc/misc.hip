@@ -209,11 +209,7 @@ extern "C" {
 int dpmn_selftest_lds_poison(unsigned pattern, int blocks, dpmn_stream_t stream) {
   DPMN_REQUIRE(blocks > 0, "selftest_lds_poison: blocks > 0");
   constexpr int bytes = 160 * 1024;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lds_poison), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_lds_poison>(bytes);
   hipLaunchKernelGGL(k_lds_poison, dim3(blocks), dim3(256), bytes, as_stream(stream), pattern, bytes / 4);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;

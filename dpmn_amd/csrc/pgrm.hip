@@ -9,7 +9,6 @@
 // SKConv gate 86-91, Mlp depthwise 34-36, tail 559-565, SwinTransformerBlock.forward 315-331,
 // PGRM.forward 546-565.
 #include "common.h"
-#include <atomic>
 
 namespace {
 
@@ -410,11 +409,7 @@ int launch_window_attn8_mfma(const float* q, const float* kv, const float* table
                              int shift, float p_drop, unsigned long long seed, hipStream_t st) {
   constexpr int N = 64, LDR = 36, TBL = 15 * 15;
   const size_t smem = (size_t)(((TBL * 2 + 3) & ~3) + 2 * 3 * N * LDR) * 4 + 2 * N * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_window_attn8_mfma<DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_window_attn8_mfma<DROP>>(smem);
   const long slabs = (long)B * (H * W / 64);
   // per (window, head): QK^T + PV = 4 * N^2 * d FLOPs; q, k, v read + out written for this group's 32 channels
   ProfScope prof(PT_WATTN8, st, 4.0 * 64 * 16 * 2 * (double)B * H * W, 4.0 * 4 * 32 * (double)B * H * W);
@@ -575,11 +570,7 @@ int launch_window_attn_mfma(const float* q, const float* kv, const float* table,
                             int shift, hipStream_t st, float p_drop = 0.f, unsigned long long seed = 0ull) {
   constexpr int N = WS * WS, CG = 2 * D, LDR = CG + 4, TBL = (2 * WS - 1) * (2 * WS - 1), ROWS = WS == 16 ? 256 : 64, SETS = WS == 16 ? 1 : 2;
   const size_t smem = (size_t)(((TBL * 2 + 3) & ~3) + SETS * 2 * ROWS * LDR) * 4 + (size_t)SETS * ROWS * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_window_attn_mfma<WS, D, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_window_attn_mfma<WS, D, DROP>>(smem);
   const long sets = (long)B * (H * W / ROWS);
   ProfScope prof(PT_WATTN_MFMA32, st, 4.0 * N * D * 2 * (double)B * H * W, 4.0 * 4 * CG * (double)B * H * W);
   hipLaunchKernelGGL((k_window_attn_mfma<WS, D, DROP>), dim3((unsigned)((sets + SETS - 1) / SETS)), dim3(WS == 16 ? 512 : 256), smem, st, q, kv, table,
@@ -593,11 +584,7 @@ int launch_window_attn(const float* q, const float* kv, const float* table, floa
                        int shift, float p_drop, unsigned long long seed, hipStream_t st) {
   constexpr int N = WS * WS, CG = 2 * D, KROWS = 64, LDR = CG + 4, TBL = (2 * WS - 1) * (2 * WS - 1);
   const size_t smem = (size_t)(((TBL * 2 + 3) & ~3) + 2 * (64 + 2 * KROWS) * LDR) * 4 + 2 * KROWS * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_window_attn<WS, D, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_window_attn<WS, D, DROP>>(smem);
   const long slabs = (long)B * (H * W / 64);
   ProfScope prof(PT_WATTN_SCALAR, st, 4.0 * N * D * 2 * (double)B * H * W, 4.0 * 4 * CG * (double)B * H * W);
   hipLaunchKernelGGL((k_window_attn<WS, D, DROP>), dim3((unsigned)((slabs + 1) / 2)), dim3(256), smem, st, q, kv, table, out, B, H, W,
@@ -1047,7 +1034,7 @@ int dpmn_sk_gate_f32(const float* colsum_partials, int parts_per_image, int L, c
   // the project has one, and the kernel before this one, which read the weights from global memory, accepted it.
   const size_t smem = ((size_t)7 * C + 2 * dmid + (size_t)2 * dmid * C) * 4;
   DPMN_REQUIRE(smem <= 160 * 1024, "sk_gate: fc1 / fc2 do not fit in LDS");
-  if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sk_gate), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  dpmn_lds_optin<k_sk_gate>(smem);
   hipLaunchKernelGGL(k_sk_gate, dim3(B), dim3(SKG_T), smem, as_stream(stream), colsum_partials,
                      parts_per_image, L, fc1_w, fc1_b, fc2_w, fc2_b, attn_vec, C, groups, dmid);
   DPMN_CHECK_LAUNCH();
@@ -1058,15 +1045,7 @@ int dpmn_sk_gate_f32(const float* colsum_partials, int parts_per_image, int L, c
 // grid of at most 7 blocks per CU (21.8 KB of LDS each) in which every wave walks the same number of planes (the last ones one
 // less when the count does not divide); every other plane size takes k_dwconv_gelu on whole planes or 16-row bands.
 static unsigned dwconv32_grid(long planes) {
-  static std::atomic<int> cus[64];                 // CU count per device ordinal, read once each (relaxed: every writer stores the same value)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  int n_cu = cus[dev].load(std::memory_order_relaxed);
-  if (n_cu < 1) {
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
-    cus[dev].store(n_cu, std::memory_order_relaxed);
-  }
-  const long cap = 7L * n_cu * 4;                  // resident waves (3, 4 and 6 blocks per CU measured slower or equal)
+  const long cap = 7L * dpmn_cu_count() * 4;       // resident waves (3, 4 and 6 blocks per CU measured slower or equal)
   const long per = (planes + cap - 1) / cap;       // planes per wave
   const long waves = (planes + per - 1) / per;
   return (unsigned)((waves + 3) / 4);
@@ -1087,7 +1066,7 @@ static int launch_dwconv(const float* y, const float* w, const float* bias, floa
     const int rb = dwconv_band_rows(r);
     const long vplanes = planes * (r / rb);
     const size_t smem = (size_t)4 * (rb + 2) * (r + 8) * 4;
-    if (smem > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwconv_gelu), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    dpmn_lds_optin<k_dwconv_gelu>(smem);
     hipLaunchKernelGGL(k_dwconv_gelu, dim3((unsigned)((vplanes + 3) / 4)), dim3(256), smem, st, y, w, bias, g, Ch, r, planes, apply_gelu, g2,
                        in_gelu, p_drop, seed, rb);
   }

@@ -11,6 +11,19 @@ int dpmn_set_error(int code, const char* msg) {
   return code;
 }
 
+int dpmn_cu_count() {
+  static std::atomic<int> cus[DPMN_MAX_DEVICES];
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  const bool keyed = dev >= 0 && dev < DPMN_MAX_DEVICES;
+  int n = keyed ? cus[dev].load(std::memory_order_relaxed) : 0;
+  if (n < 1) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) return 256;
+    if (keyed) cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
 // ------------------------------------------------------------------ in-pipeline kernel profiler (common.h ProfScope)
 unsigned long long g_dpmn_prof_mask = 0ull;
 double g_dpmn_prof_hint_bytes = 0.0;

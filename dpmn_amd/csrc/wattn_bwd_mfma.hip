@@ -279,11 +279,7 @@ int launch(const float* q, const float* kv, const float* tbl, const float* dout,
            int W, int C, int g, int shift, float p_drop, unsigned long long seed, hipStream_t st, int part_mode) {
   constexpr int N = WS * WS, NW = N / 32, LDR = D + 4, TBL = (2 * WS - 1) * (2 * WS - 1), TB4 = (TBL + 3) & ~3;
   const size_t smem = (size_t)(TB4 + 2 * N * LDR + NW * TB4 + 3 * N) * 4 + 2 * N * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_window_attn_bwd_mfma<WS, D, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  dpmn_lds_optin<k_window_attn_bwd_mfma<WS, D, DROP>>(smem);
   const long blocks = (long)B * (H * W / N) * 2;
   // per (window, head): S and dP twice, dQ, dK, dV = 7 products of 2 N^2 D FLOPs; q, k, v, dO in, dq, dk, dv out
   ProfScope prof(PT_WATTN_BWD, st, 7.0 * 2.0 * N * D * 2 * (double)B * H * W, 4.0 * 7 * 2 * D * (double)B * H * W);
