@@ -7,7 +7,10 @@ Every function takes tensors of any float dtype and returns float64.
 The second half holds the references of the small BACKWARD kernels (csrc/backward_pgrm.hip, backward.hip, the tail of conv_bwd.hip):
 the gradient formulas written out by hand from the forward definition (plus torch.erf for the exact GELU), pinned in
 tests/test_ref64.py to torch.autograd of an independent forward in double.  They take `dtype` (default float64): the same formula
-evaluated with dtype=torch.float32 is the fp32 CPU evaluation that tests/test_gpu_small_backward.py derives its tolerances from."""
+evaluated with dtype=torch.float32 is the fp32 CPU evaluation that tests/test_gpu_small_backward.py derives its tolerances from.
+
+The last part holds the references of the convolution family (tests/test_gpu_conv_family.py): forward, transposed forward, weight
+gradient, data gradient and the BatchNorm statistics, as loops over the taps with one slice and one matmul / einsum per tap."""
 import math
 
 import torch
@@ -484,3 +487,148 @@ def gemm_tn(dy, x, dtype=torch.float64):
     """dW = dy^T x, db = column sums of dy: the nn.Linear weight / bias gradient for dy (M, N), x (M, K) -> ((N, K), (N,))"""
     dy, x = _c(dy, dtype), _c(x, dtype)
     return dy.t() @ x, dy.sum(0)
+
+
+# ====================================================================================================================
+# conv family (csrc/conv.hip, conv_body.h, conv_x3.hip, k_conv_wgrad of conv_bwd.hip, conv_wgrad_x3.hip): each written from the
+# operation's definition -- a loop over the taps, a strided slice and one matmul / einsum per tap; `dtype` as above.  Activations are
+# NHWC, weights in the nn.Conv2d (Cout, Cin, KH, KW) / nn.ConvTranspose2d (Cin, Cout, KH, KW) parameter layout.
+def _pair(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def conv_out_size(n, k, stride, pad, dil):
+    return (n + 2 * pad - dil * (k - 1) - 1) // stride + 1
+
+
+def conv_input(segs, affine=None, pro=0, dtype=torch.float64):
+    """What the conv multiplies: the channel concatenation of the NHWC segments, each through its own per-channel affine
+    (affine[i] = (scale, shift) or None), then the input activation `pro` -- all BEFORE the zero padding, which so stays exactly 0."""
+    xs = []
+    for i, s in enumerate(segs):
+        x = _c(s, dtype)
+        if affine is not None and affine[i] is not None:
+            x = x * _c(affine[i][0], dtype) + _c(affine[i][1], dtype)
+        xs.append(x)
+    return act(torch.cat(xs, 3), pro, dtype=dtype)
+
+
+def _padded(x, ph, pw):
+    B, H, W, C = x.shape
+    xp = x.new_zeros(B, H + 2 * ph, W + 2 * pw, C)
+    xp[:, ph:ph + H, pw:pw + W] = x
+    return xp
+
+
+def _tap(xp, ky, kx, Ho, Wo, stride, dil):
+    """the padded input at the pixels tap (ky, kx) meets: rows ky dil + oy stride, oy < Ho"""
+    return xp[:, ky * dil:ky * dil + (Ho - 1) * stride + 1:stride, kx * dil:kx * dil + (Wo - 1) * stride + 1:stride]
+
+
+def _corr(x, w, stride, pad, dil):
+    """y[b, oy, ox, co] = sum_{ky, kx, ci} x[b, oy stride + ky dil - pad_y, ox stride + kx dil - pad_x, ci] w[co, ci, ky, kx]"""
+    (ph, pw), (KH, KW) = _pair(pad), w.shape[2:]
+    Ho, Wo = conv_out_size(x.shape[1], KH, stride, ph, dil), conv_out_size(x.shape[2], KW, stride, pw, dil)
+    xp = _padded(x, ph, pw)
+    y = x.new_zeros(x.shape[0], Ho, Wo, w.shape[0])
+    for ky in range(KH):
+        for kx in range(KW):
+            y = y + _tap(xp, ky, kx, Ho, Wo, stride, dil) @ w[:, :, ky, kx].t()
+    return y
+
+
+def _corr_t(x, w, stride, pad):
+    """y[b, iy stride - pad + ky, ix stride - pad + kx, co] += x[b, iy, ix, ci] w[ci, co, ky, kx] (nn.ConvTranspose2d)"""
+    (ph, pw), (KH, KW) = _pair(pad), w.shape[2:]
+    B, H, W, _ = x.shape
+    full = x.new_zeros(B, (H - 1) * stride + KH, (W - 1) * stride + KW, w.shape[1])
+    for ky in range(KH):
+        for kx in range(KW):
+            full[:, ky:ky + (H - 1) * stride + 1:stride, kx:kx + (W - 1) * stride + 1:stride] += x @ w[:, :, ky, kx]
+    return full[:, ph:full.shape[1] - ph, pw:full.shape[2] - pw]
+
+
+def conv_epilogue(y, bias=None, epi=0, slope=0.0, res=None, pixel_shuffle=False, out_nchw=False, dtype=torch.float64):
+    """bias, activation, residual -- in that order -- then the store form: PixelShuffle(2) as NHWC (B, 2 H, 2 W, C / 4), out[b, 2 y + i,
+    2 x + j, c] = y[b, y, x, 4 c + 2 i + j], or NCHW."""
+    if bias is not None:
+        y = y + _c(bias, dtype)
+    y = act(y, epi, slope, dtype)
+    if res is not None:
+        y = y + _c(res, dtype)
+    if pixel_shuffle:
+        B, H, W, C = y.shape
+        y = y.reshape(B, H, W, C // 4, 2, 2).permute(0, 1, 4, 2, 5, 3).reshape(B, 2 * H, 2 * W, C // 4)
+    return y.permute(0, 3, 1, 2).contiguous() if out_nchw else y
+
+
+def conv2d(segs, w, bias=None, stride=1, pad=0, dil=1, pro=0, epi=0, slope=0.0, affine=None, res=None, pixel_shuffle=False,
+           out_nchw=False, dtype=torch.float64):
+    """nn.Conv2d over conv_input(segs, affine, pro), then conv_epilogue.  w (Cout, Cin, KH, KW)."""
+    y = _corr(conv_input(segs, affine, pro, dtype), _c(w, dtype), stride, pad, dil)
+    return conv_epilogue(y, bias, epi, slope, res, pixel_shuffle, out_nchw, dtype)
+
+
+def conv_transpose2d(segs, w, bias=None, stride=1, pad=0, pro=0, epi=0, slope=0.0, affine=None, res=None, dtype=torch.float64):
+    """nn.ConvTranspose2d(k, stride, pad) -- (3, 1, 1) and (4, 2, 1) here -- over conv_input, then conv_epilogue.  w (Cin, Cout, KH, KW)."""
+    y = _corr_t(conv_input(segs, affine, pro, dtype), _c(w, dtype), stride, pad)
+    return conv_epilogue(y, bias, epi, slope, res, dtype=dtype)
+
+
+def conv_stats(raw, dtype=torch.float64):
+    """per-channel sum and sum of squares of the raw (pre-activation, bias included) NHWC output -> ((C,), (C,))"""
+    raw = _c(raw, dtype)
+    return raw.sum((0, 1, 2)), (raw * raw).sum((0, 1, 2))
+
+
+def conv2d_wgrad(segs, dy, k, stride=1, pad=0, dil=1, pro=0, affine=None, dtype=torch.float64):
+    """dW[co, ci, ky, kx] = sum_{b, oy, ox} dy[b, oy, ox, co] X[b, oy stride + ky dil - pad, ox stride + kx dil - pad, ci] with
+    X = conv_input(segs, affine, pro): the weight gradient of conv2d for the cotangent dy (B, Ho, Wo, Cout) of the raw output."""
+    x, dy = conv_input(segs, affine, pro, dtype), _c(dy, dtype)
+    (KH, KW), (ph, pw) = _pair(k), _pair(pad)
+    Ho, Wo = dy.shape[1], dy.shape[2]
+    assert (Ho, Wo) == (conv_out_size(x.shape[1], KH, stride, ph, dil), conv_out_size(x.shape[2], KW, stride, pw, dil))
+    xp = _padded(x, ph, pw)
+    dw = x.new_zeros(dy.shape[3], x.shape[3], KH, KW)
+    for ky in range(KH):
+        for kx in range(KW):
+            dw[:, :, ky, kx] = torch.einsum("bhwo,bhwi->oi", dy, _tap(xp, ky, kx, Ho, Wo, stride, dil))
+    return dw
+
+
+def conv_transpose2d_wgrad(segs, dy, k, stride=1, pad=0, pro=0, affine=None, dtype=torch.float64):
+    """dW[ci, co, ky, kx] = sum_{b, iy, ix} X[b, iy, ix, ci] dy[b, iy stride - pad + ky, ix stride - pad + kx, co]: the weight gradient
+    of conv_transpose2d (terms outside dy's plane do not exist)."""
+    x, dy = conv_input(segs, affine, pro, dtype), _c(dy, dtype)
+    (KH, KW), (ph, pw) = _pair(k), _pair(pad)
+    B, H, W, _ = x.shape
+    full = _padded(dy, ph, pw)
+    assert full.shape[1] == (H - 1) * stride + KH and full.shape[2] == (W - 1) * stride + KW
+    dw = x.new_zeros(x.shape[3], dy.shape[3], KH, KW)
+    for ky in range(KH):
+        for kx in range(KW):
+            dw[:, :, ky, kx] = torch.einsum("bhwi,bhwo->io", x, full[:, ky:ky + (H - 1) * stride + 1:stride, kx:kx + (W - 1) * stride + 1:stride])
+    return dw
+
+
+def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, dil=1, c0=0, cs=None, dtype=torch.float64):
+    """The adjoint of conv2d with respect to the conv's input, channels [c0, c0 + cs): dX[b, oy stride + ky dil - pad, ox stride + kx dil
+    - pad, ci] += dy[b, oy, ox, co] w[co, c0 + ci, ky, kx] -> (B, Hin, Win, cs); input pixels no tap reaches keep 0."""
+    dy, w = _c(dy, dtype), _c(w, dtype)
+    cs = w.shape[1] - c0 if cs is None else cs
+    (ph, pw), (KH, KW), (Hin, Win) = _pair(pad), w.shape[2:], in_hw
+    Ho, Wo = dy.shape[1], dy.shape[2]
+    assert (Ho, Wo) == (conv_out_size(Hin, KH, stride, ph, dil), conv_out_size(Win, KW, stride, pw, dil))
+    dxp = dy.new_zeros(dy.shape[0], Hin + 2 * ph, Win + 2 * pw, cs)
+    for ky in range(KH):
+        for kx in range(KW):
+            dxp[:, ky * dil:ky * dil + (Ho - 1) * stride + 1:stride, kx * dil:kx * dil + (Wo - 1) * stride + 1:stride] += dy @ w[:, c0:c0 + cs, ky, kx]
+    return dxp[:, ph:ph + Hin, pw:pw + Win].contiguous()
+
+
+def conv_transpose2d_dgrad(dy, w, stride=1, pad=0, c0=0, cs=None, dtype=torch.float64):
+    """The adjoint of conv_transpose2d with respect to its input channels [c0, c0 + cs): dX[b, iy, ix, ci] = sum dy[b, iy stride - pad
+    + ky, ix stride - pad + kx, co] w[c0 + ci, co, ky, kx] -- the correlation of dy with w read as (out = Cin, in = Cout)."""
+    w = _c(w, dtype)
+    cs = w.shape[0] - c0 if cs is None else cs
+    return _corr(_c(dy, dtype), w[c0:c0 + cs], stride, pad, 1)

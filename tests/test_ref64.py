@@ -388,3 +388,100 @@ def test_gemm_tn_vs_autograd(M, N, K):
     dW, db = ref64.gemm_tn(dy, x)
     close(dW, gw, "gemm_tn dW")
     close(db, gb, "gemm_tn db")
+
+
+# ====================================================================================================================
+# conv family references: tiny ragged planes, stride 2, dilation 2, a padding larger than the kernel's radius, 1 .. 3 segments
+def _nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+CODE = ref64.ACT_CODES
+CONV_GEOM = [(3, 1, 1, 1), (3, 2, 1, 1), (3, 1, 2, 2), (4, 2, 3, 2), (4, 2, 1, 1), (3, 1, 3, 1), (1, 1, 0, 1), (9, 1, 4, 1), (2, 2, 3, 2)]
+
+
+def _conv_pin_case(k, segs_c, cout, B, H, W):
+    segs = [u("cs%d" % i, (B, H, W, c), -2, 2) for i, c in enumerate(segs_c)]
+    aff = [(u("csc%d" % i, (c,), 0.5, 1.5), u("csh%d" % i, (c,), -0.5, 0.5)) if i != 1 else None for i, c in enumerate(segs_c)]
+    w, b = u("cw", (cout, sum(segs_c), k, k), -0.3, 0.3), u("cb", (cout,))
+    return segs, aff, w, b
+
+
+def _torch_conv_input(segs, aff, pro):
+    xs = [s if a is None else s * a[0] + a[1] for s, a in zip(segs, aff)]
+    return _nchw(_torch_act(torch.cat(xs, 3), pro, 0.0))
+
+
+@pytest.mark.parametrize("k,stride,pad,dil", CONV_GEOM)
+@pytest.mark.parametrize("segs_c", [(5,), (3, 4), (2, 1, 3)])
+def test_conv2d_vs_f_conv2d(k, stride, pad, dil, segs_c):
+    B, H, W, cout = 2, 7, 11, 8
+    segs, aff, w, b = _conv_pin_case(k, segs_c, cout, B, H, W)
+    for pro, epi in (("none", "none"), ("leaky02", "mish"), ("relu", "prelu")):
+        raw = F.conv2d(_torch_conv_input(segs, aff, pro), w, b, stride, pad, dil)
+        res = u("cres", tuple(_nhwc(raw).shape))
+        want = _nhwc(_torch_act(raw, epi, 0.25)) + res
+        got = ref64.conv2d(segs, w, b, stride, pad, dil, CODE[pro], CODE[epi], 0.25, aff, res)
+        close(got, want, "conv2d %s %s" % (pro, epi))
+    close(ref64.conv2d(segs, w, None, stride, pad, dil), _nhwc(F.conv2d(_nchw(torch.cat(segs, 3)), w, None, stride, pad, dil)), "conv2d plain")
+    raw = F.conv2d(_nchw(torch.cat(segs, 3)), w, b, stride, pad, dil)
+    close(ref64.conv2d(segs, w, b, stride, pad, dil, out_nchw=True), raw.contiguous(), "conv2d NCHW")
+    close(ref64.conv2d(segs, w, b, stride, pad, dil, epi=CODE["relu"], pixel_shuffle=True), _nhwc(F.pixel_shuffle(F.relu(raw), 2)), "conv2d pixel shuffle")
+    s, q = ref64.conv_stats(_nhwc(raw))
+    close(s, raw.sum((0, 2, 3)), "stats sum")
+    close(q, (raw * raw).sum((0, 2, 3)), "stats sum of squares")
+
+
+def test_conv2d_zero_padding_stays_zero_under_the_affine():
+    """a shift would otherwise leak into the border: the affine and the activation come BEFORE the padding"""
+    x, w = torch.zeros(1, 3, 3, 1, dtype=torch.float64), torch.ones(1, 1, 3, 3, dtype=torch.float64)
+    got = ref64.conv2d([x], w, None, 1, 1, 1, affine=[(torch.ones(1), torch.ones(1))])
+    assert got.reshape(3, 3).tolist() == [[4.0, 6.0, 4.0], [6.0, 9.0, 6.0], [4.0, 6.0, 4.0]]
+
+
+@pytest.mark.parametrize("k,stride,pad", [(3, 1, 1), (4, 2, 1)])
+@pytest.mark.parametrize("segs_c", [(5,), (2, 1, 3)])
+def test_conv_transpose2d_and_its_gradients_vs_autograd(k, stride, pad, segs_c):
+    B, H, W, cout = 2, 3, 5, 6
+    segs, aff, _, b = _conv_pin_case(k, segs_c, cout, B, H, W)
+    w = leaf("ctw", (sum(segs_c), cout, k, k), -0.3, 0.3)
+    xin = _torch_conv_input(segs, aff, "relu").requires_grad_(True)
+    raw = F.conv_transpose2d(xin, w, b, stride, pad)
+    dy = u("ctdy", tuple(_nhwc(raw).shape))
+    close(ref64.conv_transpose2d(segs, w, b, stride, pad, CODE["relu"], CODE["tanh"], affine=aff), _nhwc(torch.tanh(raw)).detach(), "conv_transpose2d")
+    gx, gw = torch.autograd.grad(raw, (xin, w), _nchw(dy))
+    close(ref64.conv_transpose2d_wgrad(segs, dy, k, stride, pad, CODE["relu"], aff), gw, "conv_transpose2d_wgrad")
+    close(ref64.conv_transpose2d_dgrad(dy, w, stride, pad), _nhwc(gx), "conv_transpose2d_dgrad")
+    c0, cs = 1, sum(segs_c) - 2
+    close(ref64.conv_transpose2d_dgrad(dy, w, stride, pad, c0, cs), _nhwc(gx)[..., c0:c0 + cs].contiguous(), "conv_transpose2d_dgrad slice")
+
+
+@pytest.mark.parametrize("k,stride,pad,dil", CONV_GEOM)
+@pytest.mark.parametrize("segs_c", [(5,), (2, 1, 3)])
+def test_conv2d_gradients_vs_autograd(k, stride, pad, dil, segs_c):
+    B, H, W, cout = 2, 7, 11, 4
+    segs, aff, _, b = _conv_pin_case(k, segs_c, cout, B, H, W)
+    w = leaf("gw", (cout, sum(segs_c), k, k), -0.3, 0.3)
+    xin = _torch_conv_input(segs, aff, "leaky001").requires_grad_(True)
+    raw = F.conv2d(xin, w, b, stride, pad, dil)
+    dy = u("gdy", tuple(_nhwc(raw).shape))
+    gx, gw = torch.autograd.grad(raw, (xin, w), _nchw(dy))
+    close(ref64.conv2d_wgrad(segs, dy, k, stride, pad, dil, CODE["leaky001"], aff), gw, "conv2d_wgrad")
+    close(ref64.conv2d_dgrad(dy, w, (H, W), stride, pad, dil), _nhwc(gx), "conv2d_dgrad")
+    c0, cs = 1, sum(segs_c) - 2
+    close(ref64.conv2d_dgrad(dy, w, (H, W), stride, pad, dil, c0, cs), _nhwc(gx)[..., c0:c0 + cs].contiguous(), "conv2d_dgrad slice")
+
+
+def test_conv_references_fp32_evaluation():
+    """dtype=float32 evaluates the same formulas in fp32 (the yardstick of the continuous-kind tolerances)"""
+    segs, aff, w, b = _conv_pin_case(3, (3, 4), 8, 2, 5, 6)
+    pro, epi = CODE["leaky02"], CODE["mish"]
+    y64, y32 = ref64.conv2d(segs, w, b, 1, 1, 1, pro, epi, affine=aff), ref64.conv2d(segs, w, b, 1, 1, 1, pro, epi, affine=aff, dtype=torch.float32)
+    assert y32.dtype == torch.float32 and 0 < float((y32.double() - y64).abs().max()) < 1e-5
+    dy = u("fdy", tuple(y64.shape))
+    g32 = ref64.conv2d_wgrad(segs, dy, 3, 1, 1, 1, pro, aff, dtype=torch.float32)
+    assert g32.dtype == torch.float32 and float((g32.double() - ref64.conv2d_wgrad(segs, dy, 3, 1, 1, 1, pro, aff)).abs().max()) < 1e-4
