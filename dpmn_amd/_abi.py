@@ -291,6 +291,8 @@ SIGNATURES = {
     "dpmn_degrade_noise_f32": (_i, [_u64, fp, _l, _i, _i, fp, fp]),
     "dpmn_jpeg_roundtrip_workspace_bytes": (_sz, [_i, _i, _i]),
     "dpmn_jpeg_roundtrip_u8": (_i, [fp, fp, fp, _i, _i, _i, fp, _sz, fp]),
+    "dpmn_psf_blur_ragged_u8": (_i, [fp, _l, fp, fp, _i, fp, fp, _i, _i, fp, fp]),
+    "dpmn_cutblur_ragged_u8": (_i, [fp, _l, fp, _i, _i, fp, fp]),
     "dpmn_render_words_u8": (_i, [fp, fp, fp, fp, fp, fp, fp, fp, _i, fp, _l, _i, _i, _i, _i, fp, fp, fp, fp, fp]),
     "dpmn_resize_windows_workspace_bytes": (_sz, [_l, _l, _i]),
     "dpmn_resize_windows_u8": (_i, [fp, _l, fp, _i, fp, _l, fp, _i, _l, _i, fp, _i, _i, fp, _sz, fp]),

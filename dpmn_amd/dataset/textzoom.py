@@ -128,12 +128,16 @@ class alignCollate_realWTLAMask(object):
     reference's cutblur).  The random draws happen in sr_batches, in the main process, not in the loader's workers.
     jpeg=(lo, hi, prob) (ours, needs degrade): with probability prob a synthesised LR image, after its resize, goes through a JPEG of a
     quality drawn from lo .. hi (ops.jpeg_roundtrip_u8; the reference's JPEG_compress, dataset.py:559, fixes 40).
+    psf=(kinds, prob, frac) (ours, needs degrade; main.py --psf_blur): with probability prob the HR pixels an LR image is synthesised
+    from are first blurred by a random point-spread function of one of `kinds` (motion, disk, aniso; utils/psf.py) whose radius is
+    drawn up to frac of the image's height (ops.psf_blur_ragged_u8); the HR batch stays sharp.
     render=(words, atlases) (ours, needs degrade; main.py --train_words, dataset/words.py WordsHR): the batch holds no image at all --
     positions 0 and 2 are None and `sr_batches` renders the HR images on the GPU (ops.render_words_u8) from the words and parameters
     it draws per batch; `render` is then True and `words` / `atlases` carry the pair."""
 
     def __init__(self, imgH=64, imgW=256, down_sample_scale=4, keep_ratio=False, min_ratio=1, mask=False, alphabet=53, train=True,
-                 y_domain=False, gpu_finish=False, gpu_resize=False, degrade=False, cutblur=False, jpeg=None, render=None):
+                 y_domain=False, gpu_finish=False, gpu_resize=False, degrade=False, cutblur=False, jpeg=None, render=None,
+                 psf=None):
         if degrade and not gpu_resize:
             raise ValueError("alignCollate_realWTLAMask: degrade=True needs gpu_resize=True (the LR images are made on the GPU from the "
                              "packed HR pixels)")
@@ -150,6 +154,19 @@ class alignCollate_realWTLAMask(object):
                                  % (jpeg,))
             jpeg = (int(lo), int(hi), float(prob))
         self.jpeg = jpeg
+        if psf is not None and not degrade:
+            raise ValueError("alignCollate_realWTLAMask: psf=(kinds, prob, frac) needs degrade=True (the point-spread function blurs the "
+                             "HR pixels that the LR images are synthesised from on the GPU; paired TextZoom LR crops are used as they are)")
+        if psf is not None:
+            from ..utils.psf import KINDS
+            kinds, prob, frac = psf
+            kinds = tuple(kinds)
+            if not (kinds and all(k in KINDS for k in kinds) and len(set(kinds)) == len(kinds) and 0.0 <= float(prob) <= 1.0
+                    and 0.0 < float(frac) <= 1.0):
+                raise ValueError("alignCollate_realWTLAMask: psf=(kinds, prob, frac) needs distinct kinds of %s, 0 <= prob <= 1 and "
+                                 "0 < frac <= 1, got %r" % (", ".join(KINDS), psf))
+            psf = (kinds, float(prob), float(frac))
+        self.psf = psf
         if render is not None and not degrade:
             raise ValueError("alignCollate_realWTLAMask: render=(words, atlases) needs degrade=True (the rendered HR images have no LR "
                              "partner: it is synthesised on the GPU)")
@@ -220,23 +237,35 @@ def resize_on_gpu(pair, size, mask, device):
     return ops.collate_u8(ops.resize_ragged_u8(packed.to(device, non_blocking=True), meta, size[0], size[1]), mask)
 
 
-def degrade_on_gpu(pair, size, scale, mask, device, cutblur=False, rng=None, jpeg=None):
+def degrade_on_gpu(pair, size, scale, mask, device, cutblur=False, rng=None, jpeg=None, psf=None):
     """(packed, meta) of a degrade collate (the HR pixels; packed on the host, or already on `device`: a rendered batch of
     ops.render_words_u8) -> (images_hr (B, 3 + mask, H, W), images_lr (B, 3 + mask, H / scale,
     W / scale)) float on `device`, size = (H, W): one upload, the degradation of the ragged batch at the images' own sizes
     (ops.degrade_ragged_u8: the parameters of utils.degrade.draw_params and one 63-bit noise seed, both drawn from `rng`, Python's
     `random` by default), the two ragged resizes and the collate kernel.  jpeg = (lo, hi, prob): the resized LR batch, and only it,
     goes through ops.jpeg_roundtrip_u8 with the qualities of utils.jpeg.draw_jpeg, drawn from `rng` AFTER the draws above; with
-    jpeg=None not one more draw is made."""
+    jpeg=None not one more draw is made.  psf = (kinds, prob, frac) (main.py --psf_blur): the PSFs of utils.psf.draw_psf are drawn
+    from `rng` after the noise seed and BEFORE the JPEG qualities; the HR pack is blurred (ops.psf_blur_ragged_u8), the blurred pack
+    is degraded with cut_x and cut_side zeroed, and cutblur then copies its columns from the UNBLURRED pack (ops.cutblur_ragged_u8):
+    they stay the true HR pixels and the blur never reaches across the cut through the later filters' taps.  images_hr always comes
+    from the unblurred pack; with psf=None the draws and launches are exactly those without it."""
     import random
     from .. import ops
-    from ..utils.degrade import draw_params
+    from ..utils.degrade import draw_params, CUT_X, CUT_SIDE
     rng = random if rng is None else rng
     packed, meta = pair
     params = draw_params(meta.shape[0], cutblur=cutblur, hr_widths=[int(w) for w in meta[:, 2]], rng=rng)
     seed = rng.getrandbits(63)
     packed = packed.to(device, non_blocking=True)
-    low = ops.degrade_ragged_u8(packed, meta, params, seed=seed)
+    if psf is None:
+        low = ops.degrade_ragged_u8(packed, meta, params, seed=seed)
+    else:
+        from ..utils.psf import draw_psf
+        taps = draw_psf(meta.shape[0], psf[0], psf[1], psf[2], [int(h) for h in meta[:, 1]], rng=rng)
+        uncut = params.copy()
+        uncut[:, [CUT_X, CUT_SIDE]] = 0
+        low = ops.degrade_ragged_u8(ops.psf_blur_ragged_u8(packed, meta, taps), meta, uncut, seed=seed)
+        low = ops.cutblur_ragged_u8(low, packed, meta, params)
     H, W = size
     low = ops.resize_ragged_u8(low, meta, H // scale, W // scale)
     if jpeg is not None:
@@ -279,7 +308,7 @@ def sr_batches(loader, device=None, mask=None, size=None):
             rng = random.Random(pass_key + j)
             labels, cls, lens, params = draw_render(col.words, col.atlases.n_fonts, rng, n=len(labels))
             hr, lr = degrade_on_gpu(ops.render_words_u8(cls, lens, params, col.atlases, device=device), (H, W), scale, mask, device,
-                                    cutblur=col.cutblur, rng=rng, jpeg=getattr(col, "jpeg", None))
+                                    cutblur=col.cutblur, rng=rng, jpeg=getattr(col, "jpeg", None), psf=getattr(col, "psf", None))
         elif isinstance(hr, (tuple, list)):
             if size is None:
                 if not hasattr(col, "imgH"):
@@ -289,7 +318,7 @@ def sr_batches(loader, device=None, mask=None, size=None):
             H, W, scale = size
             if degrade:
                 hr, lr = degrade_on_gpu(hr, (H, W), scale, mask, device, cutblur=col.cutblur, rng=random.Random(pass_key + j),
-                                            jpeg=getattr(col, "jpeg", None))
+                                            jpeg=getattr(col, "jpeg", None), psf=getattr(col, "psf", None))
             else:
                 hr, lr = resize_on_gpu(hr, (H, W), mask, device), resize_on_gpu(lr, (H // scale, W // scale), mask, device)
         elif hr.dtype == torch.uint8:

@@ -18,6 +18,7 @@ from ..model import pgrm, cmm, tsrn, tatt, tbsrn
 from ..model.native import frozen as _frozen
 from ..utils import ssim_psnr
 from ..utils.jpeg import jpeg_setting
+from ..utils.psf import psf_setting
 
 
 def parse_list(s):
@@ -47,10 +48,12 @@ def _val_weights(config, key, path, what):
 # holds tensors and plain Python values only, so it loads with torch.load(weights_only=True).
 TRAIN_STATE_VERSION = 1
 FINGERPRINT_FIELDS = ("arch", "stu_iter_b1", "stu_iter_b2", "sr_share", "patch_size", "embed_dim", "depths", "num_heads", "window_size",
-                      "window_num", "mlp_ratio", "height", "width", "manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema", "train_words")
-# booleans, jpeg_degrade: None or [lo, hi, prob], ema: None or the decay of the averaged weights, and train_words: None or the dict of
+                      "window_num", "mlp_ratio", "height", "width", "manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema", "train_words",
+                      "psf_blur")
+# booleans, jpeg_degrade: None or [lo, hi, prob], psf_blur: None or [kinds, prob, frac] of utils.psf.psf_setting, ema: None or the decay
+# of the averaged weights, and train_words: None or the dict of
 # utils.render.words_setting (crc32 of the word list, sorted font names, epoch size); a state written before they existed has them off
-DATA_FIELDS = ("manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema", "train_words")
+DATA_FIELDS = ("manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema", "train_words", "psf_blur")
 
 
 def state_fingerprint(args, config, ema=None, train_words=None):
@@ -67,6 +70,8 @@ def state_fingerprint(args, config, ema=None, train_words=None):
     fp["train_hr_dir"] = bool(getattr(args, "train_hr_dir", None))
     jpeg = jpeg_setting(args)
     fp["jpeg_degrade"] = None if jpeg is None else list(jpeg)
+    psf = psf_setting(args)
+    fp["psf_blur"] = None if psf is None else [list(psf[0]), psf[1], psf[2]]
     # the averaged weights are part of the trainer's state: a run with them only continues a run that kept them, at the same decay
     fp["ema"] = None if ema is None else float(ema)
     # the word list, fonts and epoch size decide which HR images a step sees: a run rendered from words only continues its like
@@ -86,7 +91,7 @@ def _data_field(v):
         return None
     if isinstance(v, dict):
         return sorted((k, list(x) if isinstance(x, (list, tuple)) else x) for k, x in v.items())
-    return v if isinstance(v, (bool, float)) else list(v)
+    return v if isinstance(v, (bool, float)) else [list(x) if isinstance(x, (list, tuple)) else x for x in v]
 
 
 def check_fingerprint(saved, current, path=""):
@@ -184,7 +189,7 @@ class TextBase(object):
 
     # ------------------------------------------------------------------ data (base.py:85-125)
     def _loader(self, dirs, test, shuffle, drop_last, shard=False, gpu_finish=True, gpu_resize=False, degrade=False, cutblur=False,
-                hr_dir=None, jpeg=None, words=None):
+                hr_dir=None, jpeg=None, words=None, psf=None):
         """shard=True (training under torch.distributed): every rank walks its own 1/world of a per-epoch permutation
         (DistributedSampler, call `self.train_sampler.set_epoch(epoch)`) with batch_size // world samples per step, so the
         GLOBAL batch stays config.TRAIN.batch_size at the configured learning rate -- nn.DataParallel's scatter of one batch
@@ -195,7 +200,9 @@ class TextBase(object):
         from the HR images on the GPU (ops.degrade_ragged_u8 in sr_batches; cutblur=True: with cutblur), which needs gpu_finish and
         turns gpu_resize on.  hr_dir (--train_hr_dir): a folder of HR images instead of the LMDBs of `dirs` (dataset/folder.py
         FolderHR), always degraded.  jpeg=(lo, hi, prob) (--jpeg_degrade / --jpeg_prob; with degrade, training data only): JPEG
-        artefacts on the synthesised LR images (ops.jpeg_roundtrip_u8 in sr_batches).  words=(words, atlases, epoch size)
+        artefacts on the synthesised LR images (ops.jpeg_roundtrip_u8 in sr_batches).  psf=(kinds, prob, frac) (--psf_blur / --psf_prob /
+        --psf_radius; with degrade, training data only): a random point-spread function on the HR pixels that the LR images are synthesised
+        from (ops.psf_blur_ragged_u8 in sr_batches).  words=(words, atlases, epoch size)
         (--train_words): no image data at all -- dataset/words.py WordsHR, the HR images are rendered on the GPU by sr_batches
         (ops.render_words_u8), always degraded."""
         from ..dataset import textzoom as tz
@@ -226,7 +233,7 @@ class TextBase(object):
             collate_fn=tz.alignCollate_realWTLAMask(imgH=cfg.height, imgW=cfg.width, down_sample_scale=cfg.down_sample_scale, mask=self.mask,
                                                     gpu_finish=gpu_finish,      # True: ToTensor + mask channel on the GPU by sr_batches
                                                     gpu_resize=gpu_finish and (gpu_resize or degrade or bool(getattr(self.args, "gpu_resize", False))),
-                                                    degrade=degrade, cutblur=cutblur, jpeg=jpeg,
+                                                    degrade=degrade, cutblur=cutblur, jpeg=jpeg, psf=psf,
                                                     render=(words[0], words[1]) if words else None))
         # (dataset/textzoom.py; uint8 pixels in the batch); False: the reference's float (B, 3 + mask, H, W) tensors for consumers that
         # iterate the loader themselves
@@ -240,16 +247,18 @@ class TextBase(object):
         cfg = self.config.TRAIN
         degrade, cutblur = degrade_flags(self.args)
         hr_dir = getattr(self.args, "train_hr_dir", None)
-        jpeg = jpeg_setting(self.args)
+        jpeg, psf = jpeg_setting(self.args), psf_setting(self.args)
         if train_words is not None:
             if hr_dir:
                 raise ValueError("dpmn_amd: train_words and train_hr_dir are two sources of the HR images; give one")
-            return self._loader([], False, True, True, shard=True, degrade=True, cutblur=cutblur, jpeg=jpeg, words=tuple(train_words))
+            return self._loader([], False, True, True, shard=True, degrade=True, cutblur=cutblur, jpeg=jpeg, words=tuple(train_words),
+                                psf=psf)
         if hr_dir:
-            return self._loader([], False, True, True, shard=True, degrade=True, cutblur=cutblur, hr_dir=hr_dir, jpeg=jpeg)
+            return self._loader([], False, True, True, shard=True, degrade=True, cutblur=cutblur, hr_dir=hr_dir, jpeg=jpeg, psf=psf)
         if not isinstance(cfg.train_data_dir, list):
             raise TypeError('check trainRoot')
-        return self._loader(cfg.train_data_dir, False, True, True, shard=True, degrade=degrade, cutblur=cutblur, jpeg=jpeg)
+        return self._loader(cfg.train_data_dir, False, True, True, shard=True, degrade=degrade, cutblur=cutblur, jpeg=jpeg,
+                            psf=psf)
 
     def get_val_data(self):
         pairs = [self.get_test_data(d) for d in self.config.TRAIN.VAL.val_data_dir]

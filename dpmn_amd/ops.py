@@ -302,7 +302,7 @@ def resize_ragged_u8(packed, meta, H, W):
     return out
 
 
-DEGRADE_TILE = 32      # csrc/degrade.hip DG_TILE
+DEGRADE_TILE = 32      # csrc/degrade.hip DG_TILE, csrc/psf.hip PSF_TILE
 
 
 def _degrade_plan(packed, meta, what):
@@ -365,6 +365,77 @@ def degrade_noise(seed, meta, device=None):
     check(lib.dpmn_degrade_noise_f32(int(seed) & (2 ** 64 - 1), d.data_ptr(), nbytes, m.shape[0],
                                      int((m[:, 1] * m[:, 2]).max()), out.data_ptr(), stream()))
     return out
+
+
+def _psf_tables(taps_per_image, B):
+    """Checks of psf_blur_ragged_u8's PSFs -> (psf (B, 3) int32 [first tap, taps, R], taps (total, 3) int32)."""
+    import numpy as np
+    from .utils.psf import MAX_RADIUS, MAX_TAPS, ONE
+    if torch.is_tensor(taps_per_image) or isinstance(taps_per_image, np.ndarray) or len(taps_per_image) != B:
+        raise _abi.DpmnError("psf_blur_ragged_u8: taps_per_image must be a list of %d tap arrays, one per image" % B)
+    arrays = [t if isinstance(t, np.ndarray) else np.asarray(t) for t in taps_per_image]
+    for i, t in enumerate(arrays):
+        if t.ndim != 2 or t.shape[1] != 3 or t.dtype.kind not in "iu" or not (1 <= t.shape[0] <= MAX_TAPS):
+            raise _abi.DpmnError("psf_blur_ragged_u8: the PSF of image %d must be an integer (n, 3) array of (dy, dx, q), 1 <= n <= %d"
+                                 % (i, MAX_TAPS))
+    # every other check on the concatenated list: one pass over all taps, not one per image
+    flat = np.concatenate(arrays, axis=0).astype(np.int64)
+    psf = np.empty((B, 3), np.int32)
+    psf[:, 1] = [t.shape[0] for t in arrays]
+    psf[:, 0] = np.cumsum(psf[:, 1]) - psf[:, 1]
+    first = psf[:, 0].astype(np.int64)
+    R = np.maximum.reduceat(np.abs(flat[:, :2]).max(axis=1), first)
+    if R.max() > MAX_RADIUS:
+        raise _abi.DpmnError("psf_blur_ragged_u8: the PSF of image %d has a tap with |dy| or |dx| above %d"
+                             % (int(np.argmax(R > MAX_RADIUS)), MAX_RADIUS))
+    bad = (np.minimum.reduceat(flat[:, 2], first) <= 0) | (np.add.reduceat(flat[:, 2], first) != ONE)
+    if bad.any():
+        raise _abi.DpmnError("psf_blur_ragged_u8: the PSF of image %d needs every q > 0 and sum q = %d exactly" % (int(np.argmax(bad)), ONE))
+    psf[:, 2] = R
+    return psf, np.ascontiguousarray(flat, dtype=np.int32)
+
+
+def psf_blur_ragged_u8(packed, meta, taps_per_image):
+    """A point-spread function per image of a ragged batch (csrc/psf.hip; main.py --psf_blur): packed = the device copy of
+    utils.resize.pack_ragged's buffer, meta = its (B, 3) integer array, taps_per_image = B integer (n, 3) arrays of (dy, dx, q) as
+    utils.psf.psf_taps / draw_psf return them (|dy|, |dx| <= 10, q > 0, sum q = 65536, at most 441 taps; the identity leaves its image
+    as it is) -> the blurred images in the same packed layout (a new 1-D uint8 device tensor), per image byte for byte
+    utils.psf.psf_blur_u8.  One upload and one launch per call; integer arithmetic, the same bytes on every run and in every compute
+    mode."""
+    m, items, tiles = _degrade_plan(packed, meta, "psf_blur_ragged_u8")
+    psf, taps = _psf_tables(taps_per_image, m.shape[0])
+    d, d_items, d_tiles, d_psf, d_taps = _upload(packed.device, items, tiles, psf, taps)
+    out = torch.zeros_like(packed)      # (bytes of the buffer that belong to no image stay 0)
+    check(lib.dpmn_psf_blur_ragged_u8(packed.data_ptr(), packed.numel(), d_items, d_tiles, tiles.shape[0], d_psf, d_taps, taps.shape[0],
+                                      m.shape[0], out.data_ptr(), stream()))
+    return out
+
+
+def cutblur_ragged_u8(low, packed, meta, params):
+    """Cutblur as a step of its own (csrc/psf.hip): low = a synthesised LR batch in the packed layout of `packed` (the HR pixels), meta =
+    their (B, 3) integer array, params = (B, 16) rows of utils.degrade.draw_params, of which only cut_x and cut_side are read -> `low`
+    itself, where for every image with cut_side 1 (2) the columns >= (<) cut_x now are the HR image's (utils.psf.cutblur_u8).  One upload
+    and one launch; no launch at all when no image has a cut."""
+    import numpy as np
+    from .utils.degrade import CUT_X, CUT_SIDE
+    m = _ragged_batch(packed, meta, "cutblur_ragged_u8")
+    if (not torch.is_tensor(low) or low.device != packed.device or low.dtype != torch.uint8 or low.shape != packed.shape
+            or not low.is_contiguous() or low.data_ptr() == packed.data_ptr()):
+        raise _abi.DpmnError("cutblur_ragged_u8: low must be another contiguous uint8 tensor of packed's size on its device")
+    p = np.asarray(params.cpu().numpy() if torch.is_tensor(params) else params, dtype=np.float32)
+    B = m.shape[0]
+    if p.shape != (B, 16):
+        raise _abi.DpmnError("cutblur_ragged_u8: params must be (%d, 16), got %s" % (B, p.shape))
+    cut = p[:, [CUT_X, CUT_SIDE]]
+    if not (np.isfinite(cut).all() and (cut == np.floor(cut)).all() and np.isin(cut[:, 1], (0, 1, 2)).all() and (cut[:, 0] >= 0).all()
+            and (cut[:, 0] <= m[:, 2]).all()):
+        raise _abi.DpmnError("cutblur_ragged_u8: a params row is outside its domain (cut_side 0 / 1 / 2, cut_x an integer in 0 .. w)")
+    if not cut[:, 1].any():
+        return low
+    cuts = np.ascontiguousarray(np.concatenate((m, cut.astype(np.int64)), axis=1))
+    d, d_cuts = _upload(packed.device, cuts)
+    check(lib.dpmn_cutblur_ragged_u8(packed.data_ptr(), packed.numel(), d_cuts, B, int((m[:, 1] * m[:, 2]).max()), low.data_ptr(), stream()))
+    return low
 
 
 RENDER_TILE = (8, 128)      # csrc/render.hip RD_TILE_H, RD_TILE_W

@@ -513,6 +513,20 @@ int dpmn_degrade_noise_f32(unsigned long long seed, const long long* items, long
 size_t dpmn_jpeg_roundtrip_workspace_bytes(int B, int h, int w);
 int dpmn_jpeg_roundtrip_u8(const unsigned char* in, unsigned char* out, const int* quality, int B, int h, int w, void* workspace,
                            size_t workspace_bytes, dpmn_stream_t stream);
+/* A point-spread function per image (psf.hip; main.py --psf_blur): a RAGGED batch in the packed layout of dpmn_resize_ragged_u8 -> every
+ * image blurred with its own PSF at its own size, same layout, byte for byte utils/psf.py psf_blur_u8: per byte (2^15 + sum q *
+ * in[reflect101(y + dy), reflect101(x + dx)]) >> 16, integer arithmetic throughout.  items: device int64 (B, 4) [byte offset, h, w,
+ * first tile]; tiles: device int32 (n_tiles, 3) [image, tile row, tile column] over 32 x 32 tiles, image after image in row-major order;
+ * psf: device int32 (B, 3) [first tap, number of taps 1 .. 441, R = the largest |dy|, |dx| of the image's taps, 0 .. 10]; taps: device
+ * int32 (n_taps, 3) [dy, dx, q], q > 0, each image's q summing to 65536 (the identity is the one tap (0, 0, 65536)).  packed_out: the
+ * bytes that belong to no image are left as they are; not packed_in.  One launch, nothing synchronises. */
+int dpmn_psf_blur_ragged_u8(const unsigned char* packed_in, long packed_bytes, const long long* items, const int* tiles, int n_tiles,
+                            const int* psf, const int* taps, int n_taps, int B, unsigned char* packed_out, dpmn_stream_t stream);
+/* Cutblur as a step of its own (psf.hip; utils/psf.py cutblur_u8): for every image with cut_side 1 (2) the columns >= (<) cut_x of
+ * packed_low become those of packed_hr, same packed layout; cuts: device int64 (B, 5) [byte offset, h, w, cut_x, cut_side], any other
+ * cut_side leaves the image alone.  max_pixels: the largest h * w (sizes the launch). */
+int dpmn_cutblur_ragged_u8(const unsigned char* packed_hr, long packed_bytes, const long long* cuts, int B, int max_pixels,
+                           unsigned char* packed_low, dpmn_stream_t stream);
 /* HR text crops from strings (render.hip; main.py --train_words): B words laid out of a glyph atlas into a RAGGED batch written straight
  * into the packed layout of dpmn_resize_ragged_u8 (the images back to back, HWC), byte for byte utils/render.py render_u8 -- scaled
  * advances, shear, integer bilinear alpha (Q16), flat or gradient background with grain, integer blend.  classes: device int32 (B, 25),

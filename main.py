@@ -17,7 +17,7 @@ strip by strip on the GPU (polygon regions are written as files; `--demo_paste_p
 the photo, strip by strip, in box-file order with the quadrilaterals).  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--ema DECAY` keeps an exponential moving average of the trained weights; the
 validation passes score it and the best-model checkpoints hold it.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
-(`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB); `--train_words FILE` trains from a word list alone: the HR images are rendered on the GPU (`--train_words_fonts DIR`: in the fonts of a directory; `--train_words_epoch N`: samples per epoch).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
+(`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image; `--psf_blur KINDS`: with a random motion, defocus or elongated-Gaussian blur of the HR pixels first); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB); `--train_words FILE` trains from a word list alone: the HR images are rendered on the GPU (`--train_words_fonts DIR`: in the fonts of a directory; `--train_words_epoch N`: samples per epoch).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
 per GPU, RCCL gradient all-reduce; replaces nn.DataParallel)."""
 import argparse
 import csv
@@ -143,6 +143,14 @@ def main(config, args):
     if jpeg is not None and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None) or words_on):
         raise SystemExit("main.py: --jpeg_degrade needs --manmade_degrade (or --train_hr_dir): the JPEG artefacts are put on the "
                          "synthesised LR images")
+    from dpmn_amd.utils.psf import psf_setting
+    try:
+        psf = psf_setting(args)
+    except ValueError as e:
+        raise SystemExit("main.py: %s" % e)
+    if psf is not None and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None) or words_on):
+        raise SystemExit("main.py: --psf_blur needs --manmade_degrade (or --train_hr_dir or --train_words): the point-spread function "
+                         "blurs the HR pixels that the LR images are synthesised from")
     if getattr(args, "demo_tile", False) and not getattr(args, "demo_dir", None):
         raise SystemExit("main.py: --demo_tile needs --demo_dir: it super-resolves the wide images of that folder in overlapping windows")
     if getattr(args, "demo_boxes", None) and not getattr(args, "demo_dir", None):
@@ -381,6 +389,14 @@ if __name__ == '__main__':
                              '(1 .. 100, for example 30,95; 40,40 is the fixed quality of the reference\'s helper) with probability '
                              '--jpeg_prob')
     parser.add_argument('--jpeg_prob', type=float, default=0.5, help='with --jpeg_degrade: the probability of the JPEG stage per image')
+    parser.add_argument('--psf_blur', type=str, default=None, metavar='KINDS',
+                        help='with --manmade_degrade: the HR pixels a synthesised LR image is made from are first blurred by a random '
+                             'point-spread function, a comma list of motion (camera shake: a line at a random angle), disk (defocus) and '
+                             'aniso (an elongated Gaussian), with probability --psf_prob')
+    parser.add_argument('--psf_prob', type=float, default=0.5, help='with --psf_blur: the probability of the blur per image')
+    parser.add_argument('--psf_radius', type=float, default=0.12,
+                        help='with --psf_blur: the largest radius of the point-spread function as a fraction of the image height '
+                             '(drawn from 1 pixel up to it, 10 pixels at the most)')
     parser.add_argument('--train_hr_dir', type=str, default=None,
                         help='train from this folder of HR images (optional labels.txt: file name<TAB>word); implies --manmade_degrade, '
                              'needs no LMDB')
