@@ -262,6 +262,10 @@ SIGNATURES = {
     "dpmn_bilstm_f32": (_i, [fp, fp, fp, fp, _i, _i, _i, fp]),
     "dpmn_ctc_greedy_i32": (_i, [fp, _i, _i, fp, fp, _i, _i, fp]),
     "dpmn_crnn_label_vecs_f32": (_i, [fp, _i, _i, fp, _i, _i, fp]),
+    "dpmn_ctc_lexicon_workspace_bytes": (_sz, [_i, _i]),
+    "dpmn_ctc_lexicon_f32": (_i, [fp, _i, _i, fp, _i, fp, fp, fp, _i, _i, fp]),
+    "dpmn_edit_lexicon_workspace_bytes": (_sz, [_i, _i]),
+    "dpmn_edit_lexicon_i32": (_i, [fp, fp, _i, fp, fp, fp, _i, fp]),
     "dpmn_aster_prep_f32": (_i, [fp, _l, fp, fp, _i, _i, _i, _i, _i, fp]),
     "dpmn_subsample_nhwc_f32": (_i, [fp, fp, _i, _i, _i, _i, _i, _i, fp]),
     "dpmn_aster_beam_workspace_bytes": (_sz, [_i, _i]),

@@ -222,7 +222,7 @@ class TextSR(base.TextBase):
 
     @torch.no_grad()
     def eval(self, model_list, val_loader, index=0, rec=None, aster_info=None, rec_list=None, model_psn=None, crnn_psn=None,
-             text_prior_fn=None, display=False, display_failures=False):
+             text_prior_fn=None, display=False, display_failures=False, lexicon=None):
         """super_resolution.py:340-513.  PSNR/SSIM always; recognition accuracy (lines 453-493) only when `rec` reads the SR images
         and the loader yields label strings as a 4th item: `rec` is the native CRNN (TextBase.CRNN_init, --rec crnn: its `read`), the
         native ASTER (TextBase.Aster_init, --rec aster: its `read`), the native MORAN (TextBase.MORAN_init, --rec moran: its `read`, the
@@ -233,15 +233,21 @@ class TextSR(base.TextBase):
         (one extra recogniser call, on that batch's LR images; empty strings without a recogniser or labels).  display_failures=True
         (test(display=True); the call the reference has commented out at line 762): test_display on EVERY batch -- one more
         recogniser call per batch for the LR strings -- and their total under the key 'visualized'.  With both off nothing is
-        written, no extra recogniser call is made and the returned dict has the keys it always had."""
+        written, no extra recogniser call is made and the returned dict has the keys it always had.
+        lexicon (ours; an ops.Lexicon, main.py --rec_lexicon): the SR images are also read under the lexicon -- a native recogniser's
+        read_lexicon (the CRNN: the word of the highest CTC likelihood, in the same forward pass; ASTER / MORAN: the word nearest to
+        the greedy string), a plain callable's strings through ops.edit_read -- and the dict gains 'accuracy_lexicon', counted like
+        'accuracy' (None when nothing was labelled or there is no recogniser).  'accuracy' and everything else are what they are
+        without it."""
         from ..utils.util import str_filt
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
+        lex_reader = self._lexicon_reader(rec, reader, lexicon)
         for m in model_list:
             m.eval()
         fn = text_prior_fn or self.default_text_prior()
         psnr, ssim, n = [], [], 0
-        n_correct, n_labelled = 0, 0
+        n_correct, n_labelled, n_correct_lex = 0, 0, 0
         last, visualized = None, 0      # display: (images_lr, sr, images_hr, LR strings | None, SR strings | None, labels | None) of the last batch
         # the batches of an evaluation pass are independent: two of them in flight (RefinePipeline).  The loop is software-pipelined:
         # batch i + 1 is prepared and SUBMITTED before this stream waits for batch i and queues its metrics -- a lane is ordered
@@ -256,7 +262,7 @@ class TextSR(base.TextBase):
             pipe = cached[1]
 
         def finish(sr, images_hr, labels, images_lr):
-            nonlocal n, n_correct, n_labelled, last, visualized
+            nonlocal n, n_correct, n_labelled, n_correct_lex, last, visualized
             if pipe is not None:
                 RefinePipeline.wait(sr)      # (the display kernels below read sr on this stream: behind the batch's lane)
             p, s = ops.psnr_ssim(sr, images_hr)
@@ -265,7 +271,12 @@ class TextSR(base.TextBase):
             n += sr.shape[0]
             preds_sr = preds_lr = None
             if reader is not None and labels is not None:      # (the host sync of the read: batch i + 1 is already submitted)
-                preds_sr = reader(sr[:, :3])
+                if lex_reader is not None:
+                    preds_sr, preds_lex, _ = lex_reader(sr[:, :3])
+                    for pred, target in zip(preds_lex, labels):
+                        n_correct_lex += int(pred == str_filt(target, 'lower'))
+                else:
+                    preds_sr = reader(sr[:, :3])
                 for pred, target in zip(preds_sr, labels):
                     n_correct += int(pred == str_filt(target, 'lower'))
                 n_labelled += len(labels)
@@ -305,11 +316,30 @@ class TextSR(base.TextBase):
         res = {'psnr': psnr, 'ssim': ssim, 'accuracy': accuracy, 'psnr_avg': round(psnr_avg, 6), 'ssim_avg': round(ssim_avg, 6)}
         if display_failures:
             res['visualized'] = visualized
+        if lexicon is not None:
+            res['accuracy_lexicon'] = round(n_correct_lex / n_labelled, 4) if n_labelled and lex_reader is not None else None
         return res
+
+    @staticmethod
+    def _lexicon_reader(rec, reader, lexicon):
+        """eval / demo: images -> (greedy strings, the lexicon's strings, scores) for a recogniser resolved to `reader`, or None
+        without a lexicon or a recogniser.  A native recogniser brings its own read_lexicon; any other callable's strings take the
+        edit protocol (ops.edit_read)."""
+        if lexicon is None or reader is None:
+            return None
+        if hasattr(rec, "read_lexicon"):
+            return lambda images: rec.read_lexicon(images, lexicon)
+        if lexicon.mode == "score":
+            raise ValueError("the CTC score protocol of a lexicon needs a CTC recogniser (NativeCRNN); a callable recogniser takes mode 'edit'")
+
+        def read(images):
+            strings = list(reader(images))
+            return (strings,) + ops.edit_read(strings, lexicon, images.device)
+        return read
 
     @torch.no_grad()
     def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None, boxes=False, paste=False,
-             feather=1.0, paste_polygons=False):
+             feather=1.0, paste_polygons=False, lexicon=None):
         """Super-resolve someone's own images (ours; main.py --demo_dir): batches yields (names, images_lr) as
         dataset.folder.folder_batches does.  Per batch `refine` (label_vecs from the frozen CRNN for tatt / tpgsr, as in eval), then
         save_image's quantisation on the GPU (ops.quantize_sr_u8), ONE device-to-host copy and one <stem>_sr.png per input under
@@ -342,9 +372,17 @@ class TextSR(base.TextBase):
         like any other, with or without tile.  With paste=True the polygons' SR regions are written as files but not pasted, unless
         paste_polygons=True (main.py --demo_paste_polygons; needs paste=True): every strip of a polygon's SR region then goes back into
         its piece of the enlarged photo by the inverse of the strip's bilinear map (utils/paste_poly.py), and quadrilaterals and
-        polygons are pasted from one list in box-file order (ops.paste_mixed_u8).  The region files and demo_result.csv do not change."""
+        polygons are pasted from one list in box-file order (ops.paste_mixed_u8).  The region files and demo_result.csv do not change.
+        lexicon (an ops.Lexicon, main.py --rec_lexicon; needs a recogniser, not with tile: a window is not a word): the SR image is
+        also read under the lexicon (as in eval) and every row and demo_result.csv gain the columns sr_lexicon, sr_lexicon_score after
+        sr_string: the lexicon's word and its CTC log-likelihood (the CRNN's score protocol) or its edit distance to sr_string."""
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
+        if lexicon is not None and tile:
+            raise ValueError("demo: a lexicon does not combine with tile=True (a window of a line is not a word)")
+        if lexicon is not None and reader is None:
+            raise ValueError("demo: a lexicon needs a recogniser")
+        lex_reader = self._lexicon_reader(rec, reader, lexicon)
         for m in model_list:
             m.eval()
         fn = text_prior_fn or self.default_text_prior()
@@ -356,13 +394,14 @@ class TextSR(base.TextBase):
             raise ValueError("demo: paste_polygons=True needs paste=True (the polygons are pasted into the photo that paste=True writes)")
         if boxes:
             labels = []
-            for names, pixels, preds_lr, preds_sr, photos in self._demo_regions(model_list, model_psn, batches, fn, reader, chunk, tile, labels,
-                                                                                 float(feather) if paste else None, bool(paste_polygons)):
-                self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken)
+            for names, pixels, preds_lr, preds_sr, photos, *lex in self._demo_regions(model_list, model_psn, batches, fn, reader, chunk, tile, labels,
+                                                                                       float(feather) if paste else None, bool(paste_polygons),
+                                                                                       lex_reader):
+                self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken, *lex)
                 self._demo_write(out_dir, [stem + "_photo.png" for stem, _ in photos], [a for _, a in photos], [''] * len(photos),
                                  [''] * len(photos), [], taken)
             # <stem>_<k>.png, lr, sr -> stem, k, label, lr, sr
-            rows = [r[0][:-4].rsplit("_", 1) + [label] + r[1:] for r, label in zip(rows, labels)]
+            rows = [r[0][:-4].rsplit("_", 1) + [label] + r[1:] for r, label in zip(rows, labels)]      # (+ the lexicon's two columns)
             batches = ()
         elif tile:
             for names, pixels, preds_lr, preds_sr, _ in self._demo_windows(model_list, model_psn, batches, fn, reader, chunk):
@@ -378,19 +417,26 @@ class TextSR(base.TextBase):
             pixels = ops.quantize_sr_u8(sr).cpu().numpy()
             blank = [''] * n
             preds_lr = reader(images_lr[:n, :3]) if reader is not None else blank
+            if lex_reader is not None:
+                preds_sr, *lex = lex_reader(sr[:, :3])
+                self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex)
+                continue
             preds_sr = reader(sr[:, :3]) if reader is not None else blank
             self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken)
         with open(os.path.join(out_dir, "demo_result.csv"), "w", newline="") as out:
             w = csv.writer(out)
-            w.writerow(["file", "box", "label", "lr_string", "sr_string"] if boxes else ["file", "lr_string", "sr_string"])
+            w.writerow((["file", "box", "label", "lr_string", "sr_string"] if boxes else ["file", "lr_string", "sr_string"])
+                       + (["sr_lexicon", "sr_lexicon_score"] if lexicon is not None else []))
             w.writerows(rows)
         return rows
 
     @staticmethod
-    def _demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken):
-        """demo: one <stem>_sr.png per image of a batch and its row."""
+    def _demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex=None):
+        """demo: one <stem>_sr.png per image of a batch and its row; lex: None, or (the lexicon's strings, their scores), two more
+        columns."""
         from PIL import Image
-        for name, a, s_lr, s_sr in zip(names, pixels, preds_lr, preds_sr):
+        more = [[str(w), "%.6g" % sc] for w, sc in zip(*lex)] if lex is not None else [[]] * len(names)
+        for name, a, s_lr, s_sr, extra in zip(names, pixels, preds_lr, preds_sr, more):
             out_name = os.path.splitext(name)[0] + "_sr.png"
             if out_name in taken:
                 out_name = name + "_sr.png"
@@ -398,13 +444,15 @@ class TextSR(base.TextBase):
                 out_name = "_" + out_name
             taken.add(out_name)
             Image.fromarray(a).save(os.path.join(out_dir, out_name))
-            rows.append([name, str(s_lr), str(s_sr)])
+            rows.append([name, str(s_lr), str(s_sr)] + extra)
 
-    def _demo_regions(self, model_list, model_psn, batches, fn, reader, chunk, tile, labels_out, feather=None, paste_polygons=False):
+    def _demo_regions(self, model_list, model_psn, batches, fn, reader, chunk, tile, labels_out, feather=None, paste_polygons=False,
+                      lex_reader=None):
         """demo(boxes=True): per batch of regions -> (names, one (H, W_r, 3) uint8 array per region, the LR reads, the SR reads, the
         pasted photos); the regions' labels are appended to labels_out.  tile: the batches carry a plan and go through _demo_windows.
         feather: None, or demo(paste=True)'s -- the batches then end with the photos item and the pasted photos are _demo_paste's list
-        (empty otherwise); paste_polygons: demo's."""
+        (empty otherwise); paste_polygons: demo's.  lex_reader (demo's lexicon; not with tile): the SR regions are read through it
+        and the tuple gets a sixth item, (the lexicon's strings, their scores)."""
         paste = feather is not None
         if tile:
             held = []
@@ -423,6 +471,7 @@ class TextSR(base.TextBase):
             labels_out.extend(labels)
             images_lr = images_lr.to(self.device)
             pixels, preds_lr, preds_sr, on_device = [], [], [], []
+            lex = ([], [])
             for lo in range(0, images_lr.shape[0], chunk):
                 x = images_lr[lo:lo + chunk]
                 n = x.shape[0]
@@ -435,7 +484,13 @@ class TextSR(base.TextBase):
                 if paste:
                     on_device.append(q)
                 preds_lr += list(reader(x[:n, :3])) if reader is not None else [''] * n
-                preds_sr += list(reader(sr[:, :3])) if reader is not None else [''] * n
+                if lex_reader is not None:
+                    got = lex_reader(sr[:, :3])
+                    preds_sr += list(got[0])
+                    lex[0].extend(got[1])
+                    lex[1].extend(got[2])
+                else:
+                    preds_sr += list(reader(sr[:, :3])) if reader is not None else [''] * n
             pasted = []
             if paste:
                 # the quantised regions of the batch, all H x W x 3: flat, they are pack_ragged's layout
@@ -443,6 +498,9 @@ class TextSR(base.TextBase):
                 R, H, W = q.shape[:3]
                 pasted = self._demo_paste(names, photos[0], q.reshape(-1), [(r * H * W * 3, H, W) for r in range(R)], feather,
                                           paste_polygons)
+            if lex_reader is not None:
+                yield names, [a for p in pixels for a in p], preds_lr, preds_sr, pasted, lex
+                continue
             yield names, [a for p in pixels for a in p], preds_lr, preds_sr, pasted
 
     def _demo_paste(self, names, photos, sr_packed, sr_meta, feather, paste_polygons=False):
@@ -1005,12 +1063,15 @@ class TextSR(base.TextBase):
     def _psn_crnn_path(self):
         return os.path.join(self.resume, "recognizer_best_crnn.pth") if self.resume and os.path.isdir(self.resume) else None
 
-    def test(self, loader=None, rec=None, display=False):
+    def test(self, loader=None, rec=None, display=False, lexicon=None):
         """super_resolution.py:515-775: PGRMs from model_best_{k}.pth, CMM from model_best_cmm.pth, PSN from model_{arch}.pth
         under --resume (all required: there is no evaluation of untrained weights).  display=True: the comparison images of the
-        last batch under <vis_dir>/0/ and those of every wrongly read image under <vis_dir>/display/ (their number: 'visualized')."""
+        last batch under <vis_dir>/0/ and those of every wrongly read image under <vis_dir>/display/ (their number: 'visualized').
+        lexicon: eval's (an ops.Lexicon: the dict gains 'accuracy_lexicon')."""
         models, psn = self.build_models(testing=True)
         if loader is None:
             raise RuntimeError("dpmn_amd: pass a loader of (images_hr, images_lr, label_vecs) batches: "
                                "dataset.textzoom.sr_batches(self.get_test_data(dir)[1], device) or dpmn_amd.utils.synth.synth_batch")
+        if lexicon is not None:
+            return self.eval(models, loader, 0, rec=rec, model_psn=psn, display=display, display_failures=display, lexicon=lexicon)
         return self.eval(models, loader, 0, rec=rec, model_psn=psn, display=display, display_failures=display)

@@ -350,3 +350,13 @@ class NativeASTER(PackedEval, ASTER):
         if info is None:
             raise ValueError("dpmn_amd NativeASTER.read: pass the AsterInfo of this vocabulary")
         return ids_to_strings(self.pred_rec(images).numpy(), info)
+
+    @torch.no_grad()
+    def read_lexicon(self, images, lex, info=None):
+        """-> (greedy strings, the lexicon's strings, distances): `read`'s strings, then per string the lexicon word at the least
+        edit distance (ops.edit_read: the strings packed and uploaded, dpmn_edit_lexicon_i32, one copy back).  An attention decoder
+        has no frame posteriors, so lex.mode 'score' is refused."""
+        if lex.mode == "score":
+            raise ValueError("dpmn_amd NativeASTER.read_lexicon: the CTC score protocol needs a CTC recogniser (--rec crnn); use mode 'edit'")
+        greedy = self.read(images, info)
+        return (greedy,) + ops.edit_read(greedy, lex, images.device)

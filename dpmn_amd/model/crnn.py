@@ -164,6 +164,25 @@ class NativeCRNN(PackedEval, CRNN):
         return decode_classes(h[:B * T].reshape(B, T), h[B * T:])
 
     @torch.no_grad()
+    def read_lexicon(self, images, lex):
+        """Open-vocabulary and lexicon-constrained reading in one forward pass (ours; ops.Lexicon) -> (greedy strings, the lexicon's
+        strings, scores).  The greedy strings are `read`'s.  Default / lex.mode 'score': dpmn_ctc_lexicon_f32 on the same logits
+        rows picks the word of the highest CTC log-likelihood -- the scores are those log-likelihoods ('' and -inf when no word fits
+        the T frames) -- and ONE device-to-host copy brings both results.  lex.mode 'edit': the word nearest to the greedy string
+        (ops.edit_read), the scores are the distances."""
+        self._check_eval()
+        if lex.mode == "edit":
+            greedy = self.read(images)
+            return (greedy,) + ops.edit_read(greedy, lex, images.device)
+        rows, B, T = self.logits_rows(self.prep(images), self._packs())
+        buf, _, _ = ops.ctc_greedy(rows, B, T, self.nclass, extra=2 * B)
+        ops.ctc_lexicon(rows, B, T, self.nclass, lex, out=buf[B * T + B:])
+        h = buf.cpu().numpy()
+        n = B * T + B
+        greedy = decode_classes(h[:B * T].reshape(B, T), h[B * T:n])
+        return greedy, lex.strings(h[n:n + B]), [float(v) for v in h[n + B:].view("float32")]
+
+    @torch.no_grad()
     def label_vecs(self, images_lr3):
         """super_resolution.py:165-169 on the native path: (B, 37, 1, T) softmax of the logits."""
         self._check_eval()

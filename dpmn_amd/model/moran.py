@@ -359,3 +359,13 @@ class NativeMORAN(PackedEval, MORAN):
         """Recognised strings of (B, >=3, H, W) images in [0, 1]: every stage on the current stream, then ONE device-to-host copy
         (the arg-max ids) and the cut at '$' on the host."""
         return moran_strings(self.pred_ids(images).cpu().numpy())
+
+    @torch.no_grad()
+    def read_lexicon(self, images, lex):
+        """-> (greedy strings, the lexicon's strings, distances): `read`'s strings, then per string the lexicon word at the least
+        edit distance (ops.edit_read: the strings packed and uploaded, dpmn_edit_lexicon_i32, one copy back).  An attention decoder
+        has no frame posteriors, so lex.mode 'score' is refused."""
+        if lex.mode == "score":
+            raise ValueError("dpmn_amd NativeMORAN.read_lexicon: the CTC score protocol needs a CTC recogniser (--rec crnn); use mode 'edit'")
+        greedy = self.read(images)
+        return (greedy,) + ops.edit_read(greedy, lex, images.device)

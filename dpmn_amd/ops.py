@@ -1491,14 +1491,15 @@ def bilstm(gx, w_hh, B, T):
     return out
 
 
-def ctc_greedy(logits, B, T, n_class):
+def ctc_greedy(logits, B, T, n_class, extra=0):
     """logits rows b*T + t (B*T, ld) -> one int32 buffer (B*T + B): cls (B, T) collapsed classes then length (B); returned as
-    (buffer, cls view, length view) so that the host reads both with one copy."""
+    (buffer, cls view, length view) so that the host reads both with one copy.  extra: that many more int32 at the end of the
+    buffer, for a caller that wants further results in the same copy (ctc_lexicon's `out`)."""
     if logits.dim() != 2 or logits.shape[0] != B * T or logits.shape[1] < n_class:
         raise _abi.DpmnError("ctc_greedy: logits rows (B*T, >= n_class) expected")
-    buf = torch.empty(B * T + B, dtype=torch.int32, device=logits.device)
+    buf = torch.empty(B * T + B + extra, dtype=torch.int32, device=logits.device)
     check(lib.dpmn_ctc_greedy_i32(dptr(logits), logits.shape[1], n_class, buf.data_ptr(), buf.data_ptr() + 4 * B * T, B, T, stream()))
-    return buf, buf[:B * T].view(B, T), buf[B * T:]
+    return buf, buf[:B * T].view(B, T), buf[B * T:B * T + B]
 
 
 def crnn_label_vecs(logits, B, T, n_class):
@@ -1508,6 +1509,116 @@ def crnn_label_vecs(logits, B, T, n_class):
     out = torch.empty(B, n_class, 1, T, device=logits.device)
     check(lib.dpmn_crnn_label_vecs_f32(dptr(logits), logits.shape[1], n_class, dptr(out), B, T, stream()))
     return out
+
+
+# ------------------------------------------------------------------------------ lexicon-constrained reading (csrc/lexicon.hip)
+class Lexicon:
+    """A word list for lexicon-constrained reading (utils/lexicon.py): `words` (distinct strings over `alphabet`, default the
+    CRNN's), `packed` their (L, 32) uint8 records.  The records are uploaded once per device and the kernels' workspace is kept per
+    (device, stream).  mode: None (the recogniser's own protocol: CTC score for the CRNN, edit distance for the others), 'score' or
+    'edit' (main.py --rec_lexicon_mode)."""
+
+    def __init__(self, words, alphabet=None, mode=None):
+        from .utils import lexicon as lx
+        if mode not in (None, "score", "edit"):
+            raise ValueError("Lexicon: mode is None, 'score' or 'edit', got %r" % (mode,))
+        self.words = list(words)
+        if not 1 <= len(self.words) <= lx.MAX_WORDS:
+            raise ValueError("Lexicon: 1 .. %d words are supported, got %d" % (lx.MAX_WORDS, len(self.words)))
+        self.alphabet = alphabet
+        self.packed = lx.pack_lexicon(self.words, alphabet)
+        self.max_class = int(self.packed[:, 1:].max())
+        self.mode = mode
+        self._dev, self._ws = {}, {}
+
+    @classmethod
+    def from_file(cls, path, voc_type="lower", mode=None):
+        from .utils import lexicon as lx
+        return cls(lx.load_lexicon(path, voc_type), mode=mode)
+
+    def __len__(self):
+        return len(self.words)
+
+    def device_words(self, device):
+        """The records on `device` (a flat uint8 tensor of 32 L bytes), uploaded on first use."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _abi.DpmnError("Lexicon: the lexicon kernels run on the GPU only (got %s); there is no CPU fallback" % device)
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.from_numpy(self.packed.reshape(-1)).to(torch.device("cuda", key))
+        return t
+
+    def workspace(self, device, nbytes):
+        """At least nbytes of scratch on `device` for the current stream (kept; grown when a larger batch comes)."""
+        device = torch.device(device)
+        key = (device.index if device.index is not None else torch.cuda.current_device(), _abi.stream_of(device))
+        t = self._ws.get(key)
+        if t is None or t.numel() < nbytes:
+            t = self._ws[key] = torch.empty(max(int(nbytes), 4), dtype=torch.uint8, device=device)
+        return t
+
+    def strings(self, idx):
+        """word indices (-1: no word) -> strings ('' for -1)"""
+        return [self.words[i] if i >= 0 else "" for i in (int(v) for v in idx)]
+
+
+def _lex_out(out, B, device, what):
+    if out is None:
+        return torch.empty(2 * B, dtype=torch.int32, device=device)
+    if not (torch.is_tensor(out) and out.device == device and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == 2 * B):
+        raise _abi.DpmnError("%s: out must be a contiguous int32 tensor of 2 B elements on %s" % (what, device))
+    return out
+
+
+def ctc_lexicon(logits, B, T, n_class, lex, out=None):
+    """The lexicon word of the highest CTC likelihood per image: logits rows b*T + t (B*T, ld >= n_class; logits_rows' layout, the
+    padding columns are not read), lex a Lexicon -> one int32 buffer (2 B): the word indices (B; -1 when no word fits T frames),
+    then the bits of the float32 log-likelihoods (B; -inf with -1): `buf[B:].view(torch.float32)`.  out: write into this int32
+    tensor of 2 B elements instead (ctc_greedy's `extra`)."""
+    if not isinstance(lex, Lexicon):
+        raise _abi.DpmnError("ctc_lexicon: lex must be an ops.Lexicon")
+    if logits.dim() != 2 or logits.shape[0] != B * T or logits.shape[1] < n_class:
+        raise _abi.DpmnError("ctc_lexicon: logits rows (B*T, >= n_class) expected")
+    if lex.max_class >= n_class:
+        raise _abi.DpmnError("ctc_lexicon: the lexicon holds class %d, the logits have %d classes" % (lex.max_class, n_class))
+    words = lex.device_words(logits.device)
+    L = len(lex)
+    out = _lex_out(out, B, logits.device, "ctc_lexicon")
+    ws = lex.workspace(logits.device, lib.dpmn_ctc_lexicon_workspace_bytes(B, L))
+    check(lib.dpmn_ctc_lexicon_f32(dptr(logits), logits.shape[1], n_class, words.data_ptr(), L, out.data_ptr(), out.data_ptr() + 4 * B,
+                                   ws.data_ptr(), B, T, stream()))
+    return out
+
+
+def edit_lexicon(strings_packed, lex, out=None):
+    """The lexicon word at the least Levenshtein distance per string: strings_packed a (B, 32) uint8 CUDA tensor of records
+    (utils.lexicon.pack_strings; length 0 allowed), lex a Lexicon -> one int32 buffer (2 B): the word indices, then the distances."""
+    if not isinstance(lex, Lexicon):
+        raise _abi.DpmnError("edit_lexicon: lex must be an ops.Lexicon")
+    s = strings_packed
+    if not (torch.is_tensor(s) and s.is_cuda and s.dtype == torch.uint8 and s.dim() == 2 and s.shape[1] == 32 and s.is_contiguous()
+            and s.shape[0] > 0):
+        raise _abi.DpmnError("edit_lexicon: a contiguous (B, 32) uint8 CUDA tensor of packed strings is required; there is no CPU fallback")
+    B, L = s.shape[0], len(lex)
+    words = lex.device_words(s.device)
+    out = _lex_out(out, B, s.device, "edit_lexicon")
+    ws = lex.workspace(s.device, lib.dpmn_edit_lexicon_workspace_bytes(B, L))
+    check(lib.dpmn_edit_lexicon_i32(s.data_ptr(), words.data_ptr(), L, out.data_ptr(), out.data_ptr() + 4 * B, ws.data_ptr(), B, stream()))
+    return out
+
+
+def edit_read(strings, lex, device):
+    """The edit protocol for a recogniser's strings: packed on the host (utils.lexicon.pack_strings, under the lexicon's alphabet),
+    uploaded, dpmn_edit_lexicon_i32, ONE copy back -> (the lexicon's words, the distances), one per string."""
+    from .utils import lexicon as lx
+    if not len(strings):
+        return [], []
+    packed = torch.from_numpy(lx.pack_strings(strings, lex.alphabet)).to(device)
+    h = edit_lexicon(packed, lex).cpu().numpy()
+    B = len(strings)
+    return lex.strings(h[:B]), [int(d) for d in h[B:]]
 
 
 # ------------------------------------------------------------------------------ native ASTER recogniser (csrc/aster.hip)

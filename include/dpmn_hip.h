@@ -397,6 +397,23 @@ int dpmn_bilstm_f32(const float* gx, const float* w_hh, float* out, float* c_sta
 int dpmn_ctc_greedy_i32(const float* logits, int ld, int n_class, int* cls, int* length, int B, int T, dpmn_stream_t stream);
 int dpmn_crnn_label_vecs_f32(const float* logits, int ld, int n_class, float* out, int B, int T, dpmn_stream_t stream);
 
+/* ------------------------------------------------------------------ lexicon-constrained reading (lexicon.hip; utils/lexicon.py is the
+ * NumPy restatement; main.py --rec_lexicon).  words: L records of 32 bytes, 16-byte aligned: byte 0 the length n (1 .. 31), bytes
+ * 1 .. n the classes (1-based, 0 = the CTC blank), the rest 0; 1 <= L <= 2^20.  ws: *_workspace_bytes(B, L) bytes, 4-byte aligned.
+ * Neither call depends on the compute mode.
+ * ctc_lexicon:  rows b*T + t of logits (leading dimension ld >= n_class; columns >= n_class are never read), T <= 64, n_class <= 64
+ *               -> per image the word with the highest CTC log-likelihood (log sum over all alignments on the log-softmax of the
+ *               logits, fp32 in the log domain): best_idx (B), best_logp (B).  The lowest index among equal scores; -1 and -inf
+ *               when no word fits the T frames.  A class byte >= n_class is read as n_class - 1.
+ * edit_lexicon: strings: B records of the same form (a length of 0 is allowed) -> per string the word at the least Levenshtein
+ *               distance (insert, delete, substitute: 1 each; exact): best_idx (B), best_dist (B), the lowest index among equals. */
+size_t dpmn_ctc_lexicon_workspace_bytes(int B, int L);
+int dpmn_ctc_lexicon_f32(const float* logits, int ld, int n_class, const unsigned char* words, int L, int* best_idx, float* best_logp,
+                         void* ws, int B, int T, dpmn_stream_t stream);
+size_t dpmn_edit_lexicon_workspace_bytes(int B, int L);
+int dpmn_edit_lexicon_i32(const unsigned char* strings, const unsigned char* words, int L, int* best_idx, int* best_dist, void* ws, int B,
+                          dpmn_stream_t stream);
+
 /* ------------------------------------------------------------------ native ASTER recogniser (aster.hip; model/aster.py NativeASTER)
  * aster_prep:      parse_aster_data (x * 2 - 1, interfaces/base.py:441-450) + F.interpolate(x, (Hs, Ws), bilinear,
  *                  align_corners=True) (recognizer_builder.py:77): img (B, >=3, H, W) planes with batch stride img_stride (channels

@@ -88,6 +88,47 @@ def paste_feather(args):
     return f
 
 
+def rec_lexicon_setting(args, load=True):
+    """--rec_lexicon FILE [--rec_lexicon_mode score|edit], checked -> (the words, the mode), or None without the flag.  The mode
+    defaults to score for --rec crnn and to edit for --rec aster / moran.  Every problem is a ValueError of one line: the mode without
+    the file, score with a recogniser that is not the CRNN, the flag together with --demo_tile, the flag on a training run, a missing
+    file, a file without a usable word.  load=False: only the checks that need no file contents (-> (None, mode))."""
+    path, mode = getattr(args, "rec_lexicon", None), getattr(args, "rec_lexicon_mode", None)
+    if not path:
+        if mode:
+            raise ValueError("--rec_lexicon_mode needs --rec_lexicon FILE: the word list the recogniser's answer is taken from")
+        return None
+    rec = getattr(args, "rec", None)
+    if mode not in (None, "score", "edit"):
+        raise ValueError("--rec_lexicon_mode is score or edit, got %r" % (mode,))
+    if mode is None:
+        mode = "score" if rec == "crnn" else "edit"
+    if mode == "score" and rec != "crnn":
+        raise ValueError("--rec_lexicon_mode score needs --rec crnn: the CTC likelihood of a word is computed from the CRNN's frame "
+                         "posteriors; --rec %s reads under a lexicon with --rec_lexicon_mode edit" % rec)
+    if getattr(args, "demo_tile", False):
+        raise ValueError("--rec_lexicon does not combine with --demo_tile: a window of a line is not a word")
+    if not (getattr(args, "test", False) or getattr(args, "demo_dir", None)):
+        raise ValueError("--rec_lexicon needs --test or --demo_dir: the lexicon is used where SR images are read, not in training")
+    if not os.path.isfile(path):
+        raise ValueError("--rec_lexicon %s is not a file" % path)
+    if not load:
+        return None, mode
+    from dpmn_amd.utils.lexicon import load_lexicon
+    return load_lexicon(path, "lower"), mode
+
+
+def lexicon_accuracies(rows):
+    """The rows of demo_result.csv with boxes and a lexicon (file, box, label, lr_string, sr_string, sr_lexicon, sr_lexicon_score) ->
+    (labelled regions, open-vocabulary accuracy, lexicon accuracy); the accuracies are None without a labelled region."""
+    from dpmn_amd.utils.util import str_filt
+    labelled = [(str_filt(r[2], "lower"), r[4], r[5]) for r in rows if str_filt(r[2], "lower")]
+    if not labelled:
+        return 0, None, None
+    n = len(labelled)
+    return n, round(sum(t == s for t, s, _ in labelled) / n, 4), round(sum(t == w for t, _, w in labelled) / n, 4)
+
+
 TRAIN_WORDS_OR_HR_DIR = ("main.py: --train_words and --train_hr_dir are two sources of the HR training images (a word list rendered on the "
                          "GPU, a folder of images); give one of them")
 TRAIN_WORDS_FONTS_NEEDS = "main.py: --train_words_fonts needs --train_words: the fonts are those the words are rendered in"
@@ -165,6 +206,11 @@ def main(config, args):
         feather = paste_feather(args)
     except ValueError as e:
         raise SystemExit("main.py: %s" % e)
+    # (the lexicon is read before anything touches the GPU: a bad file or a wrong combination ends the run here)
+    try:
+        lex_words = rec_lexicon_setting(args)
+    except ValueError as e:
+        raise SystemExit("main.py: %s" % e)
     hr_dir = getattr(args, "train_hr_dir", None)
     if hr_dir and not os.path.isdir(hr_dir):
         raise SystemExit("main.py: --train_hr_dir %s is not a directory" % hr_dir)
@@ -188,6 +234,13 @@ def main(config, args):
     bs = args.batch_size or config.TRAIN.batch_size
     os.makedirs(config.TRAIN.ckpt_dir, exist_ok=True)
     rec = recogniser(mission, args)
+    lex_kw = {}
+    if lex_words is not None:
+        if rec is None:
+            raise SystemExit("main.py: --rec_lexicon needs a recogniser, and --rec %s built none (see the line above)" % args.rec)
+        from dpmn_amd.ops import Lexicon
+        lex_kw = {"lexicon": Lexicon(lex_words[0], mode=lex_words[1])}
+        print("rec_lexicon: %d words, mode %s" % (len(lex_words[0]), lex_words[1]))
     if getattr(args, "demo_dir", None):
         # a folder of the user's own text crops -> one <stem>_sr.png per image and demo_result.csv (TextSR.demo); the trained models
         # are loaded as for --test
@@ -216,10 +269,12 @@ def main(config, args):
                 batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device, photos=True)
                 # (--demo_paste_polygons: the polygons too, strip by strip, in box-file order with the quadrilaterals: utils/paste_poly.py)
                 rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, paste=True, feather=feather,
-                                    paste_polygons=bool(getattr(args, "demo_paste_polygons", False)))
+                                    paste_polygons=bool(getattr(args, "demo_paste_polygons", False)), **lex_kw)
             else:
                 batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device)
-                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True)
+                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, **lex_kw)
+            if lex_kw:
+                print("accuracy %s accuracy_lexicon %s over %d labelled regions" % tuple(lexicon_accuracies(rows)[i] for i in (1, 2, 0)))
             print("%d regions super-resolved into %s" % (len(rows), out_dir))
             return
         if getattr(args, "demo_tile", False):
@@ -228,23 +283,26 @@ def main(config, args):
             rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=True, chunk=bs)
         else:
             batches = folder_batches(args.demo_dir, bs, lr_size, mission.mask, mission.device)
-            rows = mission.demo(models, psn, batches, out_dir, rec=rec)
+            rows = mission.demo(models, psn, batches, out_dir, rec=rec, **lex_kw)
         print("%d images super-resolved into %s" % (len(rows), out_dir))
         return
     if args.test:
         result_path = os.path.join(config.TRAIN.ckpt_dir, "test_result.csv")
         if rank == 0 and not os.path.exists(result_path):
             with open(result_path, "w+") as out:
-                csv.writer(out).writerow(["recognizer", "subset", "accuracy", "psnr", "ssim"])
+                csv.writer(out).writerow(["recognizer", "subset", "accuracy", "psnr", "ssim"] + (["accuracy_lexicon"] if lex_kw else []))
         if args.test_data_dir and os.path.isdir(args.test_data_dir):       # a TextZoom LMDB directory (needs the lmdb package)
             from dpmn_amd.dataset.textzoom import sr_batches
             loader = sr_batches(mission.get_test_data(args.test_data_dir)[1], mission.device, mission.mask)
         else:
             loader = synthetic_loader(bs, args.synthetic_steps, 1000 + rank, labels=rec is not None)
-        res = mission.test(loader, rec=rec, display=args.vis_dir is not None and rank == 0)
+        res = mission.test(loader, rec=rec, display=args.vis_dir is not None and rank == 0, **lex_kw)
         if rank == 0:
             with open(result_path, "a") as out:
-                csv.writer(out).writerow([args.rec, "synthetic", res["accuracy"], res["psnr_avg"], res["ssim_avg"]])
+                csv.writer(out).writerow([args.rec, "synthetic", res["accuracy"], res["psnr_avg"], res["ssim_avg"]]
+                                         + ([res["accuracy_lexicon"]] if lex_kw else []))
+            if lex_kw:
+                print("accuracy_lexicon %s" % res["accuracy_lexicon"])
             print("psnr %.4f ssim %.4f accuracy %s over %d synthetic batches" % (res["psnr_avg"], res["ssim_avg"], res["accuracy"],
                                                                                 args.synthetic_steps))
     else:
@@ -404,6 +462,14 @@ if __name__ == '__main__':
                         help='train from this word list alone (one word per line, UTF-8): the HR images are rendered on the GPU in random '
                              'fonts, sizes, colours, spacing and shear, every sample with its true label; implies --manmade_degrade, needs '
                              'no image data; not together with --train_hr_dir')
+    parser.add_argument('--rec_lexicon', type=str, default=None, metavar='FILE',
+                        help='with --test or --demo_dir and a recogniser: also read every SR image under this word list (one word per '
+                             'line, UTF-8; filtered like --train_words, duplicates dropped): --test reports accuracy_lexicon beside '
+                             'accuracy, --demo_dir writes the columns sr_lexicon and sr_lexicon_score; not with --demo_tile')
+    parser.add_argument('--rec_lexicon_mode', default=None, choices=['score', 'edit'],
+                        help='with --rec_lexicon: score = the word of the highest CTC likelihood under the frame posteriors (--rec crnn '
+                             'only, its default), edit = the word at the least edit distance to the recognised string (any recogniser; '
+                             'the default of --rec aster / moran)')
     parser.add_argument('--train_words_fonts', type=str, default=None, metavar='DIR',
                         help='with --train_words: every *.ttf / *.otf of this directory is a font (default: PIL\'s built-in font)')
     parser.add_argument('--train_words_epoch', type=int, default=10000, metavar='N',
@@ -423,6 +489,10 @@ if __name__ == '__main__':
         parser.error(DEMO_PASTE_POLYGONS_NEEDS[len("main.py: "):])
     try:
         paste_feather(args)
+    except ValueError as e:
+        parser.error(str(e))
+    try:
+        rec_lexicon_setting(args, load=False)
     except ValueError as e:
         parser.error(str(e))
     config_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config', 'super_resolution.yaml')
