@@ -1196,9 +1196,14 @@ static int window_attn_bwd_impl(const float* q, const float* kv, const float* co
   DPMN_REQUIRE(heads_per_group == 2 && C % n_groups == 0 && (H * W) % 64 == 0, "window_attn_bwd: unsupported geometry");
   const int D = C / n_groups / heads_per_group;
   hipStream_t st = as_stream(stream);
+  for (int g = 0; g < n_groups; ++g) {      // every group is checked before the first launch: a rejected call writes nothing
+    const int ws = windows[g], sh = shifts[g];
+    DPMN_REQUIRE((D == 16 && (ws == 2 || ws == 4 || ws == 8 || ws == 16)) || (D == 32 && (ws == 4 || ws == 8 || ws == 16)),
+                 "window_attn_bwd: unsupported (window, head_dim)");
+    DPMN_REQUIRE(H % ws == 0 && W % ws == 0 && sh >= 0 && sh < ws, "window_attn_bwd: bad window / shift");
+  }
   for (int g = 0; g < n_groups; ++g) {
     const int ws = windows[g], sh = shifts[g];
-    DPMN_REQUIRE(H % ws == 0 && W % ws == 0 && sh >= 0 && sh < ws, "window_attn_bwd: bad window / shift");
     int rc = DPMN_ERR_ARG;
     const long slabs = (long)B * (H * W / 64);
     if (ws == 8 && D == 16) {

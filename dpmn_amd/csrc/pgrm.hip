@@ -988,10 +988,15 @@ int dpmn_window_attn_drop_f32(const float* q, const float* kv, const float* cons
   const int D = C / n_groups / heads_per_group;
   DPMN_REQUIRE((H * W) % 64 == 0, "window_attn: token count must be a multiple of 64");
   hipStream_t st = as_stream(stream);
-  for (int g = 0; g < n_groups; ++g) {
+  for (int g = 0; g < n_groups; ++g) {      // every group is checked before the first launch: a rejected call writes nothing
     const int ws = windows[g], sh = shifts[g];
+    DPMN_REQUIRE((D == 16 && (ws == 2 || ws == 4 || ws == 8)) || (D == 32 && (ws == 4 || ws == 8 || ws == 16)),
+                 "window_attn: unsupported (window, head_dim); built: {2,4,8}x16, {4,8,16}x32");
     DPMN_REQUIRE(H % ws == 0 && W % ws == 0, "window_attn: padding path (H or W not divisible by window) would crash the reference (quirk Q1)");
     DPMN_REQUIRE(sh >= 0 && sh < ws, "window_attn: shift must be in [0, window)");
+  }
+  for (int g = 0; g < n_groups; ++g) {
+    const int ws = windows[g], sh = shifts[g];
     int rc = DPMN_ERR_ARG;
     if (ws == 8 && D == 16) {
       rc = p_drop > 0.f ? launch_window_attn8_mfma<true>(q, kv, bias_tables[g], out, B, H, W, C, g, sh, p_drop, seed, st)

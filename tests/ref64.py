@@ -10,7 +10,10 @@ tests/test_ref64.py to torch.autograd of an independent forward in double.  They
 evaluated with dtype=torch.float32 is the fp32 CPU evaluation that tests/test_gpu_small_backward.py derives its tolerances from.
 
 The last part holds the references of the convolution family (tests/test_gpu_conv_family.py): forward, transposed forward, weight
-gradient, data gradient and the BatchNorm statistics, as loops over the taps with one slice and one matmul / einsum per tap."""
+gradient, data gradient and the BatchNorm statistics, as loops over the taps with one slice and one matmul / einsum per tap; then the
+window-attention family (tests/test_gpu_attn_family.py): the multi-window shifted-window attention and its hand-written backward, alone
+and behind the LayerNorm + q / kv projections -- roll as torch.roll on the token plane, window partition as a reshape, the region mask
+from the Swin definition's nine labelled slices; from oracle.pgrm only drop_mask (the counter hash of the masks)."""
 import math
 
 import torch
@@ -632,3 +635,146 @@ def conv_transpose2d_dgrad(dy, w, stride=1, pad=0, c0=0, cs=None, dtype=torch.fl
     w = _c(w, dtype)
     cs = w.shape[0] - c0 if cs is None else cs
     return _corr(_c(dy, dtype), w[c0:c0 + cs], stride, pad, 1)
+
+
+# ====================================================================================================================
+# window-attention family (k_window_attn*, k_window_attn*_bwd* and the fused LayerNorm + q / kv + attention kernels): written from the
+# definition of the shifted-window attention of one SwinTransformerBlock with several window sizes -- group g of n_groups takes channels
+# [g cg, (g + 1) cg) of q (B, L, C) and of the k and v halves of kv (B, L, 2 C), two heads of D = cg / 2 channels each.  Per group: roll the
+# (H, W) token plane by -shift along both axes, cut it into ws x ws windows (a reshape), attend within each window with
+# logit = (q D^-0.5) . k + bias[head][n][m] + mask[window][n][m], softmax over the keys, attn_drop on the probabilities, P V.  The output
+# stays in window-major order, the roll is NOT undone (quirk Q1): cat[b, win N + n, g cg + head D + d].  `dtype` as above.
+def _wattn_src(H, W, ws, shift):
+    """source raster token of every window-major slot: torch.roll of the token plane by -shift, then the window partition as a reshape"""
+    plane = torch.roll(torch.arange(H * W).reshape(H, W), shifts=(-shift, -shift), dims=(0, 1))
+    return plane.reshape(H // ws, ws, W // ws, ws).permute(0, 2, 1, 3).reshape(-1)
+
+
+def _wattn_rel_index(ws):
+    """(N, N): row of the (2 ws - 1)^2 bias table for query n and key m -- the pair's row and column offsets, each moved into
+    [0, 2 ws - 2], the row offset counted in whole table rows"""
+    coords = torch.stack(torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing="ij")).reshape(2, -1)      # (2, N): i, j of a token
+    rel = coords[:, :, None] - coords[:, None, :] + (ws - 1)
+    return rel[0] * (2 * ws - 1) + rel[1]
+
+
+def _wattn_labels(H, W, ws, shift):
+    """(nW, N) region label of every token of the rolled frame: the frame is cut by the three row slices and the three column slices
+    [0, -ws), [-ws, -shift), [-shift, end) and every one of the nine pieces gets its own label (the attention mask of the Swin
+    transformer); only tokens with the same label attend to each other"""
+    img = torch.zeros(H, W, dtype=torch.long)
+    cnt = 0
+    for hs in (slice(0, -ws), slice(-ws, -shift), slice(-shift, None)):
+        for wsl in (slice(0, -ws), slice(-ws, -shift), slice(-shift, None)):
+            img[hs, wsl] = cnt
+            cnt += 1
+    return img.reshape(H // ws, ws, W // ws, ws).permute(0, 2, 1, 3).reshape(-1, ws * ws)
+
+
+def _wattn_drop_index(B, G, g, L, N):
+    """(B, nW, 2, N, N) element index of the attn_drop mask (include/dpmn_hip.h): ((((b G + g) 2 + head) L + window-major query token)
+    N + key row in the window)"""
+    import numpy as np
+    b, win, h, n, m = np.meshgrid(np.arange(B), np.arange(L // N), np.arange(2), np.arange(N), np.arange(N), indexing="ij")
+    return (((b * G + g) * 2 + h) * L + win * N + n) * N + m
+
+
+def _wattn_group(q, kv, table, g, G, ws, shift, H, W, p_drop, seed, dtype):
+    """one group's attention -> dict of the window-major operands Q, K, V (B, nW, 2, N, D), the logits S, the probabilities P, the
+    dropout mask M (None: off), the output O (B, nW, 2, N, D), and src / idx / scale"""
+    B, L, C = q.shape
+    cg, N = C // G, ws * ws
+    D, nW = cg // 2, L // N
+    src = _wattn_src(H, W, ws, shift)
+
+    def split(x, c0):
+        return x[:, src, c0:c0 + cg].reshape(B, nW, N, 2, D).permute(0, 1, 3, 2, 4)
+    Q, K, V = split(q, g * cg), split(kv, g * cg), split(kv, C + g * cg)
+    scale = D ** -0.5
+    idx = _wattn_rel_index(ws)
+    bias = table.reshape(-1, 2)[idx.reshape(-1)].reshape(N, N, 2).permute(2, 0, 1)
+    S = (Q * scale) @ K.transpose(-1, -2) + bias
+    if shift > 0:      # the mask adds -100, not -inf: the operation's definition
+        lab = _wattn_labels(H, W, ws, shift)
+        S = S + torch.where(lab[:, :, None] == lab[:, None, :], 0.0, -100.0).to(dtype)[None, :, None]
+    P = _softmax(S)                  # the denominator is over the undropped row
+    M = None
+    if p_drop > 0:
+        from oracle.pgrm import drop_mask       # the counter hash of the masks, not attention arithmetic
+        M = drop_mask(seed, _wattn_drop_index(B, G, g, L, N), p_drop).to(dtype)
+    O = (P if M is None else P * M) @ V
+    return {"Q": Q, "K": K, "V": V, "S": S, "P": P, "M": M, "O": O, "src": src, "idx": idx, "scale": scale}
+
+
+def _wattn_merge(X, B, L):
+    """(B, nW, 2, N, D) -> (B, L, 2 D) window-major"""
+    return X.permute(0, 1, 3, 2, 4).reshape(B, L, -1)
+
+
+def window_attn(q, kv, tables, windows, shifts, H, W, p_drop=0.0, seed=0, dtype=torch.float64, parts=None):
+    """-> cat (B, L, C).  tables[g]: ((2 ws_g - 1)^2, 2).  parts: a list that receives every group's _wattn_group dict"""
+    q, kv = _c(q, dtype), _c(kv, dtype)
+    B, L, _ = q.shape
+    G = len(windows)
+    outs = []
+    for g in range(G):
+        r = _wattn_group(q, kv, _c(tables[g], dtype), g, G, windows[g], shifts[g], H, W, p_drop, seed, dtype)
+        if parts is not None:
+            parts.append(r)
+        outs.append(_wattn_merge(r["O"], B, L))
+    return torch.cat(outs, -1)
+
+
+def window_attn_bwd(q, kv, tables, windows, shifts, H, W, dout, p_drop=0.0, seed=0, dtype=torch.float64, parts=None):
+    """Backward of window_attn for the cotangent dout (B, L, C) of cat (window-major, as cat): with the dropout mask M,
+    dP = dO V^T M, dS = P (dP - sum_m P dP), dQ = scale dS K, dK = scale dS^T Q, dV = (P M)^T dO; dq / dk / dv go back to the raster token
+    the roll and the window partition took them from; dtable[idx[n, m], head] += dS[.., head, n, m] over images and windows.
+    -> (dq (B, L, C), dkv (B, L, 2 C), [dtable_g ((2 ws_g - 1)^2, 2)]).  parts: receives every group's dict, with dP and dS added"""
+    q, kv, dout = _c(q, dtype), _c(kv, dtype), _c(dout, dtype)
+    B, L, C = q.shape
+    G = len(windows)
+    cg = C // G
+    dq, dkv, dtables = torch.zeros_like(q), torch.zeros_like(kv), []
+    for g in range(G):
+        ws = windows[g]
+        N = ws * ws
+        r = _wattn_group(q, kv, _c(tables[g], dtype), g, G, ws, shifts[g], H, W, p_drop, seed, dtype)
+        P, M = r["P"], r["M"]
+        dO = dout[:, :, g * cg:(g + 1) * cg].reshape(B, L // N, N, 2, cg // 2).permute(0, 1, 3, 2, 4)
+        dP = dO @ r["V"].transpose(-1, -2)
+        if M is not None:
+            dP = dP * M
+        dS = P * (dP - (P * dP).sum(-1, keepdim=True))
+        dQ = r["scale"] * (dS @ r["K"])
+        dK = r["scale"] * (dS.transpose(-1, -2) @ r["Q"])
+        dV = (P if M is None else P * M).transpose(-1, -2) @ dO
+        dq[:, r["src"], g * cg:(g + 1) * cg] = _wattn_merge(dQ, B, L)
+        dkv[:, r["src"], g * cg:(g + 1) * cg] = _wattn_merge(dK, B, L)
+        dkv[:, r["src"], C + g * cg:C + (g + 1) * cg] = _wattn_merge(dV, B, L)
+        dt = torch.zeros((2 * ws - 1) ** 2, 2, dtype=dtype)
+        dt.index_add_(0, r["idx"].reshape(-1), dS.sum((0, 1)).permute(1, 2, 0).reshape(N * N, 2))
+        dtables.append(dt)
+        if parts is not None:
+            r.update(dP=dP, dS=dS, dO=dO)
+            parts.append(r)
+    return dq, dkv, dtables
+
+
+def ln_qkv(tq, tkv, lnq_w, lnq_b, lnkv_w, lnkv_b, wq, bq, wkv, bkv, eps=1e-5, dtype=torch.float64):
+    """q = Linear_q(LayerNorm_q(tq)) (B, L, C), kv = Linear_kv(LayerNorm_kv(tkv)) (B, L, 2 C): _ln and linear above"""
+    B, L, C = tq.shape
+    q = linear(_c(tq, dtype).reshape(B * L, C), wq, bq, pro=("ln", lnq_w, lnq_b, eps), dtype=dtype)
+    kv = linear(_c(tkv, dtype).reshape(B * L, C), wkv, bkv, pro=("ln", lnkv_w, lnkv_b, eps), dtype=dtype)
+    return q.reshape(B, L, C), kv.reshape(B, L, 2 * C)
+
+
+def ln_qkv_window_attn(tq, tkv, ln, tables, windows, shifts, H, W, p_drop=0.0, seed=0, eps=1e-5, dtype=torch.float64, parts=None):
+    """The fused operator: ln = (lnq_w, lnq_b, lnkv_w, lnkv_b, wq, bq, wkv, bkv) -> (cat, q, kv)"""
+    q, kv = ln_qkv(tq, tkv, *ln, eps=eps, dtype=dtype)
+    return window_attn(q, kv, tables, windows, shifts, H, W, p_drop, seed, dtype, parts), q, kv
+
+
+def ln_qkv_window_attn_bwd(tq, tkv, ln, tables, windows, shifts, H, W, dout, p_drop=0.0, seed=0, eps=1e-5, dtype=torch.float64, parts=None):
+    """Its backward twin: (dq, dkv, [dtable_g]) of the recomputed PROJECTED q / kv, not of the tokens"""
+    q, kv = ln_qkv(tq, tkv, *ln, eps=eps, dtype=dtype)
+    return window_attn_bwd(q, kv, tables, windows, shifts, H, W, dout, p_drop, seed, dtype, parts)

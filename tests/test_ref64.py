@@ -485,3 +485,65 @@ def test_conv_references_fp32_evaluation():
     dy = u("fdy", tuple(y64.shape))
     g32 = ref64.conv2d_wgrad(segs, dy, 3, 1, 1, 1, pro, aff, dtype=torch.float32)
     assert g32.dtype == torch.float32 and float((g32.double() - ref64.conv2d_wgrad(segs, dy, 3, 1, 1, 1, pro, aff)).abs().max()) < 1e-4
+
+
+# ------------------------------------------------------------------------------------------------------------------ window attention
+# forward against oracle.pgrm.window_attention_core in double, backward against torch.autograd through it; H == ws for the window of 8 /
+# W > H, and H == W == ws for the window of 16; unsorted window sets, shifts 0, 1, ws / 2 (+ 1), ws - 1
+WATTN_GEOM = [(8, 16, [8, 2, 4], [7, 1, 3]), (16, 16, [16, 4, 8], [5, 0, 1])]
+
+
+@pytest.mark.parametrize("p_drop", [0.0, 0.3])
+@pytest.mark.parametrize("H,W,windows,shifts", WATTN_GEOM)
+def test_window_attn_vs_oracle_and_autograd(H, W, windows, shifts, p_drop):
+    from oracle import pgrm as op
+    B, C, L, seed = 2, 96, H * W, 0x1234ABCD
+    q, k, v = leaf("waq", (B, L, C), -2, 2), leaf("wak", (B, L, C), -2, 2), leaf("wav", (B, L, C))
+    sd = {"a.relative_position_bias_table_%d" % g: leaf("watbl%d" % g, ((2 * ws - 1) ** 2, 2)) for g, ws in enumerate(windows)}
+    tables = [sd["a.relative_position_bias_table_%d" % g] for g in range(3)]
+    dout = u("wadout", (B, L, C))
+    ref = op.window_attention_core(q, k, v, sd, "a.", H, W, windows, shifts, 2, p_drop, seed)
+    grads = torch.autograd.grad(ref, [q, k, v] + tables, dout)
+    kv = torch.cat([k, v], -1).detach()
+    close(ref64.window_attn(q, kv, tables, windows, shifts, H, W, p_drop, seed), ref.detach(), "window_attn")
+    dq, dkv, dt = ref64.window_attn_bwd(q, kv, tables, windows, shifts, H, W, dout, p_drop, seed)
+    close(dq, grads[0], "window_attn_bwd dq")
+    close(dkv, torch.cat([grads[1], grads[2]], -1), "window_attn_bwd dkv")
+    for g in range(3):
+        close(dt[g], grads[3 + g], "window_attn_bwd dtable %d" % g)
+
+
+def test_ln_qkv_window_attn_vs_oracle():
+    """the fused operator = nn.LayerNorm + nn.Linear + the core; its backward twin returns the gradients of the PROJECTED q / kv"""
+    from oracle import pgrm as op
+    B, C, H, W, windows, shifts, p, seed = 2, 96, 8, 16, [8, 2, 4], [7, 1, 3], 0.3, 77
+    L = H * W
+    tq, tkv = u("ftq", (B, L, C)), u("ftkv", (B, L, C))
+    ln = (u("g1", (C,), 0.5, 1.5), u("b1", (C,), -0.2, 0.2), u("g2", (C,), 0.5, 1.5), u("b2", (C,), -0.2, 0.2),
+          u("fwq", (C, C), -0.3, 0.3), u("fbq", (C,)), u("fwkv", (2 * C, C), -0.3, 0.3), u("fbkv", (2 * C,)))
+    sd = {"a.relative_position_bias_table_%d" % g: u("ftbl%d" % g, ((2 * ws - 1) ** 2, 2)) for g, ws in enumerate(windows)}
+    tables = [sd["a.relative_position_bias_table_%d" % g] for g in range(3)]
+    q = F.linear(F.layer_norm(tq, (C,), ln[0], ln[1]), ln[4], ln[5]).requires_grad_(True)
+    kv = F.linear(F.layer_norm(tkv, (C,), ln[2], ln[3]), ln[6], ln[7]).requires_grad_(True)
+    ref = op.window_attention_core(q, kv[..., :C], kv[..., C:], sd, "a.", H, W, windows, shifts, 2, p, seed)
+    dout = u("fdout", (B, L, C))
+    gq, gkv = torch.autograd.grad(ref, (q, kv), dout)
+    cat, q64, kv64 = ref64.ln_qkv_window_attn(tq, tkv, ln, tables, windows, shifts, H, W, p, seed)
+    close(q64, q.detach(), "ln_qkv q")
+    close(kv64, kv.detach(), "ln_qkv kv")
+    close(cat, ref.detach(), "ln_qkv_window_attn")
+    dq, dkv, _ = ref64.ln_qkv_window_attn_bwd(tq, tkv, ln, tables, windows, shifts, H, W, dout, p, seed)
+    close(dq, gq, "ln_qkv_window_attn_bwd dq")
+    close(dkv, gkv, "ln_qkv_window_attn_bwd dkv")
+
+
+def test_window_attn_fp32_evaluation():
+    """dtype=float32 evaluates the same formulas in fp32 (the yardstick of the GPU suite's bounds)"""
+    B, C, H, W, windows, shifts = 1, 96, 8, 8, [2, 4, 8], [1, 2, 7]
+    q, kv = u("yq", (B, 64, C)), u("ykv", (B, 64, 2 * C))
+    tables = [u("ytbl%d" % g, ((2 * ws - 1) ** 2, 2)) for g, ws in enumerate(windows)]
+    o64, o32 = ref64.window_attn(q, kv, tables, windows, shifts, H, W, 0.3, 5), ref64.window_attn(q, kv, tables, windows, shifts, H, W, 0.3, 5, dtype=torch.float32)
+    assert o32.dtype == torch.float32 and 0 < float((o32.double() - o64).abs().max()) < 1e-5
+    g32 = ref64.window_attn_bwd(q, kv, tables, windows, shifts, H, W, o64, 0.3, 5, dtype=torch.float32)
+    g64 = ref64.window_attn_bwd(q, kv, tables, windows, shifts, H, W, o64, 0.3, 5)
+    assert all(a.dtype == torch.float32 and float((a.double() - b).abs().max()) < 1e-5 for a, b in zip((g32[0], g32[1], *g32[2]), (g64[0], g64[1], *g64[2])))
