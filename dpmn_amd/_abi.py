@@ -298,6 +298,7 @@ SIGNATURES = {
     "dpmn_psf_blur_ragged_u8": (_i, [fp, _l, fp, fp, _i, fp, fp, _i, _i, fp, fp]),
     "dpmn_cutblur_ragged_u8": (_i, [fp, _l, fp, _i, _i, fp, fp]),
     "dpmn_render_words_u8": (_i, [fp, fp, fp, fp, fp, fp, fp, fp, _i, fp, _l, _i, _i, _i, _i, fp, fp, fp, fp, fp]),
+    "dpmn_render_words_fx_u8": (_i, [fp, fp, fp, fp, fp, fp, fp, fp, fp, _i, fp, _l, fp, _i, fp, _l, _i, _i, _i, _i, fp, fp, fp, fp, fp, fp, fp]),
     "dpmn_resize_windows_workspace_bytes": (_sz, [_l, _l, _i]),
     "dpmn_resize_windows_u8": (_i, [fp, _l, fp, _i, fp, _l, fp, _i, _l, _i, fp, _i, _i, fp, _sz, fp]),
     "dpmn_stitch_windows_u8": (_i, [fp, _l, _l, _i, _i, _i, _i, fp, _i, fp, _i, fp, _l, fp]),

@@ -133,11 +133,13 @@ class alignCollate_realWTLAMask(object):
     drawn up to frac of the image's height (ops.psf_blur_ragged_u8); the HR batch stays sharp.
     render=(words, atlases) (ours, needs degrade; main.py --train_words, dataset/words.py WordsHR): the batch holds no image at all --
     positions 0 and 2 are None and `sr_batches` renders the HR images on the GPU (ops.render_words_u8) from the words and parameters
-    it draws per batch; `render` is then True and `words` / `atlases` carry the pair."""
+    it draws per batch; `render` is then True and `words` / `atlases` carry the pair.  render_fx (ours, needs render; main.py
+    --train_words_fx): the utils.render.RenderFx of the run -- `sr_batches` then draws with draw_render_fx and renders with
+    ops.render_words_fx_u8 (outline, drop shadow, photo background)."""
 
     def __init__(self, imgH=64, imgW=256, down_sample_scale=4, keep_ratio=False, min_ratio=1, mask=False, alphabet=53, train=True,
                  y_domain=False, gpu_finish=False, gpu_resize=False, degrade=False, cutblur=False, jpeg=None, render=None,
-                 psf=None):
+                 psf=None, render_fx=None):
         if degrade and not gpu_resize:
             raise ValueError("alignCollate_realWTLAMask: degrade=True needs gpu_resize=True (the LR images are made on the GPU from the "
                              "packed HR pixels)")
@@ -172,6 +174,9 @@ class alignCollate_realWTLAMask(object):
                              "partner: it is synthesised on the GPU)")
         self.render = render is not None
         self.words, self.atlases = (list(render[0]), render[1]) if self.render else (None, None)
+        if render_fx and not self.render:
+            raise ValueError("alignCollate_realWTLAMask: render_fx needs render=(words, atlases) (the effects are drawn on rendered words)")
+        self.render_fx = render_fx or None
         self.imgH, self.imgW, self.down_sample_scale, self.mask = imgH, imgW, down_sample_scale, mask
         self.gpu_finish, self.gpu_resize, self.degrade, self.cutblur = gpu_finish, gpu_resize, bool(degrade), bool(cutblur)
         self.alphabet = "0123456789abcdefghijklmnopqrstuvwxyz"
@@ -286,7 +291,9 @@ def sr_batches(loader, device=None, mask=None, size=None):
     continuation; keyed by (pass, batch) a continued run (--train_state restores the stream the key came from) sees exactly the LR
     images the uninterrupted run saw.  Batches of a render collate (main.py --train_words) hold no image: from the batch's stream come
     FIRST the words and render parameters (utils.render.draw_render, one sample per item of the batch), THEN exactly the draws of
-    degrade_on_gpu; the HR images are rendered on the GPU (ops.render_words_u8) and the yielded labels are the drawn words."""
+    degrade_on_gpu; the HR images are rendered on the GPU (ops.render_words_u8) and the yielded labels are the drawn words.  With the
+    collate's render_fx (main.py --train_words_fx) the draws are utils.render.draw_render_fx's (every sample's fx draws follow its
+    render draws, still before the degradation's) and the render is ops.render_words_fx_u8; without it nothing changes."""
     import random
     col = getattr(loader, "collate_fn", None)
     if mask is None:
@@ -306,8 +313,15 @@ def sr_batches(loader, device=None, mask=None, size=None):
                 size = (col.imgH, col.imgW, col.down_sample_scale)
             H, W, scale = size
             rng = random.Random(pass_key + j)
-            labels, cls, lens, params = draw_render(col.words, col.atlases.n_fonts, rng, n=len(labels))
-            hr, lr = degrade_on_gpu(ops.render_words_u8(cls, lens, params, col.atlases, device=device), (H, W), scale, mask, device,
+            fx = getattr(col, "render_fx", None)
+            if fx:
+                from ..utils.render import draw_render_fx
+                labels, cls, lens, params, rows = draw_render_fx(col.words, col.atlases.n_fonts, rng, len(labels), fx)
+                pair = ops.render_words_fx_u8(cls, lens, params, rows, col.atlases, fx.pool, device=device)
+            else:
+                labels, cls, lens, params = draw_render(col.words, col.atlases.n_fonts, rng, n=len(labels))
+                pair = ops.render_words_u8(cls, lens, params, col.atlases, device=device)
+            hr, lr = degrade_on_gpu(pair, (H, W), scale, mask, device,
                                     cutblur=col.cutblur, rng=rng, jpeg=getattr(col, "jpeg", None), psf=getattr(col, "psf", None))
         elif isinstance(hr, (tuple, list)):
             if size is None:

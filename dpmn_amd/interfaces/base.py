@@ -52,7 +52,9 @@ FINGERPRINT_FIELDS = ("arch", "stu_iter_b1", "stu_iter_b2", "sr_share", "patch_s
                       "psf_blur")
 # booleans, jpeg_degrade: None or [lo, hi, prob], psf_blur: None or [kinds, prob, frac] of utils.psf.psf_setting, ema: None or the decay
 # of the averaged weights, and train_words: None or the dict of
-# utils.render.words_setting (crc32 of the word list, sorted font names, epoch size); a state written before they existed has them off
+# utils.render.words_setting (crc32 of the word list, sorted font names, epoch size; with --train_words_fx, and only then, its kinds, its
+# probability and the crc32 of the background pool: a state written without them loads into a run without them, any difference is
+# refused); a state written before they existed has them off
 DATA_FIELDS = ("manmade_degrade", "cutblur", "train_hr_dir", "jpeg_degrade", "ema", "train_words", "psf_blur")
 
 
@@ -204,7 +206,8 @@ class TextBase(object):
         --psf_radius; with degrade, training data only): a random point-spread function on the HR pixels that the LR images are synthesised
         from (ops.psf_blur_ragged_u8 in sr_batches).  words=(words, atlases, epoch size)
         (--train_words): no image data at all -- dataset/words.py WordsHR, the HR images are rendered on the GPU by sr_batches
-        (ops.render_words_u8), always degraded."""
+        (ops.render_words_u8), always degraded; a fourth item, the utils.render.RenderFx of --train_words_fx (or None), makes that
+        ops.render_words_fx_u8: outline, drop shadow, photo background."""
         from ..dataset import textzoom as tz
         cfg = self.config.TRAIN
         degrade = bool(degrade or hr_dir or words)
@@ -234,7 +237,8 @@ class TextBase(object):
                                                     gpu_finish=gpu_finish,      # True: ToTensor + mask channel on the GPU by sr_batches
                                                     gpu_resize=gpu_finish and (gpu_resize or degrade or bool(getattr(self.args, "gpu_resize", False))),
                                                     degrade=degrade, cutblur=cutblur, jpeg=jpeg, psf=psf,
-                                                    render=(words[0], words[1]) if words else None))
+                                                    render=(words[0], words[1]) if words else None,
+                                                    render_fx=words[3] if words and len(words) > 3 else None))
         # (dataset/textzoom.py; uint8 pixels in the batch); False: the reference's float (B, 3 + mask, H, W) tensors for consumers that
         # iterate the loader themselves
         if shard:
@@ -242,8 +246,9 @@ class TextBase(object):
         return ds, loader
 
     def get_train_data(self, train_words=None):
-        """train_words (main.py --train_words): (words, atlases, epoch size) -- the filtered word list, utils.render.build_atlases of
-        the fonts and the number of samples that counts as one epoch; the training set is then rendered from it."""
+        """train_words (main.py --train_words): (words, atlases, epoch size[, fx]) -- the filtered word list, utils.render.build_atlases
+        of the fonts, the number of samples that counts as one epoch and, optionally, the utils.render.RenderFx of --train_words_fx;
+        the training set is then rendered from it."""
         cfg = self.config.TRAIN
         degrade, cutblur = degrade_flags(self.args)
         hr_dir = getattr(self.args, "train_hr_dir", None)

@@ -839,7 +839,8 @@ class TextSR(base.TextBase):
         checkpoints written from it hold them -- they are what was scored; checkpoint.pth keeps the live weights, the state file
         carries the average, and a state only continues a run with the same setting.
         train_words (main.py --train_words): the setting of a run whose HR images are rendered from a word list
-        (utils.render.words_setting: crc32 of the list, font names, epoch size; the loader itself comes from
+        (utils.render.words_setting: crc32 of the list, font names, epoch size and, with --train_words_fx, the kinds, the probability
+        and the background pool's crc32; the loader itself comes from
         get_train_data(train_words=...)).  It only goes into the state's fingerprint: a state continues a run with the same setting."""
         dist = torch.distributed
         world = dist.get_world_size() if dist.is_initialized() else 1

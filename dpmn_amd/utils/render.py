@@ -4,7 +4,9 @@ ops.render_words_u8).  The semantics are FIXED HERE; integers on
 come from the PIL / FreeType atlas of utils/glyphs.py (`build_atlases`: one uint8 alpha atlas per font).  The one deliberate difference
 from PIL's own draw.text of the whole string: there is NO KERNING AND NO LIGATURE -- every glyph is placed by its own advance, as
 k_text_prior (csrc/visionlan.hip) lays its strings out.  A character without a glyph in the atlas (punctuation under voc_type 'all') is
-drawn as the blank of class 0; the label keeps it.  Pure NumPy: importable on any machine (PIL only inside build_atlases).
+drawn as the blank of class 0; the label keeps it.  Pure NumPy: importable on any machine (PIL only inside build_atlases and
+load_backgrounds).  Outline, drop shadow and photo backgrounds (main.py --train_words_fx) stand beside all this at the end of the module:
+draw_render_fx, check_render_fx, render_fx_u8.
 
 Columns of a params row (int64, 24 per sample):
    0 font        index of the atlas
@@ -127,10 +129,14 @@ def build_atlases(font_paths=None, heights=BASE_H):
     return Atlases(alpha, np.stack([c[1] for c in cells]), [c[2] for c in cells], [c[3] for c in cells])
 
 
-def words_setting(words, atlases, epoch):
+def words_setting(words, atlases, epoch, fx=None):
     """The value of the `train_words` field of the --train_state fingerprint (interfaces/base.py): the crc32 of the filtered word
-    list, the sorted font names and the epoch size."""
-    return {"crc32": zlib.crc32("\n".join(words).encode("utf-8")) & 0xFFFFFFFF, "fonts": sorted(atlases.names), "epoch": int(epoch)}
+    list, the sorted font names and the epoch size; with a RenderFx (main.py --train_words_fx), and only then, also its kinds, its
+    probability and the crc32 of its background pool (None without one)."""
+    s = {"crc32": zlib.crc32("\n".join(words).encode("utf-8")) & 0xFFFFFFFF, "fonts": sorted(atlases.names), "epoch": int(epoch)}
+    if fx:
+        s.update(fx_kinds=list(fx.kinds), fx_prob=float(fx.prob), fx_pool=None if fx.pool is None else int(fx.pool.crc32))
+    return s
 
 
 # -------------------------------------------------------------------------------------------------------------------------- draws
@@ -306,3 +312,310 @@ def render_u8(word_classes_, params_row, atlases):
     back = np.clip(back + grain(row[SEED], h * w).reshape(h, w, 1), 0, 255)
     a = alpha[:, :, None]
     return ((row[FG:FG + 3][None, None, :] * a + back * (255 - a) + 127) // 255).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------- outline, drop shadow, photo background (the fx path)
+# main.py --train_words_fx: three more stages of the MJSynth recipe BESIDE the plain renderer above, which stays as it is -- the draws
+# of a sample (`draw_render_fx`: draw_render's, then the fx draws), the domain of an fx row (`check_render_fx`) and the NumPy
+# restatement of the image (`render_fx_u8`), the CPU reference of k_render_words_fx (csrc/render.hip through ops.render_words_fx_u8).
+# The canvas is layout's, so render_meta serves both paths; with flags 0 the image is render_u8's byte for byte.
+#
+# Columns of an fx row (int64, 20 per sample); the columns of a kind whose flag bit is 0 are not read:
+#    0 flags      bit 0 outline, bit 1 shadow, bit 2 texture
+#    1 r          outline radius, 1 .. 3
+#    2 .. 4       outline R, G, B (drawn with an integer BT.601 luma at least MIN_CONTRAST away from the foreground's)
+#    5, 6         shadow offset dx, dy, each -3 .. 3, not both 0
+#    7 q          shadow opacity, 96 .. 255
+#    8 .. 10      shadow R, G, B
+#   11 photo      index of the photo in the pool
+#   12 .. 15      crop x0, y0, cw, ch inside that photo
+#   16 m          blend weight of the texture, 64 .. 224 (of 256)
+#   17 .. 19      spare, 0
+#
+# The image, with alpha(x, y) the plane of render_u8 and 0 outside the canvas:
+#   background  style 0 / 1 / 2 as render_u8 gives bg; with the texture bit the crop is sampled at the canvas pixel's centre --
+#               _axis_sample(x, cw, w, cw - 1) along x, _axis_sample(y, ch, h, ch - 1) along y, the integer bilinear blend of alpha
+#               per channel -> tex; bg = (tex * m + bg * (256 - m) + 128) >> 8; then + grain, clipped, as render_u8 -> c
+#   shadow      a_s = (alpha(x - dx, y - dy) * q + 127) // 255;  c = (shadow * a_s + c * (255 - a_s) + 127) // 255
+#   outline     a_o = the largest alpha(x + i, y + j) over the disk i * i + j * j <= r * r (5, 13, 29 points);  c blended the same way
+#   fill        (fg * alpha + c * (255 - alpha) + 127) // 255
+N_FX = 20
+(FX_FLAGS, FX_R, FX_OUTLINE, FX_DX, FX_DY, FX_Q, FX_SHADOW, FX_PHOTO, FX_X0, FX_Y0, FX_CW, FX_CH, FX_M) = (0, 1, 2, 5, 6, 7, 8, 11, 12, 13, 14, 15, 16)
+FX_KINDS = ("outline", "shadow", "texture")      # bit k of the flags: kind k
+R_MAX = 3                    # largest outline radius and shadow offset: the halo of the kernel's alpha tile
+Q_MIN, Q_MAX = 96, 255
+M_MIN, M_MAX = 64, 224
+POOL_SIDE = 512              # load_backgrounds: a photo's long side after the reduction
+POOL_MAX_PHOTOS, POOL_MAX_BYTES = 4096, 512 << 20
+
+
+class Backgrounds(object):
+    """The pool of background photos: pixels, 1-D uint8, the photos back to back (HWC, the layout of utils.resize.pack_ragged); table
+    (n, 3) int64 of (byte offset, h, w); crc32 of the pixels (the --train_state fingerprint).  images: (h, w, 3) uint8 arrays."""
+
+    def __init__(self, images):
+        images = [np.ascontiguousarray(im, np.uint8) for im in images]
+        if not images or any(im.ndim != 3 or im.shape[2] != 3 or min(im.shape[:2]) < 1 or max(im.shape[:2]) > MAX_SIDE for im in images):
+            raise ValueError("Backgrounds: one (h, w, 3) uint8 photo at least, sides 1 .. %d" % MAX_SIDE)
+        sizes = np.asarray([im.size for im in images], np.int64)
+        self.table = np.stack([np.cumsum(sizes) - sizes, [im.shape[0] for im in images], [im.shape[1] for im in images]], axis=1).astype(np.int64)
+        self.pixels = np.concatenate([im.reshape(-1) for im in images])
+        self.n_photos = len(images)
+        self.crc32 = zlib.crc32(self.pixels.tobytes()) & 0xFFFFFFFF
+        self._device = {}          # ops.render_words_fx_u8: the device copies, per device
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d["_device"] = {}
+        return d
+
+    def photo(self, i):
+        off, h, w = (int(v) for v in self.table[i])
+        return self.pixels[off:off + h * w * 3].reshape(h, w, 3)
+
+
+def load_backgrounds(dir_):
+    """The pool of --train_words_backgrounds: every file of the folder that PIL opens, in sorted name order, converted to RGB; a photo
+    whose long side passes POOL_SIDE is reduced with Image.thumbnail((512, 512), BICUBIC).  At most 4096 photos and 512 MB are kept;
+    what is left over is dropped with one printed line.  ValueError for a folder without a usable photo."""
+    from PIL import Image
+    images, total, dropped = [], 0, 0
+    names = [f for f in sorted(os.listdir(dir_)) if os.path.isfile(os.path.join(dir_, f))]
+    for k, f in enumerate(names):
+        try:
+            with Image.open(os.path.join(dir_, f)) as im:
+                im = im.convert("RGB")
+                if max(im.size) > POOL_SIDE:
+                    im.thumbnail((POOL_SIDE, POOL_SIDE), Image.BICUBIC)
+                a = np.asarray(im, np.uint8)
+        except Exception:          # whatever PIL raises on a file that is no image
+            continue
+        if len(images) >= POOL_MAX_PHOTOS or total + a.size > POOL_MAX_BYTES:
+            dropped = len(names) - k
+            break
+        images.append(a)
+        total += a.size
+    if not images:
+        raise ValueError("%s holds no image that PIL can open" % dir_)
+    if dropped:
+        print("train_words: the background pool is full (%d photos, %d bytes); the last %d files of %s are not read"
+              % (len(images), total, dropped, dir_))
+    print("train_words: %d background photos of %s, %d bytes" % (len(images), dir_, total))
+    return Backgrounds(images)
+
+
+class RenderFx(object):
+    """The fx setting of a run: kinds (of FX_KINDS, kept in that order), prob (each listed kind is on per sample with this probability,
+    independently), pool (a Backgrounds; texture needs it, and only texture takes it) and atlases (texture needs them: the crop is
+    drawn against the sample's canvas size)."""
+
+    def __init__(self, kinds, prob=0.5, pool=None, atlases=None):
+        self.kinds = fx_kinds(kinds, prob, pool is not None)
+        if pool is not None and atlases is None:
+            raise ValueError("RenderFx: texture needs the atlases (the crop is drawn against the canvas size)")
+        self.prob, self.pool, self.atlases = float(prob), pool, atlases
+
+
+def fx_kinds(kinds, prob, has_pool):
+    """The checks of --train_words_fx / --train_words_fx_prob / --train_words_backgrounds on the values alone -> the kinds in FX_KINDS'
+    order; ValueError with the one line main.py prints."""
+    kinds = [str(k) for k in kinds]
+    if not kinds or len(set(kinds)) != len(kinds) or any(k not in FX_KINDS for k in kinds):
+        raise ValueError("--train_words_fx takes a comma list of distinct kinds of %s, got %r" % (", ".join(FX_KINDS), ",".join(kinds)))
+    if not 0.0 <= float(prob) <= 1.0:          # (NaN fails both comparisons)
+        raise ValueError("--train_words_fx_prob must be a probability in 0 .. 1, got %r" % (prob,))
+    if ("texture" in kinds) != bool(has_pool):
+        raise ValueError("--train_words_fx texture and --train_words_backgrounds DIR go together: the texture is a crop of a photo of "
+                         "that folder")
+    return tuple(k for k in FX_KINDS if k in kinds)
+
+
+def draw_render_fx(words, n_fonts, rng, n=1, fx=()):
+    """draw_render plus the fx rows: -> (labels, classes, lengths, params, fx (n, 20) int64).  fx: a RenderFx, or () / None: no fx
+    draw at all and rows of zeros.  Sample by sample: exactly the draws of draw_render for ONE sample, then for every LISTED kind in
+    the order outline, shadow, texture one random() -- the kind is on where it is below prob -- followed at once, where the kind is
+    on, by its parameters, every one of them below(k) = int(random() * k):
+      outline   r - 1 (3); R, G, B (256 each), the triple drawn AGAIN until its luma is MIN_CONTRAST away from the foreground's
+      shadow    dx + 3, dy + 3 (7 each), the pair drawn AGAIN while both are 0; q - 96 (160); R, G, B (256 each)
+      texture   photo (the pool's size); cw - max(1, w // 2) (2 w - max(1, w // 2) + 1), then clipped to the photo's width pw;
+                ch = max(1, cw * h // w) clipped to the photo's height ph, no draw; x0 (pw - cw + 1); y0 (ph - ch + 1); m - 64 (161)
+                -- h, w: the sample's canvas size from layout
+    A kind that is not listed makes no draw; one that is listed and off makes the one."""
+    def below(k):
+        return min(int(rng.random() * k), k - 1)
+
+    n = int(n)
+    labels, classes, lengths, params = [], [], [], []
+    rows = np.zeros((max(n, 0), N_FX), np.int64)
+    if n < 1:
+        draw_render(words, n_fonts, rng, n)          # (its ValueError)
+    for i in range(n):
+        l, c, ln, p = draw_render(words, n_fonts, rng, 1)
+        labels += l
+        classes.append(c)
+        lengths.append(ln)
+        params.append(p)
+        if not fx:
+            continue
+        row, fg = rows[i], p[0, FG:FG + 3]
+        if "outline" in fx.kinds and rng.random() < fx.prob:
+            row[FX_FLAGS] |= 1
+            row[FX_R] = 1 + below(R_MAX)
+            while True:
+                col = [below(256) for _ in range(3)]
+                if abs(luma(col) - luma(fg)) >= MIN_CONTRAST:
+                    break
+            row[FX_OUTLINE:FX_OUTLINE + 3] = col
+        if "shadow" in fx.kinds and rng.random() < fx.prob:
+            row[FX_FLAGS] |= 2
+            while True:
+                dx, dy = below(2 * R_MAX + 1) - R_MAX, below(2 * R_MAX + 1) - R_MAX
+                if dx or dy:
+                    break
+            row[FX_DX], row[FX_DY] = dx, dy
+            row[FX_Q] = Q_MIN + below(Q_MAX - Q_MIN + 1)
+            row[FX_SHADOW:FX_SHADOW + 3] = [below(256) for _ in range(3)]
+        if "texture" in fx.kinds and rng.random() < fx.prob:
+            row[FX_FLAGS] |= 4
+            h, w = layout(c[0, :ln[0]].tolist(), p[0], fx.atlases)[:2]
+            k = below(fx.pool.n_photos)
+            ph, pw = int(fx.pool.table[k, 1]), int(fx.pool.table[k, 2])
+            lo = max(1, w // 2)
+            cw = min(lo + below(2 * w - lo + 1), pw)
+            ch = min(max(1, cw * h // w), ph)
+            row[FX_PHOTO], row[FX_CW], row[FX_CH] = k, cw, ch
+            row[FX_X0] = below(pw - cw + 1)
+            row[FX_Y0] = below(ph - ch + 1)
+            row[FX_M] = M_MIN + below(M_MAX - M_MIN + 1)
+    return labels, np.concatenate(classes), np.concatenate(lengths), np.concatenate(params), rows
+
+
+def check_render_fx(fx, pool=None, n=None):
+    """ValueError for an fx row outside its domain or a crop that leaves its photo (what the kernel's entry point rejects too); only
+    the columns of the kinds whose flag bit is set are read, the spare columns are 0 -> the rows as (n, 20) int64."""
+    fx = np.ascontiguousarray(fx, np.int64)
+    if fx.ndim != 2 or fx.shape[1] != N_FX or fx.shape[0] < 1 or (n is not None and fx.shape[0] != n):
+        raise ValueError("render_fx: fx (n, %d) with one row per sample expected, got %s" % (N_FX, fx.shape))
+    fl = fx[:, FX_FLAGS]
+    if fl.min() < 0 or fl.max() > 7 or fx[:, FX_M + 1:].any():
+        raise ValueError("render_fx: flags outside 0 .. 7, or a spare column that is not 0")
+    o, s, t = fx[(fl & 1) != 0], fx[(fl & 2) != 0], fx[(fl & 4) != 0]
+    if o.size and not (o[:, FX_R].min() >= 1 and o[:, FX_R].max() <= R_MAX and o[:, FX_OUTLINE:FX_OUTLINE + 3].min() >= 0
+                       and o[:, FX_OUTLINE:FX_OUTLINE + 3].max() <= 255):
+        raise ValueError("render_fx: an outline outside its domain (radius 1 .. %d, colour 0 .. 255)" % R_MAX)
+    if s.size and not (np.abs(s[:, FX_DX:FX_DY + 1]).max() <= R_MAX and (s[:, FX_DX:FX_DY + 1] != 0).any(axis=1).all()
+                       and s[:, FX_Q].min() >= Q_MIN and s[:, FX_Q].max() <= Q_MAX and s[:, FX_SHADOW:FX_SHADOW + 3].min() >= 0
+                       and s[:, FX_SHADOW:FX_SHADOW + 3].max() <= 255):
+        raise ValueError("render_fx: a shadow outside its domain (dx, dy in -%d .. %d and not both 0, q %d .. %d, colour 0 .. 255)"
+                         % (R_MAX, R_MAX, Q_MIN, Q_MAX))
+    if t.size:
+        if pool is None:
+            raise ValueError("render_fx: a row has the texture bit and there is no pool of photos")
+        k = t[:, FX_PHOTO]
+        if k.min() < 0 or k.max() >= pool.n_photos:
+            raise ValueError("render_fx: a photo index outside the pool (0 .. %d)" % (pool.n_photos - 1))
+        ph, pw = pool.table[k, 1], pool.table[k, 2]
+        if not ((t[:, FX_X0:FX_Y0 + 1] >= 0).all() and (t[:, FX_CW:FX_CH + 1] >= 1).all() and (t[:, FX_X0] + t[:, FX_CW] <= pw).all()
+                and (t[:, FX_Y0] + t[:, FX_CH] <= ph).all()):
+            raise ValueError("render_fx: a crop leaves its photo (x0, y0 >= 0, cw, ch >= 1, x0 + cw <= the photo's width, y0 + ch <= its height)")
+        if t[:, FX_M].min() < M_MIN or t[:, FX_M].max() > M_MAX:
+            raise ValueError("render_fx: a blend weight outside %d .. %d" % (M_MIN, M_MAX))
+    return fx
+
+
+def _alpha_plane(cls, row, atlases):
+    """The alpha plane (h, w) int64 of render_u8 -- the same statements, up to the plane."""
+    f, gh, s = int(row[FONT]), int(row[GH]), int(row[SHEAR])
+    A = int(atlases.height[f])
+    h, w, pens, advs, planes, room, x0 = layout(cls, row, atlases)
+    n = len(cls)
+    tw = max(pens[n] - int(row[SPACING]), 1)
+    ys, xs = np.arange(h, dtype=np.int64)[:, None], np.arange(w, dtype=np.int64)[None, :]
+    v = np.broadcast_to(ys - int(row[M_TOP]), (h, w))
+    u = xs - ((s * (int(row[M_TOP]) + gh - 1 - ys)) >> 16) - x0
+    pens_a = np.asarray(pens[:n], np.int64)
+    k = np.clip(np.searchsorted(pens_a, u, side="right") - 1, 0, n - 1)
+    ug = u - pens_a[k]
+    inside = (v >= 0) & (v < gh) & (u >= 0) & (u < tw) & (ug >= 0) & (ug < np.asarray(advs, np.int64)[k])
+    pk, ck = np.asarray(planes)[k], np.asarray(cls)[k]
+    cell_w = atlases.advance[f][pk, ck].astype(np.int64)
+    x_0, x_1, fx = _axis_sample(np.where(inside, ug, 0), A, gh, np.maximum(cell_w - 1, 0))
+    y_0, y_1, fy = _axis_sample(np.where(inside, v, 0), A, gh, A - 1)
+    at = atlases.alpha[f].astype(np.int64)
+    top = at[pk, ck, y_0, x_0] * (65536 - fx) + at[pk, ck, y_0, x_1] * fx
+    bot = at[pk, ck, y_1, x_0] * (65536 - fx) + at[pk, ck, y_1, x_1] * fx
+    return np.where(inside, (top * (65536 - fy) + bot * fy + (1 << 31)) >> 32, 0)
+
+
+def _shifted(alpha, dx, dy):
+    """alpha(x + dx, y + dy) as a plane, 0 where that leaves the canvas."""
+    h, w = alpha.shape
+    out = np.zeros_like(alpha)
+    ys, xs = slice(max(0, -dy), min(h, h - dy)), slice(max(0, -dx), min(w, w - dx))
+    if ys.start < ys.stop and xs.start < xs.stop:
+        out[ys, xs] = alpha[ys.start + dy:ys.stop + dy, xs.start + dx:xs.stop + dx]
+    return out
+
+
+def _fx_planes(alpha, fxr):
+    """(a_s, a_o): the shadow's and the outline's alpha planes of one sample, zeros for a kind whose flag bit is 0."""
+    flags = int(fxr[FX_FLAGS])
+    a_s = a_o = np.zeros_like(alpha)
+    if flags & 2:
+        a_s = (_shifted(alpha, -int(fxr[FX_DX]), -int(fxr[FX_DY])) * int(fxr[FX_Q]) + 127) // 255
+    if flags & 1:
+        r = int(fxr[FX_R])
+        for j in range(-r, r + 1):
+            for i in range(-r, r + 1):
+                if i * i + j * j <= r * r:
+                    a_o = np.maximum(a_o, _shifted(alpha, i, j))
+    return a_s, a_o
+
+
+def _render_fx(cls, row, fxr, atlases, pool, grain_plane=None):
+    """render_fx_u8 behind its checks: the fx row is taken as it is (a test may pass m = 256, the crop's own bytes), grain_plane
+    (h, w) replaces the grain of the row's seed."""
+    alpha = _alpha_plane(cls, row, atlases)
+    h, w = alpha.shape
+    ys, xs = np.arange(h, dtype=np.int64)[:, None], np.arange(w, dtype=np.int64)[None, :]
+    bg, bg2 = row[BG:BG + 3][None, None, :], row[BG2:BG2 + 3][None, None, :]
+    style, flags = int(row[STYLE]), int(fxr[FX_FLAGS])
+    if style == 0:
+        back = np.broadcast_to(bg, (h, w, 3))
+    else:
+        t, m = (xs, max(w - 1, 1)) if style == 1 else (ys, max(h - 1, 1))
+        back = np.broadcast_to((bg * (m - t[:, :, None]) + bg2 * t[:, :, None] + m // 2) // m, (h, w, 3))
+    if flags & 4:
+        x0, y0, cw, ch, m = (int(fxr[c]) for c in (FX_X0, FX_Y0, FX_CW, FX_CH, FX_M))
+        crop = pool.photo(int(fxr[FX_PHOTO]))[y0:y0 + ch, x0:x0 + cw].astype(np.int64)
+        x_0, x_1, fx = _axis_sample(xs, cw, w, cw - 1)
+        y_0, y_1, fy = _axis_sample(ys, ch, h, ch - 1)
+        fx, fy = fx[:, :, None], fy[:, :, None]
+        top = crop[y_0, x_0] * (65536 - fx) + crop[y_0, x_1] * fx
+        bot = crop[y_1, x_0] * (65536 - fx) + crop[y_1, x_1] * fx
+        tex = (top * (65536 - fy) + bot * fy + (1 << 31)) >> 32
+        back = (tex * m + back * (256 - m) + 128) >> 8
+    g = grain(row[SEED], h * w).reshape(h, w) if grain_plane is None else np.asarray(grain_plane, np.int64).reshape(h, w)
+    c = np.clip(back + g[:, :, None], 0, 255)
+
+    def over(colour, a):
+        a = a[:, :, None]
+        return (np.asarray(colour, np.int64)[None, None, :] * a + c * (255 - a) + 127) // 255
+
+    a_s, a_o = _fx_planes(alpha, fxr)
+    c = over(fxr[FX_SHADOW:FX_SHADOW + 3], a_s)
+    c = over(fxr[FX_OUTLINE:FX_OUTLINE + 3], a_o)
+    return over(row[FG:FG + 3], alpha).astype(np.uint8)
+
+
+def render_fx_u8(word_classes_, params_row, fx_row, atlases, pool=None):
+    """One sample -> its (h, w, 3) uint8 image with outline, shadow and photo background (the comment above states every formula):
+    word_classes_ and params_row as render_u8 takes them, fx_row one row of draw_render_fx, pool the Backgrounds (None: no row may
+    have the texture bit).  The canvas is render_u8's; an outline or a shadow that reaches past a margin is clipped at its edge."""
+    cls = [int(c) for c in word_classes_]
+    row = np.asarray(params_row, np.int64)
+    if not 1 <= len(cls) <= MAX_LEN:
+        raise ValueError("render: a word has a length outside 1 .. %d" % MAX_LEN)
+    check_render(np.pad(np.asarray(cls, np.int32), (0, MAX_LEN - len(cls)))[None], [len(cls)], row[None], atlases)
+    fxr = check_render_fx(np.asarray(fx_row, np.int64)[None], pool)[0]
+    return _render_fx(cls, row, fxr, atlases, pool)

@@ -559,6 +559,22 @@ int dpmn_render_words_u8(const int* classes, const int* lengths, const long long
                          const int* atlas_h, const long long* meta, const int* tiles, int n_tiles, unsigned char* out_packed, long out_bytes,
                          int B, int n_fonts, int GH, int GW, const int* host_classes, const int* host_lengths, const long long* host_params,
                          const long long* host_meta, dpmn_stream_t stream);
+/* The same crops with an outline, a drop shadow and a photo background (render.hip; main.py --train_words_fx), byte for byte
+ * utils/render.py render_fx_u8; every argument of dpmn_render_words_u8 keeps its meaning, the canvas sizes, the 8 x 128 tile table and
+ * the packed layout are the same.  fx: device int64 (B, 20), the rows of utils/render.py draw_render_fx [flags (bit 0 outline, 1 shadow,
+ * 2 texture), r, outline R G B, dx, dy, q, shadow R G B, photo, crop x0 y0 cw ch, m, 3 spare]; a row of zeros gives the image of
+ * dpmn_render_words_u8.  pool_u8: device uint8, the background photos back to back (HWC), pool_bytes its size; photos: device int64
+ * (n_photos, 3), per photo [byte offset in pool_u8, h, w]; n_photos = 0 (pool_u8 and both tables may then be null): no row may have the
+ * texture bit.  host_fx / host_photos: the HOST copies, checked with the others before the launch: flags outside 0 .. 7, and for a kind
+ * whose bit is set a radius outside 1 .. 3, an offset outside -3 .. 3 or (0, 0), q outside 96 .. 255, a colour outside 0 .. 255, a photo
+ * index outside the pool, a crop that leaves its photo, m outside 64 .. 224, a photo outside the pool's bytes is an error.  The kernel
+ * clamps what it reads all the same.  One launch. */
+int dpmn_render_words_fx_u8(const int* classes, const int* lengths, const long long* params, const long long* fx, const unsigned char* atlas_u8,
+                            const int* advance, const int* atlas_h, const long long* meta, const int* tiles, int n_tiles,
+                            const unsigned char* pool_u8, long pool_bytes, const long long* photos, int n_photos, unsigned char* out_packed,
+                            long out_bytes, int B, int n_fonts, int GH, int GW, const int* host_classes, const int* host_lengths,
+                            const long long* host_params, const long long* host_fx, const long long* host_meta, const long long* host_photos,
+                            dpmn_stream_t stream);
 /* A wide text line as overlapping windows of the model's LR size (tile.hip; utils/tile.py holds the plan arithmetic and the numpy
  * restatement).  resize_windows: a RAGGED batch in the packed layout of dpmn_resize_ragged_u8 -> every image resized with PIL's
  * fixed-point bicubic (the arithmetic of dpmn_resize_ragged_u8, byte for byte Image.resize((w_line, lr_h), BICUBIC)) to the height lr_h

@@ -134,14 +134,50 @@ TRAIN_WORDS_OR_HR_DIR = ("main.py: --train_words and --train_hr_dir are two sour
 TRAIN_WORDS_FONTS_NEEDS = "main.py: --train_words_fonts needs --train_words: the fonts are those the words are rendered in"
 
 
+TRAIN_WORDS_FX_NEEDS = ("main.py: --train_words_fx and --train_words_backgrounds need --train_words: outline, shadow and texture are drawn "
+                        "on the rendered words")
+
+
+def train_words_fx(args, atlases=None):
+    """--train_words_fx KINDS [--train_words_fx_prob P] [--train_words_backgrounds DIR], checked -> the utils.render.RenderFx of the
+    run (atlases: those the words are rendered from), or None without the flags.  Every problem is a SystemExit of one line: the flags
+    without --train_words, an unknown kind, a probability outside 0 .. 1, texture without the folder or the folder without texture, a
+    folder that is missing or holds no image PIL can open."""
+    kinds, folder = getattr(args, "train_words_fx", None), getattr(args, "train_words_backgrounds", None)
+    if not kinds and not folder:
+        return None
+    if not getattr(args, "train_words", None):
+        raise SystemExit(TRAIN_WORDS_FX_NEEDS)
+    if not kinds:
+        raise SystemExit("main.py: --train_words_backgrounds needs --train_words_fx texture: the photos are the texture's backgrounds")
+    from dpmn_amd.utils import render
+    kinds = [k.strip() for k in str(kinds).split(",")]
+    prob = getattr(args, "train_words_fx_prob", None)
+    prob = 0.5 if prob is None else prob
+    try:
+        render.fx_kinds(kinds, prob, bool(folder))
+    except ValueError as e:
+        raise SystemExit("main.py: %s" % e)
+    pool = None
+    if folder:
+        if not os.path.isdir(folder):
+            raise SystemExit("main.py: --train_words_backgrounds %s is not a directory" % folder)
+        try:
+            pool = render.load_backgrounds(folder)
+        except ValueError as e:
+            raise SystemExit("main.py: --train_words_backgrounds %s" % e)
+    return render.RenderFx(kinds, prob, pool, atlases)
+
+
 def train_words_source(args, voc_type):
-    """--train_words FILE [--train_words_fonts DIR] [--train_words_epoch N] -> (words, atlases, epoch size), or None without the flag.
-    Every problem is a SystemExit of one line: the two-sources conflict, a missing file, a file without a usable word, a font directory
-    without a usable font, an epoch size below 1."""
+    """--train_words FILE [--train_words_fonts DIR] [--train_words_epoch N] -> (words, atlases, epoch size, fx), or None without the
+    flag; fx: the RenderFx of --train_words_fx, or None.  Every problem is a SystemExit of one line: the two-sources conflict, a missing
+    file, a file without a usable word, a font directory without a usable font, an epoch size below 1, and those of train_words_fx."""
     path, fonts = getattr(args, "train_words", None), getattr(args, "train_words_fonts", None)
     if not path:
         if fonts:
             raise SystemExit(TRAIN_WORDS_FONTS_NEEDS)
+        train_words_fx(args)
         return None
     if getattr(args, "train_hr_dir", None):
         raise SystemExit(TRAIN_WORDS_OR_HR_DIR)
@@ -164,7 +200,7 @@ def train_words_source(args, voc_type):
         atlases = render.build_atlases(files)
     except ValueError:
         raise SystemExit("main.py: --train_words_fonts %s holds no font that PIL can open" % fonts)
-    return words, atlases, epoch
+    return words, atlases, epoch, train_words_fx(args, atlases)
 
 
 def main(config, args):
@@ -173,6 +209,8 @@ def main(config, args):
         raise SystemExit(TRAIN_WORDS_OR_HR_DIR)
     if getattr(args, "train_words_fonts", None) and not words_on:
         raise SystemExit(TRAIN_WORDS_FONTS_NEEDS)
+    if not words_on:
+        train_words_fx(args)
     if getattr(args, "cutblur", False) and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None) or words_on):
         raise SystemExit("main.py: --cutblur needs --manmade_degrade (or --train_hr_dir): it mixes columns of the HR image into the "
                          "synthesised LR image")
@@ -474,6 +512,13 @@ if __name__ == '__main__':
                         help='with --train_words: every *.ttf / *.otf of this directory is a font (default: PIL\'s built-in font)')
     parser.add_argument('--train_words_epoch', type=int, default=10000, metavar='N',
                         help='with --train_words: the number of rendered samples that counts as one epoch')
+    parser.add_argument('--train_words_fx', type=str, default=None, metavar='KINDS',
+                        help='with --train_words: a comma list of outline (a border of 1 .. 3 pixels in a contrasting colour), shadow (a '
+                             'drop shadow up to 3 pixels away) and texture (a crop of a photo of --train_words_backgrounds blended into '
+                             'the background); each listed kind is on per sample with probability --train_words_fx_prob')
+    parser.add_argument('--train_words_fx_prob', type=float, default=0.5, help='with --train_words_fx: the probability of each kind per sample')
+    parser.add_argument('--train_words_backgrounds', type=str, default=None, metavar='DIR',
+                        help='with --train_words_fx texture: a folder of photos (whatever PIL opens; reduced to 512 pixels on the long side)')
     args = parser.parse_args()
     if args.train_words and args.train_hr_dir:
         parser.error(TRAIN_WORDS_OR_HR_DIR[len("main.py: "):])
