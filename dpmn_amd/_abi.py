@@ -172,6 +172,8 @@ SIGNATURES = {
     "dpmn_tatt_encoder_layer_f32": (_i, [fp, fp, _PP, fp, _i, _i, _i, _i, fp]),
     "dpmn_cross_attn_f32": (_i, [fp, fp, fp, fp, fp, _i, _i, _i, _i, _i, fp]),
     "dpmn_add_layernorm64_f32": (_i, [fp, fp, fp, fp, fp, fp, fp, fp, _f, _i, C.c_long, fp]),
+    "dpmn_cross_attn_qproj_f32": (_i, [fp, fp, fp, fp, fp, fp, fp, fp, _i, _i, _i, _i, _i, fp]),
+    "dpmn_tatt_dec_tail_f32": (_i, [fp, fp, C.POINTER(TattDecLayer), fp, fp, fp, fp, _f, _i, C.c_long, fp]),
     "dpmn_gru_gate_f32": (_i, [fp, fp, fp, fp, C.c_long, _i, _i, fp]),
     "dpmn_to_mask_f32": (_i, [fp, C.c_long, fp, _i, _i, _i, fp]),
     "dpmn_mha32_f32": (_i, [fp, fp, _i, _i, _i, _f, fp]),

@@ -93,8 +93,9 @@ int dpmn_psn_trunk_f32(const dpmn_psn_weights* w, const float* b1, const float* 
 // ---------------------------------------------------------------------------------- TATT text-prior interpreter
 // TPInterpreter.forward (tatt.py:196-237) + InfoTransformer (transformer_v2.py: one encoder layer over the 26 text slots, three
 // decoder layers whose queries are the image feature map + the cached query embedding, mean of the normalised layer outputs):
-// 2 + 3 x 9 launches from one C call.  x: the (B * S, t_emb) text-prior rows, qe: (B * L, 64) query embedding (quirk Q5: computed
-// once per batch size by the host mirror), pos: (S, 64) sinusoid rows; out tp (B * L, 64), pw (B, L, S) or NULL.
+// 2 + 3 x 4 launches from one C call (2 + 3 x 9 where the fused decoder kernels are not built).  x: the (B * S, t_emb) text-prior
+// rows, qe: (B * L, 64) query embedding (quirk Q5: computed once per batch size by the host mirror), pos: (S, 64) sinusoid rows; out
+// tp (B * L, 64), pw (B, L, S) or NULL.
 namespace {
 struct TpiWs {
   float *src, *mem, *q, *k, *v, *o, *t1, *out[2], *f;
@@ -138,9 +139,21 @@ int dpmn_tatt_interpreter_f32(const dpmn_tatt_interp_weights* w, const float* x,
   RUN(dpmn_small_linear_f32(x, nullptr, 0, w->fc_in_w, w->fc_in_b, s.src, BS, E, t_emb, DPMN_ACT_PRELU, w->fc_in_slope, stream));
   RUN(dpmn_tatt_encoder_layer_f32(s.src, pos, w->enc, s.mem, B, S, E, w->nhead, stream));
   const float* out = b1;
+  // two launches per layer behind k and v where the fused kernels are built (d_model 64, 4 heads, <= 32 text slots): the q projection
+  // runs inside the attention launch and everything after the attention in dpmn_tatt_dec_tail_f32; s.q, s.t1 and s.f stay unused
+  const bool fused = E == 64 && w->nhead == 4 && S <= 32;
   for (int li = 0; li < w->n_dec; ++li) {
     const dpmn_tatt_dec_layer& d = w->dec[li];
     const bool last = li == w->n_dec - 1;
+    if (fused) {
+      RUN(dpmn_small_linear_f32(s.mem, pos, S, d.wk, d.bk, s.k, BS, E, E, DPMN_ACT_NONE, 0.f, stream));
+      RUN(dpmn_small_linear_f32(s.mem, nullptr, 0, d.wv, d.bv, s.v, BS, E, E, DPMN_ACT_NONE, 0.f, stream));
+      RUN(dpmn_cross_attn_qproj_f32(out, qe, d.wq, d.bq, s.k, s.v, s.o, last ? pw : nullptr, B, L, S, E, w->nhead, stream));
+      float* o2 = s.out[li & 1];
+      RUN(dpmn_tatt_dec_tail_f32(s.o, out, &d, o2, w->dec_norm_w, w->dec_norm_b, tp, 1.0f / w->n_dec, li > 0 ? 1 : 0, BL, stream));
+      out = o2;
+      continue;
+    }
     // cross attention: q = (tgt + query_embed) Wq, k = (memory + pos) Wk, v = memory Wv (transformer_v2.py:826-838)
     RUN(dpmn_add_linear_f32(out, qe, d.wq, d.bq, s.q, BL, E, E, DPMN_ACT_NONE, stream));
     RUN(dpmn_small_linear_f32(s.mem, pos, S, d.wk, d.bk, s.k, BS, E, E, DPMN_ACT_NONE, 0.f, stream));

@@ -34,7 +34,8 @@ const char* const kTagNames[PT_COUNT] = {
     "k_conv_igemm<128,128>", "k_conv_igemm<64,64>", "k_conv_igemm<128,16|32>", "k_conv_splitk_reduce", "k_conv_halo", "k_conv_halo_c4",
     "k_gemm_pw", "k_gemm_wstat|rowreg", "k_gemm_kloop", "k_dwconv_gelu", "k_window_attn8_mfma", "k_window_attn<2|4>", "k_ln_qkv_window_attn",
     "k_bigru", "k_mha32", "k_patch_embed_ln", "k_sk_gate", "k_tail_conv2", "k_gemm_wstat|rowreg<LN prologue>", "k_conv_igemm_sk", "k_ln_qkv_window_attn_bwd", "k_window_attn_bwd_mfma",
-    "k_conv_wgrad", "k_gemm_tn_reg", "k_tn_reduce_multi", "k_dwconv_bwd", "k_wgrad_unpack_multi", "k_conv_pack_multi", "k_affine_act_bwd", "k_ln_bwd", "k_window_attn_mfma<4|8|16,32>"};
+    "k_conv_wgrad", "k_gemm_tn_reg", "k_tn_reduce_multi", "k_dwconv_bwd", "k_wgrad_unpack_multi", "k_conv_pack_multi", "k_affine_act_bwd", "k_ln_bwd", "k_window_attn_mfma<4|8|16,32>", "k_cross_attn",
+    "k_tatt_dec_tail"};
 struct Rec { int tag; double flops, bytes; };
 struct Prof {
   int cap = 0, count = 0, limit = 0;      // cap: allocated event pairs (only grows); limit: max_launches of the current dpmn_profile_begin

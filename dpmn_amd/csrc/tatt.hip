@@ -4,6 +4,7 @@
 //     the input projection (conv1x1 folded with W_ih) is a separate implicit-GEMM launch;
 //   * TPInterpreter pieces (tatt.py:193-223, transformer_v2.py:198-244, 455-469, 806-833): tiny linear,
 //     fused 26-token encoder layer (one workgroup per image), 1024x26 cross attention, add+LayerNorm,
+//     the decoder layer in two launches (q projection + cross attention; out_proj, norms and FFN after it),
 //     and the gate step of the query-embedding GRU (batch_first quirk Q5).
 // Token tensors here are (N, L, E) row-major (N = image, L = 26 text slots or 1024 pixels, E = 64):
 // the reference's (L, N, E) differs only by a transpose no kernel needs.
@@ -379,6 +380,285 @@ __global__ __launch_bounds__(256) void k_add_layernorm64(const float* __restrict
   }
 }
 
+// ---------------------------------------------------------------------------------- decoder layer after the attention (E = 64)
+// out_proj + residual -> norm2 -> linear1 + ReLU -> linear2 + residual -> norm3 (-> decoder.norm, scaled into acc_out) of a
+// TransformerDecoderLayer.forward_post (transformer_v2.py:838-849) in ONE launch, in the rows-in-registers form of k_gemm_rowreg /
+// k_sk_mlp_in (gemm.hip): a wave owns a 16-row tile, lane (lr = l & 15, kq = l >> 4) holds x[row lr][16 c + 4 kq .. + 3] as the MFMA B
+// operand, the weights' rows are the A operand from an LDS copy, and the accumulator layout (y[row lr][16 nt + 4 kq + r]) IS the B-operand
+// layout of the next product: nothing between the four row reads (o, residual, and acc_out when it accumulates) and the two row writes
+// goes through memory.  The LayerNorms are nn.LayerNorm's two passes over the row, whose 64 values sit in the four kq partners of a lane.
+// Blocks are persistent over tiles; the next tile's rows are requested before the current tile's MFMAs and its residual rows before the
+// current tile's stores (vmcnt retires in order -- see k_sk_mlp_in).  Rows are clamped, never predicated: the lanes past M in a ragged
+// last tile recompute and rewrite row M - 1 with the value its own lane writes (every lane reads a row before any lane stores it, so
+// y may be the residual's buffer and the duplicates of an accumulating acc_out add once).
+struct DecTailW {
+  const float *out_w, *out_b, *n2_w, *n2_b, *l1_w, *l1_b, *l2_w, *l2_b, *n3_w, *n3_b, *dn_w, *dn_b;
+};
+constexpr int DT_LDW = 64 + 4;      // weight row stride in LDS (floats): conflict-free ds_read_b128 of 16 rows x 4 k quads
+constexpr size_t DT_SMEM = (size_t)(3 * 64 * DT_LDW + 9 * 64) * sizeof(float);
+template <int E, int ACC>      // ACC: 0 = y only, 1 = acc_out = alpha * LN'(y), 2 = acc_out += alpha * LN'(y)
+__global__ __launch_bounds__(256, 2) void k_tatt_dec_tail(const float* __restrict__ o, const float* res, DecTailW w, float* y,
+                                                          float* acc_out, float alpha, int M) {
+  static_assert(E == 64, "built for d_model = 64: four 16-wide k chunks = four 16-wide n tiles");
+  constexpr int KC = E / 16, NT = E / 16, LDW = DT_LDW;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* Ws = smem;                        // [3][E][LDW]: out_proj, linear1, linear2
+  float* pv = Ws + 3 * E * LDW;            // [9][E]: out_b, l1_b, l2_b, n2_w, n2_b, n3_w, n3_b, dn_w, dn_b
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, kq = lane >> 4;
+  const int tiles = (M + 15) / 16;
+  const int stride = gridDim.x * 4;
+  int tile = blockIdx.x * 4 + wave;
+  auto row_of = [&](int t_) -> size_t {
+    const int m = (t_ < tiles ? t_ : tiles - 1) * 16 + lr;
+    return (size_t)(m < M ? m : M - 1);
+  };
+  f32x4 xr[KC], rr[NT], ta[NT];
+  auto load_rows = [&](int t_) {
+    const float* p = o + row_of(t_) * E + 4 * kq;
+#pragma unroll
+    for (int c = 0; c < KC; ++c) xr[c] = *reinterpret_cast<const f32x4*>(p + 16 * c);
+  };
+  auto load_res = [&](int t_) {
+    const size_t ro = row_of(t_) * E + 4 * kq;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      rr[nt] = *reinterpret_cast<const f32x4*>(res + ro + 16 * nt);
+      if (ACC == 2) ta[nt] = *reinterpret_cast<const f32x4*>(acc_out + ro + 16 * nt);
+    }
+  };
+  load_rows(tile);
+  load_res(tile);
+  for (int i = tid; i < 3 * E * (E / 4); i += 256) {
+    const int mat = i / (E * (E / 4)), j = i % (E * (E / 4)), r = j / (E / 4), c4 = (j % (E / 4)) * 4;
+    const float* src = mat == 0 ? w.out_w : (mat == 1 ? w.l1_w : w.l2_w);
+    *reinterpret_cast<float4*>(Ws + (mat * E + r) * LDW + c4) = *reinterpret_cast<const float4*>(src + (size_t)r * E + c4);
+  }
+  if (tid < E) {
+    pv[tid] = w.out_b[tid]; pv[E + tid] = w.l1_b[tid]; pv[2 * E + tid] = w.l2_b[tid];
+    pv[3 * E + tid] = w.n2_w[tid]; pv[4 * E + tid] = w.n2_b[tid]; pv[5 * E + tid] = w.n3_w[tid]; pv[6 * E + tid] = w.n3_b[tid];
+    if (ACC) { pv[7 * E + tid] = w.dn_w[tid]; pv[8 * E + tid] = w.dn_b[tid]; }
+  }
+  __syncthreads();
+
+  // acc = W b for one 64 x 64 weight: A fragments double-buffered one k chunk ahead (the fences keep hipcc from hoisting every chunk's
+  // LDS reads to the top, as in k_gemm_rowreg)
+  auto mm = [&](const float* W, const f32x4 (&b)[KC], f32x4 (&acc)[NT]) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float* wa = W + lr * LDW + 4 * kq;
+    f32x4 wf[2][NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) wf[0][nt] = *reinterpret_cast<const f32x4*>(wa + 16 * nt * LDW);
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+      if (c + 1 < KC) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) wf[(c + 1) & 1][nt] = *reinterpret_cast<const f32x4*>(wa + 16 * nt * LDW + 16 * (c + 1));
+      }
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[nt] = mfma16(wf[c & 1][nt][s4], b[c][s4], acc[nt]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // v = LayerNorm(v) * g + b over the row: the expression of k_add_layernorm64, the sums over the lane's 16 values, then the 4 partners
+  auto ln = [&](f32x4 (&v)[NT], const float* g, const float* b) {
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) { s0 += v[nt][0] + v[nt][1]; s1 += v[nt][2] + v[nt][3]; }
+    float s_ = s0 + s1;
+    s_ += xshfl<16>(s_); s_ += xshfl<32>(s_);
+    const float mean = s_ * (1.0f / E);
+    float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      v[nt][0] -= mean; v[nt][1] -= mean; v[nt][2] -= mean; v[nt][3] -= mean;
+      q0 = fmaf(v[nt][0], v[nt][0], q0); q1 = fmaf(v[nt][1], v[nt][1], q1); q2 = fmaf(v[nt][2], v[nt][2], q2); q3 = fmaf(v[nt][3], v[nt][3], q3);
+    }
+    float q = (q0 + q1) + (q2 + q3);
+    q += xshfl<16>(q); q += xshfl<32>(q);
+    const float rstd = 1.0f / sqrtf(q * (1.0f / E) + 1e-5f);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const f32x4 g4 = *reinterpret_cast<const f32x4*>(g + 16 * nt + 4 * kq), b4 = *reinterpret_cast<const f32x4*>(b + 16 * nt + 4 * kq);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[nt][r] = v[nt][r] * rstd * g4[r] + b4[r];
+    }
+  };
+
+  for (; tile < tiles; tile += stride) {
+    const size_t off = row_of(tile) * E + 4 * kq;
+    f32x4 xb[KC], acc[NT], h[NT], tc[NT];
+#pragma unroll
+    for (int c = 0; c < KC; ++c) xb[c] = xr[c];
+    __builtin_amdgcn_sched_barrier(0);
+    load_rows(tile + stride);                  // the next tile's attention rows fly during this tile's MFMAs
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- t1 = o Wo^T + bo + residual ; o1 = norm2(t1)
+    mm(Ws, xb, acc);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      h[nt] = acc[nt] + *reinterpret_cast<const f32x4*>(pv + 16 * nt + 4 * kq) + rr[nt];
+      if (ACC == 2) tc[nt] = ta[nt];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_res(tile + stride);                   // the next tile's residual (and acc_out) rows, ahead of this tile's stores
+    __builtin_amdgcn_sched_barrier(0);
+    ln(h, pv + 3 * E, pv + 4 * E);
+    // ---- f = relu(o1 W1^T + b1) ; t2 = f W2^T + b2 + o1 ; y = norm3(t2)
+    mm(Ws + E * LDW, h, acc);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const f32x4 b4 = *reinterpret_cast<const f32x4*>(pv + E + 16 * nt + 4 * kq);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { const float a = acc[nt][r] + b4[r]; xb[nt][r] = a > 0.f ? a : 0.f; }
+    }
+    mm(Ws + 2 * E * LDW, xb, acc);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) h[nt] = acc[nt] + *reinterpret_cast<const f32x4*>(pv + 2 * E + 16 * nt + 4 * kq) + h[nt];
+    ln(h, pv + 5 * E, pv + 6 * E);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) *reinterpret_cast<f32x4*>(y + off + 16 * nt) = h[nt];
+    if (ACC) {                                 // decoder.norm of the layer output, scaled into the mean over the layers
+      ln(h, pv + 7 * E, pv + 8 * E);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        f32x4 v = h[nt] * alpha;
+        if (ACC == 2) v = tc[nt] + v;
+        *reinterpret_cast<f32x4*>(acc_out + off + 16 * nt) = v;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------- q projection + cross attention (S <= 32 keys)
+// k_cross_attn with q = (x + qe) Wq^T + bq computed by the block itself: every wave projects its own 64 query rows with MFMAs (four
+// 16-row tiles in the layout of k_tatt_dec_tail, Wq staged once per block) into a wave-private LDS tile and reads its lane's row back
+// from there -- the (N, L, E) q tensor and the launch that wrote it are gone.  The LDS form and not registers: the MFMA result spreads a
+// row over the four kq lanes while the score loop wants the whole row in one lane, so a transpose is needed either way, and the
+// projection's row registers are dead before the score loop's 100-odd live values exist.  From the tile on, the instructions of
+// k_cross_attn in its order.
+constexpr int CA_LDQ = 64 + 4;
+constexpr size_t CA_SMEM = (size_t)(2 * 32 * 64 + 64 * CA_LDQ + 64 + 4 * 64 * CA_LDQ) * sizeof(float);
+template <int E, int NH>
+__global__ __launch_bounds__(256) void k_cross_attn_qproj(const float* __restrict__ x, const float* __restrict__ qe,
+                                                           const float* __restrict__ wq, const float* __restrict__ bq,
+                                                           const float* __restrict__ k, const float* __restrict__ v,
+                                                           float* __restrict__ o, float* __restrict__ pw, int L, int S) {
+  static_assert(E == 64, "built for d_model = 64");
+  constexpr int SMAX = 32, D = E / NH, KC = E / 16, NT = E / 16, LDQ = CA_LDQ;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float (*Ks)[E] = reinterpret_cast<float (*)[E]>(smem);
+  float (*Vs)[E] = reinterpret_cast<float (*)[E]>(smem + SMAX * E);
+  float* Wq = smem + 2 * SMAX * E;          // [E][LDQ]
+  float* bqs = Wq + E * LDQ;                // [E]
+  const int n = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, kq = lane >> 4;
+  float* Q = bqs + E + wave * 64 * LDQ;     // [64][LDQ], this wave's projected queries
+  const int l0 = blockIdx.x * 256 + wave * 64;
+  // this wave's rows of x and qe first (clamped to the last row of the image), so that they fly during the staging
+  f32x4 xa[4][KC], qa[4][KC];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    const int lq = l0 + 16 * mt + lr;
+    const size_t ro = ((size_t)n * L + (lq < L ? lq : L - 1)) * E + 4 * kq;
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+      xa[mt][c] = *reinterpret_cast<const f32x4*>(x + ro + 16 * c);
+      qa[mt][c] = *reinterpret_cast<const f32x4*>(qe + ro + 16 * c);
+    }
+  }
+  for (int i = tid; i < S * E; i += 256) {
+    Ks[i / E][i % E] = k[(size_t)n * S * E + i];
+    Vs[i / E][i % E] = v[(size_t)n * S * E + i];
+  }
+  for (int i = tid; i < E * (E / 4); i += 256) {
+    const int r = i / (E / 4), c4 = (i % (E / 4)) * 4;
+    *reinterpret_cast<float4*>(Wq + r * LDQ + c4) = *reinterpret_cast<const float4*>(wq + (size_t)r * E + c4);
+  }
+  if (tid < E) bqs[tid] = bq ? bq[tid] : 0.f;
+  __syncthreads();
+  if (l0 >= L) return;                      // whole wave (no block-level barrier below)
+  {
+    const float* wa = Wq + lr * LDQ + 4 * kq;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      f32x4 acc[NT];
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < KC; ++c) {
+        const f32x4 xb = xa[mt][c] + qa[mt][c];
+        f32x4 wf[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) wf[nt] = *reinterpret_cast<const f32x4*>(wa + 16 * nt * LDQ + 16 * c);
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+          for (int nt = 0; nt < NT; ++nt) acc[nt] = mfma16(wf[nt][s4], xb[s4], acc[nt]);
+      }
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+        *reinterpret_cast<f32x4*>(Q + (16 * mt + lr) * LDQ + 16 * nt + 4 * kq) = acc[nt] + *reinterpret_cast<const f32x4*>(bqs + 16 * nt + 4 * kq);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();          // the tile is wave-private and LDS is in order within a wave
+  const int l = l0 + lane;
+  if (l >= L) return;
+  const float* qr = Q + lane * LDQ;
+  float* orow = o + ((size_t)n * L + l) * E;
+  const float scale = 1.0f / sqrtf((float)D);
+  float pavg[SMAX];
+#pragma unroll
+  for (int s = 0; s < SMAX; ++s) pavg[s] = 0.f;
+#pragma unroll
+  for (int hh = 0; hh < NH; ++hh) {
+    float qv[D];
+#pragma unroll
+    for (int d = 0; d < D; d += 4) {
+      const float4 t4 = *reinterpret_cast<const float4*>(qr + hh * D + d);
+      qv[d] = t4.x * scale; qv[d + 1] = t4.y * scale; qv[d + 2] = t4.z * scale; qv[d + 3] = t4.w * scale;
+    }
+    float sc[SMAX];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      float a = -INFINITY;
+      if (s < S) {
+        a = 0.f;
+#pragma unroll
+        for (int d = 0; d < D; ++d) a += qv[d] * Ks[s][hh * D + d];
+      }
+      sc[s] = a;
+      mx = fmaxf(mx, a);
+    }
+    float den = 0.f;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) { sc[s] = (s < S) ? expf(sc[s] - mx) : 0.f; den += sc[s]; }
+    const float inv = 1.0f / den;
+    float acc[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) acc[d] = 0.f;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      const float p = sc[s] * inv;
+      pavg[s] += p;
+      if (s < S) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) acc[d] += p * Vs[s][hh * D + d];
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < D; d += 4)
+      *reinterpret_cast<float4*>(orow + hh * D + d) = make_float4(acc[d], acc[d + 1], acc[d + 2], acc[d + 3]);
+  }
+  if (pw) {
+    float* pr = pw + ((size_t)n * L + l) * S;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) if (s < S) pr[s] = pavg[s] * (1.0f / NH);
+  }
+}
+
 // ---------------------------------------------------------------------------------- GRU gate step (query-embed GRU)
 // gi (R, 3H) constant input projection (bias folded), gh (R, 3H) = h_prev . W_hh^T + b_hh ; h (R, H) updated in place;
 // hist (R, H) receives a copy (the GRU output at this step).
@@ -453,7 +733,51 @@ int dpmn_cross_attn_f32(const float* q, const float* k, const float* v, float* o
                         int nhead, dpmn_stream_t stream) {
   DPMN_REQUIRE(q && k && v && o && N > 0, "cross_attn: bad arguments");
   DPMN_REQUIRE(E == 64 && nhead == 4 && S <= 32, "cross_attn: built for d_model=64, 4 heads, <=32 keys");
+  ProfScope prof(PT_CROSS_ATTN, as_stream(stream), 4.0 * N * (double)L * S * E,
+                 4.0 * (2.0 * N * (double)L * E + 2.0 * N * (double)S * E + (pw ? (double)N * L * S : 0.0)));
   hipLaunchKernelGGL((k_cross_attn<64, 4>), dim3(cdiv(L, 256), N), dim3(256), 0, as_stream(stream), q, k, v, o, pw, L, S);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+int dpmn_cross_attn_qproj_f32(const float* x, const float* qe, const float* wq, const float* bq, const float* k, const float* v,
+                              float* o, float* pw, int N, int L, int S, int E, int nhead, dpmn_stream_t stream) {
+  DPMN_REQUIRE(x && qe && wq && k && v && o && N > 0 && L > 0 && S > 0, "cross_attn_qproj: bad arguments");
+  DPMN_REQUIRE(E == 64 && nhead == 4 && S <= 32, "cross_attn_qproj: built for d_model=64, 4 heads, <=32 keys");
+  ProfScope prof(PT_CROSS_ATTN, as_stream(stream), 4.0 * N * (double)L * S * E + 2.0 * N * (double)L * E * E,
+                 4.0 * (3.0 * N * (double)L * E + 2.0 * N * (double)S * E + (double)E * E + (pw ? (double)N * L * S : 0.0)));
+  dpmn_lds_optin<k_cross_attn_qproj<64, 4>>(CA_SMEM);
+  hipLaunchKernelGGL((k_cross_attn_qproj<64, 4>), dim3(cdiv(L, 256), N), dim3(256), CA_SMEM, as_stream(stream), x, qe, wq, bq, k, v, o,
+                     pw, L, S);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+int dpmn_tatt_dec_tail_f32(const float* o, const float* res, const dpmn_tatt_dec_layer* d, float* y, const float* g2, const float* b2,
+                           float* acc_out, float alpha, int accumulate, long M, dpmn_stream_t stream) {
+  DPMN_REQUIRE(o && res && d && y && M > 0 && M <= (1L << 30), "tatt_dec_tail: bad arguments");
+  DPMN_REQUIRE(d->out_w && d->out_b && d->norm2_w && d->norm2_b && d->lin1_w && d->lin1_b && d->lin2_w && d->lin2_b && d->norm3_w && d->norm3_b,
+               "tatt_dec_tail: null layer parameter");
+  DPMN_REQUIRE(!acc_out || (g2 && b2), "tatt_dec_tail: second norm parameters required with acc_out");
+  const DecTailW w{d->out_w, d->out_b, d->norm2_w, d->norm2_b, d->lin1_w, d->lin1_b, d->lin2_w, d->lin2_b, d->norm3_w, d->norm3_b, g2, b2};
+  // two resident blocks per CU (55 KB of LDS each); a wave gets at least three tiles where there are that many, so that its load /
+  // MFMA / store pipeline has something to overlap (launch_rowreg's rule)
+  const int tiles = (int)((M + 15) / 16), cus = dpmn_cu_count();
+  int gx = 2 * cus;
+  while (gx > cus && (long)gx * 4 * 3 > tiles) gx -= cus;
+  if (gx * 4 > tiles) gx = cdiv(tiles, 4);
+  const int mode = !acc_out ? 0 : (accumulate ? 2 : 1);
+  ProfScope prof(PT_TATT_DEC_TAIL, as_stream(stream), 3.0 * 2.0 * (double)M * 64 * 64, 4.0 * (double)M * 64 * (mode == 0 ? 3 : (mode == 1 ? 4 : 5)));
+#define DPMN_DT_LAUNCH(ACC)                                                                                                        \
+  do {                                                                                                                             \
+    dpmn_lds_optin<k_tatt_dec_tail<64, ACC>>(DT_SMEM);                                                                             \
+    hipLaunchKernelGGL((k_tatt_dec_tail<64, ACC>), dim3(gx), dim3(256), DT_SMEM, as_stream(stream), o, res, w, y, acc_out, alpha, \
+                       (int)M);                                                                                                    \
+  } while (0)
+  if (mode == 0) DPMN_DT_LAUNCH(0);
+  else if (mode == 1) DPMN_DT_LAUNCH(1);
+  else DPMN_DT_LAUNCH(2);
+#undef DPMN_DT_LAUNCH
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }

@@ -191,11 +191,20 @@ class TSRN_TL_TRANS(_PSNBase):
         dn = ig.upsample_transformer.decoder.norm
         pw = None
         layers = ig.upsample_transformer.decoder.layers
+        fused = E == 64 and S <= 32          # the launches dpmn_tatt_interpreter_f32 issues: two per layer behind k and v
         for li, (d, pk) in enumerate(zip(layers, P["dec"])):
-            q = ops.add_linear(out, qe, pk["wq"], pk["bq"])
             k = ops.small_linear(mem, pk["wk"], pk["bk"], add=pos)
             v = ops.small_linear(mem, pk["wv"], pk["bv"])
             last = li == len(layers) - 1
+            if fused:
+                o, w_ = ops.cross_attn_qproj(out.reshape(B, L, E), qe.reshape(B, L, E), pk["wq"], pk["bq"], k.reshape(B, S, E),
+                                             v.reshape(B, S, E), need_weights=last and self.need_pr_weights)
+                pw = w_ if last else pw
+                out = ops.tatt_dec_tail(o.reshape(B * L, E), out, d.multihead_attn.out_proj.weight, d.multihead_attn.out_proj.bias,
+                                        d.norm2.weight, d.norm2.bias, d.linear1.weight, d.linear1.bias, d.linear2.weight, d.linear2.bias,
+                                        d.norm3.weight, d.norm3.bias, dn.weight, dn.bias, tp, alpha=1.0 / len(layers), accumulate=li > 0)
+                continue
+            q = ops.add_linear(out, qe, pk["wq"], pk["bq"])
             o, w_ = ops.cross_attn(q.reshape(B, L, E), k.reshape(B, S, E), v.reshape(B, S, E),
                                    need_weights=last and self.need_pr_weights)
             pw = w_ if last else pw

@@ -1371,6 +1371,31 @@ def add_layernorm64(x, res, g, b, g2=None, b2=None, acc_out=None, alpha=1.0, acc
     return y
 
 
+def cross_attn_qproj(x, qe, wq, bq, k, v, nhead=4, need_weights=False):
+    """cross_attn(add_linear(x, qe, wq, bq), k, v) with the q projection inside the attention launch"""
+    N, L, E = x.shape
+    S = k.shape[1]
+    o = torch.empty_like(x)
+    pw = torch.empty(N, L, S, device=x.device) if need_weights else None
+    check(lib.dpmn_cross_attn_qproj_f32(dptr(x), dptr(qe), dptr(wq), dptr(bq, True), dptr(k), dptr(v), dptr(o), dptr(pw, True),
+                                        N, L, S, E, nhead, stream()))
+    return o, pw
+
+
+def tatt_dec_tail(o, res, out_w, out_b, n2_w, n2_b, l1_w, l1_b, l2_w, l2_b, n3_w, n3_b, g2=None, b2=None, acc_out=None, alpha=1.0,
+                  accumulate=False):
+    """one decoder layer after its cross attention (out_proj + res, norm2, FFN + res, norm3, optional second norm into acc_out)"""
+    M = o.numel() // 64
+    d = _abi.TattDecLayer()
+    for n, t in (("out_w", out_w), ("out_b", out_b), ("norm2_w", n2_w), ("norm2_b", n2_b), ("lin1_w", l1_w), ("lin1_b", l1_b),
+                 ("lin2_w", l2_w), ("lin2_b", l2_b), ("norm3_w", n3_w), ("norm3_b", n3_b)):
+        setattr(d, n, dptr(t))
+    y = torch.empty_like(o)
+    check(lib.dpmn_tatt_dec_tail_f32(dptr(o), dptr(res), _abi.C.byref(d), dptr(y), dptr(g2, True), dptr(b2, True), dptr(acc_out, True),
+                                     float(alpha), int(accumulate), M, stream()))
+    return y
+
+
 def gru_gate(gi, gh, h, hist, hist_row_stride):
     R, H = h.shape
     check(lib.dpmn_gru_gate_f32(dptr(gi), dptr(gh), dptr(h), hist.data_ptr(), hist_row_stride, R, H, stream()))

@@ -1122,6 +1122,16 @@ typedef struct {
   dpmn_tatt_dec_layer dec[4];
   const float *dec_norm_w, *dec_norm_b;            /* decoder.norm */
 } dpmn_tatt_interp_weights;
+/* One decoder layer after its cross attention, in one launch (E = 64): y = norm3(t + linear2(relu(linear1(t)))) with
+ * t = norm2(o out_proj^T + res) (transformer_v2.py:838-849); optional acc_out (+)= alpha * LayerNorm64(y; g2, b2), the epilogue of
+ * dpmn_add_layernorm64_f32.  o, res, y, acc_out (M, 64), any M >= 1; y may be res.  Of d, wq .. bv are not read.  Plain fp32 in every
+ * compute mode. */
+int dpmn_tatt_dec_tail_f32(const float* o, const float* res, const dpmn_tatt_dec_layer* d, float* y, const float* g2, const float* b2,
+                           float* acc_out, float alpha, int accumulate, long M, dpmn_stream_t stream);
+/* dpmn_cross_attn_f32 on q = (x + qe) wq^T + bq, projected inside the launch: x, qe (N, L, 64), wq (64, 64) nn.Linear layout, bq (64)
+ * or NULL; k, v, o, pw as for dpmn_cross_attn_f32.  Plain fp32 in every compute mode. */
+int dpmn_cross_attn_qproj_f32(const float* x, const float* qe, const float* wq, const float* bq, const float* k, const float* v,
+                              float* o, float* pw, int N, int L, int S, int E, int nhead, dpmn_stream_t stream);
 size_t dpmn_tatt_interpreter_workspace_bytes(int B, int L, int S);
 /* x (B*S, t_emb) text-prior rows, b1 (B*L, 64) block1's NHWC output, qe (B*L, 64) query embedding, pos (S, 64);
  * tp (B*L, 64) out, pw (B, L, S) attention weights of the last layer or NULL. */
