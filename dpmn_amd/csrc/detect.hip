@@ -1,0 +1,378 @@
+// The text regions of a photo without a box file (utils/detect.py fixes the semantics; main.py --demo_detect): a RAGGED batch of RGB
+// uint8 photos (resize.hip's packed layout) -> per photo the gradient map, its histogram, the smoothed binary map, the component
+// labels and a table of the components' bounding boxes and pixel counts.  Integers only: independent of the compute mode, and every
+// map byte for byte the numpy restatement.  Every kernel walks the same table of 64 x 16 tiles of the WORKING maps (hm x wm =
+// H // r x W // r, r = ceil(max(H, W) / 1024)), one block of 4 waves per tile: a wave owns 4 rows of the tile, a lane one column, so a
+// wave's ballot over "is foreground" IS the 64-pixel word of its row.
+//   k_detect_grad     box-reduce + luma + 3 x 3 max - min in one launch: the tile's Y with a 1-pixel halo is staged in LDS once and the
+//                     9 taps are read from there; the histogram is counted in LDS and added to the photo's 256 counters.
+//   k_detect_hsmooth  g >= T and the run-length smoothing of the rows: per row of the tile the 3 words x0 - 64 .. x0 + 128 in LDS; a
+//                     pixel finds its nearest foreground on either side with clz / ffs on two shifted words (gap <= 64).
+//   k_detect_vsmooth  the same down the columns: the words of the rows y0 - vgap .. y0 + 16 + vgap in LDS, a lane walks its bit up and
+//                     down at most vgap words.  Also the initial label: the least index of the pixel's run inside its word.
+//   k_detect_union    label equivalence: neighbours are united by atomicMin on roots.  One pass over the edges.
+//   k_detect_roots    a pixel that is its own label is a root: it takes a row of the photo's table (atomicAdd on the photo's counter).
+//   k_detect_stats    every pixel finds its root, stores it (the flattened label) and adds itself to the root's row with integer
+//                     atomicMin / atomicMax / atomicAdd, which commute; a word whose pixels share one root sends one update.
+// Termination: a label only ever decreases (atomicMin) and L[i] <= i holds from the start, so find() follows a strictly decreasing
+// chain of non-negative indices and stops (it also stops at any value that is not below its index, whatever the buffer holds); an
+// iteration of unite() that does not return replaces one of its two roots by a strictly smaller one and find() never increases one, so
+// the sum of the two decreases and the loop ends.  No launch is repeated "until nothing changes": one union pass is complete, because a
+// link that an atomicMin overwrites is re-established by the thread that sees the overwritten value.
+#include "u8_pixel.h"
+
+namespace {
+
+constexpr int DT_W = 64, DT_H = 16, DT_THREADS = 256, DT_WAVES = 4, DT_WAVE_ROWS = DT_H / DT_WAVES;
+constexpr int DETECT_ITEM_WORDS = 8, DETECT_MAP_SIDE = 1024, DETECT_MAX_GAP = 64, DETECT_ROW = 5;
+typedef unsigned long long u64;
+
+// One photo as the kernels see it (include/dpmn_hip.h: 8 int64 per photo).  The numbers are data from the caller: an item that is not
+// consistent with the buffers is not touched.  packed_bytes < 0: the photo itself is not read by this launch.
+__host__ __device__ inline bool detect_item_ok(const long long* p, long packed_bytes, long map_px) {
+  const long long in_off = p[0], H = p[1], W = p[2], map_off = p[3], hm = p[4], wm = p[5], r = p[6];
+  if (!(H >= 1 && H <= RESIZE_MAX_SIDE && W >= 1 && W <= RESIZE_MAX_SIDE)) return false;
+  if (r != ((H > W ? H : W) + DETECT_MAP_SIDE - 1) / DETECT_MAP_SIDE || hm != H / r || wm != W / r) return false;
+  if (packed_bytes >= 0 && !(in_off >= 0 && in_off <= packed_bytes - H * W * 3)) return false;
+  return map_off >= 0 && map_off <= map_px - hm * wm;
+}
+
+struct DetTile {
+  int b, x0, y0, hm, wm, r, W;
+  long long in_off, map_off;
+};
+
+// The block's tile; false (for the whole block) when the tile names no photo, a bad item or a place outside its map.
+__device__ inline bool detect_tile(const long long* __restrict__ items, int B, const int* __restrict__ tiles, long packed_bytes, long map_px,
+                                   DetTile& t) {
+  const int* q = tiles + (size_t)blockIdx.x * 3;
+  const int b = q[0], tr = q[1], tc = q[2];
+  if (b < 0 || b >= B) return false;
+  const long long* p = items + (size_t)b * DETECT_ITEM_WORDS;
+  if (!detect_item_ok(p, packed_bytes, map_px)) return false;
+  t.b = b; t.in_off = p[0]; t.W = (int)p[2]; t.map_off = p[3]; t.hm = (int)p[4]; t.wm = (int)p[5]; t.r = (int)p[6];
+  if (t.hm < 1 || t.wm < 1 || tr < 0 || tc < 0 || tr > (t.hm - 1) / DT_H || tc > (t.wm - 1) / DT_W) return false;
+  t.x0 = tc * DT_W; t.y0 = tr * DT_H;
+  return true;
+}
+
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_grad(const unsigned char* __restrict__ packed, long packed_bytes, const long long* __restrict__ items, int B,
+              const int* __restrict__ tiles, unsigned char* __restrict__ g, long map_px, unsigned* __restrict__ hist) {
+  __shared__ unsigned char sY[DT_H + 2][DT_W + 4];
+  __shared__ unsigned sHist[256];
+  DetTile t;
+  if (!detect_tile(items, B, tiles, packed_bytes, map_px, t)) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  sHist[tid] = 0;
+  const unsigned char* src = packed + t.in_off;
+  const int r = t.r, rr = r * r, half = rr / 2;
+  for (int i = tid; i < (DT_H + 2) * (DT_W + 2); i += DT_THREADS) {
+    const int ly = i / (DT_W + 2), lx = i - ly * (DT_W + 2);
+    // (edges replicated: the halo outside the map repeats the border pixel, so every read stays inside the photo)
+    const int my = min(max(t.y0 + ly - 1, 0), t.hm - 1), mx = min(max(t.x0 + lx - 1, 0), t.wm - 1);
+    const unsigned char* p = src + ((size_t)my * r * t.W + (size_t)mx * r) * 3;
+    int s0 = 0, s1 = 0, s2 = 0;
+    for (int dy = 0; dy < r; ++dy) {
+      const unsigned char* q = p + (size_t)dy * t.W * 3;
+      for (int dx = 0; dx < r; ++dx, q += 3) {
+        s0 += q[0];
+        s1 += q[1];
+        s2 += q[2];
+      }
+    }
+    const int R = (s0 + half) / rr, G = (s1 + half) / rr, Bc = (s2 + half) / rr;
+    sY[ly][lx] = (unsigned char)((77 * R + 150 * G + 29 * Bc + 128) >> 8);
+  }
+  __syncthreads();
+  const int x = t.x0 + lane;
+  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
+    const int ly = wave * DT_WAVE_ROWS + k, y = t.y0 + ly;
+    if (x < t.wm && y < t.hm) {
+      int mx = 0, mn = 255;
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const int v = sY[ly + dy][lane + dx];
+          mx = max(mx, v);
+          mn = min(mn, v);
+        }
+      g[t.map_off + (size_t)y * t.wm + x] = (unsigned char)(mx - mn);
+      atomicAdd(&sHist[mx - mn], 1u);
+    }
+  }
+  __syncthreads();
+  if (sHist[tid]) atomicAdd(&hist[(size_t)t.b * 256 + tid], sHist[tid]);
+}
+
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_hsmooth(const unsigned char* __restrict__ g, long map_px, const long long* __restrict__ items, int B, const int* __restrict__ tiles,
+                 const int* __restrict__ thresholds, int gap, unsigned char* __restrict__ out) {
+  __shared__ u64 sW[DT_H][3];
+  DetTile t;
+  if (!detect_tile(items, B, tiles, -1, map_px, t)) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int T = thresholds[t.b];
+  const unsigned char* src = g + t.map_off;
+  for (int i = wave; i < DT_H * 3; i += DT_WAVES) {
+    const int ly = i / 3, k = i - ly * 3, y = t.y0 + ly, x = t.x0 + (k - 1) * DT_W + lane;
+    const bool f = y < t.hm && x >= 0 && x < t.wm && (int)src[(size_t)y * t.wm + x] >= T;
+    const u64 m = __ballot(f);
+    if (lane == 0) sW[ly][k] = m;
+  }
+  __syncthreads();
+  const int x = t.x0 + lane;
+  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
+    const int ly = wave * DT_WAVE_ROWS + k, y = t.y0 + ly;
+    if (x >= t.wm || y >= t.hm) continue;
+    const u64 w0 = sW[ly][0], w1 = sW[ly][1], w2 = sW[ly][2];
+    bool f = (w1 >> lane) & 1;
+    if (!f) {
+      // Lm: bit 63 is the pixel at x - 1, bit 63 - i the one at x - 1 - i; Rm: bit 0 is the pixel at x + 1, bit i the one at x + 1 + i
+      const u64 Lm = (lane ? w1 << (64 - lane) : 0ull) | (w0 >> lane);
+      const u64 Rm = ((w1 >> lane) >> 1) | (w2 << (63 - lane));
+      if (Lm && Rm) f = __clzll((long long)Lm) + __ffsll((long long)Rm) <= gap;      // dl + dr - 1, dl = clz + 1, dr = ffs
+    }
+    out[t.map_off + (size_t)y * t.wm + x] = f ? 1 : 0;
+  }
+}
+
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_vsmooth(const unsigned char* __restrict__ in, long map_px, const long long* __restrict__ items, int B, const int* __restrict__ tiles,
+                 int vgap, unsigned char* __restrict__ smooth, int* __restrict__ labels) {
+  __shared__ u64 sR[DT_H + 2 * DETECT_MAX_GAP];
+  DetTile t;
+  if (!detect_tile(items, B, tiles, -1, map_px, t)) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned char* src = in + t.map_off;
+  const int x = t.x0 + lane;
+  for (int i = wave; i < DT_H + 2 * vgap; i += DT_WAVES) {
+    const int y = t.y0 - vgap + i;
+    const bool f = y >= 0 && y < t.hm && x < t.wm && src[(size_t)y * t.wm + x] != 0;
+    const u64 m = __ballot(f);
+    if (lane == 0) sR[i] = m;
+  }
+  __syncthreads();
+  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
+    const int ly = wave * DT_WAVE_ROWS + k, y = t.y0 + ly, c = ly + vgap;
+    const bool inside = x < t.wm && y < t.hm;
+    bool f = (sR[c] >> lane) & 1;
+    if (!f) {
+      int du = 0, dd = 0;
+      for (int i = 1; i <= vgap; ++i) {
+        if (!du && ((sR[c - i] >> lane) & 1)) du = i;
+        if (!dd && ((sR[c + i] >> lane) & 1)) dd = i;
+      }
+      f = du && dd && du + dd - 1 <= vgap;
+    }
+    f = f && inside;
+    const u64 word = __ballot(f);
+    if (!inside) continue;
+    const size_t idx = t.map_off + (size_t)y * t.wm + x;
+    smooth[idx] = f ? 1 : 0;
+    int lab = -1;
+    if (f) {      // the least index of the pixel's run inside this word: below it, and in the pixel's component
+      const u64 z = ~word & ((1ull << lane) - 1);
+      lab = y * t.wm + t.x0 + (z ? 64 - __clzll((long long)z) : 0);
+    }
+    labels[idx] = lab;
+  }
+}
+
+// The root of i: the chain L[i] > L[L[i]] > ... ends at the first index that is its own label.  A value that is not below its index
+// (never written by these kernels) ends it too, so the walk is bounded by i whatever the buffer holds.
+__device__ inline int detect_find(int* L, int i) {
+  for (;;) {
+    const int p = __hip_atomic_load(&L[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (p >= i || p < 0) return i;
+    i = p;
+  }
+}
+
+__device__ inline void detect_unite(int* L, int a, int b) {
+  for (;;) {
+    a = detect_find(L, a);
+    b = detect_find(L, b);
+    if (a == b) return;
+    if (a < b) {
+      const int s = a;
+      a = b;
+      b = s;
+    }
+    const int old = atomicMin(&L[a], b);      // a was a root when find read it: link it below b
+    if (old == a) return;
+    a = old;      // another thread linked a first (old < a): what it linked a to joins b in the next turn
+  }
+}
+
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_union(const unsigned char* __restrict__ smooth, int* __restrict__ labels, long map_px, const long long* __restrict__ items, int B,
+               const int* __restrict__ tiles) {
+  DetTile t;
+  if (!detect_tile(items, B, tiles, -1, map_px, t)) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned char* S = smooth + t.map_off;
+  int* L = labels + t.map_off;
+  const int x = t.x0 + lane, wm = t.wm;
+  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
+    const int y = t.y0 + wave * DT_WAVE_ROWS + k;
+    if (x >= wm || y >= t.hm) continue;
+    const int i = y * wm + x;
+    if (!S[i]) continue;
+    if (lane == 0 && x > 0 && S[i - 1]) detect_unite(L, i, i - 1);      // (inside a word the run already shares its label)
+    if (y > 0) {
+      // the pixel above joins its own neighbours along its row: the two diagonals matter only where it is background
+      if (S[i - wm]) detect_unite(L, i, i - wm);
+      else {
+        if (x > 0 && S[i - wm - 1]) detect_unite(L, i, i - wm - 1);
+        if (x + 1 < wm && S[i - wm + 1]) detect_unite(L, i, i - wm + 1);
+      }
+    }
+  }
+}
+
+// slices: int64 (B, 2) per photo [first row of its table, rows it may use]
+__device__ inline bool detect_slice(const long long* __restrict__ slices, int b, long table_rows, long long& first, long long& cap) {
+  first = slices[(size_t)b * 2];
+  cap = slices[(size_t)b * 2 + 1];
+  return first >= 0 && cap >= 0 && first <= table_rows - cap;
+}
+
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_roots(const int* __restrict__ labels, long map_px, const long long* __restrict__ items, int B, const int* __restrict__ tiles,
+               const long long* __restrict__ slices, int* __restrict__ counts, int* __restrict__ slots, int* __restrict__ table, long table_rows) {
+  DetTile t;
+  if (!detect_tile(items, B, tiles, -1, map_px, t)) return;
+  long long first, cap;
+  if (!detect_slice(slices, t.b, table_rows, first, cap)) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int x = t.x0 + lane;
+  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
+    const int y = t.y0 + wave * DT_WAVE_ROWS + k;
+    if (x >= t.wm || y >= t.hm) continue;
+    const int i = y * t.wm + x;
+    if (labels[t.map_off + i] != i) continue;
+    const int slot = atomicAdd(&counts[t.b], 1);      // (the counter goes on past cap: the caller learns how many rows it needs)
+    if (slot < cap) {
+      int* row = table + (size_t)(first + slot) * DETECT_ROW;
+      row[0] = x; row[1] = y; row[2] = x; row[3] = y; row[4] = 0;
+    }
+    slots[t.map_off + i] = slot < cap ? slot : -1;
+  }
+}
+
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_stats(const unsigned char* __restrict__ smooth, int* __restrict__ labels, long map_px, const long long* __restrict__ items, int B,
+               const int* __restrict__ tiles, const long long* __restrict__ slices, const int* __restrict__ slots, int* __restrict__ table,
+               long table_rows) {
+  DetTile t;
+  if (!detect_tile(items, B, tiles, -1, map_px, t)) return;
+  long long first, cap;
+  if (!detect_slice(slices, t.b, table_rows, first, cap)) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int* L = labels + t.map_off;
+  const int x = t.x0 + lane;
+  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
+    const int y = t.y0 + wave * DT_WAVE_ROWS + k;      // (uniform over the wave: every lane reaches the ballots)
+    const bool f = x < t.wm && y < t.hm && smooth[t.map_off + (size_t)y * t.wm + x] != 0;
+    int root = -1, slot = -1;
+    if (f) {
+      root = detect_find(L, y * t.wm + x);
+      L[y * t.wm + x] = root;
+      slot = slots[t.map_off + root];
+      if (slot >= cap) slot = -1;
+    }
+    const u64 word = __ballot(f);
+    if (!word) continue;
+    const int lead = __ffsll((long long)word) - 1, root0 = __shfl(root, lead);
+    const bool one = __ballot(f && root != root0) == 0;
+    if (!f || slot < 0) continue;
+    int* row = table + (size_t)(first + slot) * DETECT_ROW;
+    if (one) {      // the word's pixels share a root: its leading lane sends their extent and count
+      if (lane != lead) continue;
+      atomicMin(&row[0], t.x0 + lead);
+      atomicMax(&row[2], t.x0 + 63 - __clzll((long long)word));
+      atomicMin(&row[1], y);
+      atomicMax(&row[3], y);
+      atomicAdd(&row[4], __popcll(word));
+    } else {
+      atomicMin(&row[0], x);
+      atomicMax(&row[2], x);
+      atomicMin(&row[1], y);
+      atomicMax(&row[3], y);
+      atomicAdd(&row[4], 1);
+    }
+  }
+}
+
+int detect_check(const long long* items_host, int B, long packed_bytes, long map_px) {
+  for (int b = 0; b < B; ++b)
+    if (!detect_item_ok(items_host + (size_t)b * DETECT_ITEM_WORDS, packed_bytes, map_px)) return 0;
+  return 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpmn_detect_gradient_u8(const unsigned char* packed, long packed_bytes, const long long* items, const long long* items_host, int B,
+                            const int* tiles, int n_tiles, unsigned char* g, long map_px, unsigned* hist, dpmn_stream_t stream) {
+  DPMN_REQUIRE(packed && items && items_host && hist, "detect_gradient: null pointer");
+  DPMN_REQUIRE(B > 0 && B <= 65535 && n_tiles >= 0 && (tiles || n_tiles == 0) && map_px >= 0 && (g || map_px == 0), "detect_gradient: bad sizes");
+  DPMN_REQUIRE(packed_bytes > 0 && detect_check(items_host, B, packed_bytes, map_px),
+               "detect_gradient: a photo does not fit the buffers, has a side outside 1 .. 8192 or a working map that is not its own");
+  if (hipMemsetAsync(hist, 0, (size_t)B * 256 * sizeof(unsigned), as_stream(stream)) != hipSuccess)
+    return dpmn_set_error(DPMN_ERR_LAUNCH, "detect_gradient: hipMemsetAsync failed");
+  if (n_tiles > 0) {
+    hipLaunchKernelGGL(k_detect_grad, dim3((unsigned)n_tiles), dim3(DT_THREADS), 0, as_stream(stream), packed, packed_bytes, items, B, tiles, g,
+                       map_px, hist);
+    DPMN_CHECK_LAUNCH();
+  }
+  return DPMN_OK;
+}
+
+int dpmn_detect_label_i32(const unsigned char* g, long map_px, const long long* items, const long long* items_host, int B, const int* tiles,
+                          int n_tiles, const int* thresholds, int gap, int vgap, unsigned char* tmp, unsigned char* smooth, int* labels,
+                          dpmn_stream_t stream) {
+  if (n_tiles == 0) return DPMN_OK;
+  DPMN_REQUIRE(g && items && items_host && tiles && thresholds && tmp && smooth && labels, "detect_label: null pointer");
+  DPMN_REQUIRE(B > 0 && B <= 65535 && n_tiles > 0 && map_px > 0, "detect_label: bad sizes");
+  DPMN_REQUIRE(gap >= 1 && gap <= DETECT_MAX_GAP && vgap >= 1 && vgap <= DETECT_MAX_GAP, "detect_label: gap and vgap must be 1 .. 64");
+  DPMN_REQUIRE(detect_check(items_host, B, -1, map_px), "detect_label: a working map does not fit the buffers or is not its photo's");
+  const dim3 grid((unsigned)n_tiles), block(DT_THREADS);
+  hipLaunchKernelGGL(k_detect_hsmooth, grid, block, 0, as_stream(stream), g, map_px, items, B, tiles, thresholds, gap, tmp);
+  DPMN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_detect_vsmooth, grid, block, 0, as_stream(stream), (const unsigned char*)tmp, map_px, items, B, tiles, vgap, smooth, labels);
+  DPMN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_detect_union, grid, block, 0, as_stream(stream), (const unsigned char*)smooth, labels, map_px, items, B, tiles);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+int dpmn_detect_stats_i32(const unsigned char* smooth, int* labels, long map_px, const long long* items, const long long* items_host, int B,
+                          const int* tiles, int n_tiles, const long long* slices, const long long* slices_host, int* counts, int* slots,
+                          int* table, long table_rows, dpmn_stream_t stream) {
+  DPMN_REQUIRE(items && items_host && slices && slices_host && counts, "detect_stats: null pointer");
+  DPMN_REQUIRE(B > 0 && B <= 65535 && n_tiles >= 0 && map_px >= 0 && table_rows >= 0, "detect_stats: bad sizes");
+  DPMN_REQUIRE(n_tiles == 0 || (smooth && labels && tiles && slots && map_px > 0), "detect_stats: null pointer");
+  DPMN_REQUIRE(table || table_rows == 0, "detect_stats: null table");
+  DPMN_REQUIRE(detect_check(items_host, B, -1, map_px), "detect_stats: a working map does not fit the buffers or is not its photo's");
+  for (int b = 0; b < B; ++b) {
+    const long long first = slices_host[(size_t)b * 2], cap = slices_host[(size_t)b * 2 + 1];
+    DPMN_REQUIRE(first >= 0 && cap >= 0 && first <= table_rows - cap, "detect_stats: a photo's rows leave the table");
+  }
+  if (hipMemsetAsync(counts, 0, (size_t)B * sizeof(int), as_stream(stream)) != hipSuccess)
+    return dpmn_set_error(DPMN_ERR_LAUNCH, "detect_stats: hipMemsetAsync failed");
+  if (n_tiles == 0) return DPMN_OK;
+  const dim3 grid((unsigned)n_tiles), block(DT_THREADS);
+  hipLaunchKernelGGL(k_detect_roots, grid, block, 0, as_stream(stream), (const int*)labels, map_px, items, B, tiles, slices, counts, slots, table,
+                     table_rows);
+  DPMN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_detect_stats, grid, block, 0, as_stream(stream), smooth, labels, map_px, items, B, tiles, slices, (const int*)slots, table,
+                     table_rows);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+}  // extern "C"

@@ -11,6 +11,8 @@ crop of the folder.  With photos=True (main.py --demo_paste) the two generators 
 quadrilaterals, which TextSR.demo(paste=True) needs to put the SR regions back (utils/paste.py).  With polygons=True (main.py
 --demo_polygons) a line of a box file may name a curved word by a polygon of more than 4 points (utils/poly.py): it is rectified strip
 by strip (ops.poly_crop_u8) into the same packed buffer as the quadrilaterals (ops.crop_regions_u8).
+`detect_box_files` (main.py --demo_detect) writes the box files itself: the regions of every photo are found on the GPU
+(ops.detect_text_u8, utils/detect.py).
 """
 import os
 
@@ -20,11 +22,11 @@ import torch
 LABELS_FILE = "labels.txt"
 
 
-def host_batches(dir_, batch_size, check=None):
+def host_batches(dir_, batch_size, check=None, skip_txt=False):
     """Yields (names, packed, meta) per batch of at most batch_size images: the file names and utils.resize.pack_ragged of their RGB
     pixels.  Regular files of `dir_` in sorted name order; a file PIL cannot open, or an image pack_ragged rejects (check: a callable
     (image, name) in place of utils.resize.check_image, which raises for an image it rejects), is skipped with one printed line.  A
-    directory without files raises."""
+    directory without files raises.  skip_txt: files named *.txt are passed over without a line, as box_batches passes them over."""
     from PIL import Image
     from ..utils.resize import MAX_PACKED_BYTES, check_image, pack_ragged
     batch_size = int(batch_size)
@@ -35,6 +37,8 @@ def host_batches(dir_, batch_size, check=None):
         raise FileNotFoundError("folder: %s holds no files" % dir_)
     names, images, nbytes = [], [], 0
     for f in files:
+        if skip_txt and f.lower().endswith(".txt"):
+            continue
         try:
             with Image.open(os.path.join(dir_, f)) as im:
                 a = np.asarray(im.convert('RGB'), dtype=np.uint8)
@@ -77,6 +81,25 @@ def folder_window_batches(dir_, batch_size, lr_size, mask, device):
     for names, packed, meta in host_batches(dir_, batch_size, check=lambda a, f: check_line(a, (h, w), f)):
         windows, plan = ops.resize_windows_u8(packed.to(device, non_blocking=True), meta, h, w)
         yield names, plan, ops.collate_u8(windows, mask)
+
+
+def detect_box_files(dir_, box_dir, batch_size, device, gap=12, floor=24):
+    """main.py --demo_detect: the text regions of every photo of `dir_` (host_batches' files, *.txt passed over), found on the GPU
+    (ops.detect_text_u8; utils/detect.py holds the recipe and its limits), written as box_dir/<stem>.txt in the format that box_batches
+    reads -- an ordinary box file that can be corrected by hand and fed back with --demo_boxes.  Per batch one upload of the packed
+    photos.  A photo without a region gets an empty file and one printed line.  -> the number of boxes written."""
+    from .. import ops
+    from ..utils.detect import write_boxes
+    os.makedirs(box_dir, exist_ok=True)
+    n = 0
+    for names, packed, meta in host_batches(dir_, batch_size, skip_txt=True):
+        found = ops.detect_text_u8(packed.to(device, non_blocking=True), meta[:, 0], meta[:, 1:], gap=gap, floor=floor, names=names)
+        for name, boxes in zip(names, found):
+            if len(boxes) == 0:
+                print("detect: no text region found in %s" % name)
+            write_boxes(os.path.join(box_dir, os.path.splitext(name)[0] + ".txt"), boxes)
+            n += len(boxes)
+    return n
 
 
 def box_batches(dir_, box_dir, batch_size, check=None, quads=False, polygons=False):

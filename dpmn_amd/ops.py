@@ -1005,6 +1005,113 @@ def paste_mixed_u8(photo2, sr_packed, sr_meta, regions):
     return photo2
 
 
+DETECT_TILE = (16, 64)      # csrc/detect.hip DT_H, DT_W
+DETECT_TABLE = 4096         # rows of a photo's component table; a photo with more components gets ONE second pass with as many as it has
+
+
+def _detect_plan(packed, offsets, sizes, what="detect_text_u8"):
+    """Checks and per-call host data of the detect ops -> host: items (B, 8) int64 [byte offset, H, W, offset of the working map, hm, wm,
+    r, 0], tiles (n_tiles, 3) int32 [photo, tile row, tile column] over the working maps, map_px: the pixels of all maps."""
+    import numpy as np
+    from .utils.detect import MAP_SIDE
+    off = np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets)
+    sz = np.asarray(sizes.cpu() if torch.is_tensor(sizes) else sizes)
+    if off.ndim != 1 or sz.ndim != 2 or sz.shape != (off.shape[0], 2) or off.dtype.kind not in "iu" or sz.dtype.kind not in "iu":
+        raise _abi.DpmnError("%s: offsets must be an integer (B) array of byte offsets and sizes an integer (B, 2) array of (h, w)" % what)
+    m = _ragged_batch(packed, np.concatenate((off[:, None].astype(np.int64), sz.astype(np.int64)), axis=1), what)
+    r = -(-np.maximum(m[:, 1], m[:, 2]) // MAP_SIDE)
+    hm, wm = m[:, 1] // r, m[:, 2] // r
+    first = np.concatenate(([0], np.cumsum(hm * wm)))
+    items = np.zeros((m.shape[0], 8), np.int64)
+    items[:, :3], items[:, 3], items[:, 4], items[:, 5], items[:, 6] = m, first[:-1], hm, wm, r
+    return dict(items=items, tiles=_tile_table(hm, wm, *DETECT_TILE)[0], map_px=int(first[-1]))
+
+
+def _detect_gradient(packed, host, d_items, d_tiles):
+    """The gradient launch of one batch -> (g uint8 (map_px), hist int32 (B, 256)) on the device."""
+    items, B = host["items"], host["items"].shape[0]
+    g = torch.empty(max(host["map_px"], 1), dtype=torch.uint8, device=packed.device)
+    hist = torch.empty(B, 256, dtype=torch.int32, device=packed.device)
+    check(lib.dpmn_detect_gradient_u8(packed.data_ptr(), packed.numel(), d_items, items.ctypes.data, B, d_tiles, host["tiles"].shape[0],
+                                      g.data_ptr(), host["map_px"], hist.data_ptr(), stream()))
+    return g, hist
+
+
+def _detect_run(packed, host, gap, vgap, floor):
+    """The launches of one batch -> (g, hist (host, int64 (B, 256)), smooth, labels, comps): the maps on the device, flat over the batch
+    (host["items"] says where a photo's lies), and per photo the int64 (n, 5) table [x0, y0, x1, y1, area] of its components, ends
+    exclusive, in no fixed order.  Two copies to the host: the histograms (the thresholds come from them: utils.detect.threshold) and
+    the component tables behind their counters; a third, with the second pass over the tables, when a photo has more than DETECT_TABLE
+    components."""
+    import numpy as np
+    from .utils.detect import threshold
+    items, tiles, map_px, dev = host["items"], host["tiles"], host["map_px"], packed.device
+    B, n_tiles = items.shape[0], tiles.shape[0]
+    d, d_items, d_tiles = _upload(dev, items, tiles)
+    g, hist = _detect_gradient(packed, host, d_items, d_tiles)
+    hist = hist.cpu().numpy().astype(np.int64)
+    thr = torch.from_numpy(np.array([threshold(hist[b], floor) for b in range(B)], np.int32)).to(dev)
+    tmp, smooth = torch.empty_like(g), torch.empty_like(g)
+    labels, slots = torch.empty(g.numel(), dtype=torch.int32, device=dev), torch.empty(g.numel(), dtype=torch.int32, device=dev)
+    check(lib.dpmn_detect_label_i32(g.data_ptr(), map_px, d_items, items.ctypes.data, B, d_tiles, n_tiles, thr.data_ptr(), gap, vgap,
+                                    tmp.data_ptr(), smooth.data_ptr(), labels.data_ptr(), stream()))
+    caps = np.full(B, DETECT_TABLE, np.int64)
+    for _ in range(2):      # (the counters of the first pass are exact: the second pass has a row for every component)
+        first = np.concatenate(([0], np.cumsum(caps)))
+        slices = np.ascontiguousarray(np.stack((first[:-1], caps), axis=1))
+        d_slices = torch.from_numpy(slices).to(dev)
+        out = torch.empty(B + int(first[-1]) * 5, dtype=torch.int32, device=dev)      # the counters, then the table: one copy back
+        check(lib.dpmn_detect_stats_i32(smooth.data_ptr(), labels.data_ptr(), map_px, d_items, items.ctypes.data, B, d_tiles, n_tiles,
+                                        d_slices.data_ptr(), slices.ctypes.data, out.data_ptr(), slots.data_ptr(),
+                                        out.data_ptr() + 4 * B, int(first[-1]), stream()))
+        out = out.cpu().numpy()
+        counts, table = out[:B].astype(np.int64), out[B:].reshape(-1, 5).astype(np.int64)
+        if (counts <= caps).all():
+            break
+        caps = np.maximum(caps, counts)
+    else:
+        raise _abi.DpmnError("detect: the component counters of two passes over the same labels disagree")
+    comps =[table[first[b]:first[b] + counts[b]] + np.array([0, 0, 1, 1, 0]) for b in range(B)]
+    return g, hist, smooth, labels, comps
+
+
+def detect_text_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, names=None):
+    """The text regions of a ragged batch of photos (csrc/detect.hip; utils/detect.py holds the recipe): packed = the device copy of
+    utils.resize.pack_ragged's buffer, offsets / sizes = the columns of its meta, integer (B) byte offsets and (B, 2) (h, w) -> per
+    photo an int32 (n, 4) numpy array of boxes x0, y0, x1, y1 in photo pixels, ends exclusive, sorted by (top, left, bottom, right), at
+    most utils.detect.MAX_BOXES: box for box utils.detect.detect_text_np.  gap / vgap: the longest background run that the smoothing
+    fills along a row / a column (1 .. 64), floor: the least threshold on the gradient (1 .. 255).  names: per photo, for the line that
+    is printed when boxes are dropped.  Integer kernels: the same in every compute mode.  Only the histograms and the component tables
+    cross to the host."""
+    from .utils.detect import boxes_from_components, check_params
+    try:
+        gap, vgap, floor = check_params(gap, vgap, floor)
+    except ValueError as e:
+        raise _abi.DpmnError("detect_text_u8: %s" % e) from e
+    host = _detect_plan(packed, offsets, sizes)
+    comps = _detect_run(packed, host, gap, vgap, floor)[4]
+    return [boxes_from_components(c, int(it[1]), int(it[2]), names[b] if names else None) for b, (c, it) in enumerate(zip(comps, host["items"]))]
+
+
+def detect_maps_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24):
+    """The maps behind detect_text_u8, for tests: per photo (g uint8 (hm, wm), histogram int64 (256), smoothed map uint8 of 0 / 1,
+    labels int32: the least linear index of the pixel's component, -1 on the background) as numpy arrays, byte for byte
+    utils.detect.detect_maps_np."""
+    from .utils.detect import check_params
+    try:
+        gap, vgap, floor = check_params(gap, vgap, floor)
+    except ValueError as e:
+        raise _abi.DpmnError("detect_maps_u8: %s" % e) from e
+    host = _detect_plan(packed, offsets, sizes, "detect_maps_u8")
+    g, hist, smooth, labels, _ = _detect_run(packed, host, gap, vgap, floor)
+    g, smooth, labels = g.cpu().numpy(), smooth.cpu().numpy(), labels.cpu().numpy()
+    out = []
+    for b, (_, _, _, at, hm, wm, _, _) in enumerate(host["items"].tolist()):
+        cut = lambda a: a[at:at + hm * wm].reshape(hm, wm).copy()
+        out.append((cut(g), hist[b], cut(smooth), cut(labels)))
+    return out
+
+
 def maxpool(x, kh, kw, scale=None, shift=None):
     """nn.MaxPool2d((kh,kw), stride (kh,kw)) over NHWC; scale/shift: the producer's BatchNorm affine + ReLU applied on load."""
     B, H, W, Cc = x.shape

@@ -661,6 +661,35 @@ int dpmn_paste_mixed_u8(unsigned char* photo, int H2, int W2, const unsigned cha
 int dpmn_poly_crop_u8(const unsigned char* packed, long packed_bytes, const long long* regions, const long long* regions_host /* HOST array */,
                       int R, const long long* cells, const long long* cells_host /* HOST array */, int n_cells, const int* tiles, int n_tiles,
                       unsigned char* out, long out_bytes, dpmn_stream_t stream);
+/* The text regions of a photo without a box file (detect.hip; utils/detect.py holds the recipe, the numpy restatement and everything
+ * the host does with these results): a RAGGED batch of photos in the packed layout of dpmn_resize_ragged_u8.  Per photo the WORKING
+ * map is hm x wm = H // r x W // r with r = ceil(max(H, W) / 1024); the maps of a batch lie back to back, one element per pixel, map_px
+ * elements in all.  items: device int64 (B, 8), per photo [byte offset in packed, H, W, offset of its map in elements, hm, wm, r, 0];
+ * items_host: the same table in HOST memory (the entry points check it and refuse the call before any launch; the kernels check the
+ * device copy and skip a photo that fails).  tiles: device int32 (n_tiles, 3), per 64 x 16 tile (w x h) of a working map [photo, tile
+ * row, tile column]: one block per tile; a tile that names no photo or lies outside its map does nothing.  Integers only: independent
+ * of the compute mode.
+ * dpmn_detect_gradient_u8: r x r box means per channel rounded half up, Y = (77 R + 150 G + 29 B + 128) >> 8, g = max3x3(Y) - min3x3(Y)
+ * with the edges replicated -> g (map_px bytes), and hist, uint32 (B, 256): the histogram of every photo's g (zeroed here).  One launch.
+ * dpmn_detect_label_i32: b = g >= thresholds[photo] (device int32 (B)); in every row a background run of length 1 .. gap between two
+ * foreground pixels is filled (-> tmp), then the same down every column with vgap (-> smooth, bytes 0 / 1); then the components of
+ * smooth under 8-connectivity by label equivalence -> labels, int32 (map_px): -1 on the background, else an index y * wm + x of the
+ * pixel's component that is not above its own; following labels from a pixel ends at the component's least index.  gap, vgap 1 .. 64.
+ * Three launches.
+ * dpmn_detect_stats_i32: flattens labels (every foreground pixel holds its component's least index) and fills table, int32
+ * (table_rows, 5): per component [x0, y0, greatest x, greatest y, pixel count] in working-map pixels.  slices: device int64 (B, 2), per
+ * photo [first row of its part of the table, rows in it] (slices_host: the same in HOST memory); the components of a photo take the
+ * rows of its part in no fixed order.  counts, int32 (B) (zeroed here): the components of every photo -- where that exceeds the
+ * photo's rows the surplus is left out of the table and the caller calls again with a larger one (the call may be repeated: flat
+ * labels stay as they are).  slots: int32 (map_px) of scratch.  Two launches. */
+int dpmn_detect_gradient_u8(const unsigned char* packed, long packed_bytes, const long long* items, const long long* items_host /* HOST array */,
+                            int B, const int* tiles, int n_tiles, unsigned char* g, long map_px, unsigned int* hist, dpmn_stream_t stream);
+int dpmn_detect_label_i32(const unsigned char* g, long map_px, const long long* items, const long long* items_host /* HOST array */, int B,
+                          const int* tiles, int n_tiles, const int* thresholds, int gap, int vgap, unsigned char* tmp, unsigned char* smooth,
+                          int* labels, dpmn_stream_t stream);
+int dpmn_detect_stats_i32(const unsigned char* smooth, int* labels, long map_px, const long long* items, const long long* items_host /* HOST array */,
+                          int B, const int* tiles, int n_tiles, const long long* slices, const long long* slices_host /* HOST array */,
+                          int* counts, int* slots, int* table, long table_rows, dpmn_stream_t stream);
 
 /* rotation augmentation of the trainer (utils/util.py:37-58 torch_rotate_img; super_resolution.py:144-151, 358-365):
  * per-image affine with aspect-ratio jitter -> affine_grid (align_corners=False) -> bilinear grid_sample, zeros padding.

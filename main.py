@@ -14,7 +14,9 @@ the GPU, its SR regions are warped back into their quadrilaterals and blended in
 in SR pixels, 0 for a hard edge), and written as `<stem>_photo_sr.png`; with `--demo_polygons` a line of a box file may also name a curved
 word by a polygon (2k points, k along the top edge and k along the bottom, as CTW1500 and Total-Text write them), which is straightened
 strip by strip on the GPU (polygon regions are written as files; `--demo_paste_polygons` on top of `--demo_paste` also warps them back into
-the photo, strip by strip, in box-file order with the quadrilaterals).  `--train_state PATH` makes a training run continuable: the same command line starts the
+the photo, strip by strip, in box-file order with the quadrilaterals); with `--demo_detect` in place of `--demo_boxes` the box files are
+written by the run itself: the text regions of every photo are found on the GPU by a classical, integer recipe (utils/detect.py) into
+`<demo_out>/boxes`, and the run goes on as with `--demo_boxes <demo_out>/boxes`.  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--ema DECAY` keeps an exponential moving average of the trained weights; the
 validation passes score it and the best-model checkpoints hold it.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
 (`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image; `--psf_blur KINDS`: with a random motion, defocus or elongated-Gaussian blur of the HR pixels first); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB); `--train_words FILE` trains from a word list alone: the HR images are rendered on the GPU (`--train_words_fonts DIR`: in the fonts of a directory; `--train_words_epoch N`: samples per epoch).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
@@ -76,6 +78,34 @@ DEMO_POLYGONS_NEEDS_BOXES = "main.py: --demo_polygons needs --demo_boxes: the po
 DEMO_PASTE_POLYGONS_NEEDS = ("main.py: --demo_paste_polygons needs --demo_paste and --demo_polygons: it pastes the SR regions of the polygons "
                              "that --demo_polygons reads into the photo that --demo_paste writes")
 DEMO_PASTE_FEATHER = "main.py: --demo_paste_feather must be a finite number >= 0 (the width of the blended edge in SR pixels; 0: a hard edge)"
+DEMO_DETECT_NEEDS_DIR = "main.py: --demo_detect needs --demo_dir: the text regions are looked for in the photos of that folder"
+DEMO_DETECT_OR_BOXES = ("main.py: --demo_detect does not combine with --demo_boxes or --demo_polygons: it writes the box files itself, as "
+                        "upright rectangles (correct them by hand and pass them with --demo_boxes in a second run)")
+DEMO_DETECT_GAP = "main.py: --demo_detect_gap must be 1 .. 64 (the longest gap between letters, in pixels of the working map, that joins a word)"
+DEMO_DETECT_FLOOR = "main.py: --demo_detect_floor must be 1 .. 255 (the least gradient of the luma that counts as an edge of a letter)"
+DEMO_DETECT_FLAGS_NEED = "main.py: --demo_detect_gap and --demo_detect_floor need --demo_detect"
+
+
+def demo_detect_setting(args):
+    """--demo_detect and its two numbers, checked -> None without the flag, else (gap, floor).  ValueError (the message without its
+    'main.py: ') for the flag without --demo_dir or with --demo_boxes / --demo_polygons, a number outside its range, or a number without
+    the flag."""
+    from dpmn_amd.utils.detect import FLOOR, GAP, MAX_GAP
+    gap, floor = getattr(args, "demo_detect_gap", None), getattr(args, "demo_detect_floor", None)
+    if not getattr(args, "demo_detect", False):
+        if gap is not None or floor is not None:
+            raise ValueError(DEMO_DETECT_FLAGS_NEED[len("main.py: "):])
+        return None
+    if not getattr(args, "demo_dir", None):
+        raise ValueError(DEMO_DETECT_NEEDS_DIR[len("main.py: "):])
+    if getattr(args, "demo_boxes", None) or getattr(args, "demo_polygons", False):
+        raise ValueError(DEMO_DETECT_OR_BOXES[len("main.py: "):])
+    gap, floor = GAP if gap is None else int(gap), FLOOR if floor is None else int(floor)
+    if not 1 <= gap <= MAX_GAP:
+        raise ValueError(DEMO_DETECT_GAP[len("main.py: "):])
+    if not 1 <= floor <= 255:
+        raise ValueError(DEMO_DETECT_FLOOR[len("main.py: "):])
+    return gap, floor
 
 
 def paste_feather(args):
@@ -232,9 +262,13 @@ def main(config, args):
                          "blurs the HR pixels that the LR images are synthesised from")
     if getattr(args, "demo_tile", False) and not getattr(args, "demo_dir", None):
         raise SystemExit("main.py: --demo_tile needs --demo_dir: it super-resolves the wide images of that folder in overlapping windows")
+    try:
+        detect = demo_detect_setting(args)
+    except ValueError as e:
+        raise SystemExit("main.py: %s" % e)
     if getattr(args, "demo_boxes", None) and not getattr(args, "demo_dir", None):
         raise SystemExit(DEMO_BOXES_NEEDS_DIR)
-    if getattr(args, "demo_paste", False) and not getattr(args, "demo_boxes", None):
+    if getattr(args, "demo_paste", False) and not (getattr(args, "demo_boxes", None) or detect):
         raise SystemExit(DEMO_PASTE_NEEDS_BOXES)
     if getattr(args, "demo_polygons", False) and not getattr(args, "demo_boxes", None):
         raise SystemExit(DEMO_POLYGONS_NEEDS_BOXES)
@@ -292,6 +326,12 @@ def main(config, args):
         out_dir = getattr(args, "demo_out", None) or os.path.join(mission.vis_dir, "demo")
         lr_size = (config.TRAIN.height // scale, config.TRAIN.width // scale)
         box_dir = getattr(args, "demo_boxes", None)
+        if detect:
+            # no box files: the regions of every photo are found on the GPU (utils/detect.py) and written as <demo_out>/boxes/<stem>.txt;
+            # from here the run is the one that --demo_boxes <demo_out>/boxes starts
+            from dpmn_amd.dataset.folder import detect_box_files
+            box_dir = os.path.join(out_dir, "boxes")
+            print("%d regions detected, box files in %s" % (detect_box_files(args.demo_dir, box_dir, bs, mission.device, *detect), box_dir))
         if box_dir:
             # whole photos and one box file per photo: every quadrilateral is rectified on the GPU (utils/quad.py), then goes the way
             # of a crop of the folder -- one <stem>_<k>_sr.png per region
@@ -466,6 +506,19 @@ if __name__ == '__main__':
     parser.add_argument('--demo_paste_feather', type=float, default=1.0, metavar='F',
                         help='with --demo_paste: the width, in SR pixels, of the edge over which a pasted region is blended into the '
                              'photo (>= 0; 0 gives a hard edge)')
+    parser.add_argument('--demo_detect', action='store_true', default=False,
+                        help='with --demo_dir and without box files: the folder holds whole photos whose text regions are found on the '
+                             'GPU by a classical recipe (gradient of the luma, Otsu threshold, run-length smoothing, connected '
+                             'components, geometric filters), written as <demo_out>/boxes/<stem>.txt and then used as --demo_boxes uses '
+                             'them (combines with --demo_tile, --demo_paste and --rec).  It finds well-contrasted, roughly horizontal '
+                             'words and lines; it is no learned detector (not EAST or DBNet): low-contrast, vertical or strongly rotated '
+                             'text is missed and very large glyphs may split into several boxes.  The files are ordinary box files: '
+                             'correct them by hand and pass them with --demo_boxes')
+    parser.add_argument('--demo_detect_gap', type=int, default=None, metavar='N',
+                        help='with --demo_detect: the longest gap between letters, in pixels of the working map (the photo reduced to at '
+                             'most 1024 on its long side), that still joins them into one word (1 .. 64, default 12)')
+    parser.add_argument('--demo_detect_floor', type=int, default=None, metavar='N',
+                        help='with --demo_detect: the least threshold on the 3 x 3 gradient of the luma (1 .. 255, default 24)')
     parser.add_argument('--gpu_resize', action='store_true', default=False,
                         help='TextZoom loaders: the bicubic resize of the decoded images runs on the GPU (same bytes as PIL)')
     parser.add_argument('--train_state', type=str, default=None,
@@ -524,9 +577,13 @@ if __name__ == '__main__':
         parser.error(TRAIN_WORDS_OR_HR_DIR[len("main.py: "):])
     if args.train_words_fonts and not args.train_words:
         parser.error(TRAIN_WORDS_FONTS_NEEDS[len("main.py: "):])
+    try:
+        demo_detect_setting(args)
+    except ValueError as e:
+        parser.error(str(e))
     if args.demo_boxes and not args.demo_dir:
         parser.error(DEMO_BOXES_NEEDS_DIR[len("main.py: "):])
-    if args.demo_paste and not args.demo_boxes:
+    if args.demo_paste and not (args.demo_boxes or args.demo_detect):
         parser.error(DEMO_PASTE_NEEDS_BOXES[len("main.py: "):])
     if args.demo_polygons and not args.demo_boxes:
         parser.error(DEMO_POLYGONS_NEEDS_BOXES[len("main.py: "):])
