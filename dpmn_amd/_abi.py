@@ -310,6 +310,8 @@ SIGNATURES = {
     "dpmn_detect_gradient_u8": (_i, [fp, _l, fp, fp, _i, fp, _i, fp, _l, fp, fp]),
     "dpmn_detect_label_i32": (_i, [fp, _l, fp, fp, _i, fp, _i, fp, _i, _i, fp, fp, fp, fp]),
     "dpmn_detect_stats_i32": (_i, [fp, fp, _l, fp, fp, _i, fp, _i, fp, fp, fp, fp, fp, _l, fp]),
+    "dpmn_detect_moments_i64": (_i, [fp, fp, _l, fp, fp, _i, fp, _i, fp, fp, fp, fp, _l, fp]),
+    "dpmn_detect_extents_i32": (_i, [fp, fp, _l, fp, fp, _i, fp, _i, fp, fp, fp, fp, fp, _l, fp]),
     "dpmn_profile_tag_count": (_i, []),
     "dpmn_profile_hint_bytes": (_i, [C.c_double]),
     "dpmn_profile_tag_name": (C.c_char_p, [_i]),

@@ -14,6 +14,10 @@
 //   k_detect_roots    a pixel that is its own label is a root: it takes a row of the photo's table (atomicAdd on the photo's counter).
 //   k_detect_stats    every pixel finds its root, stores it (the flattened label) and adds itself to the root's row with integer
 //                     atomicMin / atomicMax / atomicAdd, which commute; a word whose pixels share one root sends one update.
+//   k_detect_moments  (oriented regions) every pixel adds x, y, x^2, x y, y^2 to its component's int64 row with 64-bit atomicAdd; a word
+//                     with one root reduces x and x^2 over the wave and its leading lane sends one update per sum.
+//   k_detect_extents  (oriented regions) atomicMax of the projections of the pixel centres along and across the component's direction,
+//                     which the host chose from the moments; in a word with one root its first and last pixel give the extremes.
 // Termination: a label only ever decreases (atomicMin) and L[i] <= i holds from the start, so find() follows a strictly decreasing
 // chain of non-negative indices and stops (it also stops at any value that is not below its index, whatever the buffer holds); an
 // iteration of unite() that does not return replaces one of its two roots by a strictly smaller one and find() never increases one, so
@@ -306,6 +310,113 @@ k_detect_stats(const unsigned char* __restrict__ smooth, int* __restrict__ label
   }
 }
 
+// The oriented regions (utils/detect.py, stages a and c) read what k_detect_stats left: labels[pixel] = root, slots[root] = table row.
+// The word of a wave's row, its root test and the row of the table, as k_detect_stats finds them; false for the whole wave when the
+// word is empty.  slot < 0: this lane adds nothing.
+__device__ inline bool detect_word(const unsigned char* __restrict__ smooth, const int* __restrict__ labels, const int* __restrict__ slots,
+                                   const DetTile& t, int x, int y, long long cap, bool& f, u64& word, bool& one, int& slot) {
+  f = x < t.wm && y < t.hm && smooth[t.map_off + (size_t)y * t.wm + x] != 0;
+  int root = -1;
+  slot = -1;
+  if (f) {
+    root = labels[t.map_off + (size_t)y * t.wm + x];
+    if (root >= 0 && root < t.hm * t.wm) slot = slots[t.map_off + root];      // (a label that is no index of the map names no row)
+    if (slot >= cap) slot = -1;
+  }
+  word = __ballot(f);
+  if (!word) return false;
+  const int root0 = __shfl(root, __ffsll((long long)word) - 1);
+  one = __ballot(f && root != root0) == 0;
+  return true;
+}
+
+// table: u64 (table_rows, 5) [sum x, sum y, sum x^2, sum x y, sum y^2] per component (the area is in the table of k_detect_stats),
+// zeroed by the entry point.  Every sum of a word is below 2^31; the table's are below 2^60.
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_moments(const unsigned char* __restrict__ smooth, const int* __restrict__ labels, long map_px, const long long* __restrict__ items,
+                 int B, const int* __restrict__ tiles, const long long* __restrict__ slices, const int* __restrict__ slots,
+                 u64* __restrict__ table, long table_rows) {
+  DetTile t;
+  if (!detect_tile(items, B, tiles, -1, map_px, t)) return;
+  long long first, cap;
+  if (!detect_slice(slices, t.b, table_rows, first, cap)) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int x = t.x0 + lane;
+  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
+    const int y = t.y0 + wave * DT_WAVE_ROWS + k;      // (uniform over the wave: every lane reaches the ballots and the shuffles)
+    bool f, one;
+    u64 word;
+    int slot;
+    if (!detect_word(smooth, labels, slots, t, x, y, cap, f, word, one, slot)) continue;
+    if (one) {      // one root: sum x and sum x^2 over the set bits by a wave reduction, the rest follows from y and the popcount
+      int sx = f ? x : 0, sxx = f ? x * x : 0;
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) {
+        sx += __shfl_xor(sx, d);
+        sxx += __shfl_xor(sxx, d);
+      }
+      if (lane != __ffsll((long long)word) - 1 || slot < 0) continue;
+      u64* row = table + (size_t)(first + slot) * 5;
+      const u64 n = (u64)__popcll(word);
+      atomicAdd(&row[0], (u64)sx);
+      atomicAdd(&row[1], (u64)y * n);
+      atomicAdd(&row[2], (u64)sxx);
+      atomicAdd(&row[3], (u64)y * (u64)sx);
+      atomicAdd(&row[4], (u64)y * (u64)y * n);
+    } else if (f && slot >= 0) {
+      u64* row = table + (size_t)(first + slot) * 5;
+      atomicAdd(&row[0], (u64)x);
+      atomicAdd(&row[1], (u64)y);
+      atomicAdd(&row[2], (u64)(x * x));
+      atomicAdd(&row[3], (u64)(x * y));
+      atomicAdd(&row[4], (u64)(y * y));
+    }
+  }
+}
+
+// dirs: int32 (table_rows, 2) per component (c, s) of its direction, (0, 0): the component is passed over.  table: int32
+// (table_rows, 4) [max -U2, max U2, max -V2, max V2], U2 = c (2x + 1) + s (2y + 1), V2 = -s (2x + 1) + c (2y + 1) (below 2^27 in
+// magnitude), every byte set to 0x80 by the entry point: a value below every projection, so that four atomicMax do it.
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_extents(const unsigned char* __restrict__ smooth, const int* __restrict__ labels, long map_px, const long long* __restrict__ items,
+                 int B, const int* __restrict__ tiles, const long long* __restrict__ slices, const int* __restrict__ slots,
+                 const int* __restrict__ dirs, int* __restrict__ table, long table_rows) {
+  DetTile t;
+  if (!detect_tile(items, B, tiles, -1, map_px, t)) return;
+  long long first, cap;
+  if (!detect_slice(slices, t.b, table_rows, first, cap)) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int x = t.x0 + lane;
+  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
+    const int y = t.y0 + wave * DT_WAVE_ROWS + k;
+    bool f, one;
+    u64 word;
+    int slot;
+    if (!detect_word(smooth, labels, slots, t, x, y, cap, f, word, one, slot)) continue;
+    if (!f || slot < 0) continue;
+    const int lead = __ffsll((long long)word) - 1;
+    if (one && lane != lead) continue;
+    const int c = dirs[(size_t)(first + slot) * 2], s = dirs[(size_t)(first + slot) * 2 + 1];
+    if (c == 0 && s == 0) continue;
+    int* row = table + (size_t)(first + slot) * 4;
+    const int Y = 2 * y + 1, Xa = 2 * x + 1;
+    if (one) {      // one root: U2 and V2 are linear in x, so the word's first and last set bit give its extremes
+      const int Xb = 2 * (t.x0 + 63 - __clzll((long long)word)) + 1;
+      const int Ua = c * Xa + s * Y, Ub = c * Xb + s * Y, Va = c * Y - s * Xa, Vb = c * Y - s * Xb;
+      atomicMax(&row[0], -min(Ua, Ub));
+      atomicMax(&row[1], max(Ua, Ub));
+      atomicMax(&row[2], -min(Va, Vb));
+      atomicMax(&row[3], max(Va, Vb));
+    } else {
+      const int U = c * Xa + s * Y, V = c * Y - s * Xa;
+      atomicMax(&row[0], -U);
+      atomicMax(&row[1], U);
+      atomicMax(&row[2], -V);
+      atomicMax(&row[3], V);
+    }
+  }
+}
+
 int detect_check(const long long* items_host, int B, long packed_bytes, long map_px) {
   for (int b = 0; b < B; ++b)
     if (!detect_item_ok(items_host + (size_t)b * DETECT_ITEM_WORDS, packed_bytes, map_px)) return 0;
@@ -371,6 +482,53 @@ int dpmn_detect_stats_i32(const unsigned char* smooth, int* labels, long map_px,
   DPMN_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_detect_stats, grid, block, 0, as_stream(stream), smooth, labels, map_px, items, B, tiles, slices, (const int*)slots, table,
                      table_rows);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+// The checks that the two oriented entry points share with dpmn_detect_stats_i32.
+static int detect_oriented_check(const void* smooth, const void* labels, long map_px, const long long* items,
+                                 const long long* items_host, int B, const int* tiles, int n_tiles, const long long* slices,
+                                 const long long* slices_host, const void* slots, const void* table, long table_rows) {
+  DPMN_REQUIRE(items && items_host && slices && slices_host, "detect_oriented: null pointer");
+  DPMN_REQUIRE(B > 0 && B <= 65535 && n_tiles >= 0 && map_px >= 0 && table_rows >= 0, "detect_oriented: bad sizes");
+  DPMN_REQUIRE(n_tiles == 0 || (smooth && labels && tiles && slots && map_px > 0), "detect_oriented: null pointer");
+  DPMN_REQUIRE(table || table_rows == 0, "detect_oriented: null table");
+  DPMN_REQUIRE(detect_check(items_host, B, -1, map_px), "detect_oriented: a working map does not fit the buffers or is not its photo's");
+  for (int b = 0; b < B; ++b) {
+    const long long first = slices_host[(size_t)b * 2], cap = slices_host[(size_t)b * 2 + 1];
+    DPMN_REQUIRE(first >= 0 && cap >= 0 && first <= table_rows - cap, "detect_oriented: a photo's rows leave the table");
+  }
+  return DPMN_OK;
+}
+
+int dpmn_detect_moments_i64(const unsigned char* smooth, const int* labels, long map_px, const long long* items, const long long* items_host,
+                            int B, const int* tiles, int n_tiles, const long long* slices, const long long* slices_host, const int* slots,
+                            long long* table, long table_rows, dpmn_stream_t stream) {
+  const int rc = detect_oriented_check(smooth, labels, map_px, items, items_host, B, tiles, n_tiles, slices, slices_host,
+                                       slots, table, table_rows);
+  if (rc != DPMN_OK) return rc;
+  if (table_rows > 0 && hipMemsetAsync(table, 0, (size_t)table_rows * 5 * sizeof(long long), as_stream(stream)) != hipSuccess)
+    return dpmn_set_error(DPMN_ERR_LAUNCH, "detect_moments: hipMemsetAsync failed");
+  if (n_tiles == 0 || table_rows == 0) return DPMN_OK;
+  hipLaunchKernelGGL(k_detect_moments, dim3((unsigned)n_tiles), dim3(DT_THREADS), 0, as_stream(stream), smooth, labels, map_px, items, B, tiles,
+                     slices, slots, (u64*)table, table_rows);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+int dpmn_detect_extents_i32(const unsigned char* smooth, const int* labels, long map_px, const long long* items, const long long* items_host,
+                            int B, const int* tiles, int n_tiles, const long long* slices, const long long* slices_host, const int* slots,
+                            const int* dirs, int* table, long table_rows, dpmn_stream_t stream) {
+  const int rc = detect_oriented_check(smooth, labels, map_px, items, items_host, B, tiles, n_tiles, slices, slices_host,
+                                       slots, table, table_rows);
+  if (rc != DPMN_OK) return rc;
+  DPMN_REQUIRE(dirs || table_rows == 0, "detect_extents: null directions");
+  if (table_rows > 0 && hipMemsetAsync(table, 0x80, (size_t)table_rows * 4 * sizeof(int), as_stream(stream)) != hipSuccess)
+    return dpmn_set_error(DPMN_ERR_LAUNCH, "detect_extents: hipMemsetAsync failed");
+  if (n_tiles == 0 || table_rows == 0) return DPMN_OK;
+  hipLaunchKernelGGL(k_detect_extents, dim3((unsigned)n_tiles), dim3(DT_THREADS), 0, as_stream(stream), smooth, labels, map_px, items, B, tiles,
+                     slices, slots, dirs, table, table_rows);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }

@@ -12,7 +12,8 @@ quadrilaterals, which TextSR.demo(paste=True) needs to put the SR regions back (
 --demo_polygons) a line of a box file may name a curved word by a polygon of more than 4 points (utils/poly.py): it is rectified strip
 by strip (ops.poly_crop_u8) into the same packed buffer as the quadrilaterals (ops.crop_regions_u8).
 `detect_box_files` (main.py --demo_detect) writes the box files itself: the regions of every photo are found on the GPU
-(ops.detect_text_u8, utils/detect.py).
+(ops.detect_text_u8, utils/detect.py), with oriented=True (main.py --demo_detect_oriented) as rotated quadrilaterals
+(ops.detect_oriented_u8).
 """
 import os
 
@@ -83,21 +84,24 @@ def folder_window_batches(dir_, batch_size, lr_size, mask, device):
         yield names, plan, ops.collate_u8(windows, mask)
 
 
-def detect_box_files(dir_, box_dir, batch_size, device, gap=12, floor=24):
+def detect_box_files(dir_, box_dir, batch_size, device, gap=12, floor=24, oriented=False):
     """main.py --demo_detect: the text regions of every photo of `dir_` (host_batches' files, *.txt passed over), found on the GPU
     (ops.detect_text_u8; utils/detect.py holds the recipe and its limits), written as box_dir/<stem>.txt in the format that box_batches
     reads -- an ordinary box file that can be corrected by hand and fed back with --demo_boxes.  Per batch one upload of the packed
-    photos.  A photo without a region gets an empty file and one printed line.  -> the number of boxes written."""
+    photos.  A photo without a region gets an empty file and one printed line.  oriented (main.py --demo_detect_oriented): the
+    regions are rotated quadrilaterals along the text's own direction, in decimals (ops.detect_oriented_u8).  -> the number of boxes
+    written."""
     from .. import ops
-    from ..utils.detect import write_boxes
+    from ..utils.detect import write_boxes, write_quads
+    find, write = (ops.detect_oriented_u8, write_quads) if oriented else (ops.detect_text_u8, write_boxes)
     os.makedirs(box_dir, exist_ok=True)
     n = 0
     for names, packed, meta in host_batches(dir_, batch_size, skip_txt=True):
-        found = ops.detect_text_u8(packed.to(device, non_blocking=True), meta[:, 0], meta[:, 1:], gap=gap, floor=floor, names=names)
+        found = find(packed.to(device, non_blocking=True), meta[:, 0], meta[:, 1:], gap=gap, floor=floor, names=names)
         for name, boxes in zip(names, found):
             if len(boxes) == 0:
                 print("detect: no text region found in %s" % name)
-            write_boxes(os.path.join(box_dir, os.path.splitext(name)[0] + ".txt"), boxes)
+            write(os.path.join(box_dir, os.path.splitext(name)[0] + ".txt"), boxes)
             n += len(boxes)
     return n
 

@@ -1037,20 +1037,26 @@ def _detect_gradient(packed, host, d_items, d_tiles):
     return g, hist
 
 
-def _detect_run(packed, host, gap, vgap, floor):
-    """The launches of one batch -> (g, hist (host, int64 (B, 256)), smooth, labels, comps): the maps on the device, flat over the batch
-    (host["items"] says where a photo's lies), and per photo the int64 (n, 5) table [x0, y0, x1, y1, area] of its components, ends
-    exclusive, in no fixed order.  Two copies to the host: the histograms (the thresholds come from them: utils.detect.threshold) and
-    the component tables behind their counters; a third, with the second pass over the tables, when a photo has more than DETECT_TABLE
-    components."""
+def _detect_thresholds(packed, host, floor):
+    """The uploads, the gradient launch, the histogram copy and the thresholds of one batch (utils.detect.threshold, on the host) ->
+    (d, d_items, d_tiles, g, hist (host, int64 (B, 256)), thr (device, int32 (B))); d keeps the uploaded buffer alive."""
     import numpy as np
     from .utils.detect import threshold
-    items, tiles, map_px, dev = host["items"], host["tiles"], host["map_px"], packed.device
-    B, n_tiles = items.shape[0], tiles.shape[0]
-    d, d_items, d_tiles = _upload(dev, items, tiles)
+    d, d_items, d_tiles = _upload(packed.device, host["items"], host["tiles"])
     g, hist = _detect_gradient(packed, host, d_items, d_tiles)
     hist = hist.cpu().numpy().astype(np.int64)
-    thr = torch.from_numpy(np.array([threshold(hist[b], floor) for b in range(B)], np.int32)).to(dev)
+    thr = torch.from_numpy(np.array([threshold(h, floor) for h in hist], np.int32)).to(packed.device)
+    return d, d_items, d_tiles, g, hist, thr
+
+
+def _detect_pass(host, d_items, d_tiles, g, thr, gap, vgap):
+    """The label and stats launches of one batch over its gradient maps -> dict(smooth, labels, slots: the device maps; slices, d_slices:
+    int64 (B, 2) [first row, rows] of every photo's part of the tables; counts (B); table int64 (rows, 5) [x0, y0, greatest x, greatest
+    y, area], the rows of a photo in no fixed order).  One copy to the host, the component tables behind their counters; a second, with
+    the second pass over the tables, when a photo has more than DETECT_TABLE components."""
+    import numpy as np
+    items, tiles, map_px, dev = host["items"], host["tiles"], host["map_px"], g.device
+    B, n_tiles = items.shape[0], tiles.shape[0]
     tmp, smooth = torch.empty_like(g), torch.empty_like(g)
     labels, slots = torch.empty(g.numel(), dtype=torch.int32, device=dev), torch.empty(g.numel(), dtype=torch.int32, device=dev)
     check(lib.dpmn_detect_label_i32(g.data_ptr(), map_px, d_items, items.ctypes.data, B, d_tiles, n_tiles, thr.data_ptr(), gap, vgap,
@@ -1071,8 +1077,145 @@ def _detect_run(packed, host, gap, vgap, floor):
         caps = np.maximum(caps, counts)
     else:
         raise _abi.DpmnError("detect: the component counters of two passes over the same labels disagree")
-    comps =[table[first[b]:first[b] + counts[b]] + np.array([0, 0, 1, 1, 0]) for b in range(B)]
-    return g, hist, smooth, labels, comps
+    return dict(smooth=smooth, labels=labels, slots=slots, slices=slices, d_slices=d_slices, counts=counts, table=table)
+
+
+def _detect_run(packed, host, gap, vgap, floor):
+    """The launches of one batch -> (g, hist (host, int64 (B, 256)), smooth, labels, comps): the maps on the device, flat over the batch
+    (host["items"] says where a photo's lies), and per photo the int64 (n, 5) table [x0, y0, x1, y1, area] of its components, ends
+    exclusive, in no fixed order.  Two copies to the host: the histograms (the thresholds come from them: utils.detect.threshold) and
+    the component tables behind their counters; a third, with the second pass over the tables, when a photo has more than DETECT_TABLE
+    components."""
+    d, d_items, d_tiles, g, hist, thr = _detect_thresholds(packed, host, floor)
+    p = _detect_pass(host, d_items, d_tiles, g, thr, gap, vgap)
+    return g, hist, p["smooth"], p["labels"], _detect_comps(p)
+
+
+def _detect_comps(p):
+    """Per photo the int64 (n, 5) table [x0, y0, x1, y1, area] of a pass of _detect_pass, ends exclusive, in the order of its rows."""
+    import numpy as np
+    first = p["slices"][:, 0]
+    return [p["table"][first[b]:first[b] + n] + np.array([0, 0, 1, 1, 0]) for b, n in enumerate(p["counts"].tolist())]
+
+
+def _detect_oriented_args(host, d_items, d_tiles, p):
+    """The tables of the oriented launches hold exactly the components of a pass, photo after photo: a component's row is its slot of
+    _detect_pass behind the components of the photos before it, so only rows that are used are initialised and copied.  -> (the
+    leading arguments that the two entry points share, slices int64 (B, 2) [first row, rows], their device copy, the rows in all)."""
+    import numpy as np
+    items, counts = host["items"], p["counts"]
+    first = np.concatenate(([0], np.cumsum(counts)))
+    slices = np.ascontiguousarray(np.stack((first[:-1], counts), axis=1))
+    d_slices = torch.from_numpy(slices).to(p["smooth"].device)
+    args = (p["smooth"].data_ptr(), p["labels"].data_ptr(), host["map_px"], d_items, items.ctypes.data, items.shape[0], d_tiles,
+            host["tiles"].shape[0], d_slices.data_ptr(), slices.ctypes.data, p["slots"].data_ptr())
+    return args, slices, d_slices, int(first[-1])
+
+
+def _detect_moments(args, rows, dev):
+    """The moments launch and its copy -> int64 (rows, 5) on the host."""
+    mom = torch.empty(rows, 5, dtype=torch.int64, device=dev)
+    check(lib.dpmn_detect_moments_i64(*args, mom.data_ptr(), rows, stream()))
+    return mom.cpu().numpy()
+
+
+def _detect_dirs(comps, mom, slices):
+    """The host's step between the two launches: per photo (comps (n, 5), moments (n, 6), k (n)) -- every component's direction
+    (utils.detect.axis_index, in Python ints; -1 where utils.detect.prefilter passes it over) -- and the int32 (rows, 2) table of
+    (c, s) that the extents launch reads, (0, 0) for k = -1."""
+    import numpy as np
+    from .utils.detect import DIRS, axis_index, prefilter
+    out, dirs = [], np.zeros((len(mom), 2), np.int32)
+    table = np.array(DIRS + ((0, 0),), np.int32)
+    for b, c in enumerate(comps):
+        at = int(slices[b, 0])
+        m = np.concatenate((c[:, 4:5], mom[at:at + len(c)]), axis=1)
+        ok = prefilter(c)
+        ks = np.full(len(c), -1, np.int64)
+        ks[ok] = axis_index(m[ok])
+        dirs[at:at + len(c)] = table[ks]
+        out.append((c, m, ks))
+    return out, dirs
+
+
+def _detect_extents(args, rows, dirs, dev):
+    """The upload of the directions, the extents launch and its copy -> int64 (rows, 4) [U2min, U2max, V2min, V2max] on the host (the
+    kernel keeps max -U2, max U2, max -V2, max V2)."""
+    import numpy as np
+    d_dirs = torch.from_numpy(dirs).to(dev)
+    ext = torch.empty(rows, 4, dtype=torch.int32, device=dev)
+    check(lib.dpmn_detect_extents_i32(*args, d_dirs.data_ptr(), ext.data_ptr(), rows, stream()))
+    return ext.cpu().numpy().astype(np.int64) * np.array([-1, 1, -1, 1])
+
+
+def _detect_oriented_pass(host, d_items, d_tiles, p):
+    """The two oriented launches behind one pass of _detect_pass -> per photo (comps (n, 5), moments (n, 6), k (n), extents (n, 4)) as
+    utils.detect's components / moments / axis_index / extents give them, in the order of the photo's table rows.  Two copies to the
+    host, the moment table and the extents, each of exactly the components' rows; between them the host chooses the directions."""
+    dev = p["smooth"].device
+    args, slices, d_slices, rows = _detect_oriented_args(host, d_items, d_tiles, p)
+    tables, dirs = _detect_dirs(_detect_comps(p), _detect_moments(args, rows, dev), slices)
+    ext = _detect_extents(args, rows, dirs, dev)
+    res = []
+    for b, (c, m, ks) in enumerate(tables):
+        at = int(slices[b, 0])
+        e = ext[at:at + len(c)].copy()
+        e[ks < 0] = 0
+        res.append((c, m, ks, e))
+    return res
+
+
+def _detect_oriented_run(packed, offsets, sizes, gap, vgap, floor, what):
+    """The checks and launches of the oriented ops -> (host, [row pass, column pass]): per pass (what _detect_pass returns, what
+    _detect_oriented_pass returns).  One gradient launch and one histogram copy serve both passes."""
+    from .utils.detect import check_params
+    try:
+        gap, vgap, floor = check_params(gap, vgap, floor)
+    except ValueError as e:
+        raise _abi.DpmnError("%s: %s" % (what, e)) from e
+    host = _detect_plan(packed, offsets, sizes, what)
+    d, d_items, d_tiles, g, hist, thr = _detect_thresholds(packed, host, floor)
+    passes = []
+    for a, b in ((gap, vgap), (vgap, gap)):      # the row pass, then the column pass: the same kernels with the gaps swapped
+        p = _detect_pass(host, d_items, d_tiles, g, thr, a, b)
+        passes.append((p, _detect_oriented_pass(host, d_items, d_tiles, p)))
+    return host, passes
+
+
+def detect_oriented_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, names=None):
+    """The ORIENTED text regions of a ragged batch of photos (csrc/detect.hip; utils/detect.py holds the recipe): the arguments of
+    detect_text_u8 -> per photo an int64 (n, 8) numpy array of quads tl, tr, br, bl (x, y) in hundredths of a photo pixel, not clamped
+    to the photo, at most utils.detect.MAX_BOXES: row for row utils.detect.detect_oriented_np.  Two passes over one gradient map and one
+    threshold (the smoothing with its gaps as given, then swapped); per pass the components' second moments and, along the direction
+    the host chooses from them, their extents.  Integer kernels: the same in every compute mode.  Beyond detect_text_u8's copies, the
+    moment tables and the extents of each pass cross to the host."""
+    from .utils.detect import cross_pass, oriented_rects, quads_from_rects
+    import numpy as np
+    host, passes = _detect_oriented_run(packed, offsets, sizes, gap, vgap, floor, "detect_oriented_u8")
+    out = []
+    for b, it in enumerate(host["items"]):
+        H, W = int(it[1]), int(it[2])
+        rows, cols = (oriented_rects(c, ks, e, H, W, column) for column, (c, m, ks, e) in ((False, passes[0][1][b]), (True, passes[1][1][b])))
+        out.append(quads_from_rects(cross_pass(rows, cols), H, W, names[b] if names else None))
+    return out
+
+
+def detect_oriented_tables_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24):
+    """The tables behind detect_oriented_u8, for tests: per photo [row pass, column pass], each (moments int64 (n, 6), k int64 (n),
+    extents int64 (n, 4)) in LABEL order (the labels and slots of every pass are copied back to find it): what
+    utils.detect.oriented_pass_np returns first."""
+    import numpy as np
+    host, passes = _detect_oriented_run(packed, offsets, sizes, gap, vgap, floor, "detect_oriented_tables_u8")
+    out = [[] for _ in host["items"]]
+    for p, tables in passes:
+        labels, slots = p["labels"].cpu().numpy(), p["slots"].cpu().numpy()
+        for b, (_, _, _, at, hm, wm, _, _) in enumerate(host["items"].tolist()):
+            lab = labels[at:at + hm * wm]
+            roots = np.nonzero(lab == np.arange(hm * wm))[0]      # ascending: the label order
+            order = slots[at:at + hm * wm][roots]
+            c, m, ks, e = tables[b]
+            out[b].append((m[order], ks[order], e[order]))
+    return out
 
 
 def detect_text_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, names=None):

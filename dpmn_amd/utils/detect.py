@@ -21,6 +21,36 @@ Per photo (RGB uint8, H x W, sides 1 .. utils.resize.MAX_SIDE):
 What it finds: well-contrasted, roughly horizontal words and lines.  What it misses: text less than about 50 luma levels from its
 background (below the Otsu threshold), vertical or strongly rotated text (5 w >= 6 h), glyphs taller than half the working map, and
 very large glyphs whose word spaces exceed `gap` at the working resolution (the word splits).  It is no learned detector.
+
+Oriented regions (main.py --demo_detect_oriented; detect_oriented_np, ops.detect_oriented_u8): stages 1 to 3 as above, then TWO passes
+over the one gradient map and the one threshold -- the row pass smooth(b, gap, vgap) and the column pass smooth(b, vgap, gap) -- and per
+component of a pass, still in integers only:
+  a. moments: area A and the sums of x, y, x^2, x y, y^2 over its pixels; mxx = A Sxx - Sx^2, mxy = A Sxy - Sx Sy, myy = A Syy - Sy^2.
+  b. axis: the k of the 64 directions DIRS (c_k, s_k) = round(16384 (cos, sin) of (k - 32) * 2.8125 degrees), c_k >= 0, that maximises
+     c^2 mxx + 2 c s mxy + s^2 myy, compared exactly in Python integers; ties go to the k nearest 32, then to the lower k.  Components
+     whose upright box is lower than MIN_H get no axis and are passed over (k = -1): a FURTHER filter of this recipe, not a shortcut
+     (a thin slanted component may reach H2 >= 6 S from an upright box 5 high), the same in the restatement and on the GPU.
+  c. extents: the least and greatest U2 = c (2x + 1) + s (2y + 1) and V2 = -s (2x + 1) + c (2y + 1) over its pixels (the pixel centres
+     along and across the axis, doubled and scaled by 16384); with e2 = |c| + |s| and S = 32768 the rectangle that covers the pixel
+     squares measures W2 = U2max - U2min + 2 e2 by H2 = V2max - V2min + 2 e2 (at k = 32: S w and S h of the upright box).
+  d. filter: H2 >= 6 S, 2 H2 <= S X (X = hm in the row pass, wm in the column pass), 5 W2 >= 6 H2, 100 A S^2 >= 35 W2 H2; the row pass
+     keeps |k - 32| <= 16 (at most 45 degrees), the column pass |k - 32| > 16.  Cross-pass rule: a rectangle is COVERED when its
+     centre lies inside a rectangle of the other pass that passed the filter (padding included, borders included, tested exactly in
+     that rectangle's frame) and whose W2 H2 is greater -- or, for a column-pass rectangle, not smaller.  A covered column-pass
+     rectangle is dropped: a word that both passes find is written once, and the letters that the column pass splits off a
+     horizontal word go.  A covered row-pass rectangle is dropped only when it is SQUAT, 2 W2 < 3 H2: such a piece of a larger steep
+     rectangle is a turned letter (most glyphs are at most 1.5 times as high as wide), while a piece 1.5 times as long as high may be a
+     line of a narrow block of horizontal text, which the column pass joins into one tall blob, and stays.  Nothing that one pass
+     finds is lost to the other; what the shape cannot tell is written twice: stacked short lines come with the blob around them
+     (steep, to be deleted by hand), and a steep word of unusually narrow glyphs (a turned l) comes with those letters beside it.
+     (Dropping column-pass rectangles only, whatever their size, loses a steep word whose centre falls on one of its own letters;
+     dropping by area alone loses the lines of the block.  The two cases are the same shape up to scale, hence the squatness.)
+  e. quads: padded by p S, p = (H2 // S + 5) // 10, on all four sides; the corners (U2, V2) go back by x = (c U2 - s V2) / (2 n),
+     y = (s U2 + c V2) / (2 n), n = c^2 + s^2, times r, in HUNDREDTHS of a photo pixel rounded half up, not clamped; tl, tr, br, bl with
+     u to the right and v down (clockwise in image coordinates); sorted by the top-left corner's (y, x), then the other corners; more
+     than MAX_BOXES: those of largest W2 H2 stay (ties: the earlier) and the same line is printed.
+Text steeper than 45 degrees is read along +u: whether a vertical sign reads upward or downward cannot be told from its shape, and at
+exactly 90 degrees the tie rule gives k = 0, -90 degrees, reading upward.
 """
 import numpy as np
 
@@ -215,3 +245,203 @@ def write_boxes(path, boxes):
     """The boxes of one photo as a box file that utils.quad.numbered_boxes reads (empty for no box)."""
     with open(path, "w", encoding="utf-8") as fh:
         fh.write(box_lines(boxes))
+
+
+# ---- oriented regions: everything below is integers only (Python ints where 64 bits do not suffice) ----
+
+UNIT = 16384         # the scale of DIRS
+S2 = 2 * UNIT        # one map pixel in the doubled, scaled units of U2 and V2
+AXIS_ROW = 16        # the row pass keeps |k - 32| <= AXIS_ROW, the column pass the rest
+# (c_k, s_k) = round(16384 cos, 16384 sin) of (k - 32) * 180 / 64 degrees: literal, so that no libm decides a byte
+DIRS = (
+    (0, -16384), (804, -16364), (1606, -16305), (2404, -16207), (3196, -16069), (3981, -15893), (4756, -15679), (5520, -15426),
+    (6270, -15137), (7005, -14811), (7723, -14449), (8423, -14053), (9102, -13623), (9760, -13160), (10394, -12665), (11003, -12140),
+    (11585, -11585), (12140, -11003), (12665, -10394), (13160, -9760), (13623, -9102), (14053, -8423), (14449, -7723), (14811, -7005),
+    (15137, -6270), (15426, -5520), (15679, -4756), (15893, -3981), (16069, -3196), (16207, -2404), (16305, -1606), (16364, -804),
+    (16384, 0), (16364, 804), (16305, 1606), (16207, 2404), (16069, 3196), (15893, 3981), (15679, 4756), (15426, 5520), (15137, 6270),
+    (14811, 7005), (14449, 7723), (14053, 8423), (13623, 9102), (13160, 9760), (12665, 10394), (12140, 11003), (11585, 11585),
+    (11003, 12140), (10394, 12665), (9760, 13160), (9102, 13623), (8423, 14053), (7723, 14449), (7005, 14811), (6270, 15137),
+    (5520, 15426), (4756, 15679), (3981, 15893), (3196, 16069), (2404, 16207), (1606, 16305), (804, 16364),
+)
+_TIE_ORDER = sorted(range(64), key=lambda k: (abs(k - 32), k))      # a later k of this order wins only when strictly greater
+
+
+def moments(labels):
+    """The labels of label() -> int64 (n, 6) [area, sum x, sum y, sum x^2, sum x y, sum y^2] per component, in label order."""
+    labels = np.asarray(labels)
+    ys, xs = np.nonzero(labels >= 0)
+    if len(ys) == 0:
+        return np.zeros((0, 6), np.int64)
+    _, inv = np.unique(labels[ys, xs], return_inverse=True)
+    n = int(inv.max()) + 1
+    out = np.zeros((n, 6), np.int64)
+    ys, xs = ys.astype(np.int64), xs.astype(np.int64)
+    for col, v in enumerate((np.ones_like(xs), xs, ys, xs * xs, xs * ys, ys * ys)):
+        np.add.at(out[:, col], inv, v)
+    return out
+
+
+def axis_index(moments):
+    """The table of moments() -> int64 (n): per component the k of DIRS that maximises c^2 mxx + 2 c s mxy + s^2 myy (the second moment
+    along the direction, times A^2), compared exactly; ties go to the k nearest 32, then to the lower k.  float64 only SELECTS: a k
+    whose rounded value (relative error below 1e-14) is more than 1e-9 of the greatest below it cannot be the exact maximum, and the
+    k that remain are compared in Python ints."""
+    m = np.asarray(moments, np.int64).reshape(-1, 6).astype(object)      # Python ints: the terms pass 2^64
+    n = m.shape[0]
+    if n == 0:
+        return np.zeros(0, np.int64)
+    A, sx, sy, sxx, sxy, syy = m.T
+    mxx, mxy, myy = A * sxx - sx * sx, A * sxy - sx * sy, A * syy - sy * sy
+    d = np.array(DIRS, np.float64)
+    V = (np.outer(mxx.astype(np.float64), d[:, 0] * d[:, 0]) + np.outer(mxy.astype(np.float64), 2 * d[:, 0] * d[:, 1])
+         + np.outer(myy.astype(np.float64), d[:, 1] * d[:, 1]))
+    scale = np.abs(mxx.astype(np.float64)) + np.abs(mxy.astype(np.float64)) + np.abs(myy.astype(np.float64))
+    cand = V >= V.max(axis=1, keepdims=True) - 1e-9 * UNIT * UNIT * scale[:, None]
+    arg = np.argmax(cand, axis=1).astype(np.int64)      # (exact where one k remains)
+    for i in np.nonzero(cand.sum(axis=1) > 1)[0].tolist():
+        best = None
+        for k in _TIE_ORDER:
+            if cand[i, k]:
+                c, s = DIRS[k]
+                v = (c * c) * mxx[i] + (2 * c * s) * mxy[i] + (s * s) * myy[i]
+                if best is None or v > best:      # (a later k of the order wins only when strictly greater)
+                    best, arg[i] = v, k
+    return arg
+
+
+def prefilter(comps):
+    """The table of components() -> bool (n): the components that get an axis at all, those whose upright box is at least MIN_H high.
+    A filter of its own (stage b), not only a shortcut: the oriented filter alone would let a few thin slanted components through."""
+    c = np.asarray(comps, np.int64).reshape(-1, 5)
+    return c[:, 3] - c[:, 1] >= MIN_H
+
+
+def extents(labels, k_of_component):
+    """The labels of label() and per component (in label order) its k of DIRS, or -1 for a component that is passed over -> int64
+    (n, 4) [U2min, U2max, V2min, V2max] over the component's pixels, U2 = c (2x + 1) + s (2y + 1), V2 = -s (2x + 1) + c (2y + 1); a
+    row of zeros where k is -1."""
+    labels = np.asarray(labels)
+    ks = np.asarray(k_of_component, np.int64).reshape(-1)
+    out = np.zeros((len(ks), 4), np.int64)
+    ys, xs = np.nonzero(labels >= 0)
+    if len(ys) == 0:
+        return out
+    _, inv = np.unique(labels[ys, xs], return_inverse=True)
+    if int(inv.max()) + 1 != len(ks):
+        raise ValueError("extents: %d components, %d directions" % (int(inv.max()) + 1, len(ks)))
+    d = np.array(DIRS + ((0, 0),), np.int64)[ks]      # (k = -1 takes the last row)
+    c, s = d[inv, 0], d[inv, 1]
+    X, Y = 2 * xs.astype(np.int64) + 1, 2 * ys.astype(np.int64) + 1
+    U, V = c * X + s * Y, c * Y - s * X
+    big = np.int64(1) << 40
+    for col, v, fn, init in ((0, U, np.minimum, big), (1, U, np.maximum, -big), (2, V, np.minimum, big), (3, V, np.maximum, -big)):
+        acc = np.full(len(ks), init, np.int64)
+        fn.at(acc, inv, v)
+        out[:, col] = acc
+    out[ks < 0] = 0
+    return out
+
+
+def oriented_rects(comps, ks, ext, H, W, column=False):
+    """Stage d without the cross-pass rule: the tables of one pass over an H x W photo (components(), the k per component with -1 for
+    none, extents(); rows in any common order) -> int64 (m, 8) [k, U2 of the left side, U2 of the right side, V2 of the top, V2 of the
+    bottom (padding included), W2, H2, 0] of the components that pass the filter and lie on the pass's side of 45 degrees."""
+    r, hm, wm = working_size(H, W)
+    comps = np.asarray(comps, np.int64).reshape(-1, 5)
+    ks, ext = np.asarray(ks, np.int64).reshape(-1), np.asarray(ext, np.int64).reshape(-1, 4)
+    d = np.array(DIRS + ((0, 0),), np.int64)[ks]
+    e2 = np.abs(d[:, 0]) + np.abs(d[:, 1])
+    W2, H2 = ext[:, 1] - ext[:, 0] + 2 * e2, ext[:, 3] - ext[:, 2] + 2 * e2
+    side = (np.abs(ks - 32) > AXIS_ROW) if column else (np.abs(ks - 32) <= AXIS_ROW)
+    keep = ((ks >= 0) & side & (H2 >= MIN_H * S2) & (2 * H2 <= S2 * (wm if column else hm)) & (5 * W2 >= 6 * H2)
+            & (100 * comps[:, 4] * S2 * S2 >= 35 * W2 * H2))
+    pad = ((H2 // S2 + 5) // 10) * S2 + e2
+    out = np.stack([ks, ext[:, 0] - pad, ext[:, 1] + pad, ext[:, 2] - pad, ext[:, 3] + pad, W2, H2, np.zeros_like(ks)], axis=1)
+    return out[keep]
+
+
+def covered(rects, others, ties):
+    """Stage d's cross-pass rule for one side: rows of oriented_rects() and those of the other pass -> bool (n): the centre lies inside
+    one of `others` whose W2 H2 is greater (ties: or equal).  The centre (Xc, Yc), times 4 n' in the rectangle's own direction
+    (c', s'), is projected onto the other's (c, s): U2 = 2 (c Xc + s Yc), so U2 * 2 n' = c PX + s PY is compared with the sides times
+    2 n' (all below 2^59)."""
+    rects, others = np.asarray(rects, np.int64).reshape(-1, 8), np.asarray(others, np.int64).reshape(-1, 8)
+    out = np.zeros(len(rects), bool)
+    if len(rects) == 0 or len(others) == 0:
+        return out
+    d = np.array(DIRS, np.int64)[others[:, 0]]
+    c, s, area = d[:, 0], d[:, 1], others[:, 5] * others[:, 6]
+    for i, (k, u0, u1, v0, v1, W2, H2, _) in enumerate(rects.tolist()):
+        c1, s1 = DIRS[k]
+        n2 = 2 * (c1 * c1 + s1 * s1)
+        PX, PY = c1 * (u0 + u1) - s1 * (v0 + v1), s1 * (u0 + u1) + c1 * (v0 + v1)
+        U, V = c * PX + s * PY, c * PY - s * PX
+        larger = (area >= W2 * H2) if ties else (area > W2 * H2)
+        out[i] = (larger & (others[:, 1] * n2 <= U) & (U <= others[:, 2] * n2) & (others[:, 3] * n2 <= V) & (V <= others[:, 4] * n2)).any()
+    return out
+
+
+def cross_pass(row_rects, col_rects):
+    """Stage d's cross-pass rule: the rows of oriented_rects() of the two passes -> those that stay, the row pass first.  A column-pass
+    rectangle goes when covered by a row-pass rectangle that is not smaller; a row-pass rectangle goes when covered by a larger
+    column-pass rectangle AND squat (2 W2 < 3 H2: a turned letter, not a line)."""
+    row_rects, col_rects = np.asarray(row_rects, np.int64).reshape(-1, 8), np.asarray(col_rects, np.int64).reshape(-1, 8)
+    squat = 2 * row_rects[:, 5] < 3 * row_rects[:, 6]
+    return np.concatenate([row_rects[~(squat & covered(row_rects, col_rects, False))], col_rects[~covered(col_rects, row_rects, True)]])
+
+
+def quads_from_rects(rects, H, W, name=None):
+    """Stage e: rows of oriented_rects() of an H x W photo -> int64 (n, 8) quads tl, tr, br, bl as x, y in hundredths of a photo pixel,
+    sorted, at most MAX_BOXES (one printed line when some are dropped; name: the photo)."""
+    r = working_size(H, W)[0]
+    quads = []
+    for k, u0, u1, v0, v1, W2, H2, _ in np.asarray(rects, np.int64).reshape(-1, 8).tolist():
+        c, s = DIRS[k]
+        n = c * c + s * s
+        q = []
+        for u, v in ((u0, v0), (u1, v0), (u1, v1), (u0, v1)):
+            q += [(100 * r * (c * u - s * v) + n) // (2 * n), (100 * r * (s * u + c * v) + n) // (2 * n)]      # half up
+        quads.append((q, W2 * H2))
+    quads.sort(key=lambda t: (t[0][1], t[0][0], t[0][2:]))
+    if len(quads) > MAX_BOXES:
+        print("detect: %s%d regions found, the %d of largest area kept" % (name + ": " if name else "", len(quads), MAX_BOXES))
+        big = sorted(sorted(range(len(quads)), key=lambda i: -quads[i][1])[:MAX_BOXES])      # (sorted() is stable: ties keep the earlier)
+        quads = [quads[i] for i in big]
+    return np.array([q for q, _ in quads], np.int64).reshape(-1, 8)
+
+
+def oriented_pass_np(labels, H, W, column=False):
+    """One pass of the restatement: the labels of a smoothed map -> (moments (n, 6), k (n) with -1 for a component that is passed
+    over, extents (n, 4), the rows of oriented_rects()), the tables in label order: what ops.detect_oriented_tables_u8 returns."""
+    comps, m = components(labels), moments(labels)
+    ks = np.where(prefilter(comps), axis_index(m), -1)
+    ext = extents(labels, ks)
+    return m, ks, ext, oriented_rects(comps, ks, ext, H, W, column)
+
+
+def detect_oriented_np(photo, gap=GAP, vgap=VGAP, floor=FLOOR, name=None):
+    """One photo -> its oriented regions, int64 (n, 8): quads tl, tr, br, bl in hundredths of a photo pixel.  The CPU reference of
+    ops.detect_oriented_u8."""
+    gap, vgap, floor = check_params(gap, vgap, floor)
+    g, hist = gradient(luma_map(photo))
+    b = g >= threshold(hist, floor)
+    H, W = photo.shape[:2]
+    rows = oriented_pass_np(label(smooth(b, gap, vgap)), H, W)[3]
+    cols = oriented_pass_np(label(smooth(b, vgap, gap)), H, W, True)[3]
+    return quads_from_rects(cross_pass(rows, cols), H, W, name)
+
+
+def _hundredths(v):
+    v = int(v)
+    return "%s%d.%02d" % ("-" if v < 0 else "", abs(v) // 100, abs(v) % 100)
+
+
+def quad_lines(quads):
+    """Quads (n, 8) in hundredths of a pixel -> the text of a box file: one line x1,y1,x2,y2,x3,y3,x4,y4 per quad in decimals."""
+    return "".join(",".join(_hundredths(v) for v in q) + "\n" for q in np.asarray(quads, np.int64).reshape(-1, 8).tolist())
+
+
+def write_quads(path, quads):
+    """The oriented regions of one photo as a box file that utils.quad.numbered_boxes reads (empty for none)."""
+    with open(path, "w", encoding="utf-8") as fh:
+        fh.write(quad_lines(quads))

@@ -681,7 +681,14 @@ int dpmn_poly_crop_u8(const unsigned char* packed, long packed_bytes, const long
  * photo [first row of its part of the table, rows in it] (slices_host: the same in HOST memory); the components of a photo take the
  * rows of its part in no fixed order.  counts, int32 (B) (zeroed here): the components of every photo -- where that exceeds the
  * photo's rows the surplus is left out of the table and the caller calls again with a larger one (the call may be repeated: flat
- * labels stay as they are).  slots: int32 (map_px) of scratch.  Two launches. */
+ * labels stay as they are).  slots: int32 (map_px) of scratch.  Two launches.
+ * The oriented regions (utils/detect.py, stages a and c) read what dpmn_detect_stats_i32 left behind: the flat labels and slots
+ * (slots[least index of a component] = its row in the photo's part of the table), with the same items, tiles and slices.
+ * dpmn_detect_moments_i64: table, int64 (table_rows, 5) (zeroed here): per component [sum x, sum y, sum x^2, sum x y, sum y^2] over
+ * its pixels (its area is in the table of dpmn_detect_stats_i32).  One launch.
+ * dpmn_detect_extents_i32: dirs, device int32 (table_rows, 2): per component the (c, s) of its direction, (0, 0): passed over.  table,
+ * int32 (table_rows, 4) (every byte set to 0x80 here, which is what a row that is passed over keeps): per component [max -U2, max U2,
+ * max -V2, max V2] over its pixels, U2 = c (2x + 1) + s (2y + 1), V2 = -s (2x + 1) + c (2y + 1); |c|, |s| <= 16384.  One launch. */
 int dpmn_detect_gradient_u8(const unsigned char* packed, long packed_bytes, const long long* items, const long long* items_host /* HOST array */,
                             int B, const int* tiles, int n_tiles, unsigned char* g, long map_px, unsigned int* hist, dpmn_stream_t stream);
 int dpmn_detect_label_i32(const unsigned char* g, long map_px, const long long* items, const long long* items_host /* HOST array */, int B,
@@ -690,6 +697,14 @@ int dpmn_detect_label_i32(const unsigned char* g, long map_px, const long long* 
 int dpmn_detect_stats_i32(const unsigned char* smooth, int* labels, long map_px, const long long* items, const long long* items_host /* HOST array */,
                           int B, const int* tiles, int n_tiles, const long long* slices, const long long* slices_host /* HOST array */,
                           int* counts, int* slots, int* table, long table_rows, dpmn_stream_t stream);
+int dpmn_detect_moments_i64(const unsigned char* smooth, const int* labels, long map_px, const long long* items,
+                            const long long* items_host /* HOST array */, int B, const int* tiles, int n_tiles, const long long* slices,
+                            const long long* slices_host /* HOST array */, const int* slots, long long* table, long table_rows,
+                            dpmn_stream_t stream);
+int dpmn_detect_extents_i32(const unsigned char* smooth, const int* labels, long map_px, const long long* items,
+                            const long long* items_host /* HOST array */, int B, const int* tiles, int n_tiles, const long long* slices,
+                            const long long* slices_host /* HOST array */, const int* slots, const int* dirs, int* table, long table_rows,
+                            dpmn_stream_t stream);
 
 /* rotation augmentation of the trainer (utils/util.py:37-58 torch_rotate_img; super_resolution.py:144-151, 358-365):
  * per-image affine with aspect-ratio jitter -> affine_grid (align_corners=False) -> bilinear grid_sample, zeros padding.

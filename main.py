@@ -16,7 +16,8 @@ word by a polygon (2k points, k along the top edge and k along the bottom, as CT
 strip by strip on the GPU (polygon regions are written as files; `--demo_paste_polygons` on top of `--demo_paste` also warps them back into
 the photo, strip by strip, in box-file order with the quadrilaterals); with `--demo_detect` in place of `--demo_boxes` the box files are
 written by the run itself: the text regions of every photo are found on the GPU by a classical, integer recipe (utils/detect.py) into
-`<demo_out>/boxes`, and the run goes on as with `--demo_boxes <demo_out>/boxes`.  `--train_state PATH` makes a training run continuable: the same command line starts the
+`<demo_out>/boxes`, and the run goes on as with `--demo_boxes <demo_out>/boxes` (`--demo_detect_oriented` on top: the regions are
+rotated quadrilaterals along the text's own direction, so slanted and vertical text is found too).  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--ema DECAY` keeps an exponential moving average of the trained weights; the
 validation passes score it and the best-model checkpoints hold it.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
 (`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image; `--psf_blur KINDS`: with a random motion, defocus or elongated-Gaussian blur of the HR pixels first); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB); `--train_words FILE` trains from a word list alone: the HR images are rendered on the GPU (`--train_words_fonts DIR`: in the fonts of a directory; `--train_words_epoch N`: samples per epoch).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
@@ -84,15 +85,19 @@ DEMO_DETECT_OR_BOXES = ("main.py: --demo_detect does not combine with --demo_box
 DEMO_DETECT_GAP = "main.py: --demo_detect_gap must be 1 .. 64 (the longest gap between letters, in pixels of the working map, that joins a word)"
 DEMO_DETECT_FLOOR = "main.py: --demo_detect_floor must be 1 .. 255 (the least gradient of the luma that counts as an edge of a letter)"
 DEMO_DETECT_FLAGS_NEED = "main.py: --demo_detect_gap and --demo_detect_floor need --demo_detect"
+DEMO_DETECT_ORIENTED_NEEDS = ("main.py: --demo_detect_oriented needs --demo_detect: it makes the regions that --demo_detect finds rotated "
+                              "quadrilaterals along the text's own direction")
 
 
 def demo_detect_setting(args):
     """--demo_detect and its two numbers, checked -> None without the flag, else (gap, floor).  ValueError (the message without its
-    'main.py: ') for the flag without --demo_dir or with --demo_boxes / --demo_polygons, a number outside its range, or a number without
-    the flag."""
+    'main.py: ') for the flag without --demo_dir or with --demo_boxes / --demo_polygons, a number outside its range, or a number or
+    --demo_detect_oriented without the flag."""
     from dpmn_amd.utils.detect import FLOOR, GAP, MAX_GAP
     gap, floor = getattr(args, "demo_detect_gap", None), getattr(args, "demo_detect_floor", None)
     if not getattr(args, "demo_detect", False):
+        if getattr(args, "demo_detect_oriented", False):
+            raise ValueError(DEMO_DETECT_ORIENTED_NEEDS[len("main.py: "):])
         if gap is not None or floor is not None:
             raise ValueError(DEMO_DETECT_FLAGS_NEED[len("main.py: "):])
         return None
@@ -331,7 +336,9 @@ def main(config, args):
             # from here the run is the one that --demo_boxes <demo_out>/boxes starts
             from dpmn_amd.dataset.folder import detect_box_files
             box_dir = os.path.join(out_dir, "boxes")
-            print("%d regions detected, box files in %s" % (detect_box_files(args.demo_dir, box_dir, bs, mission.device, *detect), box_dir))
+            print("%d regions detected, box files in %s"
+                  % (detect_box_files(args.demo_dir, box_dir, bs, mission.device, *detect,
+                                      oriented=getattr(args, "demo_detect_oriented", False)), box_dir))
         if box_dir:
             # whole photos and one box file per photo: every quadrilateral is rectified on the GPU (utils/quad.py), then goes the way
             # of a crop of the folder -- one <stem>_<k>_sr.png per region
@@ -514,6 +521,14 @@ if __name__ == '__main__':
                              'words and lines; it is no learned detector (not EAST or DBNet): low-contrast, vertical or strongly rotated '
                              'text is missed and very large glyphs may split into several boxes.  The files are ordinary box files: '
                              'correct them by hand and pass them with --demo_boxes')
+    parser.add_argument('--demo_detect_oriented', action='store_true', default=False,
+                        help='with --demo_detect: the box files hold rotated quadrilaterals along every region\'s own direction (one of '
+                             '64 directions, 2.8125 degrees apart, from the second moments of its pixels) instead of upright rectangles, '
+                             'so slanted and vertical text is found and rectified along its baseline.  Of a word that both smoothing '
+                             'passes find one region is written, and a turned letter inside a steep word is left out; a narrow block '
+                             'of short horizontal lines keeps its lines and also gets one steep region around the block, to be '
+                             'deleted by hand.  Text steeper than 45 degrees is read along its longer side; whether a vertical sign reads upward '
+                             'or downward cannot be told from its shape (exactly vertical text is read upward)')
     parser.add_argument('--demo_detect_gap', type=int, default=None, metavar='N',
                         help='with --demo_detect: the longest gap between letters, in pixels of the working map (the photo reduced to at '
                              'most 1024 on its long side), that still joins them into one word (1 .. 64, default 12)')
