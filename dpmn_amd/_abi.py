@@ -268,6 +268,9 @@ SIGNATURES = {
     "dpmn_ctc_lexicon_f32": (_i, [fp, _i, _i, fp, _i, fp, fp, fp, _i, _i, fp]),
     "dpmn_edit_lexicon_workspace_bytes": (_sz, [_i, _i]),
     "dpmn_edit_lexicon_i32": (_i, [fp, fp, _i, fp, fp, fp, _i, fp]),
+    "dpmn_ctc_conf_f32": (_i, [fp, _i, _i, fp, fp, fp, _i, _i, fp]),
+    "dpmn_attn_conf_f32": (_i, [fp, fp, _i, fp, fp, _i, _i, _i, fp]),
+    "dpmn_turn180_f32": (_i, [fp, fp, _i, _i, _i, _i, fp]),
     "dpmn_aster_prep_f32": (_i, [fp, _l, fp, fp, _i, _i, _i, _i, _i, fp]),
     "dpmn_subsample_nhwc_f32": (_i, [fp, fp, _i, _i, _i, _i, _i, _i, fp]),
     "dpmn_aster_beam_workspace_bytes": (_sz, [_i, _i]),

@@ -339,7 +339,7 @@ class TextSR(base.TextBase):
 
     @torch.no_grad()
     def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None, boxes=False, paste=False,
-             feather=1.0, paste_polygons=False, lexicon=None):
+             feather=1.0, paste_polygons=False, lexicon=None, confidence=False, upright=False, min_conf=None):
         """Super-resolve someone's own images (ours; main.py --demo_dir): batches yields (names, images_lr) as
         dataset.folder.folder_batches does.  Per batch `refine` (label_vecs from the frozen CRNN for tatt / tpgsr, as in eval), then
         save_image's quantisation on the GPU (ops.quantize_sr_u8), ONE device-to-host copy and one <stem>_sr.png per input under
@@ -375,7 +375,23 @@ class TextSR(base.TextBase):
         polygons are pasted from one list in box-file order (ops.paste_mixed_u8).  The region files and demo_result.csv do not change.
         lexicon (an ops.Lexicon, main.py --rec_lexicon; needs a recogniser, not with tile: a window is not a word): the SR image is
         also read under the lexicon (as in eval) and every row and demo_result.csv gain the columns sr_lexicon, sr_lexicon_score after
-        sr_string: the lexicon's word and its CTC log-likelihood (the CRNN's score protocol) or its edit distance to sr_string."""
+        sr_string: the lexicon's word and its CTC log-likelihood (the CRNN's score protocol) or its edit distance to sr_string.
+        confidence / upright / min_conf (ours; main.py --demo_conf, --demo_upright, --demo_min_conf; utils/confidence.py; not with
+        tile): rec must be an object with read_conf(images) -> (strings, scores, terms) -- the native recognisers, or a stub; a plain
+        callable returns no score and is refused.  Every read then comes from read_conf, and with any of the three the rows gain
+        lr_conf after lr_string and sr_conf after sr_string (exp(score / terms), written with %.4f).
+        upright: every LR batch is read twice on the device, as it is and through ops.turn180 (the mask channel turns along);
+        utils.confidence.choose_direction picks per image, and the chosen tensor is what `refine`, the region file and sr_string see
+        (one more recogniser pass per LR batch, no SR pass more).  lr_string / lr_conf are the chosen direction's, and a column turned
+        (0 / 1) follows sr_conf.  With paste a turned region goes into its quadrilateral with the corner list rotated by two (a
+        polygon of 2k points: by k), so the pixels land where they were cut.
+        min_conf C (0 < C < 1; needs boxes): a region whose sr_string is empty or whose sr_conf < C is dropped -- no region file, not
+        pasted -- and its row stays, with a last column kept = 0 (1 otherwise); one printed line per photo gives the dropped count.
+        With boxes, upright or min_conf write out_dir/boxes_read/<stem>.txt: the kept regions in box-file order, the corners in the
+        chosen reading order, sr_string as the transcription -- a box file for a second run.  The corner lists come with the batches:
+        they must then be made with photos=True, whether paste is set or not.
+        The columns, in order: file, [box, label,] lr_string, lr_conf, sr_string, sr_conf, [turned,] [sr_lexicon, sr_lexicon_score,]
+        [kept]; the lexicon's read of the SR image stays a second call through read_lexicon.  Without the three nothing changes."""
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
         if lexicon is not None and tile:
@@ -383,6 +399,7 @@ class TextSR(base.TextBase):
         if lexicon is not None and reader is None:
             raise ValueError("demo: a lexicon needs a recogniser")
         lex_reader = self._lexicon_reader(rec, reader, lexicon)
+        conf_reader = self._conf_reader(rec, tile, boxes, confidence, upright, min_conf)
         for m in model_list:
             m.eval()
         fn = text_prior_fn or self.default_text_prior()
@@ -394,10 +411,14 @@ class TextSR(base.TextBase):
             raise ValueError("demo: paste_polygons=True needs paste=True (the polygons are pasted into the photo that paste=True writes)")
         if boxes:
             labels = []
+            conf_kw = {} if conf_reader is None else dict(conf_reader=conf_reader, upright=bool(upright), min_conf=min_conf, out_dir=out_dir)
             for names, pixels, preds_lr, preds_sr, photos, *lex in self._demo_regions(model_list, model_psn, batches, fn, reader, chunk, tile, labels,
                                                                                        float(feather) if paste else None, bool(paste_polygons),
-                                                                                       lex_reader):
-                self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken, *lex)
+                                                                                       lex_reader, **conf_kw):
+                if conf_reader is not None:      # lex = [the lexicon's item or None, (lr_conf, sr_conf, turned or None), kept or None]
+                    self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken, lex[0], conf=lex[1], kept=lex[2])
+                else:
+                    self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken, *lex)
                 self._demo_write(out_dir, [stem + "_photo.png" for stem, _ in photos], [a for _, a in photos], [''] * len(photos),
                                  [''] * len(photos), [], taken)
             # <stem>_<k>.png, lr, sr -> stem, k, label, lr, sr
@@ -410,11 +431,18 @@ class TextSR(base.TextBase):
         for names, images_lr in batches:
             n = len(names)
             images_lr = images_lr.to(self.device)
+            if conf_reader is not None:
+                images_lr, preds_lr, conf_lr, turned = self._demo_upright(conf_reader, images_lr, upright)
             if n == 1:
                 images_lr = torch.cat([images_lr, images_lr], 0)
             label_vecs = self.label_vecs_from_crnn(images_lr) if self.args.arch in ('tatt', 'tpgsr') else None
             sr = self.refine(model_list, model_psn, images_lr, label_vecs, fn)[:n]
             pixels = ops.quantize_sr_u8(sr).cpu().numpy()
+            if conf_reader is not None:
+                preds_sr, conf_sr = conf_reader(sr[:, :3])
+                self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex_reader(sr[:, :3])[1:] if lex_reader is not None else None,
+                                 conf=(conf_lr, conf_sr, turned if upright else None))
+                continue
             blank = [''] * n
             preds_lr = reader(images_lr[:n, :3]) if reader is not None else blank
             if lex_reader is not None:
@@ -425,34 +453,87 @@ class TextSR(base.TextBase):
             self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken)
         with open(os.path.join(out_dir, "demo_result.csv"), "w", newline="") as out:
             w = csv.writer(out)
-            w.writerow((["file", "box", "label", "lr_string", "sr_string"] if boxes else ["file", "lr_string", "sr_string"])
-                       + (["sr_lexicon", "sr_lexicon_score"] if lexicon is not None else []))
+            head = ["file", "box", "label"] if boxes else ["file"]
+            if conf_reader is None:
+                head += ["lr_string", "sr_string"]
+            else:
+                head += ["lr_string", "lr_conf", "sr_string", "sr_conf"] + (["turned"] if upright else [])
+            w.writerow(head + (["sr_lexicon", "sr_lexicon_score"] if lexicon is not None else []) + (["kept"] if min_conf is not None else []))
             w.writerows(rows)
         return rows
 
     @staticmethod
-    def _demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex=None):
+    def _conf_reader(rec, tile, boxes, confidence, upright, min_conf):
+        """demo: images -> (strings, conf values) through rec.read_conf, or None without confidence / upright / min_conf.  ValueError
+        of one line for the flags with tile, a recogniser without read_conf, min_conf without boxes or outside (0, 1)."""
+        if not (confidence or upright or min_conf is not None):
+            return None
+        from ..utils.confidence import confidence as conf_of
+        if tile:
+            raise ValueError("demo: confidence, upright and min_conf do not combine with tile=True (a window of a line is not a word)")
+        if not callable(getattr(rec, "read_conf", None)):
+            raise ValueError("demo: confidence, upright and min_conf need a recogniser object with read_conf(images) -> (strings, scores, "
+                             "terms); a plain callable returns no score")
+        if min_conf is not None and not boxes:
+            raise ValueError("demo: min_conf needs boxes=True (it drops regions of a photo; an image of a folder is not a candidate region)")
+        if min_conf is not None and not 0.0 < float(min_conf) < 1.0:
+            raise ValueError("demo: min_conf must lie in (0, 1), got %r" % (min_conf,))
+
+        def read(images):
+            strings, scores, terms = rec.read_conf(images)
+            return [str(s) for s in strings], conf_of(scores, terms)
+        return read
+
+    @staticmethod
+    def _demo_upright(conf_reader, x, upright):
+        """demo: the LR read of a batch x (n, C, h, w) -> (the batch, its strings, its conf values, turned flags).  upright: the batch
+        is also read through ops.turn180 and every image is taken in the direction utils.confidence.choose_direction picks."""
+        from ..utils.confidence import choose_direction
+        s_up, c_up = conf_reader(x[:, :3])
+        if not upright:
+            return x, s_up, c_up, [0] * len(s_up)
+        xt = ops.turn180(x)
+        s_t, c_t = conf_reader(xt[:, :3])
+        turned = [choose_direction(cu, su, ct, st) for cu, su, ct, st in zip(c_up, s_up, c_t, s_t)]
+        if any(turned):
+            x = torch.where(torch.tensor(turned, device=x.device).view(-1, 1, 1, 1), xt, x)
+        return (x, [st if t else su for t, su, st in zip(turned, s_up, s_t)], [ct if t else cu for t, cu, ct in zip(turned, c_up, c_t)],
+                [int(t) for t in turned])
+
+    @staticmethod
+    def _demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex=None, conf=None, kept=None):
         """demo: one <stem>_sr.png per image of a batch and its row; lex: None, or (the lexicon's strings, their scores), two more
-        columns."""
+        columns.  conf: None, or (lr conf values, sr conf values, turned flags or None): the row's confidence columns.  kept: None,
+        or one flag per image: an image that is not kept gets no file, and the row ends with the flag."""
         from PIL import Image
         more = [[str(w), "%.6g" % sc] for w, sc in zip(*lex)] if lex is not None else [[]] * len(names)
-        for name, a, s_lr, s_sr, extra in zip(names, pixels, preds_lr, preds_sr, more):
-            out_name = os.path.splitext(name)[0] + "_sr.png"
-            if out_name in taken:
-                out_name = name + "_sr.png"
-            while out_name in taken:
-                out_name = "_" + out_name
-            taken.add(out_name)
-            Image.fromarray(a).save(os.path.join(out_dir, out_name))
-            rows.append([name, str(s_lr), str(s_sr)] + extra)
+        for i, (name, a, s_lr, s_sr, extra) in enumerate(zip(names, pixels, preds_lr, preds_sr, more)):
+            if kept is None or kept[i]:
+                out_name = os.path.splitext(name)[0] + "_sr.png"
+                if out_name in taken:
+                    out_name = name + "_sr.png"
+                while out_name in taken:
+                    out_name = "_" + out_name
+                taken.add(out_name)
+                Image.fromarray(a).save(os.path.join(out_dir, out_name))
+            if conf is None:
+                rows.append([name, str(s_lr), str(s_sr)] + extra)
+                continue
+            rows.append([name, str(s_lr), "%.4f" % conf[0][i], str(s_sr), "%.4f" % conf[1][i]] + ([str(int(conf[2][i]))] if conf[2] is not None else [])
+                        + extra + ([str(int(bool(kept[i])))] if kept is not None else []))
 
     def _demo_regions(self, model_list, model_psn, batches, fn, reader, chunk, tile, labels_out, feather=None, paste_polygons=False,
-                      lex_reader=None):
+                      lex_reader=None, conf_reader=None, upright=False, min_conf=None, out_dir=None):
         """demo(boxes=True): per batch of regions -> (names, one (H, W_r, 3) uint8 array per region, the LR reads, the SR reads, the
         pasted photos); the regions' labels are appended to labels_out.  tile: the batches carry a plan and go through _demo_windows.
         feather: None, or demo(paste=True)'s -- the batches then end with the photos item and the pasted photos are _demo_paste's list
         (empty otherwise); paste_polygons: demo's.  lex_reader (demo's lexicon; not with tile): the SR regions are read through it
-        and the tuple gets a sixth item, (the lexicon's strings, their scores)."""
+        and the tuple gets a sixth item, (the lexicon's strings, their scores).
+        conf_reader (demo's confidence / upright / min_conf; not with tile): every read comes from it, the LR read through
+        _demo_upright, and the tuple ends with three items: the lexicon's item or None, (lr conf values, sr conf values, turned flags
+        or None), kept flags or None.  A turned region is pasted with its corner list rotated, a dropped one not at all; with upright or
+        min_conf the batches carry the photos item and out_dir/boxes_read/<stem>.txt is written per photo."""
+        from ..utils.confidence import box_line, rotate_corners
         paste = feather is not None
         if tile:
             held = []
@@ -472,9 +553,15 @@ class TextSR(base.TextBase):
             images_lr = images_lr.to(self.device)
             pixels, preds_lr, preds_sr, on_device = [], [], [], []
             lex = ([], [])
+            conf_lr, conf_sr, turned = [], [], []
             for lo in range(0, images_lr.shape[0], chunk):
                 x = images_lr[lo:lo + chunk]
                 n = x.shape[0]
+                if conf_reader is not None:
+                    x, s_lr, c_lr, t = self._demo_upright(conf_reader, x, upright)
+                    preds_lr += s_lr
+                    conf_lr += c_lr
+                    turned += t
                 if n == 1:
                     x = torch.cat([x, x], 0)
                 label_vecs = self.label_vecs_from_crnn(x) if self.args.arch in ('tatt', 'tpgsr') else None
@@ -483,6 +570,15 @@ class TextSR(base.TextBase):
                 pixels.append(q.cpu().numpy())
                 if paste:
                     on_device.append(q)
+                if conf_reader is not None:
+                    s_sr, c_sr = conf_reader(sr[:, :3])
+                    preds_sr += s_sr
+                    conf_sr += c_sr
+                    if lex_reader is not None:
+                        got = lex_reader(sr[:, :3])
+                        lex[0].extend(got[1])
+                        lex[1].extend(got[2])
+                    continue
                 preds_lr += list(reader(x[:n, :3])) if reader is not None else [''] * n
                 if lex_reader is not None:
                     got = lex_reader(sr[:, :3])
@@ -492,18 +588,41 @@ class TextSR(base.TextBase):
                 else:
                     preds_sr += list(reader(sr[:, :3])) if reader is not None else [''] * n
             pasted = []
+            kept, skip = None, ()
+            if conf_reader is not None and (upright or min_conf is not None):
+                if not photos:
+                    raise ValueError("demo: upright and min_conf with boxes=True need batches made with photos=True (they carry the corner "
+                                     "lists that boxes_read is written from)")
+                if min_conf is not None:
+                    kept = [bool(s) and c >= float(min_conf) for s, c in zip(preds_sr, conf_sr)]
+                    skip = {r for r, k in enumerate(kept) if not k}
+                # (a turned region is read, and pasted, from its opposite corner)
+                photos = [photos[0][:3] + ([rotate_corners(q) if t else q for q, t in zip(photos[0][3], turned)],)]
+                os.makedirs(os.path.join(out_dir, "boxes_read"), exist_ok=True)
+                stems = [name.rsplit("_", 1)[0] for name in names]
+                for stem in sorted(set(stems), key=stems.index):
+                    mine = [r for r, s in enumerate(stems) if s == stem]
+                    with open(os.path.join(out_dir, "boxes_read", stem + ".txt"), "w", encoding="utf-8") as fh:
+                        fh.writelines(box_line(photos[0][3][r], preds_sr[r]) + "\n" for r in mine if r not in skip)
+                    if min_conf is not None:
+                        print("demo: %d of %d regions of %s dropped (empty read or confidence below %g)"
+                              % (sum(r in skip for r in mine), len(mine), stem, float(min_conf)))
             if paste:
                 # the quantised regions of the batch, all H x W x 3: flat, they are pack_ragged's layout
                 q = on_device[0] if len(on_device) == 1 else torch.cat(on_device, 0)
                 R, H, W = q.shape[:3]
                 pasted = self._demo_paste(names, photos[0], q.reshape(-1), [(r * H * W * 3, H, W) for r in range(R)], feather,
-                                          paste_polygons)
+                                          paste_polygons, *((skip,) if skip else ()))
+            if conf_reader is not None:
+                yield (names, [a for p in pixels for a in p], preds_lr, preds_sr, pasted, lex if lex_reader is not None else None,
+                       (conf_lr, conf_sr, turned if upright else None), kept)
+                continue
             if lex_reader is not None:
                 yield names, [a for p in pixels for a in p], preds_lr, preds_sr, pasted, lex
                 continue
             yield names, [a for p in pixels for a in p], preds_lr, preds_sr, pasted
 
-    def _demo_paste(self, names, photos, sr_packed, sr_meta, feather, paste_polygons=False):
+    def _demo_paste(self, names, photos, sr_packed, sr_meta, feather, paste_polygons=False, skip=()):
         """demo(paste=True): the photos of one batch with their SR regions pasted back -> [(stem, (scale * H, scale * W, 3) uint8
         array)] in batch order.  photos = (packed, meta, owners, quads) as dataset.folder.box_region_batches(photos=True) yields it;
         sr_packed / sr_meta hold the batch's SR regions on the device, one per name, in pack_ragged's layout.  Per photo: the enlargement
@@ -511,7 +630,8 @@ class TextSR(base.TextBase):
         host.  A photo too large to enlarge, or a region utils.paste.paste_coeffs refuses, is passed over with one printed line.  The
         regions of polygons (more than 4 points: the batches were made with polygons=True) are not pasted -- one printed line per photo
         gives their count -- unless paste_polygons: a polygon then joins the photo's list with its strip table
-        (utils.paste_poly.strip_table; one it refuses gets a refused quadrilateral's printed line)."""
+        (utils.paste_poly.strip_table; one it refuses gets a refused quadrilateral's printed line).  skip: the regions (indices into
+        names) that demo's min_conf dropped; they are not pasted, and a photo all of whose regions were dropped is not written."""
         import numpy as np
         from ..utils.paste import paste_coeffs
         from ..utils.paste_poly import strip_table
@@ -526,6 +646,10 @@ class TextSR(base.TextBase):
             if not mine:
                 continue
             stem = names[mine[0]].rsplit("_", 1)[0]
+            if skip:
+                mine = [r for r in mine if r not in skip]
+                if not mine:
+                    continue
             if s * H > MAX_SIDE or s * W > MAX_SIDE:
                 print("demo: no pasted photo for %s (%d x %d times %d: a side above %d is not resized)" % (stem, H, W, s, MAX_SIDE))
                 continue

@@ -352,6 +352,22 @@ class NativeASTER(PackedEval, ASTER):
         return ids_to_strings(self.pred_rec(images).numpy(), info)
 
     @torch.no_grad()
+    def read_conf(self, images, info=None):
+        """`read` with a confidence (ours; utils/confidence.py) -> (strings, scores, terms): the strings are `read`'s, from the same
+        forward pass; score = the stored sequence score of the returned hypothesis at the step where it ends, terms = its length
+        counted with the EOS.  Host code over the stored tensors that `read`'s single copy already brings
+        (utils.confidence.beam_score): no launch and no copy more."""
+        from ..utils.confidence import beam_score
+        info = info or self.info
+        if info is None:
+            raise ValueError("dpmn_amd NativeASTER.read_conf: pass the AsterInfo of this vocabulary")
+        self._check_eval()
+        P = self._packs()
+        rec, st = self.beam_search(self.encode(self.rectify(*self.prep(images), P)[1], P), return_stored=True, P=P)
+        _, score, terms = beam_score(st["symbols"], st["predecessors"], st["scores"], rec.shape[0], BEAM, self.eos)
+        return ids_to_strings(rec.numpy(), info), [float(v) for v in score], [int(v) for v in terms]
+
+    @torch.no_grad()
     def read_lexicon(self, images, lex, info=None):
         """-> (greedy strings, the lexicon's strings, distances): `read`'s strings, then per string the lexicon word at the least
         edit distance (ops.edit_read: the strings packed and uploaded, dpmn_edit_lexicon_i32, one copy back).  An attention decoder

@@ -183,6 +183,22 @@ class NativeCRNN(PackedEval, CRNN):
         return greedy, lex.strings(h[n:n + B]), [float(v) for v in h[n + B:].view("float32")]
 
     @torch.no_grad()
+    def read_conf(self, images):
+        """`read` with a confidence (ours; utils/confidence.py) -> (strings, scores, terms): the strings are `read`'s, from the same
+        forward pass; score = the CTC log-likelihood of each image's own greedy string (dpmn_ctc_conf_f32 on the same logits rows,
+        written behind the lengths so that ONE device-to-host copy brings everything), terms = max(its length, 1).
+        utils.confidence.confidence(scores, terms) gives exp(score / terms)."""
+        self._check_eval()
+        rows, B, T = self.logits_rows(self.prep(images), self._packs())
+        buf, _, _ = ops.ctc_greedy(rows, B, T, self.nclass, extra=B)
+        ops.ctc_confidence(rows, B, T, self.nclass, buf)
+        h = buf.cpu().numpy()
+        n = B * T + B
+        length = h[B * T:n]
+        return (decode_classes(h[:B * T].reshape(B, T), length), [float(v) for v in h[n:n + B].view("float32")],
+                [max(int(v), 1) for v in length])
+
+    @torch.no_grad()
     def label_vecs(self, images_lr3):
         """super_resolution.py:165-169 on the native path: (B, 37, 1, T) softmax of the logits."""
         self._check_eval()

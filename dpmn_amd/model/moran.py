@@ -27,7 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from ..utils.labelmaps import moran_strings
+from ..utils.labelmaps import MORAN_ALPHABET, moran_strings
 from . import packing
 from .native import PackedEval, bilstm_stack
 
@@ -359,6 +359,20 @@ class NativeMORAN(PackedEval, MORAN):
         """Recognised strings of (B, >=3, H, W) images in [0, 1]: every stage on the current stream, then ONE device-to-host copy
         (the arg-max ids) and the cut at '$' on the host."""
         return moran_strings(self.pred_ids(images).cpu().numpy())
+
+    @torch.no_grad()
+    def read_conf(self, images):
+        """`read` with a confidence (ours; utils/confidence.py) -> (strings, scores, terms): the strings are `read`'s, from the same
+        forward pass; score = the sum of the log-softmax values of the arg-max ids up to and with the first '$' (dpmn_attn_conf_f32
+        on the decoder's logits), terms = the number of summed steps.  ONE device-to-host copy: the ids with the scores and terms
+        behind them."""
+        self._check_eval()
+        logits, ids = self._run(*self.prep(images), MAX_ITER)
+        B, steps = ids.shape
+        conf = ops.attn_confidence(logits, ids, MORAN_ALPHABET.index('$'))
+        h = torch.cat([ids.reshape(-1), conf]).cpu().numpy()
+        n = B * steps
+        return (moran_strings(h[:n].reshape(B, steps)), [float(v) for v in h[n:n + B].view("float32")], [int(v) for v in h[n + B:]])
 
     @torch.no_grad()
     def read_lexicon(self, images, lex):

@@ -1951,6 +1951,47 @@ def edit_read(strings, lex, device):
     return lex.strings(h[:B]), [int(d) for d in h[B:]]
 
 
+# ------------------------------------------------------------------------------ recogniser confidence (csrc/confidence.hip)
+def ctc_confidence(logits, B, T, n_class, buf):
+    """The CTC log-likelihood of every image's own greedy string (utils.confidence.ctc_score): logits rows b*T + t (B*T, ld >=
+    n_class; the padding columns are not read), buf = ctc_greedy's buffer made with extra >= B.  The float32 score bits go behind
+    the lengths, `buf[B*T + B:B*T + 2*B].view(torch.float32)` (returned), so that one copy of buf brings string and score."""
+    if logits.dim() != 2 or logits.shape[0] != B * T or logits.shape[1] < n_class:
+        raise _abi.DpmnError("ctc_confidence: logits rows (B*T, >= n_class) expected")
+    if not (torch.is_tensor(buf) and buf.device == logits.device and buf.dtype == torch.int32 and buf.is_contiguous()
+            and buf.dim() == 1 and buf.numel() >= B * T + 2 * B):
+        raise _abi.DpmnError("ctc_confidence: buf must be ops.ctc_greedy's int32 buffer with extra >= B")
+    n = B * T
+    check(lib.dpmn_ctc_conf_f32(dptr(logits), logits.shape[1], n_class, buf.data_ptr(), buf.data_ptr() + 4 * n,
+                                buf.data_ptr() + 4 * (n + B), B, T, stream()))
+    return buf[n + B:n + 2 * B].view(torch.float32)
+
+
+def attn_confidence(logits, ids, eos):
+    """A greedy attention decoder's score (utils.confidence.attn_score): logits (B, steps, n_class) float32, ids (B, steps) int32
+    -> one int32 buffer (2 B): the bits of the float32 scores (`buf[:B].view(torch.float32)`), then the terms."""
+    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3 and logits.is_contiguous()):
+        raise _abi.DpmnError("attn_confidence: contiguous float32 CUDA logits (B, steps, n_class) expected; there is no CPU fallback")
+    B, steps, n_class = logits.shape
+    if tuple(ids.shape) != (B, steps) or ids.device != logits.device:
+        raise _abi.DpmnError("attn_confidence: ids (B, steps) on the logits' device expected")
+    buf = torch.empty(2 * B, dtype=torch.int32, device=logits.device)
+    check(lib.dpmn_attn_conf_f32(dptr(logits), _i32(ids, "attn_confidence"), int(eos), buf.data_ptr(), buf.data_ptr() + 4 * B,
+                                 B, steps, n_class, stream()))
+    return buf
+
+
+def turn180(x):
+    """x (B, C, H, W) float32 turned by 180 degrees in every plane: bitwise x.flip(2, 3), as a new contiguous tensor."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0):
+        raise _abi.DpmnError("turn180: a non-empty float32 CUDA tensor (B, C, H, W) expected; there is no CPU fallback")
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    B, Cc, H, W = x.shape
+    check(lib.dpmn_turn180_f32(dptr(x), dptr(y), B, Cc, H, W, stream()))
+    return y
+
+
 # ------------------------------------------------------------------------------ native ASTER recogniser (csrc/aster.hip)
 def aster_prep(img, stn_h=32, stn_w=64):
     """parse_aster_data + the STN head's bilinear (align_corners=True) resize for a batch: (B, >=3, H, W) in [0, 1] ->

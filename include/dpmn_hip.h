@@ -414,6 +414,21 @@ size_t dpmn_edit_lexicon_workspace_bytes(int B, int L);
 int dpmn_edit_lexicon_i32(const unsigned char* strings, const unsigned char* words, int L, int* best_idx, int* best_dist, void* ws, int B,
                           dpmn_stream_t stream);
 
+/* ------------------------------------------------------------------ recogniser confidence (confidence.hip; utils/confidence.py is the
+ * NumPy restatement; main.py --demo_conf / --demo_upright / --demo_min_conf).  No call depends on the compute mode.
+ * ctc_conf:  rows b*T + t of logits (leading dimension ld >= n_class; columns >= n_class are never read), T <= 64, n_class <= 64,
+ *            and ctc_greedy's cls (B, T) / len (B) -> out_score (B): the CTC log-likelihood of each image's own collapsed string
+ *            (any length 0 .. T; 0 gives the sum of the blank log-probabilities).  A class outside 0 .. n_class - 1 is clamped.
+ * attn_conf: logits (B, steps, n_class), ids (B, steps), steps <= 128, n_class <= 128 -> out_score (B): the sum of
+ *            log_softmax(logits[b][t])[ids[b][t]] over t = 0 .. the first step with ids == eos (that step included; every step when
+ *            there is none), out_terms (B): the number of summed steps.
+ * turn180:   y (B, C, H, W) = x turned by 180 degrees in every plane (x[..., H - 1 - h, W - 1 - w]); y must not alias x. */
+int dpmn_ctc_conf_f32(const float* logits, int ld, int n_class, const int* cls, const int* len, float* out_score, int B, int T,
+                      dpmn_stream_t stream);
+int dpmn_attn_conf_f32(const float* logits, const int* ids, int eos, float* out_score, int* out_terms, int B, int steps, int n_class,
+                       dpmn_stream_t stream);
+int dpmn_turn180_f32(const float* x, float* y, int B, int C, int H, int W, dpmn_stream_t stream);
+
 /* ------------------------------------------------------------------ native ASTER recogniser (aster.hip; model/aster.py NativeASTER)
  * aster_prep:      parse_aster_data (x * 2 - 1, interfaces/base.py:441-450) + F.interpolate(x, (Hs, Ws), bilinear,
  *                  align_corners=True) (recognizer_builder.py:77): img (B, >=3, H, W) planes with batch stride img_stride (channels

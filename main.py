@@ -113,6 +113,35 @@ def demo_detect_setting(args):
     return gap, floor
 
 
+DEMO_CONF_NEEDS_DIR = ("main.py: --demo_conf, --demo_upright and --demo_min_conf need --demo_dir: the confidence is that of the reads of the "
+                       "images of that folder")
+DEMO_CONF_OR_TILE = "main.py: --demo_conf, --demo_upright and --demo_min_conf do not combine with --demo_tile: a window of a line is not a word"
+DEMO_MIN_CONF_NEEDS_BOXES = ("main.py: --demo_min_conf needs --demo_boxes or --demo_detect: it drops candidate regions of a photo by the "
+                             "confidence of their SR read")
+DEMO_MIN_CONF_RANGE = "main.py: --demo_min_conf must lie strictly between 0 and 1 (a confidence is a geometric-mean probability)"
+
+
+def demo_conf_setting(args):
+    """--demo_conf, --demo_upright, --demo_min_conf C, checked -> None without the three, else TextSR.demo's keywords
+    {confidence, upright, min_conf} (--demo_conf is implied by the other two).  ValueError (the message without its 'main.py: ') for
+    a flag without --demo_dir or with --demo_tile, --demo_min_conf without --demo_boxes / --demo_detect, or C outside (0, 1)."""
+    import math
+    upright, c = bool(getattr(args, "demo_upright", False)), getattr(args, "demo_min_conf", None)
+    if not (getattr(args, "demo_conf", False) or upright or c is not None):
+        return None
+    if not getattr(args, "demo_dir", None):
+        raise ValueError(DEMO_CONF_NEEDS_DIR[len("main.py: "):])
+    if getattr(args, "demo_tile", False):
+        raise ValueError(DEMO_CONF_OR_TILE[len("main.py: "):])
+    if c is not None:
+        if not (getattr(args, "demo_boxes", None) or getattr(args, "demo_detect", False)):
+            raise ValueError(DEMO_MIN_CONF_NEEDS_BOXES[len("main.py: "):])
+        c = float(c)
+        if not (math.isfinite(c) and 0.0 < c < 1.0):
+            raise ValueError(DEMO_MIN_CONF_RANGE[len("main.py: "):])
+    return {"confidence": True, "upright": upright, "min_conf": c}
+
+
 def paste_feather(args):
     """--demo_paste_feather as a float, checked; 1.0 when the flag is absent."""
     import math
@@ -288,6 +317,10 @@ def main(config, args):
         lex_words = rec_lexicon_setting(args)
     except ValueError as e:
         raise SystemExit("main.py: %s" % e)
+    try:
+        conf_kw = demo_conf_setting(args) or {}
+    except ValueError as e:
+        raise SystemExit("main.py: %s" % e)
     hr_dir = getattr(args, "train_hr_dir", None)
     if hr_dir and not os.path.isdir(hr_dir):
         raise SystemExit("main.py: --train_hr_dir %s is not a directory" % hr_dir)
@@ -318,6 +351,9 @@ def main(config, args):
         from dpmn_amd.ops import Lexicon
         lex_kw = {"lexicon": Lexicon(lex_words[0], mode=lex_words[1])}
         print("rec_lexicon: %d words, mode %s" % (len(lex_words[0]), lex_words[1]))
+    if conf_kw and not callable(getattr(rec, "read_conf", None)):
+        raise SystemExit("main.py: --demo_conf, --demo_upright and --demo_min_conf need a native recogniser (--rec crnn, aster or moran), "
+                         "and --rec %s built none with a confidence (see the line above)" % args.rec)
     if getattr(args, "demo_dir", None):
         # a folder of the user's own text crops -> one <stem>_sr.png per image and demo_result.csv (TextSR.demo); the trained models
         # are loaded as for --test
@@ -349,17 +385,21 @@ def main(config, args):
             if getattr(args, "demo_polygons", False):
                 # a line of more than 4 points is a curved word, straightened strip by strip (utils/poly.py)
                 make = functools.partial(make, polygons=True)
+            # (--demo_upright / --demo_min_conf write boxes_read/<stem>.txt from the corner lists, which come with photos=True)
+            with_photos = bool(conf_kw.get("upright") or conf_kw.get("min_conf") is not None)
             if getattr(args, "demo_paste", False):
                 # every photo enlarged and its SR regions pasted back into their quadrilaterals: <stem>_photo_sr.png (utils/paste.py)
                 batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device, photos=True)
                 # (--demo_paste_polygons: the polygons too, strip by strip, in box-file order with the quadrilaterals: utils/paste_poly.py)
                 rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, paste=True, feather=feather,
-                                    paste_polygons=bool(getattr(args, "demo_paste_polygons", False)), **lex_kw)
+                                    paste_polygons=bool(getattr(args, "demo_paste_polygons", False)), **lex_kw, **conf_kw)
             else:
-                batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device)
-                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, **lex_kw)
+                batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device, **({"photos": True} if with_photos else {}))
+                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, **lex_kw, **conf_kw)
             if lex_kw:
-                print("accuracy %s accuracy_lexicon %s over %d labelled regions" % tuple(lexicon_accuracies(rows)[i] for i in (1, 2, 0)))
+                # (with the confidence columns sr_string is column 5 and the lexicon's word follows sr_conf and turned)
+                lex_rows = [r[:4] + [r[5], r[7 + bool(conf_kw["upright"])]] for r in rows] if conf_kw else rows
+                print("accuracy %s accuracy_lexicon %s over %d labelled regions" % tuple(lexicon_accuracies(lex_rows)[i] for i in (1, 2, 0)))
             print("%d regions super-resolved into %s" % (len(rows), out_dir))
             return
         if getattr(args, "demo_tile", False):
@@ -368,7 +408,7 @@ def main(config, args):
             rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=True, chunk=bs)
         else:
             batches = folder_batches(args.demo_dir, bs, lr_size, mission.mask, mission.device)
-            rows = mission.demo(models, psn, batches, out_dir, rec=rec, **lex_kw)
+            rows = mission.demo(models, psn, batches, out_dir, rec=rec, **lex_kw, **conf_kw)
         print("%d images super-resolved into %s" % (len(rows), out_dir))
         return
     if args.test:
@@ -513,6 +553,17 @@ if __name__ == '__main__':
     parser.add_argument('--demo_paste_feather', type=float, default=1.0, metavar='F',
                         help='with --demo_paste: the width, in SR pixels, of the edge over which a pasted region is blended into the '
                              'photo (>= 0; 0 gives a hard edge)')
+    parser.add_argument('--demo_conf', action='store_true', default=False,
+                        help='with --demo_dir and a native recogniser (--rec crnn / aster / moran): demo_result.csv gains lr_conf and '
+                             'sr_conf, the geometric-mean symbol probability of each read (exp(score / terms), utils/confidence.py), at no '
+                             'extra forward pass; implied by --demo_upright and --demo_min_conf; not with --demo_tile')
+    parser.add_argument('--demo_upright', action='store_true', default=False,
+                        help='with --demo_dir: every LR image is read as it is and turned by 180 degrees, and goes through the model in '
+                             'the direction of the more confident read (column turned); with box files the regions are written in '
+                             'their reading order to <demo_out>/boxes_read/<stem>.txt; not with --demo_tile')
+    parser.add_argument('--demo_min_conf', type=float, default=None, metavar='C',
+                        help='with --demo_boxes or --demo_detect: a region whose SR read is empty or less confident than C (0 < C < 1) '
+                             'is dropped: no region file, not pasted, column kept = 0; not with --demo_tile')
     parser.add_argument('--demo_detect', action='store_true', default=False,
                         help='with --demo_dir and without box files: the folder holds whole photos whose text regions are found on the '
                              'GPU by a classical recipe (gradient of the luma, Otsu threshold, run-length smoothing, connected '
@@ -610,6 +661,10 @@ if __name__ == '__main__':
         parser.error(str(e))
     try:
         rec_lexicon_setting(args, load=False)
+    except ValueError as e:
+        parser.error(str(e))
+    try:
+        demo_conf_setting(args)
     except ValueError as e:
         parser.error(str(e))
     config_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config', 'super_resolution.yaml')
