@@ -339,7 +339,7 @@ class TextSR(base.TextBase):
 
     @torch.no_grad()
     def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None, boxes=False, paste=False,
-             feather=1.0, paste_polygons=False, lexicon=None, confidence=False, upright=False, min_conf=None):
+             feather=1.0, paste_polygons=False, lexicon=None, confidence=False, upright=False, min_conf=None, line_read=False, line_space=0):
         """Super-resolve someone's own images (ours; main.py --demo_dir): batches yields (names, images_lr) as
         dataset.folder.folder_batches does.  Per batch `refine` (label_vecs from the frozen CRNN for tatt / tpgsr, as in eval), then
         save_image's quantisation on the GPU (ops.quantize_sr_u8), ONE device-to-host copy and one <stem>_sr.png per input under
@@ -391,7 +391,17 @@ class TextSR(base.TextBase):
         chosen reading order, sr_string as the transcription -- a box file for a second run.  The corner lists come with the batches:
         they must then be made with photos=True, whether paste is set or not.
         The columns, in order: file, [box, label,] lr_string, lr_conf, sr_string, sr_conf, [turned,] [sr_lexicon, sr_lexicon_score,]
-        [kept]; the lexicon's read of the SR image stays a second call through read_lexicon.  Without the three nothing changes."""
+        [kept]; the lexicon's read of the SR image stays a second call through read_lexicon.  Without the three nothing changes.
+        line_read (ours; main.py --demo_line_read; utils/line_read.py; needs tile=True and a CTC recogniser with window_rows and
+        read_lines -- NativeCRNN; ASTER and MORAN have no frame posteriors): lr_string / sr_string are ONE read of the whole line per
+        side, with no '|': the frame posteriors of the line's windows are kept on the device chunk by chunk, blended along the line
+        with the pixel stitch's ramp in the log domain, decoded once and scored once (three launches and one device-to-host copy
+        per side and batch; the recogniser runs as often as without the flag).  An image of one window gets `read`'s string.  The
+        blend cannot repair a glyph that both windows see cut, and the string is over the CRNN's 36 symbols.  line_space N (0 ..
+        64): a space goes where at least N line frames lie between two symbols' arg-max runs -- a heuristic on the blank runs, the
+        CRNN has no space class; 0 inserts none.  With line_read, confidence=True combines with tile: lr_conf / sr_conf are
+        exp(score / terms) of the line's CTC likelihood; upright, min_conf and a lexicon stay refused with tile.  The <stem>_sr.png
+        files do not change."""
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
         if lexicon is not None and tile:
@@ -399,7 +409,10 @@ class TextSR(base.TextBase):
         if lexicon is not None and reader is None:
             raise ValueError("demo: a lexicon needs a recogniser")
         lex_reader = self._lexicon_reader(rec, reader, lexicon)
-        conf_reader = self._conf_reader(rec, tile, boxes, confidence, upright, min_conf)
+        line_kw = self._line_reader(rec, tile, line_read, line_space)
+        # (with line_read the confidence columns are the lines' own: no read_conf, and nothing else of the three combines with tile)
+        conf_reader = self._conf_reader(rec, tile, boxes, confidence and not line_kw, upright, min_conf)
+        line_conf = bool(line_kw) and bool(confidence)
         for m in model_list:
             m.eval()
         fn = text_prior_fn or self.default_text_prior()
@@ -414,7 +427,7 @@ class TextSR(base.TextBase):
             conf_kw = {} if conf_reader is None else dict(conf_reader=conf_reader, upright=bool(upright), min_conf=min_conf, out_dir=out_dir)
             for names, pixels, preds_lr, preds_sr, photos, *lex in self._demo_regions(model_list, model_psn, batches, fn, reader, chunk, tile, labels,
                                                                                        float(feather) if paste else None, bool(paste_polygons),
-                                                                                       lex_reader, **conf_kw):
+                                                                                       lex_reader, **conf_kw, **self._line_kw(line_kw, line_conf)):
                 if conf_reader is not None:      # lex = [the lexicon's item or None, (lr_conf, sr_conf, turned or None), kept or None]
                     self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken, lex[0], conf=lex[1], kept=lex[2])
                 else:
@@ -425,8 +438,8 @@ class TextSR(base.TextBase):
             rows = [r[0][:-4].rsplit("_", 1) + [label] + r[1:] for r, label in zip(rows, labels)]      # (+ the lexicon's two columns)
             batches = ()
         elif tile:
-            for names, pixels, preds_lr, preds_sr, _ in self._demo_windows(model_list, model_psn, batches, fn, reader, chunk):
-                self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken)
+            for names, pixels, preds_lr, preds_sr, _, conf in self._demo_windows(model_list, model_psn, batches, fn, reader, chunk, line_kw):
+                self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, conf=conf + (None,) if line_conf else None)
             batches = ()
         for names, images_lr in batches:
             n = len(names)
@@ -454,13 +467,36 @@ class TextSR(base.TextBase):
         with open(os.path.join(out_dir, "demo_result.csv"), "w", newline="") as out:
             w = csv.writer(out)
             head = ["file", "box", "label"] if boxes else ["file"]
-            if conf_reader is None:
+            if conf_reader is None and not line_conf:
                 head += ["lr_string", "sr_string"]
             else:
                 head += ["lr_string", "lr_conf", "sr_string", "sr_conf"] + (["turned"] if upright else [])
             w.writerow(head + (["sr_lexicon", "sr_lexicon_score"] if lexicon is not None else []) + (["kept"] if min_conf is not None else []))
             w.writerows(rows)
         return rows
+
+    @staticmethod
+    def _line_reader(rec, tile, line_read, line_space):
+        """demo: None without line_read, else _demo_windows' line_kw {rec, gap}.  ValueError of one line for line_read without tile or
+        with a recogniser that has no frame posteriors, and for a line_space outside 0 .. 64 or without line_read."""
+        gap = int(line_space or 0)
+        if not line_read:
+            if gap:
+                raise ValueError("demo: line_space needs line_read=True (the spaces go into the one read of a tiled line)")
+            return None
+        if not tile:
+            raise ValueError("demo: line_read needs tile=True (it reads a line that was super-resolved in overlapping windows as one string)")
+        if not (callable(getattr(rec, "window_rows", None)) and callable(getattr(rec, "read_lines", None))):
+            raise ValueError("demo: line_read needs a CTC recogniser with window_rows and read_lines (NativeCRNN, --rec crnn); ASTER and "
+                             "MORAN have no frame posteriors to blend along a line")
+        if not 0 <= gap <= 64:
+            raise ValueError("demo: line_space must be 0 .. 64 line frames, got %r" % (line_space,))
+        return {"rec": rec, "gap": gap}
+
+    @staticmethod
+    def _line_kw(line_kw, line_conf):
+        """demo(boxes=True): _demo_regions' keywords for a line read; none without one."""
+        return {"line_kw": line_kw, "line_conf": line_conf} if line_kw else {}
 
     @staticmethod
     def _conf_reader(rec, tile, boxes, confidence, upright, min_conf):
@@ -523,7 +559,7 @@ class TextSR(base.TextBase):
                         + extra + ([str(int(bool(kept[i])))] if kept is not None else []))
 
     def _demo_regions(self, model_list, model_psn, batches, fn, reader, chunk, tile, labels_out, feather=None, paste_polygons=False,
-                      lex_reader=None, conf_reader=None, upright=False, min_conf=None, out_dir=None):
+                      lex_reader=None, conf_reader=None, upright=False, min_conf=None, out_dir=None, line_kw=None, line_conf=False):
         """demo(boxes=True): per batch of regions -> (names, one (H, W_r, 3) uint8 array per region, the LR reads, the SR reads, the
         pasted photos); the regions' labels are appended to labels_out.  tile: the batches carry a plan and go through _demo_windows.
         feather: None, or demo(paste=True)'s -- the batches then end with the photos item and the pasted photos are _demo_paste's list
@@ -543,9 +579,12 @@ class TextSR(base.TextBase):
                     labels_out.extend(labels)
                     held[:] = photos
                     yield names, plan, images_lr
-            for names, pixels, preds_lr, preds_sr, device in self._demo_windows(model_list, model_psn, windows(), fn, reader, chunk):
-                yield names, pixels, preds_lr, preds_sr, (self._demo_paste(names, held[0], device[0], device[1], feather, paste_polygons)
-                                                            if paste else [])
+            for names, pixels, preds_lr, preds_sr, device, conf in self._demo_windows(model_list, model_psn, windows(), fn, reader, chunk, line_kw):
+                pasted = self._demo_paste(names, held[0], device[0], device[1], feather, paste_polygons) if paste else []
+                if line_conf:      # (demo(line_read=True, confidence=True): no lexicon item, the lines' conf values, nothing turned)
+                    yield names, pixels, preds_lr, preds_sr, pasted, None, conf + (None,)
+                else:
+                    yield names, pixels, preds_lr, preds_sr, pasted
             return
         chunk = max(int(chunk if chunk is not None else self.batch_size), 1)
         for names, labels, images_lr, *photos in batches:
@@ -670,15 +709,20 @@ class TextSR(base.TextBase):
             out.append((stem, ops.paste_mixed_u8(photo2, sr_packed, sr_meta, regions).cpu().numpy()))
         return out
 
-    def _demo_windows(self, model_list, model_psn, batches, fn, reader, chunk):
+    def _demo_windows(self, model_list, model_psn, batches, fn, reader, chunk, line_kw=None):
         """demo(tile=True): per batch (names, plan, images_lr) of windows -> (names, one (H, W_b, 3) uint8 array per image, the LR
-        reads, the SR reads, (packed, meta)), the reads of an image's windows joined with '|'; packed / meta: the stitched lines as
-        ops.stitch_windows_u8 returns them, still on the device."""
+        reads, the SR reads, (packed, meta), None), the reads of an image's windows joined with '|'; packed / meta: the stitched lines
+        as ops.stitch_windows_u8 returns them, still on the device.
+        line_kw (demo's line_read: {rec, gap}): instead of reading every window, rec.window_rows keeps the frame logits of the LR and
+        of the SR windows of every chunk on the device -- a line's windows may span chunks -- and rec.read_lines reads every line
+        once per side; the reads are the lines' strings and the last item is (lr conf values, sr conf values)."""
+        from ..utils.confidence import confidence as conf_of
         chunk = max(int(chunk if chunk is not None else self.batch_size), 1)
         for names, plan, images_lr in batches:
             images_lr = images_lr.to(self.device)
             T = images_lr.shape[0]
             srs, reads_lr, reads_sr = [], [], []
+            rows_lr, rows_sr = [], []
             for lo in range(0, T, chunk):
                 x = images_lr[lo:lo + chunk]
                 n = x.shape[0]
@@ -687,18 +731,26 @@ class TextSR(base.TextBase):
                 label_vecs = self.label_vecs_from_crnn(x) if self.args.arch in ('tatt', 'tpgsr') else None
                 sr = self.refine(model_list, model_psn, x, label_vecs, fn)[:n]
                 srs.append(sr)
-                if reader is not None:
+                if line_kw:
+                    rows_lr.append(line_kw["rec"].window_rows(x[:n, :3])[0])
+                    rows_sr.append(line_kw["rec"].window_rows(sr[:, :3])[0])
+                elif reader is not None:
                     reads_lr += [str(s) for s in reader(x[:n, :3])]
                     reads_sr += [str(s) for s in reader(sr[:, :3])]
             packed, meta = ops.stitch_windows_u8(srs[0] if len(srs) == 1 else torch.cat(srs, 0), plan, scale=self.scale_factor)
             flat = packed.cpu().numpy()
             pixels = [flat[off:off + h * w * 3].reshape(h, w, 3) for off, h, w in meta]
+            if line_kw:
+                lr_w = images_lr.shape[3]
+                side = [line_kw["rec"].read_lines(r[0] if len(r) == 1 else torch.cat(r, 0), plan, line_kw["gap"], lr_w)[:3] for r in (rows_lr, rows_sr)]
+                yield names, pixels, side[0][0], side[1][0], (packed, meta), (conf_of(*side[0][1:]), conf_of(*side[1][1:]))
+                continue
             preds_lr, preds_sr = [[] for _ in names], [[] for _ in names]
             if reader is not None:
                 for (b, _), s_lr, s_sr in zip(plan, reads_lr, reads_sr):
                     preds_lr[b].append(s_lr)
                     preds_sr[b].append(s_sr)
-            yield names, pixels, ['|'.join(p) for p in preds_lr], ['|'.join(p) for p in preds_sr], (packed, meta)
+            yield names, pixels, ['|'.join(p) for p in preds_lr], ['|'.join(p) for p in preds_sr], (packed, meta), None
 
     # ------------------------------------------------------------------ training (super_resolution.py:113-278)
     def build_training(self, world_size=1, group=None):

@@ -199,6 +199,37 @@ class NativeCRNN(PackedEval, CRNN):
                 [max(int(v), 1) for v in length])
 
     @torch.no_grad()
+    def window_rows(self, images):
+        """The frame logits of (B, >=3, H, W) images, the windows of tiled lines -> (rows (B*T, 40), B, T): `read`'s stages up to the
+        decode, everything still on the device.  The rows of several calls, concatenated in plan order, are read_lines' input."""
+        self._check_eval()
+        return self.logits_rows(self.prep(images), self._packs())
+
+    @torch.no_grad()
+    def read_lines(self, rows, plan, gap=0, lr_w=64):
+        """One read per tiled line (ours; utils/line_read.py): rows = window_rows' logits of the windows of `plan` (utils/tile.py: an
+        (image, x0) per window, lr_w columns wide) -> (strings, scores, terms, spans), one entry per image: the windows' frame
+        posteriors blended along the line (dpmn_line_stitch_f32), decoded once (dpmn_line_greedy_i32) and scored once
+        (dpmn_line_ctc_f32: the CTC log-likelihood of the line's own string, terms = max(its symbols, 1)) -- three launches and ONE
+        device-to-host copy.  spans: per symbol the (first, last) line frame of its arg-max run.  gap >= 1: a space goes into the
+        string where at least `gap` line frames lie between two symbols' runs (utils.line_read.insert_spaces, a heuristic: the CRNN
+        has no space class; scores, terms and spans are those of the symbols).  An image of one window gives `read`'s string."""
+        from ..utils.line_read import SPACE, insert_spaces
+        if not len(plan) or rows.shape[0] % len(plan):
+            raise ValueError("dpmn_amd NativeCRNN.read_lines: %d logits rows do not divide into the plan's %d windows" % (rows.shape[0], len(plan)))
+        line_lp, lines = ops.line_stitch(rows, rows.shape[0] // len(plan), self.nclass, plan, lr_w)
+        B, N = len(lines), lines.frames
+        buf = ops.line_greedy(line_lp, lines, extra=B)[0]
+        ops.line_ctc_confidence(line_lp, lines, buf)
+        h = buf.cpu().numpy()
+        length = h[3 * N:3 * N + B]
+        strings, spans = [], []
+        for (f0, _), n in zip(lines, length.tolist()):
+            spans.append(list(zip(h[N + f0:N + f0 + n].tolist(), h[2 * N + f0:2 * N + f0 + n].tolist())))
+            strings.append("".join(" " if c == SPACE else ALPHABET[c - 1] for c in insert_spaces(h[f0:f0 + n].tolist(), spans[-1], gap)))
+        return strings, [float(v) for v in h[3 * N + B:3 * N + 2 * B].view("float32")], [max(int(n), 1) for n in length], spans
+
+    @torch.no_grad()
     def label_vecs(self, images_lr3):
         """super_resolution.py:165-169 on the native path: (B, 37, 1, T) softmax of the logits."""
         self._check_eval()

@@ -1992,6 +1992,109 @@ def turn180(x):
     return y
 
 
+# ------------------------------------------------------------------------------ one read per tiled line (csrc/line_read.hip)
+class LineTable:
+    """The lines of a ragged batch of line posteriors (utils/line_read.py): `host`, an int32 (B, 2) array of [first row of line_lp, L]
+    per image -- the lines back to back from row 0, every L >= 1 -- `frames` = the sum of the L and `max_L`.  Iterating gives
+    (first row, L) tuples.  The table is uploaded once per device and kept for the launches that read it."""
+
+    def __init__(self, table):
+        import numpy as np
+        host = np.ascontiguousarray(np.asarray(table, np.int64).reshape(-1, 2))
+        if not len(host) or (host[:, 1] < 1).any() or host[0, 0] != 0 or (host[1:, 0] != np.cumsum(host[:-1, 1])).any():
+            raise _abi.DpmnError("LineTable: (first row, L >= 1) per line expected, the lines back to back from row 0")
+        if host.sum(1).max() > 2 ** 31 - 1:
+            raise _abi.DpmnError("LineTable: the batch has more rows than an int32 counts")
+        self.host = host.astype(np.int32)
+        self.frames, self.max_L = int(host[:, 1].sum()), int(host[:, 1].max())
+        self._dev = {}
+
+    def __len__(self):
+        return len(self.host)
+
+    def __iter__(self):
+        return iter([(int(f), int(n)) for f, n in self.host])
+
+    def __array__(self, dtype=None, copy=None):
+        return self.host if dtype is None else self.host.astype(dtype)
+
+    def device_ptr(self, device):
+        """The device pointer of the table on `device` (uploaded on first use)."""
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        if key not in self._dev:
+            self._dev[key] = _upload(torch.device("cuda", key), self.host)
+        return self._dev[key][1]
+
+
+def _line_lp(line_lp, lines, what):
+    """The checks the two ops on line posteriors share -> (the LineTable, n_class)."""
+    if not isinstance(lines, LineTable):
+        lines = LineTable(lines)
+    if not (torch.is_tensor(line_lp) and line_lp.is_cuda and line_lp.dtype == torch.float32 and line_lp.dim() == 2
+            and line_lp.is_contiguous() and line_lp.shape[0] == lines.frames and line_lp.shape[1] >= 1):
+        raise _abi.DpmnError("%s: contiguous float32 CUDA line posteriors (%d, n_class) expected, one row per frame of the table; there "
+                             "is no CPU fallback" % (what, lines.frames))
+    return lines, line_lp.shape[1]
+
+
+def line_stitch(rows, T, n_class, plan, lr_w):
+    """The frame posteriors of the windows of a tile plan blended into one posterior per LINE frame (utils.line_read.stitch_lp_np):
+    rows (windows * T, ld >= n_class) logits, row w*T + t (NativeCRNN.window_rows' layout; the padding columns are not read), plan the
+    windows' (image, x0) (utils/tile.py), lr_w the window width in columns -> (line_lp, lines): the float32 (sum L_b, n_class)
+    log-posteriors of every image's line, back to back, and their LineTable."""
+    import numpy as np
+    from .utils.line_read import covered_lines
+    T, n_class, lr_w = int(T), int(n_class), int(lr_w)
+    if not (torch.is_tensor(rows) and rows.is_cuda):
+        raise _abi.DpmnError("line_stitch: the windows' logits are blended on the GPU (got a %s tensor); there is no CPU fallback"
+                             % (rows.device if torch.is_tensor(rows) else type(rows).__name__))
+    if rows.dim() != 2 or T < 2 or lr_w < 2 or n_class < 1 or not len(plan) or rows.shape[0] != len(plan) * T or rows.shape[1] < n_class:
+        raise _abi.DpmnError("line_stitch: logits rows (windows * T, >= n_class) with T >= 2 and a plan of as many windows expected, got "
+                             "%s, T %d, %d classes, %d windows" % (tuple(rows.shape), T, n_class, len(plan)))
+    try:
+        per_line = covered_lines(plan, lr_w)
+    except ValueError as e:
+        raise _abi.DpmnError("line_stitch: %s" % e) from e
+    L = [(w_line * (T - 1)) // lr_w + 1 for _, _, w_line in per_line]
+    lines = LineTable(np.stack([np.concatenate(([0], np.cumsum(L[:-1]))), L], 1))
+    d, d_lines, d_wins, d_x0 = _upload(rows.device, lines.host, np.array([l[:2] for l in per_line], np.int32),
+                                       np.ascontiguousarray(np.asarray(plan, np.int32).reshape(-1, 2)[:, 1]))
+    lines._dev[d.device.index] = (d, d_lines)
+    line_lp = torch.empty(lines.frames, n_class, device=rows.device)
+    check(lib.dpmn_line_stitch_f32(dptr(rows), rows.shape[1], n_class, T, lr_w, d_lines, d_wins, d_x0, len(lines), lines.max_L,
+                                   dptr(line_lp), stream()))
+    return line_lp, lines
+
+
+def line_greedy(line_lp, lines, extra=0):
+    """The greedy CTC decode of every line (utils.line_read.greedy_np): line_lp (N = sum L_b, n_class), lines its LineTable (or a host
+    (B, 2) table) -> one int32 buffer (3 N + B + extra): cls (N), start (N), end (N), length (B).  A line's entries stand at its first
+    row: the collapsed classes, then per kept symbol the first and the last line frame of its arg-max run, zero behind the length.
+    Returned as (buffer, cls, start, end, length) views, so that the host reads everything with one copy; extra as for ctc_greedy."""
+    lines, n_class = _line_lp(line_lp, lines, "line_greedy")
+    N, B = lines.frames, len(lines)
+    buf = torch.empty(3 * N + B + int(extra), dtype=torch.int32, device=line_lp.device)
+    p = buf.data_ptr()
+    check(lib.dpmn_line_greedy_i32(dptr(line_lp), n_class, lines.device_ptr(line_lp.device), B, lines.max_L, p, p + 4 * N, p + 8 * N,
+                                   p + 12 * N, stream()))
+    return buf, buf[:N], buf[N:2 * N], buf[2 * N:3 * N], buf[3 * N:3 * N + B]
+
+
+def line_ctc_confidence(line_lp, lines, buf):
+    """The CTC log-likelihood of every line's own greedy string (utils.line_read.line_score_np): buf = line_greedy's buffer made with
+    extra >= B.  The float32 score bits go behind the lengths, `buf[3 N + B:3 N + 2 B].view(torch.float32)` (returned), as
+    ctc_confidence writes them."""
+    lines, n_class = _line_lp(line_lp, lines, "line_ctc_confidence")
+    N, B = lines.frames, len(lines)
+    if not (torch.is_tensor(buf) and buf.device == line_lp.device and buf.dtype == torch.int32 and buf.is_contiguous()
+            and buf.dim() == 1 and buf.numel() >= 3 * N + 2 * B):
+        raise _abi.DpmnError("line_ctc_confidence: buf must be ops.line_greedy's int32 buffer with extra >= B")
+    p = buf.data_ptr()
+    check(lib.dpmn_line_ctc_f32(dptr(line_lp), n_class, lines.device_ptr(line_lp.device), p, p + 12 * N, p + 4 * (3 * N + B), B,
+                                lines.max_L, stream()))
+    return buf[3 * N + B:3 * N + 2 * B].view(torch.float32)
+
+
 # ------------------------------------------------------------------------------ native ASTER recogniser (csrc/aster.hip)
 def aster_prep(img, stn_h=32, stn_w=64):
     """parse_aster_data + the STN head's bilinear (align_corners=True) resize for a batch: (B, >=3, H, W) in [0, 1] ->

@@ -57,16 +57,21 @@ def ctc_word_score(lp, word):
     a[0] = lp[0, 0]
     if S > 1:
         a[1] = lp[0, ext[1]]
+    # every state of a frame at once (a tiled line has thousands of states): per state the terms a[s], a[s - 1] and, over a blank
+    # between different labels, a[s - 2], summed in this order as _lse sums them; an absent term is -inf and adds exactly 0
+    ext = np.array(ext, np.int64)
+    skip = np.zeros(S, bool)
+    skip[2:] = (ext[2:] != 0) & (ext[2:] != ext[:-2])
     for t in range(1, T):
-        new = np.full(S, -np.inf)
-        for s in range(S):
-            terms = [a[s]]
-            if s >= 1:
-                terms.append(a[s - 1])
-            if s >= 2 and ext[s] != 0 and ext[s] != ext[s - 2]:
-                terms.append(a[s - 2])
-            new[s] = _lse(terms) + lp[t, ext[s]]
-        a = new
+        p1, p2 = np.full(S, -np.inf), np.full(S, -np.inf)
+        p1[1:] = a[:-1]
+        p2[2:] = np.where(skip[2:], a[:-2], -np.inf)
+        m = np.maximum(np.maximum(a, p1), p2)
+        live = ~np.isneginf(m)
+        ms = np.where(live, m, 0.0)
+        with np.errstate(divide="ignore"):      # (a dead state: log(0), replaced by -inf)
+            new = np.where(live, ms + np.log((np.exp(a - ms) + np.exp(p1 - ms)) + np.exp(p2 - ms)), -np.inf)
+        a = new + lp[t, ext]
     return _lse([a[S - 1]] + ([a[S - 2]] if S > 1 else []))
 
 

@@ -429,6 +429,26 @@ int dpmn_attn_conf_f32(const float* logits, const int* ids, int eos, float* out_
                        dpmn_stream_t stream);
 int dpmn_turn180_f32(const float* x, float* y, int B, int C, int H, int W, dpmn_stream_t stream);
 
+/* ------------------------------------------------------------------ one read per tiled text line (line_read.hip; utils/line_read.py is
+ * the NumPy restatement and the definition; main.py --demo_line_read).  No call depends on the compute mode.  Device tables: lines (B, 2)
+ * int32 [first row of line_lp, L] per line, the lines back to back; wins (B, 2) [first window, windows]; x0: every window's first column
+ * (not decreasing within a line).  max_L: the largest L of the table.  Limits: 2 <= T <= 64 frames per window, n_class <= 64,
+ * max_L <= 3201, 2 <= lr_w <= 8192, B <= 65535.
+ * line_stitch: rows w*T + t of the windows' logits (leading dimension ld >= n_class; columns >= n_class are never read) -> line_lp
+ *              (sum L, n_class): per line frame the windows' log-softmax rows, interpolated and blended in fp64 in the log domain with
+ *              the pixel stitch's ramp, renormalised, rounded to fp32 once.
+ * line_greedy: line_lp -> cls / start / end (sum L each, a line's entries at its first row) and length (B): the arg-max classes (first
+ *              maximum) with repeats collapsed and blank 0 dropped, and the first and last line frame of every kept symbol's arg-max
+ *              run; zero behind the length.
+ * line_ctc:    line_lp and line_greedy's cls / length -> out_score (B): the CTC log-likelihood of each line's own string (any length
+ *              0 .. L, up to 6403 states).  A class outside 0 .. n_class - 1 is clamped. */
+int dpmn_line_stitch_f32(const float* logits, int ld, int n_class, int T, int lr_w, const int* lines, const int* wins, const int* x0,
+                         int B, int max_L, float* line_lp, dpmn_stream_t stream);
+int dpmn_line_greedy_i32(const float* line_lp, int n_class, const int* lines, int B, int max_L, int* cls, int* start, int* end,
+                         int* length, dpmn_stream_t stream);
+int dpmn_line_ctc_f32(const float* line_lp, int n_class, const int* lines, const int* cls, const int* length, float* out_score, int B,
+                      int max_L, dpmn_stream_t stream);
+
 /* ------------------------------------------------------------------ native ASTER recogniser (aster.hip; model/aster.py NativeASTER)
  * aster_prep:      parse_aster_data (x * 2 - 1, interfaces/base.py:441-450) + F.interpolate(x, (Hs, Ws), bilinear,
  *                  align_corners=True) (recognizer_builder.py:77): img (B, >=3, H, W) planes with batch stride img_stride (channels

@@ -8,7 +8,8 @@ HIP-backed modules.  `--rec crnn` loads the native CRNN recogniser (config TRAIN
 batches of the real shapes -- `--synthetic_steps` of them -- and the text priors come from `TextSR.synthetic_text_prior()`;
 everything between the loader and the optimizer step is the real path.  `--demo_dir DIR --resume CKPT` super-resolves a folder of images
 (any sizes; resized on the GPU) into `--demo_out`; with `--demo_tile` a wide image keeps its aspect ratio and goes through the model in
-overlapping windows; with `--demo_boxes BOXDIR` the folder holds whole photos and BOXDIR one text file of quadrilaterals per photo, each
+overlapping windows (`--demo_line_read` with `--rec crnn`: its text is then ONE read of the line, not the windows' reads joined with
+`|`); with `--demo_boxes BOXDIR` the folder holds whole photos and BOXDIR one text file of quadrilaterals per photo, each
 rectified on the GPU and super-resolved as a crop of its own; with `--demo_paste` on top every photo is also enlarged by the scale factor on
 the GPU, its SR regions are warped back into their quadrilaterals and blended in (`--demo_paste_feather F`: the width of the blended edge
 in SR pixels, 0 for a hard edge), and written as `<stem>_photo_sr.png`; with `--demo_polygons` a line of a box file may also name a curved
@@ -131,7 +132,8 @@ def demo_conf_setting(args):
         return None
     if not getattr(args, "demo_dir", None):
         raise ValueError(DEMO_CONF_NEEDS_DIR[len("main.py: "):])
-    if getattr(args, "demo_tile", False):
+    # (--demo_line_read gives a tiled line one read and one score: --demo_conf then combines with --demo_tile, the other two do not)
+    if getattr(args, "demo_tile", False) and (upright or c is not None or not getattr(args, "demo_line_read", False)):
         raise ValueError(DEMO_CONF_OR_TILE[len("main.py: "):])
     if c is not None:
         if not (getattr(args, "demo_boxes", None) or getattr(args, "demo_detect", False)):
@@ -140,6 +142,33 @@ def demo_conf_setting(args):
         if not (math.isfinite(c) and 0.0 < c < 1.0):
             raise ValueError(DEMO_MIN_CONF_RANGE[len("main.py: "):])
     return {"confidence": True, "upright": upright, "min_conf": c}
+
+
+DEMO_LINE_READ_NEEDS_TILE = ("main.py: --demo_line_read needs --demo_dir and --demo_tile: it reads a line that was super-resolved in overlapping "
+                             "windows as one string")
+DEMO_LINE_READ_NEEDS_CRNN = ("main.py: --demo_line_read needs --rec crnn: the frame posteriors of the CRNN are blended along the line; ASTER "
+                             "and MORAN have none")
+DEMO_LINE_SPACE_NEEDS = "main.py: --demo_line_space needs --demo_line_read: the spaces go into the one read of a tiled line"
+DEMO_LINE_SPACE_RANGE = "main.py: --demo_line_space must be an integer 0 .. 64 (the blank line frames between two symbols that make a space; 0: none)"
+
+
+def demo_line_setting(args):
+    """--demo_line_read [--demo_line_space N], checked -> None without the flag, else TextSR.demo's keywords {line_read, line_space}.
+    ValueError (the message without its 'main.py: ') for the flag without --demo_dir and --demo_tile or with a recogniser that is not
+    the CRNN, and for N without the flag or outside 0 .. 64."""
+    n = getattr(args, "demo_line_space", None)
+    n = 0 if n is None else n
+    if not getattr(args, "demo_line_read", False):
+        if n:
+            raise ValueError(DEMO_LINE_SPACE_NEEDS[len("main.py: "):])
+        return None
+    if not (getattr(args, "demo_dir", None) and getattr(args, "demo_tile", False)):
+        raise ValueError(DEMO_LINE_READ_NEEDS_TILE[len("main.py: "):])
+    if getattr(args, "rec", None) != "crnn":
+        raise ValueError(DEMO_LINE_READ_NEEDS_CRNN[len("main.py: "):])
+    if isinstance(n, bool) or n != int(n) or not 0 <= int(n) <= 64:
+        raise ValueError(DEMO_LINE_SPACE_RANGE[len("main.py: "):])
+    return {"line_read": True, "line_space": int(n)}
 
 
 def paste_feather(args):
@@ -319,6 +348,7 @@ def main(config, args):
         raise SystemExit("main.py: %s" % e)
     try:
         conf_kw = demo_conf_setting(args) or {}
+        line_kw = demo_line_setting(args) or {}
     except ValueError as e:
         raise SystemExit("main.py: %s" % e)
     hr_dir = getattr(args, "train_hr_dir", None)
@@ -351,6 +381,8 @@ def main(config, args):
         from dpmn_amd.ops import Lexicon
         lex_kw = {"lexicon": Lexicon(lex_words[0], mode=lex_words[1])}
         print("rec_lexicon: %d words, mode %s" % (len(lex_words[0]), lex_words[1]))
+    if line_kw and not callable(getattr(rec, "read_lines", None)):
+        raise SystemExit("main.py: --demo_line_read needs the native CRNN, and --rec %s built none (see the line above)" % args.rec)
     if conf_kw and not callable(getattr(rec, "read_conf", None)):
         raise SystemExit("main.py: --demo_conf, --demo_upright and --demo_min_conf need a native recogniser (--rec crnn, aster or moran), "
                          "and --rec %s built none with a confidence (see the line above)" % args.rec)
@@ -392,10 +424,10 @@ def main(config, args):
                 batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device, photos=True)
                 # (--demo_paste_polygons: the polygons too, strip by strip, in box-file order with the quadrilaterals: utils/paste_poly.py)
                 rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, paste=True, feather=feather,
-                                    paste_polygons=bool(getattr(args, "demo_paste_polygons", False)), **lex_kw, **conf_kw)
+                                    paste_polygons=bool(getattr(args, "demo_paste_polygons", False)), **lex_kw, **conf_kw, **line_kw)
             else:
                 batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device, **({"photos": True} if with_photos else {}))
-                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, **lex_kw, **conf_kw)
+                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, **lex_kw, **conf_kw, **line_kw)
             if lex_kw:
                 # (with the confidence columns sr_string is column 5 and the lexicon's word follows sr_conf and turned)
                 lex_rows = [r[:4] + [r[5], r[7 + bool(conf_kw["upright"])]] for r in rows] if conf_kw else rows
@@ -405,7 +437,8 @@ def main(config, args):
         if getattr(args, "demo_tile", False):
             # wide images keep their aspect ratio: overlapping LR windows per image, one stitched <stem>_sr.png (utils/tile.py)
             batches = folder_window_batches(args.demo_dir, bs, lr_size, mission.mask, mission.device)
-            rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=True, chunk=bs)
+            # (--demo_line_read: one read per line instead of the windows' reads joined with '|'; with it --demo_conf combines)
+            rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=True, chunk=bs, **conf_kw, **line_kw)
         else:
             batches = folder_batches(args.demo_dir, bs, lr_size, mission.mask, mission.device)
             rows = mission.demo(models, psn, batches, out_dir, rec=rec, **lex_kw, **conf_kw)
@@ -564,6 +597,14 @@ if __name__ == '__main__':
     parser.add_argument('--demo_min_conf', type=float, default=None, metavar='C',
                         help='with --demo_boxes or --demo_detect: a region whose SR read is empty or less confident than C (0 < C < 1) '
                              'is dropped: no region file, not pasted, column kept = 0; not with --demo_tile')
+    parser.add_argument('--demo_line_read', action='store_true', default=False,
+                        help='with --demo_tile and --rec crnn: lr_string / sr_string are ONE read of the whole line instead of the '
+                             "windows' reads joined with '|': the CRNN's frame posteriors of the overlapping windows are blended along "
+                             'the line, decoded once and scored once (utils/line_read.py), at no extra recogniser pass; --demo_conf then '
+                             'combines with --demo_tile.  The string is over the 36 symbols of the CRNN')
+    parser.add_argument('--demo_line_space', type=int, default=0, metavar='N',
+                        help='with --demo_line_read: a space goes where at least N (0 .. 64) line frames lie between two symbols; a '
+                             'heuristic on the blank runs, the CRNN has no space class; 0 (default) inserts none')
     parser.add_argument('--demo_detect', action='store_true', default=False,
                         help='with --demo_dir and without box files: the folder holds whole photos whose text regions are found on the '
                              'GPU by a classical recipe (gradient of the luma, Otsu threshold, run-length smoothing, connected '
@@ -665,6 +706,7 @@ if __name__ == '__main__':
         parser.error(str(e))
     try:
         demo_conf_setting(args)
+        demo_line_setting(args)
     except ValueError as e:
         parser.error(str(e))
     config_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config', 'super_resolution.yaml')
