@@ -274,6 +274,10 @@ SIGNATURES = {
     "dpmn_line_stitch_f32": (_i, [fp, _i, _i, _i, _i, fp, fp, fp, _i, _i, fp, fp]),
     "dpmn_line_greedy_i32": (_i, [fp, _i, fp, _i, _i, fp, fp, fp, fp, fp]),
     "dpmn_line_ctc_f32": (_i, [fp, _i, fp, fp, fp, fp, _i, _i, fp]),
+    "dpmn_line_words_block": (_i, []),
+    "dpmn_line_words_lds_nodes": (_i, []),
+    "dpmn_line_words_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dpmn_line_words_f64": (_i, [fp, _i, _i, fp, _i, _i, _i, fp, _i, C.c_double, _i, fp, fp, fp, fp, fp, fp]),
     "dpmn_aster_prep_f32": (_i, [fp, _l, fp, fp, _i, _i, _i, _i, _i, fp]),
     "dpmn_subsample_nhwc_f32": (_i, [fp, fp, _i, _i, _i, _i, _i, _i, fp]),
     "dpmn_aster_beam_workspace_bytes": (_sz, [_i, _i]),

@@ -182,6 +182,8 @@ static inline hipStream_t as_stream(dpmn_stream_t s) { return (hipStream_t)s; }
 constexpr int DPMN_MAX_DEVICES = 64;
 // CUs of the current device, 256 when the query fails.  Rounding to a grid stays with the caller.
 int dpmn_cu_count();
+// The most LDS in bytes a block of the current device may opt in to (dpmn_lds_optin), 65536 when the query fails.
+int dpmn_lds_limit();
 // Opt Kernel in to `bytes` of dynamic LDS on the current device: hipFuncSetAttribute acts on that device's copy of the kernel, so the
 // largest count already set is kept per kernel AND per device, and the call is made only for more than that.  A failure is not
 // recorded (the next launch retries) and not reported here: the launch that follows fails and DPMN_CHECK_LAUNCH returns it.

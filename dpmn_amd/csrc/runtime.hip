@@ -24,6 +24,19 @@ int dpmn_cu_count() {
   return n;
 }
 
+int dpmn_lds_limit() {
+  static std::atomic<int> lds[DPMN_MAX_DEVICES];
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return 65536;
+  const bool keyed = dev >= 0 && dev < DPMN_MAX_DEVICES;
+  int n = keyed ? lds[dev].load(std::memory_order_relaxed) : 0;
+  if (n < 1) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || n < 1) return 65536;
+    if (keyed) lds[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
 // ------------------------------------------------------------------ in-pipeline kernel profiler (common.h ProfScope)
 unsigned long long g_dpmn_prof_mask = 0ull;
 double g_dpmn_prof_hint_bytes = 0.0;

@@ -339,7 +339,8 @@ class TextSR(base.TextBase):
 
     @torch.no_grad()
     def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None, boxes=False, paste=False,
-             feather=1.0, paste_polygons=False, lexicon=None, confidence=False, upright=False, min_conf=None, line_read=False, line_space=0):
+             feather=1.0, paste_polygons=False, lexicon=None, confidence=False, upright=False, min_conf=None, line_read=False, line_space=0,
+             lexicon_penalty=0.0):
         """Super-resolve someone's own images (ours; main.py --demo_dir): batches yields (names, images_lr) as
         dataset.folder.folder_batches does.  Per batch `refine` (label_vecs from the frozen CRNN for tatt / tpgsr, as in eval), then
         save_image's quantisation on the GPU (ops.quantize_sr_u8), ONE device-to-host copy and one <stem>_sr.png per input under
@@ -400,16 +401,35 @@ class TextSR(base.TextBase):
         blend cannot repair a glyph that both windows see cut, and the string is over the CRNN's 36 symbols.  line_space N (0 ..
         64): a space goes where at least N line frames lie between two symbols' arg-max runs -- a heuristic on the blank runs, the
         CRNN has no space class; 0 inserts none.  With line_read, confidence=True combines with tile: lr_conf / sr_conf are
-        exp(score / terms) of the line's CTC likelihood; upright, min_conf and a lexicon stay refused with tile.  The <stem>_sr.png
-        files do not change."""
+        exp(score / terms) of the line's CTC likelihood; upright and min_conf stay refused with tile.  The <stem>_sr.png files do
+        not change.
+        lexicon with tile=True and line_read=True (ours; main.py --rec_lexicon with --demo_tile --demo_line_read;
+        utils/line_words.py; the lexicon's mode None or 'score', rec with read_lines): the SR line's stitched posteriors are also
+        decoded as a sequence of the lexicon's words -- the one-pass Viterbi over "blank gap, word, blank gap, ...", in the same
+        read_lines call and the same host copy -- and sr_lexicon / sr_lexicon_score are the words joined by single spaces and the
+        line's Viterbi score.  lexicon_penalty (finite, default 0.0, untuned): added once per word; negative means fewer, longer
+        words.  Every frame must be explained by a lexicon word or a gap, so a word outside the list comes back as its
+        nearest-scoring neighbours (sr_string beside it stays the open-vocabulary read), and two words need a blank frame between
+        them.  Without line_read a lexicon stays refused with tile."""
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
-        if lexicon is not None and tile:
+        if lexicon is not None and tile and not line_read:
             raise ValueError("demo: a lexicon does not combine with tile=True (a window of a line is not a word)")
         if lexicon is not None and reader is None:
             raise ValueError("demo: a lexicon needs a recogniser")
-        lex_reader = self._lexicon_reader(rec, reader, lexicon)
         line_kw = self._line_reader(rec, tile, line_read, line_space)
+        if lexicon is not None and line_kw:
+            # (a tiled line under a lexicon: the SR line's stitched posteriors are decoded as a sequence of its words)
+            import math
+            if lexicon.mode == "edit":
+                raise ValueError("demo: a lexicon in mode 'edit' does not combine with tile=True and line_read=True (the line's words "
+                                 "come from its frame posteriors)")
+            if not math.isfinite(float(lexicon_penalty)):
+                raise ValueError("demo: lexicon_penalty must be finite, got %r" % (lexicon_penalty,))
+            line_kw = dict(line_kw, lexicon=lexicon, penalty=float(lexicon_penalty))
+        elif lexicon_penalty:
+            raise ValueError("demo: lexicon_penalty needs a lexicon and line_read=True (it is the per-word score of a line's lexicon read)")
+        lex_reader = self._lexicon_reader(rec, reader, lexicon) if not line_kw else None
         # (with line_read the confidence columns are the lines' own: no read_conf, and nothing else of the three combines with tile)
         conf_reader = self._conf_reader(rec, tile, boxes, confidence and not line_kw, upright, min_conf)
         line_conf = bool(line_kw) and bool(confidence)
@@ -438,8 +458,8 @@ class TextSR(base.TextBase):
             rows = [r[0][:-4].rsplit("_", 1) + [label] + r[1:] for r, label in zip(rows, labels)]      # (+ the lexicon's two columns)
             batches = ()
         elif tile:
-            for names, pixels, preds_lr, preds_sr, _, conf in self._demo_windows(model_list, model_psn, batches, fn, reader, chunk, line_kw):
-                self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, conf=conf + (None,) if line_conf else None)
+            for names, pixels, preds_lr, preds_sr, _, conf, lex in self._demo_windows(model_list, model_psn, batches, fn, reader, chunk, line_kw):
+                self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex, conf=conf + (None,) if line_conf else None)
             batches = ()
         for names, images_lr in batches:
             n = len(names)
@@ -579,10 +599,12 @@ class TextSR(base.TextBase):
                     labels_out.extend(labels)
                     held[:] = photos
                     yield names, plan, images_lr
-            for names, pixels, preds_lr, preds_sr, device, conf in self._demo_windows(model_list, model_psn, windows(), fn, reader, chunk, line_kw):
+            for names, pixels, preds_lr, preds_sr, device, conf, lex in self._demo_windows(model_list, model_psn, windows(), fn, reader, chunk, line_kw):
                 pasted = self._demo_paste(names, held[0], device[0], device[1], feather, paste_polygons) if paste else []
-                if line_conf:      # (demo(line_read=True, confidence=True): no lexicon item, the lines' conf values, nothing turned)
-                    yield names, pixels, preds_lr, preds_sr, pasted, None, conf + (None,)
+                if line_conf:      # (demo(line_read=True, confidence=True): the lexicon's item or None, the lines' conf values, nothing turned)
+                    yield names, pixels, preds_lr, preds_sr, pasted, lex, conf + (None,)
+                elif lex is not None:
+                    yield names, pixels, preds_lr, preds_sr, pasted, lex
                 else:
                     yield names, pixels, preds_lr, preds_sr, pasted
             return
@@ -711,11 +733,13 @@ class TextSR(base.TextBase):
 
     def _demo_windows(self, model_list, model_psn, batches, fn, reader, chunk, line_kw=None):
         """demo(tile=True): per batch (names, plan, images_lr) of windows -> (names, one (H, W_b, 3) uint8 array per image, the LR
-        reads, the SR reads, (packed, meta), None), the reads of an image's windows joined with '|'; packed / meta: the stitched lines
+        reads, the SR reads, (packed, meta), None, None), the reads of an image's windows joined with '|'; packed / meta: the stitched lines
         as ops.stitch_windows_u8 returns them, still on the device.
         line_kw (demo's line_read: {rec, gap}): instead of reading every window, rec.window_rows keeps the frame logits of the LR and
         of the SR windows of every chunk on the device -- a line's windows may span chunks -- and rec.read_lines reads every line
-        once per side; the reads are the lines' strings and the last item is (lr conf values, sr conf values)."""
+        once per side; the reads are the lines' strings and the sixth item is (lr conf values, sr conf values).  With a lexicon in
+        line_kw ({lexicon, penalty}: demo's lexicon with line_read) the SR side's read_lines also reads the line as lexicon words and
+        the last item is (the words joined by spaces, the Viterbi scores); None otherwise."""
         from ..utils.confidence import confidence as conf_of
         chunk = max(int(chunk if chunk is not None else self.batch_size), 1)
         for names, plan, images_lr in batches:
@@ -742,15 +766,19 @@ class TextSR(base.TextBase):
             pixels = [flat[off:off + h * w * 3].reshape(h, w, 3) for off, h, w in meta]
             if line_kw:
                 lr_w = images_lr.shape[3]
-                side = [line_kw["rec"].read_lines(r[0] if len(r) == 1 else torch.cat(r, 0), plan, line_kw["gap"], lr_w)[:3] for r in (rows_lr, rows_sr)]
-                yield names, pixels, side[0][0], side[1][0], (packed, meta), (conf_of(*side[0][1:]), conf_of(*side[1][1:]))
+                # (demo's lexicon: the SR side's read_lines also decodes the line as lexicon words, in the same host copy)
+                lex_kw = {"lexicon": line_kw["lexicon"], "penalty": line_kw["penalty"]} if line_kw.get("lexicon") is not None else {}
+                side = [line_kw["rec"].read_lines(r[0] if len(r) == 1 else torch.cat(r, 0), plan, line_kw["gap"], lr_w, **kw)
+                        for r, kw in ((rows_lr, {}), (rows_sr, lex_kw))]
+                yield (names, pixels, side[0][0], side[1][0], (packed, meta), (conf_of(*side[0][1:3]), conf_of(*side[1][1:3])),
+                       (side[1][4], side[1][5]) if lex_kw else None)
                 continue
             preds_lr, preds_sr = [[] for _ in names], [[] for _ in names]
             if reader is not None:
                 for (b, _), s_lr, s_sr in zip(plan, reads_lr, reads_sr):
                     preds_lr[b].append(s_lr)
                     preds_sr[b].append(s_sr)
-            yield names, pixels, ['|'.join(p) for p in preds_lr], ['|'.join(p) for p in preds_sr], (packed, meta), None
+            yield names, pixels, ['|'.join(p) for p in preds_lr], ['|'.join(p) for p in preds_sr], (packed, meta), None, None
 
     # ------------------------------------------------------------------ training (super_resolution.py:113-278)
     def build_training(self, world_size=1, group=None):

@@ -206,28 +206,38 @@ class NativeCRNN(PackedEval, CRNN):
         return self.logits_rows(self.prep(images), self._packs())
 
     @torch.no_grad()
-    def read_lines(self, rows, plan, gap=0, lr_w=64):
+    def read_lines(self, rows, plan, gap=0, lr_w=64, lexicon=None, penalty=0.0):
         """One read per tiled line (ours; utils/line_read.py): rows = window_rows' logits of the windows of `plan` (utils/tile.py: an
         (image, x0) per window, lr_w columns wide) -> (strings, scores, terms, spans), one entry per image: the windows' frame
         posteriors blended along the line (dpmn_line_stitch_f32), decoded once (dpmn_line_greedy_i32) and scored once
         (dpmn_line_ctc_f32: the CTC log-likelihood of the line's own string, terms = max(its symbols, 1)) -- three launches and ONE
         device-to-host copy.  spans: per symbol the (first, last) line frame of its arg-max run.  gap >= 1: a space goes into the
         string where at least `gap` line frames lie between two symbols' runs (utils.line_read.insert_spaces, a heuristic: the CRNN
-        has no space class; scores, terms and spans are those of the symbols).  An image of one window gives `read`'s string."""
+        has no space class; scores, terms and spans are those of the symbols).  An image of one window gives `read`'s string.
+        lexicon (an ops.Lexicon) [penalty]: the same stitched posteriors are also read as a sequence of the lexicon's words
+        (ops.line_words_records; utils/line_words.py), its records behind the scores in the same buffer -- still ONE device-to-host
+        copy -- and the tuple gains three items: the words joined by single spaces, the Viterbi scores (float64) and the words'
+        (first, last) frame spans.  Without a lexicon the return and the launches are unchanged."""
         from ..utils.line_read import SPACE, insert_spaces
         if not len(plan) or rows.shape[0] % len(plan):
             raise ValueError("dpmn_amd NativeCRNN.read_lines: %d logits rows do not divide into the plan's %d windows" % (rows.shape[0], len(plan)))
         line_lp, lines = ops.line_stitch(rows, rows.shape[0] // len(plan), self.nclass, plan, lr_w)
         B, N = len(lines), lines.frames
-        buf = ops.line_greedy(line_lp, lines, extra=B)[0]
+        buf = ops.line_greedy(line_lp, lines, extra=B if lexicon is None else 3 * N + 5 * B)[0]
         ops.line_ctc_confidence(line_lp, lines, buf)
+        if lexicon is not None:
+            ops.line_words_records(line_lp, lines, lexicon, penalty, out=buf[3 * N + 2 * B:])
         h = buf.cpu().numpy()
         length = h[3 * N:3 * N + B]
         strings, spans = [], []
         for (f0, _), n in zip(lines, length.tolist()):
             spans.append(list(zip(h[N + f0:N + f0 + n].tolist(), h[2 * N + f0:2 * N + f0 + n].tolist())))
             strings.append("".join(" " if c == SPACE else ALPHABET[c - 1] for c in insert_spaces(h[f0:f0 + n].tolist(), spans[-1], gap)))
-        return strings, [float(v) for v in h[3 * N + B:3 * N + 2 * B].view("float32")], [max(int(n), 1) for n in length], spans
+        out = strings, [float(v) for v in h[3 * N + B:3 * N + 2 * B].view("float32")], [max(int(n), 1) for n in length], spans
+        if lexicon is None:
+            return out
+        reads = ops.line_words_decode(h[3 * N + 2 * B:], lines)
+        return out + ([" ".join(lexicon.words[w] for w in r[0]) for r in reads], [r[2] for r in reads], [r[1] for r in reads])
 
     @torch.no_grad()
     def label_vecs(self, images_lr3):

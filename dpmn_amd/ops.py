@@ -1860,6 +1860,26 @@ class Lexicon:
         self.max_class = int(self.packed[:, 1:].max())
         self.mode = mode
         self._dev, self._ws = {}, {}
+        self._trie, self._trie_dev = None, {}
+
+    @property
+    def trie(self):
+        """The prefix trie of the words (utils.line_words.build_trie: an (N, 4) int32 table), built on first use."""
+        if self._trie is None:
+            from .utils.line_words import build_trie
+            self._trie = build_trie(self.packed)
+        return self._trie
+
+    def device_trie(self, device):
+        """The trie on `device` (a flat int32 tensor of 4 N entries), uploaded on first use."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _abi.DpmnError("Lexicon: the lexicon kernels run on the GPU only (got %s); there is no CPU fallback" % device)
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        t = self._trie_dev.get(key)
+        if t is None:
+            t = self._trie_dev[key] = torch.from_numpy(self.trie.reshape(-1)).to(torch.device("cuda", key))
+        return t
 
     @classmethod
     def from_file(cls, path, voc_type="lower", mode=None):
@@ -2093,6 +2113,83 @@ def line_ctc_confidence(line_lp, lines, buf):
     check(lib.dpmn_line_ctc_f32(dptr(line_lp), n_class, lines.device_ptr(line_lp.device), p, p + 12 * N, p + 4 * (3 * N + B), B,
                                 lines.max_L, stream()))
     return buf[3 * N + B:3 * N + 2 * B].view(torch.float32)
+
+
+# ------------------------------------------------------------------------------ a tiled line as lexicon words (csrc/line_words.hip)
+LINE_WORDS_BLOCK = lib.dpmn_line_words_block()      # the trie nodes one block of the frame-per-launch arm covers
+LINE_WORDS_ARMS = ("step", "lds")                   # dpmn_line_words_f64's arm 0 / 1
+
+
+def line_words_lds_nodes(device):
+    """The most trie nodes the single-launch arm holds in the LDS of `device`."""
+    with torch.cuda.device(device):
+        return int(lib.dpmn_line_words_lds_nodes())
+
+
+def line_words_arm(nodes, device):
+    """The arm ops.line_words takes for a trie of `nodes` nodes on `device`: 'lds' (one launch per call, the state in LDS) while the
+    trie fits the device's LDS, else 'step' (one launch per frame).  Measured (profiles/line_words_bench.json): the single launch
+    is the faster one wherever it can run."""
+    return "lds" if int(nodes) <= line_words_lds_nodes(device) else "step"
+
+
+def line_words_records(line_lp, lines, lex, penalty=0.0, out=None, arm=None):
+    """The launches of line_words -> one int32 buffer (3 N + 4 B): per line frame the word of E[t], its start and whether G[t] was
+    entered from E[t-1], then per line the fp64 bits of G[L-1] and E[L-1] (utils.line_words.decode_records reads them).  out: write
+    into this int32 tensor of 3 N + 4 B elements instead (line_greedy's `extra`); arm: None (line_words_arm's), 'step' or 'lds'."""
+    import math
+    if not isinstance(lex, Lexicon):
+        raise _abi.DpmnError("line_words: lex must be an ops.Lexicon")
+    if not isinstance(lines, LineTable):
+        lines = LineTable(lines)
+    if not (torch.is_tensor(line_lp) and line_lp.is_cuda and line_lp.dtype == torch.float32 and line_lp.dim() == 2
+            and line_lp.shape[0] == lines.frames and line_lp.shape[1] >= 1 and line_lp.stride(1) == 1
+            and line_lp.stride(0) >= line_lp.shape[1]):
+        raise _abi.DpmnError("line_words: float32 CUDA line posteriors (%d, n_class) with unit column stride expected, one row per frame "
+                             "of the table; there is no CPU fallback" % lines.frames)
+    n_class, N, B = line_lp.shape[1], lines.frames, len(lines)
+    if lex.max_class >= n_class:
+        raise _abi.DpmnError("line_words: the lexicon holds class %d, the line has %d classes" % (lex.max_class, n_class))
+    if not math.isfinite(float(penalty)):
+        raise _abi.DpmnError("line_words: the penalty must be finite, got %r" % (penalty,))
+    trie = lex.device_trie(line_lp.device)
+    nodes = trie.numel() // 4
+    arm = line_words_arm(nodes, line_lp.device) if arm is None else arm
+    if arm not in LINE_WORDS_ARMS:
+        raise _abi.DpmnError("line_words: arm is None, 'step' or 'lds', got %r" % (arm,))
+    if out is None:
+        out = torch.empty(3 * N + 4 * B, dtype=torch.int32, device=line_lp.device)
+    elif not (torch.is_tensor(out) and out.device == line_lp.device and out.dtype == torch.int32 and out.is_contiguous()
+              and out.numel() == 3 * N + 4 * B):
+        raise _abi.DpmnError("line_words: out must be a contiguous int32 tensor of 3 N + 4 B elements on %s" % line_lp.device)
+    ws = lex.workspace(line_lp.device, lib.dpmn_line_words_workspace_bytes(B, N, nodes)) if arm == "step" else None
+    p = out.data_ptr()
+    with torch.cuda.device(line_lp.device):
+        check(lib.dpmn_line_words_f64(line_lp.data_ptr(), line_lp.stride(0), n_class, lines.device_ptr(line_lp.device), B, lines.max_L, N,
+                                      trie.data_ptr(), nodes, float(penalty), LINE_WORDS_ARMS.index(arm), p, p + 4 * N, p + 8 * N,
+                                      p + 12 * N, ws.data_ptr() if ws is not None else None, stream()))
+    return out
+
+
+def line_words_decode(h, lines):
+    """The host half: h = line_words_records' buffer as a NumPy int32 array -> per line (word indices, spans, score)."""
+    from .utils.line_words import decode_records
+    N, B = lines.frames, len(lines)
+    fin = h[3 * N:3 * N + 4 * B].view("float64").reshape(B, 2)
+    return [decode_records(L, fin[b], h[f0:f0 + L], h[N + f0:N + f0 + L], h[2 * N + f0:2 * N + f0 + L])
+            for b, (f0, L) in enumerate(lines)]
+
+
+def line_words(line_lp, lines, lex, penalty=0.0, arm=None):
+    """Every line read as a sequence of lexicon words (utils.line_words.line_words_np: the one-pass Viterbi over "blank gap, word,
+    blank gap, ..."): line_lp (N = sum L_b, n_class) float32 log-posteriors (ops.line_stitch's; rows may be a column slice of a
+    wider buffer, the columns behind n_class are not read), lines its LineTable (or a host (B, 2) table), lex an ops.Lexicon,
+    penalty a finite float added once per word -> per line (word indices, [(first, last)] spans, score), the score a float64 with
+    the restatement's bits.  ONE device-to-host copy.  arm: line_words_records'."""
+    if not isinstance(lines, LineTable):
+        lines = LineTable(lines)
+    out = line_words_records(line_lp, lines, lex, penalty, arm=arm)
+    return line_words_decode(out.cpu().numpy(), lines)
 
 
 # ------------------------------------------------------------------------------ native ASTER recogniser (csrc/aster.hip)

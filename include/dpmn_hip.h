@@ -449,6 +449,25 @@ int dpmn_line_greedy_i32(const float* line_lp, int n_class, const int* lines, in
 int dpmn_line_ctc_f32(const float* line_lp, int n_class, const int* lines, const int* cls, const int* length, float* out_score, int B,
                       int max_L, dpmn_stream_t stream);
 
+/* ------------------------------------------------------------------ a tiled line read as lexicon words (line_words.hip;
+ * utils/line_words.py is the NumPy restatement and the definition; main.py --rec_lexicon with --demo_tile --demo_line_read).  The
+ * one-pass Viterbi over "blank gap, word, blank gap, ..." on the lexicon's prefix trie, fp64 + and compares on the exactly widened
+ * float32 rows: the bits of line_words_trie_np.  No call depends on the compute mode.
+ * line_lp: rows (frames, ld >= n_class), columns >= n_class never read; lines (B, 2) int32 [first row, L], back to back; trie: nodes
+ * records of four int32 [parent or -1, class, 1 if the class equals the parent's, word index or -1] (utils.line_words.build_trie; a
+ * parent stands before its children), 16-byte aligned.  Limits: n_class <= 64, max_L <= 3201, B <= 65535, nodes <= 2^25, a finite
+ * penalty.  arm 0: one launch per frame, any trie, ws = workspace_bytes(B, frames, nodes) bytes, 8-byte aligned; arm 1: one launch per
+ * call with the state in LDS, nodes <= dpmn_line_words_lds_nodes() on the current device, ws unused.
+ * Out, per line frame: rec_word / rec_start (the word of E[t], the best word end of that frame by (score, lower index), and the frame
+ * at which it was entered) and rec_enter (1 where G[t] came from E[t-1]); per line fin (B, 4): the fp64 bits, low word first, of
+ * G[L-1] and E[L-1].  utils.line_words.decode_records walks them.  dpmn_line_words_block: the nodes a block of arm 0 covers. */
+int dpmn_line_words_block(void);
+int dpmn_line_words_lds_nodes(void);
+size_t dpmn_line_words_workspace_bytes(int B, int frames, int nodes);
+int dpmn_line_words_f64(const float* line_lp, int ld, int n_class, const int* lines, int B, int max_L, int frames, const int* trie,
+                        int nodes, double penalty, int arm, int* rec_word, int* rec_start, int* rec_enter, int* fin, void* ws,
+                        dpmn_stream_t stream);
+
 /* ------------------------------------------------------------------ native ASTER recogniser (aster.hip; model/aster.py NativeASTER)
  * aster_prep:      parse_aster_data (x * 2 - 1, interfaces/base.py:441-450) + F.interpolate(x, (Hs, Ws), bilinear,
  *                  align_corners=True) (recognizer_builder.py:77): img (B, >=3, H, W) planes with batch stride img_stride (channels

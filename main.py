@@ -184,8 +184,9 @@ def paste_feather(args):
 def rec_lexicon_setting(args, load=True):
     """--rec_lexicon FILE [--rec_lexicon_mode score|edit], checked -> (the words, the mode), or None without the flag.  The mode
     defaults to score for --rec crnn and to edit for --rec aster / moran.  Every problem is a ValueError of one line: the mode without
-    the file, score with a recogniser that is not the CRNN, the flag together with --demo_tile, the flag on a training run, a missing
-    file, a file without a usable word.  load=False: only the checks that need no file contents (-> (None, mode))."""
+    the file, score with a recogniser that is not the CRNN, the flag together with --demo_tile (unless --demo_line_read is set: the
+    line is then read as a sequence of the lexicon's words, in score mode only), --rec_lexicon_penalty without its two flags, the
+    flag on a training run, a missing file, a file without a usable word.  load=False: only the checks that need no file contents (-> (None, mode))."""
     path, mode = getattr(args, "rec_lexicon", None), getattr(args, "rec_lexicon_mode", None)
     if not path:
         if mode:
@@ -200,7 +201,13 @@ def rec_lexicon_setting(args, load=True):
         raise ValueError("--rec_lexicon_mode score needs --rec crnn: the CTC likelihood of a word is computed from the CRNN's frame "
                          "posteriors; --rec %s reads under a lexicon with --rec_lexicon_mode edit" % rec)
     if getattr(args, "demo_tile", False):
-        raise ValueError("--rec_lexicon does not combine with --demo_tile: a window of a line is not a word")
+        # (--demo_line_read reads a tiled line once: its posteriors are then decoded as a sequence of the lexicon's words)
+        if not getattr(args, "demo_line_read", False):
+            raise ValueError("--rec_lexicon does not combine with --demo_tile: a window of a line is not a word")
+        if mode != "score":
+            raise ValueError("--rec_lexicon_mode edit does not combine with --demo_tile --demo_line_read: the line's words come from "
+                             "its frame posteriors, and there is no single string to take an edit distance to")
+    rec_lexicon_penalty(args)
     if not (getattr(args, "test", False) or getattr(args, "demo_dir", None)):
         raise ValueError("--rec_lexicon needs --test or --demo_dir: the lexicon is used where SR images are read, not in training")
     if not os.path.isfile(path):
@@ -211,11 +218,31 @@ def rec_lexicon_setting(args, load=True):
     return load_lexicon(path, "lower"), mode
 
 
-def lexicon_accuracies(rows):
+def rec_lexicon_penalty(args):
+    """--rec_lexicon_penalty F, checked -> the float, 0.0 without the flag: the log-domain score every word of a tiled line's lexicon
+    read pays (utils/line_words.py; negative: fewer, longer words).  ValueError of one line for a value that is not finite and for
+    the flag without --rec_lexicon and --demo_line_read."""
+    import math
+    f = getattr(args, "rec_lexicon_penalty", None)
+    if f is None:
+        return 0.0
+    if not (getattr(args, "rec_lexicon", None) and getattr(args, "demo_line_read", False)):
+        raise ValueError("--rec_lexicon_penalty needs --rec_lexicon and --demo_line_read: it is the per-word score of a tiled line's "
+                         "lexicon read")
+    f = float(f)
+    if not math.isfinite(f):
+        raise ValueError("--rec_lexicon_penalty must be a finite number (a log-domain score added once per word)")
+    return f
+
+
+def lexicon_accuracies(rows, spaces=True):
     """The rows of demo_result.csv with boxes and a lexicon (file, box, label, lr_string, sr_string, sr_lexicon, sr_lexicon_score) ->
-    (labelled regions, open-vocabulary accuracy, lexicon accuracy); the accuracies are None without a labelled region."""
+    (labelled regions, open-vocabulary accuracy, lexicon accuracy); the accuracies are None without a labelled region.
+    spaces=False (the rows of --demo_line_read: a line's reads hold spaces, a filtered label none): the reads are compared with
+    their spaces removed."""
     from dpmn_amd.utils.util import str_filt
-    labelled = [(str_filt(r[2], "lower"), r[4], r[5]) for r in rows if str_filt(r[2], "lower")]
+    keep = (lambda s: s) if spaces else (lambda s: s.replace(" ", ""))
+    labelled = [(keep(str_filt(r[2], "lower")), keep(r[4]), keep(r[5])) for r in rows if str_filt(r[2], "lower")]
     if not labelled:
         return 0, None, None
     n = len(labelled)
@@ -344,6 +371,7 @@ def main(config, args):
     # (the lexicon is read before anything touches the GPU: a bad file or a wrong combination ends the run here)
     try:
         lex_words = rec_lexicon_setting(args)
+        lex_penalty = rec_lexicon_penalty(args)
     except ValueError as e:
         raise SystemExit("main.py: %s" % e)
     try:
@@ -381,6 +409,8 @@ def main(config, args):
         from dpmn_amd.ops import Lexicon
         lex_kw = {"lexicon": Lexicon(lex_words[0], mode=lex_words[1])}
         print("rec_lexicon: %d words, mode %s" % (len(lex_words[0]), lex_words[1]))
+        if line_kw:
+            lex_kw["lexicon_penalty"] = lex_penalty
     if line_kw and not callable(getattr(rec, "read_lines", None)):
         raise SystemExit("main.py: --demo_line_read needs the native CRNN, and --rec %s built none (see the line above)" % args.rec)
     if conf_kw and not callable(getattr(rec, "read_conf", None)):
@@ -431,14 +461,17 @@ def main(config, args):
             if lex_kw:
                 # (with the confidence columns sr_string is column 5 and the lexicon's word follows sr_conf and turned)
                 lex_rows = [r[:4] + [r[5], r[7 + bool(conf_kw["upright"])]] for r in rows] if conf_kw else rows
-                print("accuracy %s accuracy_lexicon %s over %d labelled regions" % tuple(lexicon_accuracies(lex_rows)[i] for i in (1, 2, 0)))
+                # (a line read holds spaces and a filtered label none: there both sides are compared without them)
+                print("accuracy %s accuracy_lexicon %s over %d labelled regions"
+                      % tuple(lexicon_accuracies(lex_rows, spaces=not line_kw)[i] for i in (1, 2, 0)))
             print("%d regions super-resolved into %s" % (len(rows), out_dir))
             return
         if getattr(args, "demo_tile", False):
             # wide images keep their aspect ratio: overlapping LR windows per image, one stitched <stem>_sr.png (utils/tile.py)
             batches = folder_window_batches(args.demo_dir, bs, lr_size, mission.mask, mission.device)
             # (--demo_line_read: one read per line instead of the windows' reads joined with '|'; with it --demo_conf combines)
-            rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=True, chunk=bs, **conf_kw, **line_kw)
+            # (... and so does --rec_lexicon: lex_kw is empty otherwise, rec_lexicon_setting refused it)
+            rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=True, chunk=bs, **lex_kw, **conf_kw, **line_kw)
         else:
             batches = folder_batches(args.demo_dir, bs, lr_size, mission.mask, mission.device)
             rows = mission.demo(models, psn, batches, out_dir, rec=rec, **lex_kw, **conf_kw)
@@ -663,7 +696,11 @@ if __name__ == '__main__':
     parser.add_argument('--rec_lexicon', type=str, default=None, metavar='FILE',
                         help='with --test or --demo_dir and a recogniser: also read every SR image under this word list (one word per '
                              'line, UTF-8; filtered like --train_words, duplicates dropped): --test reports accuracy_lexicon beside '
-                             'accuracy, --demo_dir writes the columns sr_lexicon and sr_lexicon_score; not with --demo_tile')
+                             'accuracy, --demo_dir writes the columns sr_lexicon and sr_lexicon_score; with --demo_tile only under '
+                             '--demo_line_read: the line is then read as a sequence of the words (utils/line_words.py)')
+    parser.add_argument('--rec_lexicon_penalty', type=float, default=None, metavar='F',
+                        help='with --rec_lexicon and --demo_tile --demo_line_read: a log-domain score added once per word of a line\'s '
+                             'lexicon read (default 0.0, untuned; negative: fewer, longer words)')
     parser.add_argument('--rec_lexicon_mode', default=None, choices=['score', 'edit'],
                         help='with --rec_lexicon: score = the word of the highest CTC likelihood under the frame posteriors (--rec crnn '
                              'only, its default), edit = the word at the least edit distance to the recognised string (any recogniser; '
@@ -702,6 +739,7 @@ if __name__ == '__main__':
         parser.error(str(e))
     try:
         rec_lexicon_setting(args, load=False)
+        rec_lexicon_penalty(args)
     except ValueError as e:
         parser.error(str(e))
     try:
