@@ -322,6 +322,9 @@ SIGNATURES = {
     "dpmn_detect_stats_i32": (_i, [fp, fp, _l, fp, fp, _i, fp, _i, fp, fp, fp, fp, fp, _l, fp]),
     "dpmn_detect_moments_i64": (_i, [fp, fp, _l, fp, fp, _i, fp, _i, fp, fp, fp, fp, _l, fp]),
     "dpmn_detect_extents_i32": (_i, [fp, fp, _l, fp, fp, _i, fp, _i, fp, fp, fp, fp, fp, _l, fp]),
+    "dpmn_region_block": (_i, []),
+    "dpmn_region_area_u64": (_i, [fp, _l, fp, fp, _i, fp, fp, _i, fp, fp]),
+    "dpmn_region_inter_u64": (_i, [fp, _l, fp, fp, _i, fp, fp, _i, fp, fp, _i, fp, fp]),
     "dpmn_profile_tag_count": (_i, []),
     "dpmn_profile_hint_bytes": (_i, [C.c_double]),
     "dpmn_profile_tag_name": (C.c_char_p, [_i]),

@@ -1255,6 +1255,88 @@ def detect_maps_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24):
     return out
 
 
+def _region_units_table(first_items, rows, block):
+    """One block per `block` sample rows of every item -> int32 (n_units, 2) [item, first row]."""
+    import numpy as np
+    n = -(-rows // block)
+    item = np.repeat(np.arange(len(rows), dtype=np.int64) + first_items, n)
+    start = np.cumsum(n) - n
+    return np.stack([item, (np.arange(int(n.sum()), dtype=np.int64) - np.repeat(start, n)) * block], axis=1).astype(np.int32)
+
+
+def _region_plan(regions_a, regions_b):
+    """The host half of region_overlap_counts: the unit coordinates, boxes, pair list and block tables of a batch, packed for one
+    upload -> dict(host, offsets (verts, regions, pairs, area units, pair units) in int64 words, n_verts, R, P, n_area_units,
+    n_pair_units, first, pairs, n_pairs)."""
+    import numpy as np
+    from .utils import detect_eval as de
+    if len(regions_a) != len(regions_b):
+        raise _abi.DpmnError("region_overlap_counts: %d and %d photos" % (len(regions_a), len(regions_b)))
+    try:
+        verts, n_pts, boxes = de.regions_flat([r for photo in zip(regions_a, regions_b) for side in photo for r in side])
+    except (ValueError, TypeError) as e:
+        raise _abi.DpmnError("region_overlap_counts: %s" % e) from e
+    n_side = np.array([[len(a), len(b)] for a, b in zip(regions_a, regions_b)], np.int64).reshape(-1, 2)
+    first = np.concatenate(([0], np.cumsum(n_side.reshape(-1)))).astype(np.int64)      # photo p: a from first[2p], b from first[2p + 1]
+    pairs = [de.meeting_pairs(boxes[first[2 * p]:first[2 * p + 1]], boxes[first[2 * p + 1]:first[2 * p + 2]]) for p in range(len(n_side))]
+    n_pairs = np.array([len(p) for p in pairs], np.int64)
+    plan = dict(R=len(n_pts), P=int(n_pairs.sum()), first=first, pairs=pairs, n_pairs=n_pairs)
+    if not plan["R"]:
+        return plan
+    block = int(lib.dpmn_region_block())
+    table = np.zeros((plan["R"], 8), np.int32)
+    table[:, 0], table[:, 1], table[:, 2:6] = np.cumsum(n_pts) - n_pts, n_pts, boxes
+    verts = verts.astype(np.int32)
+    gpairs = np.concatenate([p + (first[2 * i], first[2 * i + 1]) for i, p in enumerate(pairs)]) if plan["P"] else np.zeros((0, 2), np.int64)
+    ua = _region_units_table(0, de.SUB * (boxes[:, 3] - boxes[:, 1]), block)
+    ba, bb = boxes[gpairs[:, 0]], boxes[gpairs[:, 1]]
+    ub = _region_units_table(0, de.SUB * (np.minimum(ba[:, 3], bb[:, 3]) - np.maximum(ba[:, 1], bb[:, 1])), block)
+    host, offsets = _pack(verts, table, np.ascontiguousarray(gpairs, np.int32), ua, ub)
+    plan.update(host=host, offsets=offsets, n_verts=len(verts), n_area_units=len(ua), n_pair_units=len(ub))
+    return plan
+
+
+def _region_launch(plan, d, out):
+    """The two launches of region_overlap_counts: d = the uploaded plan["host"], out = int64 (R + P) on the device (areas, then pairs)."""
+    o_v, o_r, o_p, o_ua, o_ub = plan["offsets"]
+    dp, hp, R, st = d.data_ptr(), plan["host"].ctypes.data, plan["R"], _abi.stream_of(d.device)
+    check(lib.dpmn_region_area_u64(dp + 8 * o_v, plan["n_verts"], dp + 8 * o_r, hp + 8 * o_r, R, dp + 8 * o_ua, hp + 8 * o_ua,
+                                   plan["n_area_units"], out.data_ptr(), st))
+    check(lib.dpmn_region_inter_u64(dp + 8 * o_v, plan["n_verts"], dp + 8 * o_r, hp + 8 * o_r, R, dp + 8 * o_p, hp + 8 * o_p, plan["P"],
+                                    dp + 8 * o_ub, hp + 8 * o_ub, plan["n_pair_units"], out.data_ptr() + 8 * R, st))
+
+
+def region_overlap_counts(regions_a, regions_b, device=None):
+    """The overlap counts of a batch of photos (csrc/detect_eval.hip; main.py --demo_eval): regions_a / regions_b hold per photo a list
+    of (n, 2) point arrays in pixels (the detections and the ground truth) -> per photo the four arrays of
+    utils.detect_eval.region_counts_np -- area_a, area_b uint64, pairs int64 (p, 2) in row-major order, inter uint64 (p) -- equal to it
+    with == (region_counts_batch_np is the restatement of the whole call).  The host makes the unit coordinates, the integer boxes and
+    from them, with NumPy, the pair list (pairs never cross photos); then one upload, two launches (the areas of all regions, the
+    intersections of all pairs) and one device-to-host copy.  A batch without a region launches nothing.  Validated on the host; no
+    CPU fallback."""
+    import numpy as np
+    if not torch.cuda.is_available():
+        raise _abi.DpmnError("region_overlap_counts: the regions are counted on the GPU; there is no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise _abi.DpmnError("region_overlap_counts: the regions are counted on the GPU (got device %s); there is no CPU fallback" % dev)
+    plan = _region_plan(regions_a, regions_b)
+    R, first, n_pairs = plan["R"], plan["first"], plan["n_pairs"]
+    counts = np.zeros(R + plan["P"], np.uint64)
+    if R:
+        with torch.cuda.device(dev):
+            d = torch.from_numpy(plan["host"]).to(dev)
+            out = torch.empty(R + plan["P"], dtype=torch.int64, device=dev)
+            _region_launch(plan, d, out)
+            counts = out.cpu().numpy().view(np.uint64)      # (synchronous: d and out are done with)
+    res, at = [], R
+    for p in range(len(n_pairs)):
+        res.append((counts[first[2 * p]:first[2 * p + 1]].copy(), counts[first[2 * p + 1]:first[2 * p + 2]].copy(), plan["pairs"][p],
+                    counts[at:at + n_pairs[p]].copy()))
+        at += int(n_pairs[p])
+    return res
+
+
 def maxpool(x, kh, kw, scale=None, shift=None):
     """nn.MaxPool2d((kh,kw), stride (kh,kw)) over NHWC; scale/shift: the producer's BatchNorm affine + ReLU applied on load."""
     B, H, W, Cc = x.shape

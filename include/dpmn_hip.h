@@ -759,6 +759,25 @@ int dpmn_detect_extents_i32(const unsigned char* smooth, const int* labels, long
                             const long long* items_host /* HOST array */, int B, const int* tiles, int n_tiles, const long long* slices,
                             const long long* slices_host /* HOST array */, const int* slots, const int* dirs, int* table, long table_rows,
                             dpmn_stream_t stream);
+/* The overlap of detected and ground-truth regions in samples (detect_eval.hip; utils/detect_eval.py is the definition and the NumPy
+ * restatement; main.py --demo_eval): 4 x 4 samples per pixel, even-odd rule, integers only, independent of the compute mode.
+ * verts: device int32 (n_verts, 2), the vertices (x, y) of all regions of a batch of photos in units of 1 / 800 pixel.  regions:
+ * device int32 (n_regions, 8), per region [first vertex, vertices (4 .. 64), x0, y0, x1, y1 of its pixel box (ends exclusive,
+ * |v| <= 16385), 0, 0].  units: device int32 (n_units, 2), per block [item, first sample row of the block counted from the top of
+ * the item's box, a multiple of dpmn_region_block()]: a block takes dpmn_region_block() sample rows, one per thread, and counts the
+ * samples between a row's sorted edge crossings by subtraction (a row with more than 8 crossings of a region tests its samples one
+ * by one).  Every *_host is the same table in HOST memory: the entry points check it and refuse the call before any launch; the
+ * kernels check the device copy and skip what fails.  Counts are uint64, zeroed here; n_units == 0 launches nothing.
+ * dpmn_region_area_u64: item = a region, area[region] = the samples inside it over its box.  One launch.
+ * dpmn_region_inter_u64: pairs: device int32 (n_pairs, 2) of region indices; item = a pair, inter[pair] = the samples inside both
+ * over the intersection of the two boxes.  One launch. */
+int dpmn_region_block(void);
+int dpmn_region_area_u64(const int* verts, long n_verts, const int* regions, const int* regions_host /* HOST array */, int n_regions,
+                         const int* units, const int* units_host /* HOST array */, int n_units, unsigned long long* area,
+                         dpmn_stream_t stream);
+int dpmn_region_inter_u64(const int* verts, long n_verts, const int* regions, const int* regions_host /* HOST array */, int n_regions,
+                          const int* pairs, const int* pairs_host /* HOST array */, int n_pairs, const int* units,
+                          const int* units_host /* HOST array */, int n_units, unsigned long long* inter, dpmn_stream_t stream);
 
 /* rotation augmentation of the trainer (utils/util.py:37-58 torch_rotate_img; super_resolution.py:144-151, 358-365):
  * per-image affine with aspect-ratio jitter -> affine_grid (align_corners=False) -> bilinear grid_sample, zeros padding.

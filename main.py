@@ -144,6 +144,41 @@ def demo_conf_setting(args):
     return {"confidence": True, "upright": upright, "min_conf": c}
 
 
+DEMO_EVAL_NEEDS_DIR = "main.py: --demo_eval needs --demo_dir: the regions that are scored are those of the photos of that folder"
+DEMO_EVAL_NEEDS_BOXES = ("main.py: --demo_eval needs --demo_detect or --demo_boxes: it scores the regions of the run's box files against "
+                         "the ground truth")
+
+
+def demo_eval_setting(args):
+    """--demo_eval GTDIR, checked -> None without the flag, else GTDIR.  ValueError (the message without its 'main.py: ') for the flag
+    without --demo_dir or without a box source (--demo_detect or --demo_boxes), and for a GTDIR that is not a directory."""
+    gt_dir = getattr(args, "demo_eval", None)
+    if not gt_dir:
+        return None
+    if not getattr(args, "demo_dir", None):
+        raise ValueError(DEMO_EVAL_NEEDS_DIR[len("main.py: "):])
+    if not (getattr(args, "demo_detect", False) or getattr(args, "demo_boxes", None)):
+        raise ValueError(DEMO_EVAL_NEEDS_BOXES[len("main.py: "):])
+    if not os.path.isdir(gt_dir):
+        raise ValueError("--demo_eval %s is not a directory" % gt_dir)
+    return gt_dir
+
+
+def demo_eval(rows, demo_dir, box_dir, gt_dir, out_dir, device, recogniser=True, conf=False, upright=False, lexicon=False, min_conf=False,
+              spaces=True):
+    """--demo_eval: the rows TextSR.demo returned for the photos of demo_dir and the box files of box_dir, scored against
+    gt_dir/<stem>.txt (or gt_<stem>.txt) by utils/detect_eval.py with the overlap counts of ops.region_overlap_counts on `device`;
+    writes out_dir/detect_eval.csv and prints one line with the totals -> (records, totals).  The lines of a box file without a row
+    (regions the run refused, or dropped under --demo_min_conf) are left out.  conf / upright / lexicon / min_conf: which columns
+    the rows hold; recogniser=False: the e2e columns stay empty; spaces=False: the rows of --demo_line_read."""
+    from dpmn_amd import ops
+    from dpmn_amd.utils import detect_eval as de
+    stems = list(dict.fromkeys(os.path.splitext(f)[0] for f in sorted(os.listdir(demo_dir))
+                               if os.path.isfile(os.path.join(demo_dir, f)) and not f.lower().endswith(".txt")))
+    return de.evaluate_dir(stems, de.row_reads(rows, conf, upright, lexicon, min_conf), box_dir, gt_dir, os.path.join(out_dir, "detect_eval.csv"),
+                           lambda a, b: ops.region_overlap_counts(a, b, device), recogniser, lexicon, spaces)
+
+
 DEMO_LINE_READ_NEEDS_TILE = ("main.py: --demo_line_read needs --demo_dir and --demo_tile: it reads a line that was super-resolved in overlapping "
                              "windows as one string")
 DEMO_LINE_READ_NEEDS_CRNN = ("main.py: --demo_line_read needs --rec crnn: the frame posteriors of the CRNN are blended along the line; ASTER "
@@ -377,6 +412,7 @@ def main(config, args):
     try:
         conf_kw = demo_conf_setting(args) or {}
         line_kw = demo_line_setting(args) or {}
+        eval_dir = demo_eval_setting(args)
     except ValueError as e:
         raise SystemExit("main.py: %s" % e)
     hr_dir = getattr(args, "train_hr_dir", None)
@@ -465,6 +501,11 @@ def main(config, args):
                 print("accuracy %s accuracy_lexicon %s over %d labelled regions"
                       % tuple(lexicon_accuracies(lex_rows, spaces=not line_kw)[i] for i in (1, 2, 0)))
             print("%d regions super-resolved into %s" % (len(rows), out_dir))
+            if eval_dir:
+                # the run's regions and reads scored against the ground truth of GTDIR: detect_eval.csv (utils/detect_eval.py)
+                demo_eval(rows, args.demo_dir, box_dir, eval_dir, out_dir, mission.device, recogniser=rec is not None, conf=bool(conf_kw),
+                          upright=bool(conf_kw.get("upright")), lexicon=bool(lex_kw), min_conf=conf_kw.get("min_conf") is not None,
+                          spaces=not line_kw)
             return
         if getattr(args, "demo_tile", False):
             # wide images keep their aspect ratio: overlapping LR windows per image, one stitched <stem>_sr.png (utils/tile.py)
@@ -630,6 +671,13 @@ if __name__ == '__main__':
     parser.add_argument('--demo_min_conf', type=float, default=None, metavar='C',
                         help='with --demo_boxes or --demo_detect: a region whose SR read is empty or less confident than C (0 < C < 1) '
                              'is dropped: no region file, not pasted, column kept = 0; not with --demo_tile')
+    parser.add_argument('--demo_eval', type=str, default=None, metavar='GTDIR',
+                        help='with --demo_detect or --demo_boxes: score the regions of the run\'s box files against the ground truth of '
+                             'GTDIR (<stem>.txt or gt_<stem>.txt per photo; ICDAR 2015 quads, CTW1500 / Total-Text polygons, ### for '
+                             'don\'t-care): precision, recall and h-mean at IoU > 0.5 by the ICDAR protocol, and end to end (a match '
+                             'counts when the SR read equals the transcription), per photo and in total, into '
+                             '<demo_out>/detect_eval.csv.  Regions dropped by --demo_min_conf are left out.  IoU is counted on 4 x 4 '
+                             'samples per pixel on the GPU (utils/detect_eval.py)')
     parser.add_argument('--demo_line_read', action='store_true', default=False,
                         help='with --demo_tile and --rec crnn: lr_string / sr_string are ONE read of the whole line instead of the '
                              "windows' reads joined with '|': the CRNN's frame posteriors of the overlapping windows are blended along "
@@ -745,6 +793,7 @@ if __name__ == '__main__':
     try:
         demo_conf_setting(args)
         demo_line_setting(args)
+        demo_eval_setting(args)
     except ValueError as e:
         parser.error(str(e))
     config_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'config', 'super_resolution.yaml')
