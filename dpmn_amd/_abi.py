@@ -271,6 +271,7 @@ SIGNATURES = {
     "dpmn_ctc_conf_f32": (_i, [fp, _i, _i, fp, fp, fp, _i, _i, fp]),
     "dpmn_attn_conf_f32": (_i, [fp, fp, _i, fp, fp, _i, _i, _i, fp]),
     "dpmn_turn180_f32": (_i, [fp, fp, _i, _i, _i, _i, fp]),
+    "dpmn_ctc_beam_f64": (_i, [fp, _i, _i, fp, _i, _i, C.c_double, C.c_double, fp, fp, fp, _i, _i, fp]),
     "dpmn_line_stitch_f32": (_i, [fp, _i, _i, _i, _i, fp, fp, fp, _i, _i, fp, fp]),
     "dpmn_line_greedy_i32": (_i, [fp, _i, fp, _i, _i, fp, fp, fp, fp, fp]),
     "dpmn_line_ctc_f32": (_i, [fp, _i, fp, fp, fp, fp, _i, _i, fp]),

@@ -222,7 +222,7 @@ class TextSR(base.TextBase):
 
     @torch.no_grad()
     def eval(self, model_list, val_loader, index=0, rec=None, aster_info=None, rec_list=None, model_psn=None, crnn_psn=None,
-             text_prior_fn=None, display=False, display_failures=False, lexicon=None):
+             text_prior_fn=None, display=False, display_failures=False, lexicon=None, beam=None):
         """super_resolution.py:340-513.  PSNR/SSIM always; recognition accuracy (lines 453-493) only when `rec` reads the SR images
         and the loader yields label strings as a 4th item: `rec` is the native CRNN (TextBase.CRNN_init, --rec crnn: its `read`), the
         native ASTER (TextBase.Aster_init, --rec aster: its `read`), the native MORAN (TextBase.MORAN_init, --rec moran: its `read`, the
@@ -238,16 +238,20 @@ class TextSR(base.TextBase):
         read_lexicon (the CRNN: the word of the highest CTC likelihood, in the same forward pass; ASTER / MORAN: the word nearest to
         the greedy string), a plain callable's strings through ops.edit_read -- and the dict gains 'accuracy_lexicon', counted like
         'accuracy' (None when nothing was labelled or there is no recogniser).  'accuracy' and everything else are what they are
-        without it."""
+        without it.
+        beam (ours; main.py --rec_beam / --rec_lm; utils/beam.py): a dict or an object with lm (an ops.CharLM or None), width, alpha,
+        beta.  The SR images are also read by the CTC prefix beam search (rec.read_beam: the native CRNN, in the same forward pass as
+        the greedy read; with a lexicon too, one pass more) and the dict gains 'accuracy_lm', counted exactly as 'accuracy_lexicon'."""
         from ..utils.util import str_filt
         from ..model.native import PackedEval
         reader = rec.read if isinstance(rec, PackedEval) and hasattr(rec, "read") else (rec if callable(rec) else None)
         lex_reader = self._lexicon_reader(rec, reader, lexicon)
+        beam_reader = self._beam_reader(rec, reader, beam)
         for m in model_list:
             m.eval()
         fn = text_prior_fn or self.default_text_prior()
         psnr, ssim, n = [], [], 0
-        n_correct, n_labelled, n_correct_lex = 0, 0, 0
+        n_correct, n_labelled, n_correct_lex, n_correct_lm = 0, 0, 0, 0
         last, visualized = None, 0      # display: (images_lr, sr, images_hr, LR strings | None, SR strings | None, labels | None) of the last batch
         # the batches of an evaluation pass are independent: two of them in flight (RefinePipeline).  The loop is software-pipelined:
         # batch i + 1 is prepared and SUBMITTED before this stream waits for batch i and queues its metrics -- a lane is ordered
@@ -262,7 +266,7 @@ class TextSR(base.TextBase):
             pipe = cached[1]
 
         def finish(sr, images_hr, labels, images_lr):
-            nonlocal n, n_correct, n_labelled, n_correct_lex, last, visualized
+            nonlocal n, n_correct, n_labelled, n_correct_lex, n_correct_lm, last, visualized
             if pipe is not None:
                 RefinePipeline.wait(sr)      # (the display kernels below read sr on this stream: behind the batch's lane)
             p, s = ops.psnr_ssim(sr, images_hr)
@@ -275,8 +279,13 @@ class TextSR(base.TextBase):
                     preds_sr, preds_lex, _ = lex_reader(sr[:, :3])
                     for pred, target in zip(preds_lex, labels):
                         n_correct_lex += int(pred == str_filt(target, 'lower'))
-                else:
+                elif beam_reader is None:
                     preds_sr = reader(sr[:, :3])
+                if beam_reader is not None:      # (without a lexicon the greedy strings come from the same pass)
+                    greedy, preds_lm, _ = beam_reader(sr[:, :3])
+                    preds_sr = greedy if preds_sr is None else preds_sr
+                    for pred, target in zip(preds_lm, labels):
+                        n_correct_lm += int(pred == str_filt(target, 'lower'))
                 for pred, target in zip(preds_sr, labels):
                     n_correct += int(pred == str_filt(target, 'lower'))
                 n_labelled += len(labels)
@@ -318,7 +327,39 @@ class TextSR(base.TextBase):
             res['visualized'] = visualized
         if lexicon is not None:
             res['accuracy_lexicon'] = round(n_correct_lex / n_labelled, 4) if n_labelled and lex_reader is not None else None
+        if beam is not None:
+            res['accuracy_lm'] = round(n_correct_lm / n_labelled, 4) if n_labelled and beam_reader is not None else None
         return res
+
+    @staticmethod
+    def _beam_settings(beam):
+        """eval / demo's `beam` (a dict or an object with lm, width, alpha, beta; missing ones take read_beam's defaults) -> the
+        keywords of read_beam."""
+        get = beam.get if isinstance(beam, dict) else (lambda k, d=None: getattr(beam, k, d))
+        return {"lm": get("lm"), "width": int(get("width", 16)), "alpha": float(get("alpha", 0.5)), "beta": float(get("beta", 0.0))}
+
+    @classmethod
+    def _beam_reader(cls, rec, reader, beam):
+        """eval / demo: images -> (greedy strings, the beam search's strings, scores), or None without `beam` or a recogniser.  The
+        search needs frame posteriors: a recogniser without read_beam (ASTER, MORAN, a plain callable) is a ValueError."""
+        if beam is None or reader is None:
+            return None
+        if not callable(getattr(rec, "read_beam", None)):
+            raise ValueError("the CTC beam search needs a CTC recogniser with read_beam (NativeCRNN, --rec crnn); ASTER and MORAN have their "
+                             "own decoders")
+        kw = cls._beam_settings(beam)
+        return lambda images: rec.read_beam(images, **kw)
+
+    @staticmethod
+    def _with_beam(lex_reader, beam_reader):
+        """demo: one reader for the lexicon's and the beam search's columns: images -> (greedy strings, [the lexicon's strings, their
+        scores,] the beam search's strings, their scores).  Without a lexicon it is read_beam's one pass."""
+        if lex_reader is None:
+            return beam_reader
+
+        def read(images):
+            return tuple(lex_reader(images)) + tuple(beam_reader(images)[1:])
+        return read
 
     @staticmethod
     def _lexicon_reader(rec, reader, lexicon):
@@ -340,7 +381,7 @@ class TextSR(base.TextBase):
     @torch.no_grad()
     def demo(self, model_list, model_psn, batches, out_dir, rec=None, text_prior_fn=None, tile=False, chunk=None, boxes=False, paste=False,
              feather=1.0, paste_polygons=False, lexicon=None, confidence=False, upright=False, min_conf=None, line_read=False, line_space=0,
-             lexicon_penalty=0.0):
+             lexicon_penalty=0.0, beam=None):
         """Super-resolve someone's own images (ours; main.py --demo_dir): batches yields (names, images_lr) as
         dataset.folder.folder_batches does.  Per batch `refine` (label_vecs from the frozen CRNN for tatt / tpgsr, as in eval), then
         save_image's quantisation on the GPU (ops.quantize_sr_u8), ONE device-to-host copy and one <stem>_sr.png per input under
@@ -393,6 +434,13 @@ class TextSR(base.TextBase):
         they must then be made with photos=True, whether paste is set or not.
         The columns, in order: file, [box, label,] lr_string, lr_conf, sr_string, sr_conf, [turned,] [sr_lexicon, sr_lexicon_score,]
         [kept]; the lexicon's read of the SR image stays a second call through read_lexicon.  Without the three nothing changes.
+        beam (ours; main.py --rec_beam / --rec_lm; utils/beam.py; eval's setting: lm, width, alpha, beta; needs a recogniser with
+        read_beam -- NativeCRNN; not with tile: a line has word boundaries that the CRNN has no class for): the SR image is also read by
+        the CTC prefix beam search with the character model and the rows gain sr_lm, sr_lm_score (the string and its float64 score,
+        %.6g).  With every option the columns are, in order: file, [box, label,] lr_string, [lr_conf,] sr_string, [sr_conf,] then
+        EITHER (with a lexicon) [turned,] sr_lexicon, sr_lexicon_score, sr_lm, sr_lm_score OR (without one) sr_lm, sr_lm_score,
+        [turned,] and last [kept]: sr_lm follows the lexicon's columns where they are, else sr_string or sr_conf.  Without a lexicon
+        the greedy strings come from read_beam's own pass; with one, read_beam is one call more.
         line_read (ours; main.py --demo_line_read; utils/line_read.py; needs tile=True and a CTC recogniser with window_rows and
         read_lines -- NativeCRNN; ASTER and MORAN have no frame posteriors): lr_string / sr_string are ONE read of the whole line per
         side, with no '|': the frame posteriors of the line's windows are kept on the device chunk by chunk, blended along the line
@@ -430,6 +478,16 @@ class TextSR(base.TextBase):
         elif lexicon_penalty:
             raise ValueError("demo: lexicon_penalty needs a lexicon and line_read=True (it is the per-word score of a line's lexicon read)")
         lex_reader = self._lexicon_reader(rec, reader, lexicon) if not line_kw else None
+        if beam is not None and tile:
+            raise ValueError("demo: the CTC beam search does not combine with tile=True (a line has word boundaries that the CRNN has no "
+                             "class for, and a window of a line is not a word)")
+        if beam is not None and reader is None:
+            raise ValueError("demo: the CTC beam search needs a recogniser")
+        beam_reader = self._beam_reader(rec, reader, beam)
+        lm_kw = {}
+        if beam_reader is not None:
+            # (from here the lexicon's item holds the beam search's two lists behind the lexicon's two, or alone)
+            lex_reader, lm_kw = self._with_beam(lex_reader, beam_reader), {"lm": True}
         # (with line_read the confidence columns are the lines' own: no read_conf, and nothing else of the three combines with tile)
         conf_reader = self._conf_reader(rec, tile, boxes, confidence and not line_kw, upright, min_conf)
         line_conf = bool(line_kw) and bool(confidence)
@@ -449,9 +507,10 @@ class TextSR(base.TextBase):
                                                                                        float(feather) if paste else None, bool(paste_polygons),
                                                                                        lex_reader, **conf_kw, **self._line_kw(line_kw, line_conf)):
                 if conf_reader is not None:      # lex = [the lexicon's item or None, (lr_conf, sr_conf, turned or None), kept or None]
-                    self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken, lex[0], conf=lex[1], kept=lex[2])
+                    self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken, lex[0], conf=lex[1], kept=lex[2],
+                                     **lm_kw)
                 else:
-                    self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken, *lex)
+                    self._demo_write(out_dir, [n + ".png" for n in names], pixels, preds_lr, preds_sr, rows, taken, *lex, **lm_kw)
                 self._demo_write(out_dir, [stem + "_photo.png" for stem, _ in photos], [a for _, a in photos], [''] * len(photos),
                                  [''] * len(photos), [], taken)
             # <stem>_<k>.png, lr, sr -> stem, k, label, lr, sr
@@ -474,24 +533,27 @@ class TextSR(base.TextBase):
             if conf_reader is not None:
                 preds_sr, conf_sr = conf_reader(sr[:, :3])
                 self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex_reader(sr[:, :3])[1:] if lex_reader is not None else None,
-                                 conf=(conf_lr, conf_sr, turned if upright else None))
+                                 conf=(conf_lr, conf_sr, turned if upright else None), **lm_kw)
                 continue
             blank = [''] * n
             preds_lr = reader(images_lr[:n, :3]) if reader is not None else blank
             if lex_reader is not None:
                 preds_sr, *lex = lex_reader(sr[:, :3])
-                self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex)
+                self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex, **lm_kw)
                 continue
             preds_sr = reader(sr[:, :3]) if reader is not None else blank
             self._demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken)
         with open(os.path.join(out_dir, "demo_result.csv"), "w", newline="") as out:
             w = csv.writer(out)
             head = ["file", "box", "label"] if boxes else ["file"]
+            lm_head = ["sr_lm", "sr_lm_score"] if beam_reader is not None else []
             if conf_reader is None and not line_conf:
                 head += ["lr_string", "sr_string"]
-            else:
-                head += ["lr_string", "lr_conf", "sr_string", "sr_conf"] + (["turned"] if upright else [])
-            w.writerow(head + (["sr_lexicon", "sr_lexicon_score"] if lexicon is not None else []) + (["kept"] if min_conf is not None else []))
+            else:      # (without a lexicon sr_lm follows sr_conf, before turned)
+                head += ["lr_string", "lr_conf", "sr_string", "sr_conf"] + (lm_head if lexicon is None else []) + (["turned"] if upright else [])
+                lm_head = lm_head if lexicon is not None else []
+            w.writerow(head + (["sr_lexicon", "sr_lexicon_score"] if lexicon is not None else []) + lm_head
+                       + (["kept"] if min_conf is not None else []))
             w.writerows(rows)
         return rows
 
@@ -557,12 +619,14 @@ class TextSR(base.TextBase):
                 [int(t) for t in turned])
 
     @staticmethod
-    def _demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex=None, conf=None, kept=None):
+    def _demo_write(out_dir, names, pixels, preds_lr, preds_sr, rows, taken, lex=None, conf=None, kept=None, lm=False):
         """demo: one <stem>_sr.png per image of a batch and its row; lex: None, or (the lexicon's strings, their scores), two more
         columns.  conf: None, or (lr conf values, sr conf values, turned flags or None): the row's confidence columns.  kept: None,
-        or one flag per image: an image that is not kept gets no file, and the row ends with the flag."""
+        or one flag per image: an image that is not kept gets no file, and the row ends with the flag.  lm: the LAST two lists of lex
+        are the beam search's (strings, scores) -- alone, or behind the lexicon's two; alone they stand before the turned flag."""
         from PIL import Image
-        more = [[str(w), "%.6g" % sc] for w, sc in zip(*lex)] if lex is not None else [[]] * len(names)
+        more = [[cell for k in range(0, len(t), 2) for cell in (str(t[k]), "%.6g" % t[k + 1])] for t in zip(*lex)] if lex is not None else [[]] * len(names)
+        lm_first = bool(lm) and lex is not None and len(lex) == 2      # (no lexicon's columns to follow)
         for i, (name, a, s_lr, s_sr, extra) in enumerate(zip(names, pixels, preds_lr, preds_sr, more)):
             if kept is None or kept[i]:
                 out_name = os.path.splitext(name)[0] + "_sr.png"
@@ -575,8 +639,9 @@ class TextSR(base.TextBase):
             if conf is None:
                 rows.append([name, str(s_lr), str(s_sr)] + extra)
                 continue
-            rows.append([name, str(s_lr), "%.4f" % conf[0][i], str(s_sr), "%.4f" % conf[1][i]] + ([str(int(conf[2][i]))] if conf[2] is not None else [])
-                        + extra + ([str(int(bool(kept[i])))] if kept is not None else []))
+            turned = [str(int(conf[2][i]))] if conf[2] is not None else []
+            rows.append([name, str(s_lr), "%.4f" % conf[0][i], str(s_sr), "%.4f" % conf[1][i]] + (extra + turned if lm_first else turned + extra)
+                        + ([str(int(bool(kept[i])))] if kept is not None else []))
 
     def _demo_regions(self, model_list, model_psn, batches, fn, reader, chunk, tile, labels_out, feather=None, paste_polygons=False,
                       lex_reader=None, conf_reader=None, upright=False, min_conf=None, out_dir=None, line_kw=None, line_conf=False):
@@ -637,15 +702,17 @@ class TextSR(base.TextBase):
                     conf_sr += c_sr
                     if lex_reader is not None:
                         got = lex_reader(sr[:, :3])
-                        lex[0].extend(got[1])
-                        lex[1].extend(got[2])
+                        lex = lex if len(lex) == len(got) - 1 else tuple([] for _ in got[1:])      # (two more lists with the beam search)
+                        for held, new in zip(lex, got[1:]):
+                            held.extend(new)
                     continue
                 preds_lr += list(reader(x[:n, :3])) if reader is not None else [''] * n
                 if lex_reader is not None:
                     got = lex_reader(sr[:, :3])
                     preds_sr += list(got[0])
-                    lex[0].extend(got[1])
-                    lex[1].extend(got[2])
+                    lex = lex if len(lex) == len(got) - 1 else tuple([] for _ in got[1:])
+                    for held, new in zip(lex, got[1:]):
+                        held.extend(new)
                 else:
                     preds_sr += list(reader(sr[:, :3])) if reader is not None else [''] * n
             pasted = []
@@ -1268,15 +1335,16 @@ class TextSR(base.TextBase):
     def _psn_crnn_path(self):
         return os.path.join(self.resume, "recognizer_best_crnn.pth") if self.resume and os.path.isdir(self.resume) else None
 
-    def test(self, loader=None, rec=None, display=False, lexicon=None):
+    def test(self, loader=None, rec=None, display=False, lexicon=None, beam=None):
         """super_resolution.py:515-775: PGRMs from model_best_{k}.pth, CMM from model_best_cmm.pth, PSN from model_{arch}.pth
         under --resume (all required: there is no evaluation of untrained weights).  display=True: the comparison images of the
         last batch under <vis_dir>/0/ and those of every wrongly read image under <vis_dir>/display/ (their number: 'visualized').
-        lexicon: eval's (an ops.Lexicon: the dict gains 'accuracy_lexicon')."""
+        lexicon: eval's (an ops.Lexicon: the dict gains 'accuracy_lexicon'); beam: eval's (the dict gains 'accuracy_lm')."""
         models, psn = self.build_models(testing=True)
         if loader is None:
             raise RuntimeError("dpmn_amd: pass a loader of (images_hr, images_lr, label_vecs) batches: "
                                "dataset.textzoom.sr_batches(self.get_test_data(dir)[1], device) or dpmn_amd.utils.synth.synth_batch")
-        if lexicon is not None:
-            return self.eval(models, loader, 0, rec=rec, model_psn=psn, display=display, display_failures=display, lexicon=lexicon)
+        if lexicon is not None or beam is not None:
+            more = dict(({"lexicon": lexicon} if lexicon is not None else {}), **({"beam": beam} if beam is not None else {}))
+            return self.eval(models, loader, 0, rec=rec, model_psn=psn, display=display, display_failures=display, **more)
         return self.eval(models, loader, 0, rec=rec, model_psn=psn, display=display, display_failures=display)

@@ -183,6 +183,22 @@ class NativeCRNN(PackedEval, CRNN):
         return greedy, lex.strings(h[n:n + B]), [float(v) for v in h[n + B:].view("float32")]
 
     @torch.no_grad()
+    def read_beam(self, images, lm=None, width=16, alpha=0.5, beta=0.0):
+        """Greedy and beam-search reading in one forward pass (ours; utils/beam.py, ops.ctc_beam) -> (greedy strings, the beam
+        search's strings, scores).  The greedy strings are `read`'s.  The CTC prefix beam search of `width` prefixes runs on the same
+        logits rows in one launch (dpmn_ctc_beam_f64), weighing every new symbol with alpha times the character model lm (an
+        ops.CharLM; None: no model) plus beta; the scores (float64) are log P_CTC(prefix) + its model score.  Its result lies
+        behind the greedy decode's in the same buffer: ONE device-to-host copy brings both."""
+        self._check_eval()
+        rows, B, T = self.logits_rows(self.prep(images), self._packs())
+        buf, _, _ = ops.ctc_greedy(rows, B, T, self.nclass, extra=B * T + 3 * B)
+        ops.ctc_beam(rows, B, T, self.nclass, lm, width, alpha, beta, out=buf[B * T + B:])
+        h = buf.cpu().numpy()
+        n = B * T + B
+        cls, length, scores = ops.ctc_beam_decode(h[n:], B, T)
+        return decode_classes(h[:B * T].reshape(B, T), h[B * T:n]), decode_classes(cls, length), [float(v) for v in scores]
+
+    @torch.no_grad()
     def read_conf(self, images):
         """`read` with a confidence (ours; utils/confidence.py) -> (strings, scores, terms): the strings are `read`'s, from the same
         forward pass; score = the CTC log-likelihood of each image's own greedy string (dpmn_ctc_conf_f32 on the same logits rows,

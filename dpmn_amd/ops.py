@@ -2053,6 +2053,92 @@ def edit_read(strings, lex, device):
     return lex.strings(h[:B]), [int(d) for d in h[B:]]
 
 
+# ------------------------------------------------------------------------------ CTC beam search with a character model (csrc/beam.hip)
+class CharLM:
+    """A character n-gram model for ctc_beam (utils/beam.py): `table`, the float32 natural logs (37 ** (order - 1), 37) of
+    utils.beam.build_char_lm, and its `order` (1 .. 3).  The table is uploaded once per device and kept."""
+
+    def __init__(self, table, order):
+        import numpy as np
+        from .utils import beam as bm
+        table = np.ascontiguousarray(table)
+        if order not in (1, 2, 3) or bm.table_order(table) != order:
+            raise _abi.DpmnError("CharLM: order is 1 .. %d and the table float32 (37 ** (order - 1), 37), got order %r and %s %s"
+                                 % (bm.MAX_ORDER, order, table.dtype, table.shape))
+        if not np.isfinite(table).all():
+            raise _abi.DpmnError("CharLM: the table holds a value that is not finite")
+        self.table, self.order = table, int(order)
+        self.uploads = 0
+        self._dev = {}
+
+    @classmethod
+    def from_file(cls, path, voc_type="lower", order=3, k=4.0):
+        """The model of a word file (utils.beam.load_lm_words: the lexicon loader's filter, duplicates count)."""
+        from .utils import beam as bm
+        if order not in (1, 2, 3):
+            raise _abi.DpmnError("CharLM: order is 1 .. %d, got %r" % (bm.MAX_ORDER, order))
+        return cls(bm.build_char_lm(bm.load_lm_words(path, voc_type), order, k), order)
+
+    def device_table(self, device):
+        """The table on `device` (a flat float32 tensor), uploaded on first use (`uploads` counts them)."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _abi.DpmnError("CharLM: the beam search runs on the GPU only (got %s); there is no CPU fallback" % device)
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.from_numpy(self.table.reshape(-1)).to(torch.device("cuda", key))
+            self.uploads += 1
+        return t
+
+
+def ctc_beam(logits, B, T, n_class, lm=None, width=16, alpha=0.5, beta=0.0, out=None):
+    """The CTC prefix beam search of utils/beam.py per image, in ONE launch: logits rows b*T + t (B*T, >= n_class) float32 with unit
+    column stride (logits_rows' layout or a column slice of it; the columns at or beyond n_class are not read), lm a CharLM or None
+    (alpha then counts as 0), width 1 .. 32, alpha the model's weight, beta added per symbol -> one int32 buffer (B*T + 3 B): the
+    classes of the best prefix (B, T) zero-filled, the lengths (B), then the bits of the float64 scores (B):
+    `buf[B*T + B:].view(torch.float64)` on the host copy.  out: write into this int32 tensor of B*T + 3 B elements instead
+    (ctc_greedy's `extra`).  T <= 64, n_class <= 64 (<= 37 with a model); DpmnError outside the limits."""
+    import math
+    from .utils import beam as bm
+    if lm is not None and not isinstance(lm, CharLM):
+        raise _abi.DpmnError("ctc_beam: lm must be an ops.CharLM or None")
+    if not (torch.is_tensor(logits) and logits.is_cuda):
+        raise _abi.DpmnError("ctc_beam: the beam search runs on the GPU only (got a %s tensor); there is no CPU fallback"
+                             % (logits.device if torch.is_tensor(logits) else type(logits).__name__))
+    if (logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape[0] != B * T or logits.shape[1] < n_class or B < 1
+            or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]):
+        raise _abi.DpmnError("ctc_beam: float32 logits rows (B*T, >= n_class) with unit column stride expected")
+    if not (1 <= T <= bm.MAX_T and 2 <= n_class <= bm.MAX_CLASS):
+        raise _abi.DpmnError("ctc_beam: 1 .. %d frames and 2 .. %d classes are supported, got T = %d, n_class = %d"
+                             % (bm.MAX_T, bm.MAX_CLASS, T, n_class))
+    if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= bm.MAX_WIDTH:
+        raise _abi.DpmnError("ctc_beam: the width is an integer 1 .. %d, got %r" % (bm.MAX_WIDTH, width))
+    if not (math.isfinite(float(alpha)) and math.isfinite(float(beta))):
+        raise _abi.DpmnError("ctc_beam: alpha and beta must be finite, got %r, %r" % (alpha, beta))
+    if lm is not None and n_class > bm.LM_CLASSES:
+        raise _abi.DpmnError("ctc_beam: the model knows %d classes, the logits have %d" % (bm.LM_CLASSES, n_class))
+    n = B * T + 3 * B
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=logits.device)
+    elif not (torch.is_tensor(out) and out.device == logits.device and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == n):
+        raise _abi.DpmnError("ctc_beam: out must be a contiguous int32 tensor of B*T + 3 B elements on %s" % logits.device)
+    table = lm.device_table(logits.device) if lm is not None else None
+    p = out.data_ptr()
+    with torch.cuda.device(logits.device):
+        check(lib.dpmn_ctc_beam_f64(logits.data_ptr(), logits.stride(0), n_class, table.data_ptr() if table is not None else None,
+                                    lm.order if lm is not None else 0, width, float(alpha), float(beta), p, p + 4 * B * T,
+                                    p + 4 * (B * T + B), B, T, stream()))
+    return out
+
+
+def ctc_beam_decode(h, B, T):
+    """The host half: h = ctc_beam's buffer as a NumPy int32 array -> (classes (B, T), lengths (B), float64 scores (B))."""
+    import numpy as np
+    h = np.ascontiguousarray(h)
+    return h[:B * T].reshape(B, T), h[B * T:B * T + B], h[B * T + B:B * T + 3 * B].copy().view(np.float64)
+
+
 # ------------------------------------------------------------------------------ recogniser confidence (csrc/confidence.hip)
 def ctc_confidence(logits, B, T, n_class, buf):
     """The CTC log-likelihood of every image's own greedy string (utils.confidence.ctc_score): logits rows b*T + t (B*T, ld >=

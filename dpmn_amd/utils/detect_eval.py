@@ -57,6 +57,7 @@ _CHUNK = 1 << 21        # samples per slab of the sample form
 CSV_HEAD = ["file", "gt", "gt_care", "det", "det_care", "matched", "precision", "recall", "hmean", "e2e_labelled", "e2e_correct",
             "e2e_precision", "e2e_recall", "e2e_hmean"]
 CSV_LEXICON = ["e2e_lexicon_precision", "e2e_lexicon_recall", "e2e_lexicon_hmean"]
+CSV_LM = ["e2e_lm_precision", "e2e_lm_recall", "e2e_lm_hmean"]      # (the reads of the CTC beam search: main.py --rec_beam / --rec_lm)
 
 
 def region_units(points):
@@ -274,11 +275,11 @@ def e2e(record, gt_labels, gt_dont_care, det_reads, spaces=True):
 def score(records):
     """The dataset line: matched, care ground truth and care detections summed over the photos' records (micro average; prf with
     total=True) -> {gt, gt_care, det, det_care, matched, precision, recall, hmean}, and the same sums of the e2e keys where the
-    records hold them (e2e_*, and e2e_lexicon_* when present)."""
+    records hold them (e2e_*, and e2e_lexicon_* / e2e_lm_* when present)."""
     records = list(records)
     tot = {k: sum(r[k] for r in records) for k in ("gt", "gt_care", "det", "det_care", "matched")}
     tot["precision"], tot["recall"], tot["hmean"] = prf(tot["matched"], tot["gt_care"], tot["det_care"], total=True)
-    for pre in ("e2e_", "e2e_lexicon_"):
+    for pre in ("e2e_", "e2e_lexicon_", "e2e_lm_"):
         if records and all(pre + "correct" in r for r in records):
             for k in ("labelled", "correct", "det"):
                 tot[pre + k] = sum(r[pre + k] for r in records)
@@ -365,9 +366,10 @@ def _fmt(v):
     return "%.4f" % v
 
 
-def evaluate(photos, counts, recogniser=True, lexicon=False, spaces=True):
+def evaluate(photos, counts, recogniser=True, lexicon=False, spaces=True, lm=False):
     """The records of a list of load_photo's photos: counts is region_counts_batch_np or a callable with its contract
-    (ops.region_overlap_counts on a device).  recogniser=False: no e2e keys.  -> (records, totals)."""
+    (ops.region_overlap_counts on a device).  recogniser=False: no e2e keys.  lm: the reads hold a third item, the beam search's
+    string, scored under e2e_lm_* as the lexicon's word is under e2e_lexicon_*.  -> (records, totals)."""
     records = []
     for photo, (ad, ag, pairs, inter) in zip(photos, counts([p["det"] for p in photos], [p["gt"] for p in photos]) if photos else ()):
         rec = match(ad, ag, pairs, inter, photo["gt_dont_care"], photo["det_absent"])
@@ -377,13 +379,16 @@ def evaluate(photos, counts, recogniser=True, lexicon=False, spaces=True):
             if lexicon:
                 lex = e2e(rec, photo["gt_labels"], photo["gt_dont_care"], [r[1] or "" for r in photo["det_reads"]], spaces)
                 rec.update({"e2e_lexicon_" + k[4:]: v for k, v in lex.items()})
+            if lm:
+                got = e2e(rec, photo["gt_labels"], photo["gt_dont_care"], [r[2] or "" for r in photo["det_reads"]], spaces)
+                rec.update({"e2e_lm_" + k[4:]: v for k, v in got.items()})
         records.append(rec)
     return records, score(records)
 
 
-def csv_rows(records, totals, recogniser=True, lexicon=False):
+def csv_rows(records, totals, recogniser=True, lexicon=False, lm=False):
     """The rows of detect_eval.csv, header first and TOTAL last; ratios with four decimals, the e2e columns empty without a recogniser."""
-    head = CSV_HEAD + (CSV_LEXICON if lexicon else [])
+    head = CSV_HEAD + (CSV_LEXICON if lexicon else []) + (CSV_LM if lm else [])
     rows = [head]
     for rec in list(records) + [dict(totals, file="TOTAL")]:
         row = [rec["file"]] + [str(rec[k]) for k in ("gt", "gt_care", "det", "det_care", "matched")] + [_fmt(rec[k]) for k in ("precision", "recall", "hmean")]
@@ -393,50 +398,56 @@ def csv_rows(records, totals, recogniser=True, lexicon=False):
             row += [""] * 5
         if lexicon:
             row += [_fmt(rec["e2e_lexicon_" + k]) for k in ("precision", "recall", "hmean")] if "e2e_lexicon_correct" in rec else [""] * 3
+        if lm:
+            row += [_fmt(rec["e2e_lm_" + k]) for k in ("precision", "recall", "hmean")] if "e2e_lm_correct" in rec else [""] * 3
         rows.append(row)
     return rows
 
 
-def write_csv(path, records, totals, recogniser=True, lexicon=False):
+def write_csv(path, records, totals, recogniser=True, lexicon=False, lm=False):
     with open(path, "w", newline="") as out:
-        csv.writer(out).writerows(csv_rows(records, totals, recogniser, lexicon))
+        csv.writer(out).writerows(csv_rows(records, totals, recogniser, lexicon, lm))
 
 
 def totals_line(totals, n_photos):
     """The one printed line of a run."""
     line = ("detect_eval: %d photos, %d of %d care ground-truth regions matched by %d care detections: precision %.4f recall %.4f hmean %.4f"
             % (n_photos, totals["matched"], totals["gt_care"], totals["det_care"], totals["precision"], totals["recall"], totals["hmean"]))
-    for pre, name in (("e2e_", "end to end"), ("e2e_lexicon_", "end to end under the lexicon")):
+    for pre, name in (("e2e_", "end to end"), ("e2e_lexicon_", "end to end under the lexicon"),
+                      ("e2e_lm_", "end to end under the beam search")):
         if pre + "correct" in totals:
             line += "; %s %d of %d read correctly: precision %.4f recall %.4f hmean %.4f" % (
                 name, totals[pre + "correct"], totals[pre + "labelled"], totals[pre + "precision"], totals[pre + "recall"], totals[pre + "hmean"])
     return line
 
 
-def evaluate_dir(stems, reads_by_stem, box_dir, gt_dir, out_path, counts, recogniser=True, lexicon=False, spaces=True, batch=64):
+def evaluate_dir(stems, reads_by_stem, box_dir, gt_dir, out_path, counts, recogniser=True, lexicon=False, spaces=True, batch=64, lm=False):
     """main.py --demo_eval: the photos `stems` of a run, scored in batches of `batch` photos (one counts call each), written to
     out_path as detect_eval.csv -> (records, totals); one line with the totals is printed.  reads_by_stem: {stem: {k: (sr_string,
-    sr_lexicon or None)}} of the regions the run read and kept."""
+    sr_lexicon or None)}} of the regions the run read and kept; lm: the reads are (sr_string, sr_lexicon or None, sr_lm)."""
     photos = [p for p in (load_photo(s, box_dir, gt_dir, reads_by_stem.get(s, {})) for s in stems) if p is not None]
     records = []
     for i in range(0, len(photos), int(batch)):
-        records += evaluate(photos[i:i + int(batch)], counts, recogniser, lexicon, spaces)[0]
+        records += evaluate(photos[i:i + int(batch)], counts, recogniser, lexicon, spaces, lm)[0]
     totals = score(records)
     if not recogniser:
         totals = {k: v for k, v in totals.items() if not k.startswith("e2e_")}
-    write_csv(out_path, records, totals, recogniser, lexicon)
+    write_csv(out_path, records, totals, recogniser, lexicon, lm)
     print(totals_line(totals, len(records)))
     return records, totals
 
 
-def row_reads(rows, conf=False, upright=False, lexicon=False, min_conf=False):
+def row_reads(rows, conf=False, upright=False, lexicon=False, min_conf=False, lm=False):
     """The rows TextSR.demo returns with boxes=True (file, box, label, lr_string, [lr_conf,] sr_string, [sr_conf, [turned,]]
-    [sr_lexicon, sr_lexicon_score,] [kept]) -> {stem: {k: (sr_string, sr_lexicon or None)}} of the regions that were kept."""
+    [sr_lexicon, sr_lexicon_score,] [kept]) -> {stem: {k: (sr_string, sr_lexicon or None)}} of the regions that were kept.
+    lm: the rows also hold sr_lm, sr_lm_score -- behind the lexicon's columns, or without a lexicon behind sr_string / sr_conf and
+    before turned -- and the values are (sr_string, sr_lexicon or None, sr_lm)."""
     out = {}
     i_sr = 5 if conf else 4
     i_lex = i_sr + 1 + (1 + bool(upright) if conf else 0)
+    i_lm = i_lex + 2 if lexicon else i_sr + 1 + bool(conf)
     for r in rows:
         if min_conf and str(r[-1]) == "0":
             continue
-        out.setdefault(r[0], {})[int(r[1])] = (r[i_sr], r[i_lex] if lexicon else None)
+        out.setdefault(r[0], {})[int(r[1])] = (r[i_sr], r[i_lex] if lexicon else None) + ((r[i_lm],) if lm else ())
     return out

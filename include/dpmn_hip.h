@@ -429,6 +429,17 @@ int dpmn_attn_conf_f32(const float* logits, const int* ids, int eos, float* out_
                        dpmn_stream_t stream);
 int dpmn_turn180_f32(const float* x, float* y, int B, int C, int H, int W, dpmn_stream_t stream);
 
+/* ------------------------------------------------------------------ CTC prefix beam search with a character n-gram model (beam.hip;
+ * utils/beam.py is the definition and the NumPy restatement; main.py --rec_beam / --rec_lm).  No call depends on the compute mode.
+ * logits: rows b*T + t with leading dimension ld >= n_class (columns >= n_class are not read), T <= 64, 2 <= n_class <= 64.
+ * lm_table: null (lm_order 0; alpha is then taken as 0) or the float32 natural logs (37^(lm_order - 1), 37) of
+ * utils.beam.build_char_lm, lm_order 1 .. 3, n_class <= 37.  width 1 .. 32; alpha (the model's weight) and beta (added per symbol)
+ * finite.  One launch, one wave per image, every score in fp64 -> out_cls (B, T): the classes of the best prefix, zero-filled;
+ * out_len (B); out_score (B, 2): the bits of its fp64 rank score lse(pb, pnb) + lm, the low dword first.  Ties: the lower parent
+ * rank, then the lower class. */
+int dpmn_ctc_beam_f64(const float* logits, int ld, int n_class, const float* lm_table, int lm_order, int width, double alpha, double beta,
+                      int* out_cls, int* out_len, int* out_score, int B, int T, dpmn_stream_t stream);
+
 /* ------------------------------------------------------------------ one read per tiled text line (line_read.hip; utils/line_read.py is
  * the NumPy restatement and the definition; main.py --demo_line_read).  No call depends on the compute mode.  Device tables: lines (B, 2)
  * int32 [first row of line_lp, L] per line, the lines back to back; wins (B, 2) [first window, windows]; x0: every window's first column

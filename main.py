@@ -165,18 +165,20 @@ def demo_eval_setting(args):
 
 
 def demo_eval(rows, demo_dir, box_dir, gt_dir, out_dir, device, recogniser=True, conf=False, upright=False, lexicon=False, min_conf=False,
-              spaces=True):
+              spaces=True, lm=False):
     """--demo_eval: the rows TextSR.demo returned for the photos of demo_dir and the box files of box_dir, scored against
     gt_dir/<stem>.txt (or gt_<stem>.txt) by utils/detect_eval.py with the overlap counts of ops.region_overlap_counts on `device`;
     writes out_dir/detect_eval.csv and prints one line with the totals -> (records, totals).  The lines of a box file without a row
     (regions the run refused, or dropped under --demo_min_conf) are left out.  conf / upright / lexicon / min_conf: which columns
-    the rows hold; recogniser=False: the e2e columns stay empty; spaces=False: the rows of --demo_line_read."""
+    the rows hold; recogniser=False: the e2e columns stay empty; spaces=False: the rows of --demo_line_read; lm: the rows hold sr_lm,
+    sr_lm_score (--rec_beam / --rec_lm), scored end to end as the lexicon's word is (e2e_lm_*)."""
     from dpmn_amd import ops
     from dpmn_amd.utils import detect_eval as de
     stems = list(dict.fromkeys(os.path.splitext(f)[0] for f in sorted(os.listdir(demo_dir))
                                if os.path.isfile(os.path.join(demo_dir, f)) and not f.lower().endswith(".txt")))
-    return de.evaluate_dir(stems, de.row_reads(rows, conf, upright, lexicon, min_conf), box_dir, gt_dir, os.path.join(out_dir, "detect_eval.csv"),
-                           lambda a, b: ops.region_overlap_counts(a, b, device), recogniser, lexicon, spaces)
+    return de.evaluate_dir(stems, de.row_reads(rows, conf, upright, lexicon, min_conf, **({"lm": True} if lm else {})), box_dir, gt_dir,
+                           os.path.join(out_dir, "detect_eval.csv"), lambda a, b: ops.region_overlap_counts(a, b, device), recogniser, lexicon,
+                           spaces, **({"lm": True} if lm else {}))
 
 
 DEMO_LINE_READ_NEEDS_TILE = ("main.py: --demo_line_read needs --demo_dir and --demo_tile: it reads a line that was super-resolved in overlapping "
@@ -268,6 +270,51 @@ def rec_lexicon_penalty(args):
     if not math.isfinite(f):
         raise ValueError("--rec_lexicon_penalty must be a finite number (a log-domain score added once per word)")
     return f
+
+
+def rec_beam_setting(args, load=True):
+    """--rec_beam W, --rec_lm FILE [--rec_lm_order N] [--rec_lm_weight A], [--rec_lm_bonus B], checked -> None without --rec_beam and
+    --rec_lm, else {width, order, alpha, beta, words}: the CTC prefix beam search of utils/beam.py on the SR images (--rec_lm implies
+    --rec_beam 16; words: the file's, duplicates kept, or None without a model).  Every problem is a ValueError of one line: a number
+    without its flag, a recogniser that is not the CRNN, --demo_tile, a training run, a width outside 1 .. 32, an order outside
+    1 .. 3, a weight or bonus that is not finite, a missing file, a file without a usable word.  load=False: the file is not read."""
+    import math
+    width, path = getattr(args, "rec_beam", None), getattr(args, "rec_lm", None)
+    order, alpha, beta = (getattr(args, k, None) for k in ("rec_lm_order", "rec_lm_weight", "rec_lm_bonus"))
+    if (order is not None or alpha is not None) and not path:
+        raise ValueError("--rec_lm_order and --rec_lm_weight need --rec_lm FILE: the word list the character model is built from")
+    if width is None and not path:
+        if beta is not None:
+            raise ValueError("--rec_lm_bonus needs --rec_beam or --rec_lm: it is added per symbol of the beam search's prefixes")
+        return None
+    rec = getattr(args, "rec", None)
+    if rec != "crnn":
+        raise ValueError("--rec_beam and --rec_lm need --rec crnn: the beam search runs on the CRNN's frame posteriors; --rec %s has its "
+                         "own decoder" % rec)
+    if getattr(args, "demo_tile", False):
+        raise ValueError("--rec_beam and --rec_lm do not combine with --demo_tile: a line has word boundaries that the CRNN has no class "
+                         "for, so a character model of words cannot weigh it")
+    if not (getattr(args, "test", False) or getattr(args, "demo_dir", None)):
+        raise ValueError("--rec_beam and --rec_lm need --test or --demo_dir: the beam search is used where SR images are read, not in training")
+    width = 16 if width is None else width
+    if isinstance(width, bool) or width != int(width) or not 1 <= int(width) <= 32:
+        raise ValueError("--rec_beam must be an integer 1 .. 32 (the prefixes kept per frame), got %r" % (width,))
+    order = 3 if order is None else order
+    if isinstance(order, bool) or order != int(order) or not 1 <= int(order) <= 3:
+        raise ValueError("--rec_lm_order must be 1 .. 3 (the symbols of an n-gram), got %r" % (order,))
+    alpha, beta = 0.5 if alpha is None else float(alpha), 0.0 if beta is None else float(beta)
+    if not math.isfinite(alpha):
+        raise ValueError("--rec_lm_weight must be a finite number (the weight of the model's log-probabilities)")
+    if not math.isfinite(beta):
+        raise ValueError("--rec_lm_bonus must be a finite number (a log-domain score added per symbol)")
+    words = None
+    if path:
+        if not os.path.isfile(path):
+            raise ValueError("--rec_lm %s is not a file" % path)
+        if load:
+            from dpmn_amd.utils.beam import load_lm_words
+            words = load_lm_words(path, "lower")
+    return {"width": int(width), "order": int(order), "alpha": alpha, "beta": beta, "words": words, "model": bool(path)}
 
 
 def lexicon_accuracies(rows, spaces=True):
@@ -407,6 +454,7 @@ def main(config, args):
     try:
         lex_words = rec_lexicon_setting(args)
         lex_penalty = rec_lexicon_penalty(args)
+        beam_set = rec_beam_setting(args)
     except ValueError as e:
         raise SystemExit("main.py: %s" % e)
     try:
@@ -447,6 +495,18 @@ def main(config, args):
         print("rec_lexicon: %d words, mode %s" % (len(lex_words[0]), lex_words[1]))
         if line_kw:
             lex_kw["lexicon_penalty"] = lex_penalty
+    beam_kw = {}
+    if beam_set is not None:
+        if not callable(getattr(rec, "read_beam", None)):
+            raise SystemExit("main.py: --rec_beam and --rec_lm need the native CRNN, and --rec %s built none (see the line above)" % args.rec)
+        lm = None
+        if beam_set["model"]:
+            from dpmn_amd.ops import CharLM
+            from dpmn_amd.utils.beam import build_char_lm
+            lm = CharLM(build_char_lm(beam_set["words"], beam_set["order"]), beam_set["order"])
+            print("rec_lm: %d words, order %d, weight %g" % (len(beam_set["words"]), beam_set["order"], beam_set["alpha"]))
+        print("rec_beam: width %d, bonus %g per symbol" % (beam_set["width"], beam_set["beta"]))
+        beam_kw = {"beam": {"lm": lm, "width": beam_set["width"], "alpha": beam_set["alpha"], "beta": beam_set["beta"]}}
     if line_kw and not callable(getattr(rec, "read_lines", None)):
         raise SystemExit("main.py: --demo_line_read needs the native CRNN, and --rec %s built none (see the line above)" % args.rec)
     if conf_kw and not callable(getattr(rec, "read_conf", None)):
@@ -490,10 +550,11 @@ def main(config, args):
                 batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device, photos=True)
                 # (--demo_paste_polygons: the polygons too, strip by strip, in box-file order with the quadrilaterals: utils/paste_poly.py)
                 rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, paste=True, feather=feather,
-                                    paste_polygons=bool(getattr(args, "demo_paste_polygons", False)), **lex_kw, **conf_kw, **line_kw)
+                                    paste_polygons=bool(getattr(args, "demo_paste_polygons", False)), **lex_kw, **conf_kw, **line_kw, **beam_kw)
             else:
                 batches = make(args.demo_dir, box_dir, bs, lr_size, mission.mask, mission.device, **({"photos": True} if with_photos else {}))
-                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, **lex_kw, **conf_kw, **line_kw)
+                rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=tile, chunk=bs, boxes=True, **lex_kw, **conf_kw, **line_kw,
+                                    **beam_kw)
             if lex_kw:
                 # (with the confidence columns sr_string is column 5 and the lexicon's word follows sr_conf and turned)
                 lex_rows = [r[:4] + [r[5], r[7 + bool(conf_kw["upright"])]] for r in rows] if conf_kw else rows
@@ -505,7 +566,7 @@ def main(config, args):
                 # the run's regions and reads scored against the ground truth of GTDIR: detect_eval.csv (utils/detect_eval.py)
                 demo_eval(rows, args.demo_dir, box_dir, eval_dir, out_dir, mission.device, recogniser=rec is not None, conf=bool(conf_kw),
                           upright=bool(conf_kw.get("upright")), lexicon=bool(lex_kw), min_conf=conf_kw.get("min_conf") is not None,
-                          spaces=not line_kw)
+                          spaces=not line_kw, lm=bool(beam_kw))
             return
         if getattr(args, "demo_tile", False):
             # wide images keep their aspect ratio: overlapping LR windows per image, one stitched <stem>_sr.png (utils/tile.py)
@@ -515,26 +576,29 @@ def main(config, args):
             rows = mission.demo(models, psn, batches, out_dir, rec=rec, tile=True, chunk=bs, **lex_kw, **conf_kw, **line_kw)
         else:
             batches = folder_batches(args.demo_dir, bs, lr_size, mission.mask, mission.device)
-            rows = mission.demo(models, psn, batches, out_dir, rec=rec, **lex_kw, **conf_kw)
+            rows = mission.demo(models, psn, batches, out_dir, rec=rec, **lex_kw, **conf_kw, **beam_kw)
         print("%d images super-resolved into %s" % (len(rows), out_dir))
         return
     if args.test:
         result_path = os.path.join(config.TRAIN.ckpt_dir, "test_result.csv")
         if rank == 0 and not os.path.exists(result_path):
             with open(result_path, "w+") as out:
-                csv.writer(out).writerow(["recognizer", "subset", "accuracy", "psnr", "ssim"] + (["accuracy_lexicon"] if lex_kw else []))
+                csv.writer(out).writerow(["recognizer", "subset", "accuracy", "psnr", "ssim"] + (["accuracy_lexicon"] if lex_kw else [])
+                                         + (["accuracy_lm"] if beam_kw else []))
         if args.test_data_dir and os.path.isdir(args.test_data_dir):       # a TextZoom LMDB directory (needs the lmdb package)
             from dpmn_amd.dataset.textzoom import sr_batches
             loader = sr_batches(mission.get_test_data(args.test_data_dir)[1], mission.device, mission.mask)
         else:
             loader = synthetic_loader(bs, args.synthetic_steps, 1000 + rank, labels=rec is not None)
-        res = mission.test(loader, rec=rec, display=args.vis_dir is not None and rank == 0, **lex_kw)
+        res = mission.test(loader, rec=rec, display=args.vis_dir is not None and rank == 0, **lex_kw, **beam_kw)
         if rank == 0:
             with open(result_path, "a") as out:
                 csv.writer(out).writerow([args.rec, "synthetic", res["accuracy"], res["psnr_avg"], res["ssim_avg"]]
-                                         + ([res["accuracy_lexicon"]] if lex_kw else []))
+                                         + ([res["accuracy_lexicon"]] if lex_kw else []) + ([res["accuracy_lm"]] if beam_kw else []))
             if lex_kw:
                 print("accuracy_lexicon %s" % res["accuracy_lexicon"])
+            if beam_kw:
+                print("accuracy_lm %s" % res["accuracy_lm"])
             print("psnr %.4f ssim %.4f accuracy %s over %d synthetic batches" % (res["psnr_avg"], res["ssim_avg"], res["accuracy"],
                                                                                 args.synthetic_steps))
     else:
@@ -753,6 +817,20 @@ if __name__ == '__main__':
                         help='with --rec_lexicon: score = the word of the highest CTC likelihood under the frame posteriors (--rec crnn '
                              'only, its default), edit = the word at the least edit distance to the recognised string (any recogniser; '
                              'the default of --rec aster / moran)')
+    parser.add_argument('--rec_beam', type=int, default=None, metavar='W',
+                        help='with --test or --demo_dir and --rec crnn: also read every SR image by a CTC prefix beam search of W (1 .. 32) '
+                             'prefixes over the frame posteriors (utils/beam.py; one HIP launch per batch): --test reports accuracy_lm '
+                             'beside accuracy, --demo_dir writes the columns sr_lm and sr_lm_score; not with --demo_tile')
+    parser.add_argument('--rec_lm', type=str, default=None, metavar='FILE',
+                        help='a character n-gram model for the beam search, built from this word list (one word per line, UTF-8; filtered '
+                             'like --rec_lexicon, but a repeated word counts as often as it is listed); implies --rec_beam 16.  The '
+                             'vocabulary stays open: the model weighs every new symbol, it forbids none')
+    parser.add_argument('--rec_lm_order', type=int, default=None, metavar='N', help='with --rec_lm: the n of the n-gram, 1 .. 3 (default 3)')
+    parser.add_argument('--rec_lm_weight', type=float, default=None, metavar='A',
+                        help='with --rec_lm: the weight of the model\'s log-probabilities in a prefix\'s score (default 0.5, untuned)')
+    parser.add_argument('--rec_lm_bonus', type=float, default=None, metavar='B',
+                        help='with --rec_beam or --rec_lm: a log-domain score added per symbol of a prefix (default 0.0, untuned; positive: '
+                             'longer strings)')
     parser.add_argument('--train_words_fonts', type=str, default=None, metavar='DIR',
                         help='with --train_words: every *.ttf / *.otf of this directory is a font (default: PIL\'s built-in font)')
     parser.add_argument('--train_words_epoch', type=int, default=10000, metavar='N',
@@ -788,6 +866,7 @@ if __name__ == '__main__':
     try:
         rec_lexicon_setting(args, load=False)
         rec_lexicon_penalty(args)
+        rec_beam_setting(args, load=False)
     except ValueError as e:
         parser.error(str(e))
     try:
