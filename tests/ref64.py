@@ -13,7 +13,9 @@ The last part holds the references of the convolution family (tests/test_gpu_con
 gradient, data gradient and the BatchNorm statistics, as loops over the taps with one slice and one matmul / einsum per tap; then the
 window-attention family (tests/test_gpu_attn_family.py): the multi-window shifted-window attention and its hand-written backward, alone
 and behind the LayerNorm + q / kv projections -- roll as torch.roll on the token plane, window partition as a reshape, the region mask
-from the Swin definition's nine labelled slices; from oracle.pgrm only drop_mask (the counter hash of the masks)."""
+from the Swin definition's nine labelled slices; from oracle.pgrm only drop_mask (the counter hash of the masks); and the recogniser
+kernels (tests/test_gpu_recogniser_kernels.py): BiLSTM, the ASTER decoder step and beam search, the MORAN decoder and rectifier, the
+prep resizes, the VisionLAN pooling -- the decoders either free running or replaying a kernel's own decisions."""
 import math
 
 import torch
@@ -778,3 +780,254 @@ def ln_qkv_window_attn_bwd(tq, tkv, ln, tables, windows, shifts, H, W, dout, p_d
     """Its backward twin: (dq, dkv, [dtable_g]) of the recomputed PROJECTED q / kv, not of the tokens"""
     q, kv = ln_qkv(tq, tkv, *ln, eps=eps, dtype=dtype)
     return window_attn_bwd(q, kv, tables, windows, shifts, H, W, dout, p_drop, seed, dtype, parts)
+
+
+# ====================================================================================================================
+# recogniser kernels (csrc/crnn.hip, aster.hip, moran.hip, visionlan.hip; tests/test_gpu_recogniser_kernels.py).  The widths (hidden
+# size, attention width) are read from the operands, so tests/test_ref64.py pins these functions to nn.LSTM / nn.GRUCell / F.grid_sample
+# / F.max_pool2d / F.interpolate / log_softmax + topk at small widths.  `gates`: a list that receives the sigmoid activations of the
+# recurrences (the fixtures' gate-spread assertion).  The decoders that feed discrete decisions back take those decisions as an
+# argument (the REPLAY of a kernel's own ids) or, without it, make them by the documented rule (free running).
+def first_argmax(x):
+    """index of the FIRST maximum along the last axis (the rule of k_moran_decode, k_ctc_greedy, k_vl_decode)"""
+    n = x.shape[-1]
+    at = torch.where(x == x.amax(-1, keepdim=True), torch.arange(n), torch.tensor(n))
+    return at.amin(-1)
+
+
+def bilstm(gx, w_hh, B, T, dtype=torch.float64, gates=None):
+    """Recurrence of a bidirectional one-layer nn.LSTM on precomputed input projections: gx (B T, 8 H), row b T + t, columns [forward
+    i f g o | backward i f g o] (both biases folded), w_hh (2, 4 H, H); h0 = c0 = 0, the backward direction starts at t = T - 1.
+    -> (out (B T, 2 H) = [h_fwd | h_bwd], the cell state of both directions after their last step (2, B, H))"""
+    gx, w_hh = _c(gx, dtype), _c(w_hh, dtype)
+    H = w_hh.shape[2]
+    g = gx.reshape(B, T, 2, 4 * H)
+    out, cst = gx.new_zeros(B, T, 2 * H), gx.new_zeros(2, B, H)
+    for d in range(2):
+        h, c = gx.new_zeros(B, H), gx.new_zeros(B, H)
+        for t in (range(T) if d == 0 else range(T - 1, -1, -1)):
+            a = g[:, t, d] + h @ w_hh[d].t()
+            i, f, o = _sigmoid(a[:, :H]), _sigmoid(a[:, H:2 * H]), _sigmoid(a[:, 3 * H:])
+            c = f * c + i * torch.tanh(a[:, 2 * H:3 * H])
+            h = o * torch.tanh(c)
+            out[:, t, d * H:(d + 1) * H] = h
+            if gates is not None:
+                gates.append(torch.cat([i, f, o]).reshape(-1))
+        cst[d] = c
+    return out.reshape(B * T, 2 * H), cst
+
+
+def gru_cell_table(e, ctx, wih_ctx, h, whh, bhh, gates=None):
+    """nn.GRUCell whose input product is split: e = the embedding half (a row of the table E, b_ih folded) + ctx W_ih_ctx^T;
+    r = sig(i_r + h_r), z = sig(i_z + h_z), n = tanh(i_n + r (W_hn h + b_hn)), h' = (1 - z) n + z h"""
+    D = h.shape[1]
+    gi = e + ctx @ wih_ctx.t()
+    gh = h @ whh.t() + bhh
+    r, z = _sigmoid(gi[:, :D] + gh[:, :D]), _sigmoid(gi[:, D:2 * D] + gh[:, D:2 * D])
+    if gates is not None:
+        gates.append(torch.cat([r, z]).reshape(-1))
+    return (1.0 - z) * torch.tanh(gi[:, 2 * D:] + r * gh[:, 2 * D:]) + z * h
+
+
+def additive_attention(sp, xp, feats, w, b):
+    """e[r, t] = w . tanh(sp[r] + xp[r, t]) + b; alpha = softmax_t e; ctx = sum_t alpha feats[r, t] -> (e, alpha, ctx)"""
+    e = (torch.tanh(xp + sp[:, None]) * w).sum(-1) + b
+    alpha = _softmax(e)
+    return e, alpha, (alpha[:, :, None] * feats).sum(1)
+
+
+def aster_decode_step(w, feats, xproj, row_img, state, y_prev, n_class, dtype=torch.float64, gates=None):
+    """One teacher-forced step of ASTER's attention decoder for R rows; row r attends to image row_img[r].  w: the fields of
+    dpmn_aster_dec_weights (E has a row per class and the BOS row n_class).  -> dict sproj, e, alpha, ctx, state_out, logits"""
+    w = {k: _c(v, dtype) for k, v in w.items()}
+    feats, xproj, state = _c(feats, dtype), _c(xproj, dtype), _c(state, dtype)
+    ri, yp = torch.as_tensor(row_img).long(), torch.as_tensor(y_prev).long()
+    sproj = state @ w["s_w"].t() + w["s_b"]
+    e, alpha, ctx = additive_attention(sproj, xproj[ri], feats[ri], w["w_w"], w["w_b"])
+    snew = gru_cell_table(w["E"][yp], ctx, w["wih_ctx"], state, w["whh"], w["bhh"], gates)
+    return {"sproj": sproj, "e": e, "alpha": alpha, "ctx": ctx, "state_out": snew, "logits": snew @ w["fc_w"][:n_class].t() + w["fc_b"][:n_class]}
+
+
+def beam_select(cand, beam):
+    """cand (B, beam n_class) -> the flat indices of the `beam` best of every image, best first; equal scores: the lower flat index"""
+    return torch.sort(cand, dim=-1, descending=True, stable=True)[1][:, :beam]
+
+
+def aster_beam(w, feats, xproj, beam, n_class, eos, steps, decisions=None, dtype=torch.float64, gates=None):
+    """ASTER's beam search (attention_recognition_head.py:187-268): per step the decoder step of every beam row, log-softmax, sequence
+    score + log-probability, the `beam` best of an image's beam x n_class candidates, EOS erase (the sequence score of a beam that
+    emitted EOS becomes -inf), state reorder.  At step 0 only beam row 0 of an image is live; the first input is the BOS row n_class of E.
+    decisions = (sym, pred) (steps, R) as the kernel stores them (pred = the global predecessor row): the reference takes them instead of
+    choosing.  -> dict sym, pred (steps, R), score (steps, R), cand [(R, n_class) per step], state (R, D), seq (R), ended [(R) bool per step]"""
+    B, R = feats.shape[0], feats.shape[0] * beam
+    row_img = torch.arange(R) // beam
+    fd = _c(feats, dtype)
+    state = fd.new_zeros(R, fd.shape[2])
+    seq = fd.new_full((R,), float("-inf"))
+    seq[::beam] = 0.0
+    yprev = torch.full((R,), n_class, dtype=torch.long)
+    res = {"sym": [], "pred": [], "score": [], "cand": [], "ended": []}
+    for s in range(steps):
+        st = aster_decode_step(w, feats, xproj, row_img, state, yprev, n_class, dtype, gates)
+        x = st["logits"]
+        m = x.amax(-1, keepdim=True)
+        lse = m + torch.log(torch.exp(x - m).sum(-1, keepdim=True))
+        cand = seq[:, None] + (x - lse)
+        if decisions is None:
+            flat = beam_select(cand.reshape(B, beam * n_class), beam)
+            k, c = flat // n_class, flat % n_class
+            pred = (k + torch.arange(B)[:, None] * beam).reshape(R)
+            sym = c.reshape(R)
+        else:
+            sym, pred = decisions[0][s].long(), decisions[1][s].long()
+        score = cand[pred, sym]
+        seq = torch.where(sym == eos, torch.full_like(score, float("-inf")), score)
+        yprev, state = sym, st["state_out"][pred]
+        for key, v in (("sym", sym), ("pred", pred), ("score", score), ("cand", cand), ("ended", sym == eos)):
+            res[key].append(v)
+    for key in ("sym", "pred", "score"):
+        res[key] = torch.stack(res[key])
+    res["state"], res["seq"] = state, seq
+    return res
+
+
+def moran_decode(w, feats, fproj, steps, n_class, ids=None, dtype=torch.float64, gates=None):
+    """MORAN's greedy attention decoder (asrn_res.py:127-144): h0 = 0, first input row 0 of E; per step h2h(h), additive attention over
+    fproj, GRU cell with the table row E[previous id + 1], generator, first-maximum arg-max fed back -- or `ids` (B, steps), the
+    kernel's own decisions.  w: the fields of dpmn_moran_dec_weights.  -> (logits (B, steps, n_class), ids (B, steps))"""
+    w = {k: _c(v, dtype) for k, v in w.items()}
+    feats, fproj = _c(feats, dtype), _c(fproj, dtype)
+    B = feats.shape[0]
+    h = feats.new_zeros(B, feats.shape[2])
+    y = torch.zeros(B, dtype=torch.long)
+    logits, out_ids = [], []
+    for s in range(steps):
+        ps = h @ w["h2h_w"].t() + w["h2h_b"]
+        _, _, ctx = additive_attention(ps, fproj, feats, w["score_w"], 0.0)
+        h = gru_cell_table(w["E"][y], ctx, w["wih_ctx"], h, w["whh"], w["bhh"], gates)
+        lg = h @ w["gen_w"][:n_class].t() + w["gen_b"][:n_class]
+        best = first_argmax(lg) if ids is None else torch.as_tensor(ids)[:, s].long()
+        y = best + 1
+        logits.append(lg)
+        out_ids.append(best)
+    return torch.stack(logits, 1), torch.stack(out_ids, 1)
+
+
+def _pool2x2s1(x):
+    """MaxPool2d(2, 1) of (B, H, W)"""
+    return torch.maximum(torch.maximum(x[:, :-1, :-1], x[:, :-1, 1:]), torch.maximum(x[:, 1:, :-1], x[:, 1:, 1:]))
+
+
+def grid_sample_bilinear(img, cx, cy):
+    """F.grid_sample(bilinear, zeros padding, align_corners=False) of planes img (B, h, w) at normalised coordinates cx, cy (B, H, W):
+    pixel = ((coord + 1) size - 1) / 2, the four neighbours weighted, neighbours outside the plane count as zero"""
+    B, h, w = img.shape
+    fx, fy = ((cx + 1.0) * w - 1.0) / 2.0, ((cy + 1.0) * h - 1.0) / 2.0
+    x0, y0 = torch.floor(fx), torch.floor(fy)
+    out = torch.zeros_like(fx)
+    bi = torch.arange(B)[:, None, None].expand(fx.shape)
+    for dy in (0, 1):
+        for dx in (0, 1):
+            px, py = x0 + dx, y0 + dy
+            wgt = (fx - x0 if dx else (x0 + 1.0) - fx) * (fy - y0 if dy else (y0 + 1.0) - fy)
+            ok = (px >= 0) & (px < w) & (py >= 0) & (py < h)
+            v = img[bi, py.clamp(0, h - 1).long(), px.clamp(0, w - 1).long()]
+            out = out + torch.where(ok, v * wgt, torch.zeros_like(v))
+    return out
+
+
+def moran_rectify(omap, plane, grid_x, grid_y, acc=None, dtype=torch.float64):
+    """One pass of MORN behind its offset head (morn.py:63-82): offsets = pool(relu(o)) - pool(relu(-o)) with MaxPool2d(2, 1) of omap
+    (B, Hm, Wm), sampled on the identity grid (grid_x (W), grid_y (H)), added to the running offsets `acc` (B, H, W); the plane
+    (B, H, W) is then sampled at (grid_x, grid_y + offsets).  -> (accumulated offsets, rectified plane), both (B, H, W)"""
+    o, p, gx, gy, acc = _c(omap, dtype), _c(plane, dtype), _c(grid_x, dtype), _c(grid_y, dtype), _c(acc, dtype)
+    B, H, W = p.shape
+    pooled = _pool2x2s1(o.clamp(min=0.0)) - _pool2x2s1((-o).clamp(min=0.0))
+    cx, cy = gx[None, None, :].expand(B, H, W), gy[None, :, None].expand(B, H, W)
+    off = grid_sample_bilinear(pooled, cx, cy)
+    a = off if acc is None else acc + off
+    return a, grid_sample_bilinear(p, cx, cy + a)
+
+
+def _resize_matrix(n_in, n_out, mode, dtype):
+    """(n_out, n_in) interpolation matrix of one axis.  'bicubic': torch's upsample_bicubic2d, align_corners=False, A = -0.75, source
+    index (dst + 0.5) in / out - 0.5, taps clamped to the plane; 'linear_ac': bilinear with align_corners=True, source dst (in - 1) / (out - 1)"""
+    dst = torch.arange(n_out, dtype=dtype)
+    M = torch.zeros(n_out, n_in, dtype=dtype)
+    rows = torch.arange(n_out)
+    if mode == "bicubic":
+        real = (torch.tensor(float(n_in), dtype=dtype) / n_out) * (dst + 0.5) - 0.5
+        i0 = torch.floor(real)
+        t = real - i0
+        A = -0.75
+        x1, x2 = t + 1.0, 1.0 - t
+        x3 = x2 + 1.0
+        wts = [((A * x1 - 5.0 * A) * x1 + 8.0 * A) * x1 - 4.0 * A, ((A + 2.0) * t - (A + 3.0)) * t * t + 1.0,
+               ((A + 2.0) * x2 - (A + 3.0)) * x2 * x2 + 1.0, ((A * x3 - 5.0 * A) * x3 + 8.0 * A) * x3 - 4.0 * A]
+        for k, wk in enumerate(wts):
+            M.index_put_((rows, (i0.long() - 1 + k).clamp(0, n_in - 1)), wk, accumulate=True)
+        return M
+    scale = torch.tensor(float(n_in - 1), dtype=dtype) / (n_out - 1) if n_out > 1 else torch.tensor(0.0, dtype=dtype)
+    real = scale * dst
+    i0 = real.long().clamp(max=n_in - 1)
+    l1 = real - i0.to(dtype)
+    M.index_put_((rows, i0), 1.0 - l1, accumulate=True)
+    M.index_put_((rows, (i0 + 1).clamp(max=n_in - 1)), l1, accumulate=True)
+    return M
+
+
+def gray_prep(img, Ho, Wo, dtype=torch.float64):
+    """parse_crnn_data / parse_moran_data: bicubic resize of channels 0..2 of img (B, >= 3, H, W) to Ho x Wo, ITU-601 luma -> (B, Ho, Wo)"""
+    x = _c(img, dtype)[:, :3]
+    My, Mx = _resize_matrix(x.shape[2], Ho, "bicubic", dtype), _resize_matrix(x.shape[3], Wo, "bicubic", dtype)
+    v = My @ x @ Mx.t()
+    return (0.299 * v[:, 0] + 0.587 * v[:, 1]) + 0.114 * v[:, 2]
+
+
+def aster_prep(img, Hs, Ws, dtype=torch.float64):
+    """parse_aster_data (x 2 - 1) -> (normalised (B, 3, H, W), its bilinear align_corners=True resize to Hs x Ws as NHWC (B, Hs, Ws, 3))"""
+    x = _c(img, dtype)[:, :3] * 2.0 - 1.0
+    My, Mx = _resize_matrix(x.shape[2], Hs, "linear_ac", dtype), _resize_matrix(x.shape[3], Ws, "linear_ac", dtype)
+    return x, (My @ x @ Mx.t()).permute(0, 2, 3, 1)
+
+
+def vl_pp_pool(scores, enc, w_vrm, b_vrm, n_steps, dtype=torch.float64):
+    """PP_layer + Prediction of VisionLAN: scores (B, L, ld >= n_steps), enc (B, L, C): p = softmax over the positions of scores[b, :, n],
+    g = sum_l p_l enc[b, l], logits[b, n] = g W^T + bias -> (B, n_steps, n_class)"""
+    s, enc, wv, bv = _c(scores, dtype), _c(enc, dtype), _c(w_vrm, dtype), _c(b_vrm, dtype)
+    p = _softmax(s[:, :, :n_steps].transpose(1, 2))
+    return (p @ enc) @ wv.t() + bv
+
+
+def crnn_label_vecs(logits, n_class, B, T, dtype=torch.float64):
+    """softmax over the first n_class columns of the rows b T + t of logits (B T, ld) -> (B, n_class, 1, T)"""
+    p = _softmax(_c(logits, dtype)[:, :n_class])
+    return p.reshape(B, T, n_class).permute(0, 2, 1).reshape(B, n_class, 1, T)
+
+
+def ctc_greedy(logits, n_class, B, T):
+    """strLabelConverter.decode(raw=False) after the first-maximum arg-max: repeats collapsed, blanks (class 0) dropped
+    -> (cls (B, T) padded with 0, length (B))"""
+    best = first_argmax(torch.as_tensor(logits)[:, :n_class]).reshape(B, T).tolist()
+    cls, length = torch.zeros(B, T, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)
+    for b in range(B):
+        n, prev = 0, -1
+        for c in best[b]:
+            if c != 0 and c != prev:
+                cls[b, n] = c
+                n += 1
+            prev = c
+        length[b] = n
+    return cls, length
+
+
+def vl_decode(logits, max_len):
+    """MLM_VRM.forward 107-126: first-maximum arg-max of the first max_len steps of logits (B, n_steps, n_class); length = the first
+    step that reads class 0, + 1, else max_len -> (cls (B, max_len), length (B))"""
+    cls = first_argmax(torch.as_tensor(logits)[:, :max_len]).to(torch.int32)
+    length = torch.full((cls.shape[0],), max_len, dtype=torch.int32)
+    for b in range(cls.shape[0]):
+        hit = (cls[b] == 0).nonzero()
+        if hit.numel():
+            length[b] = int(hit[0]) + 1
+    return cls, length

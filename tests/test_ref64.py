@@ -547,3 +547,173 @@ def test_window_attn_fp32_evaluation():
     g32 = ref64.window_attn_bwd(q, kv, tables, windows, shifts, H, W, o64, 0.3, 5, dtype=torch.float32)
     g64 = ref64.window_attn_bwd(q, kv, tables, windows, shifts, H, W, o64, 0.3, 5)
     assert all(a.dtype == torch.float32 and float((a.double() - b).abs().max()) < 1e-5 for a, b in zip((g32[0], g32[1], *g32[2]), (g64[0], g64[1], *g64[2])))
+
+
+# ------------------------------------------------------------------------------------------------------------------ recogniser kernels
+def _grucell(I, D, tag):
+    cell = torch.nn.GRUCell(I, D).double()
+    sd = {k: u(tag + k, v.shape, -0.5, 0.5) for k, v in cell.state_dict().items()}
+    cell.load_state_dict(sd)
+    return cell, sd
+
+
+@pytest.mark.parametrize("B,T", [(1, 1), (3, 4), (2, 7)])
+def test_bilstm_vs_nn_lstm(B, T):
+    H, I = 8, 5
+    lstm = torch.nn.LSTM(I, H, bidirectional=True, batch_first=True).double()
+    sd = {k: u(k, v.shape, -0.5, 0.5) for k, v in lstm.state_dict().items()}
+    lstm.load_state_dict(sd)
+    x = u("lstm_x", (B, T, I), -2, 2)
+    gx = torch.cat([F.linear(x, sd["weight_ih_l0" + s], sd["bias_ih_l0" + s] + sd["bias_hh_l0" + s]) for s in ("", "_reverse")], -1)
+    with torch.no_grad():
+        ref, (_, cn) = lstm(x)
+    out, cst = ref64.bilstm(gx.reshape(B * T, 8 * H), torch.stack([sd["weight_hh_l0"], sd["weight_hh_l0_reverse"]]), B, T)
+    close(out, ref.reshape(B * T, 2 * H), "bilstm out")
+    close(cst, cn, "bilstm cell state")
+
+
+def test_gru_cell_table_vs_nn_grucell():
+    D, Ie, n = 8, 6, 5
+    cell, sd = _grucell(Ie + D, D, "gct")
+    table, ctx, h = u("gct_tab", (n, Ie)), u("gct_ctx", (4, D)), u("gct_h", (4, D))
+    y = torch.tensor([0, 4, 2, 4])
+    E = F.linear(table, sd["weight_ih"][:, :Ie], sd["bias_ih"])
+    with torch.no_grad():
+        ref = cell(torch.cat([table[y], ctx], 1), h)
+    close(ref64.gru_cell_table(E[y], ctx, sd["weight_ih"][:, Ie:], h, sd["weight_hh"], sd["bias_hh"]), ref, "gru_cell_table")
+
+
+def _aster_small(D=8, n_class=6, B=3, T=4, tag="as"):
+    cell, sd = _grucell(2 * D, D, tag)
+    emb = u(tag + "emb", (n_class + 1, D))
+    w = {"s_w": u(tag + "s_w", (D, D)), "s_b": u(tag + "s_b", (D,)), "w_w": u(tag + "w_w", (D,), -2, 2), "w_b": u(tag + "w_b", (1,)),
+         "E": F.linear(emb, sd["weight_ih"][:, :D], sd["bias_ih"]), "wih_ctx": sd["weight_ih"][:, D:], "whh": sd["weight_hh"],
+         "bhh": sd["bias_hh"], "fc_w": u(tag + "fc_w", (n_class, D), -3, 3), "fc_b": u(tag + "fc_b", (n_class,))}
+    return cell, emb, w, u(tag + "feats", (B, T, D)), u(tag + "xproj", (B, T, D))
+
+
+def _aster_stock_step(cell, emb, w, feats, xproj, row_img, state, y_prev):
+    """the same step from nn.GRUCell, F.linear and F.softmax"""
+    sproj = F.linear(state, w["s_w"], w["s_b"])
+    e = F.linear(torch.tanh(sproj[:, None] + xproj[row_img]), w["w_w"][None], w["w_b"]).squeeze(-1)
+    alpha = F.softmax(e, -1)
+    ctx = torch.bmm(alpha[:, None], feats[row_img]).squeeze(1)
+    with torch.no_grad():
+        snew = cell(torch.cat([emb[y_prev], ctx], 1), state)
+    return sproj, alpha, ctx, snew, F.linear(snew, w["fc_w"], w["fc_b"])
+
+
+def test_aster_decode_step_vs_stock():
+    cell, emb, w, feats, xproj = _aster_small()
+    row_img, y_prev, state = torch.tensor([2, 0, 0, 1, 2]), torch.tensor([0, 6, 3, 5, 6]), u("as_state", (5, 8))
+    got = ref64.aster_decode_step(w, feats, xproj, row_img, state, y_prev, 6)
+    for name, ref in zip(("sproj", "alpha", "ctx", "state_out", "logits"), _aster_stock_step(cell, emb, w, feats, xproj, row_img, state, y_prev)):
+        close(got[name], ref, "aster_decode_step " + name)
+
+
+@pytest.mark.parametrize("beam,eos", [(1, 0), (3, 2)])
+def test_aster_beam_vs_log_softmax_topk(beam, eos):
+    n_class, steps = 6, 4
+    cell, emb, w, feats, xproj = _aster_small()
+    B, R = feats.shape[0], feats.shape[0] * beam
+    got = ref64.aster_beam(w, feats, xproj, beam, n_class, eos, steps)
+    state, yprev = torch.zeros(R, 8, dtype=torch.float64), torch.full((R,), n_class)
+    seq = torch.full((B, beam), float("-inf"), dtype=torch.float64)
+    seq[:, 0] = 0.0
+    for s in range(steps):
+        snew, logits = _aster_stock_step(cell, emb, w, feats, xproj, torch.arange(R) // beam, state, yprev)[3:]
+        cand = (seq[:, :, None] + F.log_softmax(logits, -1).reshape(B, beam, n_class)).reshape(B, beam * n_class)
+        top, flat = cand.topk(beam, -1)
+        finite = torch.isfinite(top)
+        gap = (top[:, :-1] - top[:, 1:])[finite[:, 1:]]
+        assert gap.numel() == 0 or float(gap.min()) > 1e-6      # no near-ties among the finite ones: topk's order is the documented one
+        pred, sym = (flat // n_class + torch.arange(B)[:, None] * beam).reshape(R), (flat % n_class).reshape(R)
+        ok = finite.reshape(R)      # among -inf candidates topk's order is unspecified: the values are still pinned
+        assert torch.equal(got["sym"][s][ok], sym[ok]) and torch.equal(got["pred"][s][ok], pred[ok]), "beam step %d" % s
+        assert torch.equal(torch.isfinite(got["score"][s]), ok)
+        close(got["score"][s][ok], top.reshape(R)[ok], "beam score step %d" % s)
+        sym, pred = got["sym"][s], got["pred"][s]
+        seq = torch.where(sym == eos, torch.tensor(float("-inf"), dtype=torch.float64), got["score"][s]).reshape(B, beam)
+        state, yprev = snew[pred], sym
+    close(got["state"], state, "beam final state")
+    # the replay of its own decisions is the same computation
+    again = ref64.aster_beam(w, feats, xproj, beam, n_class, eos, steps, decisions=(got["sym"], got["pred"]))
+    assert torch.equal(again["score"], got["score"]) and torch.equal(again["state"], got["state"])
+
+
+def test_beam_select_ties_take_the_lower_flat_index():
+    cand = torch.tensor([[1.0, 3.0, 3.0, 2.0, 3.0, float("-inf")], [float("-inf")] * 6], dtype=torch.float64)
+    assert ref64.beam_select(cand, 4).tolist() == [[1, 2, 4, 3], [0, 1, 2, 3]]
+    assert ref64.first_argmax(torch.tensor([[1.0, 5.0, 5.0], [2.0, 2.0, 2.0]])).tolist() == [1, 0]
+
+
+def test_moran_decode_vs_stock():
+    D, n_class, B, T, steps = 8, 5, 3, 4, 6
+    cell, sd = _grucell(2 * D, D, "mo")          # MORAN's order: [context | embedding]
+    emb = u("mo_emb", (n_class + 1, D))
+    w = {"h2h_w": u("mo_h2h", (D, D)), "h2h_b": u("mo_h2hb", (D,)), "score_w": u("mo_sc", (D,), -2, 2),
+         "E": F.linear(emb, sd["weight_ih"][:, D:], sd["bias_ih"]), "wih_ctx": sd["weight_ih"][:, :D], "whh": sd["weight_hh"],
+         "bhh": sd["bias_hh"], "gen_w": u("mo_gen", (n_class, D), -3, 3), "gen_b": u("mo_genb", (n_class,))}
+    feats, fproj = u("mo_feats", (B, T, D)), u("mo_fproj", (B, T, D))
+    logits, ids = ref64.moran_decode(w, feats, fproj, steps, n_class)
+    h, y = torch.zeros(B, D, dtype=torch.float64), torch.zeros(B, dtype=torch.long)
+    for s in range(steps):
+        alpha = F.softmax(F.linear(torch.tanh(fproj + F.linear(h, w["h2h_w"], w["h2h_b"])[:, None]), w["score_w"][None]).squeeze(-1), -1)
+        with torch.no_grad():
+            h = cell(torch.cat([torch.bmm(alpha[:, None], feats).squeeze(1), emb[y]], 1), h)
+        lg = F.linear(h, w["gen_w"], w["gen_b"])
+        top2 = lg.topk(2, -1)[0]
+        assert float((top2[:, 0] - top2[:, 1]).min()) > 1e-6
+        close(logits[:, s], lg, "moran logits step %d" % s)
+        assert torch.equal(ids[:, s], lg.argmax(-1))
+        y = ids[:, s] + 1
+    again, ids2 = ref64.moran_decode(w, feats, fproj, steps, n_class, ids=ids)
+    assert torch.equal(again, logits) and torch.equal(ids2, ids)
+    forced = (ids + 1) % n_class          # a replay follows the ids it is given, not its own arg-max
+    assert torch.equal(ref64.moran_decode(w, feats, fproj, steps, n_class, ids=forced)[1], forced)
+
+
+@pytest.mark.parametrize("H,W,Hm,Wm", [(3, 5, 2, 2), (7, 9, 2, 5), (6, 4, 5, 3)])
+@pytest.mark.parametrize("with_acc", [False, True])
+def test_moran_rectify_vs_grid_sample(H, W, Hm, Wm, with_acc):
+    B = 2
+    omap, plane = u("mr_o", (B, Hm, Wm), -1.5, 1.5), u("mr_p", (B, H, W))
+    gx, gy = torch.linspace(-1.2, 1.1, W, dtype=torch.float64), torch.linspace(-1.0, 1.3, H, dtype=torch.float64)
+    acc = u("mr_acc", (B, H, W), -0.6, 0.6) if with_acc else None
+    o4 = omap[:, None]
+    pooled = F.max_pool2d(F.relu(o4), 2, 1) - F.max_pool2d(F.relu(-o4), 2, 1)
+    grid = torch.stack([gx[None, None, :].expand(B, H, W), gy[None, :, None].expand(B, H, W)], -1)
+    off = F.grid_sample(pooled, grid, mode="bilinear", padding_mode="zeros", align_corners=False)[:, 0]
+    a = off if acc is None else acc + off
+    moved = torch.stack([grid[..., 0], grid[..., 1] + a], -1)
+    rect = F.grid_sample(plane[:, None], moved, mode="bilinear", padding_mode="zeros", align_corners=False)[:, 0]
+    got_a, got_r = ref64.moran_rectify(omap, plane, gx, gy, acc)
+    close(got_a, a, "moran_rectify offsets")
+    close(got_r, rect, "moran_rectify plane")
+
+
+@pytest.mark.parametrize("H,W,Ho,Wo", [(1, 1, 2, 3), (3, 5, 32, 100), (37, 141, 32, 100), (4, 6, 1, 1), (9, 7, 32, 64)])
+def test_prep_vs_interpolate(H, W, Ho, Wo):
+    img = u("prep_img", (2, 3, H, W), 0.0, 1.0)
+    v = F.interpolate(img, (Ho, Wo), mode="bicubic", align_corners=False)
+    close(ref64.gray_prep(img, Ho, Wo), 0.299 * v[:, 0] + 0.587 * v[:, 1] + 0.114 * v[:, 2], "gray_prep")
+    norm, stn = ref64.aster_prep(img, Ho, Wo)
+    close(norm, img * 2 - 1, "aster_prep norm")
+    close(stn, F.interpolate(img * 2 - 1, (Ho, Wo), mode="bilinear", align_corners=True).permute(0, 2, 3, 1).contiguous(), "aster_prep stn")
+
+
+def test_vl_pp_pool_and_label_vecs_vs_softmax():
+    B, L, C, n_steps, ld, n_class = 2, 7, 6, 3, 5, 4
+    scores, enc, wv, bv = u("pp_s", (B, L, ld), -3, 3), u("pp_e", (B, L, C)), u("pp_w", (n_class, C)), u("pp_b", (n_class,))
+    p = F.softmax(scores[:, :, :n_steps], 1)
+    close(ref64.vl_pp_pool(scores, enc, wv, bv, n_steps), F.linear(torch.einsum("bln,blc->bnc", p, enc), wv, bv), "vl_pp_pool")
+    lg = u("lv", (B * L, ld), -3, 3)
+    close(ref64.crnn_label_vecs(lg, n_class, B, L), F.softmax(lg[:, :n_class], -1).reshape(B, L, n_class).permute(0, 2, 1)[:, :, None].contiguous(), "label_vecs")
+
+
+def test_ctc_greedy_and_vl_decode_rules():
+    oh = lambda ids, n: F.one_hot(torch.tensor(ids), n).double()
+    cls, length = ref64.ctc_greedy(oh([0, 2, 2, 0, 2, 3, 3, 0], 4), 4, 2, 4)
+    assert cls.tolist() == [[2, 0, 0, 0], [2, 3, 0, 0]] and length.tolist() == [1, 2]
+    cls, length = ref64.vl_decode(oh([[1, 0, 2, 0], [1, 2, 3, 0]], 4), 3)
+    assert cls.tolist() == [[1, 0, 2], [1, 2, 3]] and length.tolist() == [2, 3]
