@@ -8,6 +8,8 @@
 //                     9 taps are read from there; the histogram is counted in LDS and added to the photo's 256 counters.
 //   k_detect_hsmooth  g >= T and the run-length smoothing of the rows: per row of the tile the 3 words x0 - 64 .. x0 + 128 in LDS; a
 //                     pixel finds its nearest foreground on either side with clz / ffs on two shifted words (gap <= 64).
+//   k_detect_cell_otsu, k_detect_hsmooth_local  (the locally adaptive threshold, off by default) Otsu's threshold per cell of the working
+//                     map, found on the device, and k_detect_hsmooth against the threshold map interpolated between the cell centres.
 //   k_detect_vsmooth  the same down the columns: the words of the rows y0 - vgap .. y0 + 16 + vgap in LDS, a lane walks its bit up and
 //                     down at most vgap words.  Also the initial label: the least index of the pixel's run inside its word.
 //   k_detect_union    label equivalence: neighbours are united by atomicMin on roots.  One pass over the edges.
@@ -110,6 +112,25 @@ k_detect_grad(const unsigned char* __restrict__ packed, long packed_bytes, const
   if (sHist[tid]) atomicAdd(&hist[(size_t)t.b * 256 + tid], sHist[tid]);
 }
 
+// The run-length smoothing of the rows of a tile from the words of its ballots (sW[row] = the words at x0 - 64, x0, x0 + 64), shared by
+// the two kernels that threshold.
+__device__ inline void detect_smooth_rows(const u64 (*sW)[3], const DetTile& t, int lane, int wave, int gap, unsigned char* __restrict__ out) {
+  const int x = t.x0 + lane;
+  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
+    const int ly = wave * DT_WAVE_ROWS + k, y = t.y0 + ly;
+    if (x >= t.wm || y >= t.hm) continue;
+    const u64 w0 = sW[ly][0], w1 = sW[ly][1], w2 = sW[ly][2];
+    bool f = (w1 >> lane) & 1;
+    if (!f) {
+      // Lm: bit 63 is the pixel at x - 1, bit 63 - i the one at x - 1 - i; Rm: bit 0 is the pixel at x + 1, bit i the one at x + 1 + i
+      const u64 Lm = (lane ? w1 << (64 - lane) : 0ull) | (w0 >> lane);
+      const u64 Rm = ((w1 >> lane) >> 1) | (w2 << (63 - lane));
+      if (Lm && Rm) f = __clzll((long long)Lm) + __ffsll((long long)Rm) <= gap;      // dl + dr - 1, dl = clz + 1, dr = ffs
+    }
+    out[t.map_off + (size_t)y * t.wm + x] = f ? 1 : 0;
+  }
+}
+
 __global__ void __launch_bounds__(DT_THREADS)
 k_detect_hsmooth(const unsigned char* __restrict__ g, long map_px, const long long* __restrict__ items, int B, const int* __restrict__ tiles,
                  const int* __restrict__ thresholds, int gap, unsigned char* __restrict__ out) {
@@ -126,20 +147,185 @@ k_detect_hsmooth(const unsigned char* __restrict__ g, long map_px, const long lo
     if (lane == 0) sW[ly][k] = m;
   }
   __syncthreads();
-  const int x = t.x0 + lane;
-  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
-    const int ly = wave * DT_WAVE_ROWS + k, y = t.y0 + ly;
-    if (x >= t.wm || y >= t.hm) continue;
-    const u64 w0 = sW[ly][0], w1 = sW[ly][1], w2 = sW[ly][2];
-    bool f = (w1 >> lane) & 1;
-    if (!f) {
-      // Lm: bit 63 is the pixel at x - 1, bit 63 - i the one at x - 1 - i; Rm: bit 0 is the pixel at x + 1, bit i the one at x + 1 + i
-      const u64 Lm = (lane ? w1 << (64 - lane) : 0ull) | (w0 >> lane);
-      const u64 Rm = ((w1 >> lane) >> 1) | (w2 << (63 - lane));
-      if (Lm && Rm) f = __clzll((long long)Lm) + __ffsll((long long)Rm) <= gap;      // dl + dr - 1, dl = clz + 1, dr = ffs
+  detect_smooth_rows(sW, t, lane, wave, gap, out);
+}
+
+// ---- the locally adaptive threshold (utils/detect.py, local = C): one Otsu threshold per cell of the working map, bilinear between the
+// cell centres.  Per axis of `size` pixels n = ceil(size / C) cells with the edges e_i = i * size / n; a photo's ny * nx thresholds lie
+// at word 7 of its item in one int32 table of n_cells entries, photo after photo in the order of the items.
+
+__host__ __device__ inline int detect_cells(int size, int C) { return (size + C - 1) / C; }
+
+// Word 7 of an item against the table: false unless the photo's cells lie inside it.
+__host__ __device__ inline bool detect_cells_ok(const long long* p, int C, long n_cells) {
+  const long long at = p[7], n = (long long)detect_cells((int)p[4], C) * detect_cells((int)p[5], C);
+  return at >= 0 && at <= n_cells - n;
+}
+
+// One pixel of one axis: the two cells k and k1 around it and their weights, w0 + w1 = D <= size <= 1024 (D = e_{k+2} - e_k).
+struct DetAxis {
+  int k, k1, w0, w1;
+};
+
+__device__ inline DetAxis detect_axis(int x, int size, int C) {
+  const int n = detect_cells(size, C);
+  DetAxis a = {0, 0, 1, 0};
+  if (n < 2 || x < 0 || x >= size) return a;
+  const int j = ((x + 1) * n - 1) / size;                                  // the pixel's own cell: e_j <= x < e_{j+1}
+  const int p = 2 * x + 1, cj = j * size / n + (j + 1) * size / n;       // doubled: the pixel's centre and the cell's
+  const int k = min(max(p >= cj ? j : j - 1, 0), n - 2);                  // the greatest k with c_k <= p, capped
+  const int ck = k * size / n + (k + 1) * size / n, ck1 = (k + 1) * size / n + (k + 2) * size / n;
+  const int q = min(max(p, ck), ck1);                                      // (outside the outermost centres: their own value)
+  a.k = k; a.k1 = k + 1; a.w0 = ck1 - q; a.w1 = q - ck;
+  return a;
+}
+
+// T(y, x) = (2 sum of the four w_y w_x t + Dy Dx) / (2 Dy Dx), rounded half up.  t <= 255 and D <= 1024 per axis, so the numerator is
+// at most 511 * 2^20 < 2^31: 32-bit arithmetic is exact.
+__device__ inline int detect_local_T(const int* __restrict__ cell, int nx, const DetAxis& ay, const DetAxis& ax) {
+  const int* r0 = cell + ay.k * nx;
+  const int* r1 = cell + ay.k1 * nx;
+  const int s = ay.w0 * (ax.w0 * r0[ax.k] + ax.w1 * r0[ax.k1]) + ay.w1 * (ax.w0 * r1[ax.k] + ax.w1 * r1[ax.k1]);
+  const int dd = (ay.w0 + ay.w1) * (ax.w0 + ax.w1);
+  return (int)((unsigned)(2 * s + dd) / (unsigned)(2 * dd));
+}
+
+// k_detect_hsmooth with every pixel compared against its own T(y, x), the halo words at x0 - 64 and x0 + 64 included: the weights of the
+// tile's 192 columns and 16 rows are worked out once per block into LDS, the four cell thresholds of a pixel come from the photo's
+// table.  tmap (may be null; for tests): T of the tile's own pixels, int32 (map_px).
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_hsmooth_local(const unsigned char* __restrict__ g, long map_px, const long long* __restrict__ items, int B,
+                       const int* __restrict__ tiles, const int* __restrict__ table, long n_cells, int C, int gap,
+                       unsigned char* __restrict__ out, int* __restrict__ tmap) {
+  __shared__ u64 sW[DT_H][3];
+  __shared__ DetAxis sX[3 * DT_W], sY[DT_H];
+  DetTile t;
+  if (!detect_tile(items, B, tiles, -1, map_px, t)) return;
+  const long long* item = items + (size_t)t.b * DETECT_ITEM_WORDS;
+  if (!detect_cells_ok(item, C, n_cells)) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int* cell = table + item[7];
+  const int nx = detect_cells(t.wm, C);
+  if (tid < 3 * DT_W) sX[tid] = detect_axis(t.x0 - DT_W + tid, t.wm, C);
+  else if (tid < 3 * DT_W + DT_H) sY[tid - 3 * DT_W] = detect_axis(t.y0 + tid - 3 * DT_W, t.hm, C);
+  __syncthreads();
+  const unsigned char* src = g + t.map_off;
+  for (int i = wave; i < DT_H * 3; i += DT_WAVES) {
+    const int ly = i / 3, k = i - ly * 3, y = t.y0 + ly, x = t.x0 + (k - 1) * DT_W + lane;
+    bool f = false;
+    if (y < t.hm && x >= 0 && x < t.wm) {
+      const int T = detect_local_T(cell, nx, sY[ly], sX[k * DT_W + lane]);
+      f = (int)src[(size_t)y * t.wm + x] >= T;
+      if (tmap && k == 1) tmap[t.map_off + (size_t)y * t.wm + x] = T;
     }
-    out[t.map_off + (size_t)y * t.wm + x] = f ? 1 : 0;
+    const u64 m = __ballot(f);
+    if (lane == 0) sW[ly][k] = m;
   }
+  __syncthreads();
+  detect_smooth_rows(sW, t, lane, wave, gap, out);
+}
+
+// One block per (photo, cell): the histogram of g over the cell in LDS (a copy per wave, so that a flat cell does not serialise the whole
+// block on one counter), then wave 0 finds Otsu's t -> table[cell] = max(t + 1, floor).  The block finds its photo from word 7 of the
+// items, which the entry point checked to be the running sum of the photos' cell counts (16 halvings: B <= 65535).
+// The comparison is utils.detect.otsu's, exact: candidate (a, b) = ((S0 N - S N0)^2, N0 N1) beats (num, den) when a den > num b.  With
+// N <= 2^20 pixels of at most 255: S < 2^28, |S0 N - S N0| < 2^48, a < 2^96, b < 2^40, and a product a * b' < 2^136 does not fit 128
+// bits.  It is held in three limbs: a = ah 2^64 + al (ah < 2^32), a b' = (ah b' + (al b' >> 64)) 2^64 + (al b' mod 2^64), the upper
+// part below 2^73, so unsigned __int128 holds each part and two products compare part by part.  No floating point.
+typedef unsigned __int128 u128;
+
+struct DetProduct {
+  u128 hi;
+  u64 lo;
+};
+
+__device__ inline DetProduct detect_mul(u128 a, u64 b) {
+  const u128 low = (u128)(u64)a * b;
+  DetProduct p = {(u128)(u64)(a >> 64) * b + (low >> 64), (u64)low};
+  return p;
+}
+
+// a den > num b
+__device__ inline bool detect_ratio_gt(u128 a, u64 b, u128 num, u64 den) {
+  const DetProduct l = detect_mul(a, den), r = detect_mul(num, b);
+  return l.hi > r.hi || (l.hi == r.hi && l.lo > r.lo);
+}
+
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_cell_otsu(const unsigned char* __restrict__ g, long map_px, const long long* __restrict__ items, int B, int C, int floor_,
+                   int* __restrict__ table, long n_cells) {
+  __shared__ unsigned sH[DT_WAVES][256];
+  const long idx = (long)blockIdx.x;
+  if (idx >= n_cells) return;
+  int b = 0;
+  for (int step = 1 << 15; step; step >>= 1)      // the greatest photo whose first cell is not past this one
+    if (b + step < B && items[(size_t)(b + step) * DETECT_ITEM_WORDS + 7] <= idx) b += step;
+  const long long* item = items + (size_t)b * DETECT_ITEM_WORDS;
+  if (!detect_item_ok(item, -1, map_px) || !detect_cells_ok(item, C, n_cells)) return;
+  const int hm = (int)item[4], wm = (int)item[5], ny = detect_cells(hm, C), nx = detect_cells(wm, C);
+  const long long rel = idx - item[7];
+  if (rel < 0 || rel >= (long long)ny * nx) return;
+  const int cy = (int)(rel / nx), cx = (int)(rel - (long long)cy * nx);
+  const int y0 = cy * hm / ny, y1 = (cy + 1) * hm / ny, x0 = cx * wm / nx, x1 = (cx + 1) * wm / nx;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int w = 0; w < DT_WAVES; ++w) sH[w][tid] = 0;
+  __syncthreads();
+  const unsigned char* src = g + item[3];
+  for (int y = y0 + wave; y < y1; y += DT_WAVES)      // a wave per row, a lane per column: every read stays inside the cell
+    for (int x = x0 + lane; x < x1; x += 64) atomicAdd(&sH[wave][src[(size_t)y * wm + x]], 1u);
+  __syncthreads();
+  if (wave) return;
+  // lane l owns the bins 4 l .. 4 l + 3; N0 and S0 before its first bin come from a prefix sum over the wave
+  unsigned h[4], n = 0, s = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    h[j] = sH[0][4 * lane + j] + sH[1][4 * lane + j] + sH[2][4 * lane + j] + sH[3][4 * lane + j];
+    n += h[j];
+    s += (unsigned)(4 * lane + j) * h[j];
+  }
+  unsigned pn = n, ps = s;      // inclusive
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned un = __shfl_up(pn, d), us = __shfl_up(ps, d);
+    if (lane >= d) {
+      pn += un;
+      ps += us;
+    }
+  }
+  const long long N = __shfl(pn, 63), S = __shfl(ps, 63);
+  long long N0 = pn - n, S0 = ps - s;
+  int best = 0;
+  u128 num = 0;
+  u64 den = 1;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    N0 += h[j];
+    S0 += (long long)(4 * lane + j) * h[j];
+    const long long N1 = N - N0;
+    if (N0 == 0 || N1 == 0) continue;
+    const long long d = S0 * N - S * N0;
+    const u64 ad = (u64)(d < 0 ? -d : d), bb = (u64)N0 * (u64)N1;
+    const u128 a = (u128)ad * ad;
+    if (detect_ratio_gt(a, bb, num, den)) {
+      best = 4 * lane + j;
+      num = a;
+      den = bb;
+    }
+  }
+  // the greatest ratio of the wave, the earliest t on a tie (a lane without a candidate holds 0 / 1 at t = 0, which is otsu's start)
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const int ot = __shfl_xor(best, d);
+    const u64 nl = __shfl_xor((u64)num, d), nh = __shfl_xor((u64)(num >> 64), d), od = __shfl_xor(den, d);
+    const u128 on = ((u128)nh << 64) | nl;
+    const bool gt = detect_ratio_gt(on, od, num, den), lt = detect_ratio_gt(num, den, on, od);
+    if (gt || (!lt && ot < best)) {
+      best = ot;
+      num = on;
+      den = od;
+    }
+  }
+  if (lane == 0) table[idx] = max(best + 1, floor_);
 }
 
 __global__ void __launch_bounds__(DT_THREADS)
@@ -453,6 +639,53 @@ int dpmn_detect_label_i32(const unsigned char* g, long map_px, const long long* 
   DPMN_REQUIRE(detect_check(items_host, B, -1, map_px), "detect_label: a working map does not fit the buffers or is not its photo's");
   const dim3 grid((unsigned)n_tiles), block(DT_THREADS);
   hipLaunchKernelGGL(k_detect_hsmooth, grid, block, 0, as_stream(stream), g, map_px, items, B, tiles, thresholds, gap, tmp);
+  DPMN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_detect_vsmooth, grid, block, 0, as_stream(stream), (const unsigned char*)tmp, map_px, items, B, tiles, vgap, smooth, labels);
+  DPMN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_detect_union, grid, block, 0, as_stream(stream), (const unsigned char*)smooth, labels, map_px, items, B, tiles);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+// Word 7 of every item is the running sum of the photos' cell counts and the sums end at n_cells: the table has exactly one owner per
+// entry, and k_detect_cell_otsu may look a cell's photo up by halving.
+static int detect_cells_check(const long long* items_host, int B, int C, long n_cells) {
+  long long at = 0;
+  for (int b = 0; b < B; ++b) {
+    const long long* p = items_host + (size_t)b * DETECT_ITEM_WORDS;
+    if (p[7] != at) return 0;
+    at += (long long)detect_cells((int)p[4], C) * detect_cells((int)p[5], C);
+  }
+  return at == n_cells;
+}
+
+int dpmn_detect_cell_otsu_i32(const unsigned char* g, long map_px, const long long* items, const long long* items_host, int B, int cell,
+                              int floor, int* table, long n_cells, dpmn_stream_t stream) {
+  DPMN_REQUIRE(items && items_host, "detect_cell_otsu: null pointer");
+  DPMN_REQUIRE(B > 0 && B <= 65535 && map_px >= 0 && n_cells >= 0 && n_cells <= 0x7fffffffL, "detect_cell_otsu: bad sizes");
+  DPMN_REQUIRE(cell >= 32 && cell <= DETECT_MAP_SIDE && floor >= 1 && floor <= 255, "detect_cell_otsu: the cell side must be 32 .. 1024 and the floor 1 .. 255");
+  DPMN_REQUIRE(detect_check(items_host, B, -1, map_px), "detect_cell_otsu: a working map does not fit the buffers or is not its photo's");
+  DPMN_REQUIRE(detect_cells_check(items_host, B, cell, n_cells), "detect_cell_otsu: the items' cell offsets are not the running sum of their cell counts");
+  if (n_cells == 0) return DPMN_OK;
+  DPMN_REQUIRE(g && table && map_px > 0, "detect_cell_otsu: null pointer");
+  hipLaunchKernelGGL(k_detect_cell_otsu, dim3((unsigned)n_cells), dim3(DT_THREADS), 0, as_stream(stream), g, map_px, items, B, cell, floor, table,
+                     n_cells);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+int dpmn_detect_label_local_i32(const unsigned char* g, long map_px, const long long* items, const long long* items_host, int B,
+                                const int* tiles, int n_tiles, const int* table, long n_cells, int cell, int gap, int vgap, unsigned char* tmp,
+                                unsigned char* smooth, int* labels, int* tmap, dpmn_stream_t stream) {
+  if (n_tiles == 0) return DPMN_OK;
+  DPMN_REQUIRE(g && items && items_host && tiles && table && tmp && smooth && labels, "detect_label_local: null pointer");
+  DPMN_REQUIRE(B > 0 && B <= 65535 && n_tiles > 0 && map_px > 0 && n_cells > 0, "detect_label_local: bad sizes");
+  DPMN_REQUIRE(gap >= 1 && gap <= DETECT_MAX_GAP && vgap >= 1 && vgap <= DETECT_MAX_GAP, "detect_label_local: gap and vgap must be 1 .. 64");
+  DPMN_REQUIRE(cell >= 32 && cell <= DETECT_MAP_SIDE, "detect_label_local: the cell side must be 32 .. 1024");
+  DPMN_REQUIRE(detect_check(items_host, B, -1, map_px), "detect_label_local: a working map does not fit the buffers or is not its photo's");
+  DPMN_REQUIRE(detect_cells_check(items_host, B, cell, n_cells), "detect_label_local: the items' cell offsets are not the running sum of their cell counts");
+  const dim3 grid((unsigned)n_tiles), block(DT_THREADS);
+  hipLaunchKernelGGL(k_detect_hsmooth_local, grid, block, 0, as_stream(stream), g, map_px, items, B, tiles, table, n_cells, cell, gap, tmp, tmap);
   DPMN_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_detect_vsmooth, grid, block, 0, as_stream(stream), (const unsigned char*)tmp, map_px, items, B, tiles, vgap, smooth, labels);
   DPMN_CHECK_LAUNCH();

@@ -13,7 +13,7 @@ quadrilaterals, which TextSR.demo(paste=True) needs to put the SR regions back (
 by strip (ops.poly_crop_u8) into the same packed buffer as the quadrilaterals (ops.crop_regions_u8).
 `detect_box_files` (main.py --demo_detect) writes the box files itself: the regions of every photo are found on the GPU
 (ops.detect_text_u8, utils/detect.py), with oriented=True (main.py --demo_detect_oriented) as rotated quadrilaterals
-(ops.detect_oriented_u8).
+(ops.detect_oriented_u8), with local=C (main.py --demo_detect_local) under a threshold of its own per C x C cell of the working map.
 """
 import os
 
@@ -84,20 +84,22 @@ def folder_window_batches(dir_, batch_size, lr_size, mask, device):
         yield names, plan, ops.collate_u8(windows, mask)
 
 
-def detect_box_files(dir_, box_dir, batch_size, device, gap=12, floor=24, oriented=False):
+def detect_box_files(dir_, box_dir, batch_size, device, gap=12, floor=24, oriented=False, local=0):
     """main.py --demo_detect: the text regions of every photo of `dir_` (host_batches' files, *.txt passed over), found on the GPU
     (ops.detect_text_u8; utils/detect.py holds the recipe and its limits), written as box_dir/<stem>.txt in the format that box_batches
     reads -- an ordinary box file that can be corrected by hand and fed back with --demo_boxes.  Per batch one upload of the packed
     photos.  A photo without a region gets an empty file and one printed line.  oriented (main.py --demo_detect_oriented): the
-    regions are rotated quadrilaterals along the text's own direction, in decimals (ops.detect_oriented_u8).  -> the number of boxes
+    regions are rotated quadrilaterals along the text's own direction, in decimals (ops.detect_oriented_u8).  local (main.py
+    --demo_detect_local): the cell side of the locally adaptive threshold, 0 for the one threshold per photo.  -> the number of boxes
     written."""
     from .. import ops
     from ..utils.detect import write_boxes, write_quads
     find, write = (ops.detect_oriented_u8, write_quads) if oriented else (ops.detect_text_u8, write_boxes)
+    kw = {"local": int(local)} if local else {}      # (off: the call is the one it was)
     os.makedirs(box_dir, exist_ok=True)
     n = 0
     for names, packed, meta in host_batches(dir_, batch_size, skip_txt=True):
-        found = find(packed.to(device, non_blocking=True), meta[:, 0], meta[:, 1:], gap=gap, floor=floor, names=names)
+        found = find(packed.to(device, non_blocking=True), meta[:, 0], meta[:, 1:], gap=gap, floor=floor, names=names, **kw)
         for name, boxes in zip(names, found):
             if len(boxes) == 0:
                 print("detect: no text region found in %s" % name)

@@ -1009,11 +1009,18 @@ DETECT_TILE = (16, 64)      # csrc/detect.hip DT_H, DT_W
 DETECT_TABLE = 4096         # rows of a photo's component table; a photo with more components gets ONE second pass with as many as it has
 
 
-def _detect_plan(packed, offsets, sizes, what="detect_text_u8"):
+def _detect_plan(packed, offsets, sizes, what="detect_text_u8", local=0):
     """Checks and per-call host data of the detect ops -> host: items (B, 8) int64 [byte offset, H, W, offset of the working map, hm, wm,
-    r, 0], tiles (n_tiles, 3) int32 [photo, tile row, tile column] over the working maps, map_px: the pixels of all maps."""
+    r, 0], tiles (n_tiles, 3) int32 [photo, tile row, tile column] over the working maps, map_px: the pixels of all maps.  local (the
+    cell side of the locally adaptive threshold, checked here; 0: none): the last word of an item is the offset of the photo's
+    ceil(hm / local) x ceil(wm / local) cell thresholds in the batch's table of host["n_cells"] entries -- the cell plan travels with
+    the items, in the same upload."""
     import numpy as np
-    from .utils.detect import MAP_SIDE
+    from .utils.detect import MAP_SIDE, check_local
+    try:
+        local = check_local(local)
+    except ValueError as e:
+        raise _abi.DpmnError("%s: %s" % (what, e)) from e
     off = np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets)
     sz = np.asarray(sizes.cpu() if torch.is_tensor(sizes) else sizes)
     if off.ndim != 1 or sz.ndim != 2 or sz.shape != (off.shape[0], 2) or off.dtype.kind not in "iu" or sz.dtype.kind not in "iu":
@@ -1024,7 +1031,11 @@ def _detect_plan(packed, offsets, sizes, what="detect_text_u8"):
     first = np.concatenate(([0], np.cumsum(hm * wm)))
     items = np.zeros((m.shape[0], 8), np.int64)
     items[:, :3], items[:, 3], items[:, 4], items[:, 5], items[:, 6] = m, first[:-1], hm, wm, r
-    return dict(items=items, tiles=_tile_table(hm, wm, *DETECT_TILE)[0], map_px=int(first[-1]))
+    n_cells = 0
+    if local:
+        cells = np.concatenate(([0], np.cumsum(-(-hm // local) * -(-wm // local))))
+        items[:, 7], n_cells = cells[:-1], int(cells[-1])
+    return dict(items=items, tiles=_tile_table(hm, wm, *DETECT_TILE)[0], map_px=int(first[-1]), local=local, n_cells=n_cells)
 
 
 def _detect_gradient(packed, host, d_items, d_tiles):
@@ -1039,14 +1050,34 @@ def _detect_gradient(packed, host, d_items, d_tiles):
 
 def _detect_thresholds(packed, host, floor):
     """The uploads, the gradient launch, the histogram copy and the thresholds of one batch (utils.detect.threshold, on the host) ->
-    (d, d_items, d_tiles, g, hist (host, int64 (B, 256)), thr (device, int32 (B))); d keeps the uploaded buffer alive."""
+    (d, d_items, d_tiles, g, hist (host, int64 (B, 256)), thr (device, int32 (B))); d keeps the uploaded buffer alive.
+    With host["local"]: no copy and no host step -- the cell-Otsu launch fills thr, the device int32 (n_cells) table of the batch's cell
+    thresholds, and hist stays on the device (int32 (B, 256); only detect_maps_u8 copies it)."""
     import numpy as np
     from .utils.detect import threshold
     d, d_items, d_tiles = _upload(packed.device, host["items"], host["tiles"])
     g, hist = _detect_gradient(packed, host, d_items, d_tiles)
+    if host["local"]:
+        thr = torch.empty(max(host["n_cells"], 1), dtype=torch.int32, device=packed.device)
+        check(lib.dpmn_detect_cell_otsu_i32(g.data_ptr(), host["map_px"], d_items, host["items"].ctypes.data, host["items"].shape[0],
+                                            host["local"], floor, thr.data_ptr(), host["n_cells"], stream()))
+        return d, d_items, d_tiles, g, hist, thr
     hist = hist.cpu().numpy().astype(np.int64)
     thr = torch.from_numpy(np.array([threshold(h, floor) for h in hist], np.int32)).to(packed.device)
     return d, d_items, d_tiles, g, hist, thr
+
+
+def _detect_label(host, d_items, d_tiles, g, thr, gap, vgap, tmp, smooth, labels, tmap=None):
+    """The label launches of one batch: against one threshold per photo, or with host["local"] against the threshold map of the cell
+    table thr (tmap: an int32 (map_px) tensor that receives the map)."""
+    items, map_px, n_tiles = host["items"], host["map_px"], host["tiles"].shape[0]
+    if host["local"]:
+        check(lib.dpmn_detect_label_local_i32(g.data_ptr(), map_px, d_items, items.ctypes.data, items.shape[0], d_tiles, n_tiles, thr.data_ptr(),
+                                              host["n_cells"], host["local"], gap, vgap, tmp.data_ptr(), smooth.data_ptr(), labels.data_ptr(),
+                                              tmap.data_ptr() if tmap is not None else None, stream()))
+    else:
+        check(lib.dpmn_detect_label_i32(g.data_ptr(), map_px, d_items, items.ctypes.data, items.shape[0], d_tiles, n_tiles, thr.data_ptr(), gap,
+                                        vgap, tmp.data_ptr(), smooth.data_ptr(), labels.data_ptr(), stream()))
 
 
 def _detect_pass(host, d_items, d_tiles, g, thr, gap, vgap):
@@ -1059,8 +1090,7 @@ def _detect_pass(host, d_items, d_tiles, g, thr, gap, vgap):
     B, n_tiles = items.shape[0], tiles.shape[0]
     tmp, smooth = torch.empty_like(g), torch.empty_like(g)
     labels, slots = torch.empty(g.numel(), dtype=torch.int32, device=dev), torch.empty(g.numel(), dtype=torch.int32, device=dev)
-    check(lib.dpmn_detect_label_i32(g.data_ptr(), map_px, d_items, items.ctypes.data, B, d_tiles, n_tiles, thr.data_ptr(), gap, vgap,
-                                    tmp.data_ptr(), smooth.data_ptr(), labels.data_ptr(), stream()))
+    _detect_label(host, d_items, d_tiles, g, thr, gap, vgap, tmp, smooth, labels)
     caps = np.full(B, DETECT_TABLE, np.int64)
     for _ in range(2):      # (the counters of the first pass are exact: the second pass has a row for every component)
         first = np.concatenate(([0], np.cumsum(caps)))
@@ -1085,7 +1115,7 @@ def _detect_run(packed, host, gap, vgap, floor):
     (host["items"] says where a photo's lies), and per photo the int64 (n, 5) table [x0, y0, x1, y1, area] of its components, ends
     exclusive, in no fixed order.  Two copies to the host: the histograms (the thresholds come from them: utils.detect.threshold) and
     the component tables behind their counters; a third, with the second pass over the tables, when a photo has more than DETECT_TABLE
-    components."""
+    components.  With host["local"] the first copy falls away: the thresholds are found on the device and hist stays there."""
     d, d_items, d_tiles, g, hist, thr = _detect_thresholds(packed, host, floor)
     p = _detect_pass(host, d_items, d_tiles, g, thr, gap, vgap)
     return g, hist, p["smooth"], p["labels"], _detect_comps(p)
@@ -1165,15 +1195,15 @@ def _detect_oriented_pass(host, d_items, d_tiles, p):
     return res
 
 
-def _detect_oriented_run(packed, offsets, sizes, gap, vgap, floor, what):
+def _detect_oriented_run(packed, offsets, sizes, gap, vgap, floor, what, local=0):
     """The checks and launches of the oriented ops -> (host, [row pass, column pass]): per pass (what _detect_pass returns, what
-    _detect_oriented_pass returns).  One gradient launch and one histogram copy serve both passes."""
+    _detect_oriented_pass returns).  One gradient launch and one histogram copy -- with local one cell table -- serve both passes."""
     from .utils.detect import check_params
     try:
         gap, vgap, floor = check_params(gap, vgap, floor)
     except ValueError as e:
         raise _abi.DpmnError("%s: %s" % (what, e)) from e
-    host = _detect_plan(packed, offsets, sizes, what)
+    host = _detect_plan(packed, offsets, sizes, what, local)
     d, d_items, d_tiles, g, hist, thr = _detect_thresholds(packed, host, floor)
     passes = []
     for a, b in ((gap, vgap), (vgap, gap)):      # the row pass, then the column pass: the same kernels with the gaps swapped
@@ -1182,16 +1212,16 @@ def _detect_oriented_run(packed, offsets, sizes, gap, vgap, floor, what):
     return host, passes
 
 
-def detect_oriented_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, names=None):
+def detect_oriented_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, names=None, local=0):
     """The ORIENTED text regions of a ragged batch of photos (csrc/detect.hip; utils/detect.py holds the recipe): the arguments of
     detect_text_u8 -> per photo an int64 (n, 8) numpy array of quads tl, tr, br, bl (x, y) in hundredths of a photo pixel, not clamped
     to the photo, at most utils.detect.MAX_BOXES: row for row utils.detect.detect_oriented_np.  Two passes over one gradient map and one
     threshold (the smoothing with its gaps as given, then swapped); per pass the components' second moments and, along the direction
     the host chooses from them, their extents.  Integer kernels: the same in every compute mode.  Beyond detect_text_u8's copies, the
-    moment tables and the extents of each pass cross to the host."""
+    moment tables and the extents of each pass cross to the host.  local: as detect_text_u8 takes it."""
     from .utils.detect import cross_pass, oriented_rects, quads_from_rects
     import numpy as np
-    host, passes = _detect_oriented_run(packed, offsets, sizes, gap, vgap, floor, "detect_oriented_u8")
+    host, passes = _detect_oriented_run(packed, offsets, sizes, gap, vgap, floor, "detect_oriented_u8", local)
     out = []
     for b, it in enumerate(host["items"]):
         H, W = int(it[1]), int(it[2])
@@ -1200,12 +1230,12 @@ def detect_oriented_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, names=N
     return out
 
 
-def detect_oriented_tables_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24):
+def detect_oriented_tables_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, local=0):
     """The tables behind detect_oriented_u8, for tests: per photo [row pass, column pass], each (moments int64 (n, 6), k int64 (n),
     extents int64 (n, 4)) in LABEL order (the labels and slots of every pass are copied back to find it): what
     utils.detect.oriented_pass_np returns first."""
     import numpy as np
-    host, passes = _detect_oriented_run(packed, offsets, sizes, gap, vgap, floor, "detect_oriented_tables_u8")
+    host, passes = _detect_oriented_run(packed, offsets, sizes, gap, vgap, floor, "detect_oriented_tables_u8", local)
     out = [[] for _ in host["items"]]
     for p, tables in passes:
         labels, slots = p["labels"].cpu().numpy(), p["slots"].cpu().numpy()
@@ -1218,41 +1248,67 @@ def detect_oriented_tables_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24):
     return out
 
 
-def detect_text_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, names=None):
+def detect_text_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, names=None, local=0):
     """The text regions of a ragged batch of photos (csrc/detect.hip; utils/detect.py holds the recipe): packed = the device copy of
     utils.resize.pack_ragged's buffer, offsets / sizes = the columns of its meta, integer (B) byte offsets and (B, 2) (h, w) -> per
     photo an int32 (n, 4) numpy array of boxes x0, y0, x1, y1 in photo pixels, ends exclusive, sorted by (top, left, bottom, right), at
     most utils.detect.MAX_BOXES: box for box utils.detect.detect_text_np.  gap / vgap: the longest background run that the smoothing
     fills along a row / a column (1 .. 64), floor: the least threshold on the gradient (1 .. 255).  names: per photo, for the line that
     is printed when boxes are dropped.  Integer kernels: the same in every compute mode.  Only the histograms and the component tables
-    cross to the host."""
+    cross to the host.  local (0: off; else a cell side 32 .. 1024 on the working map): the locally adaptive threshold of
+    utils/detect.py -- Otsu's threshold per cell, found on the device, interpolated between the cell centres; the histograms then stay
+    on the device, one copy fewer.  local = 1024 is one cell per photo: the boxes of local = 0."""
     from .utils.detect import boxes_from_components, check_params
     try:
         gap, vgap, floor = check_params(gap, vgap, floor)
     except ValueError as e:
         raise _abi.DpmnError("detect_text_u8: %s" % e) from e
-    host = _detect_plan(packed, offsets, sizes)
+    host = _detect_plan(packed, offsets, sizes, local=local)
     comps = _detect_run(packed, host, gap, vgap, floor)[4]
     return [boxes_from_components(c, int(it[1]), int(it[2]), names[b] if names else None) for b, (c, it) in enumerate(zip(comps, host["items"]))]
 
 
-def detect_maps_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24):
+def detect_maps_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, local=0):
     """The maps behind detect_text_u8, for tests: per photo (g uint8 (hm, wm), histogram int64 (256), smoothed map uint8 of 0 / 1,
     labels int32: the least linear index of the pixel's component, -1 on the background) as numpy arrays, byte for byte
-    utils.detect.detect_maps_np."""
+    utils.detect.detect_maps_np.  local: as detect_text_u8 takes it (the histogram is the whole map's either way)."""
+    import numpy as np
     from .utils.detect import check_params
     try:
         gap, vgap, floor = check_params(gap, vgap, floor)
     except ValueError as e:
         raise _abi.DpmnError("detect_maps_u8: %s" % e) from e
-    host = _detect_plan(packed, offsets, sizes, "detect_maps_u8")
+    host = _detect_plan(packed, offsets, sizes, "detect_maps_u8", local)
     g, hist, smooth, labels, _ = _detect_run(packed, host, gap, vgap, floor)
+    if torch.is_tensor(hist):
+        hist = hist.cpu().numpy().astype(np.int64)
     g, smooth, labels = g.cpu().numpy(), smooth.cpu().numpy(), labels.cpu().numpy()
     out = []
     for b, (_, _, _, at, hm, wm, _, _) in enumerate(host["items"].tolist()):
         cut = lambda a: a[at:at + hm * wm].reshape(hm, wm).copy()
         out.append((cut(g), hist[b], cut(smooth), cut(labels)))
     return out
+
+
+def detect_thresholds_u8(packed, offsets, sizes, local, floor=24):
+    """The thresholds behind detect_text_u8(local=...), for tests: per photo (the cell table int32 (ny, nx), the threshold map int32
+    (hm, wm)) as numpy arrays -- utils.detect.cell_thresholds and threshold_map.  The table is what the cell-Otsu launch wrote; the map
+    is written by the very launch that thresholds (the local row smoothing, under its test pointer)."""
+    from .utils.detect import check_params
+    try:
+        floor = check_params(floor=floor)[2]
+        if not int(local):
+            raise ValueError("detect: local 0 has no cell table")
+    except ValueError as e:
+        raise _abi.DpmnError("detect_thresholds_u8: %s" % e) from e
+    host = _detect_plan(packed, offsets, sizes, "detect_thresholds_u8", local)
+    d, d_items, d_tiles, g, hist, thr = _detect_thresholds(packed, host, floor)
+    tmp, smooth = torch.empty_like(g), torch.empty_like(g)
+    labels, tmap = torch.empty(g.numel(), dtype=torch.int32, device=g.device), torch.zeros(g.numel(), dtype=torch.int32, device=g.device)
+    _detect_label(host, d_items, d_tiles, g, thr, 1, 1, tmp, smooth, labels, tmap)
+    thr, tmap, C = thr.cpu().numpy(), tmap.cpu().numpy(), host["local"]
+    return [(thr[c:c + -(-hm // C) * -(-wm // C)].reshape(-(-hm // C), -(-wm // C)).copy(), tmap[at:at + hm * wm].reshape(hm, wm).copy())
+            for _, _, _, at, hm, wm, _, c in host["items"].tolist()]
 
 
 def _region_units_table(first_items, rows, block):

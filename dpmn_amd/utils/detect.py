@@ -18,9 +18,26 @@ Per photo (RGB uint8, H x W, sides 1 .. utils.resize.MAX_SIDE):
   6. filter: with h = y1 - y0, w = x1 - x0 a component stays if h >= 6, 2 h <= hm, 5 w >= 6 h and 100 area >= 35 w h.
   7. boxes: padded by (h + 5) // 10 on every side, multiplied by r, clamped to the photo, sorted by (top, left, bottom, right); more
      than MAX_BOXES: the MAX_BOXES of largest area stay (ties: the earlier in that order) and one line is printed.
-What it finds: well-contrasted, roughly horizontal words and lines.  What it misses: text less than about 50 luma levels from its
-background (below the Otsu threshold), vertical or strongly rotated text (5 w >= 6 h), glyphs taller than half the working map, and
-very large glyphs whose word spaces exceed `gap` at the working resolution (the word splits).  It is no learned detector.
+What it finds: well-contrasted, roughly horizontal words and lines.  What it misses: under the one threshold per photo, text fainter
+than the photo's strongest edges -- in a plain photo text less than about 50 luma levels from its background, and one high-contrast
+sign anywhere lifts the threshold for every word (with local = C, below, only text under `floor` levels of gradient is lost to the
+threshold); vertical or strongly rotated text (5 w >= 6 h), glyphs taller than half the working map, and very large glyphs whose
+word spaces exceed `gap` at the working resolution (the word splits).  It is no learned detector.
+
+Locally adaptive threshold (main.py --demo_detect_local; local = C on every function below, 0 = off = the recipe above): stage 3 with
+a threshold per pixel, still in integers only.  C, MIN_LOCAL .. MAP_SIDE, is the cell side on the working map.
+  3a. cells: per axis of length `size`, n = ceil(size / C) cells with the edges e_i = i * size // n (cell_edges): balanced, never empty,
+      never wider than C.  A map with hm <= C and wm <= C is one cell.
+  3b. cell thresholds: t[i][j] = max(otsu(histogram of g over the cell) + 1, floor) (cell_thresholds), the same otsu, exactly.
+  3c. threshold map (threshold_map): bilinear between the cell centres.  Per axis the doubled centres c_i = e_i + e_{i+1}; a pixel's
+      doubled centre p = 2x + 1, clamped to [c_0, c_{n-1}]; k the greatest index with c_k <= p, capped at n - 2; weights (c_{k+1} - p,
+      p - c_k), D = c_{k+1} - c_k.  T(y, x) = (2 * sum of the four w_y w_x t + Dy Dx) // (2 Dy Dx): rounded half up.  An axis with one
+      cell contributes weight 1 and D = 1.  b = g >= T(y, x).  Stages 4 to 7 and the oriented recipe are unchanged.
+Consequences: with one cell T is threshold(hist, floor) everywhere, so local = 1024 gives byte for byte the maps and boxes of local = 0
+for every photo; T >= floor; T lies within [min t, max t]; D = e_{k+2} - e_k <= size <= 1024 per axis and t <= 255, so
+2 * 255 * Dy * Dx + Dy * Dx < 2^31 (csrc/detect.hip computes T in 32 bits).  Limits: the floor still rules; a textured cell (foliage,
+brickwork) gets a threshold inside its own texture, so more clutter reaches the filters than under a high global threshold; a word
+that straddles a faint cell and a cell with a strong edge sees a ramp of thresholds and can lose its faint end; C is untuned.
 
 Oriented regions (main.py --demo_detect_oriented; detect_oriented_np, ops.detect_oriented_u8): stages 1 to 3 as above, then TWO passes
 over the one gradient map and the one threshold -- the row pass smooth(b, gap, vgap) and the column pass smooth(b, vgap, gap) -- and per
@@ -61,6 +78,7 @@ FLOOR, GAP, VGAP = 24, 12, 2
 MAX_GAP = 64         # of gap and vgap: a fill decision looks at most this far (csrc/detect.hip DETECT_MAX_GAP)
 MAX_BOXES = 256
 MIN_H = 6
+MIN_LOCAL = 32       # the least cell side of the locally adaptive threshold (the greatest is MAP_SIDE: one cell)
 
 
 def check_params(gap=GAP, vgap=VGAP, floor=FLOOR):
@@ -125,6 +143,69 @@ def otsu(hist):
 def threshold(hist, floor=FLOOR):
     """T = max(otsu + 1, floor): a pixel is foreground where g >= T."""
     return max(otsu(hist) + 1, int(floor))
+
+
+def check_local(local=0):
+    """local as an int; ValueError unless it is 0 (one threshold per photo) or a cell side MIN_LOCAL .. MAP_SIDE."""
+    local = int(local)
+    if local != 0 and not MIN_LOCAL <= local <= MAP_SIDE:
+        raise ValueError("detect: local %d must be 0 (one threshold per photo) or a cell side %d .. %d" % (local, MIN_LOCAL, MAP_SIDE))
+    return local
+
+
+def cell_edges(size, C):
+    """The edges e_0 .. e_n of the n = ceil(size / C) balanced cells of an axis of `size` pixels: e_i = i * size // n (a list of
+    n + 1 ints; [0] for size 0).  No cell is empty, none is wider than C, and their widths differ by at most 1."""
+    size, C = int(size), int(C)
+    n = -(-size // C)
+    return [i * size // n for i in range(n + 1)] if n else [0]
+
+
+def cell_thresholds(g, C, floor=FLOOR):
+    """The gradient map g (hm, wm) -> int32 (ny, nx): per cell max(otsu(histogram of g over the cell) + 1, floor)."""
+    g = np.asarray(g, np.uint8)
+    ey, ex = cell_edges(g.shape[0], C), cell_edges(g.shape[1], C)
+    t = np.empty((len(ey) - 1, len(ex) - 1), np.int32)      # (an empty map has no cell along its empty axis)
+    for i in range(t.shape[0]):
+        for j in range(t.shape[1]):
+            t[i, j] = threshold(np.bincount(g[ey[i]:ey[i + 1], ex[j]:ex[j + 1]].reshape(-1), minlength=256), floor)
+    return t
+
+
+def _axis_weights(size, C):
+    """Per pixel of an axis (k, k1, w0, w1, D): the two cells k and k1 whose centres lie around it, their integer weights and the
+    weights' sum D (stage 3 of the local recipe).  One cell: (0, 0, 1, 0, 1)."""
+    e = np.array(cell_edges(size, C), np.int64)
+    n = len(e) - 1
+    if n <= 1:
+        z = np.zeros(size, np.int64)
+        return z, z, z + 1, z, z + 1
+    c = e[:-1] + e[1:]
+    p = np.clip(2 * np.arange(size, dtype=np.int64) + 1, c[0], c[-1])
+    k = np.minimum(np.searchsorted(c, p, side="right") - 1, n - 2)
+    return k, k + 1, c[k + 1] - p, p - c[k], c[k + 1] - c[k]
+
+
+def threshold_map(t, hm, wm, C):
+    """The cell table of cell_thresholds -> T int32 (hm, wm): bilinear between the cell centres in integers, rounded half up, constant
+    outside the outermost centres.  Every term is below 2^31 (D <= 1024 per axis, t <= 255)."""
+    t = np.asarray(t, np.int64)
+    ny, nx = len(cell_edges(hm, C)) - 1, len(cell_edges(wm, C)) - 1
+    if hm == 0 or wm == 0:
+        return np.zeros((hm, wm), np.int32)
+    if t.shape != (ny, nx):
+        raise ValueError("threshold_map: a table of %s cells for a %d x %d map with cells of %d (%d x %d expected)" % (t.shape, hm, wm, C, ny, nx))
+    ky, ky1, wy0, wy1, Dy = (a[:, None] for a in _axis_weights(hm, C))
+    kx, kx1, wx0, wx1, Dx = (a[None, :] for a in _axis_weights(wm, C))
+    s = wy0 * (wx0 * t[ky, kx] + wx1 * t[ky, kx1]) + wy1 * (wx0 * t[ky1, kx] + wx1 * t[ky1, kx1])
+    return ((2 * s + Dy * Dx) // (2 * Dy * Dx)).astype(np.int32)
+
+
+def foreground(g, hist, floor=FLOOR, local=0):
+    """Stage 3: b = g >= T, T the photo's one threshold (local = 0) or the threshold map of its cells of side `local`."""
+    if not local:
+        return g >= threshold(hist, floor)
+    return g >= threshold_map(cell_thresholds(g, local, floor), g.shape[0], g.shape[1], local)
 
 
 def smooth_rows(b, gap):
@@ -221,18 +302,20 @@ def boxes_from_components(comps, H, W, name=None):
     return b.astype(np.int32)
 
 
-def detect_maps_np(photo, gap=GAP, vgap=VGAP, floor=FLOOR):
+def detect_maps_np(photo, gap=GAP, vgap=VGAP, floor=FLOOR, local=0):
     """One photo -> (g uint8, histogram int64 (256,), smoothed map uint8 of 0 / 1, labels int32), each map hm x wm: stages 1 to 5.
-    The CPU reference of ops.detect_maps_u8."""
+    The CPU reference of ops.detect_maps_u8.  local: 0, or the cell side of the locally adaptive threshold (the histogram stays that
+    of the whole map)."""
     gap, vgap, floor = check_params(gap, vgap, floor)
+    local = check_local(local)
     g, hist = gradient(luma_map(photo))
-    s = smooth(g >= threshold(hist, floor), gap, vgap)
+    s = smooth(foreground(g, hist, floor, local), gap, vgap)
     return g, hist, s.astype(np.uint8), label(s)
 
 
-def detect_text_np(photo, gap=GAP, vgap=VGAP, floor=FLOOR, name=None):
+def detect_text_np(photo, gap=GAP, vgap=VGAP, floor=FLOOR, name=None, local=0):
     """One photo -> its boxes, int32 (n, 4).  The CPU reference of ops.detect_text_u8."""
-    labels = detect_maps_np(photo, gap, vgap, floor)[3]
+    labels = detect_maps_np(photo, gap, vgap, floor, local)[3]
     return boxes_from_components(components(labels), photo.shape[0], photo.shape[1], name)
 
 
@@ -419,12 +502,13 @@ def oriented_pass_np(labels, H, W, column=False):
     return m, ks, ext, oriented_rects(comps, ks, ext, H, W, column)
 
 
-def detect_oriented_np(photo, gap=GAP, vgap=VGAP, floor=FLOOR, name=None):
+def detect_oriented_np(photo, gap=GAP, vgap=VGAP, floor=FLOOR, name=None, local=0):
     """One photo -> its oriented regions, int64 (n, 8): quads tl, tr, br, bl in hundredths of a photo pixel.  The CPU reference of
-    ops.detect_oriented_u8."""
+    ops.detect_oriented_u8.  local: as detect_maps_np takes it; both passes share the one threshold map."""
     gap, vgap, floor = check_params(gap, vgap, floor)
+    local = check_local(local)
     g, hist = gradient(luma_map(photo))
-    b = g >= threshold(hist, floor)
+    b = foreground(g, hist, floor, local)
     H, W = photo.shape[:2]
     rows = oriented_pass_np(label(smooth(b, gap, vgap)), H, W)[3]
     cols = oriented_pass_np(label(smooth(b, vgap, gap)), H, W, True)[3]

@@ -753,7 +753,22 @@ int dpmn_poly_crop_u8(const unsigned char* packed, long packed_bytes, const long
  * its pixels (its area is in the table of dpmn_detect_stats_i32).  One launch.
  * dpmn_detect_extents_i32: dirs, device int32 (table_rows, 2): per component the (c, s) of its direction, (0, 0): passed over.  table,
  * int32 (table_rows, 4) (every byte set to 0x80 here, which is what a row that is passed over keeps): per component [max -U2, max U2,
- * max -V2, max V2] over its pixels, U2 = c (2x + 1) + s (2y + 1), V2 = -s (2x + 1) + c (2y + 1); |c|, |s| <= 16384.  One launch. */
+ * max -V2, max V2] over its pixels, U2 = c (2x + 1) + s (2y + 1), V2 = -s (2x + 1) + c (2y + 1); |c|, |s| <= 16384.  One launch.
+ * The locally adaptive threshold (utils/detect.py, local = cell): per axis of a working map ceil(size / cell) balanced cells with the
+ * edges i * size / n, cell 32 .. 1024.  Word 7 of a photo's item is then the offset of its ny * nx cell thresholds in table, device
+ * int32 (n_cells), row-major per photo: the running sum of the cell counts of the photos before it, ending at n_cells -- both entry
+ * points check that on items_host and refuse anything else; the kernels check the device copy and skip a photo that fails.
+ * dpmn_detect_cell_otsu_i32: table[cell] = max(otsu(histogram of g over the cell) + 1, floor), Otsu's t found on the device exactly as
+ * utils.detect.otsu finds it (three-limb integer products, the earliest t on a tie, 0 without a valid split).  One block per cell, one
+ * launch, no atomics on global memory.
+ * dpmn_detect_label_local_i32: dpmn_detect_label_i32 with b = g >= T(y, x), the thresholds of table interpolated bilinearly between
+ * the cell centres in integers, rounded half up (with one cell per photo: dpmn_detect_label_i32 with that threshold).  tmap: NULL, or
+ * int32 (map_px) that receives T of every pixel (for tests).  Three launches. */
+int dpmn_detect_cell_otsu_i32(const unsigned char* g, long map_px, const long long* items, const long long* items_host /* HOST array */, int B,
+                              int cell, int floor, int* table, long n_cells, dpmn_stream_t stream);
+int dpmn_detect_label_local_i32(const unsigned char* g, long map_px, const long long* items, const long long* items_host /* HOST array */, int B,
+                                const int* tiles, int n_tiles, const int* table, long n_cells, int cell, int gap, int vgap, unsigned char* tmp,
+                                unsigned char* smooth, int* labels, int* tmap, dpmn_stream_t stream);
 int dpmn_detect_gradient_u8(const unsigned char* packed, long packed_bytes, const long long* items, const long long* items_host /* HOST array */,
                             int B, const int* tiles, int n_tiles, unsigned char* g, long map_px, unsigned int* hist, dpmn_stream_t stream);
 int dpmn_detect_label_i32(const unsigned char* g, long map_px, const long long* items, const long long* items_host /* HOST array */, int B,

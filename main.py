@@ -18,7 +18,8 @@ strip by strip on the GPU (polygon regions are written as files; `--demo_paste_p
 the photo, strip by strip, in box-file order with the quadrilaterals); with `--demo_detect` in place of `--demo_boxes` the box files are
 written by the run itself: the text regions of every photo are found on the GPU by a classical, integer recipe (utils/detect.py) into
 `<demo_out>/boxes`, and the run goes on as with `--demo_boxes <demo_out>/boxes` (`--demo_detect_oriented` on top: the regions are
-rotated quadrilaterals along the text's own direction, so slanted and vertical text is found too).  `--train_state PATH` makes a training run continuable: the same command line starts the
+rotated quadrilaterals along the text's own direction, so slanted and vertical text is found too; `--demo_detect_local [C]` on top: a
+threshold of its own per C x C cell of the working map, so a faint word is not lost to a strong edge elsewhere).  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--ema DECAY` keeps an exponential moving average of the trained weights; the
 validation passes score it and the best-model checkpoints hold it.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
 (`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image; `--psf_blur KINDS`: with a random motion, defocus or elongated-Gaussian blur of the HR pixels first); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB); `--train_words FILE` trains from a word list alone: the HR images are rendered on the GPU (`--train_words_fonts DIR`: in the fonts of a directory; `--train_words_epoch N`: samples per epoch).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
@@ -112,6 +113,25 @@ def demo_detect_setting(args):
     if not 1 <= floor <= 255:
         raise ValueError(DEMO_DETECT_FLOOR[len("main.py: "):])
     return gap, floor
+
+
+DEMO_DETECT_LOCAL_NEEDS = ("main.py: --demo_detect_local needs --demo_detect: it gives the detector of --demo_detect a threshold of its own per "
+                           "cell of the working map")
+DEMO_DETECT_LOCAL_RANGE = "main.py: --demo_detect_local must be 32 .. 1024 (the side of a cell in pixels of the working map; 1024: one cell)"
+
+
+def demo_detect_local_setting(args):
+    """--demo_detect_local, checked -> 0 without the flag, else the cell side C.  ValueError (the message without its 'main.py: ') for
+    the flag without --demo_detect or a C outside 32 .. 1024."""
+    from dpmn_amd.utils.detect import MAP_SIDE, MIN_LOCAL
+    local = getattr(args, "demo_detect_local", None)
+    if local is None:
+        return 0
+    if not getattr(args, "demo_detect", False):
+        raise ValueError(DEMO_DETECT_LOCAL_NEEDS[len("main.py: "):])
+    if not MIN_LOCAL <= int(local) <= MAP_SIDE:
+        raise ValueError(DEMO_DETECT_LOCAL_RANGE[len("main.py: "):])
+    return int(local)
 
 
 DEMO_CONF_NEEDS_DIR = ("main.py: --demo_conf, --demo_upright and --demo_min_conf need --demo_dir: the confidence is that of the reads of the "
@@ -436,6 +456,7 @@ def main(config, args):
         raise SystemExit("main.py: --demo_tile needs --demo_dir: it super-resolves the wide images of that folder in overlapping windows")
     try:
         detect = demo_detect_setting(args)
+        detect_local = demo_detect_local_setting(args)
     except ValueError as e:
         raise SystemExit("main.py: %s" % e)
     if getattr(args, "demo_boxes", None) and not getattr(args, "demo_dir", None):
@@ -532,7 +553,7 @@ def main(config, args):
             box_dir = os.path.join(out_dir, "boxes")
             print("%d regions detected, box files in %s"
                   % (detect_box_files(args.demo_dir, box_dir, bs, mission.device, *detect,
-                                      oriented=getattr(args, "demo_detect_oriented", False)), box_dir))
+                                      oriented=getattr(args, "demo_detect_oriented", False), local=detect_local), box_dir))
         if box_dir:
             # whole photos and one box file per photo: every quadrilateral is rectified on the GPU (utils/quad.py), then goes the way
             # of a crop of the folder -- one <stem>_<k>_sr.png per region
@@ -766,6 +787,12 @@ if __name__ == '__main__':
                              'of short horizontal lines keeps its lines and also gets one steep region around the block, to be '
                              'deleted by hand.  Text steeper than 45 degrees is read along its longer side; whether a vertical sign reads upward '
                              'or downward cannot be told from its shape (exactly vertical text is read upward)')
+    parser.add_argument('--demo_detect_local', type=int, nargs='?', const=128, default=None, metavar='C',
+                        help='with --demo_detect: a locally adaptive threshold -- Otsu\'s threshold per C x C cell of the working map '
+                             '(32 .. 1024, 128 when C is left out), interpolated between the cell centres, instead of one threshold per '
+                             'photo, so that a faint word is not lost to a strong edge elsewhere in the photo.  More clutter reaches the '
+                             'shape filters in textured areas (--demo_min_conf drops it downstream); --demo_detect_floor still bounds '
+                             'the threshold from below.  1024 is one cell: the regions without the flag')
     parser.add_argument('--demo_detect_gap', type=int, default=None, metavar='N',
                         help='with --demo_detect: the longest gap between letters, in pixels of the working map (the photo reduced to at '
                              'most 1024 on its long side), that still joins them into one word (1 .. 64, default 12)')
@@ -849,6 +876,7 @@ if __name__ == '__main__':
         parser.error(TRAIN_WORDS_FONTS_NEEDS[len("main.py: "):])
     try:
         demo_detect_setting(args)
+        demo_detect_local_setting(args)
     except ValueError as e:
         parser.error(str(e))
     if args.demo_boxes and not args.demo_dir:
