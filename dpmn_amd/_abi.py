@@ -312,6 +312,8 @@ SIGNATURES = {
     "dpmn_cutblur_ragged_u8": (_i, [fp, _l, fp, _i, _i, fp, fp]),
     "dpmn_render_words_u8": (_i, [fp, fp, fp, fp, fp, fp, fp, fp, _i, fp, _l, _i, _i, _i, _i, fp, fp, fp, fp, fp]),
     "dpmn_render_words_fx_u8": (_i, [fp, fp, fp, fp, fp, fp, fp, fp, fp, _i, fp, _l, fp, _i, fp, _l, _i, _i, _i, _i, fp, fp, fp, fp, fp, fp, fp]),
+    "dpmn_render_words_warp_u8": (_i, [fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, _i, fp, _l, fp, _i, fp, _l, _i, _i, _i, _i, fp, fp, fp, fp, fp, fp,
+                                        fp, fp]),
     "dpmn_resize_windows_workspace_bytes": (_sz, [_l, _l, _i]),
     "dpmn_resize_windows_u8": (_i, [fp, _l, fp, _i, fp, _l, fp, _i, _l, _i, fp, _i, _i, fp, _sz, fp]),
     "dpmn_stitch_windows_u8": (_i, [fp, _l, _l, _i, _i, _i, _i, fp, _i, fp, _i, fp, _l, fp]),

@@ -18,7 +18,7 @@ constexpr int RD_MAX_LEN = 25;
 constexpr int RD_N_GLYPH = 37;
 constexpr int RD_PARAMS = 24;
 // columns of a params row (utils/render.py)
-constexpr int P_FONT = 0, P_CASE = 1, P_GH = 2, P_SPACING = 3, P_LEFT = 4, P_TOP = 6, P_SHEAR = 8, P_FG = 9, P_BG = 12, P_STYLE = 15,
+constexpr int P_FONT = 0, P_CASE = 1, P_GH = 2, P_SPACING = 3, P_LEFT = 4, P_RIGHT = 5, P_TOP = 6, P_SHEAR = 8, P_FG = 9, P_BG = 12, P_STYLE = 15,
               P_BG2 = 16, P_SEED = 19;
 
 // atlas coordinate of the scaled index i along one axis: pixel centres, Q16, clamped to [0, limit]
@@ -178,12 +178,88 @@ __device__ __forceinline__ int over(int colour, int a, int c) { return (colour *
 
 __device__ __forceinline__ int clampi(long long v, int lo, int hi) { return (int)min(max(v, (long long)lo), (long long)hi); }
 
-__global__ void __launch_bounds__(RD_THREADS)
-k_render_words_fx(const int* __restrict__ classes, const int* __restrict__ lengths, const long long* __restrict__ params,
-                  const long long* __restrict__ fx, const unsigned char* __restrict__ atlas, const int* __restrict__ advance,
-                  const int* __restrict__ atlas_h, const long long* __restrict__ items, const int* __restrict__ tiles, int n_tiles,
-                  const unsigned char* __restrict__ pool, long pool_bytes, const long long* __restrict__ photos, int n_photos,
-                  unsigned char* __restrict__ out, long out_bytes, int B, int n_fonts, int GH, int GW) {
+// the integer bilinear blend of one alpha cell, round half up (utils/render.py: alpha)
+__device__ __forceinline__ int cell_alpha(const unsigned char* cell, int GW, int x_0, int x_1, int y_0, int y_1, long long fx_, long long fy_) {
+  const long long a00 = cell[y_0 * GW + x_0], a01 = cell[y_0 * GW + x_1], a10 = cell[y_1 * GW + x_0], a11 = cell[y_1 * GW + x_1];
+  const unsigned long long t = (unsigned long long)(a00 * (65536 - fx_) + a01 * fx_), bt = (unsigned long long)(a10 * (65536 - fx_) + a11 * fx_);
+  return (int)((t * (unsigned long long)(65536 - fy_) + bt * (unsigned long long)fy_ + (1ull << 31)) >> 32);
+}
+
+// ---- Projective distortion, rotation and a curved baseline (main.py --train_words_warp): the semantics of utils/render.py
+// render_warp_u8 (the comment above N_WARP states every formula and the bound that keeps every intermediate below 2^62).
+constexpr int WP_COLS = 16;
+// columns of a warp row (utils/render.py)
+constexpr int W_FLAGS = 0, W_AMP = 1, W_ROOM = 2, W_COEF = 3, W_H = 12, W_W = 13;
+constexpr long long WP_COEF_MAX = 1ll << 30, WP_AMP_MAX = (1ll << 23) - 1;
+
+__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return min(max(v, lo), hi); }
+
+// floor(a / b) for b > 0: C++ truncates toward 0, the restatement floors
+__device__ __forceinline__ long long floordiv(long long a, long long b) {
+  const long long q = a / b;
+  return (a - q * b < 0) ? q - 1 : q;
+}
+
+// atlas coordinate of the Q16 position pos along one axis (axis_sample at a fractional index)
+__device__ __forceinline__ void warp_sample(long long pos, long long sc, int limit, int& i0, int& i1, long long& frac) {
+  long long q = ((pos * sc) >> 16) - 32768;
+  if (q < 0) q = 0;
+  i0 = (int)min(q >> 16, (long long)limit);
+  i1 = min(i0 + 1, limit);
+  frac = q & 0xFFFF;
+}
+
+struct WarpRow {
+  long long c[9], amp, off;      // off: room << 16 for a word that arches upward
+  int w0;                        // width of the flat canvas
+};
+
+// The alpha of output pixel (x, y) of a warped sample: two int64 floor divisions to the Q16 position on the bent flat canvas, the
+// parabola, the shear at the fractional row, a binary search of the pens in LDS for the LAST k with pen_k <= u (the walk from the
+// tile's leftmost column does not hold under a warp), the fractional atlas sample.
+__device__ __forceinline__ int warp_alpha(const WarpRow& wr, int x, int y, int top, int gh, int s, int x0, int tw, int n, const int* s_pen,
+                                          const int* s_adv, const int* s_cellw, const long* s_cell, const unsigned char* atlas, long long sc,
+                                          int A, int GW) {
+  const long long X = 2ll * x + 1, Y = 2ll * y + 1;
+  const long long den = wr.c[6] * X + wr.c[7] * Y + 2 * wr.c[8];
+  if (den <= 0) return 0;
+  const long long px = floordiv((wr.c[0] * X + wr.c[1] * Y + 2 * wr.c[2]) * 65536, den);
+  if (px < 0 || px >= ((long long)wr.w0 << 16)) return 0;
+  const long long py = floordiv((wr.c[3] * X + wr.c[4] * Y + 2 * wr.c[5]) * 65536, den);
+  long long p = 0;
+  if (wr.amp != 0) {
+    const long long xq = px >> 12, Wq = (long long)wr.w0 << 4;
+    p = floordiv(wr.amp * 4 * xq * (Wq - xq), Wq * Wq);
+  }
+  const long long vq = py - wr.off - p - ((long long)top << 16);
+  if (vq < 0 || vq >= ((long long)gh << 16)) return 0;
+  const long long uq = px - (((long long)s * ((((long long)gh - 1) << 16) + 32768 - vq)) >> 16) - ((long long)x0 << 16);
+  if (uq < 0 || uq >= ((long long)tw << 16)) return 0;
+  const int u = (int)(uq >> 16);
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (s_pen[mid] <= u) lo = mid; else hi = mid - 1;
+  }
+  const long long ugq = uq - ((long long)s_pen[lo] << 16);
+  if (ugq < 0 || ugq >= ((long long)s_adv[lo] << 16)) return 0;
+  int x_0, x_1, y_0, y_1;
+  long long fx_, fy_;
+  warp_sample(ugq, sc, s_cellw[lo] - 1, x_0, x_1, fx_);
+  warp_sample(vq, sc, A - 1, y_0, y_1, fy_);
+  return cell_alpha(atlas + s_cell[lo], GW, x_0, x_1, y_0, y_1, fx_, fy_);
+}
+
+// One tile of k_render_words_fx (WARP = false) and of k_render_words_warp (WARP = true: a sample whose warp flags are not 0 takes
+// warp_alpha for its alpha plane; everything behind the plane is the same code).
+template <bool WARP>
+__device__ __forceinline__ void
+render_fx_tile(const int* __restrict__ classes, const int* __restrict__ lengths, const long long* __restrict__ params,
+               const long long* __restrict__ fx, const long long* __restrict__ warp, const unsigned char* __restrict__ atlas,
+               const int* __restrict__ advance, const int* __restrict__ atlas_h, const long long* __restrict__ items,
+               const int* __restrict__ tiles, int n_tiles, const unsigned char* __restrict__ pool, long pool_bytes,
+               const long long* __restrict__ photos, int n_photos, unsigned char* __restrict__ out, long out_bytes, int B, int n_fonts,
+               int GH, int GW) {
   __shared__ int s_pen[RD_MAX_LEN + 1], s_adv[RD_MAX_LEN], s_cellw[RD_MAX_LEN];
   __shared__ long s_cell[RD_MAX_LEN];
   __shared__ int s_first;
@@ -235,25 +311,40 @@ k_render_words_fx(const int* __restrict__ classes, const int* __restrict__ lengt
   // ---- the alpha of the tile and its halo -> LDS, every thread (no thread has left the block yet)
   const int tw = max(s_pen[n] - sp, 1);
   const long long sc = ((long long)A << 16) / gh;
+  // the warp row, block-uniform; what is read of it is clamped to its domain (the coefficients to the bound of the 2^62 argument)
+  bool warped = false;
+  WarpRow wr = {};
+  if (WARP) {
+    const long long* Wr = warp + (size_t)b * WP_COLS;
+    warped = Wr[W_FLAGS] != 0;
+    if (warped) {
+#pragma unroll
+      for (int c = 0; c < 9; ++c) wr.c[c] = clampll(Wr[W_COEF + c], -WP_COEF_MAX, WP_COEF_MAX);
+      wr.amp = (Wr[W_FLAGS] & 4) ? clampll(Wr[W_AMP], -WP_AMP_MAX, WP_AMP_MAX) : 0;
+      wr.off = wr.amp < 0 ? clampll(Wr[W_ROOM], 0, RESIZE_MAX_SIDE) << 16 : 0;
+      wr.w0 = clampi((long long)left + tw + room + clampll(P[P_RIGHT], 0, RESIZE_MAX_SIDE), 1, RESIZE_MAX_SIDE);
+    }
+  }
   for (int idx = threadIdx.x; idx < FX_ROWS * FX_USED; idx += RD_THREADS) {
     const int ly = idx / FX_USED, lx = idx - ly * FX_USED;
     const int y = ty0 - FX_HALO + ly, x = tx0 - FX_HALO + lx;
     int alpha = 0;
     if (y >= 0 && y < h && x >= 0 && x < w) {
-      const int v = y - top, u = x - ((s * (base - y)) >> 16) - x0;
-      if (v >= 0 && v < gh && u >= 0 && u < tw) {
-        int k = s_first;
-        while (k + 1 < n && u >= s_pen[k + 1]) ++k;
-        const int ug = u - s_pen[k];
-        if (ug >= 0 && ug < s_adv[k]) {
-          int x_0, x_1, y_0, y_1;
-          long long fx_, fy_;
-          axis_sample(ug, sc, s_cellw[k] - 1, x_0, x_1, fx_);
-          axis_sample(v, sc, A - 1, y_0, y_1, fy_);
-          const unsigned char* cell = atlas + s_cell[k];
-          const long long a00 = cell[y_0 * GW + x_0], a01 = cell[y_0 * GW + x_1], a10 = cell[y_1 * GW + x_0], a11 = cell[y_1 * GW + x_1];
-          const unsigned long long t = (unsigned long long)(a00 * (65536 - fx_) + a01 * fx_), bt = (unsigned long long)(a10 * (65536 - fx_) + a11 * fx_);
-          alpha = (int)((t * (unsigned long long)(65536 - fy_) + bt * (unsigned long long)fy_ + (1ull << 31)) >> 32);
+      if (WARP && warped) {
+        alpha = warp_alpha(wr, x, y, top, gh, s, x0, tw, n, s_pen, s_adv, s_cellw, s_cell, atlas, sc, A, GW);
+      } else {
+        const int v = y - top, u = x - ((s * (base - y)) >> 16) - x0;
+        if (v >= 0 && v < gh && u >= 0 && u < tw) {
+          int k = s_first;
+          while (k + 1 < n && u >= s_pen[k + 1]) ++k;
+          const int ug = u - s_pen[k];
+          if (ug >= 0 && ug < s_adv[k]) {
+            int x_0, x_1, y_0, y_1;
+            long long fx_, fy_;
+            axis_sample(ug, sc, s_cellw[k] - 1, x_0, x_1, fx_);
+            axis_sample(v, sc, A - 1, y_0, y_1, fy_);
+            alpha = cell_alpha(atlas + s_cell[k], GW, x_0, x_1, y_0, y_1, fx_, fy_);
+          }
         }
       }
     }
@@ -354,6 +445,32 @@ k_render_words_fx(const int* __restrict__ classes, const int* __restrict__ lengt
   }
 }
 
+__global__ void __launch_bounds__(RD_THREADS)
+k_render_words_fx(const int* __restrict__ classes, const int* __restrict__ lengths, const long long* __restrict__ params,
+                  const long long* __restrict__ fx, const unsigned char* __restrict__ atlas, const int* __restrict__ advance,
+                  const int* __restrict__ atlas_h, const long long* __restrict__ items, const int* __restrict__ tiles, int n_tiles,
+                  const unsigned char* __restrict__ pool, long pool_bytes, const long long* __restrict__ photos, int n_photos,
+                  unsigned char* __restrict__ out, long out_bytes, int B, int n_fonts, int GH, int GW) {
+  render_fx_tile<false>(classes, lengths, params, fx, nullptr, atlas, advance, atlas_h, items, tiles, n_tiles, pool, pool_bytes, photos,
+                        n_photos, out, out_bytes, B, n_fonts, GH, GW);
+}
+
+// items: the canvas of a warped sample is its warp row's H x W (utils/render.py render_warp_meta)
+__global__ void __launch_bounds__(RD_THREADS)
+k_render_words_warp(const int* __restrict__ classes, const int* __restrict__ lengths, const long long* __restrict__ params,
+                    const long long* __restrict__ fx, const long long* __restrict__ warp, const unsigned char* __restrict__ atlas,
+                    const int* __restrict__ advance, const int* __restrict__ atlas_h, const long long* __restrict__ items,
+                    const int* __restrict__ tiles, int n_tiles, const unsigned char* __restrict__ pool, long pool_bytes,
+                    const long long* __restrict__ photos, int n_photos, unsigned char* __restrict__ out, long out_bytes, int B,
+                    int n_fonts, int GH, int GW) {
+  render_fx_tile<true>(classes, lengths, params, fx, warp, atlas, advance, atlas_h, items, tiles, n_tiles, pool, pool_bytes, photos,
+                       n_photos, out, out_bytes, B, n_fonts, GH, GW);
+}
+
+int check_fx_batch(int n_tiles, const unsigned char* pool_u8, long pool_bytes, const long long* photos, int n_photos, long out_bytes, int B,
+                   int n_fonts, int GH, int GW, const int* host_classes, const int* host_lengths, const long long* host_params,
+                   const long long* host_fx, const long long* host_meta, const long long* host_photos);
+
 }  // namespace
 
 extern "C" {
@@ -396,6 +513,23 @@ int dpmn_render_words_fx_u8(const int* classes, const int* lengths, const long l
                             const long long* host_params, const long long* host_fx, const long long* host_meta, const long long* host_photos,
                             dpmn_stream_t stream) {
   DPMN_REQUIRE(classes && lengths && params && fx && atlas_u8 && advance && atlas_h && meta && tiles && out_packed, "render_words_fx: null pointer");
+  const int rc = check_fx_batch(n_tiles, pool_u8, pool_bytes, photos, n_photos, out_bytes, B, n_fonts, GH, GW, host_classes, host_lengths,
+                                host_params, host_fx, host_meta, host_photos);
+  if (rc != DPMN_OK) return rc;
+  hipLaunchKernelGGL(k_render_words_fx, dim3((unsigned)n_tiles), dim3(RD_THREADS), 0, as_stream(stream), classes, lengths, params, fx, atlas_u8,
+                     advance, atlas_h, meta, tiles, n_tiles, pool_u8, pool_bytes, photos, n_photos, out_packed, out_bytes, B, n_fonts, GH, GW);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the host checks of dpmn_render_words_fx_u8, which dpmn_render_words_warp_u8 makes too
+int check_fx_batch(int n_tiles, const unsigned char* pool_u8, long pool_bytes, const long long* photos, int n_photos, long out_bytes, int B,
+                   int n_fonts, int GH, int GW, const int* host_classes, const int* host_lengths, const long long* host_params,
+                   const long long* host_fx, const long long* host_meta, const long long* host_photos) {
   DPMN_REQUIRE(host_classes && host_lengths && host_params && host_fx && host_meta, "render_words_fx: the host copies of classes, lengths, params, fx and meta are required (they are checked here)");
   DPMN_REQUIRE(B > 0 && B <= 65535, "render_words_fx: bad batch size (1 <= B <= 65535)");
   DPMN_REQUIRE(n_fonts > 0 && GH > 0 && GH <= 256 && GW > 0 && GW <= 1024, "render_words_fx: bad atlas (fonts >= 1, cell 1 .. 256 x 1 .. 1024)");
@@ -443,8 +577,43 @@ int dpmn_render_words_fx_u8(const int* classes, const int* lengths, const long l
     }
   }
   DPMN_REQUIRE(n_expected == n_tiles, "render_words_fx: the tile table does not cover the images (8 x 128 tiles)");
-  hipLaunchKernelGGL(k_render_words_fx, dim3((unsigned)n_tiles), dim3(RD_THREADS), 0, as_stream(stream), classes, lengths, params, fx, atlas_u8,
-                     advance, atlas_h, meta, tiles, n_tiles, pool_u8, pool_bytes, photos, n_photos, out_packed, out_bytes, B, n_fonts, GH, GW);
+  return DPMN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpmn_render_words_warp_u8(const int* classes, const int* lengths, const long long* params, const long long* fx, const long long* warp,
+                              const unsigned char* atlas_u8, const int* advance, const int* atlas_h, const long long* meta, const int* tiles,
+                              int n_tiles, const unsigned char* pool_u8, long pool_bytes, const long long* photos, int n_photos,
+                              unsigned char* out_packed, long out_bytes, int B, int n_fonts, int GH, int GW, const int* host_classes,
+                              const int* host_lengths, const long long* host_params, const long long* host_fx, const long long* host_warp,
+                              const long long* host_meta, const long long* host_photos, dpmn_stream_t stream) {
+  DPMN_REQUIRE(classes && lengths && params && fx && warp && atlas_u8 && advance && atlas_h && meta && tiles && out_packed, "render_words_warp: null pointer");
+  DPMN_REQUIRE(host_warp, "render_words_warp: the host copy of the warp rows is required (it is checked here)");
+  const int rc = check_fx_batch(n_tiles, pool_u8, pool_bytes, photos, n_photos, out_bytes, B, n_fonts, GH, GW, host_classes, host_lengths,
+                                host_params, host_fx, host_meta, host_photos);
+  if (rc != DPMN_OK) return rc;
+  // the warp rows whose flags are not 0 (utils/render.py check_render_warp)
+  for (int b = 0; b < B; ++b) {
+    const long long* Wr = host_warp + (size_t)b * WP_COLS;
+    DPMN_REQUIRE(Wr[W_FLAGS] >= 0 && Wr[W_FLAGS] <= 7, "render_words_warp: flags outside 0 .. 7");
+    if (Wr[W_FLAGS] == 0) continue;
+    DPMN_REQUIRE(Wr[W_W + 1] == 0 && Wr[W_W + 2] == 0, "render_words_warp: a spare column that is not 0");
+    for (int c = 0; c < 9; ++c)
+      DPMN_REQUIRE(Wr[W_COEF + c] >= -WP_COEF_MAX && Wr[W_COEF + c] <= WP_COEF_MAX, "render_words_warp: a coefficient of the map passes 2^30 (an intermediate could pass 2^62)");
+    const long long H = Wr[W_H], W = Wr[W_W];
+    DPMN_REQUIRE(H == host_meta[b * 4 + 1] && W == host_meta[b * 4 + 2], "render_words_warp: the canvas of a warped sample is not its row's H x W");
+    for (int k = 0; k < 4; ++k)
+      DPMN_REQUIRE(Wr[W_COEF + 6] * ((k & 1) ? W : 0) + Wr[W_COEF + 7] * ((k & 2) ? H : 0) + Wr[W_COEF + 8] > 0, "render_words_warp: den <= 0 at a corner of the output canvas");
+    const long long amp = Wr[W_AMP] < 0 ? -Wr[W_AMP] : Wr[W_AMP], gh = host_params[(size_t)b * RD_PARAMS + P_GH];
+    DPMN_REQUIRE((Wr[W_FLAGS] & 4) ? amp <= WP_AMP_MAX && amp * 10 <= 4 * 65536 * gh : amp == 0, "render_words_warp: amp outside its range (|amp| <= 0.4 gh in Q16 with the curve bit, 0 without it)");
+    DPMN_REQUIRE(Wr[W_ROOM] == ((amp + 65535) >> 16), "render_words_warp: room is not ceil(|amp|)");
+  }
+  hipLaunchKernelGGL(k_render_words_warp, dim3((unsigned)n_tiles), dim3(RD_THREADS), 0, as_stream(stream), classes, lengths, params, fx, warp,
+                     atlas_u8, advance, atlas_h, meta, tiles, n_tiles, pool_u8, pool_bytes, photos, n_photos, out_packed, out_bytes, B, n_fonts,
+                     GH, GW);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }

@@ -135,11 +135,13 @@ class alignCollate_realWTLAMask(object):
     positions 0 and 2 are None and `sr_batches` renders the HR images on the GPU (ops.render_words_u8) from the words and parameters
     it draws per batch; `render` is then True and `words` / `atlases` carry the pair.  render_fx (ours, needs render; main.py
     --train_words_fx): the utils.render.RenderFx of the run -- `sr_batches` then draws with draw_render_fx and renders with
-    ops.render_words_fx_u8 (outline, drop shadow, photo background)."""
+    ops.render_words_fx_u8 (outline, drop shadow, photo background).  render_warp (ours, needs render; main.py --train_words_warp):
+    the utils.render.RenderWarp of the run -- `sr_batches` then draws with draw_render_warp and renders with ops.render_words_warp_u8
+    (projective distortion, rotation, curved baseline; with or without render_fx)."""
 
     def __init__(self, imgH=64, imgW=256, down_sample_scale=4, keep_ratio=False, min_ratio=1, mask=False, alphabet=53, train=True,
                  y_domain=False, gpu_finish=False, gpu_resize=False, degrade=False, cutblur=False, jpeg=None, render=None,
-                 psf=None, render_fx=None):
+                 psf=None, render_fx=None, render_warp=None):
         if degrade and not gpu_resize:
             raise ValueError("alignCollate_realWTLAMask: degrade=True needs gpu_resize=True (the LR images are made on the GPU from the "
                              "packed HR pixels)")
@@ -177,6 +179,9 @@ class alignCollate_realWTLAMask(object):
         if render_fx and not self.render:
             raise ValueError("alignCollate_realWTLAMask: render_fx needs render=(words, atlases) (the effects are drawn on rendered words)")
         self.render_fx = render_fx or None
+        if render_warp and not self.render:
+            raise ValueError("alignCollate_realWTLAMask: render_warp needs render=(words, atlases) (the warp is drawn on rendered words)")
+        self.render_warp = render_warp or None
         self.imgH, self.imgW, self.down_sample_scale, self.mask = imgH, imgW, down_sample_scale, mask
         self.gpu_finish, self.gpu_resize, self.degrade, self.cutblur = gpu_finish, gpu_resize, bool(degrade), bool(cutblur)
         self.alphabet = "0123456789abcdefghijklmnopqrstuvwxyz"
@@ -293,7 +298,9 @@ def sr_batches(loader, device=None, mask=None, size=None):
     FIRST the words and render parameters (utils.render.draw_render, one sample per item of the batch), THEN exactly the draws of
     degrade_on_gpu; the HR images are rendered on the GPU (ops.render_words_u8) and the yielded labels are the drawn words.  With the
     collate's render_fx (main.py --train_words_fx) the draws are utils.render.draw_render_fx's (every sample's fx draws follow its
-    render draws, still before the degradation's) and the render is ops.render_words_fx_u8; without it nothing changes."""
+    render draws, still before the degradation's) and the render is ops.render_words_fx_u8; without it nothing changes.  With the
+    collate's render_warp (main.py --train_words_warp) the draws are utils.render.draw_render_warp's (every sample's warp draws follow
+    its fx draws) and the render is ops.render_words_warp_u8; without it nothing changes either."""
     import random
     col = getattr(loader, "collate_fn", None)
     if mask is None:
@@ -313,8 +320,12 @@ def sr_batches(loader, device=None, mask=None, size=None):
                 size = (col.imgH, col.imgW, col.down_sample_scale)
             H, W, scale = size
             rng = random.Random(pass_key + j)
-            fx = getattr(col, "render_fx", None)
-            if fx:
+            fx, warp = getattr(col, "render_fx", None), getattr(col, "render_warp", None)
+            if warp:
+                from ..utils.render import draw_render_warp
+                labels, cls, lens, params, rows, wrows = draw_render_warp(col.words, col.atlases.n_fonts, rng, len(labels), fx, warp)
+                pair = ops.render_words_warp_u8(cls, lens, params, rows, wrows, col.atlases, fx.pool if fx else None, device=device)
+            elif fx:
                 from ..utils.render import draw_render_fx
                 labels, cls, lens, params, rows = draw_render_fx(col.words, col.atlases.n_fonts, rng, len(labels), fx)
                 pair = ops.render_words_fx_u8(cls, lens, params, rows, col.atlases, fx.pool, device=device)

@@ -4,7 +4,8 @@ knows its label.  The loader's workers render nothing and never open the GPU: an
 render parameters of a batch in the main process (utils/render.py draw_render, from the per-pass keyed stream that --train_state
 restores), renders the batch on the GPU (ops.render_words_u8) and degrades it like a batch of --train_hr_dir.  With --train_words_fx the
 collate function also carries the utils.render.RenderFx (kinds, probability, background pool): the draws are then draw_render_fx's
-and the render is ops.render_words_fx_u8; the workers still see word indices only.  The set has no end of its
+and the render is ops.render_words_fx_u8; with --train_words_warp it carries the utils.render.RenderWarp too (kinds, probability,
+magnitudes): draw_render_warp's draws and ops.render_words_warp_u8.  The workers still see word indices only.  The set has no end of its
 own: its length is the number of samples that counts as one epoch, and what a DistributedSampler shards."""
 import torch
 

@@ -207,7 +207,8 @@ class TextBase(object):
         from (ops.psf_blur_ragged_u8 in sr_batches).  words=(words, atlases, epoch size)
         (--train_words): no image data at all -- dataset/words.py WordsHR, the HR images are rendered on the GPU by sr_batches
         (ops.render_words_u8), always degraded; a fourth item, the utils.render.RenderFx of --train_words_fx (or None), makes that
-        ops.render_words_fx_u8: outline, drop shadow, photo background."""
+        ops.render_words_fx_u8: outline, drop shadow, photo background; a fifth item, the utils.render.RenderWarp of
+        --train_words_warp (or None), makes it ops.render_words_warp_u8: projective distortion, rotation, curved baseline."""
         from ..dataset import textzoom as tz
         cfg = self.config.TRAIN
         degrade = bool(degrade or hr_dir or words)
@@ -238,7 +239,8 @@ class TextBase(object):
                                                     gpu_resize=gpu_finish and (gpu_resize or degrade or bool(getattr(self.args, "gpu_resize", False))),
                                                     degrade=degrade, cutblur=cutblur, jpeg=jpeg, psf=psf,
                                                     render=(words[0], words[1]) if words else None,
-                                                    render_fx=words[3] if words and len(words) > 3 else None))
+                                                    render_fx=words[3] if words and len(words) > 3 else None,
+                                                    render_warp=words[4] if words and len(words) > 4 else None))
         # (dataset/textzoom.py; uint8 pixels in the batch); False: the reference's float (B, 3 + mask, H, W) tensors for consumers that
         # iterate the loader themselves
         if shard:
@@ -246,9 +248,10 @@ class TextBase(object):
         return ds, loader
 
     def get_train_data(self, train_words=None):
-        """train_words (main.py --train_words): (words, atlases, epoch size[, fx]) -- the filtered word list, utils.render.build_atlases
-        of the fonts, the number of samples that counts as one epoch and, optionally, the utils.render.RenderFx of --train_words_fx;
-        the training set is then rendered from it."""
+        """train_words (main.py --train_words): (words, atlases, epoch size[, fx[, warp]]) -- the filtered word list,
+        utils.render.build_atlases of the fonts, the number of samples that counts as one epoch and, optionally, the
+        utils.render.RenderFx of --train_words_fx (or None) and the utils.render.RenderWarp of --train_words_warp; the training set is
+        then rendered from it."""
         cfg = self.config.TRAIN
         degrade, cutblur = degrade_flags(self.args)
         hr_dir = getattr(self.args, "train_hr_dir", None)

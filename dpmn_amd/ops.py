@@ -545,6 +545,61 @@ def render_words_fx_u8(words_cls, lengths, params, fx, atlases, pool=None, devic
     return out, torch.from_numpy(m)
 
 
+def render_words_warp_u8(words_cls, lengths, params, fx, warp, atlases, pool=None, device=None, out=None):
+    """render_words_fx_u8 with the text under a projective map and on a curved baseline per sample (csrc/render.hip
+    k_render_words_warp; main.py --train_words_warp): warp (B, 16) = the rows of utils.render.draw_render_warp -> (packed, meta) in the
+    same layout at the sizes of utils.render.render_warp_meta, byte for byte utils.render.render_warp_u8 per image; a warp row whose
+    flags are 0 gives render_words_fx_u8's image.  One upload of the rows, one launch.  Validated on the host; no CPU fallback."""
+    import numpy as np
+    from .utils import render as rd
+    if not torch.cuda.is_available():
+        raise _abi.DpmnError("render_words_warp_u8: the images are rendered on the GPU; there is no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise _abi.DpmnError("render_words_warp_u8: the images are rendered on the GPU (got device %s); there is no CPU fallback" % dev)
+    to_np = lambda a: a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    try:
+        cls, lens, p = rd.check_render(to_np(words_cls), to_np(lengths), to_np(params), atlases)
+        fxr = rd.check_render_fx(to_np(fx), pool, n=lens.shape[0])
+        wr = rd.check_render_warp(to_np(warp), p, n=lens.shape[0])
+        m = rd.render_warp_meta(cls, lens, p, wr, atlases)
+    except ValueError as e:
+        raise _abi.DpmnError("render_words_warp_u8: %s" % e)
+    B = m.shape[0]
+    nbytes = int(m[-1, 0] + m[-1, 1] * m[-1, 2] * 3)
+    if B > 65535 or nbytes > 2 ** 31 - 1:
+        raise _abi.DpmnError("render_words_warp_u8: at most 65535 images and 2^31 - 1 bytes per batch")
+    tiles, first = _tile_table(m[:, 1], m[:, 2], *RENDER_TILE)
+    n_tiles = tiles.shape[0]
+    # one upload, as render_words_fx_u8's, with the warp rows in it
+    host, (o_meta, o_par, o_fx, o_wr, o_cls, o_len, o_til) = _pack(np.concatenate((m, first[:-1, None]), axis=1), p, fxr, wr, cls, lens, tiles)
+    d = torch.from_numpy(host).to(dev)
+    key = (dev.type, dev.index)
+    if key not in atlases._device:
+        atlases._device[key] = (torch.from_numpy(atlases.alpha).to(dev), torch.from_numpy(atlases.advance).to(dev),
+                                torch.from_numpy(atlases.height).to(dev))
+    alpha, adv, hts = atlases._device[key]
+    pix = tab = None
+    if pool is not None:
+        if key not in pool._device:
+            pool._device[key] = (torch.from_numpy(pool.pixels).to(dev), torch.from_numpy(pool.table).to(dev))
+        pix, tab = pool._device[key]
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif (not torch.is_tensor(out) or out.device != dev or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous()
+          or out.numel() < nbytes):
+        raise _abi.DpmnError("render_words_warp_u8: out must be a contiguous 1-D uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+    dp, hp = d.data_ptr(), host.ctypes.data
+    check(lib.dpmn_render_words_warp_u8(dp + 8 * o_cls, dp + 8 * o_len, dp + 8 * o_par, dp + 8 * o_fx, dp + 8 * o_wr, alpha.data_ptr(),
+                                        adv.data_ptr(), hts.data_ptr(), dp + 8 * o_meta, dp + 8 * o_til, n_tiles,
+                                        None if pix is None else pix.data_ptr(), 0 if pix is None else pix.numel(),
+                                        None if tab is None else tab.data_ptr(), 0 if pool is None else pool.n_photos, out.data_ptr(),
+                                        out.numel(), B, atlases.n_fonts, alpha.shape[3], alpha.shape[4], hp + 8 * o_cls, hp + 8 * o_len,
+                                        hp + 8 * o_par, hp + 8 * o_fx, hp + 8 * o_wr, hp + 8 * o_meta,
+                                        None if pool is None else pool.table.ctypes.data, stream()))
+    return out, torch.from_numpy(m)
+
+
 def jpeg_roundtrip_u8(images_u8, quality, out=None):
     """JPEG artefacts (csrc/jpeg.hip): images_u8 = a contiguous (B, h, w, 3) uint8 RGB batch on the device, quality = B integers (a
     sequence or a tensor), 1 .. 100 per image or 0 for "leave this image alone" -> a new (B, h, w, 3) uint8 device tensor, per image

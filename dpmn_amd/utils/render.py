@@ -6,7 +6,9 @@ from PIL's own draw.text of the whole string: there is NO KERNING AND NO LIGATUR
 k_text_prior (csrc/visionlan.hip) lays its strings out.  A character without a glyph in the atlas (punctuation under voc_type 'all') is
 drawn as the blank of class 0; the label keeps it.  Pure NumPy: importable on any machine (PIL only inside build_atlases and
 load_backgrounds).  Outline, drop shadow and photo backgrounds (main.py --train_words_fx) stand beside all this at the end of the module:
-draw_render_fx, check_render_fx, render_fx_u8.
+draw_render_fx, check_render_fx, render_fx_u8; behind them projective distortion, rotation and a curved baseline (main.py
+--train_words_warp): draw_render_warp, warp_row, check_render_warp, render_warp_meta, render_warp_u8 (the columns of a warp row and every
+formula: the comment above N_WARP).
 
 Columns of a params row (int64, 24 per sample):
    0 font        index of the atlas
@@ -129,13 +131,16 @@ def build_atlases(font_paths=None, heights=BASE_H):
     return Atlases(alpha, np.stack([c[1] for c in cells]), [c[2] for c in cells], [c[3] for c in cells])
 
 
-def words_setting(words, atlases, epoch, fx=None):
+def words_setting(words, atlases, epoch, fx=None, warp=None):
     """The value of the `train_words` field of the --train_state fingerprint (interfaces/base.py): the crc32 of the filtered word
     list, the sorted font names and the epoch size; with a RenderFx (main.py --train_words_fx), and only then, also its kinds, its
-    probability and the crc32 of its background pool (None without one)."""
+    probability and the crc32 of its background pool (None without one); with a RenderWarp (main.py --train_words_warp), and only
+    then, also its kinds, its probability and its three magnitudes."""
     s = {"crc32": zlib.crc32("\n".join(words).encode("utf-8")) & 0xFFFFFFFF, "fonts": sorted(atlases.names), "epoch": int(epoch)}
     if fx:
         s.update(fx_kinds=list(fx.kinds), fx_prob=float(fx.prob), fx_pool=None if fx.pool is None else int(fx.pool.crc32))
+    if warp:
+        s.update(warp_setting(warp))
     return s
 
 
@@ -572,10 +577,12 @@ def _fx_planes(alpha, fxr):
     return a_s, a_o
 
 
-def _render_fx(cls, row, fxr, atlases, pool, grain_plane=None):
+def _render_fx(cls, row, fxr, atlases, pool, grain_plane=None, alpha=None):
     """render_fx_u8 behind its checks: the fx row is taken as it is (a test may pass m = 256, the crop's own bytes), grain_plane
-    (h, w) replaces the grain of the row's seed."""
-    alpha = _alpha_plane(cls, row, atlases)
+    (h, w) replaces the grain of the row's seed, alpha (h, w) the plane of _alpha_plane (render_warp_u8: the warped plane, whose
+    shape is then the canvas)."""
+    if alpha is None:
+        alpha = _alpha_plane(cls, row, atlases)
     h, w = alpha.shape
     ys, xs = np.arange(h, dtype=np.int64)[:, None], np.arange(w, dtype=np.int64)[None, :]
     bg, bg2 = row[BG:BG + 3][None, None, :], row[BG2:BG2 + 3][None, None, :]
@@ -619,3 +626,298 @@ def render_fx_u8(word_classes_, params_row, fx_row, atlases, pool=None):
     check_render(np.pad(np.asarray(cls, np.int32), (0, MAX_LEN - len(cls)))[None], [len(cls)], row[None], atlases)
     fxr = check_render_fx(np.asarray(fx_row, np.int64)[None], pool)[0]
     return _render_fx(cls, row, fxr, atlases, pool)
+
+
+# ----------------------------------------------------------------------- projective distortion, rotation, curved baseline (the warp path)
+# main.py --train_words_warp: two more stages of the synthetic-text recipes (MJSynth's projective distortion, SynthText's curved
+# baseline) BESIDE the two renderers above, which stay as they are -- the draws of a sample (`draw_render_warp`: draw_render_fx's, then
+# the warp draws), the host's one computation of a warp row (`warp_row`, Python floats), the domain of a row (`check_render_warp`), the
+# canvas sizes (`render_warp_meta`, the sibling of render_meta) and the NumPy restatement of the image (`render_warp_u8`), the CPU
+# reference of k_render_words_warp (csrc/render.hip through ops.render_words_warp_u8).  Only the TEXT is warped (the fill alpha and
+# what the outline and the shadow take from it, on the warped plane, in output pixels); the background stays a function of the output
+# pixel.  A row whose flags are 0 is not read: the sample takes the integer path above, canvas and bytes are render_fx_u8's.
+#
+# Columns of a warp row (int64, 16 per sample):
+#    0 flags      bit 0 perspective, bit 1 rotate, bit 2 curve
+#    1 amp        the parabola's height in the middle of the canvas, Q16 pixels, signed (negative: the word arches upward);
+#                 |amp| <= CURVE_MAX * gh; 0 without the curve bit
+#    2 room       ceil(|amp|) in whole pixels: the bent flat canvas is layout's w0 x (h0 + room)
+#    3 .. 11      c0 .. c8, the INVERSE projective map, output pixel -> bent flat canvas, normalised so that the largest magnitude
+#                 is COEF_MAX = 2^30 and rounded to integers; THESE INTEGERS ARE THE DEFINITION, nothing is solved later
+#   12, 13        H, W: the output canvas, the bounding box of the forward-mapped corners of the bent flat canvas moved to the origin,
+#                 1 .. MAX_SIDE
+#   14, 15        spare, 0
+#
+# The alpha of output pixel (x, y), integers only, every division a FLOOR division (the flat coordinates go negative left of and
+# above the text), positions in Q16 with a pixel's centre at i + 1/2:
+#   map       X = 2 x + 1, Y = 2 y + 1 (twice the pixel centre);  den = c6 X + c7 Y + 2 c8 (> 0 on the whole canvas: checked at its
+#             four corners);  px = ((c0 X + c1 Y + 2 c2) * 65536) // den,  py = ((c3 X + c4 Y + 2 c5) * 65536) // den
+#             bound: |c| <= 2^30, X, Y <= 2^14 - 1, so |numerator| < 2^30 * 2^15 and |numerator * 65536| < 2^61.0001 < 2^62
+#   column    alpha 0 unless 0 <= px < w0 * 65536
+#   parabola  xq = px >> 12, Wq = w0 << 4 (sixteenths of a pixel);  p = (amp * 4 * xq * (Wq - xq)) // (Wq * Wq) -- 0 at both ends,
+#             amp in the middle; |amp| < 2^23 and 4 xq (Wq - xq) <= Wq^2 <= 2^34, so the product stays below 2^57;
+#             vq = py - (room << 16 if amp < 0 else 0) - p - (top << 16);  alpha 0 unless 0 <= vq < gh * 65536
+#   shear     uq = px - ((s * (((gh - 1) << 16) + 32768 - vq)) >> 16) - (x0 << 16): the shear of render_u8 at the fractional row (not
+#             floored to whole pixels);  alpha 0 unless 0 <= uq < tw * 65536
+#   glyph     the LAST k with pen_k <= uq >> 16, as render_u8;  ugq = uq - (pen_k << 16);  alpha 0 in the gap (ugq >= a_k * 65536)
+#   sample    the atlas cell at ((pos * sc) >> 16) - 32768 with sc = (A << 16) // gh, pos = ugq along x (clamped to the cell's width)
+#             and vq along y -- at a pixel's centre, pos = (2 i + 1) << 15, this is render_u8's coordinate exactly; the same integer
+#             bilinear blend, round half up
+# Then the stages of render_fx_u8 on the H x W canvas with this plane: background, texture (the crop stretched over H x W), grain,
+# shadow, outline, fill.  The columns are displaced, the glyphs are not turned along the curve; nothing is prefiltered.
+N_WARP = 16
+(WP_FLAGS, WP_AMP, WP_ROOM, WP_COEF, WP_H, WP_W) = (0, 1, 2, 3, 12, 13)
+WARP_KINDS = ("perspective", "rotate", "curve")      # bit k of the flags: kind k
+COEF_MAX = 1 << 30           # the largest magnitude of a coefficient: what keeps numerator * 65536 below 2^62 on canvases up to MAX_SIDE
+PERSP_MAX, ANGLE_MAX, CURVE_MAX = 0.3, 20.0, 0.4      # the upper ends of --train_words_warp_persp / _angle / _curve
+
+
+def warp_kinds(kinds, prob=0.5, persp=0.15, angle=10.0, curve=0.2):
+    """The checks of --train_words_warp / _prob / _persp / _angle / _curve on the values alone -> the kinds in WARP_KINDS' order;
+    ValueError with the one line main.py prints."""
+    kinds = [str(k) for k in kinds]
+    if not kinds or len(set(kinds)) != len(kinds) or any(k not in WARP_KINDS for k in kinds):
+        raise ValueError("--train_words_warp takes a comma list of distinct kinds of %s, got %r" % (", ".join(WARP_KINDS), ",".join(kinds)))
+    if not 0.0 <= float(prob) <= 1.0:          # (NaN fails both comparisons)
+        raise ValueError("--train_words_warp_prob must be a probability in 0 .. 1, got %r" % (prob,))
+    if not 0.0 < float(persp) <= PERSP_MAX:
+        raise ValueError("--train_words_warp_persp must be a fraction of the glyph height in 0 < F <= %g, got %r" % (PERSP_MAX, persp))
+    if not 0.0 < float(angle) <= ANGLE_MAX:
+        raise ValueError("--train_words_warp_angle must be an angle in degrees in 0 < DEG <= %g, got %r" % (ANGLE_MAX, angle))
+    if not 0.0 < float(curve) <= CURVE_MAX:
+        raise ValueError("--train_words_warp_curve must be a fraction of the glyph height in 0 < F <= %g, got %r" % (CURVE_MAX, curve))
+    return tuple(k for k in WARP_KINDS if k in kinds)
+
+
+class RenderWarp(object):
+    """The warp setting of a run: kinds (of WARP_KINDS, kept in that order), prob (each listed kind is on per sample with this
+    probability, independently), persp / angle / curve (the three magnitudes) and atlases (the warp is drawn against the sample's flat
+    canvas, which layout computes from them)."""
+
+    def __init__(self, kinds, prob=0.5, persp=0.15, angle=10.0, curve=0.2, atlases=None):
+        self.kinds = warp_kinds(kinds, prob, persp, angle, curve)
+        if atlases is None:
+            raise ValueError("RenderWarp: the warp needs the atlases (it is drawn against the flat canvas)")
+        self.prob, self.persp, self.angle, self.curve, self.atlases = float(prob), float(persp), float(angle), float(curve), atlases
+
+
+def warp_setting(warp):
+    """The fields a RenderWarp adds to words_setting."""
+    return dict(warp_kinds=list(warp.kinds), warp_prob=float(warp.prob), warp_persp=float(warp.persp), warp_angle=float(warp.angle),
+                warp_curve=float(warp.curve))
+
+
+def warp_quad(h0, w0, room=0, angle=0.0, jitter=None):
+    """The forward image of the corners of the bent flat canvas (w0 x (h0 + room); top left, top right, bottom right, bottom left)
+    before it is moved to the origin, in Python floats: turned about the canvas' centre by `angle` degrees (positive: clockwise on the
+    screen, y pointing down), then every corner moved by its own jitter[k] = (dx, dy) pixels."""
+    import math
+    hb = h0 + room
+    cx, cy = w0 / 2.0, hb / 2.0
+    co, si = math.cos(math.radians(angle)), math.sin(math.radians(angle))
+    quad = []
+    for k, (x, y) in enumerate(((0, 0), (w0, 0), (w0, hb), (0, hb))):
+        qx, qy = cx + co * (x - cx) - si * (y - cy), cy + si * (x - cx) + co * (y - cy)
+        if jitter is not None:
+            qx, qy = qx + float(jitter[k][0]), qy + float(jitter[k][1])
+        quad.append((qx, qy))
+    return quad
+
+
+def warp_row(h0, w0, flags, amp=0, angle=0.0, jitter=None):
+    """One warp row from the flat canvas h0 x w0 of layout and the drawn magnitudes: amp (Q16 pixels; read with the curve bit), angle
+    (degrees; with the rotate bit), jitter (four (dx, dy) in pixels; with the perspective bit).  ONE projective map takes the corners
+    of the bent flat canvas to warp_quad's; its inverse (the adjugate), scaled so that the largest magnitude is COEF_MAX and rounded
+    half up, is the row.  flags 0 -> a row of zeros.  ValueError where the quadrilateral is not convex enough for den > 0."""
+    import math
+    row = np.zeros(N_WARP, np.int64)
+    flags = int(flags)
+    if not flags:
+        return row
+    amp = int(amp) if flags & 4 else 0
+    room = (abs(amp) + 65535) >> 16
+    hb = h0 + room
+    quad = warp_quad(h0, w0, room, angle if flags & 2 else 0.0, jitter if flags & 1 else None)
+    x_min, y_min = min(q[0] for q in quad), min(q[1] for q in quad)
+    W = min(max(int(math.ceil(max(q[0] for q in quad) - x_min)), 1), MAX_SIDE)
+    H = min(max(int(math.ceil(max(q[1] for q in quad) - y_min)), 1), MAX_SIDE)
+    (x0, y0), (x1, y1), (x2, y2), (x3, y3) = [(q[0] - x_min, q[1] - y_min) for q in quad]
+    # the unit square -> the quadrilateral (Heckbert), then the flat canvas -> the unit square
+    dx1, dx2, sx, dy1, dy2, sy = x1 - x2, x3 - x2, x0 - x1 + x2 - x3, y1 - y2, y3 - y2, y0 - y1 + y2 - y3
+    det = dx1 * dy2 - dy1 * dx2
+    if det == 0.0:
+        raise ValueError("render_warp: a degenerate quadrilateral")
+    g, h = (sx * dy2 - dx2 * sy) / det, (dx1 * sy - sx * dy1) / det
+    F = [[(x1 - x0 + g * x1) / w0, (x3 - x0 + h * x3) / hb, x0], [(y1 - y0 + g * y1) / w0, (y3 - y0 + h * y3) / hb, y0], [g / w0, h / hb, 1.0]]
+    (a, b, c), (d, e, f), (g, h, i) = F
+    inv = [e * i - f * h, c * h - b * i, b * f - c * e, f * g - d * i, a * i - c * g, c * d - a * f, d * h - e * g, b * g - a * h, a * e - b * d]
+    if inv[6] * W / 2.0 + inv[7] * H / 2.0 + inv[8] < 0.0:
+        inv = [-v for v in inv]
+    scale = COEF_MAX / max(abs(v) for v in inv)
+    row[WP_FLAGS], row[WP_AMP], row[WP_ROOM], row[WP_H], row[WP_W] = flags, amp, room, H, W
+    row[WP_COEF:WP_COEF + 9] = [int(math.floor(v * scale + 0.5)) for v in inv]
+    c = [int(v) for v in row[WP_COEF:WP_COEF + 9]]
+    if min(c[6] * X + c[7] * Y + c[8] for X in (0, W) for Y in (0, H)) <= 0:
+        raise ValueError("render_warp: the quadrilateral is not convex enough (den <= 0 at a corner of the canvas)")
+    return row
+
+
+def draw_render_warp(words, n_fonts, rng, n=1, fx=(), warp=()):
+    """draw_render_fx plus the warp rows: -> (labels, classes, lengths, params, fx (n, 20), warp (n, 16) int64).  warp: a RenderWarp,
+    or () / None: no warp draw at all and rows of zeros -- the stream is then draw_render_fx's exactly.  Sample by sample: exactly
+    the draws of draw_render_fx for ONE sample, then for every LISTED kind in the order perspective, rotate, curve one random() -- the
+    kind is on where it is below prob -- followed at once, where the kind is on, by its parameters, every one (2 * random() - 1) * limit:
+      perspective   dx, dy of the top left, top right, bottom right, bottom left corner (8 draws); limit = persp * gh, and never more
+                    than a quarter of the bent flat canvas' side along that axis (the quadrilateral stays convex)
+      rotate        the angle in degrees; limit = angle
+      curve         amp = int(. * 65536) in Q16 pixels (truncated toward 0); limit = curve * gh
+    A kind that is not listed makes no draw; one that is listed and off makes the one.  Only rng.random() is called here.  The row is
+    warp_row's of the sample's flat canvas (layout) and these magnitudes; where warp_row refuses them (den <= 0 at a corner of the
+    bounding box: a narrow word, strongly keystoned and turned) the jitter is halved, up to five times, and then dropped -- no draw
+    is added."""
+    n = int(n)
+    out = ([], [], [], [], [])
+    rows = np.zeros((max(n, 0), N_WARP), np.int64)
+    if n < 1:
+        draw_render_fx(words, n_fonts, rng, n, fx)          # (its ValueError)
+    for i in range(n):
+        one = draw_render_fx(words, n_fonts, rng, 1, fx)
+        out[0].extend(one[0])
+        for dst, src in zip(out[1:], one[1:]):
+            dst.append(src)
+        if not warp:
+            continue
+        p = one[3][0]
+        gh, flags, units, turn, amp = int(p[GH]), 0, None, 0.0, 0
+        if "perspective" in warp.kinds and rng.random() < warp.prob:
+            flags |= 1
+            units = [2.0 * rng.random() - 1.0 for _ in range(8)]
+        if "rotate" in warp.kinds and rng.random() < warp.prob:
+            flags |= 2
+            turn = (2.0 * rng.random() - 1.0) * warp.angle
+        if "curve" in warp.kinds and rng.random() < warp.prob:
+            flags |= 4
+            amp = int((2.0 * rng.random() - 1.0) * warp.curve * gh * 65536.0)
+        if flags:
+            h0, w0 = layout(one[1][0, :one[2][0]].tolist(), p, warp.atlases)[:2]
+            jitter = None
+            if units:
+                lx, ly = min(warp.persp * gh, w0 / 4.0), min(warp.persp * gh, (h0 + ((abs(amp) + 65535) >> 16)) / 4.0)
+                jitter = [(units[2 * k] * lx, units[2 * k + 1] * ly) for k in range(4)]
+            for _ in range(6):          # den > 0 is asked on the whole bounding box, which a turned narrow word can push past the horizon
+                try:
+                    rows[i] = warp_row(h0, w0, flags, amp, turn, jitter)
+                    break
+                except ValueError:
+                    jitter = [(dx / 2.0, dy / 2.0) for dx, dy in jitter]
+            else:
+                rows[i] = warp_row(h0, w0, flags & 6, amp, turn) if flags & 6 else 0
+    return (out[0],) + tuple(np.concatenate(a) for a in out[1:]) + (rows,)
+
+
+def check_render_warp(warp, params, n=None):
+    """ValueError for a warp row outside its domain (what the kernel's entry point rejects too); params: the samples' params rows (the
+    range of amp follows gh).  A row with flags 0 is not read; of the others: the spare columns are 0, no coefficient passes COEF_MAX
+    (the bound that keeps every intermediate below 2^62), the canvas is 1 .. MAX_SIDE a side, den > 0 at its four corners, |amp| <=
+    CURVE_MAX * gh and room = ceil(|amp|) with the curve bit, both 0 without it -> the rows as (n, 16) int64."""
+    warp = np.ascontiguousarray(warp, np.int64)
+    params = np.ascontiguousarray(params, np.int64)
+    if (warp.ndim != 2 or warp.shape[1] != N_WARP or warp.shape[0] < 1 or (n is not None and warp.shape[0] != n)
+            or params.shape != (warp.shape[0], N_PARAMS)):
+        raise ValueError("render_warp: warp (n, %d) with one row per sample and params (n, %d) expected, got %s %s"
+                         % (N_WARP, N_PARAMS, warp.shape, params.shape))
+    fl = warp[:, WP_FLAGS]
+    if fl.min() < 0 or fl.max() > 7:
+        raise ValueError("render_warp: flags outside 0 .. 7")
+    on = fl != 0
+    r, gh = warp[on], params[on, GH]
+    if not r.size:
+        return warp
+    if r[:, WP_W + 1:].any():
+        raise ValueError("render_warp: a spare column that is not 0")
+    c = r[:, WP_COEF:WP_COEF + 9]
+    if np.abs(c).max() > COEF_MAX:
+        raise ValueError("render_warp: a coefficient of the map passes 2^30 (an intermediate could pass 2^62)")
+    H, W = r[:, WP_H], r[:, WP_W]
+    if min(H.min(), W.min()) < 1 or max(H.max(), W.max()) > MAX_SIDE:
+        raise ValueError("render_warp: a canvas side outside 1 .. %d" % MAX_SIDE)
+    for X in (0, W):
+        for Y in (0, H):
+            if (c[:, 6] * X + c[:, 7] * Y + c[:, 8] <= 0).any():
+                raise ValueError("render_warp: den <= 0 at a corner of the output canvas (the map folds the canvas over)")
+    amp, room, curve = r[:, WP_AMP], r[:, WP_ROOM], (r[:, WP_FLAGS] & 4) != 0
+    if (np.abs(amp) * 10 > int(CURVE_MAX * 10) * 65536 * gh).any() or (room != ((np.abs(amp) + 65535) >> 16)).any() or amp[~curve].any():
+        raise ValueError("render_warp: amp outside its range (|amp| <= %g gh in Q16 with the curve bit, 0 without it), or room is not "
+                         "ceil(|amp|)" % CURVE_MAX)
+    return warp
+
+
+def render_warp_meta(classes, lengths, params, warp, atlases):
+    """render_meta for warped samples: (n, 3) int64 of (byte offset, h, w) -- a sample with flags 0 has layout's canvas, any other
+    the H x W of its row."""
+    meta = render_meta(classes, lengths, params, atlases)
+    warp = check_render_warp(warp, params, n=meta.shape[0])
+    on = warp[:, WP_FLAGS] != 0
+    meta[on, 1], meta[on, 2] = warp[on, WP_H], warp[on, WP_W]
+    sizes = meta[:, 1] * meta[:, 2] * 3
+    meta[:, 0] = np.cumsum(sizes) - sizes
+    return meta
+
+
+def _warp_sample(pos, A, gh, limit):
+    """Atlas coordinates of the Q16 positions pos along one axis: _axis_sample at a fractional index."""
+    q = np.maximum(((pos * ((A << 16) // gh)) >> 16) - 32768, 0)
+    i0 = np.minimum(q >> 16, limit)
+    return i0, np.minimum(i0 + 1, limit), q & 0xFFFF
+
+
+def _alpha_plane_warp(cls, row, wr, atlases):
+    """The alpha plane (H, W) int64 of a warped sample (the comment above states every formula); flags 0: _alpha_plane."""
+    if not int(wr[WP_FLAGS]):
+        return _alpha_plane(cls, row, atlases)
+    f, gh, s, top = int(row[FONT]), int(row[GH]), int(row[SHEAR]), int(row[M_TOP])
+    A = int(atlases.height[f])
+    h0, w0, pens, advs, planes, room_s, x0 = layout(cls, row, atlases)
+    n = len(cls)
+    tw = max(pens[n] - int(row[SPACING]), 1)
+    H, W, amp, room = int(wr[WP_H]), int(wr[WP_W]), int(wr[WP_AMP]), int(wr[WP_ROOM])
+    c = [int(v) for v in wr[WP_COEF:WP_COEF + 9]]
+    Y, X = 2 * np.arange(H, dtype=np.int64)[:, None] + 1, 2 * np.arange(W, dtype=np.int64)[None, :] + 1
+    den = c[6] * X + c[7] * Y + 2 * c[8]
+    px, py = ((c[0] * X + c[1] * Y + 2 * c[2]) * 65536) // den, ((c[3] * X + c[4] * Y + 2 * c[5]) * 65536) // den
+    ok = (px >= 0) & (px < (w0 << 16))
+    px = np.where(ok, px, 0)
+    xq, Wq = px >> 12, w0 << 4
+    vq = py - ((room << 16) if amp < 0 else 0) - (amp * 4 * xq * (Wq - xq)) // (Wq * Wq) - (top << 16)
+    ok &= (vq >= 0) & (vq < (gh << 16))
+    vq = np.where(ok, vq, 0)
+    uq = px - ((s * (((gh - 1) << 16) + 32768 - vq)) >> 16) - (x0 << 16)
+    ok &= (uq >= 0) & (uq < (tw << 16))
+    uq = np.where(ok, uq, 0)
+    pens_a = np.asarray(pens[:n], np.int64)
+    k = np.clip(np.searchsorted(pens_a, uq >> 16, side="right") - 1, 0, n - 1)
+    ugq = uq - (pens_a[k] << 16)
+    ok &= ugq < (np.asarray(advs, np.int64)[k] << 16)
+    ugq = np.where(ok, ugq, 0)
+    pk, ck = np.asarray(planes)[k], np.asarray(cls)[k]
+    cell_w = atlases.advance[f][pk, ck].astype(np.int64)
+    x_0, x_1, fx = _warp_sample(ugq, A, gh, np.maximum(cell_w - 1, 0))
+    y_0, y_1, fy = _warp_sample(vq, A, gh, A - 1)
+    at = atlases.alpha[f].astype(np.int64)
+    t = at[pk, ck, y_0, x_0] * (65536 - fx) + at[pk, ck, y_0, x_1] * fx
+    b = at[pk, ck, y_1, x_0] * (65536 - fx) + at[pk, ck, y_1, x_1] * fx
+    return np.where(ok, (t * (65536 - fy) + b * fy + (1 << 31)) >> 32, 0)
+
+
+def render_warp_u8(word_classes_, params_row, fx_row, warp_row_, atlases, pool=None):
+    """One sample -> its (H, W, 3) uint8 image with the warped text (the comment above) under the stages of render_fx_u8:
+    word_classes_, params_row, fx_row and pool as render_fx_u8 takes them, warp_row_ one row of draw_render_warp.  A warp row with
+    flags 0 gives render_fx_u8's image byte for byte, with an fx row of zeros also render_u8's."""
+    cls = [int(c) for c in word_classes_]
+    row = np.asarray(params_row, np.int64)
+    if not 1 <= len(cls) <= MAX_LEN:
+        raise ValueError("render: a word has a length outside 1 .. %d" % MAX_LEN)
+    check_render(np.pad(np.asarray(cls, np.int32), (0, MAX_LEN - len(cls)))[None], [len(cls)], row[None], atlases)
+    fxr = check_render_fx(np.asarray(fx_row, np.int64)[None], pool)[0]
+    wr = check_render_warp(np.asarray(warp_row_, np.int64)[None], row[None])[0]
+    return _render_fx(cls, row, fxr, atlases, pool, alpha=_alpha_plane_warp(cls, row, wr, atlases))

@@ -640,6 +640,21 @@ int dpmn_render_words_fx_u8(const int* classes, const int* lengths, const long l
                             long out_bytes, int B, int n_fonts, int GH, int GW, const int* host_classes, const int* host_lengths,
                             const long long* host_params, const long long* host_fx, const long long* host_meta, const long long* host_photos,
                             dpmn_stream_t stream);
+/* The same crops with the TEXT under a projective map (corner jitter times a rotation) and on a curved baseline (render.hip; main.py
+ * --train_words_warp), byte for byte utils/render.py render_warp_u8; every argument of dpmn_render_words_fx_u8 keeps its meaning.
+ * warp: device int64 (B, 16), the rows of utils/render.py draw_render_warp [flags (bit 0 perspective, 1 rotate, 2 curve), amp (Q16
+ * pixels), room, c0 .. c8 (the inverse projective map in integers, |c| <= 2^30), H, W, 2 spare]; a row whose flags are 0 is not read and
+ * gives the image of dpmn_render_words_fx_u8.  meta: the canvas of a warped sample is its row's H x W (utils/render.py
+ * render_warp_meta).  host_warp: the HOST copy, checked with the others before the launch: flags outside 0 .. 7, and for a row whose
+ * flags are not 0 a spare column that is not 0, a coefficient beyond 2^30, H x W that is not the sample's canvas in meta, den = c6 x +
+ * c7 y + c8 <= 0 at a corner of that canvas, |amp| above 0.4 gh (or not 0 without the curve bit), room that is not ceil(|amp|) is an
+ * error.  Integers only; the kernel clamps what it reads all the same.  One launch. */
+int dpmn_render_words_warp_u8(const int* classes, const int* lengths, const long long* params, const long long* fx, const long long* warp,
+                              const unsigned char* atlas_u8, const int* advance, const int* atlas_h, const long long* meta, const int* tiles,
+                              int n_tiles, const unsigned char* pool_u8, long pool_bytes, const long long* photos, int n_photos,
+                              unsigned char* out_packed, long out_bytes, int B, int n_fonts, int GH, int GW, const int* host_classes,
+                              const int* host_lengths, const long long* host_params, const long long* host_fx, const long long* host_warp,
+                              const long long* host_meta, const long long* host_photos, dpmn_stream_t stream);
 /* A wide text line as overlapping windows of the model's LR size (tile.hip; utils/tile.py holds the plan arithmetic and the numpy
  * restatement).  resize_windows: a RAGGED batch in the packed layout of dpmn_resize_ragged_u8 -> every image resized with PIL's
  * fixed-point bicubic (the arithmetic of dpmn_resize_ragged_u8, byte for byte Image.resize((w_line, lr_h), BICUBIC)) to the height lr_h

@@ -391,21 +391,49 @@ def train_words_fx(args, atlases=None):
     return render.RenderFx(kinds, prob, pool, atlases)
 
 
+TRAIN_WORDS_WARP_NEEDS = ("main.py: --train_words_warp needs --train_words: perspective, rotate and curve distort the rendered words")
+
+
+def train_words_warp(args, atlases=None):
+    """--train_words_warp KINDS [--train_words_warp_prob P] [--train_words_warp_persp F] [--train_words_warp_angle DEG]
+    [--train_words_warp_curve F], checked -> the utils.render.RenderWarp of the run (atlases: those the words are rendered from; None:
+    the values are only checked), or None without the flag.  Every problem is a SystemExit of one line: the flag without --train_words,
+    an unknown kind, a probability outside 0 .. 1, a magnitude outside its range."""
+    kinds = getattr(args, "train_words_warp", None)
+    if not kinds:
+        return None
+    if not getattr(args, "train_words", None):
+        raise SystemExit(TRAIN_WORDS_WARP_NEEDS)
+    from dpmn_amd.utils import render
+    kinds = [k.strip() for k in str(kinds).split(",")]
+    val = lambda name, default: default if getattr(args, name, None) is None else getattr(args, name)
+    setting = (val("train_words_warp_prob", 0.5), val("train_words_warp_persp", 0.15), val("train_words_warp_angle", 10.0),
+               val("train_words_warp_curve", 0.2))
+    try:
+        render.warp_kinds(kinds, *setting)
+    except ValueError as e:
+        raise SystemExit("main.py: %s" % e)
+    return None if atlases is None else render.RenderWarp(kinds, *setting, atlases=atlases)
+
+
 def train_words_source(args, voc_type):
-    """--train_words FILE [--train_words_fonts DIR] [--train_words_epoch N] -> (words, atlases, epoch size, fx), or None without the
-    flag; fx: the RenderFx of --train_words_fx, or None.  Every problem is a SystemExit of one line: the two-sources conflict, a missing
-    file, a file without a usable word, a font directory without a usable font, an epoch size below 1, and those of train_words_fx."""
+    """--train_words FILE [--train_words_fonts DIR] [--train_words_epoch N] -> (words, atlases, epoch size, fx[, warp]), or None without
+    the flag; fx: the RenderFx of --train_words_fx, or None; warp, only with --train_words_warp: its RenderWarp.  Every problem is a
+    SystemExit of one line: the two-sources conflict, a missing file, a file without a usable word, a font directory without a usable
+    font, an epoch size below 1, and those of train_words_fx and train_words_warp."""
     path, fonts = getattr(args, "train_words", None), getattr(args, "train_words_fonts", None)
     if not path:
         if fonts:
             raise SystemExit(TRAIN_WORDS_FONTS_NEEDS)
         train_words_fx(args)
+        train_words_warp(args)
         return None
     if getattr(args, "train_hr_dir", None):
         raise SystemExit(TRAIN_WORDS_OR_HR_DIR)
     from dpmn_amd.utils import render
     epoch = getattr(args, "train_words_epoch", None)
     epoch = render.DEFAULT_EPOCH if epoch is None else int(epoch)
+    train_words_warp(args)
     if epoch < 1:
         raise SystemExit("main.py: --train_words_epoch must be a positive number of samples, got %d" % epoch)
     if not os.path.isfile(path):
@@ -422,7 +450,8 @@ def train_words_source(args, voc_type):
         atlases = render.build_atlases(files)
     except ValueError:
         raise SystemExit("main.py: --train_words_fonts %s holds no font that PIL can open" % fonts)
-    return words, atlases, epoch, train_words_fx(args, atlases)
+    source, warp = (words, atlases, epoch, train_words_fx(args, atlases)), train_words_warp(args, atlases)
+    return source + (warp,) if warp else source
 
 
 def main(config, args):
@@ -433,6 +462,7 @@ def main(config, args):
         raise SystemExit(TRAIN_WORDS_FONTS_NEEDS)
     if not words_on:
         train_words_fx(args)
+    train_words_warp(args)
     if getattr(args, "cutblur", False) and not (getattr(args, "manmade_degrade", False) or getattr(args, "train_hr_dir", None) or words_on):
         raise SystemExit("main.py: --cutblur needs --manmade_degrade (or --train_hr_dir): it mixes columns of the HR image into the "
                          "synthesised LR image")
@@ -867,6 +897,17 @@ if __name__ == '__main__':
                              'drop shadow up to 3 pixels away) and texture (a crop of a photo of --train_words_backgrounds blended into '
                              'the background); each listed kind is on per sample with probability --train_words_fx_prob')
     parser.add_argument('--train_words_fx_prob', type=float, default=0.5, help='with --train_words_fx: the probability of each kind per sample')
+    parser.add_argument('--train_words_warp', type=str, default=None, metavar='KINDS',
+                        help='with --train_words: a comma list of perspective (every corner of the word moves on its own), rotate (the '
+                             'word turns about its centre) and curve (a parabolic baseline; the columns are displaced, the glyphs are not '
+                             'turned); each listed kind is on per sample with probability --train_words_warp_prob')
+    parser.add_argument('--train_words_warp_prob', type=float, default=0.5, help='with --train_words_warp: the probability of each kind per sample')
+    parser.add_argument('--train_words_warp_persp', type=float, default=0.15, metavar='F',
+                        help='with --train_words_warp perspective: a corner moves by up to F of the glyph height in x and in y, 0 < F <= 0.3')
+    parser.add_argument('--train_words_warp_angle', type=float, default=10.0, metavar='DEG',
+                        help='with --train_words_warp rotate: the angle is drawn from +-DEG degrees, 0 < DEG <= 20')
+    parser.add_argument('--train_words_warp_curve', type=float, default=0.2, metavar='F',
+                        help='with --train_words_warp curve: the baseline rises or sags by up to F of the glyph height, 0 < F <= 0.4')
     parser.add_argument('--train_words_backgrounds', type=str, default=None, metavar='DIR',
                         help='with --train_words_fx texture: a folder of photos (whatever PIL opens; reduced to 512 pixels on the long side)')
     args = parser.parse_args()
