@@ -325,6 +325,7 @@ SIGNATURES = {
     "dpmn_detect_stats_i32": (_i, [fp, fp, _l, fp, fp, _i, fp, _i, fp, fp, fp, fp, fp, _l, fp]),
     "dpmn_detect_moments_i64": (_i, [fp, fp, _l, fp, fp, _i, fp, _i, fp, fp, fp, fp, _l, fp]),
     "dpmn_detect_extents_i32": (_i, [fp, fp, _l, fp, fp, _i, fp, _i, fp, fp, fp, fp, fp, _l, fp]),
+    "dpmn_detect_profile_i32": (_i, [fp, fp, _l, fp, fp, _i, fp, _i, fp, fp, fp, fp, fp, _l, fp]),
     "dpmn_detect_cell_otsu_i32": (_i, [fp, _l, fp, fp, _i, _i, _i, fp, _l, fp]),
     "dpmn_detect_label_local_i32": (_i, [fp, _l, fp, fp, _i, fp, _i, fp, _l, _i, _i, _i, fp, fp, fp, fp, fp]),
     "dpmn_region_block": (_i, []),

@@ -20,6 +20,8 @@
 //                     with one root reduces x and x^2 over the wave and its leading lane sends one update per sum.
 //   k_detect_extents  (oriented regions) atomicMax of the projections of the pixel centres along and across the component's direction,
 //                     which the host chose from the moments; in a word with one root its first and last pixel give the extremes.
+//   k_detect_profile  (bowed lines) per component and vertical bin of its box the least and greatest y, the pixel count and the sum of y,
+//                     with 32-bit atomicMax / atomicAdd; in a word with one root one update per bin segment of the word.
 // Termination: a label only ever decreases (atomicMin) and L[i] <= i holds from the start, so find() follows a strictly decreasing
 // chain of non-negative indices and stops (it also stops at any value that is not below its index, whatever the buffer holds); an
 // iteration of unite() that does not return replaces one of its two roots by a strictly smaller one and find() never increases one, so
@@ -603,6 +605,56 @@ k_detect_extents(const unsigned char* __restrict__ smooth, const int* __restrict
   }
 }
 
+// Bowed lines (utils/detect.py, stage b of the curved recipe).  bins: int32 (table_rows, 3) per component [x0, w, n]: its box's first
+// column and width and the number of its bins, n = 0: passed over.  Bin i begins at e_i = x0 + i w / n, the bin of column x is
+// ((x - x0 + 1) n - 1) / w, the greatest i with e_i <= x.  table: int32 (table_rows, DETECT_BINS, 4) [max -y, max y, count, sum y] per
+// component and bin, initialised by the entry point (the extrema to a value below every y and -y, the sums to zero).  A component has
+// at most 64 * 1024 pixels in a bin and y < 1024, so count <= 2^16 and sum y < 2^26: 32-bit atomics suffice.  A row of bins that does
+// not describe its component (x outside [x0, x0 + w), n outside 1 .. DETECT_BINS) adds nothing: no index is taken from data unchecked.
+constexpr int DETECT_BINS = 16;
+
+__global__ void __launch_bounds__(DT_THREADS)
+k_detect_profile(const unsigned char* __restrict__ smooth, const int* __restrict__ labels, long map_px, const long long* __restrict__ items,
+                 int B, const int* __restrict__ tiles, const long long* __restrict__ slices, const int* __restrict__ slots,
+                 const int* __restrict__ bins, int* __restrict__ table, long table_rows) {
+  DetTile t;
+  if (!detect_tile(items, B, tiles, -1, map_px, t)) return;
+  long long first, cap;
+  if (!detect_slice(slices, t.b, table_rows, first, cap)) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int x = t.x0 + lane;
+  for (int k = 0; k < DT_WAVE_ROWS; ++k) {
+    const int y = t.y0 + wave * DT_WAVE_ROWS + k;
+    bool f, one;
+    u64 word;
+    int slot;
+    if (!detect_word(smooth, labels, slots, t, x, y, cap, f, word, one, slot)) continue;
+    if (!f || slot < 0) continue;
+    const int* q = bins + (size_t)(first + slot) * 3;
+    const int cx0 = q[0], cw = q[1], n = q[2];
+    if (n < 1 || n > DETECT_BINS || cw < n || cw > DETECT_MAP_SIDE || x < cx0 || x - cx0 >= cw) continue;
+    const int i = ((x - cx0 + 1) * n - 1) / cw;      // 0 .. n - 1, since 0 <= x - cx0 < cw
+    int* row = table + ((size_t)(first + slot) * DETECT_BINS + i) * 4;
+    if (one) {
+      // one root: the pixels of the word that share this lane's bin lie in the lanes [e_i, e_{i+1}) - t.x0; the first of them sends the
+      // segment's update (every pixel of the word has this y).  A word may span several bins and a bin several words.
+      const int lo = max(cx0 + i * cw / n - t.x0, 0), hi = min(cx0 + (i + 1) * cw / n - t.x0, DT_W);      // lo <= lane < hi
+      const u64 seg = word & ((hi >= 64 ? ~0ull : (1ull << hi) - 1) & ~((1ull << lo) - 1));
+      if (lane != __ffsll((long long)seg) - 1) continue;
+      const int n_px = __popcll(seg);
+      atomicMax(&row[0], -y);
+      atomicMax(&row[1], y);
+      atomicAdd(&row[2], n_px);
+      atomicAdd(&row[3], y * n_px);
+    } else {
+      atomicMax(&row[0], -y);
+      atomicMax(&row[1], y);
+      atomicAdd(&row[2], 1);
+      atomicAdd(&row[3], y);
+    }
+  }
+}
+
 int detect_check(const long long* items_host, int B, long packed_bytes, long map_px) {
   for (int b = 0; b < B; ++b)
     if (!detect_item_ok(items_host + (size_t)b * DETECT_ITEM_WORDS, packed_bytes, map_px)) return 0;
@@ -762,6 +814,28 @@ int dpmn_detect_extents_i32(const unsigned char* smooth, const int* labels, long
   if (n_tiles == 0 || table_rows == 0) return DPMN_OK;
   hipLaunchKernelGGL(k_detect_extents, dim3((unsigned)n_tiles), dim3(DT_THREADS), 0, as_stream(stream), smooth, labels, map_px, items, B, tiles,
                      slices, slots, dirs, table, table_rows);
+  DPMN_CHECK_LAUNCH();
+  return DPMN_OK;
+}
+
+int dpmn_detect_profile_i32(const unsigned char* smooth, const int* labels, long map_px, const long long* items, const long long* items_host,
+                            int B, const int* tiles, int n_tiles, const long long* slices, const long long* slices_host, const int* slots,
+                            const int* bins, int* table, long table_rows, dpmn_stream_t stream) {
+  const int rc = detect_oriented_check(smooth, labels, map_px, items, items_host, B, tiles, n_tiles, slices, slices_host,
+                                       slots, table, table_rows);
+  if (rc != DPMN_OK) return rc;
+  DPMN_REQUIRE(bins || table_rows == 0, "detect_profile: null bins");
+  DPMN_REQUIRE(table_rows <= 0x7fffffffL / DETECT_BINS, "detect_profile: too many rows");
+  if (table_rows > 0) {
+    // per bin 16 bytes: the two extrema every byte 0x80 (below every y and -y, so that atomicMax does it), the two sums zero
+    const size_t n_bins = (size_t)table_rows * DETECT_BINS;
+    if (hipMemsetAsync(table, 0, n_bins * 4 * sizeof(int), as_stream(stream)) != hipSuccess ||
+        hipMemset2DAsync(table, 4 * sizeof(int), 0x80, 2 * sizeof(int), n_bins, as_stream(stream)) != hipSuccess)
+      return dpmn_set_error(DPMN_ERR_LAUNCH, "detect_profile: hipMemsetAsync failed");
+  }
+  if (n_tiles == 0 || table_rows == 0) return DPMN_OK;
+  hipLaunchKernelGGL(k_detect_profile, dim3((unsigned)n_tiles), dim3(DT_THREADS), 0, as_stream(stream), smooth, labels, map_px, items, B, tiles,
+                     slices, slots, bins, table, table_rows);
   DPMN_CHECK_LAUNCH();
   return DPMN_OK;
 }

@@ -13,7 +13,8 @@ quadrilaterals, which TextSR.demo(paste=True) needs to put the SR regions back (
 by strip (ops.poly_crop_u8) into the same packed buffer as the quadrilaterals (ops.crop_regions_u8).
 `detect_box_files` (main.py --demo_detect) writes the box files itself: the regions of every photo are found on the GPU
 (ops.detect_text_u8, utils/detect.py), with oriented=True (main.py --demo_detect_oriented) as rotated quadrilaterals
-(ops.detect_oriented_u8), with local=C (main.py --demo_detect_local) under a threshold of its own per C x C cell of the working map.
+(ops.detect_oriented_u8), with local=C (main.py --demo_detect_local) under a threshold of its own per C x C cell of the working map,
+with curved=True (main.py --demo_detect_curved) with bowed lines as polygons among the upright boxes (ops.detect_curved_u8).
 """
 import os
 
@@ -84,17 +85,22 @@ def folder_window_batches(dir_, batch_size, lr_size, mask, device):
         yield names, plan, ops.collate_u8(windows, mask)
 
 
-def detect_box_files(dir_, box_dir, batch_size, device, gap=12, floor=24, oriented=False, local=0):
+def detect_box_files(dir_, box_dir, batch_size, device, gap=12, floor=24, oriented=False, local=0, curved=False):
     """main.py --demo_detect: the text regions of every photo of `dir_` (host_batches' files, *.txt passed over), found on the GPU
     (ops.detect_text_u8; utils/detect.py holds the recipe and its limits), written as box_dir/<stem>.txt in the format that box_batches
     reads -- an ordinary box file that can be corrected by hand and fed back with --demo_boxes.  Per batch one upload of the packed
     photos.  A photo without a region gets an empty file and one printed line.  oriented (main.py --demo_detect_oriented): the
     regions are rotated quadrilaterals along the text's own direction, in decimals (ops.detect_oriented_u8).  local (main.py
-    --demo_detect_local): the cell side of the locally adaptive threshold, 0 for the one threshold per photo.  -> the number of boxes
-    written."""
+    --demo_detect_local): the cell side of the locally adaptive threshold, 0 for the one threshold per photo.  curved (main.py
+    --demo_detect_curved; not with oriented): bowed lines are written as polygons, which box_batches(polygons=True) reads
+    (ops.detect_curved_u8).  -> the number of boxes written."""
     from .. import ops
-    from ..utils.detect import write_boxes, write_quads
+    from ..utils.detect import write_boxes, write_quads, write_regions
+    if curved and oriented:
+        raise ValueError("detect_box_files: curved does not combine with oriented")
     find, write = (ops.detect_oriented_u8, write_quads) if oriented else (ops.detect_text_u8, write_boxes)
+    if curved:
+        find, write = ops.detect_curved_u8, write_regions
     kw = {"local": int(local)} if local else {}      # (off: the call is the one it was)
     os.makedirs(box_dir, exist_ok=True)
     n = 0

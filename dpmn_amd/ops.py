@@ -1303,6 +1303,76 @@ def detect_oriented_tables_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, 
     return out
 
 
+def _detect_profiles(args, rows, bins, dev):
+    """The upload of the bins, the profile launch and its copy -> int64 (rows, 16, 4) [top, bot, cnt, sy] on the host, as
+    utils.detect.curve_profile gives them (the kernel keeps max -y, max y, count, sum y), zeros where a bin was not used."""
+    import numpy as np
+    d_bins = torch.from_numpy(bins).to(dev)
+    prof = torch.empty(rows, 16, 4, dtype=torch.int32, device=dev)
+    check(lib.dpmn_detect_profile_i32(*args, d_bins.data_ptr(), prof.data_ptr(), rows, stream()))
+    prof = prof.cpu().numpy().astype(np.int64)
+    used = prof[:, :, 2] > 0
+    prof[:, :, 0], prof[:, :, 1] = -prof[:, :, 0], prof[:, :, 1] + 1
+    prof[~used] = 0
+    return prof
+
+
+def _detect_curved_run(packed, offsets, sizes, gap, vgap, floor, what, local=0):
+    """The checks and launches of the curved ops -> (host, pass, per photo (comps (n, 5), candidates (n, 3), profiles (n, 16, 4) or
+    None)) in the order of the photo's table rows: detect_text_u8's launches and copies, then the candidates' bins uploaded
+    (utils.detect.curve_candidates on the component tables that are on the host already), one launch and one copy back.  A batch
+    without a candidate has neither, and no profiles."""
+    import numpy as np
+    from .utils.detect import check_params, curve_candidates
+    try:
+        gap, vgap, floor = check_params(gap, vgap, floor)
+    except ValueError as e:
+        raise _abi.DpmnError("%s: %s" % (what, e)) from e
+    host = _detect_plan(packed, offsets, sizes, what, local)
+    d, d_items, d_tiles, g, hist, thr = _detect_thresholds(packed, host, floor)
+    p = _detect_pass(host, d_items, d_tiles, g, thr, gap, vgap)
+    comps = _detect_comps(p)
+    cands = [curve_candidates(c) for c in comps]
+    if not any((c[:, 2] > 0).any() for c in cands):
+        return host, p, [(c, k, None) for c, k in zip(comps, cands)]
+    args, slices, d_slices, rows = _detect_oriented_args(host, d_items, d_tiles, p)
+    prof = _detect_profiles(args, rows, np.ascontiguousarray(np.concatenate(cands).astype(np.int32)), g.device)
+    return host, p, [(c, k, prof[int(at):int(at) + len(c)]) for c, k, at in zip(comps, cands, slices[:, 0])]
+
+
+def detect_curved_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, names=None, local=0):
+    """The text regions of a ragged batch of photos with BOWED lines as polygons (csrc/detect.hip: k_detect_profile; utils/detect.py
+    holds the recipe and its limits): the arguments of detect_text_u8 -> per photo a list of int64 (m, 2) point arrays (x, y) in
+    hundredths of a photo pixel, m = 4 for an upright box and 2 bins for a polygon, at most utils.detect.MAX_BOXES: region for region
+    utils.detect.detect_curved_np, and for a photo without a curved component the boxes of detect_text_u8.  Beyond detect_text_u8's
+    launches and copies: the bins of the candidate components go up, one launch, and the profile table comes back -- none of the three
+    when the batch holds no candidate.  Integer kernels: the same in every compute mode."""
+    import numpy as np
+    from .utils.detect import regions_from_profiles
+    host, p, tables = _detect_curved_run(packed, offsets, sizes, gap, vgap, floor, "detect_curved_u8", local)
+    out = []
+    for b, (it, (c, k, prof)) in enumerate(zip(host["items"], tables)):
+        if prof is None:
+            prof = np.zeros((len(c), 16, 4), np.int64)
+        out.append(regions_from_profiles(c, k, prof, int(it[1]), int(it[2]), names[b] if names else None))
+    return out
+
+
+def detect_curved_tables_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, local=0):
+    """The tables behind detect_curved_u8, for tests: per photo (candidates int64 (n, 3), profiles int64 (n, 16, 4)) in LABEL order (the
+    labels and slots are copied back to find it): utils.detect.curve_candidates and curve_profile.  profiles is None for every photo
+    of a batch without a candidate: nothing was launched."""
+    import numpy as np
+    host, p, tables = _detect_curved_run(packed, offsets, sizes, gap, vgap, floor, "detect_curved_tables_u8", local)
+    labels, slots = p["labels"].cpu().numpy(), p["slots"].cpu().numpy()
+    out = []
+    for (_, _, _, at, hm, wm, _, _), (c, k, prof) in zip(host["items"].tolist(), tables):
+        roots = np.nonzero(labels[at:at + hm * wm] == np.arange(hm * wm))[0]      # ascending: the label order
+        order = slots[at:at + hm * wm][roots]
+        out.append((k[order], None if prof is None else prof[order]))
+    return out
+
+
 def detect_text_u8(packed, offsets, sizes, gap=12, vgap=2, floor=24, names=None, local=0):
     """The text regions of a ragged batch of photos (csrc/detect.hip; utils/detect.py holds the recipe): packed = the device copy of
     utils.resize.pack_ragged's buffer, offsets / sizes = the columns of its meta, integer (B) byte offsets and (B, 2) (h, w) -> per

@@ -68,6 +68,35 @@ component of a pass, still in integers only:
      than MAX_BOXES: those of largest W2 H2 stay (ties: the earlier) and the same line is printed.
 Text steeper than 45 degrees is read along +u: whether a vertical sign reads upward or downward cannot be told from its shape, and at
 exactly 90 degrees the tie rule gives k = 0, -90 degrees, reading upward.
+
+Bowed lines as polygons (main.py --demo_detect_curved; detect_curved_np, ops.detect_curved_u8): stages 1 to 5 as above (local
+included), then per component of the ordinary row pass smooth(b, gap, vgap), with w = x1 - x0 and h = y1 - y0, in integers only:
+  a. candidates (curve_candidates): h >= MIN_H and w >= CURVE_MIN_W = 16.  A candidate is cut by vertical lines into
+     n = min(CURVE_BINS, w // 8) bins, 2 <= n <= 16, with the edges e_i = x0 + i * w // n.  The bin of column x is
+     ((x - x0 + 1) * n - 1) // w: the greatest i with e_i <= x, because i * w // n <= x - x0 <=> i * w < (x - x0 + 1) * n <=>
+     i <= ((x - x0 + 1) * n - 1) // w.  An 8-connected component has a pixel in every column of its box, so no bin is empty.
+  b. profile (curve_profile): per bin over the component's pixels top_i = min y, bot_i = max y + 1, cnt_i and sy_i = sum y.
+  c. ribbon (curve_ribbons): the stations in doubled x, X2_0 = 2 x0, X2_{n-1} = 2 x1, X2_i = e_i + e_{i+1} between (the bins'
+     centres; the outermost stations are moved to the ends of the box); the doubled centre C_i = (2 sy_i + cnt_i) // cnt_i, the mean
+     of the doubled pixel centres 2y + 1, floored; ONE doubled half-height R = max_i max(2 bot_i - C_i, C_i - 2 top_i) for the whole
+     region, so that the rectification stretches every strip alike; the line height hc = R in map pixels (half of a doubled height).
+  d. curved or straight: a candidate is curved when for an interior station, with D = X2_{n-1} - X2_0,
+     2 |C_i D - (C_0 (X2_{n-1} - X2_i) + C_{n-1} (X2_i - X2_0))| > hc D -- the centre line leaves its chord by more than a quarter of the
+     line height, compared exactly.  Everything else (non-candidates and n = 2 included) is straight.
+  e. filter of a curved component: hc >= MIN_H, 2 hc <= hm, 5 w >= 6 hc and 100 area >= 35 hc w (the fill against the ribbon, whose
+     strips are e_{i+1} - e_i wide and hc high, not against the upright box).  One that fails is dropped, not boxed.
+  f. output (regions_from_profiles): the straight components give the boxes of stages 6 and 7, unchanged.  A curved component gives
+     a polygon of 2n points, clockwise from top-left as utils/poly.py reads them: the top edge (X2_i / 2, (C_i - R) / 2 - p) from left
+     to right, the bottom edge (X2_i / 2, (C_i + R) / 2 + p) from right to left, p = (hc + 5) // 10, times r, in HUNDREDTHS of a photo
+     pixel (exact: 50 r X2_i and 50 r (C_i -+ R) -+ 100 r p), not clamped.  Every strip is a trapezoid with vertical sides of length
+     R + 2p > 0 between strictly increasing stations, hence strictly convex and clockwise: utils.poly.check_polygon accepts it.
+     Boxes and polygons are sorted together by the (top, left, bottom, right) of their bounding boxes (on a tie the box first); more
+     than MAX_BOXES: those of largest bounding-box area stay (ties: the earlier) and the same line is printed.  A photo without a
+     curved component gets byte for byte the box file of the plain recipe.
+Limits: this inverts what --train_words_warp curve does -- columns displaced by a smooth curve -- and nothing more; it is no
+arbitrary-shape detector.  The cuts are vertical, so the glyphs of a steep arc are sheared, not turned: fine up to a slope of about
+0.5, wrong for a half circle.  Only the row pass is used (no vertical or steeply slanted lines).  An S-curve inside one bin is
+invisible.  Two lines that the smoothing merges become one ribbon.  The bin count, the quarter-height rule and the 35 % are untuned.
 """
 import numpy as np
 
@@ -283,9 +312,8 @@ def components(labels):
     return out
 
 
-def boxes_from_components(comps, H, W, name=None):
-    """Stages 6 and 7: the table of components() (in any order) of an H x W photo -> int32 (n, 4) boxes x0, y0, x1, y1 in photo pixels,
-    ends exclusive, sorted by (top, left, bottom, right), at most MAX_BOXES (one printed line when some are dropped; name: the photo)."""
+def _sorted_boxes(comps, H, W):
+    """Stages 6 and 7 before MAX_BOXES: the boxes of the components that pass the filter, int64 (n, 4), padded, clamped and sorted."""
     r, hm, wm = working_size(H, W)
     c = np.asarray(comps, np.int64).reshape(-1, 5)
     x0, y0, x1, y1, area = c.T
@@ -294,7 +322,13 @@ def boxes_from_components(comps, H, W, name=None):
     x0, y0, x1, y1, h = x0[keep], y0[keep], x1[keep], y1[keep], h[keep]
     p = (h + 5) // 10
     b = np.stack([np.clip((x0 - p) * r, 0, W), np.clip((y0 - p) * r, 0, H), np.clip((x1 + p) * r, 0, W), np.clip((y1 + p) * r, 0, H)], axis=1)
-    b = b[np.lexsort((b[:, 2], b[:, 3], b[:, 0], b[:, 1]))]
+    return b[np.lexsort((b[:, 2], b[:, 3], b[:, 0], b[:, 1]))]
+
+
+def boxes_from_components(comps, H, W, name=None):
+    """Stages 6 and 7: the table of components() (in any order) of an H x W photo -> int32 (n, 4) boxes x0, y0, x1, y1 in photo pixels,
+    ends exclusive, sorted by (top, left, bottom, right), at most MAX_BOXES (one printed line when some are dropped; name: the photo)."""
+    b = _sorted_boxes(comps, H, W)
     if len(b) > MAX_BOXES:
         print("detect: %s%d regions found, the %d of largest area kept" % (name + ": " if name else "", len(b), MAX_BOXES))
         big = np.argsort(-(b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1]), kind="stable")[:MAX_BOXES]
@@ -529,3 +563,137 @@ def write_quads(path, quads):
     """The oriented regions of one photo as a box file that utils.quad.numbered_boxes reads (empty for none)."""
     with open(path, "w", encoding="utf-8") as fh:
         fh.write(quad_lines(quads))
+
+
+# ---- bowed lines as polygons: integers only ----
+
+CURVE_MIN_W = 16     # a narrower component is never cut into bins
+CURVE_BINS = 16      # the most bins of a component (csrc/detect.hip DETECT_BINS); a bin is at least 8 columns wide
+
+
+def curve_bin(x, x0, w, n):
+    """The bin of column x of a component [x0, x0 + w) cut into n bins: ((x - x0 + 1) * n - 1) // w, the greatest i with
+    x0 + i * w // n <= x (arrays or ints)."""
+    return ((x - x0 + 1) * n - 1) // w
+
+
+def curve_candidates(comps):
+    """The table of components() -> int64 (n, 3) [x0, w, bins] per component; bins = 0: no candidate (lower than MIN_H or narrower than
+    CURVE_MIN_W), else min(CURVE_BINS, w // 8).  The table that the profile launch reads."""
+    c = np.asarray(comps, np.int64).reshape(-1, 5)
+    w, h = c[:, 2] - c[:, 0], c[:, 3] - c[:, 1]
+    ok = (h >= MIN_H) & (w >= CURVE_MIN_W)
+    out = np.zeros((len(c), 3), np.int64)
+    out[ok] = np.stack([c[ok, 0], w[ok], np.minimum(CURVE_BINS, w[ok] // 8)], axis=1)
+    return out
+
+
+def curve_profile(labels, candidates):
+    """The labels of label() and the rows of curve_candidates() (in label order) -> int64 (n, CURVE_BINS, 4) [top, bot, cnt, sy] per
+    component and bin over the component's pixels: the least y, the greatest y + 1, their number and the sum of y.  Zeros for a
+    component that is no candidate and for the bins past its last."""
+    labels = np.asarray(labels)
+    cand = np.asarray(candidates, np.int64).reshape(-1, 3)
+    out = np.zeros((len(cand), CURVE_BINS, 4), np.int64)
+    ys, xs = np.nonzero(labels >= 0)
+    if len(ys) == 0:
+        return out
+    _, inv = np.unique(labels[ys, xs], return_inverse=True)
+    if int(inv.max()) + 1 != len(cand):
+        raise ValueError("curve_profile: %d components, %d candidate rows" % (int(inv.max()) + 1, len(cand)))
+    on = cand[inv, 2] > 0
+    ys, xs, inv = ys[on].astype(np.int64), xs[on].astype(np.int64), inv[on]
+    if len(ys) == 0:
+        return out
+    x0, w, n = cand[inv].T
+    b = curve_bin(xs, x0, w, n)
+    assert (b >= 0).all() and (b < n).all()
+    out[:, :, 0] = labels.shape[0]
+    np.minimum.at(out[:, :, 0], (inv, b), ys)
+    np.maximum.at(out[:, :, 1], (inv, b), ys + 1)
+    np.add.at(out[:, :, 2], (inv, b), 1)
+    np.add.at(out[:, :, 3], (inv, b), ys)
+    used = np.arange(CURVE_BINS)[None, :] < cand[:, 2:3]
+    assert (out[:, :, 2][used] > 0).all()      # (a pixel in every column of the box: no bin of a candidate is empty)
+    out[~used] = 0
+    return out
+
+
+def curve_ribbons(comps, candidates, profiles, H, W):
+    """Stages c to e: the tables of components(), curve_candidates() and curve_profile() of an H x W photo (rows in any common order)
+    -> (straight bool (n): the components that go the way of the plain recipe, ribbons: per curved component that passes the
+    filter (row, X2 (bins), C (bins), R, p), Python ints, in row order).  A curved component that fails the filter is in neither."""
+    r, hm, wm = working_size(H, W)
+    comps = np.asarray(comps, np.int64).reshape(-1, 5)
+    cand = np.asarray(candidates, np.int64).reshape(-1, 3)
+    prof = np.asarray(profiles, np.int64).reshape(-1, CURVE_BINS, 4)
+    straight, ribbons = np.ones(len(comps), bool), []
+    for j in np.nonzero(cand[:, 2] > 2)[0].tolist():      # (two bins have no interior station: straight)
+        x0, w, n = cand[j].tolist()
+        top, bot, cnt, sy = (prof[j, :n, k].tolist() for k in range(4))
+        assert min(cnt) > 0
+        e = [x0 + i * w // n for i in range(n + 1)]
+        X2 = [2 * x0] + [e[i] + e[i + 1] for i in range(1, n - 1)] + [2 * (x0 + w)]
+        C = [(2 * sy[i] + cnt[i]) // cnt[i] for i in range(n)]
+        R = max(max(2 * bot[i] - C[i], C[i] - 2 * top[i]) for i in range(n))
+        hc, D = R, X2[-1] - X2[0]
+        if not any(2 * abs(C[i] * D - (C[0] * (X2[-1] - X2[i]) + C[-1] * (X2[i] - X2[0]))) > hc * D for i in range(1, n - 1)):
+            continue
+        straight[j] = False
+        if hc >= MIN_H and 2 * hc <= hm and 5 * w >= 6 * hc and 100 * int(comps[j, 4]) >= 35 * sum(hc * (e[i + 1] - e[i]) for i in range(n)):
+            ribbons.append((j, X2, C, R, (hc + 5) // 10))
+    return straight, ribbons
+
+
+def ribbon_points(X2, C, R, p, r):
+    """Stage f: one ribbon -> its polygon, int64 (2 bins, 2) points (x, y) in hundredths of a photo pixel, clockwise from top-left."""
+    top = [(50 * r * x, 50 * r * (c - R) - 100 * r * p) for x, c in zip(X2, C)]
+    bottom = [(50 * r * x, 50 * r * (c + R) + 100 * r * p) for x, c in zip(X2, C)]
+    return np.array(top + bottom[::-1], np.int64)
+
+
+def regions_from_profiles(comps, candidates, profiles, H, W, name=None):
+    """Stage f: the tables of one photo (rows in any common order) -> its regions, a list of int64 (m, 2) arrays of points (x, y) in
+    hundredths of a photo pixel: m = 4 for a box (x0, y0), (x1, y0), (x1, y1), (x0, y1), m = 2 bins for a polygon; sorted by the
+    bounding boxes' (top, left, bottom, right), at most MAX_BOXES (one printed line when some are dropped; name: the photo)."""
+    comps = np.asarray(comps, np.int64).reshape(-1, 5)
+    straight, ribbons = curve_ribbons(comps, candidates, profiles, H, W)
+    r = working_size(H, W)[0]
+    regions = [100 * np.array([(x0, y0), (x1, y0), (x1, y1), (x0, y1)], np.int64) for x0, y0, x1, y1 in _sorted_boxes(comps[straight], H, W).tolist()]
+    if ribbons:
+        regions += [ribbon_points(X2, C, R, p, r) for _, X2, C, R, p in ribbons]
+        bounds = lambda q: (int(q[:, 1].min()), int(q[:, 0].min()), int(q[:, 1].max()), int(q[:, 0].max()))
+        regions.sort(key=bounds)      # (stable: on a tie the box stays in front of the polygon)
+    if len(regions) > MAX_BOXES:
+        print("detect: %s%d regions found, the %d of largest area kept" % (name + ": " if name else "", len(regions), MAX_BOXES))
+        area = [int((q[:, 0].max() - q[:, 0].min()) * (q[:, 1].max() - q[:, 1].min())) for q in regions]
+        big = sorted(sorted(range(len(regions)), key=lambda i: -area[i])[:MAX_BOXES])      # (sorted() is stable: ties keep the earlier)
+        regions = [regions[i] for i in big]
+    return regions
+
+
+def detect_curved_np(photo, gap=GAP, vgap=VGAP, floor=FLOOR, name=None, local=0):
+    """One photo -> its regions, boxes and polygons in one list (regions_from_profiles).  The CPU reference of ops.detect_curved_u8."""
+    labels = detect_maps_np(photo, gap, vgap, floor, local)[3]
+    comps = components(labels)
+    cand = curve_candidates(comps)
+    return regions_from_profiles(comps, cand, curve_profile(labels, cand), photo.shape[0], photo.shape[1], name)
+
+
+def region_lines(regions):
+    """The regions of regions_from_profiles -> the text of a box file.  A box is the line of box_lines, x0,y0,x1,y0,x1,y1,x0,y1 in whole
+    pixels; a polygon is one line of its 2 bins points in decimals, which utils.poly.numbered_polygons reads."""
+    out = []
+    for q in regions:
+        q = np.asarray(q, np.int64).reshape(-1, 2)
+        if len(q) == 4:
+            out.append(",".join("%d" % (v // 100) for v in q.reshape(-1).tolist()) + "\n")
+        else:
+            out.append(",".join(_hundredths(v) for v in q.reshape(-1).tolist()) + "\n")
+    return "".join(out)
+
+
+def write_regions(path, regions):
+    """The regions of one photo as a box file that utils.poly.numbered_polygons reads (main.py --demo_polygons; empty for none)."""
+    with open(path, "w", encoding="utf-8") as fh:
+        fh.write(region_lines(regions))

@@ -769,6 +769,12 @@ int dpmn_poly_crop_u8(const unsigned char* packed, long packed_bytes, const long
  * dpmn_detect_extents_i32: dirs, device int32 (table_rows, 2): per component the (c, s) of its direction, (0, 0): passed over.  table,
  * int32 (table_rows, 4) (every byte set to 0x80 here, which is what a row that is passed over keeps): per component [max -U2, max U2,
  * max -V2, max V2] over its pixels, U2 = c (2x + 1) + s (2y + 1), V2 = -s (2x + 1) + c (2y + 1); |c|, |s| <= 16384.  One launch.
+ * Bowed lines (utils/detect.py, stage b of the curved recipe), on the same maps, items, tiles and slices as the two above.
+ * dpmn_detect_profile_i32: bins, device int32 (table_rows, 3): per component [x0, w, n], the first column and the width of its box and
+ * the number n of 1 .. 16 vertical bins it is cut into, bin i from x0 + i w / n; n = 0: passed over.  table, int32 (table_rows, 16, 4)
+ * (initialised here: the first two words of a bin every byte 0x80, the other two zero, which is what a bin that is not used keeps): per
+ * component and bin [max -y, max y, count, sum y] over its pixels.  A row of bins that does not hold its component adds nothing.  One
+ * launch.
  * The locally adaptive threshold (utils/detect.py, local = cell): per axis of a working map ceil(size / cell) balanced cells with the
  * edges i * size / n, cell 32 .. 1024.  Word 7 of a photo's item is then the offset of its ny * nx cell thresholds in table, device
  * int32 (n_cells), row-major per photo: the running sum of the cell counts of the photos before it, ending at n_cells -- both entry
@@ -799,6 +805,10 @@ int dpmn_detect_moments_i64(const unsigned char* smooth, const int* labels, long
 int dpmn_detect_extents_i32(const unsigned char* smooth, const int* labels, long map_px, const long long* items,
                             const long long* items_host /* HOST array */, int B, const int* tiles, int n_tiles, const long long* slices,
                             const long long* slices_host /* HOST array */, const int* slots, const int* dirs, int* table, long table_rows,
+                            dpmn_stream_t stream);
+int dpmn_detect_profile_i32(const unsigned char* smooth, const int* labels, long map_px, const long long* items,
+                            const long long* items_host /* HOST array */, int B, const int* tiles, int n_tiles, const long long* slices,
+                            const long long* slices_host /* HOST array */, const int* slots, const int* bins, int* table, long table_rows,
                             dpmn_stream_t stream);
 /* The overlap of detected and ground-truth regions in samples (detect_eval.hip; utils/detect_eval.py is the definition and the NumPy
  * restatement; main.py --demo_eval): 4 x 4 samples per pixel, even-odd rule, integers only, independent of the compute mode.

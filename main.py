@@ -19,7 +19,9 @@ the photo, strip by strip, in box-file order with the quadrilaterals); with `--d
 written by the run itself: the text regions of every photo are found on the GPU by a classical, integer recipe (utils/detect.py) into
 `<demo_out>/boxes`, and the run goes on as with `--demo_boxes <demo_out>/boxes` (`--demo_detect_oriented` on top: the regions are
 rotated quadrilaterals along the text's own direction, so slanted and vertical text is found too; `--demo_detect_local [C]` on top: a
-threshold of its own per C x C cell of the working map, so a faint word is not lost to a strong edge elsewhere).  `--train_state PATH` makes a training run continuable: the same command line starts the
+threshold of its own per C x C cell of the working map, so a faint word is not lost to a strong edge elsewhere; `--demo_detect_curved`
+on top, in place of `--demo_detect_oriented`: a bowed line is written as a polygon cut by vertical lines along its centre line and
+the run reads its box files as `--demo_polygons` does).  `--train_state PATH` makes a training run continuable: the same command line starts the
 run or, when PATH exists, continues it bit for bit.  `--ema DECAY` keeps an exponential moving average of the trained weights; the
 validation passes score it and the best-model checkpoints hold it.  `--manmade_degrade` synthesises the LR training images from the HR images on the GPU
 (`--cutblur`: with the reference's cutblur on top; `--jpeg_degrade LO,HI`: with JPEG artefacts of a random quality on the resized LR image; `--psf_blur KINDS`: with a random motion, defocus or elongated-Gaussian blur of the HR pixels first); `--train_hr_dir DIR` trains from a folder of HR images alone (no LMDB); `--train_words FILE` trains from a word list alone: the HR images are rendered on the GPU (`--train_words_fonts DIR`: in the fonts of a directory; `--train_words_epoch N`: samples per epoch).  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...` (one process
@@ -118,6 +120,24 @@ def demo_detect_setting(args):
 DEMO_DETECT_LOCAL_NEEDS = ("main.py: --demo_detect_local needs --demo_detect: it gives the detector of --demo_detect a threshold of its own per "
                            "cell of the working map")
 DEMO_DETECT_LOCAL_RANGE = "main.py: --demo_detect_local must be 32 .. 1024 (the side of a cell in pixels of the working map; 1024: one cell)"
+
+
+DEMO_DETECT_CURVED_NEEDS = ("main.py: --demo_detect_curved needs --demo_detect: it writes the bowed lines among the regions that --demo_detect "
+                            "finds as polygons")
+DEMO_DETECT_CURVED_OR_ORIENTED = ("main.py: --demo_detect_curved does not combine with --demo_detect_oriented: the polygons are cut by vertical "
+                                  "lines from the components of the row pass alone")
+
+
+def demo_detect_curved_setting(args):
+    """--demo_detect_curved, checked -> False without the flag, else True: the run then reads its own box files as --demo_polygons
+    does.  ValueError (the message without its 'main.py: ') for the flag without --demo_detect or with --demo_detect_oriented."""
+    if not getattr(args, "demo_detect_curved", False):
+        return False
+    if not getattr(args, "demo_detect", False):
+        raise ValueError(DEMO_DETECT_CURVED_NEEDS[len("main.py: "):])
+    if getattr(args, "demo_detect_oriented", False):
+        raise ValueError(DEMO_DETECT_CURVED_OR_ORIENTED[len("main.py: "):])
+    return True
 
 
 def demo_detect_local_setting(args):
@@ -485,6 +505,7 @@ def main(config, args):
     if getattr(args, "demo_tile", False) and not getattr(args, "demo_dir", None):
         raise SystemExit("main.py: --demo_tile needs --demo_dir: it super-resolves the wide images of that folder in overlapping windows")
     try:
+        detect_curved = demo_detect_curved_setting(args)
         detect = demo_detect_setting(args)
         detect_local = demo_detect_local_setting(args)
     except ValueError as e:
@@ -495,7 +516,9 @@ def main(config, args):
         raise SystemExit(DEMO_PASTE_NEEDS_BOXES)
     if getattr(args, "demo_polygons", False) and not getattr(args, "demo_boxes", None):
         raise SystemExit(DEMO_POLYGONS_NEEDS_BOXES)
-    if getattr(args, "demo_paste_polygons", False) and not (getattr(args, "demo_paste", False) and getattr(args, "demo_polygons", False)):
+    # (--demo_detect_curved writes polygons into its box files: the run reads them as --demo_polygons does)
+    polygons = bool(getattr(args, "demo_polygons", False)) or detect_curved
+    if getattr(args, "demo_paste_polygons", False) and not (getattr(args, "demo_paste", False) and polygons):
         raise SystemExit(DEMO_PASTE_POLYGONS_NEEDS)
     try:
         feather = paste_feather(args)
@@ -583,7 +606,8 @@ def main(config, args):
             box_dir = os.path.join(out_dir, "boxes")
             print("%d regions detected, box files in %s"
                   % (detect_box_files(args.demo_dir, box_dir, bs, mission.device, *detect,
-                                      oriented=getattr(args, "demo_detect_oriented", False), local=detect_local), box_dir))
+                                      oriented=getattr(args, "demo_detect_oriented", False), local=detect_local,
+                                      **({"curved": True} if detect_curved else {})), box_dir))
         if box_dir:
             # whole photos and one box file per photo: every quadrilateral is rectified on the GPU (utils/quad.py), then goes the way
             # of a crop of the folder -- one <stem>_<k>_sr.png per region
@@ -591,7 +615,7 @@ def main(config, args):
                 raise SystemExit("main.py: --demo_boxes %s is not a directory" % box_dir)
             tile = bool(getattr(args, "demo_tile", False))
             make = box_window_batches if tile else box_region_batches
-            if getattr(args, "demo_polygons", False):
+            if polygons:
                 # a line of more than 4 points is a curved word, straightened strip by strip (utils/poly.py)
                 make = functools.partial(make, polygons=True)
             # (--demo_upright / --demo_min_conf write boxes_read/<stem>.txt from the corner lists, which come with photos=True)
@@ -817,6 +841,12 @@ if __name__ == '__main__':
                              'of short horizontal lines keeps its lines and also gets one steep region around the block, to be '
                              'deleted by hand.  Text steeper than 45 degrees is read along its longer side; whether a vertical sign reads upward '
                              'or downward cannot be told from its shape (exactly vertical text is read upward)')
+    parser.add_argument('--demo_detect_curved', action='store_true', default=False,
+                        help='with --demo_detect (not with --demo_detect_oriented): a bowed line -- on a bottle, an arch, a round sign -- is '
+                             'written as a polygon of up to 16 points a side, cut by vertical lines along its centre line, and the run '
+                             'reads its box files as --demo_polygons does (--demo_paste_polygons pastes them back); straight text keeps '
+                             'its upright boxes.  Vertical cuts shear the glyphs of a steep arc: fine up to a slope of about 0.5, wrong '
+                             'for a half circle; the constants are untuned (utils/detect.py)')
     parser.add_argument('--demo_detect_local', type=int, nargs='?', const=128, default=None, metavar='C',
                         help='with --demo_detect: a locally adaptive threshold -- Otsu\'s threshold per C x C cell of the working map '
                              '(32 .. 1024, 128 when C is left out), interpolated between the cell centres, instead of one threshold per '
@@ -916,6 +946,7 @@ if __name__ == '__main__':
     if args.train_words_fonts and not args.train_words:
         parser.error(TRAIN_WORDS_FONTS_NEEDS[len("main.py: "):])
     try:
+        curved = demo_detect_curved_setting(args)
         demo_detect_setting(args)
         demo_detect_local_setting(args)
     except ValueError as e:
@@ -926,7 +957,7 @@ if __name__ == '__main__':
         parser.error(DEMO_PASTE_NEEDS_BOXES[len("main.py: "):])
     if args.demo_polygons and not args.demo_boxes:
         parser.error(DEMO_POLYGONS_NEEDS_BOXES[len("main.py: "):])
-    if args.demo_paste_polygons and not (args.demo_paste and args.demo_polygons):
+    if args.demo_paste_polygons and not (args.demo_paste and (args.demo_polygons or curved)):
         parser.error(DEMO_PASTE_POLYGONS_NEEDS[len("main.py: "):])
     try:
         paste_feather(args)
